@@ -11,24 +11,32 @@ written.  Workload = BASELINE config C3: 4096 envs/GPU x (1 ego + 16 IDM traffic
 maps (seeds 1000..1099, env e -> scenario e mod 100), actions uniform(-1,1) from numpy default_rng(0), pre-generated
 on the device, auto-reset on done.  Weak scaling: each rank owns 4096 envs.
 
-Steady state.  The first ~1000 steps after a reset are cheaper than the rest (the trigger traffic is still parked), so a
-short run would report an early-episode number.  The bench therefore ALWAYS pre-rolls and times at least the floors, whatever
---warmup / --steps say: at N = 1 BASELINE.md section 4 to the letter -- 10 k warm-up steps, then three windows of 100 k timed steps,
-the median is the value (5.5 s of stepping) --, at N > 1 1500 + 3 x 4096 per pass (every transport gets its own windows); the JSON
-line carries the requested counts ("steps", "warmup") and the counts actually run ("steps_timed", "warmup_run"); `ms_per_step` and
-`value` refer to the timed steps of the median window.  --exact turns the floors off.
+Plain run and --full.  A plain run sets up, pre-rolls, times exactly --steps steps, writes the outputs (--dump-outputs) and
+prints the line.  Everything else the bench measures is behind --full: the CPU baseline, the loaded rows, the roofline (HIP
+events over the timed launches + the committed counter passes) and the work statistics read back after the timed region.
 
-Rows.  At N = 1 the same invocation also times the LOADED workloads next to the metric's (whose uniform(-1,1) stream leaves the
-ego crawling and most traffic parked): the scripted lane-keeping ego, respawn-mode traffic (every IDM vehicle drives), BASELINE
-config 5 (multi-agent roundabout, 8 agents, 240 and 72 beams; 40 agents = the reference's default), and 32768 envs on the one GPU
-(config 4's per-node size) -- printed as `rows: [...]`, each with its own roofline (shorter windows: 1500 + 2048 steps;
---no-rows skips them).  `roofline.frac` is charged for the bytes that MOVE: the HBM bytes the rocprofv3 counters saw for that
+Steady state.  The first ~1000 steps after a reset are cheaper than the rest (the trigger traffic is still parked), so a
+short pre-roll would report an early-episode number.  The bench therefore ALWAYS pre-rolls at least the floor, whatever
+--warmup says: at N = 1 BASELINE.md section 4's 10 k warm-up steps, at N > 1 1500 steps; --exact turns the floor off.  The timed
+steps are exactly --steps.  The JSON line carries the requested counts ("steps", "warmup") and the counts actually run
+("steps_timed", "warmup_run").
+
+Rows (--full).  At N = 1 the same invocation also times the LOADED workloads next to the metric's (whose uniform(-1,1) stream
+leaves the ego crawling and most traffic parked): the scripted lane-keeping ego, respawn-mode traffic (every IDM vehicle drives),
+BASELINE config 5 (multi-agent roundabout, 8 agents, 240 and 72 beams; 40 agents = the reference's default), and 32768 envs on
+the one GPU (config 4's per-node size) -- printed as `rows: [...]`, each with its own roofline (shorter windows: 1500 + 3 x 1024
+steps; --no-rows skips them).  `roofline.frac` is charged for the bytes that MOVE: the HBM bytes the rocprofv3 counters saw for that
 row (profiles/r*_pmc_*.json, matched by workload) or, without a counter file, the record bytes of the vehicles that drove
 (`frac_active`); the nominal formula that charges all V records read + written stays next to it as `frac_nominal`.
 
-Windows.  BASELINE.md section 4 asks for the median of three timed runs: the timed region is --windows (3) consecutive windows of
-the timed step count each, every one bracketed by barrier + synchronize; `value` / `ms_per_step` are the MEDIAN window's,
-`windows` lists all of them and `window_spread` = (max - min) / median.
+Windows.  BASELINE.md section 4 asks for the median of three timed runs: the --steps timed steps are split into --windows (3)
+consecutive windows of (nearly) equal length, every one bracketed by barrier + synchronize; `value` / `ms_per_step` are the
+MEDIAN window's (by time per step), `windows` lists all of them and `window_spread` = (max - min) / median.
+
+Outputs.  --dump-outputs DIR writes what the timed path computed in its last timed step, as a caller of that path receives it
+(observation or top-down image, reward, done, flags; N > 1: the gathered rows of the headline transport on rank 0), as
+DIR/<name>.npy in float32 / float64, at most 64 MB in all (a fixed, seeded sample of the envs beyond that).  The inputs are
+seeded: the same arguments give the same outputs on every run of the same build.
 
 N > 1.  Environments are independent: the step itself has no exchange.  The north star adds ONE gather of
 (obs, reward, done) per step over xGMI.  One invocation measures, back to back on the same engine state: the step without any
@@ -55,10 +63,9 @@ sys.path.insert(0, ROOT)
 HOST_THREADS = len(os.sched_getaffinity(0))  # read before any OpenMP runtime binds the main thread to one core (OMP_PROC_BIND)
 
 PROF_STRIDE = 64      # k_step launches per HIP-event group (an event pair costs a launch gap: 16 per group took 0.4 us off every step)
-PREROLL_MIN = 1500    # steps before the timed region (steady-state traffic): N > 1 (every transport gets its own windows)
-TIMED_MIN = 4096      # timed steps per window (>= 64 event groups of PROF_STRIDE launches): N > 1
-PREROLL_HEAD = 10000  # N = 1, the metric's row: BASELINE.md section 4 to the letter -- "10 k warm-up, 100 k timed steps, median of 3"
-TIMED_HEAD = 100000   #   (three windows of 100 k steps: 5.3 s)
+PREROLL_MIN = 1500    # steps before the timed region (steady-state traffic): N > 1
+PREROLL_HEAD = 10000  # N = 1, the metric's row: BASELINE.md section 4's "10 k warm-up"
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this many bytes of .npy data in all
 
 
 # Algorithmic HBM bytes per env-step for this build's record layout:
@@ -71,6 +78,37 @@ def algorithmic_bytes(A, T, D):
     k_obs = V * (5 * 4 + 8) + 4 * A * D + A * 12 * 4
     fused = k_step + 4 * A * D  # observation fused into k_step: no re-read of the vehicle records, obs row written once
     return k_step, k_obs, fused
+
+
+def window_lengths(steps, n_win):
+    """The --steps timed steps as n_win consecutive windows of (nearly) equal length: the first steps % n_win windows get one
+    step more; never an empty window."""
+    n_win = max(1, min(n_win, steps))
+    return [steps // n_win + (1 if w < steps % n_win else 0) for w in range(n_win)]
+
+
+def dump_outputs(dirname, arrays, n_rows, limit=DUMP_BYTES):
+    """DIR/<name>.npy for every numpy array of `arrays` (name -> array): floats of up to 32 bits and integers of up to 16 bits as
+    float32, everything else as float64 -- exact either way.  When that comes to more than `limit` bytes, every array whose first
+    axis has n_rows entries (the envs) keeps the same fixed, seeded sample of its rows, and sample_rows.npy lists them."""
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        small = a.dtype.itemsize <= (4 if a.dtype.kind == "f" else 2) and a.dtype.kind in "fbiu"
+        conv[name] = a.astype(np.float32 if small else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > limit:
+        big = sum(a.nbytes for a in conv.values() if a.shape and a.shape[0] == n_rows)
+        keep = int(n_rows * (limit - (total - big) - 8 * n_rows) / big) if big else 0
+        if keep < 1:
+            raise RuntimeError("--dump-outputs: %d bytes of outputs do not fit in %d bytes" % (total, limit))
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, keep, replace=False))
+        conv = {k: (a[rows] if a.shape and a.shape[0] == n_rows else a) for k, a in conv.items()}
+        conv["sample_rows"] = rows.astype(np.float64)
+    for name, a in conv.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(conv)
 
 
 PROFILES_DIR = os.path.join(ROOT, "profiles")
@@ -362,10 +400,15 @@ def cpu_baseline(descs, args, seconds=6.0):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=2000, help="timed steps (split into --windows windows)")
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--exact", action="store_true",
-                    help="run exactly --warmup / --steps (no steady-state floors): for plumbing tests and quick A/B runs")
+                    help="pre-roll exactly --warmup steps (no steady-state floor): for plumbing tests and quick A/B runs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the loaded rows (N = 1), the roofline from HIP events and the committed "
+                         "counter passes, and the work statistics of the timed workload; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--envs", type=int, default=4096, help="environments per GPU")
     ap.add_argument("--traffic", type=int, default=16)
     ap.add_argument("--maps", type=int, default=100,
@@ -373,11 +416,11 @@ def parse_args(argv=None):
     ap.add_argument("--lasers", type=int, default=None,
                     help="lidar beams: default 240 for c3; for c5 72 x 40 m (the reference's multi-agent default) unless given "
                          "(BASELINE.md C5 is --lasers 240)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-rows", action="store_true",
-                    help="N = 1: only the metric's workload, without the loaded rows (expert / respawn / C5 / 32768 envs)")
+                    help="--full at N = 1: only the metric's workload, without the loaded rows (expert / respawn / C5 / 32768 envs)")
     ap.add_argument("--rows", default=None,
-                    help="comma-separated subset of the rows to run (names as printed in `rows`), default all")
+                    help="--full: comma-separated subset of the rows to run (names as printed in `rows`), default all")
     ap.add_argument("--mode", default="both", choices=["both", "gather", "replicas"],
                     help="N>1: time the step with the per-step gather (value), without it (value_replicas), or both")
     ap.add_argument("--gather", action="store_true", help="(old flag) same as --mode gather")
@@ -432,6 +475,10 @@ def parse_args(argv=None):
     ap.add_argument("--corrupt-gather", action="store_true",
                     help="tests only: flip one value of the received rows before the gather's self-check (gather_ok must read false)")
     args = ap.parse_args(argv)
+    if args.rows and not args.full:
+        ap.error("--rows selects rows of a --full run")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gather:
         args.mode = "gather"
     if args.no_gather:
@@ -442,8 +489,8 @@ def parse_args(argv=None):
     return args
 
 
-# The rows timed next to the metric's workload at N = 1 (name, overrides of the command line).  Pre-roll 1500 steps (C5: 1000, the
-# roundabout fills up over the first thousand steps), then --windows (3) windows of `steps` (default 1024) each, median reported.
+# The rows timed next to the metric's workload at N = 1 with --full (name, overrides of the command line).  Pre-roll 1500 steps (C5:
+# 1000, the roundabout fills up over the first thousand steps), then --windows (3) windows of `steps` (default 1024) each, median reported.
 ROWS = [
     ("c3_straight", dict(actions="straight")),                       # "a second run with constant [0, 1]"
     ("c2_1024", dict(envs=1024, traffic=0, lasers=0, steps=4096)),   # BASELINE config 2: dynamics + localisation + reward only
@@ -542,8 +589,9 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
     actions = torch.from_numpy(acts).to(dev)
 
     warm = args.warmup if args.exact else max(args.warmup, PREROLL_HEAD if world == 1 else PREROLL_MIN)
-    timed = args.steps if args.exact else max(args.steps, TIMED_HEAD if world == 1 else TIMED_MIN)
-    n_win = args.windows
+    timed = args.steps  # the timed steps in all, over every window
+    win_steps = window_lengths(timed, args.windows)
+    n_win = len(win_steps)
     want_replicas = world == 1 or args.mode in ("both", "replicas")
     want_gather = world > 1 and args.mode in ("both", "gather")
     # N > 1: the replicas pass first (no collective inside its timed loop), then the passes with the per-step gather, one per
@@ -581,7 +629,7 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
             return
         if args.step_n > 1:  # one call per K steps; the other K - 1 "steps" of the loop are part of that call
             if k % args.step_n == 0:
-                eng.step_n(actions, k % CYC, args.step_n)
+                state["step_n_out"] = eng.step_n(actions, k % CYC, args.step_n)
             return
         eng.step(actions[k % CYC], want_obs=not args.topdown)
         if args.topdown:
@@ -606,24 +654,36 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
         return [float(v) for v in t.tolist()]
 
     def timed_windows(enqueue_window):
-        """n_win windows of `timed` steps, each bracketed by barrier + synchronize; `enqueue_window()` enqueues one window's steps
-        and returns once they are enqueued (and, for the gather, drained).  Returns the per-window times (max over ranks) and
-        the host's enqueue time per step of the median window."""
+        """One window per entry of win_steps, each bracketed by barrier + synchronize; `enqueue_window(n)` enqueues the window's n
+        steps and returns once they are enqueued (and, for the gather, drained).  Returns the seconds per step of every window (max
+        over ranks), the index of the median window and the host's enqueue time per step of that window."""
         wins, enq = [], []
-        for w in range(n_win):
+        for n in win_steps:
             fence()
             t0 = time.perf_counter()
-            enqueue_window()
+            enqueue_window(n)
             t_enq = time.perf_counter()  # every launch of the window has been enqueued: the host's share of the loop
             fence()
             t1 = time.perf_counter()
-            wins.append(t1 - t0)
-            enq.append(t_enq - t0)
+            wins.append((t1 - t0) / n)
+            enq.append((t_enq - t0) / n)
         wins = max_over_ranks(wins)
         med = int(np.argsort(wins)[len(wins) // 2])
         return wins, med, enq[med]
 
-    results = {}        # "replicas" -> dict(elapsed, windows, prof, host_enqueue_s)
+    def replica_outputs():
+        """--dump-outputs: what the last timed step returned to its caller, copied to the host (after a fence)."""
+        if args.step_n > 1:
+            outs = dict(zip(("obs", "reward", "done", "flags"), state["step_n_out"]))
+        else:
+            outs = dict(reward=eng.reward, done=eng.done, flags=eng.flags)
+            outs["topdown" if args.topdown else "obs"] = eng.img if args.topdown else eng.obs
+        for j, ej in enumerate(extra):
+            outs.update({"%s_engine%d" % (k, j + 1): v for k, v in (("obs", ej.obs), ("reward", ej.reward), ("done", ej.done),
+                                                                     ("flags", ej.flags))})
+        return {k: v.cpu().numpy() for k, v in outs.items()}
+
+    results = {}        # "replicas" -> dict(sps, windows, prof, host_enqueue_sps): seconds per step of the median window
     by_transport = {}   # "root", "root+graph", ... -> dict (value filled in by make_line)
     state = dict(counter=0, work=None, aborted=None)
     watchdog = WATCHDOG if world > 1 else None
@@ -631,7 +691,7 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
     def make_line(by_t, work, aborted):
         """The JSON line from what has been measured so far (rank 0; also called by the watchdog with work = None)."""
         per_step_units = float(N) * world * max(1, args.engines)
-        rate = lambda el: per_step_units * timed / el  # noqa: E731
+        rate = lambda sps: per_step_units / sps  # noqa: E731  (env-steps/s from seconds per step)
         k_us = ((results.get("replicas") or {}).get("prof") or {}).get("k_step_ms", 0.0) * 1e3 or None
         slice_bytes = N * pdist.pack_width(D, A) * 4
         link_us = slice_bytes / (XGMI_LINK_GBPS * 1e9) * 1e6
@@ -639,11 +699,11 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
         table = {}
         for name, r in by_t.items():
             e = dict(transport=r["transport"], hip_graph=r["hip_graph"], describe=r.get("describe"), gather_mem=r.get("gather_mem"))
-            if "elapsed" in r:
-                host_us = r["host_enqueue_s"] / timed * 1e6
+            if "sps" in r:
+                host_us = r["host_enqueue_sps"] * 1e6
                 bound_us = ring_us if r["transport"] == "collective" else link_us
                 cands = [x for x in (k_us, bound_us, host_us) if x]
-                e.update(value=rate(r["elapsed"]), ms_per_step=r["elapsed"] / timed * 1e3,
+                e.update(value=rate(r["sps"]), ms_per_step=r["sps"] * 1e3,
                          windows=[rate(w) for w in r["windows"]], gather_ok=r["gather_ok"], gather_check=r["gather_check"],
                          host_enqueue_us_per_step=host_us, hip_graph_steps_per_replay=r["graph_cycle"] or None,
                          xgmi_bound_us_per_step=bound_us,
@@ -660,29 +720,29 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
         # without any, the replicas pass
         head = best or (max(measured, key=lambda n: table[n]["value"]) if measured else None)
         if head is not None:
-            elapsed, wins = by_t[head]["elapsed"], by_t[head]["windows"]
+            sps, wins = by_t[head]["sps"], by_t[head]["windows"]
         elif "replicas" in results:
-            elapsed, wins = results["replicas"]["elapsed"], results["replicas"]["windows"]
+            sps, wins = results["replicas"]["sps"], results["replicas"]["windows"]
         else:
             raise RuntimeError("nothing was measured: " + "; ".join("%s: %s" % (n, e.get("error")) for n, e in table.items()))
         out = {
             "metric": "env-steps/sec (whole node) at 4096 envs x 240 lidar beams",
-            "value": rate(elapsed), "unit": "env-steps/s", "n_gpus": state.get("ranks_ran", world), "steps": args.steps, "warmup": args.warmup,
+            "value": rate(sps), "unit": "env-steps/s", "n_gpus": state.get("ranks_ran", world), "steps": args.steps, "warmup": args.warmup,
             "steps_timed": timed, "warmup_run": warm, "steps_effective": timed, "rccl_ranks": state.get("rccl_ranks"),
-            "ms_per_step": elapsed / timed * 1e3, "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": sps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "windows": [rate(w) for w in wins], "window_spread": (max(wins) - min(wins)) / elapsed if elapsed > 0 else None,
-            "window_rule": "median of %d windows of %d steps" % (n_win, timed),
+            "windows": [rate(w) for w in wins], "window_spread": (max(wins) - min(wins)) / sps if sps > 0 else None,
+            "window_rule": "median of %d windows (%s steps)" % (n_win, " + ".join(str(n) for n in win_steps)),
         }
         if aborted:
             out["aborted"] = aborted
         if world == 1 and head is None and "replicas" in results:  # the host's share of a step: launches enqueued, not yet run
-            out["host_enqueue_us_per_step"] = results["replicas"]["host_enqueue_s"] / timed * 1e6
+            out["host_enqueue_us_per_step"] = results["replicas"]["host_enqueue_sps"] * 1e6
         if world > 1:
             out["value_mode"] = ("gather:" + head) if head is not None else "replicas"
             if "replicas" in results:
-                out["value_replicas"] = rate(results["replicas"]["elapsed"])
-                out["ms_per_step_replicas"] = results["replicas"]["elapsed"] / timed * 1e3
+                out["value_replicas"] = rate(results["replicas"]["sps"])
+                out["ms_per_step_replicas"] = results["replicas"]["sps"] * 1e3
                 out["windows_replicas"] = [rate(w) for w in results["replicas"]["windows"]]
             if table:
                 out["value_by_transport"] = table
@@ -699,7 +759,7 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
                     "slice_bytes_per_rank_per_step": slice_bytes, "xgmi_link_GBps": XGMI_LINK_GBPS,
                     "link_bound_us": link_us, "ring_allgather_bound_us": ring_us, "k_step_us": k_us,
                     "host_enqueue_us_per_step": table[head]["host_enqueue_us_per_step"],
-                    "host_enqueue_us_per_step_replicas": (results["replicas"]["host_enqueue_s"] / timed * 1e6) if "replicas" in results else None,
+                    "host_enqueue_us_per_step_replicas": (results["replicas"]["host_enqueue_sps"] * 1e6) if "replicas" in results else None,
                     "hip_graph_steps_per_replay": table[head]["hip_graph_steps_per_replay"],
                     "predicted_floor_us_per_step": table[head]["model_floor_us_per_step"],
                     "predicted_ceiling_env_steps_per_s": table[head]["model_ceiling_env_steps_per_s"],
@@ -714,6 +774,7 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
             par = "env-sharded dp%d, no data-path collective" % world
         c2 = args.workload == "c3" and args.traffic == 0 and args.lasers == 0
         TD_BYTES = 1 if getattr(args, "topdown_u8", False) else 4
+        k_ms = ((results.get("replicas") or {}).get("prof") or {}).get("k_step_ms")  # (HIP events: --full)
         out["config"] = {
             "workload": (("C2: %d envs/GPU x 1 ego, no traffic, no lidar (state observation only), PGDrive-v0 maps seeds 1000-1099, "
                           "%s actions, auto-reset" % (N, args.actions)) if c2 else
@@ -740,14 +801,13 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
                              "loop" % args.step_n} if args.step_n > 1 else {}),
             **({"observation": "top-down image 84 x 84 x 5 %s, %.1f MB written per step" % (
                 "uint8 (pgd_observe_topdown_u8)" if TD_BYTES == 1 else "float32 (pgd_observe_topdown)", N * 84 * 84 * 5 * TD_BYTES / 1e6),
-                # the image kernel's share of a step = step time - k_step's event time; its roofline is the HBM write rate
-                "topdown_us": (elapsed / timed * 1e3 - (((results.get("replicas") or {}).get("prof") or {}).get("k_step_ms") or 0.0)) * 1e3,
-                "topdown_write_frac_of_hbm_peak": (N * 84 * 84 * 5 * TD_BYTES) / max(1e-9, (elapsed / timed - (((results.get("replicas") or {}).get("prof") or {}).get("k_step_ms") or 0.0) * 1e-3)) / 8e12}
+                # the image kernel's share of a step = step time - k_step's event time (--full); its roofline is the HBM write rate
+                **({"topdown_us": (sps * 1e3 - k_ms) * 1e3,
+                    "topdown_write_frac_of_hbm_peak": (N * 84 * 84 * 5 * TD_BYTES) / max(1e-9, sps - k_ms * 1e-3) / 8e12} if k_ms else {})}
                if args.topdown else {}),
             "parallelism": par, "backend": (args.backend if world > 1 else "none"),
-            "steady_state": "pre-roll %d steps, %d x %d timed steps (floors %d / %d%s)" % (
-                warm, n_win, timed, PREROLL_HEAD if world == 1 else PREROLL_MIN, TIMED_HEAD if world == 1 else TIMED_MIN,
-                ", off: --exact" if args.exact else ""),
+            "steady_state": "pre-roll %d steps (floor %d%s), %d timed steps in %d windows" % (
+                warm, PREROLL_HEAD if world == 1 else PREROLL_MIN, ", off: --exact" if args.exact else "", timed, n_win),
         }
         out["roofline"] = make_roofline((results.get("replicas") or {}).get("prof"), (results.get("replicas") or {}).get("stride", 1),
                                         work, args, N, A, D, lib_sha=state.get("lib_sha"))
@@ -766,7 +826,8 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
             # HIP events bracket groups of PROF_STRIDE consecutive k_step launches over the whole timed region; the average
             # launch duration is group time / PROF_STRIDE (two event packets around EVERY launch leave the command processor
             # idle between back-to-back kernels and slow the thing being measured)
-            profiled = args.step_n == 1  # (the open-loop variant mixes launches with and without the observation)
+            # (--full only: the roofline is not the headline; the open-loop variant mixes launches with and without the observation)
+            profiled = args.full and args.step_n == 1
             if args.groups > 1 and getattr(args, "groups_graph", 0) > 1:
                 # the groups' steps from here on come out of graphs: U steps of group g with the actions of steps 0 .. U - 1 (+ 5 g), captured
                 # on the group's stream after the pre-roll (the launches inside a graph carry no event pairs: no k_step event time)
@@ -784,17 +845,19 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
                 state["group_graphs"] = graphs
                 state["counter"] = (state["counter"] + U - 1) // U * U
             # short --exact runs (tests, sweeps of a few hundred steps): smaller groups, so that several of them complete
-            stride = PROF_STRIDE if timed >= 8 * PROF_STRIDE else (16 if timed >= 16 else 1)
+            stride = PROF_STRIDE if min(win_steps) >= 8 * PROF_STRIDE else (16 if min(win_steps) >= 16 else 1)
             if profiled:
-                eng.profile_begin(n_win * (timed // stride + 1) + 1, stride=stride)
+                eng.profile_begin(sum(n // stride + 1 for n in win_steps) + 1, stride=stride)
 
-            def window_replicas():
-                for k in range(timed):
+            def window_replicas(n):
+                for k in range(n):
                     step_replica(state["counter"])
                     state["counter"] += 1
             wins, med, enq = timed_windows(window_replicas)
             prof = eng.profile_end() if profiled else None
-            results["replicas"] = dict(elapsed=wins[med], windows=wins, prof=prof, host_enqueue_s=enq, stride=stride)
+            results["replicas"] = dict(sps=wins[med], windows=wins, prof=prof, host_enqueue_sps=enq, stride=stride)
+            if args.dump_outputs and rank == 0:
+                results["replicas"]["outputs"] = replica_outputs()
 
         # ---- the per-step gather, one pass per transport (N > 1) -----------------------------------------------------------------
         def run_transport(transport, use_graph):
@@ -803,9 +866,10 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
             try:
                 if use_graph and transport != "peer" and args.backend != "nccl":
                     raise RuntimeError("backend %s runs its collectives on the host: they cannot be captured in a HIP graph" % args.backend)
-                if use_graph and (timed % CYC or CYC % 2):
+                if use_graph and (any(n % CYC for n in win_steps) or CYC % 2):
                     # (a shorter cycle would replay actions[0:cyc] only -- another workload than the eager passes)
-                    raise RuntimeError("the timed steps (%d) are not whole %d-step action cycles: no graph pass" % (timed, CYC))
+                    raise RuntimeError("the timed windows (%s steps) are not whole %d-step action cycles: no graph pass" % (
+                        " + ".join(str(n) for n in win_steps), CYC))
                 g = pdist.StepGather(torch, dist, N, D, A, device=dev, transport=transport, engine_lib=eng.L,
                                      device_seq=bool(use_graph and transport == "peer"))
                 res["describe"] = g.describe() + (", %d steps per HIP graph replay" % CYC if use_graph else "")
@@ -826,16 +890,18 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
                 if use_graph:
                     cycle = g.capture_cycle([(lambda rows, a_i=actions[i]: eng.step_packed(a_i, rows)) for i in range(CYC)])
 
-                def window_gather():
+                def window_gather(n):
                     if cycle is not None:  # one host call per cycle of CYC steps
-                        for c in range(timed // CYC):
+                        for c in range(n // CYC):
                             cycle.replay()
                     else:
-                        for k in range(timed):
+                        for k in range(n):
                             one_step(state["counter"] + k)
-                    state["counter"] += timed
+                    state["counter"] += n
                     g.drain()
                 wins, med, enq = timed_windows(window_gather)
+                if args.dump_outputs and rank == 0:  # the rows of the last timed step, as the gather delivered them
+                    res["outputs"] = {k: v.cpu().numpy() for k, v in zip(("obs", "reward", "done"), g.result((g.k - 1) % g.nbuf))}
                 # self-check of the exchange, after the timed loop: every rank's checksum of the rows it produced against the
                 # checksum of what arrived for it (a transport that delivers wrong rows would otherwise still print a number)
                 a_chk = actions[state["counter"] % CYC]
@@ -846,7 +912,7 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
                             buf[buf.shape[0] - 1, 3] += 1.0
                 ok, detail = g.validate(lambda rows: eng.step_packed(a_chk, rows), corrupt=corrupt)
                 state["counter"] += 1
-                res.update(elapsed=wins[med], windows=wins, host_enqueue_s=enq, gather_ok=bool(ok), gather_check=dict(ok=bool(ok), **detail),
+                res.update(sps=wins[med], windows=wins, host_enqueue_sps=enq, gather_ok=bool(ok), gather_check=dict(ok=bool(ok), **detail),
                            graph_cycle=CYC if cycle is not None else 0)
             except Exception as ex:  # noqa: BLE001  (a transport that does not come up: report it, keep the other passes)
                 res["error"] = "%s: %s" % (type(ex).__name__, str(ex)[:300])
@@ -864,7 +930,7 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
             for transport, use_graph in plan:
                 name = transport + ("+graph" if use_graph else "")
                 if watchdog is not None:
-                    if rank == 0 and ("replicas" in results or any("elapsed" in r for r in by_transport.values())):
+                    if rank == 0 and ("replicas" in results or any("sps" in r for r in by_transport.values())):
                         watchdog.partial = make_line_ref[0](dict(by_transport), None, None)
                     watchdog.label = "transport " + name
                     watchdog.arm(name, args.transport_timeout)
@@ -885,9 +951,9 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
         state["lib_sha"] = eng.L.pgd_source_sha().decode()  # of the library THIS engine runs on (PGD_LIB builds included)
     except AttributeError:
         state["lib_sha"] = "unstamped"
-    # how much work a step does at this point of the run: 5 snapshots of the state, 50 untimed steps apart
+    # how much work a step does at this point of the run (--full): 5 snapshots of the state, 50 untimed steps apart
     work = None
-    if args.workload == "c3" and N <= 65536:
+    if args.full and args.workload == "c3" and N <= 65536:
         from pgdrive_amd import _abi as abi
         act_n, with_t, ep = [], [], []
         with torch.cuda.stream(eng.stream):
@@ -909,7 +975,7 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
             # point, traffic_manager.py:199-202,292-309, and the scripted ego drives into the vehicle 1 m ahead of it at once)
             work["note"] = ("episodes last %.1f steps on average: this row times reset churn in a jam around the spawn point, not "
                             "driving" % work["episode_step_mean"])
-    elif args.workload == "c5":  # (the agent population swings with the 1000-step agent horizon: five snapshots, 100 steps apart)
+    elif args.full and args.workload == "c5":  # (the agent population swings with the 1000-step agent horizon: five snapshots, 100 steps apart)
         from pgdrive_amd import _abi as abi
         act_a, pres_a = [], []
         with torch.cuda.stream(eng.stream):
@@ -936,7 +1002,13 @@ def measure(args, rank, world, local_rank, with_cpu_baseline=True):
     out = None
     if rank == 0:
         out = make_line(by_transport, work, None)
-        if with_cpu_baseline and not args.no_cpu_baseline and world == 1:
+        if args.dump_outputs:  # the headline's pass: the chosen transport's gathered rows (N > 1), else the replicas pass
+            src = (by_transport.get(out.get("transport_chosen")) or {}).get("outputs") or (results.get("replicas") or {}).get("outputs")
+            if not src:
+                raise RuntimeError("--dump-outputs: the headline's pass left no outputs")
+            n_rows = max(src.values(), key=lambda a: a.nbytes).shape[0]  # the envs: first axis of the observation / image
+            out["outputs_written"] = dump_outputs(args.dump_outputs, src, n_rows)
+        if with_cpu_baseline and args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(descs, args) if (args.workload == "c3" and args.traffic > 0) else None
         else:
             out["cpu_baseline"] = None
@@ -1149,21 +1221,22 @@ def run_rank(args, rank, world, local_rank):
     if world > 1:
         WATCHDOG.on_termination()
     out = measure(args, rank, world, local_rank)
-    # the loaded rows, in the same invocation (N = 1, the default command only: any flag that changes the workload of the
+    # the loaded rows, in the same invocation (--full, N = 1, the default command only: any flag that changes the workload of the
     # headline -- other actions, env counts, groups ... -- is a single-workload run)
     default_cmd = (args.workload == "c3" and args.actions == "uniform" and args.traffic_mode == "trigger" and args.envs == 4096 and
                    args.traffic == 16 and args.lasers == 240 and args.maps == 100 and args.groups == 1 and args.engines == 1 and
                    args.step_n == 1 and not args.topdown and not args.exact and not args.jit)
-    if world == 1 and rank == 0 and not args.no_rows and (default_cmd or args.rows):
+    if args.full and world == 1 and rank == 0 and not args.no_rows and (default_cmd or args.rows):
         want = None if not args.rows else set(args.rows.split(","))
         rows = []
         for name, over in ROWS:
             if want is not None and name not in want:
                 continue
             ra = copy.copy(args)
-            ra.exact, ra.warmup, ra.steps = True, 1500, 1024  # (x --windows windows)
+            ra.exact, ra.warmup, ra.steps, ra.dump_outputs = True, 1500, 1024, None
             for k, v in over.items():
                 setattr(ra, k, v)
+            ra.steps *= ra.windows  # (ROWS give the steps of one window)
             try:
                 rows.append(row_summary(name, measure(ra, 0, 1, local_rank, with_cpu_baseline=False)))
             except Exception as ex:  # noqa: BLE001  (a row that fails must not take the metric's line with it)

@@ -153,12 +153,12 @@ def test_bench_spawns_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--oversubscribe", "--backend", "gloo",
-                          "--exact", "--steps", "64", "--warmup", "8", "--envs", "256", "--no-cpu-baseline"],
+                          "--exact", "--steps", "192", "--warmup", "8", "--envs", "256", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=800, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
-    assert d["n_gpus"] == 2 and d["steps"] == 64 and d["steps_timed"] == 64
+    assert d["n_gpus"] == 2 and d["steps"] == 192 and d["steps_timed"] == 192
     assert d["value_mode"].startswith("gather:") and d["value"] == d["value_gather"] and d["value_replicas"] > 0
     # the default N > 1 run times EVERY transport in the one invocation; the headline is the best one whose self-check passed
     t = d["value_by_transport"]
@@ -174,7 +174,7 @@ def test_bench_spawns_its_own_ranks():
     assert d["gather_mem"] in ("fine", "coarse") and t["peer"]["gather_mem"] == d["gather_mem"]
     assert d["config"]["global_envs"] == 512 and t[d["transport_chosen"]]["describe"] in d["config"]["parallelism"]
     assert len(d["windows"]) == 3 and d["window_spread"] >= 0 and len(d["windows_replicas"]) == 3
-    assert d["roofline"]["k_step_ms"] > 0  # measured in the replicas pass
+    assert d["roofline"]["k_step_ms"] > 0  # measured in the replicas pass (--full)
     # the exchange checks itself after the timed loop and the line carries what bounds it by construction
     assert d["gather_ok"] is True and d["gather_check"]["ranks_checked"] == 2 and d["gather_check"]["mismatched_ranks"] == []
     m = d["gather_model"]
@@ -193,14 +193,14 @@ def test_bench_world_8_under_the_drivers_launcher():
         env.pop(k, None)
     port = 29600 + (os.getpid() % 200)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "64", "--warmup", "20",
+                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "192", "--warmup", "20",
                           "--oversubscribe", "--backend", "gloo", "--exact", "--envs", "512", "--no-rows",
                           "--no-cpu-baseline"], capture_output=True, text=True, timeout=1100, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, "rank 0 alone prints, one line"
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["steps"] == 64 and d["warmup"] == 20 and d["scaling"] == "weak" and "aborted" not in d
+    assert d["n_gpus"] == 8 and d["steps"] == 192 and d["warmup"] == 20 and d["scaling"] == "weak" and "aborted" not in d
     assert d["config"]["global_envs"] == 8 * 512 and d["config"]["envs_per_gpu"] == 512
     assert d["value_mode"].startswith("gather:") and d["value"] > 0 and d["value_replicas"] > 0
     t = d["value_by_transport"]
@@ -232,7 +232,7 @@ def test_bench_gather_in_a_hip_graph():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--oversubscribe", "--backend", "gloo",
-                          "--exact", "--steps", "128", "--warmup", "8", "--envs", "256", "--no-cpu-baseline", "--transport", "peer", "--graph"],
+                          "--exact", "--steps", "384", "--warmup", "8", "--envs", "256", "--no-cpu-baseline", "--transport", "peer", "--graph"],
                          capture_output=True, text=True, timeout=800, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -260,12 +260,13 @@ def test_bench_gather_self_check_sees_a_damaged_row(transport):
 
 
 def test_bench_default_run_is_steady_state_and_reproducible_from_events():
-    """--steps 20 (what the driver passes) still pre-rolls and times the floors; the roofline time comes from >= 64 event groups."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+    """--warmup 5 still pre-rolls the floor, exactly --steps steps are timed (three windows of 4096), and under --full the roofline
+    time comes from >= 64 event groups."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12288", "--warmup", "5", "--full",
                           "--no-cpu-baseline", "--rows", "c3_respawn,c5_8x72"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
-    assert d["steps"] == 20 and d["warmup"] == 5 and d["steps_timed"] >= 2000 and d["warmup_run"] >= 1500
+    assert d["steps"] == 12288 and d["warmup"] == 5 and d["steps_timed"] == 12288 and d["warmup_run"] >= 1500
     assert d["n_gpus"] == 1 and d["roofline"]["events"] >= 64
     # launch-to-launch time (wall / steps) and the event time of the kernel agree: same workload phase
     assert abs(d["ms_per_step"] - d["roofline"]["k_step_ms"]) < 0.15 * d["ms_per_step"]
@@ -288,6 +289,29 @@ def test_bench_default_run_is_steady_state_and_reproducible_from_events():
     assert rows["c5_8x72"]["workload"].startswith("C5: 4096 envs/GPU x 8 agents") and rows["c5_8x72"]["active_agents_mean"] > 1
     assert all(0 < x["roofline"]["frac_moved"] <= x["roofline"]["frac"] for x in rows.values())
     assert all(len(x["windows"]) == 3 for x in rows.values())
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the line carries the headline alone (no rows, CPU baseline, roofline or work statistics), times exactly
+    --steps steps, and --dump-outputs writes what the last timed step returned -- the same arrays on a second run."""
+    lines = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "300", "--warmup", "5",
+                              "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
+    d = lines[0]
+    assert d["steps"] == d["steps_timed"] == 300 and d["warmup"] == 5 and d["warmup_run"] >= 1500 and len(d["windows"]) == 3
+    assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["n_gpus"] == 1
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"] and sorted(d["windows"])[1] == d["value"]
+    assert "rows" not in d and d["cpu_baseline"] is None and d["roofline"] is None and "driving_traffic_mean" not in d["config"]
+    assert d["outputs_written"] == ["done", "flags", "obs", "reward"]
+    shapes = dict(obs=(4096, 1, 274), reward=(4096, 1), done=(4096, 1), flags=(4096, 1))
+    for name, shape in shapes.items():
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.shape == shape and a.dtype == (np.float64 if name == "flags" else np.float32) and np.isfinite(a).all(), name
+        assert np.array_equal(a, b), name
+    assert np.abs(np.load(tmp_path / "a" / "obs.npy")).max() > 0
 
 
 def _graph_worker(rank, world, port, n_total, cycle, n_cycles, q, use_graph):

@@ -344,3 +344,37 @@ def test_bench_rows_are_well_formed():
             assert over.get("topdown")
     a = bench.parse_args(["--groups", "2", "--groups-graph", "64", "--topdown", "--topdown-u8"])
     assert a.groups == 2 and a.groups_graph == 64 and a.topdown_u8 and a.lasers == 0
+
+
+def test_bench_plain_options_windows_and_output_dump(tmp_path):
+    """A plain bench run is the default (--full opts into the rest; --rows only with it); --steps is split into windows that add
+    up to it exactly; --dump-outputs writes float32 / float64 copies and, beyond its byte budget, one seeded sample of the envs."""
+    import bench
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    b = bench.parse_args(["--full", "--rows", "c3_respawn", "--dump-outputs", str(tmp_path)])
+    assert b.full and b.rows == "c3_respawn" and b.dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--rows", "c3_respawn"])
+    for steps, n_win in ((20, 3), (2, 3), (192, 3), (100000, 3), (7, 1)):
+        w = bench.window_lengths(steps, n_win)
+        assert sum(w) == steps and len(w) == min(steps, n_win) and max(w) - min(w) <= 1
+    rng = np.random.default_rng(1)
+    arrays = dict(obs=rng.normal(size=(64, 1, 30)).astype(np.float32), done=(rng.uniform(size=(64, 1)) < 0.1).astype(np.uint8),
+                  flags=rng.integers(0, 1 << 30, size=(64, 1)).astype(np.int32), rew_steps=rng.normal(size=(4, 64, 1)))
+    names = bench.dump_outputs(str(tmp_path / "all"), arrays, 64)
+    assert names == ["done", "flags", "obs", "rew_steps"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == (np.float64 if k in ("flags", "rew_steps") else np.float32) and np.array_equal(got, v.astype(got.dtype)), k
+        assert np.array_equal(got.astype(v.dtype), v), k  # exact
+    # a budget of 4 KB: the env rows are sampled (the same rows for every array of 64 rows), the rest is kept whole
+    names = bench.dump_outputs(str(tmp_path / "few"), arrays, 64, limit=4096)
+    rows = np.load(tmp_path / "few" / "sample_rows.npy").astype(np.int64)
+    assert "sample_rows" in names and 0 < len(rows) < 64 and np.all(np.diff(rows) > 0)
+    assert sum(np.load(tmp_path / "few" / (n + ".npy")).nbytes for n in names) <= 4096
+    assert np.array_equal(np.load(tmp_path / "few" / "obs.npy"), arrays["obs"][rows])
+    assert np.array_equal(np.load(tmp_path / "few" / "flags.npy"), arrays["flags"][rows].astype(np.float64))
+    assert np.load(tmp_path / "few" / "rew_steps.npy").shape == (4, 64, 1)
+    again = bench.dump_outputs(str(tmp_path / "again"), arrays, 64, limit=4096)
+    assert again == names and np.array_equal(np.load(tmp_path / "again" / "sample_rows.npy"), rows.astype(np.float64))

@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; cd $R; TAG=${1:-r05final}
 O=$R/gpurun_out/$TAG; mkdir -p $O
 ( time timeout 2400 python -m pytest tests -m gpu -q --timeout 900 ) > $O/pytest.log 2>&1; tail -4 $O/pytest.log
-( time timeout 900 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null ) 2> $O/bench.time; tail -c 300 $O/bench.json; echo; cat $O/bench.time
+( time timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null ) 2> $O/bench.time; tail -c 300 $O/bench.json; echo; cat $O/bench.time
 bash tools/row_pass.sh $TAG/c5_40x72 c5 4096 uniform trigger 40 72
 bash tools/row_pass.sh $TAG/c5_8x72 c5 4096 uniform trigger 8 72
 bash tools/row_pass.sh $TAG/c5_8x240 c5 4096 uniform trigger 8 240

@@ -5,7 +5,7 @@
 R=$GRAFT_REPO_ROOT; cd $R; TAG=${1:-r06final}
 O=$R/gpurun_out/$TAG; mkdir -p $O
 if [ -z "$NO_SUITE" ]; then ( time timeout 2400 python -m pytest tests -m gpu -q --timeout 900 ) > $O/pytest.log 2>&1; tail -4 $O/pytest.log; fi
-( time timeout 900 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null ) 2> $O/bench.time; tail -c 300 $O/bench.json; echo; cat $O/bench.time
+( time timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null ) 2> $O/bench.time; tail -c 300 $O/bench.json; echo; cat $O/bench.time
 bash tools/row_pass.sh $TAG/head c3 4096 uniform trigger 1 240
 bash tools/row_pass.sh $TAG/straight c3 4096 straight trigger 1 240
 bash tools/row_pass.sh $TAG/c2_1024 c3 1024 uniform trigger 1 0 --traffic 0

@@ -1,11 +1,11 @@
 #!/bin/bash
 # workload sweep of profiles/rNN_sweep.md (one GPU, final kernels): the C3 workload rows (idle / straight / expert / dense), C3 at
 # 16384 / 32768 / 262144 envs (default kernel and throughput mode), C2, C5, async groups, open loop, top-down
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/sweep
-run() { name=$1; shift; timeout 400 python bench.py --no-cpu-baseline "$@" > gpurun_out/sweep/$name.json 2> gpurun_out/sweep/$name.err; python -c "
-import json; d=json.loads(open('gpurun_out/sweep/$name.json').read().strip().splitlines()[-1]); r=d['roofline'] or {}; c=d['config']
+cd "$(dirname "$0")/.."; D=${SWEEP_OUT:-$(mktemp -d)}  # the lines of every run: $D/<run>.json
+run() { name=$1; shift; timeout 400 python bench.py --full --no-cpu-baseline "$@" > $D/$name.json 2> $D/$name.err; python -c "
+import json; d=json.loads(open('$D/$name.json').read().strip().splitlines()[-1]); r=d['roofline'] or {}; c=d['config']
 print('| $name | %s | %.1f M | %.2f | %.2f | %.2f | %.3f | %s | %s |' % (c['workload'][:86], d['value']/1e6, d['ms_per_step']*1e3, r.get('k_step_ms',0)*1e3, r.get('k_observe_ms',0)*1e3, r.get('frac',0),
-  ('%.2f' % c['driving_traffic_mean']) if 'driving_traffic_mean' in c else '-', ('%.2f' % c['envs_with_traffic_frac']) if 'envs_with_traffic_frac' in c else '-'))" || tail -2 gpurun_out/sweep/$name.err; }
+  ('%.2f' % c['driving_traffic_mean']) if 'driving_traffic_mean' in c else '-', ('%.2f' % c['envs_with_traffic_frac']) if 'envs_with_traffic_frac' in c else '-'))" || tail -2 $D/$name.err; }
 echo "| run | workload | env-steps/s | us/step | k_step us | k_observe us | roofline frac (algorithmic bytes) | driving IDM vehicles / env | envs with driving traffic |"; echo "|---|---|---|---|---|---|---|---|---|"
 run c3_4096 --envs 4096
 run c3_straight --envs 4096 --actions straight
