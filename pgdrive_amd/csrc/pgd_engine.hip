@@ -226,7 +226,6 @@ constexpr FixSpec fix_spec(int fix) {
 // 128 and 23 scalar spills instead of 77: k_step 28.4 -> 26.3 us, k_observe_env 30.2 -> 29.5 us (64 registers), the row 76.8 -> 81.1 M
 // (round 6, profiles/r06_notes.md).  The respawn table's shape and the horizon stay run-time values (they differ between the maps).
 #define PGD_FIXM_SEAT_FIELDS(F, d, c, S, NL) F(d.V, S) F(d.A, S) F(d.sub, (WAVE / (S))) F(d.D, (18 + (NL))) F(c.num_agents, S) F(c.num_lasers, NL)
-#define PGD_FIXM_SEAT_CODES {40072, 44072, 8072, 8240}
 // BASELINE config 2: the ego alone, no lidar (dynamics + reward + the 18-float state vector), otherwise the single-agent defaults --
 // four envs per wave, 16 sub-lanes per ego, the row written by k_step itself.
 #define PGD_FIXE_FIELDS(F, d, c)                                                                                                    \
@@ -275,18 +274,6 @@ static bool fix_config_matches(const PgdDev& d, bool one_env, int kind = FIXK_DE
   }
 #undef PGD_F_TEST
   return ok;
-}
-// the multi-agent instantiations with the seat count folded: which one (0 = none) an engine that passed FIXK_MARL can run
-static int marl_fix_seats(const PgdDev& d) {  // (the code seats x 1000 + beams, or 0)
-  for (int code : PGD_FIXM_SEAT_CODES) {
-    const int S = code / 1000, NL = code % 1000;
-    bool ok = true;
-#define PGD_F_TEST(f, v) ok = ok && (f == v);
-    PGD_FIXM_SEAT_FIELDS(PGD_F_TEST, d, d.cfg, S, NL)
-#undef PGD_F_TEST
-    if (ok) return code;
-  }
-  return 0;
 }
 // What only the rare paths of a step read (an env restarting, a multi-agent respawn): a second by-value argument that is never
 // written, so its fields are fetched from the argument segment where they are used -- in the specialised kernels `d` is a local
@@ -1064,7 +1051,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
       const MapView mvb = mv;
       const unsigned lead_fl = (unsigned)__shfl((int)my_fl, g.lead);  // the step flags are complete in the slot's first lane only
       const EnvInWave in_wave{&r, &SPV, &mvb, lead_fl, scen, steps_total, valid ? s : A, g.sub};  // lanes past the last slot: no agent
-      // (V == A and WAVE / A lanes per slot: the host launches this instantiation for no other engine -- step_impl -- so the
+      // (V == A and WAVE / A lanes per slot: the host launches this instantiation for no other engine -- step_kernel -- so the
       // read-back form of the routine is not compiled into it: 2 k instructions less in a kernel that filled the instruction cache)
       observe_env_body<1, false, true, OBJ>(d, e, obs, flags, U.obs.m, U.obs.minb, d.obs_g, &in_wave);
     } else
@@ -1484,6 +1471,104 @@ struct pgd_engine {
   float* lk_act;     // pgd_step_lane_keep on engines that cannot take the policy into the step kernel: the actions in between
 };
 
+// The default row layout (see observe_agent): the STD instantiations of k_step
+static bool std_rows(const pgd_config& c) {
+  return c.side_lasers == 0 && c.lane_line_lasers == 0 && !c.random_agent_model && c.lidar_gaussian_noise <= 0.0f &&
+         c.lidar_dropout_prob <= 0.0f;
+}
+
+// The engines a step kernel built at run time can serve at all (pgd_set_step_module): single agent, one env per wave
+static bool jit_geometry_ok(const pgd_engine* h) { return !(h->d.cfg.marl_flags & PGD_MA_ENABLED) && h->d.epw == 1 && !h->d.pack_obs; }
+
+// Env group `group` of pgd_set_groups: envs [first, first + count) on the group's stream; -1 = all envs on the engine stream
+struct EnvGroup { int first, count; hipStream_t stream; };
+static int env_group(const pgd_engine* h, int group, EnvGroup& g) {
+  g = {0, h->d.N, h->stream};
+  if (group < 0) return PGD_OK;
+  if (group >= h->n_groups || !h->gstreams) return PGD_ERR_ARG;
+  g.count = h->d.N / h->n_groups;
+  g.first = group * g.count;
+  g.stream = h->gstreams[group];
+  return PGD_OK;
+}
+
+using StepFn = void (*)(PgdDev, const float*, float*, uint8_t*, uint32_t*, float*, PgdCold);
+using ObsFn = void (*)(PgdDev, float*, const uint32_t*, int);
+// The multi-agent instantiations with the seat count folded (PGD_FIXM_SEAT_FIELDS; code = seats x 1000 + beams).  40 and 44 seats
+// observe with k_observe_env<4> after the step (before / after k_step wrote the state blocks); 8 seats fuse the observation into k_step.
+struct SeatKernels { int code; StepFn step; const char* name; ObsFn observe, observe_after_state; };
+static const SeatKernels SEAT_KERNELS[] = {
+    {40072, k_step<true, true, false, false, 40072>,
+     "k_step: one env per wave, specialised for the default multi-agent configuration with 40 agent seats x 72 beams",
+     k_observe_env<4, true, true, 40072>, k_observe_env<4, true, false, 40072>},
+    {44072, k_step<true, true, false, false, 44072>,
+     "k_step: one env per wave, specialised for the default multi-agent configuration with 44 agent seats x 72 beams",
+     k_observe_env<4, true, true, 44072>, k_observe_env<4, true, false, 44072>},
+    {8072, k_step<true, true, false, false, 8072>,
+     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 72 beams", nullptr, nullptr},
+    {8240, k_step<true, true, false, false, 8240>,
+     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 240 beams", nullptr, nullptr},
+};
+// which of them (null = none) an engine that passed FIXK_MARL can run
+static const SeatKernels* marl_fix_seats(const PgdDev& d) {
+  for (const SeatKernels& s : SEAT_KERNELS) {
+    bool ok = true;
+#define PGD_F_TEST(f, v) ok = ok && (f == v);
+    PGD_FIXM_SEAT_FIELDS(PGD_F_TEST, d, d.cfg, s.code / 1000, s.code % 1000)
+#undef PGD_F_TEST
+    if (ok) return &s;
+  }
+  return nullptr;
+}
+
+// FIX 1 with one env per wave: the reference's default single-agent configuration
+static bool default_one_env(const pgd_engine* h) { return !h->has_objects && !h->no_fix && fix_config_matches(h->d, true); }
+// the engines whose step kernel has an instantiation with the scripted policy inside: the FIX 1 case, the row fused into the step
+static bool lane_keep_in_step(const pgd_engine* h) { return default_one_env(h) && !h->no_fuse; }
+
+// A k_step instantiation, its pgd_describe_step text, and whether it was built for one configuration (write_fixed_config: a run-time
+// kernel does not take its place).
+struct StepKernel { StepFn fn; const char* name; bool specialised; };
+// The instantiation a step launches: the first case that holds, evaluated per step (pgd_set_groups and the uploads change
+// what it reads).  A specialised case holds only where fix_config_matches() does, so its results are the general kernel's; the
+// PGD_FIX*_FIELDS lists pin the geometry, the multi-agent flags and the row layout, and a case adds what they cannot: the object
+// flag and PGD_NO_FIX (A/B: never specialised).  Reads h->d: step_impl's launch copy differs in no field of those lists.
+static StepKernel step_kernel(const pgd_engine* h) {
+  const PgdDev& d = h->d;
+  const bool obj = h->has_objects, fix = !h->no_fix;
+  const char* general = d.pack_obs ? "k_step: whole envs side by side in a wave, one vehicle per lane (throughput mode)"
+                                   : (d.epw == 1 ? "k_step: one env per wave" : "k_step: several envs per wave");
+  if (d.cfg.marl_flags & PGD_MA_ENABLED) {
+    if (!obj && fix && fix_config_matches(d, true, FIXK_MARL) && d.V == d.A && d.sub == WAVE / d.A) {
+      if (const SeatKernels* s = marl_fix_seats(d)) return {s->step, s->name, true};
+      return {k_step<true, true, false, false, 1>, "k_step: one env per wave, specialised for the default multi-agent configuration", true};
+    }
+    return {obj ? k_step<true, true, true> : k_step<true, true, false>, general, false};  // (objects = toll booths)
+  }
+  if (d.epw == 1) {
+    if (h->lk.obs && lane_keep_in_step(h))
+      return {k_step<true, false, false, true, 1, true>,
+              "k_step: one env per wave, specialised for the default single-agent configuration, scripted lane-keeping policy inside", true};
+    if (obj && fix && fix_config_matches(d, true, FIXK_SAFE))
+      return {k_step<true, false, true, true, 4>,
+              "k_step: one env per wave, specialised for the SafePGDriveEnv configuration (16 traffic + 40 object slots, run-time reward scheme)", true};
+    if (!obj && fix && fix_config_matches(d, true, FIXK_NO_LIDAR))
+      return {k_step<true, false, false, true, 3>, "k_step: one env per wave, specialised for the top-down envs' configuration (single agent, lidar off)", true};
+    if (default_one_env(h)) return {k_step<true, false, false, true, 1>, "k_step: one env per wave, specialised for the default single-agent configuration", true};
+    if (!obj && fix && fix_config_matches(d, true, FIXK_GEOMETRY))
+      return {k_step<true, false, false, true, 2>,
+              "k_step: one env per wave, specialised for the default single-agent configuration with a run-time reward scheme", true};
+    return {obj ? k_step<true, false, true> : (std_rows(d.cfg) ? k_step<true, false, false, true> : k_step<true, false, false>), general, false};
+  }
+  if (obj) return {k_step<false, false, true>, general, false};
+  if (fix && fix_config_matches(d, false, FIXK_EGO_ONLY))
+    return {k_step<false, false, false, false, 1>, "k_step: several envs per wave, specialised for the ego-only configuration without a lidar", true};
+  if (fix && fix_config_matches(d, false))
+    return {k_step<false, false, false, true, 1>,
+            "k_step: whole envs side by side in a wave (throughput mode), specialised for the default single-agent configuration", true};
+  return {(d.pack_obs && std_rows(d.cfg)) ? k_step<false, false, false, true> : k_step<false, false, false>, general, false};
+}
+
 // Rows written by a kernel that does not keep the zero-row marks (k_observe, one block per row): what the marks say about this
 // buffer may no longer hold -- forget them (a memset node when the stream is being captured: every replay forgets again).
 static int obs_rows_forget(pgd_engine* h, hipStream_t stream) {
@@ -1870,13 +1955,35 @@ int pgd_upload_scenarios(pgd_handle h, const pgd_scenario* scen, int n_scen, con
 #ifndef PGD_OBS_ENV_LDS
 #define PGD_OBS_ENV_LDS 16384  // dynamic LDS a block of k_observe_env may take for its rounds of observers (40 slots x 72 beams: 53.2 us with 16 KB, 55.2 with 12, 55.8 with 48)
 #endif
+// observe_env_body's observers per round: from g down until the scratch of nw waves plus `extra` words fits `budget` words
+static int observers_per_round(const PgdDev& d, int g, int nw, size_t extra, size_t budget) {
+  while (g > 1 && (size_t)nw * observe_env_words(g, d.cfg.num_lasers, d.V, d.cfg.num_others) + extra > budget) --g;
+  return g;
+}
+
+// k_observe_env's launch: all rows of an env by one block (use), waves per env, observers per round of a wave, dynamic LDS
+struct ObsEnvPlan { bool use; int nw, G; size_t dyn; };
+static ObsEnvPlan observe_env_plan(const pgd_engine* h) {
+  const PgdDev& d = h->d;
+  ObsEnvPlan p{false, 1, 1, 0};
+  if (!(d.A > 1 && d.epw == 1 && !h->row_observe)) return p;
+  const bool oth = (d.cfg.marl_flags & PGD_MA_OTHERS_STATE) != 0 && d.cfg.num_others > 0;
+  const size_t oth_words = (size_t)observe_env_oth_words(d.A, d.cfg.num_others, oth);
+  p.nw = d.A >= 4 * (WAVE / d.V) ? 4 : 1;  // many observers, few per pass: four waves per env, each with its own range
+  // observers per round of a wave: the whole range if its LDS fits (48 KB per block)
+  p.G = observers_per_round(d, (d.A + p.nw - 1) / p.nw, p.nw, oth_words, PGD_OBS_ENV_LDS / 4);
+  p.dyn = ((size_t)p.nw * observe_env_words(p.G, d.cfg.num_lasers, d.V, d.cfg.num_others) + oth_words) * 4;
+  p.use = p.dyn <= 49152;
+  return p;
+}
+
 // The multi-agent observation after a step: is it the four-wave k_observe_env (many agent slots), and may k_step write the rows'
 // state blocks itself (PgdDev::state_rows)?  The latter for rows without detector fans, neighbour rows, toll floats or the
 // random-agent-model floats -- one lane per agent would cast the fans one beam after the other.  PGD_NO_STATE_IN_STEP=1: never (A/B).
-static bool env_observe_four(const pgd_engine* h);
 static bool state_in_step_ok(const pgd_engine* h) {
   const pgd_config& c = h->d.cfg;
-  return env_observe_four(h) && c.side_lasers == 0 && c.lane_line_lasers == 0 && c.num_others == 0 && !c.random_agent_model &&
+  const ObsEnvPlan p = observe_env_plan(h);
+  return p.use && p.nw == 4 && c.side_lasers == 0 && c.lane_line_lasers == 0 && c.num_others == 0 && !c.random_agent_model &&
          !(c.marl_flags & (PGD_MA_TOLLGATE | PGD_MA_OTHERS_STATE)) && c.num_lasers > 0 && !h->no_state_in_step;
 }
 
@@ -1884,50 +1991,28 @@ static int launch_observe(pgd_handle h, float* d_obs, const uint32_t* d_flags, c
                           int n_envs = 0, bool state_done = false) {
   const PgdDev& D = dv ? *dv : h->d;
   if (!stream) stream = h->stream;
-  const int rows = (n_envs > 0 ? n_envs : h->d.N) * h->d.A;
+  const int envs = n_envs > 0 ? n_envs : h->d.N, rows = envs * h->d.A;
   const bool oth = (h->d.cfg.marl_flags & PGD_MA_OTHERS_STATE) != 0 && h->d.cfg.num_others > 0;
-  const int envs = n_envs > 0 ? n_envs : h->d.N;
-  if (h->d.A > 1 && h->d.epw == 1 && !h->row_observe) {  // all rows of an env by one block
-    const int A = h->d.A, V = h->d.V, NL = h->d.cfg.num_lasers;
-    const bool four = A >= 4 * (WAVE / V);  // many observers, few per pass: four waves per env, each with its own range
-    const int nw = four ? 4 : 1, per_wave = (A + nw - 1) / nw;
-    int G = per_wave;  // observers per round of a wave: the whole range if its LDS fits (48 KB per block)
-    const size_t oth_bytes = (size_t)observe_env_oth_words(A, h->d.cfg.num_others, oth) * 4;
-    while (G > 1 && (size_t)nw * observe_env_words(G, NL, V, h->d.cfg.num_others) * 4 + oth_bytes > PGD_OBS_ENV_LDS) --G;
-    const size_t dyn = (size_t)nw * observe_env_words(G, NL, V, h->d.cfg.num_others) * 4 + oth_bytes;
-    if (dyn <= 49152) {
-      const bool fix = !h->no_fix && !h->has_objects && fix_config_matches(D, true, FIXK_MARL);
-      void (*ke)(PgdDev, float*, const uint32_t*, int) = four ? k_observe_env<4> : k_observe_env<1>;
-      if (fix) ke = four ? k_observe_env<4, true> : k_observe_env<1, true>;
-      if (state_done && four) ke = fix ? k_observe_env<4, true, false> : k_observe_env<4, false, false>;
-      const int seats = (fix && four) ? marl_fix_seats(D) : 0;
-      if (seats == 40072) ke = state_done ? k_observe_env<4, true, false, 40072> : k_observe_env<4, true, true, 40072>;
-      if (seats == 44072) ke = state_done ? k_observe_env<4, true, false, 44072> : k_observe_env<4, true, true, 44072>;
-      hipLaunchKernelGGL(ke, dim3(envs), dim3(WAVE * nw), dyn, stream, D, d_obs, d_flags, G);
-      HIPCHK(hipGetLastError());
-      return PGD_OK;
-    }
+  const ObsEnvPlan p = observe_env_plan(h);
+  if (p.use) {
+    const bool four = p.nw == 4;
+    const bool fix = !h->no_fix && !h->has_objects && fix_config_matches(D, true, FIXK_MARL);
+    ObsFn ke = four ? k_observe_env<4> : k_observe_env<1>;
+    if (fix) ke = four ? k_observe_env<4, true> : k_observe_env<1, true>;
+    if (state_done && four) ke = fix ? k_observe_env<4, true, false> : k_observe_env<4, false, false>;
+    const SeatKernels* seats = (fix && four) ? marl_fix_seats(D) : nullptr;
+    if (seats && seats->observe) ke = state_done ? seats->observe_after_state : seats->observe;
+    hipLaunchKernelGGL(ke, dim3(envs), dim3(WAVE * p.nw), p.dyn, stream, D, d_obs, d_flags, p.G);
+    HIPCHK(hipGetLastError());
+    return PGD_OK;
   }
-  if (state_done) return PGD_ERR_STATE;  // (state_in_step_ok promised the four-wave kernel: the same conditions as above)
+  if (state_done) return PGD_ERR_STATE;  // (state_in_step_ok promised the four-wave kernel)
   { int rc = obs_rows_forget(h, stream); if (rc) return rc; }
   const bool wide = h->d.cfg.num_lasers > 128;  // up to 128 beams one wave does it in two rounds: 4x fewer waves than 256-thread blocks
-  void (*kern)(PgdDev, float*, const uint32_t*, int) =
-      wide ? (oth ? k_observe<256, true> : k_observe<256, false>) : (oth ? k_observe<64, true> : k_observe<64, false>);
+  ObsFn kern = wide ? (oth ? k_observe<256, true> : k_observe<256, false>) : (oth ? k_observe<64, true> : k_observe<64, false>);
   hipLaunchKernelGGL(kern, dim3(wide ? rows : (rows + OBS_RPB - 1) / OBS_RPB), dim3(wide ? 256 : WAVE * OBS_RPB), 0, stream, D, d_obs, d_flags, rows);
   HIPCHK(hipGetLastError());
   return PGD_OK;
-}
-
-static bool env_observe_four(const pgd_engine* h) {  // (the conditions under which launch_observe takes k_observe_env<4>)
-  if (!(h->d.A > 1 && h->d.epw == 1 && !h->row_observe)) return false;
-  const int A = h->d.A, V = h->d.V, NL = h->d.cfg.num_lasers;
-  if (!(A >= 4 * (WAVE / V))) return false;
-  const bool oth = (h->d.cfg.marl_flags & PGD_MA_OTHERS_STATE) != 0 && h->d.cfg.num_others > 0;
-  const int per_wave = (A + 3) / 4;
-  int G = per_wave;
-  const size_t oth_bytes = (size_t)observe_env_oth_words(A, h->d.cfg.num_others, oth) * 4;
-  while (G > 1 && (size_t)4 * observe_env_words(G, NL, V, h->d.cfg.num_others) * 4 + oth_bytes > PGD_OBS_ENV_LDS) --G;
-  return (size_t)4 * observe_env_words(G, NL, V, h->d.cfg.num_others) * 4 + oth_bytes <= 49152;
 }
 
 int pgd_reset(pgd_handle h, const int32_t* env_ids, const int32_t* scen_ids, int n, float* d_obs) {
@@ -1969,20 +2054,10 @@ static int step_impl(pgd_handle h, const float* d_actions, float* d_obs, float* 
   PgdDev dv = h->d;  // this launch's output addressing
   dv.ostride = ostride;
   dv.prow = packed ? d_obs : nullptr;
-  {  // fused multi-agent observation: observers per round = what the step's LDS holds
-    int G = h->d.A;
-    while (G > 1 && observe_env_words(G, h->d.cfg.num_lasers, h->d.V, h->d.cfg.num_others) > STEP_MINB_WORDS) --G;
-    dv.obs_g = G;
-  }
-  // env group: the blocks (and the stream) of envs [group * N / G, (group + 1) * N / G); -1 = all envs on the engine stream
-  hipStream_t stream = h->stream;
-  int n_env_launch = h->d.N;
-  if (group >= 0) {
-    if (group >= h->n_groups || !h->gstreams) return PGD_ERR_ARG;
-    n_env_launch = h->d.N / h->n_groups;
-    dv.unit_off = group * n_env_launch / h->d.epw;
-    stream = h->gstreams[group];
-  }
+  dv.obs_g = observers_per_round(h->d, h->d.A, 1, 0, STEP_MINB_WORDS);  // fused multi-agent observation: what the step's LDS holds
+  EnvGroup g;  // the blocks and the stream of the env group
+  { int rc = env_group(h, group, g); if (rc) return rc; }
+  dv.unit_off = g.first / h->d.epw;
   const bool marl = (h->d.cfg.marl_flags & PGD_MA_ENABLED) != 0;
   // single-agent engines fuse the row into the wave that stepped the env; multi-agent engines append observe_env_body
   // (all rows of the env) when its per-beam minima fit the step's LDS -- one launch per step either way
@@ -2007,62 +2082,9 @@ static int step_impl(pgd_handle h, const float* d_actions, float* d_obs, float* 
   hipEvent_t* pe = (prof || g_open || g_close) ? &(*h->prof_ev)[(size_t)h->prof_n * 3] : nullptr;
   const bool timing = h->step_timing && !prof && !grouped && group < 0;
   if (prof || timing || g_open) HIPCHK(hipEventRecord((prof || g_open) ? pe[0] : h->ev0, h->stream));
-  int blocks = (n_env_launch + h->d.epw - 1) / h->d.epw;
+  int blocks = (g.count + h->d.epw - 1) / h->d.epw;
   if (marl && h->d.epw != 1) return PGD_ERR_STATE;  // the multi-agent tail needs the env in one wave (V >= 33 or SUB split)
-  void (*kern)(PgdDev, const float*, float*, uint8_t*, uint32_t*, float*, PgdCold) = k_step<false, false, false>;
-  const char* kname = h->d.pack_obs ? "k_step: whole envs side by side in a wave, one vehicle per lane (throughput mode)"
-                                    : (h->d.epw == 1 ? "k_step: one env per wave" : "k_step: several envs per wave");
-  if (marl) {
-    kern = h->has_objects ? k_step<true, true, true> : k_step<true, true, false>;  // objects = toll booths
-    if (!h->has_objects && !h->no_fix && fix_config_matches(dv, true, FIXK_MARL) && dv.V == dv.A && dv.sub == WAVE / dv.A) {
-      kern = k_step<true, true, false, false, 1>;
-      kname = "k_step: one env per wave, specialised for the default multi-agent configuration";
-      const int seats = marl_fix_seats(dv);
-      if (seats == 40072) { kern = k_step<true, true, false, false, 40072>; kname = "k_step: one env per wave, specialised for the default multi-agent configuration with 40 agent seats x 72 beams"; }
-      if (seats == 44072) { kern = k_step<true, true, false, false, 44072>; kname = "k_step: one env per wave, specialised for the default multi-agent configuration with 44 agent seats x 72 beams"; }
-      if (seats == 8072) { kern = k_step<true, true, false, false, 8072>; kname = "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 72 beams"; }
-      if (seats == 8240) { kern = k_step<true, true, false, false, 8240>; kname = "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 240 beams"; }
-    }
-  }
-  else if (h->d.epw == 1) {
-    const pgd_config& c = h->d.cfg;
-    const bool std_obs = c.side_lasers == 0 && c.lane_line_lasers == 0 && !c.random_agent_model &&
-                         c.lidar_gaussian_noise <= 0.0f && c.lidar_dropout_prob <= 0.0f;
-    kern = h->has_objects ? k_step<true, false, true> : (std_obs ? k_step<true, false, false, true> : k_step<true, false, false>);
-    if (h->lk.obs) {  // (pgd_step_lane_keep checked lane_keep_in_step: the default configuration's instantiation with the policy in it)
-      kern = k_step<true, false, false, true, 1, true>;
-      kname = "k_step: one env per wave, specialised for the default single-agent configuration, scripted lane-keeping policy inside";
-    } else
-    if (h->has_objects && std_obs && !h->no_fix && fix_config_matches(dv, true, FIXK_SAFE)) {
-      kern = k_step<true, false, true, true, 4>;
-      kname = "k_step: one env per wave, specialised for the SafePGDriveEnv configuration (16 traffic + 40 object slots, run-time reward scheme)";
-    } else if (!h->has_objects && std_obs && !h->no_fix && fix_config_matches(dv, true, FIXK_NO_LIDAR)) {
-      kern = k_step<true, false, false, true, 3>;
-      kname = "k_step: one env per wave, specialised for the top-down envs' configuration (single agent, lidar off)";
-    } else
-    if (!h->has_objects && std_obs && !h->no_fix && fix_config_matches(dv, true)) {
-      kern = k_step<true, false, false, true, 1>;
-      kname = "k_step: one env per wave, specialised for the default single-agent configuration";
-    } else if (!h->has_objects && std_obs && !h->no_fix && fix_config_matches(dv, true, FIXK_GEOMETRY)) {
-      kern = k_step<true, false, false, true, 2>;
-      kname = "k_step: one env per wave, specialised for the default single-agent configuration with a run-time reward scheme";
-    }
-  }
-  else if (h->has_objects) kern = k_step<false, false, true>;
-  else if (!h->d.pack_obs && !h->no_fix && fix_config_matches(dv, false, FIXK_EGO_ONLY)) {
-    kern = k_step<false, false, false, false, 1>;
-    kname = "k_step: several envs per wave, specialised for the ego-only configuration without a lidar";
-  }
-  else if (h->d.pack_obs) {
-    const pgd_config& c = h->d.cfg;
-    const bool std_obs = c.side_lasers == 0 && c.lane_line_lasers == 0 && !c.random_agent_model &&
-                         c.lidar_gaussian_noise <= 0.0f && c.lidar_dropout_prob <= 0.0f;
-    if (std_obs) kern = k_step<false, false, false, true>;
-    if (std_obs && !h->no_fix && fix_config_matches(dv, false)) {
-      kern = k_step<false, false, false, true, 1>;
-      kname = "k_step: whole envs side by side in a wave (throughput mode), specialised for the default single-agent configuration";
-    }
-  }
+  const StepKernel sk = step_kernel(h);
   // many agent slots: the rows come from k_observe_env after the step; the state blocks of the rows that are due are k_step's
   const bool state_in_step = d_obs && !fuse && marl && state_in_step_ok(h);
   dv.state_rows = state_in_step ? d_obs : nullptr;
@@ -2071,23 +2093,23 @@ static int step_impl(pgd_handle h, const float* d_actions, float* d_obs, float* 
   float* obs_arg = fuse ? d_obs : (float*)nullptr;
   // a kernel built for this handle at run time takes the place of a GENERAL kernel only (the AOT instantiations are what it would be),
   // and only while the engine is what it was built for
-  const bool general = strstr(kname, "specialised") == nullptr || h->jit_force;  // (PGD_JIT_FORCE=1, A/B only: also in place of an AOT instantiation)
-  const bool use_jit = h->jit_fn && general && !marl && h->d.epw == 1 && !h->no_fix && !h->lk.obs && h->jit_obj == h->has_objects &&
+  const bool general = !sk.specialised || h->jit_force;  // (PGD_JIT_FORCE=1, A/B only: also in place of an AOT instantiation)
+  const bool use_jit = h->jit_fn && general && jit_geometry_ok(h) && !h->no_fix && !h->lk.obs && h->jit_obj == h->has_objects &&
                        h->jit_geom[0] == h->d.sub && h->jit_geom[1] == h->d.epw && h->jit_geom[2] == h->d.pack_obs &&
                        h->jit_geom[3] == h->d.use_imask;
   if (use_jit) {
     h->last_step_kernel = h->jit_name;
     void* kargs[] = {&dv, &d_actions, &d_reward, &d_done, &d_flags, &obs_arg, &cold_arg};
-    HIPCHK(hipModuleLaunchKernel(h->jit_fn, (unsigned)blocks, 1, 1, WAVE, 1, 1, 0, stream, kargs, nullptr));
+    HIPCHK(hipModuleLaunchKernel(h->jit_fn, (unsigned)blocks, 1, 1, WAVE, 1, 1, 0, g.stream, kargs, nullptr));
   } else {
-    h->last_step_kernel = kname;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE), 0, stream, dv, d_actions, d_reward, d_done, d_flags, obs_arg, cold_arg);
+    h->last_step_kernel = sk.name;
+    hipLaunchKernelGGL(sk.fn, dim3(blocks), dim3(WAVE), 0, g.stream, dv, d_actions, d_reward, d_done, d_flags, obs_arg, cold_arg);
   }
   HIPCHK(hipGetLastError());
   if (prof || g_close) HIPCHK(hipEventRecord(pe[1], h->stream));
   if (g_close) h->prof_n += 1;
   if (d_obs && !fuse) {
-    int rc = launch_observe(h, d_obs, marl ? d_flags : (const uint32_t*)nullptr, &dv, stream, n_env_launch, state_in_step);
+    int rc = launch_observe(h, d_obs, marl ? d_flags : (const uint32_t*)nullptr, &dv, g.stream, g.count, state_in_step);
     if (rc) return rc;
   }
   h->prof_fused = fuse;
@@ -2187,20 +2209,15 @@ int pgd_mlp_policy(pgd_handle h, int group, const float* d_obs, int obs_stride, 
   const size_t lds = mlp_lds_bytes(in_dim);
   if (lds > 65536) return PGD_ERR_ARG;
   HIPCHK(hipSetDevice(h->device));
-  hipStream_t stream = h->stream;
-  int rows = h->d.N * h->d.A, row0 = 0;
-  if (group >= 0) {  // the rows of one env group, on the group's stream (pgd_step_group's twin)
-    if (group >= h->n_groups || !h->gstreams) return PGD_ERR_ARG;
-    rows = (h->d.N / h->n_groups) * h->d.A;
-    row0 = group * rows;
-    stream = h->gstreams[group];
-  }
+  EnvGroup g;  // the rows of one env group (or all), on its stream (pgd_step_group's twin)
+  { int rc = env_group(h, group, g); if (rc) return rc; }
+  const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
   auto kern = final_tanh ? k_mlp_policy<true> : k_mlp_policy<false>;
   if (lds > 49152 && !h->mlp_attr[final_tanh ? 1 : 0]) {  // (per engine = per device: a process may hold engines on several GPUs)
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
     h->mlp_attr[final_tanh ? 1 : 0] = true;
   }
-  hipLaunchKernelGGL(kern, dim3((rows + MLP_ROWS - 1) / MLP_ROWS), dim3(WAVE * MLP_WAVES), lds, stream, d_obs, row0, rows, obs_stride, in_dim,
+  hipLaunchKernelGGL(kern, dim3((rows + MLP_ROWS - 1) / MLP_ROWS), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs, row0, rows, obs_stride, in_dim,
                      d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, out_cols, d_actions);
   HIPCHK(hipGetLastError());
   return PGD_OK;
@@ -2228,20 +2245,15 @@ int pgd_mlp_policy_prepared(pgd_handle h, int group, const float* d_obs, int obs
   const size_t lds = mlp_bf_lds_bytes(in_dim);
   if (lds > 65536) return PGD_ERR_ARG;
   HIPCHK(hipSetDevice(h->device));
-  hipStream_t stream = h->stream;
-  int rows = h->d.N * h->d.A, row0 = 0;
-  if (group >= 0) {
-    if (group >= h->n_groups || !h->gstreams) return PGD_ERR_ARG;
-    rows = (h->d.N / h->n_groups) * h->d.A;
-    row0 = group * rows;
-    stream = h->gstreams[group];
-  }
+  EnvGroup g;
+  { int rc = env_group(h, group, g); if (rc) return rc; }
+  const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
   auto kern = final_tanh ? k_mlp_policy_bf<true> : k_mlp_policy_bf<false>;
   if (lds > 49152 && !h->mlp_attr[2 + (final_tanh ? 1 : 0)]) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
     h->mlp_attr[2 + (final_tanh ? 1 : 0)] = true;
   }
-  hipLaunchKernelGGL(kern, dim3((rows + MLP_ROWS - 1) / MLP_ROWS), dim3(WAVE * MLP_WAVES), lds, stream, d_obs, row0, rows, obs_stride, in_dim,
+  hipLaunchKernelGGL(kern, dim3((rows + MLP_ROWS - 1) / MLP_ROWS), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs, row0, rows, obs_stride, in_dim,
                      reinterpret_cast<const uint4*>(d_prepared), d_actions);
   HIPCHK(hipGetLastError());
   return PGD_OK;
@@ -2250,13 +2262,9 @@ int pgd_mlp_policy_prepared(pgd_handle h, int group, const float* d_obs, int obs
 /* ---- run-time specialisation (pgdrive_amd/jit.py builds the code object with hipcc; see include/pgdrive_hip.h) -------------- */
 int pgd_step_geometry(pgd_handle h, int32_t* out12) {
   if (!h || !out12) return PGD_ERR_ARG;
-  const pgd_config& c = h->d.cfg;
-  const bool std_obs = c.side_lasers == 0 && c.lane_line_lasers == 0 && !c.random_agent_model && c.lidar_gaussian_noise <= 0.0f &&
-                       c.lidar_dropout_prob <= 0.0f;
-  const bool marl = (c.marl_flags & PGD_MA_ENABLED) != 0;
   const int v[12] = {h->d.N, h->d.A, h->d.T, h->d.V, h->d.D, h->d.NV, h->d.epw, h->d.sub, h->d.pack_obs, h->d.sstride, h->d.use_imask,
                      // bit 0: objects among the bodies; bit 1: default row layout; bit 2: the engine can take a run-time kernel at all
-                     (h->has_objects ? 1 : 0) | (std_obs ? 2 : 0) | ((!marl && h->d.epw == 1 && !h->d.pack_obs && h->have_scen) ? 4 : 0)};
+                     (h->has_objects ? 1 : 0) | (std_rows(h->d.cfg) ? 2 : 0) | ((jit_geometry_ok(h) && h->have_scen) ? 4 : 0)};
   for (int k = 0; k < 12; ++k) out12[k] = v[k];
   return PGD_OK;
 }
@@ -2272,8 +2280,7 @@ int pgd_set_step_module(pgd_handle h, const char* code_object_path, int built_wi
     h->jit_mod = nullptr;
   }
   if (!code_object_path) return PGD_OK;  // (null: back to the library's own kernels)
-  const bool marl = (h->d.cfg.marl_flags & PGD_MA_ENABLED) != 0;
-  if (marl || h->d.epw != 1 || h->d.pack_obs) return PGD_ERR_STATE;
+  if (!jit_geometry_ok(h)) return PGD_ERR_STATE;
   hipModule_t mod = nullptr;
   if (hipModuleLoad(&mod, code_object_path) != hipSuccess) { (void)hipGetLastError(); return PGD_ERR_HIP; }
   char name[160];
@@ -2300,15 +2307,6 @@ int pgd_describe_step(pgd_handle h, char* buf, int cap) {
   snprintf(buf, (size_t)cap, "%s%s", h->last_step_kernel ? h->last_step_kernel : "",
            h->left_pack_mode ? " [throughput mode switched off by pgd_set_groups: the group size is not a whole number of three-env waves]" : "");
   return PGD_OK;
-}
-
-// the engines whose step kernel has an instantiation with the scripted policy inside: the reference's default single-agent configuration
-static bool lane_keep_in_step(const pgd_engine* h) {
-  const pgd_config& c = h->d.cfg;
-  const bool std_obs = c.side_lasers == 0 && c.lane_line_lasers == 0 && !c.random_agent_model && c.lidar_gaussian_noise <= 0.0f &&
-                       c.lidar_dropout_prob <= 0.0f;
-  return h->d.epw == 1 && !(c.marl_flags & PGD_MA_ENABLED) && !h->has_objects && std_obs && !h->no_fix && !h->no_fuse &&
-         fix_config_matches(h->d, true);
 }
 
 int pgd_step_lane_keep(pgd_handle h, float k_lat, float k_head, float v_target_kmh, float noise, uint32_t tick, float* d_obs,
