@@ -424,6 +424,39 @@ int pgd_observe_topdown(pgd_handle h, float* d_img /*[N,R,R,C]*/);
  * section 14).  `d_img` 16-byte aligned.  One call advances the pose history like pgd_observe_topdown: call ONE of the two per step. */
 int pgd_observe_topdown_u8(pgd_handle h, uint8_t* d_img /*[N,R,R,C]*/);
 
+/* Top-down scene rendering: env.render(mode="top_down") (envs/base_env.py:240-248, 463-468) -> TopDownRenderer
+ * (obs/top_down_renderer.py) as kernels over the state on the device, the frames of many envs in one launch.  Each env's whole map
+ * on a film_w x film_h RGB film: lane lines on a light background, every controlled agent as a box in its own colour with a fading
+ * trail of its last num_stack rendered frames, the newest frame outlined, a red disk where an agent finished.  Frames [n][H][W][3]
+ * uint8 (pygame.surfarray.array3d of the reference's Surface is [W][H][3]: the same image transposed (1, 0, 2)).  pygame's
+ * rasterisation is unpinned; the exact definition, the film geometry and the deviations (trails and deads cleared at an env's reset,
+ * dead list capped at 256, colours from a counter hash, broken lines by the map's boxes, analytic pixel rules):
+ * pgdrive_amd/csrc/pgd_render.h.  Works in every engine mode (one or several envs per wave, throughput mode, multi-agent). */
+typedef struct pgd_render_config {
+  int32_t film_w, film_h;   /* film_size (top_down_renderer.py:128): 1000 x 1000; each in 16 .. 16384 */
+  int32_t num_stack;        /* 15: rendered frames kept per env (1 .. 64; num_stack * V + 256 <= 2048) */
+  int32_t history_smooth;   /* 0: every kept frame is painted; k > 0: only frames whose age i (1 = newest) is a multiple of k */
+  int32_t light_background; /* 1: the background inverted (255 - x): black lines on white (the reference's default) */
+  int32_t road_rgb[3];      /* road_color (255, 255, 255): the lane lines before the inversion */
+  int32_t draw_traffic;     /* 0: controlled agents only (the reference).  1 (NOT a reference option): also the IDM traffic in
+                               (100, 200, 255) and the traffic objects in (200, 0, 150), VehicleGraphics.BLUE / PURPLE */
+} pgd_render_config;
+/* The agent colours: seaborn's "colorblind" palette (seaborn/palettes.py SEABORN_PALETTES, the table base_vehicle.py:151-155
+ * draws `top_down_color` from) as 8-bit values.  Agent k of env e gets entry pgd_rng(seed, env_base + e, 0x7e4d0c01, k) % 10 (the
+ * counter hash of the device RNG streams), for life. */
+#define PGD_RENDER_PALETTE                                                                                                    \
+  {{1, 115, 178}, {222, 143, 5}, {2, 158, 115}, {213, 94, 0}, {204, 120, 188}, {202, 145, 97}, {251, 175, 228}, {148, 148, 148}, \
+   {236, 225, 51}, {86, 180, 233}}
+/* h_film_geom: HOST [n_maps][3] doubles (scaling [px / m], ox, oy [m]) per uploaded map, the film transform of the map's
+ * RoadNetwork.get_bounding_box() (pgdrive_amd/render.py computes it from the lane descriptions).  Draws every map's background once,
+ * allocates the per-env history, synchronises the engine stream.  An upload of maps or scenarios afterwards requires a new enable. */
+int pgd_render_enable(pgd_handle h, const pgd_render_config* cfg, const double* h_film_geom);
+/* Appends the present state of the listed envs (h_env_ids HOST, NULL = all N, in order; no env twice) to their histories and
+ * draws their frames into d_frames [n][film_h][film_w][3] (16-byte aligned).  Asynchronous on the engine stream, like pgd_reset: not
+ * ordered against the streams of env groups.  Only the rendered envs advance their history. */
+int pgd_render_topdown(pgd_handle h, const int32_t* h_env_ids, int n, uint8_t* d_frames);
+int pgd_render_palette(uint8_t* out /* [10][3] */);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * Per-step gather by direct peer writes (multi-GPU, one process per GPU).  The reference has no distributed layer (one env
  * per process, engine_utils.py:8-15); BASELINE.json's north star shards the envs over the GPUs of a node with one gather of

@@ -27,6 +27,12 @@ class TopDownConfig(C.Structure):
                 ("frame_skip", C.c_int32), ("mode", C.c_int32)]
 
 
+class RenderConfig(C.Structure):
+    """pgd_render_config; pgdrive_amd/render.py fills it from the arguments of env.render(mode="top_down", ...)."""
+    _fields_ = [("film_w", C.c_int32), ("film_h", C.c_int32), ("num_stack", C.c_int32), ("history_smooth", C.c_int32),
+                ("light_background", C.c_int32), ("road_rgb", C.c_int32 * 3), ("draw_traffic", C.c_int32)]
+
+
 def make_topdown_config(resolution=84, distance=30.0, frame_stack=3, post_stack=5, frame_skip=5, mode=0):
     """mode 1: the single RGB frame of TopDownObservation (obs/top_down_obs.py; reference default resolution 200)."""
     return TopDownConfig(int(resolution), float(distance), int(frame_stack), int(post_stack), int(frame_skip), int(mode))

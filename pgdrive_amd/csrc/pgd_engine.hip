@@ -1445,6 +1445,7 @@ struct pgd_engine {
   int prof_cap, prof_n, prof_stride, prof_tick;
   bool prof_grouped;
   struct pgd_topdown_state* topdown;  // top-down observation (pgd_topdown.h), null until pgd_topdown_enable
+  struct pgd_render_state* render;    // top-down scene rendering (pgd_render.h), null until pgd_render_enable
   int n_groups;          // env groups of pgd_set_groups (1 = none)
   hipStream_t* gstreams; // [n_groups] internal streams
   bool derive_pending;  // records were written through the ABI or the tables changed: k_derive has to run
@@ -1578,6 +1579,9 @@ static int obs_rows_forget(pgd_engine* h, hipStream_t stream) {
 }
 
 static void topdown_free(pgd_engine* h);
+static void render_free(pgd_engine* h);
+static void render_mark_stale(pgd_engine* h);
+static int render_forget(pgd_engine* h, const int32_t* d_env, int n);
 
 template <typename T>
 static int upload(T** dst, const T* src, size_t n, hipStream_t st) {
@@ -1616,6 +1620,7 @@ static void topdown_mark_dirty(pgd_engine* h);
 static int build_reset_image(pgd_engine* h) {
   if (!h->have_maps || !h->have_scen) return PGD_OK;
   topdown_mark_dirty(h);  // the top-down rasters follow the tables
+  render_mark_stale(h);   // and so do the rendered backgrounds (pgd_render_enable again)
   // the route context cached in the records of running envs refers to the tables: rebuild it after every upload
   h->derive_pending = true;
   { int rc = derive_records(h); if (rc) return rc; }
@@ -2041,6 +2046,7 @@ int pgd_reset(pgd_handle h, const int32_t* env_ids, const int32_t* scen_ids, int
   int blocks = (n + h->d.epw - 1) / h->d.epw;
   hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(WAVE), 0, h->stream, h->d, d_env, h->d_ids + h->d.N, n);
   HIPCHK(hipGetLastError());
+  { int rc = render_forget(h, d_env, n); if (rc) return rc; }  // rendered trails and deads end with the episode
   if (d_obs) return launch_observe(h, d_obs, nullptr);
   return PGD_OK;
 }
@@ -2571,6 +2577,7 @@ int pgd_destroy(pgd_handle h) {
     free(h->gstreams);
   }
   topdown_free(h);
+  render_free(h);
   delete h->h_maps;
   delete h->h_scen;
   if (h->own_stream) (void)hipStreamDestroy(h->stream);
@@ -2582,5 +2589,6 @@ int pgd_destroy(pgd_handle h) {
 }  // extern "C"
 
 #include "pgd_topdown.h"
+#include "pgd_render.h"
 #include "pgd_gather.h"
 #endif  // !PGD_JIT

@@ -40,6 +40,9 @@ _SIGS = {
     "pgd_topdown_enable": (C.c_int, [C.c_void_p, C.POINTER(_abi.TopDownConfig)]),
     "pgd_observe_topdown": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pgd_observe_topdown_u8": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pgd_render_enable": (C.c_int, [C.c_void_p, C.POINTER(_abi.RenderConfig), C.c_void_p]),
+    "pgd_render_topdown": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pgd_render_palette": (C.c_int, [C.c_void_p]),
     "pgd_set_groups": (C.c_int, [C.c_void_p, C.c_int]),
     "pgd_step_group": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "pgd_group_stream": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
@@ -362,6 +365,43 @@ class Engine:
         else:
             _chk(self.L.pgd_observe_topdown(self.h, C.c_void_p(img.data_ptr())), "pgd_observe_topdown")
         return img
+
+    # -- top-down scene rendering (env.render(mode="top_down"), obs/top_down_renderer.py) --------------------------------------------
+    def enable_render(self, cfg=None):
+        """Create the renderer (pgd_render_enable): `cfg` = pgdrive_amd.render.parse_kwargs' settings or a _abi.RenderConfig (None: the
+        reference's defaults).  The film of every map is fitted to its road network's bounding box (pgdrive_amd/render.py)."""
+        from . import render
+        if cfg is None or isinstance(cfg, dict):
+            cfg = render.make_config(render.parse_kwargs("top_down", cfg or {}))
+        render.check_capacity(cfg.num_stack, self.V)
+        geom = np.array([render.film_geometry(d, cfg.film_w, cfg.film_h) for d in self.bank.descs], dtype=np.float64)
+        assert len(geom) == len(self.bank.maps)
+        self.render_cfg = cfg
+        self.film_geom = geom
+        _chk(self.L.pgd_render_enable(self.h, C.byref(cfg), _np_p(np.ascontiguousarray(geom))), "pgd_render_enable")
+
+    def render_topdown(self, env_ids=None, out=None):
+        """Frames of the listed envs (None: all) as a cuda uint8 tensor [n, film_h, film_w, 3] (`out`, else a new tensor); appends the
+        present state to the envs' trails.  Asynchronous on the engine's stream (the caller's current stream, as for step)."""
+        t = self.torch
+        ids = None if env_ids is None else np.ascontiguousarray(np.asarray(env_ids, dtype=np.int64).reshape(-1), dtype=np.int32)
+        n = self.N if ids is None else len(ids)
+        shape = (n, self.render_cfg.film_h, self.render_cfg.film_w, 3)
+        if out is None:
+            out = t.empty(shape, dtype=t.uint8, device=self.device)
+        assert out.is_cuda and out.dtype == t.uint8 and out.is_contiguous() and tuple(out.shape) == shape
+        cur = t.cuda.current_stream(self.device).cuda_stream
+        if cur != self._bound_stream:
+            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
+            self._bound_stream = cur
+        _chk(self.L.pgd_render_topdown(self.h, _np_p(ids), n, C.c_void_p(out.data_ptr())), "pgd_render_topdown")
+        return out
+
+    def render_palette(self):
+        """The ten agent colours (pgd_render_palette): uint8 [10, 3]."""
+        p = np.zeros((10, 3), dtype=np.uint8)
+        _chk(self.L.pgd_render_palette(_np_p(p)), "pgd_render_palette")
+        return p
 
     # -- asynchronous env groups ----------------------------------------------------------------------------------------
     def set_groups(self, n_groups):

@@ -165,6 +165,12 @@ class MultiAgentRoundaboutVecEnv:
     def group_slice(self, g):
         return self.engine.group_slice(g)
 
+    def render(self, mode="top_down", env_ids=None, **kwargs):
+        """BaseEnv.render(mode="top_down") for the listed envs (None: all): every agent with its trail, a red disk where an agent
+        finished; a cuda uint8 tensor [n, film_h, film_w, 3].  Settings as PGDriveVecEnv.render (first call only)."""
+        from . import render
+        return render.vec_render(self, mode, env_ids, kwargs)
+
     def slot_table(self):
         """Host copy of (status, agent id) per slot: ([N, A] int, [N, A] int)."""
         f, i, _ = self.engine.get_state()
@@ -450,6 +456,10 @@ class MultiAgentRoundaboutEnv(EnvBase):  # (gym.Env when gym is importable, like
             for k in list(d.keys()):
                 d[k] = True
         return o, r, d, info
+
+    def render(self, mode="top_down", **kwargs):
+        """BaseEnv.render(mode="top_down"): numpy uint8 [film_h, film_w, 3] (MultiAgentRoundaboutVecEnv.render)."""
+        return self.vec.render(mode, **kwargs)[0].cpu().numpy()
 
     def close(self):
         self.vec.close()

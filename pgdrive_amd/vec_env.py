@@ -307,6 +307,15 @@ class PGDriveVecEnv:
             return self.engine.observe_topdown(), rew.view(-1), done.view(-1), flags.view(-1)
         return obs.view(self.num_envs, self.obs_dim), rew.view(-1), done.view(-1), flags.view(-1)
 
+    def render(self, mode="top_down", env_ids=None, **kwargs):
+        """BaseEnv.render(mode="top_down") (base_env.py:240-248, 463-468) for the listed envs (None: all): the whole map of each env
+        with its agent(s) and their trails, a cuda uint8 tensor [n, film_h, film_w, 3] (pgdrive_amd/csrc/pgd_render.h).  The first
+        call creates the renderer from its kwargs (film_size, num_stack, history_smooth, light_background, road_color, and
+        draw_traffic=True to draw the IDM traffic and traffic objects too -- the reference shows the ego only); later kwargs are
+        ignored.  Only the rendered envs advance their trails."""
+        from . import render
+        return render.vec_render(self, mode, env_ids, kwargs)
+
     # -- asynchronous env groups (pgd_set_groups / pgd_step_group; double-buffered sampling: the policy of one group runs while the other
     # steps -- bench.py's closed-loop rows, examples/fused_policy_rollout.py).  Lidar observations only (the top-down image is one launch
     # over every env of the handle).
