@@ -73,6 +73,15 @@ def lib():
         L.orc_step_range.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.orc_step_mt.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.orc_run_mt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        L.orc_margins_enable.argtypes = [C.c_void_p, C.c_int]
+        L.orc_get_margins.argtypes = [C.c_void_p, C.c_void_p]
+        L.orc_beam_margin.restype = C.c_double
+        L.orc_beam_margin.argtypes = [C.c_void_p] + [C.c_int] * 5
+        L.orc_beam_incidence.restype = C.c_double
+        L.orc_beam_incidence.argtypes = [C.c_void_p] + [C.c_int] * 5
+        L.orc_beam_body_dist.restype = C.c_double
+        L.orc_beam_body_dist.argtypes = [C.c_void_p] + [C.c_int] * 4
+        L.orc_neighbour_slot.argtypes = [C.c_void_p] + [C.c_int] * 3
         L.orc_rng.restype = C.c_uint32
         L.orc_rng.argtypes = [C.c_uint32] * 4
         for name in ("orc_upload_maps", "orc_upload_scenarios", "orc_destroy", "orc_get_state", "orc_set_state",
@@ -185,6 +194,33 @@ class Oracle:
         i = np.ascontiguousarray(i, dtype=np.int32)
         ei = np.ascontiguousarray(ei, dtype=np.int32)
         self.L.orc_set_state(self.h, _p(f), _p(i), _p(ei))
+
+    # decision margins (pgd_oracle.h): MG[class] indexes the planes of margins(); beam margins are computed on demand
+    MG = dict(BEAM=0, CONTACT=1, LANE=2, LEADER=3, NEIGHBOUR=4, ROUTE=5, CONTACT_LEVER=6)
+
+    def enable_margins(self, on=True):
+        assert self.L.orc_margins_enable(self.h, int(on)) == 0
+        self.margins_on = bool(on)
+
+    def margins(self):
+        """[7, N, V] float64: per class (MG) the smallest margin of a decision taken for the slot in the last step; inf = none."""
+        out = np.full((len(self.MG), self.N, self.V), np.inf, dtype=np.float64)
+        assert self.L.orc_get_margins(self.h, _p(out)) == 0, "enable_margins() first"
+        return out
+
+    def beam_margin(self, env, agent, fan, beam, slot=None):
+        """fan: 0 lidar, 1 side detector, 2 lane-line detector; slot: the vehicle the fan belongs to (default: the agent)."""
+        return float(self.L.orc_beam_margin(self.h, int(env), int(agent), int(agent if slot is None else slot), int(fan), int(beam)))
+
+    def beam_incidence(self, env, agent, fan, beam, slot=None):
+        """|sin| of the angle between the beam and the surface it ends on (1 = head-on, or no hit)."""
+        return float(self.L.orc_beam_incidence(self.h, int(env), int(agent), int(agent if slot is None else slot), int(fan), int(beam)))
+
+    def beam_body_dist(self, env, slot, body, beam):
+        return float(self.L.orc_beam_body_dist(self.h, int(env), int(slot), int(body), int(beam)))
+
+    def neighbour_slot(self, env, agent, rank):
+        return int(self.L.orc_neighbour_slot(self.h, int(env), int(agent), int(rank)))
 
     def close(self):
         if self.h:

@@ -36,6 +36,17 @@ int orc_run_mt(orc_handle h, int threads, int steps, const float* actions, int n
 int orc_step_range(orc_handle h, int e0, int e1, const float* actions, double* obs, double* reward, uint8_t* done,
                    uint32_t* flags);
 uint32_t orc_rng(uint32_t seed, uint32_t a, uint32_t b, uint32_t c);
+/* decision margins (see pgd_oracle.c): classes of discrete decisions; orc_get_margins gives, per class, env and slot, the smallest amount
+ * [m; rad for pure angle tests, km/h for the IDM speed tests] by which a comparison of that class taken for the slot in the last step
+ * (or in the reset / observation since) was away from equality.  BEAM margins are computed on demand by orc_beam_margin; its plane
+ * stays +inf.  Plane CONTACT_LEVER: the lever [m] of the pair that set the CONTACT margin. */
+enum { ORC_MG_BEAM = 0, ORC_MG_CONTACT, ORC_MG_LANE, ORC_MG_LEADER, ORC_MG_NEIGHBOUR, ORC_MG_ROUTE, ORC_MG_CONTACT_LEVER, ORC_MG_PLANES };
+int orc_margins_enable(orc_handle h, int on);
+int orc_get_margins(orc_handle h, double* out /*[ORC_MG_PLANES][N][V]*/);
+double orc_beam_margin(orc_handle h, int e, int agent, int slot, int fan, int beam);
+double orc_beam_incidence(orc_handle h, int e, int agent, int slot, int fan, int beam);
+double orc_beam_body_dist(orc_handle h, int e, int slot, int body, int beam);
+int orc_neighbour_slot(orc_handle h, int e, int agent, int rank);
 int orc_topdown_enable(orc_handle h, const pgd_topdown_config* c);
 int orc_observe_topdown(orc_handle h, double* img /*[N,R,R,C]*/);
 #endif

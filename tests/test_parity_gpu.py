@@ -41,12 +41,208 @@ def _engines(descs, n_envs, n_maps=8, **kw):
                                                  "idm_agent", "idm_steer_lag") if k in kw})
     eng = Engine(cfg, mb, sb)
     ora = orc.Oracle(cfg, mb, sb)
+    ora.enable_margins()  # every mismatch the tests tolerate is checked against the oracle's decision margins (tests/util.py)
     ora.map_bank, ora.scen_bank = mb, sb
     return torch, eng, ora, cfg
 
 
+def _fan_layout(cfg):
+    """The ray-cast columns of an observation row: (first column, beams, fan, neighbour rank) with fan 0 = lidar, 1 = side detector,
+    2 = lane-line detector (oracle/pgd_oracle.h orc_beam_margin) and rank -1 = the agent's own fan, k = the fan inside the state vector
+    of neighbour row k (MA_OTHERS_STATE); and the row width the layout is for."""
+    nl, ks, km = cfg.num_lasers, cfg.side_lasers, cfg.lane_line_lasers
+    toll = bool(cfg.marl_flags & _abi.MA_TOLLGATE)
+    sl = (ks or 2) + 6 + km + (2 if cfg.random_agent_model else 0) + (0 if toll else 10)
+    others_state = bool(cfg.marl_flags & _abi.MA_OTHERS_STATE)
+    D = sl + (sl if others_state else 4) * cfg.num_others + nl + (2 if toll else 0)
+    out = []
+    for rank in [-1] + (list(range(cfg.num_others)) if others_state else []):
+        off = sl * (rank + 1)
+        if ks:
+            out.append((off, ks, 1, rank))
+        if km:
+            out.append((off + (ks or 2) + 6, km, 2, rank))
+    if nl:
+        out.append((D - (2 if toll else 0) - nl, nl, 0, -1))  # TollGateObservation appends its two floats BEHIND the lidar
+    return out, D
+
+
+def _admit_beams(eng, ora, ties, where, layout, lead_tie=None, diff=None):
+    """`where`: (env, agent, column) of ray-cast values that differ by more than OBS_TOL (`diff`: by how much).  A beam is a tie only
+    where the oracle's geometry says so:
+      * its BEAM margin (a box corner / circle / range end / broad-phase radius / the origin on a boundary within eps of the beam, up
+        to where the beam ends) is admissible;
+      * or the beam slides along the face it ends on: OBS_TOL is SURVEY 8c's 0.5 mm displacement of the geometry for a beam that meets
+        its surface head-on; at an angle phi the same displacement moves the reading 1 / sin(phi) times as far (found by
+        tests/test_ties_cpu.py: 1 fp32 ulp of pose, 1.5e-5 m, moves a beam that meets a rear face at 0.02 rad by 1.3 mm).  Such a beam is
+        admitted where its difference, taken normal to the surface, keeps the tolerance: diff * sin(phi) <= OBS_TOL;
+      * or, for lidar beams, it passes within the distance a vehicle with a verified LEADER tie can have moved (another acceleration
+        on the two sides: at most g * T^2 / 2, brake limited by friction <= 1 in dynamics()) of that vehicle.
+    Returns the admitted ones as a bool array; everything else stays in the numeric comparison and fails there."""
+    cfg = eng.cfg
+    ranges = {0: cfg.lidar_dist, 1: cfg.side_dist, 2: cfg.lane_line_dist}
+    ok = np.zeros(len(where), dtype=bool)
+    T = float(cfg.dt) * cfg.decision_repeat
+    shift = 0.5 * 9.81 * T * T
+    for k, (e, a, col) in enumerate(where):
+        start, n, fan, rank = next(x for x in layout if x[0] <= col < x[0] + x[1])
+        slot = a if rank < 0 else ora.neighbour_slot(e, a, rank)
+        if slot < 0:
+            continue
+        m = ora.beam_margin(e, a, fan, col - start, slot)
+        sin_phi = ora.beam_incidence(e, a, fan, col - start, slot) if diff is not None else 1.0
+        if diff is not None and diff[k] * sin_phi <= OBS_TOL:  # (first: what it explains is no near-tie and is listed apart)
+            ok[k] = True
+            ties.add("BEAM_SLIDE", diff[k] * sin_phi * ranges[fan], dict(env=int(e), agent=int(a), fan=fan, beam=int(col - start), slide_sin=sin_phi))
+        elif util.admissible("BEAM", m, ranges[fan]):
+            ok[k] = True
+            ties.add("BEAM", m, dict(env=int(e), agent=int(a), fan=fan, beam=int(col - start)))
+        elif fan == 0 and lead_tie is not None and lead_tie[e].any():
+            for body in np.nonzero(lead_tie[e])[0]:
+                dist = ora.beam_body_dist(e, slot, int(body), col - start)
+                if body != slot and dist < shift + util.tie_eps("BEAM", ranges[0]):
+                    ok[k] = True
+                    ties.add("LEADER", dist, dict(env=int(e), agent=int(a), beam=int(col - start), moved_body=int(body)))
+                    break
+    return ok
+
+
+def _beam_flagged_sample(ora, ties, o_obs, layout, rng, k=64):
+    """Share of compared beams the BEAM predicate WOULD flag, estimated on k random lidar beams per step (must stay small: the predicate
+    may not degenerate into 'everything is a tie'; bounded at 1 % by tests/test_ties_cpu.py)."""
+    lid = [x for x in layout if x[2] == 0]
+    if not lid:
+        return
+    start, n = lid[0][0], lid[0][1]
+    N, A = o_obs.shape[:2]
+    for e, a, b in zip(rng.integers(0, N, k), rng.integers(0, A, k), rng.integers(0, n, k)):
+        if o_obs[e, a].any():  # (an empty agent seat has a zero row and no beams)
+            ties.sampled += 1
+            ties.flagged += bool(util.admissible("BEAM", ora.beam_margin(e, a, 0, b), ora.cfg.lidar_dist))
+
+
+def _flag_ties(eng, stats, same, mg):
+    """Rows whose done / flags differ: a tie (stats["flag_ties"]) only where a CONTACT / ROUTE / LANE decision of that agent was a near-tie
+    in the oracle, else stats["flag_mismatch"] (== 0 in every test)."""
+    ties = stats["ties"]
+    A = eng.cfg.num_agents
+    flag_tie = ~same & util.admitted_slots(mg, ("CONTACT", "ROUTE", "LANE"))[:, :A]
+    for cls in ("CONTACT", "ROUTE", "LANE"):
+        ties.add_slots(cls, ~same & util.admitted_slots(mg, (cls,))[:, :A], mg)
+    stats["flag_ties"] = stats.get("flag_ties", 0) + int(flag_tie.sum())
+    stats["flag_mismatch"] += int((~same & ~flag_tie).sum())
+    for e, a in np.argwhere(~same & ~flag_tie):
+        ties.reject("flags", dict(env=int(e), agent=int(a), margins={c: float(mg[util.MG[c], e, a]) for c in ("CONTACT", "ROUTE", "LANE")}))
+    return flag_tie
+
+
+# which near-tie can explain a differing integer field of a slot (oracle/pgd_oracle.c: where each is written)
+_INT_FIELD_CLASSES = dict(LANE=("LANE",), CK0=("ROUTE", "LANE"), CK1=("ROUTE", "LANE"), RLANE=("LANE", "LEADER"), TIMER=("LEADER", "LANE"),
+                          VFLAGS=("CONTACT", "LANE"), STATUS=("LANE", "CONTACT", "ROUTE"), SPAWN=("ROUTE", "CONTACT"))
+
+
+def _int_ties(gi, i, gei, ei, mg, stats, flag_tie=None):
+    """Integer state (status / lanes / checkpoints / timers / counters) that differs after one teacher-forced step.  A slot is a tie where
+    EVERY differing field has a near-tie of a class that writes it (_INT_FIELD_CLASSES): LANE (the lane pick feeds everything else of the
+    slot, off-lane removal), CONTACT (line / crash bits of SI_VFLAGS), ROUTE (checkpoints, arrival, respawn place), LEADER (routing
+    lane / timer of an IDM vehicle).  Discrete outcomes cascade inside an env within the step (an episode end resets every slot, a
+    finish frees a seat for a respawn, the ego's lane triggers traffic): a differing slot without a near-tie of its own is a tie only
+    if the same env has a verified one (a differing slot or a differing done / flags row).  Returns (ties, mismatches): slots + env
+    records."""
+    ties = stats["ties"]
+    bad = (gi != i).any(axis=0)
+    own = bad.copy()
+    for name, k in _abi.SI.items():
+        differs = gi[k] != i[k]
+        adm = util.admitted_slots(mg, _INT_FIELD_CLASSES[name])
+        own &= ~differs | adm
+        for cls in _INT_FIELD_CLASSES[name]:
+            ties.add_slots(cls, differs & util.admitted_slots(mg, (cls,)), mg)
+    env_ok = own.any(axis=1)
+    if flag_tie is not None:
+        env_ok |= flag_tie.any(axis=1)
+    bad_env = (gei != ei).any(axis=0)
+    n_bad = int(bad.sum()) + int(bad_env.sum())
+    n_tie = int((bad & env_ok[:, None]).sum()) + int((bad_env & env_ok).sum())
+    for e, s_ in np.argwhere(bad & ~env_ok[:, None]):
+        ties.reject("int_state", dict(env=int(e), slot=int(s_), fields=[k for k, v in _abi.SI.items() if gi[v, e, s_] != i[v, e, s_]],
+                                      margins={c: float(mg[util.MG[c], e, s_]) for c in ("LANE", "CONTACT", "ROUTE", "LEADER")}))
+    stats["int_ties"] = stats.get("int_ties", 0) + n_tie
+    stats["int_mismatch"] = stats.get("int_mismatch", 0) + n_bad - n_tie
+    return n_tie, n_bad - n_tie
+
+
+def _compare_rows(eng, ora, stats, g_obs, o_obs, same, mg):
+    """The observation rows of one step (float64 arrays [N, A, D]) where the discrete outcome agrees (`same`): non-ray columns into
+    stats["obs"] / ["obs_state"]; ray-cast columns over OBS_TOL into stats["grazing"] / ["det_grazing"] if _admit_beams admits them,
+    else into stats["obs"] as well."""
+    ties = stats.setdefault("ties", util.Ties(os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0]))
+    layout, D = _fan_layout(eng.cfg)
+    assert D == g_obs.shape[2]
+    nl = eng.cfg.num_lasers
+    if nl:
+        lo = [x for x in layout if x[2] == 0][0][0]
+        ties.beams += int(same.sum()) * nl
+        ties.hits += int((o_obs[same][:, lo:lo + nl] < 1.0).sum())
+        _beam_flagged_sample(ora, ties, o_obs, layout, ties.rng)
+    # numeric comparison only where the discrete outcome agrees (a flipped flag changes reward / reset / obs wholesale)
+    if same.any():
+        dfull = np.where(same[:, :, None], np.abs(g_obs - o_obs), 0.0)
+        fan = np.zeros(D, dtype=bool)  # ray-cast columns: side fan, lane-line fan, lidar
+        lidar = np.zeros(D, dtype=bool)
+        for start, n, kind, rank in layout:
+            fan[start:start + n] = True
+            lidar[start:start + n] = kind == 0
+        stats["obs"] = max(stats["obs"], float(dfull[:, :, ~fan].max()))
+        stats["obs_state"] = max(stats.get("obs_state", 0.0), float(dfull[:, :, ~fan].max()))  # the non-ray columns on their own
+        # a beam grazing a box corner can flip hit <-> miss between fp32 and fp64 (the slab test compares two nearly equal
+        # parameters): such a beam is a tie only if the oracle's geometry confirms it; ties are counted and bounded by the callers,
+        # every other beam must agree to OBS_TOL
+        over = np.argwhere((dfull > OBS_TOL) & fan[None, None, :])
+        if len(over):
+            lead_tie = None
+            if eng.cfg.num_traffic or eng.cfg.idm_agent:
+                lead_tie = util.idm_tie(eng.get_state()[0], ora.get_state()[0], mg)
+            ok = _admit_beams(eng, ora, ties, over, layout, lead_tie, diff=dfull[over[:, 0], over[:, 1], over[:, 2]])
+            stats["beams_not_admitted"] = stats.get("beams_not_admitted", 0) + int((~ok).sum())
+            for (e, a, col), adm in zip(over, ok):
+                if not adm:  # a finding: kept for the report (and it stays in stats["obs"])
+                    ties.reject("beam", dict(env=int(e), agent=int(a), column=int(col), engine=float(g_obs[e, a, col]), oracle=float(o_obs[e, a, col])))
+                if adm:
+                    dfull[e, a, col] = 0.0
+                    key = ("grazing", "beams") if lidar[col] else ("det_grazing", "det_beams")
+                    stats[key[0]] = stats.get(key[0], 0) + 1
+        n_rows = int(same.sum())
+        if nl:
+            stats["beams"] = stats.get("beams", 0) + n_rows * nl
+            stats.setdefault("grazing", 0)
+        if int(fan.sum()) - nl:
+            stats["det_beams"] = stats.get("det_beams", 0) + n_rows * (int(fan.sum()) - nl)
+            stats.setdefault("det_grazing", 0)
+        stats["obs"] = max(stats["obs"], float(dfull[:, :, fan].max()) if fan.any() else 0.0)
+
+
+def _check_reset_rows(eng, ora, g0, o0, allowance, name="reset rows"):
+    """The first observation after a reset: values over OBS_TOL are allowed only in ray-cast columns whose BEAM margin (from the state
+    the oracle holds after the reset) admits them, and at most `allowance` of those."""
+    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    same = np.ones(o0.shape[:2], dtype=bool)
+    _compare_rows(eng, ora, stats, np.asarray(g0, dtype=np.float64), o0, same, ora.margins())
+    n_ties = stats.get("grazing", 0) + stats.get("det_grazing", 0)
+    print(name, "worst not admitted", stats["obs"], "admitted beams", n_ties, stats["ties"])
+    assert stats["obs"] < OBS_TOL and n_ties <= allowance, stats
+
+
 def _compare_step(torch, eng, ora, act, stats):
+    """One step on both sides.  Discrete outcomes must agree; what does not is a tie only where the oracle's margins say so
+    (tests/util.py: admissible): rows whose done / flags differ go to stats["flag_ties"] if a CONTACT / ROUTE / LANE decision of that
+    agent was a near-tie, else to stats["flag_mismatch"] (asserted == 0 by every caller); ray-cast values over OBS_TOL go to
+    stats["grazing"] / ["det_grazing"] if _admit_beams admits them, else they stay in stats["obs"]."""
+    if not getattr(ora, "margins_on", False):
+        ora.enable_margins()
+    ties = stats.setdefault("ties", util.Ties(os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0]))
     o_obs, o_rew, o_done, o_flags = ora.step(act)
+    mg = ties.mg = ora.margins()  # (callers take the step's margins from here)
     g_obs, g_rew, g_done, g_flags = eng.step(torch.from_numpy(act).to(eng.device))
     eng.sync()
     g_obs, g_rew = g_obs.cpu().numpy().astype(np.float64), g_rew.cpu().numpy().astype(np.float64)
@@ -56,52 +252,41 @@ def _compare_step(torch, eng, ora, act, stats):
                       ("n_crash_object", _abi.F_CRASH_OBJECT), ("n_crash_vehicle", _abi.F_CRASH_VEHICLE)):
         stats[name] = stats.get(name, 0) + int(((o_flags & bit) != 0).sum())
     stats["steps"] += same.size
-    stats["flag_mismatch"] += int((~same).sum())
-    # numeric comparison only where the discrete outcome agrees (a flipped flag changes reward / reset / obs wholesale)
+    ties.flag_tie = _flag_ties(eng, stats, same, mg)
+    _compare_rows(eng, ora, stats, g_obs, o_obs, same, mg)
     if same.any():
-        d = np.abs(g_obs - o_obs)[same]
-        nl = eng.cfg.num_lasers
-        ks, km = eng.cfg.side_lasers, eng.cfg.lane_line_lasers
-        fan = np.zeros(d.shape[1], dtype=bool)  # ray-cast columns: side fan, lane-line fan, lidar
-        fan[:ks] = True
-        fan[(ks or 2) + 6:(ks or 2) + 6 + km] = True
-        if eng.cfg.marl_flags & _abi.MA_OTHERS_STATE:  # the neighbours' state vectors carry their own detector fans
-            toll = bool(eng.cfg.marl_flags & _abi.MA_TOLLGATE)
-            sl = (ks or 2) + 6 + km + (2 if eng.cfg.random_agent_model else 0) + (0 if toll else 10)
-            for r_ in range(eng.cfg.num_others):
-                off = sl + r_ * sl
-                fan[off:off + ks] = True
-                fan[off + (ks or 2) + 6:off + (ks or 2) + 6 + km] = True
-        tail = 2 if (eng.cfg.marl_flags & _abi.MA_TOLLGATE) else 0  # TollGateObservation appends its two floats BEHIND the lidar
-        if nl:
-            fan[d.shape[1] - tail - nl:d.shape[1] - tail] = True
-        stats["obs"] = max(stats["obs"], float(d[:, ~fan].max()))
-        stats["obs_state"] = max(stats.get("obs_state", 0.0), float(d[:, ~fan].max()))  # the non-ray columns on their own
-        if ks + km:  # same treatment as the lidar beams below, plus origin-on-a-line-edge flips
-            n_det = int(fan.sum()) - (nl if nl else 0)
-            beams = d[:, fan][:, :n_det]
-            graze = beams > OBS_TOL
-            stats["det_beams"] = stats.get("det_beams", 0) + beams.size
-            stats["det_grazing"] = stats.get("det_grazing", 0) + int(graze.sum())
-            if (~graze).any():
-                stats["obs"] = max(stats["obs"], float(beams[~graze].max()))
-        if nl:
-            # a beam grazing a box corner can flip hit <-> miss between fp32 and fp64 (the slab test compares two
-            # nearly equal parameters); such flips are counted and bounded, every other beam must agree to OBS_TOL
-            beams = d[:, d.shape[1] - tail - nl:d.shape[1] - tail]
-            graze = beams > OBS_TOL
-            stats["beams"] = stats.get("beams", 0) + beams.size
-            stats["grazing"] = stats.get("grazing", 0) + int(graze.sum())
-            if (~graze).any():
-                stats["obs"] = max(stats["obs"], float(beams[~graze].max()))
         stats["rew"] = max(stats["rew"], float(np.abs(g_rew - o_rew)[same].max()))
     return o_done
 
 
-@pytest.mark.parametrize("num_traffic,num_lasers", [(16, 240), (0, 0)])
-def test_teacher_forced_parity(descs, num_traffic, num_lasers):
-    """Each step starts from the same fp32-rounded state on both sides; outputs and the next state must agree."""
-    _teacher_forced(descs, num_traffic, num_lasers)
+def _report(name, stats):
+    """The line every parity test prints beside its own: beams compared, beams with a hit, items admitted per class with their largest
+    margin, the share of sampled beams the BEAM predicate would flag."""
+    t = stats.get("ties")
+    if t is not None:
+        print(name, "ties:", t.summary(), "flag_ties", stats.get("flag_ties", 0))
+        t.dump()
+    return t
+
+
+# Share of the compared lidar beams with a hit (oracle value < 1), respawn traffic, from oracle-only runs of the same inputs
+# (profiles/parity_ties.md): ego driving 26 %, floor 10 %; ego parked: see PARKED_HIT_SHARE, floor half of it.  Trigger mode: ~0.2 %,
+# printed only.
+DRIVING_HIT_FLOOR = 0.10
+PARKED_HIT_SHARE = 0.1276  # tests/test_ties_cpu.py::test_parked_respawn_hit_share holds this figure to the oracle
+PARKED_HIT_FLOOR = 0.5 * PARKED_HIT_SHARE
+
+
+@pytest.mark.parametrize("num_traffic,num_lasers,traffic_mode,ego", [
+    pytest.param(16, 240, "trigger", "driving", id="16-240"), pytest.param(0, 0, "trigger", "driving", id="0-0"),
+    pytest.param(16, 240, "respawn", "driving", id="16-240-respawn-driving"),
+    pytest.param(16, 240, "respawn", "parked", id="16-240-respawn-parked")])
+def test_teacher_forced_parity(descs, num_traffic, num_lasers, traffic_mode, ego):
+    """Each step starts from the same fp32-rounded state on both sides; outputs and the next state must agree.  In trigger mode almost
+    no beam hits anything; respawn traffic (every IDM vehicle drives from step 0) exercises the lidar: once with the ego parked (long
+    episodes, the traffic drives past: leader, lane-change and beam decisions) and once with the ego driving (it ends in the jam every
+    few steps: contacts in every sub-step)."""
+    _teacher_forced(descs, num_traffic, num_lasers, traffic_mode=traffic_mode, ego=ego)
 
 
 @pytest.mark.parametrize("idm_agent", [False, True])
@@ -125,7 +310,8 @@ def test_idm_steer_lag_parity(descs, idm_agent):
         f, i, ei = ora.get_state()
         gf, gi, gei = eng.get_state()
         agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
-        tie = util.idm_tie(gf, f)
+        tie = util.idm_tie(gf, f, stats["ties"].mg)
+        stats["ties"].add_slots("LEADER", tie & agree, stats["ties"].mg)
         util.compare_state(gf, f, agree & ~tie, worst)
         assert (~agree).sum() == 0
         drv = gi[_abi.SI["STATUS"]] == _abi.ST_ACTIVE
@@ -137,8 +323,9 @@ def test_idm_steer_lag_parity(descs, idm_agent):
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("steer lag parity:", stats, {k: round(v, 3) for k, v in worst.items()})
+    _report("steer lag parity", stats)
     assert "specialised" not in eng.describe_step()
-    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0
+    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
     assert not util.state_failures(worst), util.state_failures(worst)
     assert lagged > 1000
     eng.close()
@@ -166,16 +353,18 @@ def test_throughput_mode_parity(descs, monkeypatch):
         f, i, ei = ora.get_state()
         gf, gi, gei = eng.get_state()
         agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
-        tie = util.idm_tie(gf, f)
+        tie = util.idm_tie(gf, f, stats["ties"].mg)
         tie[:, :1] = False
+        stats["ties"].add_slots("LEADER", tie & agree, stats["ties"].mg)
         util.compare_state(gf, f, agree & ~tie, worst)
         assert (~agree).sum() == 0
         f32 = util.round_state_f32(f)
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("throughput mode parity:", stats, "episodes", n_done, "state fields (x tolerance):", {k: round(v, 3) for k, v in worst.items()})
+    _report("throughput mode parity", stats)
     assert stats["obs"] < OBS_TOL and stats["obs_state"] < STATE_OBS_TOL and stats["rew"] < REW_TOL
-    assert stats["flag_mismatch"] == 0 and n_done > 20
+    assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and n_done > 20
     assert not util.state_failures(worst), util.state_failures(worst)
     assert stats.get("grazing", 0) <= 1e-5 * stats.get("beams", 1) + 2
     monkeypatch.setenv("PGD_PACK", "0")
@@ -568,13 +757,14 @@ def test_run_time_reward_kernel_matches_the_general_kernel_and_the_oracle(descs,
         f, i, ei = ora.get_state()
         f32 = util.round_state_f32(f)
         ora.set_state(f32, i, ei); eng.set_state(f32, i, ei)
-    assert stats["flag_mismatch"] == 0 and stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and n_done > 10
+    _report("run-time reward kernel parity", stats)
+    assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and n_done > 10
     assert "run-time reward scheme" in eng.describe_step() and "specialised" not in gen.describe_step()
 
 
-def _teacher_forced(descs, num_traffic, num_lasers):
+def _teacher_forced(descs, num_traffic, num_lasers, traffic_mode="trigger", ego="driving"):
     n_envs = 64
-    torch, eng, ora, cfg = _engines(descs, n_envs, num_traffic=num_traffic, num_lasers=num_lasers)
+    torch, eng, ora, cfg = _engines(descs, n_envs, num_traffic=num_traffic, num_lasers=num_lasers, traffic_mode=traffic_mode)
     scen_ids = np.arange(n_envs) % 8
     o0 = ora.reset(scen_ids)
     g0 = eng.reset(scen_ids).cpu().numpy()
@@ -585,15 +775,17 @@ def _teacher_forced(descs, num_traffic, num_lasers):
     worst = {}  # every float field of the state, in units of its tolerance (tests/util.py STATE_TOL)
     idm_ties = active = 0
     for t in range(400):
-        act = util.driving_actions(rng, n_envs)
+        act = util.driving_actions(rng, n_envs) * (0.0 if ego == "parked" else 1.0)
         _compare_step(torch, eng, ora, act, stats)
         f, i, ei = ora.get_state()
         gf, gi, gei = eng.get_state()
         agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
         # an IDM leader exactly MAX_DIST = 30 m ahead on the 10 m spawn grid is found / not found by the last bit of a lane
-        # coordinate: that vehicle gets another throttle on the two sides (counted and bounded, as in the campaign)
-        tie = util.idm_tie(gf, f)
+        # coordinate: that vehicle gets another throttle on the two sides (counted and bounded, as in the campaign) -- where the
+        # oracle's LEADER margin confirms the near-tie; any other differing throttle stays in compare_state
+        tie = util.idm_tie(gf, f, stats["ties"].mg)
         tie[:, :cfg.num_agents] = False
+        stats["ties"].add_slots("LEADER", tie & agree, stats["ties"].mg)
         idm_ties += int((tie & agree).sum())
         active += int((i[_abi.SI["STATUS"]][:, cfg.num_agents:] == _abi.ST_ACTIVE).sum())
         if agree.any():
@@ -606,12 +798,17 @@ def _teacher_forced(descs, num_traffic, num_lasers):
         f32 = util.round_state_f32(f)
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
-    print("teacher-forced parity:", stats, "pose", pose, "idm ties", idm_ties, "of", active,
+    print("teacher-forced parity:", traffic_mode, ego, stats, "pose", pose, "idm ties", idm_ties, "of", active,
           "state fields (x tolerance):", {k: round(v, 3) for k, v in worst.items()})
+    ties = _report("teacher-forced parity", stats)
+    print("n_crash_vehicle", stats["n_crash_vehicle"], "lidar hit share", ties.hits / max(ties.beams, 1))
+    if traffic_mode == "respawn":
+        assert ties.hits >= (PARKED_HIT_FLOOR if ego == "parked" else DRIVING_HIT_FLOOR) * ties.beams
+        assert ego == "parked" or stats["n_crash_vehicle"] > 0
     assert stats["obs"] < OBS_TOL and stats["obs_state"] < STATE_OBS_TOL and stats["rew"] < REW_TOL and pose < 1e-3
     assert not util.state_failures(worst), util.state_failures(worst)
     assert idm_ties <= 2e-3 * max(active, 1) + 2
-    assert stats["flag_mismatch"] == 0  # done / flags bit-exact (north star); no tie class occurs on these 8 maps
+    assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0  # done / flags bit-exact (north star); no tie class occurs on these 8 maps
     assert stats.get("grazing", 0) <= 1e-5 * stats.get("beams", 1) + 2
 
 
@@ -637,7 +834,7 @@ def test_side_and_lane_line_detector_parity(descs, side, lane_line, num_lasers):
     scen_ids = np.arange(n_envs) % 8
     o0 = ora.reset(scen_ids)
     g0 = eng.reset(scen_ids).cpu().numpy()
-    assert (np.abs(g0 - o0) > OBS_TOL).sum() <= 2
+    _check_reset_rows(eng, ora, g0, o0, 2)
     rng = np.random.default_rng(5)
     stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
     for t in range(150):
@@ -648,8 +845,9 @@ def test_side_and_lane_line_detector_parity(descs, side, lane_line, num_lasers):
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("detector parity:", stats)
+    _report("detector parity", stats)
     assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL
-    assert stats["flag_mismatch"] == 0
+    assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
     assert stats["det_grazing"] <= 1e-4 * stats["det_beams"] + 2
     assert stats.get("grazing", 0) <= 1e-5 * stats.get("beams", 1) + 2
 
@@ -698,7 +896,7 @@ def test_action_modes_respawn_traffic_auto_termination(descs, discrete):
         eng.set_state(f32, i, ei)
     print("action modes parity:", stats, "max_step flags", n_max_step)
     assert n_max_step >= n_envs // 4  # the jumped envs hit 250 * num_blocks unless they crashed before
-    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0
+    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
 
 
 def _teleport_to_objects(mb, sb, scen_ids, f, i, back=9.0):
@@ -745,7 +943,7 @@ def test_traffic_objects_parity(descs, safe):
     scen_ids = np.arange(n_envs) % 16
     o0 = ora.reset(scen_ids)
     g0 = eng.reset(scen_ids).cpu().numpy()
-    assert (np.abs(g0 - o0) > OBS_TOL).sum() <= 2
+    _check_reset_rows(eng, ora, g0, o0, 2)
     f, i, ei = ora.get_state()
     moved = _teleport_to_objects(ora.map_bank, ora.scen_bank, scen_ids, f, i)
     assert moved >= n_envs // 2
@@ -761,13 +959,19 @@ def test_traffic_objects_parity(descs, safe):
         o_done = _compare_step(torch, eng, ora, act, stats)
         f, i, ei = ora.get_state()
         gf, gi, gei = eng.get_state()
-        assert (gi[_abi.SI["VFLAGS"]] != i[_abi.SI["VFLAGS"]]).sum() <= 2  # incl. the objects' own "crashed" bits
+        # incl. the objects' own "crashed" bits: differing only as margin-verified ties, at most the two allowed before
+        vf_bad = gi[_abi.SI["VFLAGS"]] != i[_abi.SI["VFLAGS"]]
+        vf_tie = vf_bad & (util.admitted_slots(stats["ties"].mg, ("CONTACT", "LANE")) |   # its own line / lane decisions, or the ego's
+                           util.admitted_slots(stats["ties"].mg, ("CONTACT",))[:, :1])       # contact with it (noted on the ego)
+        stats["ties"].add_slots("CONTACT", vf_tie, stats["ties"].mg)
+        assert (vf_bad & ~vf_tie).sum() == 0 and vf_tie.sum() <= 2
         n_hit_state = max(n_hit_state, int((i[_abi.SI["VFLAGS"]][:, 1:] & _abi.F_OBJECT_HIT != 0).sum()))
         f32 = util.round_state_f32(f)
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("objects parity:", stats, "objects hit", n_hit_state)
-    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0
+    _report("objects parity", stats)
+    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
     assert n_hit_state >= 8 and stats["n_crash_object"] >= 8
     assert stats.get("grazing", 0) <= 1e-5 * stats.get("beams", 1) + 3
 
@@ -779,7 +983,8 @@ def test_lidar_noise_parity(descs):
     scen_ids = np.arange(n_envs) % 8
     o0 = ora.reset(scen_ids)
     g0 = eng.reset(scen_ids).cpu().numpy()
-    assert (np.abs(g0 - o0) > OBS_TOL).sum() <= 2 and (o0[:, 0, -240:] == 0.0).mean() > 0.05
+    _check_reset_rows(eng, ora, g0, o0, 2)
+    assert (o0[:, 0, -240:] == 0.0).mean() > 0.05
     rng = np.random.default_rng(8)
     stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
     for t in range(60):
@@ -790,7 +995,8 @@ def test_lidar_noise_parity(descs):
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("noise parity:", stats)
-    assert stats["obs"] < OBS_TOL and stats["flag_mismatch"] == 0 and stats["grazing"] <= 1e-4 * stats["beams"] + 3
+    _report("noise parity", stats)
+    assert stats["obs"] < OBS_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and stats["grazing"] <= 1e-4 * stats["beams"] + 3
 
 
 def test_maximum_sizes(descs):
@@ -804,37 +1010,53 @@ def test_maximum_sizes(descs):
     scen_ids = np.arange(n_envs) % 8
     o0 = ora.reset(scen_ids)
     g0 = eng.reset(scen_ids).cpu().numpy()
-    assert (np.abs(g0 - o0) > OBS_TOL).sum() <= 2
+    _check_reset_rows(eng, ora, g0, o0, 2)
     rng = np.random.default_rng(21)
     stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    ties = stats.setdefault("ties", util.Ties("test_maximum_sizes"))
     tie_rows = rows = 0
     for t in range(80):
         act = util.driving_actions(rng, n_envs)
         o_obs, o_rew, o_done, o_flags = ora.step(act)
+        mg = ora.margins()
         g_obs, g_rew, g_done, g_flags = eng.step(torch.from_numpy(act).to(eng.device))
         eng.sync()
         same = (g_flags.cpu().numpy().astype(np.uint32) == o_flags) & (g_done.cpu().numpy() == o_done)
         stats["steps"] += same.size
         stats["flag_mismatch"] += int((~same).sum())
-        d = np.abs(g_obs.cpu().numpy().astype(np.float64) - o_obs)[same]
+        g_obs = g_obs.cpu().numpy().astype(np.float64)
+        d = np.abs(g_obs - o_obs)[same]
         # With 63 vehicles spawned on the 10 m grid, IDM front / back candidates tie exactly (equal longitudinal gaps); the
         # reference resolves such ties by Python set order, fp32 and fp64 by an ulp.  A flipped tie changes one traffic
         # vehicle's acceleration, visible in the ego's neighbour-velocity floats: such rows are counted, not hidden.
         vel = np.zeros(d.shape[1], dtype=bool)
         vel[18 + 2:18 + 64:4] = vel[18 + 3:18 + 64:4] = True
         rows += d.shape[0]
-        tie_rows += int((d[:, vel] > OBS_TOL).any(axis=1).sum())
+        # ... and only where the oracle confirms the tie: the neighbour whose velocity differs is a slot with a verified LEADER tie
+        # (util.idm_tie), or the row's NEIGHBOUR margin says that two ranks were a near-tie; any other row goes to stats["obs"]
+        lead = util.idm_tie(eng.get_state()[0], ora.get_state()[0], mg)
+        nb_tie = util.admissible("NEIGHBOUR", mg[util.MG["NEIGHBOUR"]][:, 0])
+        for e in np.nonzero(same[:, 0])[0]:
+            cols = np.nonzero((np.abs(g_obs - o_obs)[e, 0] > OBS_TOL) & vel)[0]
+            if not len(cols):
+                continue
+            slots = [ora.neighbour_slot(e, 0, (c - 18) // 4) for c in cols]
+            if nb_tie[e] or all(s_ >= 0 and lead[e, s_] for s_ in slots):
+                tie_rows += 1
+                ties.add("NEIGHBOUR" if nb_tie[e] else "LEADER", mg[util.MG["NEIGHBOUR" if nb_tie[e] else "LEADER"], e, 0 if nb_tie[e] else slots[0]],
+                         dict(env=int(e), row_columns=[int(c) for c in cols]))
+            else:
+                stats["obs"] = max(stats["obs"], float(np.abs(g_obs - o_obs)[e, 0][vel].max()))
         stats["obs"] = max(stats["obs"], float(d[:, :82][:, ~vel[:82]].max()))
-        beams = d[:, 82:]
-        stats["grazing"] = stats.get("grazing", 0) + int((beams > OBS_TOL).sum())
-        stats["beams"] = stats.get("beams", 0) + beams.size
+        _compare_rows(eng, ora, stats, np.where(vel[None, None, :], o_obs, g_obs), o_obs, same, mg)  # beams: margin-verified grazing only
         stats["rew"] = max(stats["rew"], float(np.abs(g_rew.cpu().numpy() - o_rew)[same].max()))
         f, i, ei = ora.get_state()
         f32 = util.round_state_f32(f)
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("max sizes parity:", stats, "rows with a tie-flipped neighbour velocity", tie_rows, "of", rows)
-    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0
+    _report("max sizes parity", stats)
+    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
     assert stats["grazing"] <= 1e-4 * stats["beams"] + 3 and tie_rows <= 0.01 * rows
 
 
@@ -977,6 +1199,7 @@ def test_marl_roundabout_parity(num_agents, capacity, kind="roundabout", **cfg_k
     cfg = util.marl_config(n_envs, sb, horizon=120, **cfg_kw)  # short horizon so that the episode end / reset path is exercised
     eng = Engine(cfg, mb, sb)
     ora = orc.Oracle(cfg, mb, sb)
+    ora.enable_margins()
     ids = np.arange(n_envs) % 8
     o0 = ora.reset(ids)
     g0 = eng.reset(ids).cpu().numpy()
@@ -993,7 +1216,7 @@ def test_marl_roundabout_parity(num_agents, capacity, kind="roundabout", **cfg_k
         gf, gi, gei = eng.get_state()
         # discrete state (status / lanes / ids / counters) must be bit-exact, up to box-overlap tests that sit on an fp32
         # rounding boundary (measured: 1 line-contact flip in ~77 k agent-steps); every step restarts from the oracle state
-        seen["int_mismatch"] = seen.get("int_mismatch", 0) + int((gi != i).any(axis=0).sum()) + int((gei != ei).any(axis=0).sum())
+        _int_ties(gi, i, gei, ei, stats["ties"].mg, stats, stats["ties"].flag_tie)
         seen["id_mismatch"] = seen.get("id_mismatch", 0) + int((gf[_abi.SF["AGENT_ID"]] != f[_abi.SF["AGENT_ID"]].astype(np.float32)).sum())
         seen["dying"] += int((i[_abi.SI["STATUS"]] == _abi.ST_DYING).sum())
         util.compare_state(gf, f, (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None], worst)
@@ -1001,11 +1224,15 @@ def test_marl_roundabout_parity(num_agents, capacity, kind="roundabout", **cfg_k
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("marl parity:", stats, seen, "state fields (x tolerance):", {k: round(v, 3) for k, v in worst.items()})
+    _report("marl parity", stats)
     assert not util.state_failures(worst), util.state_failures(worst)
     assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL
     # the only tie class seen in the multi-agent runs: a car whose box touches a line box exactly (fp32 vs fp64 SAT), one
-    # agent-step in 153,600 of the 12-of-16 configuration; every other configuration is bit-exact
-    assert stats["flag_mismatch"] <= 1 and seen["int_mismatch"] <= 1 and seen["id_mismatch"] == 0
+    # agent-step in 153,600 of the 12-of-16 configuration; every other configuration is bit-exact.  Such a row is admitted only where the
+    # oracle's CONTACT / ROUTE / LANE margin confirms the near-tie (at most the one seen before); anything else: 0
+    assert stats["flag_mismatch"] == 0 and stats["flag_ties"] <= 1
+    assert stats["int_mismatch"] == 0 and seen["id_mismatch"] == 0
+    assert stats["int_ties"] <= 1
     assert seen["dying"] > 0 and stats["n_new"] > 0 and stats["n_all_done"] > 0 and stats["n_report"] > 1000
 
 
@@ -1052,11 +1279,12 @@ def test_marl_tollgate_parity():
     n_envs = 16
     cfg = util.marl_config(n_envs, sb, horizon=400, **TOLL)
     eng, ora = Engine(cfg, mb, sb), orc.Oracle(cfg, mb, sb)
+    ora.enable_margins()
     assert eng.D == 156
     ids = np.arange(n_envs) % 4
     o0 = ora.reset(ids)
     g0 = eng.reset(ids).cpu().numpy()
-    assert (np.abs(g0 - o0) > OBS_TOL).sum() <= 4
+    _check_reset_rows(eng, ora, g0, o0, 4)
     f, i, ei = ora.get_state()
     SF, SI = _abi.SF, _abi.SI
     rng = np.random.default_rng(3)
@@ -1093,6 +1321,7 @@ def test_marl_tollgate_parity():
         act[..., 0] = np.clip(rng.normal(0, 0.03, size=(n_envs, 40)), -1, 1)
         act[..., 1] = np.where(np.arange(40) % 4 == 0, 0.02, 0.4)[None, :]
         o_obs, o_rew, o_done, o_flags = ora.step(act)
+        mg = ora.margins()
         g_obs, g_rew, g_done, g_flags = eng.step(torch.from_numpy(act).to(eng.device))
         eng.sync()
         g_obs = g_obs.cpu().numpy().astype(np.float64)
@@ -1100,12 +1329,8 @@ def test_marl_tollgate_parity():
         same = (gfl == o_flags) & (g_done.cpu().numpy() == o_done)
         stats["steps"] += same.size
         stats["flag_mismatch"] += int((~same).sum())
-        dd = np.abs(g_obs - o_obs)[same]
-        fan = np.zeros(156, dtype=bool)
-        fan[:72] = fan[78:82] = fan[82:154] = True
-        stats["obs"] = max(stats["obs"], float(dd[:, ~fan].max()))
-        stats["grazing"] = stats.get("grazing", 0) + int((dd[:, fan] > OBS_TOL).sum())
-        stats["beams"] = stats.get("beams", 0) + dd[:, fan].size
+        # ray-cast columns (side fan 0:72, lane-line fan 78:82, lidar 82:154) over OBS_TOL: margin-verified grazing or stats["obs"]
+        _compare_rows(eng, ora, stats, g_obs, o_obs, same, mg)
         stats["rew"] = max(stats["rew"], float(np.abs(g_rew.cpu().numpy() - o_rew)[same].max()))
         rep = (o_flags & _abi.F_REPORT) != 0
         seen["toll_obs"] += int((o_obs[..., -2][rep] > 0).sum())
@@ -1125,7 +1350,9 @@ def test_marl_tollgate_parity():
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("tollgate parity:", stats, seen)
-    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and seen["int_mismatch"] == 0
+    _report("tollgate parity", stats)
+    stats["grazing"], stats["beams"] = stats["grazing"] + stats["det_grazing"], stats["beams"] + stats["det_beams"]  # all three fans, as before
+    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and seen["int_mismatch"] == 0
     assert stats["grazing"] <= 1e-4 * stats["beams"] + 5
     assert seen["toll_obs"] > 500 and seen["long_stay"] > 50 and seen["entries"] > 20 and seen["exits"] > 10 and seen["building"] > 10
     assert seen["fast_exit"] >= 5
@@ -1424,7 +1651,9 @@ def test_config_combinations_fuzz(descs):
             f32 = util.round_state_f32(f)
             ora.set_state(f32, i, ei)
             eng.set_state(f32, i, ei)
-        assert st["obs"] < OBS_TOL and st["rew"] < REW_TOL and st["flag_mismatch"] <= 2, (kw, st)
+        _report("fuzz trial %d" % trial, st)
+        # (flags that differ: only margin-verified CONTACT / ROUTE / LANE ties, at most the two a trial was allowed before)
+        assert st["obs"] < OBS_TOL and st["rew"] < REW_TOL and st["flag_mismatch"] == 0 and st["flag_ties"] <= 2, (kw, st)
         eng.close()
 
 
@@ -1459,20 +1688,23 @@ def test_marl_config_combinations_fuzz():
         n_envs = 24
         cfg = util.marl_config(n_envs, sb, **kw)
         eng, ora = Engine(cfg, mb, sb), orc.Oracle(cfg, mb, sb)
+        ora.enable_margins()
         ids = np.arange(n_envs) % len(sb.scenarios)
         assert np.abs(eng.reset(ids).cpu().numpy() - ora.reset(ids)).max() < OBS_TOL
         rng = np.random.default_rng(trial)
         st = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
-        im = 0
         for t in range(200):
             _compare_step(torch, eng, ora, util.marl_actions(rng, n_envs, sb.A), st)
             f, i, ei = ora.get_state()
             gf, gi, gei = eng.get_state()
-            im += int((gi != i).any(axis=0).sum()) + int((gei != ei).any(axis=0).sum())
+            _int_ties(gi, i, gei, ei, st["ties"].mg, st, st["ties"].flag_tie)
             f32 = util.round_state_f32(f)
             ora.set_state(f32, i, ei)
             eng.set_state(f32, i, ei)
-        assert st["obs"] < OBS_TOL and st["rew"] < REW_TOL and st["flag_mismatch"] <= 2 and im <= 2, (kind, na, cap, kw, st, im)
+        _report("marl fuzz trial %d" % trial, st)
+        assert st["obs"] < OBS_TOL and st["rew"] < REW_TOL and st["flag_mismatch"] == 0 and st["flag_ties"] <= 2, (kind, na, cap, kw, st)
+        assert st["int_mismatch"] == 0, (kind, na, cap, kw, st)
+        assert st["int_ties"] <= 2, (kind, na, cap, kw, st)
         eng.close()
 
 
@@ -1540,7 +1772,7 @@ def test_contacts_inside_the_sub_steps(descs):
         n_mid_only += int((crash & cont & ~end_any).sum())
         assert not (end_any & cont & ~crash).any()  # an overlap at the end of the step is a contact, always
     print("sub-step contacts:", stats, "crash_vehicle", n_crash, "of which clear again at the end of the step", n_mid_only)
-    assert stats["flag_mismatch"] == 0 and stats["obs"] < OBS_TOL
+    assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and stats["obs"] < OBS_TOL
     assert n_crash > 300 and n_mid_only >= 5
 
 
@@ -1902,15 +2134,17 @@ def test_idm_agent_parity_and_arrivals(descs, traffic_mode):
     stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
     worst, ties, traffic_steps, n_done, arrive = {}, 0, 0, 0, 0
     SI = _abi.SI
-    int_mismatch = 0
+    int_ties = 0
     for t in range(260):
         act = rng.uniform(-1, 1, size=(n_envs, 1, 2)).astype(np.float32)  # ignored by both sides
         o_done = _compare_step(torch, eng, ora, act, stats)
         f, i, ei = ora.get_state()
         gf, gi, gei = eng.get_state()
         agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
-        int_mismatch += int((~agree).sum())
-        tie = util.idm_tie(gf, f)  # (the ego is an IDM vehicle here: its leader can sit on the 30 m search range as well)
+        mg = stats["ties"].mg
+        int_ties += _int_ties(gi, i, gei, ei, mg, stats, stats["ties"].flag_tie)[0]
+        tie = util.idm_tie(gf, f, mg)  # (the ego is an IDM vehicle here: its leader can sit on the 30 m search range as well)
+        stats["ties"].add_slots("LEADER", tie & agree, mg)
         ties += int((tie & agree).sum())
         traffic_steps += int((i[SI["STATUS"]] == _abi.ST_ACTIVE).sum())
         util.compare_state(gf, f, agree & ~tie, worst)
@@ -1918,10 +2152,13 @@ def test_idm_agent_parity_and_arrivals(descs, traffic_mode):
         f32 = util.round_state_f32(f)
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
-    print("IDM agent, teacher-forced:", stats, "integer-state mismatches", int_mismatch, "idm ties", ties, "of", traffic_steps,
+    print("IDM agent, teacher-forced:", stats, "integer-state ties", int_ties, "idm ties", ties, "of", traffic_steps,
           "episodes ended", n_done, {k: round(v, 3) for k, v in worst.items()})
-    assert int_mismatch <= 2 and n_done > 0
-    assert stats["flag_mismatch"] == 0 and stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL, stats
+    _report("IDM agent parity", stats)
+    # integer state that differs is a margin-verified tie (LANE / CONTACT / ROUTE / LEADER), at most the two seen before; anything else: 0
+    assert stats["int_mismatch"] == 0 and n_done > 0
+    assert int_ties <= 2
+    assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL, stats
     assert not util.state_failures(worst), util.state_failures(worst)
     assert ties <= 0.002 * traffic_steps + 2
     eng.close()

@@ -86,13 +86,101 @@ STATE_TOL = {
 }
 
 
-def idm_tie(gf, f):
-    """Slots whose applied throttle differs between engine and oracle by more than rounding: an IDM leader exactly MAX_DIST =
-    30 m ahead on the 10 m spawn grid is found / not found by the last bit of a lane coordinate (also in the reference's
-    fp64), and the vehicle then gets another acceleration on the two sides.  The enumerated tie class of the campaigns
-    (profiles/r01_parity_campaign.md): counted and bounded by the callers, excluded from the per-field comparison."""
+# ---------------------------------------------------------------------------------------------------------------------
+# Margin-verified ties.  A discrete mismatch between engine and oracle (a beam that hits on one side only, a flag, a lane id, another
+# IDM leader, another neighbour order) is excused only where the ORACLE says that the decision was a near-tie: its margin -- the
+# smallest |lhs - rhs| of the comparisons of that class taken for the item, in metres at the geometry (oracle/pgd_oracle.h,
+# ORC_MG_*) -- is below what the rounding of the shared input can move.
+#
+# Derivation of the ceiling (not tuned on the engine): both sides start every teacher-forced step from the identical fp32 state,
+# and STATE_TOL above already bounds how far the two poses may be apart after the step: tol_xy = 1e-3 m in X / Y, tol_theta = 1e-4 rad
+# in THETA.  A comparison between two bodies (or a body and a map box) can therefore move by 2 * tol_xy, plus
+# lever * tol_theta where a heading error swings a point at distance `lever` from the pivot:
+#     eps(class, lever) = 2 * tol_xy + lever * tol_theta
+# BEAM: lever = the fan's range (50 m: 7e-3 m).  CONTACT: lever = sum of the two bodies' half diagonals (a heading error moves a body's
+# own corners only; the oracle reports it with the margin).  LANE / ROUTE / LEADER / NEIGHBOUR: lever 0 (two lane coordinates or two
+# centre distances: 2e-3 m); LEADER decisions are taken on the pre-step state, bit-identical on both sides, so only the fp32 evaluation
+# of the lane coordinates differs and 2e-3 m is a generous ceiling -- one formula all the same.  It is a ceiling: the tests print the
+# largest margin they admitted (profiles/parity_ties.md) so that a tighter value can be argued from the fp32 arithmetic later.
+# ---------------------------------------------------------------------------------------------------------------------
+TIE_CLASSES = ("BEAM", "CONTACT", "LANE", "LEADER", "NEIGHBOUR", "ROUTE")
+MG = dict(BEAM=0, CONTACT=1, LANE=2, LEADER=3, NEIGHBOUR=4, ROUTE=5, CONTACT_LEVER=6)  # planes of Oracle.margins()
+TIE_TOL_XY, TIE_TOL_THETA = STATE_TOL["X"][0], STATE_TOL["THETA"][0]
+
+
+def tie_eps(cls, lever=0.0):
+    assert cls in TIE_CLASSES
+    return 2.0 * TIE_TOL_XY + lever * TIE_TOL_THETA
+
+
+def admissible(cls, margin, lever=0.0):
+    """The one admission rule: the oracle's margin of the decision is below the derived ceiling.  Works on arrays."""
+    return np.asarray(margin) < tie_eps(cls, np.asarray(lever, dtype=np.float64))
+
+
+def admitted_slots(mg, classes):
+    """[N, V] bool: slots for which a decision of one of `classes` was a near-tie in the oracle's last step.  mg: Oracle.margins()."""
+    out = np.zeros(mg.shape[1:], dtype=bool)
+    for cls in classes:
+        out |= admissible(cls, mg[MG[cls]], mg[MG["CONTACT_LEVER"]] if cls == "CONTACT" else 0.0)
+    return out
+
+
+class Ties:
+    """What a test admitted: per class the count, the largest margin, and the first cases (test, class, where, margin)."""
+    def __init__(self, name=""):
+        self.name, self.n, self.worst, self.cases, self.rejected = name, {}, {}, [], []
+        self.beams = self.hits = self.flagged = self.sampled = 0
+        self.rng = np.random.default_rng(0)  # which beams the flagged-share estimate samples
+
+    def __repr__(self):
+        return repr(self.summary())
+
+    def add(self, cls, margin, where):
+        self.n[cls] = self.n.get(cls, 0) + 1
+        self.worst[cls] = max(self.worst.get(cls, 0.0), float(margin))
+        if len(self.cases) < 200:
+            self.cases.append(dict(test=self.name, cls=cls, where=where, margin=float(margin)))
+
+    def reject(self, kind, where):
+        """A mismatch the rule did NOT admit (it fails the test): kept so that the report can say what it was."""
+        if len(self.rejected) < 50:
+            self.rejected.append(dict(test=self.name, kind=kind, where=where))
+
+    def add_slots(self, cls, mask, mg):
+        for e, s in zip(*np.nonzero(mask)):
+            self.add(cls, mg[MG[cls], e, s], dict(env=int(e), slot=int(s)))
+
+    def summary(self):
+        return dict(admitted={k: (self.n[k], float("%.3g" % self.worst[k])) for k in sorted(self.n)}, beams=self.beams, beams_hit=self.hits,
+                    hit_share=round(self.hits / max(self.beams, 1), 4),
+                    beam_flagged_share=(round(self.flagged / self.sampled, 5) if self.sampled else None), not_admitted=len(self.rejected))
+
+    def dump(self):
+        """Append this test's cases to the file named by PGD_TIES_DUMP (one JSON object per line) -- how profiles/parity_ties.json is made."""
+        import json, os
+        path = os.environ.get("PGD_TIES_DUMP")
+        if path:
+            with open(path, "a") as fh:
+                fh.write(json.dumps(dict(test=self.name, summary=self.summary(), cases=self.cases, rejected=self.rejected)) + "\n")
+
+
+def throttle_differs(gf, f):
     a, b = gf[_abi.SF["ACT1T"]].astype(np.float64), np.asarray(f[_abi.SF["ACT1T"]], dtype=np.float64)
     return np.abs(a - b) > 1e-3 + 1e-3 * np.abs(b)
+
+
+def idm_tie(gf, f, mg, ties=None):
+    """Slots whose applied throttle differs between engine and oracle by more than rounding AND for which the oracle's leader search
+    (find_front_back and the object / lane selecting branches of idm_act) took a decision within tie_eps("LEADER") of going the other
+    way: an IDM leader exactly MAX_DIST = 30 m ahead on the 10 m spawn grid is found / not found by the last bit of a lane coordinate
+    (also in the reference's fp64), two candidates are equally far, ...  The vehicle then gets another acceleration on the two sides.
+    Counted and bounded by the callers, excluded from the per-field comparison.  A slot that differs WITHOUT such a near-tie is not
+    returned: it stays in compare_state and fails there.  mg: Oracle.margins() of the step."""
+    tie = throttle_differs(gf, f) & admissible("LEADER", mg[MG["LEADER"]])
+    if ties is not None:
+        ties.add_slots("LEADER", tie, mg)
+    return tie
 
 
 def compare_state(gf, f, mask, worst, skip=()):
