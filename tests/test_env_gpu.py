@@ -971,11 +971,9 @@ env.close()
 
 
 def _mlp_numpy(x, w1, b1, w2, b2, w3, b3, final_tanh):
-    """pgdrive/examples/ppo_expert/numpy_expert.py:25-44 re-stated in float64 (the checker)."""
-    h = np.tanh(x.astype(np.float64) @ w1.astype(np.float64) + b1)
-    h = np.tanh(h @ w2.astype(np.float64) + b2)
-    o = (h @ w3.astype(np.float64) + b3)[:, :2]
-    return np.tanh(o) if final_tanh else o
+    """pgdrive/examples/ppo_expert/numpy_expert.py:25-44 re-stated in float64 (the checker, tests/policy_ref.py)."""
+    from tests.policy_ref import mlp_f64
+    return mlp_f64(x, (w1, b1, w2, b2, w3, b3), final_tanh)
 
 
 @pytest.mark.parametrize("case", ["expert_weights", "random_274", "groups"])
@@ -1031,6 +1029,7 @@ def test_mlp_policy_matches_the_numpy_expert(descs, case):
         # the same network with split bf16 operands on prepared weights (pgd_mlp_prepare / pgd_mlp_policy_prepared): every value as
         # hi + lo, a product as three bf16 matrix instructions -- 16 bits of mantissa, not 24: held to 1e-4 (measured ~3e-5)
         prep = eng.mlp_prepare(wt)
+        eng.sync()  # (prepared on the engine's stream, read on the groups' own: not ordered against each other, include/pgdrive_hip.h)
         assert prep.numel() == eng.L.pgd_mlp_prepared_bytes(in_dim)
         out2 = torch.full((n, 1, 2), 7.0, dtype=torch.float32, device="cuda")
         if case == "groups":
