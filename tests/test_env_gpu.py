@@ -287,7 +287,7 @@ def test_safe_env_cost_to_reward_and_object_contact():
     import torch
     from pgdrive_amd import _abi
     from pgdrive_amd.env import SafePGDriveEnv
-    from tests.test_parity_gpu import _teleport_to_objects
+    from tests.parity import teleport_to_objects
     env = SafePGDriveEnv({"environment_num": 16, "start_seed": 1000, "accident_prob": 1.0, "cost_to_reward": True})
     try:
         assert env.config["crash_object_penalty"] == 6.0 and env.config["out_of_road_penalty"] == 6.0
@@ -296,7 +296,7 @@ def test_safe_env_cost_to_reward_and_object_contact():
             env.reset(force_seed=seed)
             f, i, ei = env.vec.engine.get_state()
             scen = np.array([seed - 1000])
-            if not _teleport_to_objects(env.vec.map_bank, env.vec.scen_bank, scen, f, i):
+            if not teleport_to_objects(env.vec.map_bank, env.vec.scen_bank, scen, f, i):
                 continue
             env.vec.engine.set_state(f, i, ei)
             for t in range(30):

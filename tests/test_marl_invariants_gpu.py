@@ -423,14 +423,14 @@ def test_object_collision_detection():
     """tests/test_functionality/test_object_collision_detection.py:136-170: driving straight at a traffic object, the lidar sees it
     before the contact and the contact is reported as crash_object."""
     from pgdrive_amd.env import SafePGDriveEnv
-    from tests.test_parity_gpu import _teleport_to_objects
+    from tests.parity import teleport_to_objects
     env = SafePGDriveEnv({"environment_num": 16, "start_seed": 1000, "accident_prob": 1.0, "traffic_density": 0.0})
     try:
         done_cases = 0
         for seed in range(1000, 1016):
             env.reset(force_seed=seed)
             f, i, ei = env.vec.engine.get_state()
-            if not _teleport_to_objects(env.vec.map_bank, env.vec.scen_bank, np.array([seed - 1000]), f, i):
+            if not teleport_to_objects(env.vec.map_bank, env.vec.scen_bank, np.array([seed - 1000]), f, i):
                 continue
             env.vec.engine.set_state(f, i, ei)
             detect_obj = crash_obj = False

@@ -10,271 +10,10 @@ import numpy as np
 import pytest
 
 from pgdrive_amd import _abi
-from tests import util
+from tests import parity, util
+from tests.parity import OBS_TOL, REW_TOL, STATE_OBS_TOL, closed_engines  # noqa: F401 (the fixture closes every engine a test made)
 
 pytestmark = pytest.mark.gpu
-
-OBS_TOL = 2.5e-5  # ray-cast columns (lidar, side / lane-line fans): SURVEY 8c's 0.5 mm at the shortest fan range in the suite (20 m)
-STATE_OBS_TOL = 1e-5  # every other column (ego state, navigation, neighbour rows): SURVEY 8c's 1e-5, asserted separately
-REW_TOL = 2e-4
-
-
-def _engines(descs, n_envs, n_maps=8, **kw):
-    import torch
-    from oracle import orc
-    from pgdrive_amd.engine import Engine
-    mb, sb = util.make_banks(descs, n_maps=n_maps, **{k: v for k, v in kw.items() if k in (
-        "num_agents", "num_traffic", "density", "traffic_mode", "auto_termination", "accident_prob", "random_agent_model", "idm_agent")})
-    cfg = _abi.make_config(n_envs, num_agents=kw.get("num_agents", 1), num_traffic=kw.get("num_traffic", 16),
-                           num_lasers=kw.get("num_lasers", 240), auto_reset=kw.get("auto_reset", 1),
-                           side_lasers=kw.get("side_lasers", 0), side_dist=kw.get("side_dist", 50.0),
-                           lane_line_lasers=kw.get("lane_line_lasers", 0), lane_line_dist=kw.get("lane_line_dist", 20.0),
-                           discrete_action=kw.get("discrete_action", False),
-                           increment_steering=kw.get("increment_steering", False), horizon=kw.get("horizon", 0),
-                           safe_rl_env=kw.get("safe_rl_env", False), num_others=kw.get("num_others", 4),
-                           random_agent_model=kw.get("random_agent_model", False),
-                           lidar_gaussian_noise=kw.get("lidar_gaussian_noise", 0.0),
-                           lidar_dropout_prob=kw.get("lidar_dropout_prob", 0.0), seed=kw.get("seed", 0),
-                           resample_scenario=kw.get("resample_scenario", 0), decision_repeat=kw.get("decision_repeat", 5),
-                           lidar_dist=kw.get("lidar_dist", 50.0),
-                           **{k: kw[k] for k in ("success_reward", "use_lateral", "speed_reward", "driving_reward", "out_of_road_penalty",
-                                                 "idm_agent", "idm_steer_lag") if k in kw})
-    eng = Engine(cfg, mb, sb)
-    ora = orc.Oracle(cfg, mb, sb)
-    ora.enable_margins()  # every mismatch the tests tolerate is checked against the oracle's decision margins (tests/util.py)
-    ora.map_bank, ora.scen_bank = mb, sb
-    return torch, eng, ora, cfg
-
-
-def _fan_layout(cfg):
-    """The ray-cast columns of an observation row: (first column, beams, fan, neighbour rank) with fan 0 = lidar, 1 = side detector,
-    2 = lane-line detector (oracle/pgd_oracle.h orc_beam_margin) and rank -1 = the agent's own fan, k = the fan inside the state vector
-    of neighbour row k (MA_OTHERS_STATE); and the row width the layout is for."""
-    nl, ks, km = cfg.num_lasers, cfg.side_lasers, cfg.lane_line_lasers
-    toll = bool(cfg.marl_flags & _abi.MA_TOLLGATE)
-    sl = (ks or 2) + 6 + km + (2 if cfg.random_agent_model else 0) + (0 if toll else 10)
-    others_state = bool(cfg.marl_flags & _abi.MA_OTHERS_STATE)
-    D = sl + (sl if others_state else 4) * cfg.num_others + nl + (2 if toll else 0)
-    out = []
-    for rank in [-1] + (list(range(cfg.num_others)) if others_state else []):
-        off = sl * (rank + 1)
-        if ks:
-            out.append((off, ks, 1, rank))
-        if km:
-            out.append((off + (ks or 2) + 6, km, 2, rank))
-    if nl:
-        out.append((D - (2 if toll else 0) - nl, nl, 0, -1))  # TollGateObservation appends its two floats BEHIND the lidar
-    return out, D
-
-
-def _admit_beams(eng, ora, ties, where, layout, lead_tie=None, diff=None):
-    """`where`: (env, agent, column) of ray-cast values that differ by more than OBS_TOL (`diff`: by how much).  A beam is a tie only
-    where the oracle's geometry says so:
-      * its BEAM margin (a box corner / circle / range end / broad-phase radius / the origin on a boundary within eps of the beam, up
-        to where the beam ends) is admissible;
-      * or the beam slides along the face it ends on: OBS_TOL is SURVEY 8c's 0.5 mm displacement of the geometry for a beam that meets
-        its surface head-on; at an angle phi the same displacement moves the reading 1 / sin(phi) times as far (found by
-        tests/test_ties_cpu.py: 1 fp32 ulp of pose, 1.5e-5 m, moves a beam that meets a rear face at 0.02 rad by 1.3 mm).  Such a beam is
-        admitted where its difference, taken normal to the surface, keeps the tolerance: diff * sin(phi) <= OBS_TOL;
-      * or, for lidar beams, it passes within the distance a vehicle with a verified LEADER tie can have moved (another acceleration
-        on the two sides: at most g * T^2 / 2, brake limited by friction <= 1 in dynamics()) of that vehicle.
-    Returns the admitted ones as a bool array; everything else stays in the numeric comparison and fails there."""
-    cfg = eng.cfg
-    ranges = {0: cfg.lidar_dist, 1: cfg.side_dist, 2: cfg.lane_line_dist}
-    ok = np.zeros(len(where), dtype=bool)
-    T = float(cfg.dt) * cfg.decision_repeat
-    shift = 0.5 * 9.81 * T * T
-    for k, (e, a, col) in enumerate(where):
-        start, n, fan, rank = next(x for x in layout if x[0] <= col < x[0] + x[1])
-        slot = a if rank < 0 else ora.neighbour_slot(e, a, rank)
-        if slot < 0:
-            continue
-        m = ora.beam_margin(e, a, fan, col - start, slot)
-        sin_phi = ora.beam_incidence(e, a, fan, col - start, slot) if diff is not None else 1.0
-        if diff is not None and diff[k] * sin_phi <= OBS_TOL:  # (first: what it explains is no near-tie and is listed apart)
-            ok[k] = True
-            ties.add("BEAM_SLIDE", diff[k] * sin_phi * ranges[fan], dict(env=int(e), agent=int(a), fan=fan, beam=int(col - start), slide_sin=sin_phi))
-        elif util.admissible("BEAM", m, ranges[fan]):
-            ok[k] = True
-            ties.add("BEAM", m, dict(env=int(e), agent=int(a), fan=fan, beam=int(col - start)))
-        elif fan == 0 and lead_tie is not None and lead_tie[e].any():
-            for body in np.nonzero(lead_tie[e])[0]:
-                dist = ora.beam_body_dist(e, slot, int(body), col - start)
-                if body != slot and dist < shift + util.tie_eps("BEAM", ranges[0]):
-                    ok[k] = True
-                    ties.add("LEADER", dist, dict(env=int(e), agent=int(a), beam=int(col - start), moved_body=int(body)))
-                    break
-    return ok
-
-
-def _beam_flagged_sample(ora, ties, o_obs, layout, rng, k=64):
-    """Share of compared beams the BEAM predicate WOULD flag, estimated on k random lidar beams per step (must stay small: the predicate
-    may not degenerate into 'everything is a tie'; bounded at 1 % by tests/test_ties_cpu.py)."""
-    lid = [x for x in layout if x[2] == 0]
-    if not lid:
-        return
-    start, n = lid[0][0], lid[0][1]
-    N, A = o_obs.shape[:2]
-    for e, a, b in zip(rng.integers(0, N, k), rng.integers(0, A, k), rng.integers(0, n, k)):
-        if o_obs[e, a].any():  # (an empty agent seat has a zero row and no beams)
-            ties.sampled += 1
-            ties.flagged += bool(util.admissible("BEAM", ora.beam_margin(e, a, 0, b), ora.cfg.lidar_dist))
-
-
-def _flag_ties(eng, stats, same, mg):
-    """Rows whose done / flags differ: a tie (stats["flag_ties"]) only where a CONTACT / ROUTE / LANE decision of that agent was a near-tie
-    in the oracle, else stats["flag_mismatch"] (== 0 in every test)."""
-    ties = stats["ties"]
-    A = eng.cfg.num_agents
-    flag_tie = ~same & util.admitted_slots(mg, ("CONTACT", "ROUTE", "LANE"))[:, :A]
-    for cls in ("CONTACT", "ROUTE", "LANE"):
-        ties.add_slots(cls, ~same & util.admitted_slots(mg, (cls,))[:, :A], mg)
-    stats["flag_ties"] = stats.get("flag_ties", 0) + int(flag_tie.sum())
-    stats["flag_mismatch"] += int((~same & ~flag_tie).sum())
-    for e, a in np.argwhere(~same & ~flag_tie):
-        ties.reject("flags", dict(env=int(e), agent=int(a), margins={c: float(mg[util.MG[c], e, a]) for c in ("CONTACT", "ROUTE", "LANE")}))
-    return flag_tie
-
-
-# which near-tie can explain a differing integer field of a slot (oracle/pgd_oracle.c: where each is written)
-_INT_FIELD_CLASSES = dict(LANE=("LANE",), CK0=("ROUTE", "LANE"), CK1=("ROUTE", "LANE"), RLANE=("LANE", "LEADER"), TIMER=("LEADER", "LANE"),
-                          VFLAGS=("CONTACT", "LANE"), STATUS=("LANE", "CONTACT", "ROUTE"), SPAWN=("ROUTE", "CONTACT"))
-
-
-def _int_ties(gi, i, gei, ei, mg, stats, flag_tie=None):
-    """Integer state (status / lanes / checkpoints / timers / counters) that differs after one teacher-forced step.  A slot is a tie where
-    EVERY differing field has a near-tie of a class that writes it (_INT_FIELD_CLASSES): LANE (the lane pick feeds everything else of the
-    slot, off-lane removal), CONTACT (line / crash bits of SI_VFLAGS), ROUTE (checkpoints, arrival, respawn place), LEADER (routing
-    lane / timer of an IDM vehicle).  Discrete outcomes cascade inside an env within the step (an episode end resets every slot, a
-    finish frees a seat for a respawn, the ego's lane triggers traffic): a differing slot without a near-tie of its own is a tie only
-    if the same env has a verified one (a differing slot or a differing done / flags row).  Returns (ties, mismatches): slots + env
-    records."""
-    ties = stats["ties"]
-    bad = (gi != i).any(axis=0)
-    own = bad.copy()
-    for name, k in _abi.SI.items():
-        differs = gi[k] != i[k]
-        adm = util.admitted_slots(mg, _INT_FIELD_CLASSES[name])
-        own &= ~differs | adm
-        for cls in _INT_FIELD_CLASSES[name]:
-            ties.add_slots(cls, differs & util.admitted_slots(mg, (cls,)), mg)
-    env_ok = own.any(axis=1)
-    if flag_tie is not None:
-        env_ok |= flag_tie.any(axis=1)
-    bad_env = (gei != ei).any(axis=0)
-    n_bad = int(bad.sum()) + int(bad_env.sum())
-    n_tie = int((bad & env_ok[:, None]).sum()) + int((bad_env & env_ok).sum())
-    for e, s_ in np.argwhere(bad & ~env_ok[:, None]):
-        ties.reject("int_state", dict(env=int(e), slot=int(s_), fields=[k for k, v in _abi.SI.items() if gi[v, e, s_] != i[v, e, s_]],
-                                      margins={c: float(mg[util.MG[c], e, s_]) for c in ("LANE", "CONTACT", "ROUTE", "LEADER")}))
-    stats["int_ties"] = stats.get("int_ties", 0) + n_tie
-    stats["int_mismatch"] = stats.get("int_mismatch", 0) + n_bad - n_tie
-    return n_tie, n_bad - n_tie
-
-
-def _compare_rows(eng, ora, stats, g_obs, o_obs, same, mg):
-    """The observation rows of one step (float64 arrays [N, A, D]) where the discrete outcome agrees (`same`): non-ray columns into
-    stats["obs"] / ["obs_state"]; ray-cast columns over OBS_TOL into stats["grazing"] / ["det_grazing"] if _admit_beams admits them,
-    else into stats["obs"] as well."""
-    ties = stats.setdefault("ties", util.Ties(os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0]))
-    layout, D = _fan_layout(eng.cfg)
-    assert D == g_obs.shape[2]
-    nl = eng.cfg.num_lasers
-    if nl:
-        lo = [x for x in layout if x[2] == 0][0][0]
-        ties.beams += int(same.sum()) * nl
-        ties.hits += int((o_obs[same][:, lo:lo + nl] < 1.0).sum())
-        _beam_flagged_sample(ora, ties, o_obs, layout, ties.rng)
-    # numeric comparison only where the discrete outcome agrees (a flipped flag changes reward / reset / obs wholesale)
-    if same.any():
-        dfull = np.where(same[:, :, None], np.abs(g_obs - o_obs), 0.0)
-        fan = np.zeros(D, dtype=bool)  # ray-cast columns: side fan, lane-line fan, lidar
-        lidar = np.zeros(D, dtype=bool)
-        for start, n, kind, rank in layout:
-            fan[start:start + n] = True
-            lidar[start:start + n] = kind == 0
-        stats["obs"] = max(stats["obs"], float(dfull[:, :, ~fan].max()))
-        stats["obs_state"] = max(stats.get("obs_state", 0.0), float(dfull[:, :, ~fan].max()))  # the non-ray columns on their own
-        # a beam grazing a box corner can flip hit <-> miss between fp32 and fp64 (the slab test compares two nearly equal
-        # parameters): such a beam is a tie only if the oracle's geometry confirms it; ties are counted and bounded by the callers,
-        # every other beam must agree to OBS_TOL
-        over = np.argwhere((dfull > OBS_TOL) & fan[None, None, :])
-        if len(over):
-            lead_tie = None
-            if eng.cfg.num_traffic or eng.cfg.idm_agent:
-                lead_tie = util.idm_tie(eng.get_state()[0], ora.get_state()[0], mg)
-            ok = _admit_beams(eng, ora, ties, over, layout, lead_tie, diff=dfull[over[:, 0], over[:, 1], over[:, 2]])
-            stats["beams_not_admitted"] = stats.get("beams_not_admitted", 0) + int((~ok).sum())
-            for (e, a, col), adm in zip(over, ok):
-                if not adm:  # a finding: kept for the report (and it stays in stats["obs"])
-                    ties.reject("beam", dict(env=int(e), agent=int(a), column=int(col), engine=float(g_obs[e, a, col]), oracle=float(o_obs[e, a, col])))
-                if adm:
-                    dfull[e, a, col] = 0.0
-                    key = ("grazing", "beams") if lidar[col] else ("det_grazing", "det_beams")
-                    stats[key[0]] = stats.get(key[0], 0) + 1
-        n_rows = int(same.sum())
-        if nl:
-            stats["beams"] = stats.get("beams", 0) + n_rows * nl
-            stats.setdefault("grazing", 0)
-        if int(fan.sum()) - nl:
-            stats["det_beams"] = stats.get("det_beams", 0) + n_rows * (int(fan.sum()) - nl)
-            stats.setdefault("det_grazing", 0)
-        stats["obs"] = max(stats["obs"], float(dfull[:, :, fan].max()) if fan.any() else 0.0)
-
-
-def _check_reset_rows(eng, ora, g0, o0, allowance, name="reset rows"):
-    """The first observation after a reset: values over OBS_TOL are allowed only in ray-cast columns whose BEAM margin (from the state
-    the oracle holds after the reset) admits them, and at most `allowance` of those."""
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
-    same = np.ones(o0.shape[:2], dtype=bool)
-    _compare_rows(eng, ora, stats, np.asarray(g0, dtype=np.float64), o0, same, ora.margins())
-    n_ties = stats.get("grazing", 0) + stats.get("det_grazing", 0)
-    print(name, "worst not admitted", stats["obs"], "admitted beams", n_ties, stats["ties"])
-    assert stats["obs"] < OBS_TOL and n_ties <= allowance, stats
-
-
-def _compare_step(torch, eng, ora, act, stats):
-    """One step on both sides.  Discrete outcomes must agree; what does not is a tie only where the oracle's margins say so
-    (tests/util.py: admissible): rows whose done / flags differ go to stats["flag_ties"] if a CONTACT / ROUTE / LANE decision of that
-    agent was a near-tie, else to stats["flag_mismatch"] (asserted == 0 by every caller); ray-cast values over OBS_TOL go to
-    stats["grazing"] / ["det_grazing"] if _admit_beams admits them, else they stay in stats["obs"]."""
-    if not getattr(ora, "margins_on", False):
-        ora.enable_margins()
-    ties = stats.setdefault("ties", util.Ties(os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0]))
-    o_obs, o_rew, o_done, o_flags = ora.step(act)
-    mg = ties.mg = ora.margins()  # (callers take the step's margins from here)
-    g_obs, g_rew, g_done, g_flags = eng.step(torch.from_numpy(act).to(eng.device))
-    eng.sync()
-    g_obs, g_rew = g_obs.cpu().numpy().astype(np.float64), g_rew.cpu().numpy().astype(np.float64)
-    g_done, g_flags = g_done.cpu().numpy(), g_flags.cpu().numpy().astype(np.uint32)
-    same = (g_flags == o_flags) & (g_done == o_done)
-    for name, bit in (("n_new", _abi.F_NEW), ("n_all_done", _abi.F_ALL_DONE), ("n_report", _abi.F_REPORT),
-                      ("n_crash_object", _abi.F_CRASH_OBJECT), ("n_crash_vehicle", _abi.F_CRASH_VEHICLE)):
-        stats[name] = stats.get(name, 0) + int(((o_flags & bit) != 0).sum())
-    stats["steps"] += same.size
-    ties.flag_tie = _flag_ties(eng, stats, same, mg)
-    _compare_rows(eng, ora, stats, g_obs, o_obs, same, mg)
-    if same.any():
-        stats["rew"] = max(stats["rew"], float(np.abs(g_rew - o_rew)[same].max()))
-    return o_done
-
-
-def _report(name, stats):
-    """The line every parity test prints beside its own: beams compared, beams with a hit, items admitted per class with their largest
-    margin, the share of sampled beams the BEAM predicate would flag."""
-    t = stats.get("ties")
-    if t is not None:
-        print(name, "ties:", t.summary(), "flag_ties", stats.get("flag_ties", 0))
-        t.dump()
-    return t
-
-
-# Share of the compared lidar beams with a hit (oracle value < 1), respawn traffic, from oracle-only runs of the same inputs
-# (profiles/parity_ties.md): ego driving 26 %, floor 10 %; ego parked: see PARKED_HIT_SHARE, floor half of it.  Trigger mode: ~0.2 %,
-# printed only.
-DRIVING_HIT_FLOOR = 0.10
-PARKED_HIT_SHARE = 0.1276  # tests/test_ties_cpu.py::test_parked_respawn_hit_share holds this figure to the oracle
-PARKED_HIT_FLOOR = 0.5 * PARKED_HIT_SHARE
 
 
 @pytest.mark.parametrize("num_traffic,num_lasers,traffic_mode,ego", [
@@ -286,7 +25,7 @@ def test_teacher_forced_parity(descs, num_traffic, num_lasers, traffic_mode, ego
     no beam hits anything; respawn traffic (every IDM vehicle drives from step 0) exercises the lidar: once with the ego parked (long
     episodes, the traffic drives past: leader, lane-change and beam decisions) and once with the ego driving (it ends in the jam every
     few steps: contacts in every sub-step)."""
-    _teacher_forced(descs, num_traffic, num_lasers, traffic_mode=traffic_mode, ego=ego)
+    parity.single_teacher_forced(descs, num_traffic, num_lasers, traffic_mode=traffic_mode, ego=ego)
 
 
 @pytest.mark.parametrize("idm_agent", [False, True])
@@ -296,130 +35,84 @@ def test_idm_steer_lag_parity(descs, idm_agent):
     parity with the lag on, respawn traffic (every IDM vehicle drives), with and without the ego under the IDM policy; the applied
     steering (SF_STEER) stays inside [-1, 1] and differs from the raw command of the action deque (SF_ACT1S)."""
     n_envs = 96
-    torch, eng, ora, cfg = _engines(descs, n_envs, n_maps=16, seed=4, traffic_mode="respawn", idm_steer_lag=0.2, idm_agent=int(idm_agent))
+    eng, ora, cfg = parity.engines(descs, n_envs, n_maps=16, seed=4, traffic_mode="respawn", idm_steer_lag=0.2, idm_agent=int(idm_agent))
     assert "specialised" not in (eng.describe_step() or "")
     ids = np.arange(n_envs) % 16
     assert np.abs(eng.reset(ids).cpu().numpy() - ora.reset(ids)).max() < OBS_TOL
     rng = np.random.default_rng(31)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    stats = parity.new_stats()
     worst = {}
     lagged = 0
-    for t in range(250):
-        act = util.driving_actions(rng, n_envs) * (0.0 if not idm_agent else 1.0)  # (a parked ego keeps the respawn jam from restarting the env every step)
-        _compare_step(torch, eng, ora, act, stats)
-        f, i, ei = ora.get_state()
-        gf, gi, gei = eng.get_state()
-        agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
-        tie = util.idm_tie(gf, f, stats["ties"].mg)
-        stats["ties"].add_slots("LEADER", tie & agree, stats["ties"].mg)
-        util.compare_state(gf, f, agree & ~tie, worst)
+    # (a parked ego keeps the respawn jam from restarting the env every step)
+    for s in parity.teacher_forced(eng, ora, stats, 250, lambda t: util.driving_actions(rng, n_envs) * (0.0 if not idm_agent else 1.0)):
+        agree = s.agree
+        tie = s.idm_tie(agree)
+        s.compare_state(agree & ~tie, worst)
         assert (~agree).sum() == 0
-        drv = gi[_abi.SI["STATUS"]] == _abi.ST_ACTIVE
+        drv = s.gi[_abi.SI["STATUS"]] == _abi.ST_ACTIVE
         drv[:, 0] &= bool(idm_agent)
-        st, cmd = gf[_abi.SF["STEER"]][drv], gf[_abi.SF["ACT1S"]][drv]
+        st, cmd = s.gf[_abi.SF["STEER"]][drv], s.gf[_abi.SF["ACT1S"]][drv]
         assert (np.abs(st) <= 1.0 + 1e-6).all()
         lagged += int((np.abs(st - np.clip(cmd, -1, 1)) > 1e-3).sum())
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
     print("steer lag parity:", stats, {k: round(v, 3) for k, v in worst.items()})
-    _report("steer lag parity", stats)
+    parity.report("steer lag parity", stats)
     assert "specialised" not in eng.describe_step()
     assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
     assert not util.state_failures(worst), util.state_failures(worst)
     assert lagged > 1000
-    eng.close()
 
 
-def test_throughput_mode_parity(descs, monkeypatch):
+def test_throughput_mode_parity(descs):
     """Throughput mode (engines with >= 32768 envs, or PGD_PACK=1): one vehicle per lane, three whole envs of 17 slots per wave,
     the lidar rows of the wave's envs appended to the same launch (k_step<ONE_ENV = false> + pack_obs).  Same teacher-forced
     comparison against the oracle, with an env count that leaves the last wave partly empty, auto-reset with re-drawn
     scenarios; then free-running against the default kernel: flags / done / integer state bit-identical."""
-    monkeypatch.setenv("PGD_PACK", "1")
     n_envs = 65
-    torch, eng, ora, cfg = _engines(descs, n_envs, seed=3, resample_scenario=1)
+    eng, ora, cfg = parity.engines(descs, n_envs, env=dict(PGD_PACK="1"), seed=3, resample_scenario=1)
     ids = np.arange(n_envs) % 8
     assert np.abs(eng.reset(ids).cpu().numpy() - ora.reset(ids)).max() < OBS_TOL
     rng = np.random.default_rng(12)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    stats = parity.new_stats()
     worst = {}
     n_done = 0
-    for t in range(300):
-        act = util.driving_actions(rng, n_envs)
-        if t % 4 == 0:
-            act[::3, 0, :] = 1.0
-        n_done += int(_compare_step(torch, eng, ora, act, stats).sum())
-        f, i, ei = ora.get_state()
-        gf, gi, gei = eng.get_state()
-        agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
-        tie = util.idm_tie(gf, f, stats["ties"].mg)
-        tie[:, :1] = False
-        stats["ties"].add_slots("LEADER", tie & agree, stats["ties"].mg)
-        util.compare_state(gf, f, agree & ~tie, worst)
+    for s in parity.teacher_forced(eng, ora, stats, 300, parity.driving_with_bursts(rng, n_envs)):
+        n_done += int(s.o_done.sum())
+        agree = s.agree
+        tie = s.idm_tie(agree, skip_slots=1)
+        s.compare_state(agree & ~tie, worst)
         assert (~agree).sum() == 0
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
     print("throughput mode parity:", stats, "episodes", n_done, "state fields (x tolerance):", {k: round(v, 3) for k, v in worst.items()})
-    _report("throughput mode parity", stats)
+    parity.report("throughput mode parity", stats)
     assert stats["obs"] < OBS_TOL and stats["obs_state"] < STATE_OBS_TOL and stats["rew"] < REW_TOL
     assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and n_done > 20
     assert not util.state_failures(worst), util.state_failures(worst)
     assert stats.get("grazing", 0) <= 1e-5 * stats.get("beams", 1) + 2
-    monkeypatch.setenv("PGD_PACK", "0")
-    _, one, _, _ = _engines(descs, n_envs, seed=3, resample_scenario=1)
+    one, _, _ = parity.engines(descs, n_envs, env=dict(PGD_PACK="0"), seed=3, resample_scenario=1)
     eng.reset(ids); one.reset(ids)
-    for t in range(200):
-        act = util.driving_actions(rng, n_envs)
-        f, i, ei = one.get_state()
-        eng.set_state(f, i, ei)
-        a = torch.from_numpy(act).to(one.device)
-        o1, r1, d1, f1 = [x.clone() for x in one.step(a)]
-        o2, r2, d2, f2 = [x.clone() for x in eng.step(a)]
-        one.sync(); eng.sync()
-        assert torch.equal(d1, d2) and torch.equal(f1, f2), "flags differ at step %d" % t
-        assert float((o1 - o2).abs().max()) < 2e-6 and float((r1 - r2).abs().max()) < 2e-5
-        _, i1, e1 = one.get_state()
-        _, i2, e2 = eng.get_state()
-        assert (i1 == i2).all() and (e1 == e2).all(), "integer state differs at step %d" % t
+    for t, outs_one, outs_eng in parity.twins(one, eng, 200, lambda t: util.driving_actions(rng, n_envs), copy_state=one):
+        parity.same_outcome(t, outs_one, outs_eng, one, eng, obs_tol=2e-6, rew_tol=2e-5)  # (the float state is not compared here)
 
 
 @pytest.mark.parametrize("pack", ["0", "1"])
 @pytest.mark.parametrize("traffic_mode", ["trigger", "respawn"])
-def test_default_configuration_kernel_matches_the_general_kernel(descs, monkeypatch, pack, traffic_mode):
+def test_default_configuration_kernel_matches_the_general_kernel(descs, pack, traffic_mode):
     """pgd_step launches an instantiation of k_step specialised for the reference's default single-agent configuration (the
     configuration values are compile-time constants in it) whenever the engine's configuration is exactly that; PGD_NO_FIX=1
     keeps the general kernel.  Same state, same actions: flags, done and the integer state are bit-identical, observation and
     reward agree to rounding (constant folding reorders a few fp32 operations).  Any other configuration gets the general kernel."""
-    monkeypatch.setenv("PGD_PACK", pack)
+    import torch
     n_envs = 65
-    monkeypatch.delenv("PGD_NO_FIX", raising=False)
-    torch, fix, _, _ = _engines(descs, n_envs, seed=3, resample_scenario=1, traffic_mode=traffic_mode)
-    _, other, _, _ = _engines(descs, n_envs, seed=3, resample_scenario=1, traffic_mode=traffic_mode, num_lasers=120)
-    monkeypatch.setenv("PGD_NO_FIX", "1")
-    _, gen, _, _ = _engines(descs, n_envs, seed=3, resample_scenario=1, traffic_mode=traffic_mode)
+    kw = dict(seed=3, resample_scenario=1, traffic_mode=traffic_mode)
+    fix, _, _ = parity.engines(descs, n_envs, env=dict(PGD_PACK=pack, PGD_NO_FIX=None), **kw)
+    other, _, _ = parity.engines(descs, n_envs, env=dict(PGD_PACK=pack, PGD_NO_FIX=None), num_lasers=120, **kw)
+    gen, _, _ = parity.engines(descs, n_envs, env=dict(PGD_PACK=pack, PGD_NO_FIX="1"), **kw)
     ids = np.arange(n_envs) % 8
     fix.reset(ids); gen.reset(ids); other.reset(ids)
     rng = np.random.default_rng(21)
     n_done = 0
-    for t in range(300):
-        act = util.driving_actions(rng, n_envs)
-        if t % 4 == 0:
-            act[::3, 0, :] = 1.0
-        f, i, ei = gen.get_state()
-        fix.set_state(f, i, ei)
-        a = torch.from_numpy(act).to(gen.device)
-        o1, r1, d1, f1 = [x.clone() for x in gen.step(a)]
-        o2, r2, d2, f2 = [x.clone() for x in fix.step(a)]
-        gen.sync(); fix.sync()
-        assert torch.equal(d1, d2) and torch.equal(f1, f2), "flags differ at step %d" % t
-        assert float((o1 - o2).abs().max()) < 2e-6 and float((r1 - r2).abs().max()) < 2e-5
-        g1, i1, e1 = gen.get_state()
-        g2, i2, e2 = fix.get_state()
-        assert (i1 == i2).all() and (e1 == e2).all(), "integer state differs at step %d" % t
-        assert np.abs(g1 - g2).max() < 1e-4
-        n_done += int(d1.sum())
+    for t, outs_gen, outs_fix in parity.twins(gen, fix, 300, parity.driving_with_bursts(rng, n_envs), copy_state=gen):
+        parity.same_outcome(t, outs_gen, outs_fix, gen, fix, obs_tol=2e-6, rew_tol=2e-5, state_tol=1e-4)
+        n_done += int(outs_gen[2].sum())
     assert n_done > 20
     other.step(torch.from_numpy(util.driving_actions(rng, n_envs)).to(other.device)); other.sync()
     assert "specialised for the default" in fix.describe_step()
@@ -428,13 +121,14 @@ def test_default_configuration_kernel_matches_the_general_kernel(descs, monkeypa
 
 
 @pytest.mark.parametrize("variant", ["top_down", "safe"])
-def test_env_class_instantiations_match_the_general_kernel(descs, monkeypatch, variant):
+def test_env_class_instantiations_match_the_general_kernel(descs, variant):
     """Round 6: the configurations the shipped env classes produce besides the default one have their own
     instantiations of k_step -- the top-down envs' (envs/top_down_env.py:8-72: lidar off, the row is the 18 state floats)
     and SafePGDriveEnv's (envs/safe_pgdrive_env.py:9-26: 16 traffic + 40 object slots, crashes are costs).  Same protocol as the
     default configuration's test: against the general kernel (PGD_NO_FIX=1) from the same state with the same actions, flags / done /
     integer state bit-identical, floats to rounding; pgd_describe_step names the instantiation; a neighbouring configuration (another
     slot count) still gets the general kernel."""
+    import torch
     n_envs = 65
     kw = dict(seed=3, resample_scenario=1)
     if variant == "top_down":
@@ -445,40 +139,22 @@ def test_env_class_instantiations_match_the_general_kernel(descs, monkeypatch, v
         kw.update(num_traffic=56, accident_prob=0.8, safe_rl_env=True, density=0.05, use_lateral=False)
         other_kw = dict(kw, num_traffic=46)
         name = "specialised for the SafePGDriveEnv"
-    monkeypatch.delenv("PGD_NO_FIX", raising=False)
-    torch, fix, _, _ = _engines(descs, n_envs, n_maps=16, **kw)
-    _, other, _, _ = _engines(descs, n_envs, n_maps=16, **other_kw)
-    monkeypatch.setenv("PGD_NO_FIX", "1")
-    _, gen, _, _ = _engines(descs, n_envs, n_maps=16, **kw)
+    fix, _, _ = parity.engines(descs, n_envs, n_maps=16, env=dict(PGD_NO_FIX=None), **kw)
+    other, _, _ = parity.engines(descs, n_envs, n_maps=16, env=dict(PGD_NO_FIX=None), **other_kw)
+    gen, _, _ = parity.engines(descs, n_envs, n_maps=16, env=dict(PGD_NO_FIX="1"), **kw)
     ids = np.arange(n_envs) % 16
     fix.reset(ids); gen.reset(ids); other.reset(ids)
     rng = np.random.default_rng(22)
     n_done = n_obj = 0
-    for t in range(300):
-        act = util.driving_actions(rng, n_envs)
-        if t % 4 == 0:
-            act[::3, 0, :] = 1.0
-        f, i, ei = gen.get_state()
-        fix.set_state(f, i, ei)
-        a = torch.from_numpy(act).to(gen.device)
-        o1, r1, d1, f1 = [x.clone() for x in gen.step(a)]
-        o2, r2, d2, f2 = [x.clone() for x in fix.step(a)]
-        gen.sync(); fix.sync()
-        assert torch.equal(d1, d2) and torch.equal(f1, f2), "flags differ at step %d" % t
-        assert float((o1 - o2).abs().max()) < 2e-6 and float((r1 - r2).abs().max()) < 2e-5
-        g1, i1, e1 = gen.get_state()
-        g2, i2, e2 = fix.get_state()
-        assert (i1 == i2).all() and (e1 == e2).all(), "integer state differs at step %d" % t
-        assert np.abs(g1 - g2).max() < 1e-4
-        n_done += int(d1.sum())
-        n_obj += int(((f1 & _abi.F_CRASH_OBJECT) != 0).sum())
+    for t, outs_gen, outs_fix in parity.twins(gen, fix, 300, parity.driving_with_bursts(rng, n_envs), copy_state=gen):
+        parity.same_outcome(t, outs_gen, outs_fix, gen, fix, obs_tol=2e-6, rew_tol=2e-5, state_tol=1e-4)
+        n_done += int(outs_gen[2].sum())
+        n_obj += int(((outs_gen[3] & _abi.F_CRASH_OBJECT) != 0).sum())
     assert n_done > 10 and (variant != "safe" or n_obj > 0)
     other.step(torch.from_numpy(util.driving_actions(rng, n_envs)).to(other.device)); other.sync()
     assert name in fix.describe_step(), fix.describe_step()
     assert "specialised" not in gen.describe_step() and "specialised" not in other.describe_step()
     assert fix.D == (18 if variant == "top_down" else 274)
-    for e in (fix, gen, other):
-        e.close()
 
 
 @pytest.mark.parametrize("variant", ["lasers72_traffic12", "discrete_fans_noise", "objects"])
@@ -489,9 +165,8 @@ def test_run_time_kernel_matches_the_general_kernel(descs, monkeypatch, tmp_path
     AOT instantiations' tests: against the general kernel from the same state with the same actions, flags / done / integer state
     bit-identical, floats to rounding, through auto-resets with re-drawn scenarios; pgd_describe_step names it; unloading the module
     (null path) puts the general kernel back."""
-    import ctypes as C
-    monkeypatch.setenv("PGD_JIT_DIR", str(tmp_path))
-    monkeypatch.delenv("PGD_NO_FIX", raising=False)
+    import torch
+    monkeypatch.setenv("PGD_JIT_DIR", str(tmp_path))  # (read by pgdrive_amd/jit.py when the kernel is built, not by the constructor)
     n_envs = 65
     kw = dict(seed=3, resample_scenario=1)
     if variant == "lasers72_traffic12":
@@ -500,41 +175,33 @@ def test_run_time_kernel_matches_the_general_kernel(descs, monkeypatch, tmp_path
         kw.update(discrete_action=True, side_lasers=4, lane_line_lasers=2, lidar_gaussian_noise=0.02, lidar_dropout_prob=0.05, horizon=150)
     else:
         kw.update(num_traffic=30, accident_prob=0.8, density=0.05)
-    torch, jit_eng, _, _ = _engines(descs, n_envs, n_maps=16, **kw)
-    _, gen, _, _ = _engines(descs, n_envs, n_maps=16, **kw)
+    jit_eng, _, _ = parity.engines(descs, n_envs, n_maps=16, env=dict(PGD_NO_FIX=None), **kw)
+    gen, _, _ = parity.engines(descs, n_envs, n_maps=16, env=dict(PGD_NO_FIX=None), **kw)
     assert jit_eng.specialise(wait=True) is True
     assert any(f.endswith(".hsaco") for f in os.listdir(str(tmp_path)))
     ids = np.arange(n_envs) % 16
     jit_eng.reset(ids); gen.reset(ids)
     rng = np.random.default_rng(23)
     n_done = 0
-    for t in range(300):
+
+    def actions(t):
         act = util.driving_actions(rng, n_envs)
         if variant == "discrete_fans_noise":
             act = rng.integers(0, 5, size=(n_envs, 1, 2)).astype(np.float32)
             act[:, 0, 1] = np.maximum(act[:, 0, 1], 2.0)
         elif t % 4 == 0:
             act[::3, 0, :] = 1.0
-        f, i, ei = gen.get_state()
-        jit_eng.set_state(f, i, ei)
-        a = torch.from_numpy(act).to(gen.device)
-        o1, r1, d1, f1 = [x.clone() for x in gen.step(a)]
-        o2, r2, d2, f2 = [x.clone() for x in jit_eng.step(a)]
-        gen.sync(); jit_eng.sync()
-        assert torch.equal(d1, d2) and torch.equal(f1, f2), "flags differ at step %d" % t
-        assert float((o1 - o2).abs().max()) < 2e-6 and float((r1 - r2).abs().max()) < 2e-5
-        g1, i1, e1 = gen.get_state()
-        g2, i2, e2 = jit_eng.get_state()
-        assert (i1 == i2).all() and (e1 == e2).all(), "integer state differs at step %d" % t
-        assert np.abs(g1 - g2).max() < 1e-4
-        n_done += int(d1.sum())
+        actions.last = act
+        return act
+
+    for t, outs_gen, outs_jit in parity.twins(gen, jit_eng, 300, actions, copy_state=gen):
+        parity.same_outcome(t, outs_gen, outs_jit, gen, jit_eng, obs_tol=2e-6, rew_tol=2e-5, state_tol=1e-4)
+        n_done += int(outs_gen[2].sum())
     assert n_done > 10
     assert "at run time" in jit_eng.describe_step() and "specialised" not in gen.describe_step()
     assert jit_eng.L.pgd_set_step_module(jit_eng.h, None, 0, 0) == 0
-    jit_eng.step(a); jit_eng.sync()
+    jit_eng.step(torch.from_numpy(actions.last).to(jit_eng.device)); jit_eng.sync()
     assert "specialised" not in jit_eng.describe_step()
-    for e in (jit_eng, gen):
-        e.close()
 
 
 def test_run_time_kernel_is_refused_where_it_does_not_apply(descs, monkeypatch, tmp_path):
@@ -543,22 +210,16 @@ def test_run_time_kernel_is_refused_where_it_does_not_apply(descs, monkeypatch, 
     module loaded (the module only ever replaces a GENERAL kernel)."""
     monkeypatch.setenv("PGD_JIT_DIR", str(tmp_path))
     import torch
-    from pgdrive_amd.engine import Engine
     d, mb, sb = util.make_marl_banks(num_agents=8, capacity=12, kind="roundabout")
-    marl = Engine(util.marl_config(16, sb, horizon=120), mb, sb)
+    marl = parity.engine(util.marl_config(16, sb, horizon=120), mb, sb)
     assert marl.specialise() is False
-    marl.close()
-    monkeypatch.setenv("PGD_PACK", "1")
-    _, pack, _, _ = _engines(descs, 66, seed=1)
+    pack, _, _ = parity.engines(descs, 66, env=dict(PGD_PACK="1"), seed=1)
     assert pack.specialise() is False
-    pack.close()
-    monkeypatch.setenv("PGD_PACK", "0")
-    _, dflt, _, _ = _engines(descs, 64, seed=1)
+    dflt, _, _ = parity.engines(descs, 64, env=dict(PGD_PACK="0"), seed=1)
     assert dflt.specialise() is True  # (built and loaded ...)
     dflt.reset(np.arange(64) % 8)
     dflt.step(torch.zeros((64, 1, 2), device="cuda")); dflt.sync()
     assert "specialised for the default single-agent configuration" in dflt.describe_step()  # (... and not used: the AOT instantiation runs)
-    dflt.close()
     assert len([f for f in os.listdir(str(tmp_path)) if f.endswith(".hsaco")]) == 1
 
 
@@ -567,11 +228,10 @@ def test_multi_agent_env_groups_step_like_one_batch():
     kernel and the four-wave observation kernel of a group run on the group's stream over the group's envs only -- and leave, group
     by group and in any order, exactly the bytes one launch over the whole batch leaves, through finishes and respawns."""
     import torch
-    from pgdrive_amd.engine import Engine
     d, mb, sb = util.make_marl_banks(num_agents=40, capacity=40, kind="roundabout")
     n_envs = 64
     cfg = util.marl_config(n_envs, sb, horizon=120)
-    one, two = Engine(cfg, mb, sb), Engine(cfg, mb, sb)
+    one, two = parity.engine(cfg, mb, sb), parity.engine(cfg, mb, sb)
     ids = np.arange(n_envs) % 8
     one.reset(ids); two.reset(ids)
     two.set_groups(2)
@@ -592,7 +252,7 @@ def test_multi_agent_env_groups_step_like_one_batch():
     assert "40 agent seats" in one.describe_step() and "40 agent seats" in two.describe_step()
     # the same from the env surface (MultiAgent*VecEnv.set_groups / step_group / group_sync)
     from pgdrive_amd import MultiAgentRoundaboutVecEnv
-    e1, e2 = (MultiAgentRoundaboutVecEnv(dict(num_envs=16, num_agents=40, seed=3)) for _ in range(2))
+    e1, e2 = (parity.closing(MultiAgentRoundaboutVecEnv(dict(num_envs=16, num_agents=40, seed=3))) for _ in range(2))
     e1.reset(); e2.reset()
     e2.set_groups(2)
     for t in range(40):
@@ -603,15 +263,13 @@ def test_multi_agent_env_groups_step_like_one_batch():
             e2.group_sync(g)
             sl = e2.group_slice(g)
             assert torch.equal(og, o[sl]) and torch.equal(rg, r[sl]) and torch.equal(dg, dn[sl]) and torch.equal(fg, fl[sl])
-    e1.close(); e2.close()
     f1, i1, e1 = one.get_state()
     f2, i2, e2 = two.get_state()
     assert (i1 == i2).all() and (e1 == e2).all() and np.array_equal(f1, f2)
-    one.close(); two.close()
 
 
 @pytest.mark.parametrize("agents,seats,beams", [(8, 12, 72), (40, 40, 72), (40, 44, 72), (8, 8, 72), (8, 8, 240)])
-def test_default_multi_agent_kernel_matches_the_general_kernel(monkeypatch, agents, seats, beams):
+def test_default_multi_agent_kernel_matches_the_general_kernel(agents, seats, beams):
     """Multi-agent engines with the scalar fields of MULTI_AGENT_PGDRIVE_DEFAULT_CONFIG get their own instantiation of k_step (those
     fields are compile-time constants in it; agent count, spawn places and horizon stay run-time values) -- and, round 6, the seat
     counts the reference's default agent number produces (40: the vec env; 44: the dict-keyed envs' spare seats) instantiations with
@@ -619,28 +277,18 @@ def test_default_multi_agent_kernel_matches_the_general_kernel(monkeypatch, agen
     of BASELINE.json's multi-agent configuration with 72 and with 240 beams (the observation fused into the step).  Against the
     general kernels (PGD_NO_FIX=1) from the same state with the same actions: flags, done, integer state identical, floats to rounding."""
     import torch
-    from pgdrive_amd.engine import Engine
     d, mb, sb = util.make_marl_banks(num_agents=agents, capacity=seats, kind="roundabout")
     n_envs = 32
     cfg = util.marl_config(n_envs, sb, horizon=120, num_lasers=beams)
-    monkeypatch.delenv("PGD_NO_FIX", raising=False)
-    fix = Engine(cfg, mb, sb)
-    other = Engine(util.marl_config(n_envs, sb, horizon=120, delay_done=10, num_lasers=beams), mb, sb)
-    monkeypatch.setenv("PGD_NO_FIX", "1")
-    gen = Engine(cfg, mb, sb)
+    fix = parity.engine(cfg, mb, sb, env=dict(PGD_NO_FIX=None))
+    other = parity.engine(util.marl_config(n_envs, sb, horizon=120, delay_done=10, num_lasers=beams), mb, sb, env=dict(PGD_NO_FIX=None))
+    gen = parity.engine(cfg, mb, sb, env=dict(PGD_NO_FIX="1"))
     ids = np.arange(n_envs) % 8
     fix.reset(ids); gen.reset(ids); other.reset(ids)
     rng = np.random.default_rng(5)
     n_done = n_new = n_graze = 0
-    for t in range(300):
-        act = util.marl_actions(rng, n_envs, sb.A)
-        f, i, ei = gen.get_state()
-        fix.set_state(f, i, ei)
-        a = torch.from_numpy(act).to(gen.device)
-        o1, r1, d1, f1 = [x.clone() for x in gen.step(a)]
-        o2, r2, d2, f2 = [x.clone() for x in fix.step(a)]
-        gen.sync(); fix.sync()
-        assert torch.equal(d1, d2) and torch.equal(f1, f2), "flags differ at step %d" % t
+    for t, (o1, r1, d1, f1), (o2, r2, d2, f2) in parity.twins(gen, fix, 300, lambda t: util.marl_actions(rng, n_envs, sb.A), copy_state=gen):
+        parity.same_outcome(t, (o1, r1, d1, f1), (o2, r2, d2, f2), gen, fix)  # (floats: below, on the rows that are due, grazing beams counted)
         rep = ((f1 & (_abi.F_REPORT | _abi.F_NEW)) != 0)
         dd = (o1 - o2).abs() * rep[..., None]
         # (a beam that grazes a box corner is a hit in one instantiation and a miss in the other -- the slab test compares two nearly
@@ -652,17 +300,12 @@ def test_default_multi_agent_kernel_matches_the_general_kernel(monkeypatch, agen
         n_graze += int(flip.sum())
         dd[..., 18:][flip] = 0.0
         assert float(dd.max()) < 2e-6 and float(((r1 - r2).abs() * rep).max()) < 2e-5
-        g1, i1, e1 = gen.get_state()
-        g2, i2, e2 = fix.get_state()
-        assert (i1 == i2).all() and (e1 == e2).all(), "integer state differs at step %d" % t
         n_done += int(d1.sum()); n_new += int(((f1 & _abi.F_NEW) != 0).sum())
     assert n_done > 20 and n_new > 20 and n_graze <= 3, n_graze
     other.step(torch.from_numpy(util.marl_actions(rng, n_envs, sb.A)).to(other.device)); other.sync()
     assert "specialised for the default multi-agent" in fix.describe_step()
     assert ("%d agent seats x %d beams" % (seats, beams) in fix.describe_step()) == (seats in (40, 44, 8)), fix.describe_step()
     assert "specialised" not in gen.describe_step() and "specialised" not in other.describe_step()
-    for e in (fix, gen, other):
-        e.close()
 
 
 @pytest.mark.parametrize("traffic_mode", ["trigger", "hybrid"])
@@ -673,77 +316,54 @@ def test_step_hints_match_the_unhinted_path(descs, traffic_mode):
     written back before every step (always the unhinted path) must stay bit-identical: observations, rewards, flags, state --
     through traffic activations, crashes and auto-resets with re-drawn scenarios."""
     n_envs = 96
-    torch, a, _, _ = _engines(descs, n_envs, seed=9, resample_scenario=1, traffic_mode=traffic_mode)
-    _, b, _, _ = _engines(descs, n_envs, seed=9, resample_scenario=1, traffic_mode=traffic_mode)
+    a, _, _ = parity.engines(descs, n_envs, seed=9, resample_scenario=1, traffic_mode=traffic_mode)
+    b, _, _ = parity.engines(descs, n_envs, seed=9, resample_scenario=1, traffic_mode=traffic_mode)
     ids = np.arange(n_envs) % 8
     a.reset(ids); b.reset(ids)
     rng = np.random.default_rng(33)
     n_done = activations = 0
     prev_pending = None
-    for t in range(600):
-        act = util.driving_actions(rng, n_envs)
-        at = torch.from_numpy(act).to(a.device)
-        f, i, ei = b.get_state()
-        b.set_state(f, i, ei)  # hint word back to "unknown"
-        o1, r1, d1, f1 = [x.clone() for x in a.step(at)]
-        o2, r2, d2, f2 = [x.clone() for x in b.step(at)]
-        a.sync(); b.sync()
-        assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2) and torch.equal(f1, f2), "step %d" % t
-        fa, ia, ea = a.get_state()
-        fb, ib, eb = b.get_state()
-        assert (ia == ib).all() and (ea == eb).all() and np.array_equal(fa, fb), "state differs at step %d" % t
-        pending = (ia[_abi.SI["STATUS"]] == _abi.ST_PENDING).sum()
+    # (b's own state written back before every step: the hint word back to "unknown")
+    for t, outs_a, outs_b in parity.twins(a, b, 600, lambda t: util.driving_actions(rng, n_envs), copy_state=b):
+        parity.same_bits(t, outs_a, outs_b, a, b)
+        pending = (a.get_state()[1][_abi.SI["STATUS"]] == _abi.ST_PENDING).sum()
         if prev_pending is not None and pending < prev_pending:
             activations += 1
         prev_pending = pending
-        n_done += int(d1.sum())
+        n_done += int(outs_a[2].sum())
     assert n_done > 30 and activations > 10
 
 
-def test_ego_only_kernel_matches_the_general_kernel(descs, monkeypatch):
+def test_ego_only_kernel_matches_the_general_kernel(descs):
     """BASELINE config 2 (the ego alone, no lidar: dynamics + reward + the 18-float state vector) has its own instantiation of k_step
     too (four envs per wave, configuration compiled in).  Against the general kernel from the same state with the same actions."""
     n_envs = 130  # the last wave is partly empty
-    monkeypatch.delenv("PGD_NO_FIX", raising=False)
-    torch, fix, _, _ = _engines(descs, n_envs, seed=3, resample_scenario=1, num_traffic=0, num_lasers=0)
-    monkeypatch.setenv("PGD_NO_FIX", "1")
-    _, gen, _, _ = _engines(descs, n_envs, seed=3, resample_scenario=1, num_traffic=0, num_lasers=0)
+    fix, _, _ = parity.engines(descs, n_envs, env=dict(PGD_NO_FIX=None), seed=3, resample_scenario=1, num_traffic=0, num_lasers=0)
+    gen, _, _ = parity.engines(descs, n_envs, env=dict(PGD_NO_FIX="1"), seed=3, resample_scenario=1, num_traffic=0, num_lasers=0)
     ids = np.arange(n_envs) % 8
     fix.reset(ids); gen.reset(ids)
     rng = np.random.default_rng(4)
     n_done = 0
-    for t in range(400):
-        act = util.driving_actions(rng, n_envs)
-        f, i, ei = gen.get_state()
-        fix.set_state(f, i, ei)
-        a = torch.from_numpy(act).to(gen.device)
-        o1, r1, d1, f1 = [x.clone() for x in gen.step(a)]
-        o2, r2, d2, f2 = [x.clone() for x in fix.step(a)]
-        gen.sync(); fix.sync()
-        assert torch.equal(d1, d2) and torch.equal(f1, f2), "flags differ at step %d" % t
-        assert float((o1 - o2).abs().max()) < 2e-6 and float((r1 - r2).abs().max()) < 2e-5
-        g1, i1, e1 = gen.get_state()
-        g2, i2, e2 = fix.get_state()
-        assert (i1 == i2).all() and (e1 == e2).all() and np.abs(g1 - g2).max() < 1e-4
-        n_done += int(d1.sum())
-    assert n_done > 20 and o1.shape[-1] == 18
+    for t, outs_gen, outs_fix in parity.twins(gen, fix, 400, lambda t: util.driving_actions(rng, n_envs), copy_state=gen):
+        parity.same_outcome(t, outs_gen, outs_fix, gen, fix, obs_tol=2e-6, rew_tol=2e-5, state_tol=1e-4)
+        n_done += int(outs_gen[2].sum())
+    assert n_done > 20 and outs_gen[0].shape[-1] == 18
     assert "specialised for the ego-only" in fix.describe_step() and "specialised" not in gen.describe_step()
 
 
-def test_run_time_reward_kernel_matches_the_general_kernel_and_the_oracle(descs, monkeypatch):
+def test_run_time_reward_kernel_matches_the_general_kernel_and_the_oracle(descs):
     """Default geometry, own reward scheme (what training set-ups change first): k_step runs the instantiation with the geometry
     compiled in and the reward scheme read at run time.  Teacher-forced against the oracle, and against the general kernel."""
+    import torch
     kw = dict(success_reward=20.0, use_lateral=True, speed_reward=0.3, out_of_road_penalty=7.0)
     n_envs = 64
-    monkeypatch.delenv("PGD_NO_FIX", raising=False)
-    torch, eng, ora, cfg = _engines(descs, n_envs, seed=5, **kw)
-    monkeypatch.setenv("PGD_NO_FIX", "1")
-    _, gen, _, _ = _engines(descs, n_envs, seed=5, **kw)
+    eng, ora, cfg = parity.engines(descs, n_envs, env=dict(PGD_NO_FIX=None), seed=5, **kw)
+    gen, _, _ = parity.engines(descs, n_envs, env=dict(PGD_NO_FIX="1"), seed=5, **kw)
     ids = np.arange(n_envs) % 8
     assert np.abs(eng.reset(ids).cpu().numpy() - ora.reset(ids)).max() < OBS_TOL
     gen.reset(ids)
     rng = np.random.default_rng(8)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    stats = parity.new_stats()
     n_done = 0
     for t in range(300):
         act = util.driving_actions(rng, n_envs)
@@ -751,65 +371,15 @@ def test_run_time_reward_kernel_matches_the_general_kernel_and_the_oracle(descs,
         f32 = util.round_state_f32(f)
         gen.set_state(f32, i, ei)
         r_gen = gen.step(torch.from_numpy(act).to(gen.device))[1].clone()
-        n_done += int(_compare_step(torch, eng, ora, act, stats).sum())
+        n_done += int(parity.compare_step(eng, ora, act, stats).sum())
         gen.sync()
         assert float((r_gen - eng.reward).abs().max()) < 2e-5
         f, i, ei = ora.get_state()
         f32 = util.round_state_f32(f)
         ora.set_state(f32, i, ei); eng.set_state(f32, i, ei)
-    _report("run-time reward kernel parity", stats)
+    parity.report("run-time reward kernel parity", stats)
     assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and n_done > 10
     assert "run-time reward scheme" in eng.describe_step() and "specialised" not in gen.describe_step()
-
-
-def _teacher_forced(descs, num_traffic, num_lasers, traffic_mode="trigger", ego="driving"):
-    n_envs = 64
-    torch, eng, ora, cfg = _engines(descs, n_envs, num_traffic=num_traffic, num_lasers=num_lasers, traffic_mode=traffic_mode)
-    scen_ids = np.arange(n_envs) % 8
-    o0 = ora.reset(scen_ids)
-    g0 = eng.reset(scen_ids).cpu().numpy()
-    assert np.abs(g0 - o0).max() < OBS_TOL
-    rng = np.random.default_rng(0)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
-    pose = 0.0
-    worst = {}  # every float field of the state, in units of its tolerance (tests/util.py STATE_TOL)
-    idm_ties = active = 0
-    for t in range(400):
-        act = util.driving_actions(rng, n_envs) * (0.0 if ego == "parked" else 1.0)
-        _compare_step(torch, eng, ora, act, stats)
-        f, i, ei = ora.get_state()
-        gf, gi, gei = eng.get_state()
-        agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
-        # an IDM leader exactly MAX_DIST = 30 m ahead on the 10 m spawn grid is found / not found by the last bit of a lane
-        # coordinate: that vehicle gets another throttle on the two sides (counted and bounded, as in the campaign) -- where the
-        # oracle's LEADER margin confirms the near-tie; any other differing throttle stays in compare_state
-        tie = util.idm_tie(gf, f, stats["ties"].mg)
-        tie[:, :cfg.num_agents] = False
-        stats["ties"].add_slots("LEADER", tie & agree, stats["ties"].mg)
-        idm_ties += int((tie & agree).sum())
-        active += int((i[_abi.SI["STATUS"]][:, cfg.num_agents:] == _abi.ST_ACTIVE).sum())
-        if agree.any():
-            for fld in ("X", "Y", "THETA", "SPEED"):
-                dlt = np.abs(gf[_abi.SF[fld]].astype(np.float64) - f[_abi.SF[fld]])[agree & ~tie]
-                if fld == "THETA":  # heading_theta lives in [-3 pi / 2, pi / 2): a value on the seam may wrap on one side only
-                    dlt = np.minimum(dlt, np.abs(dlt - 2 * np.pi))
-                pose = max(pose, float(dlt.max()))
-        util.compare_state(gf, f, agree & ~tie, worst)
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
-    print("teacher-forced parity:", traffic_mode, ego, stats, "pose", pose, "idm ties", idm_ties, "of", active,
-          "state fields (x tolerance):", {k: round(v, 3) for k, v in worst.items()})
-    ties = _report("teacher-forced parity", stats)
-    print("n_crash_vehicle", stats["n_crash_vehicle"], "lidar hit share", ties.hits / max(ties.beams, 1))
-    if traffic_mode == "respawn":
-        assert ties.hits >= (PARKED_HIT_FLOOR if ego == "parked" else DRIVING_HIT_FLOOR) * ties.beams
-        assert ego == "parked" or stats["n_crash_vehicle"] > 0
-    assert stats["obs"] < OBS_TOL and stats["obs_state"] < STATE_OBS_TOL and stats["rew"] < REW_TOL and pose < 1e-3
-    assert not util.state_failures(worst), util.state_failures(worst)
-    assert idm_ties <= 2e-3 * max(active, 1) + 2
-    assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0  # done / flags bit-exact (north star); no tie class occurs on these 8 maps
-    assert stats.get("grazing", 0) <= 1e-5 * stats.get("beams", 1) + 2
 
 
 def test_random_lane_width_and_num_maps_parity():
@@ -818,7 +388,7 @@ def test_random_lane_width_and_num_maps_parity():
     from pgdrive_amd import bank
     maps = bank.get_descriptions(range(1000, 1008), random_lane_width=True, random_lane_num=True)
     assert all(m["lane_num"] == 2 for m in maps) and len({round(m["lane_width"], 6) for m in maps}) == 8
-    _teacher_forced(maps, 16, 240)
+    parity.single_teacher_forced(maps, 16, 240)
 
 
 @pytest.mark.parametrize("side,lane_line,num_lasers", [((12, 50.0), (6, 20.0), 240), ((2, 50.0), (2, 50.0), 0),
@@ -828,24 +398,19 @@ def test_side_and_lane_line_detector_parity(descs, side, lane_line, num_lasers):
     (state_obs.py:64-71,96-105): device grid walk vs the oracle's brute force over every line box."""
     n_envs = 64
     ram = num_lasers == 16  # one of the configurations also runs with random_agent_model (vehicle type + 2 state floats)
-    torch, eng, ora, cfg = _engines(descs, n_envs, num_lasers=num_lasers, side_lasers=side[0], side_dist=side[1],
+    eng, ora, cfg = parity.engines(descs, n_envs, num_lasers=num_lasers, side_lasers=side[0], side_dist=side[1],
                                     lane_line_lasers=lane_line[0], lane_line_dist=lane_line[1], random_agent_model=ram)
     assert eng.D == (side[0] or 2) + 6 + lane_line[0] + (2 if ram else 0) + 10 + 4 * cfg.num_others + num_lasers
     scen_ids = np.arange(n_envs) % 8
     o0 = ora.reset(scen_ids)
     g0 = eng.reset(scen_ids).cpu().numpy()
-    _check_reset_rows(eng, ora, g0, o0, 2)
+    parity.check_reset_rows(eng, ora, g0, o0, 2)
     rng = np.random.default_rng(5)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
-    for t in range(150):
-        act = util.driving_actions(rng, n_envs)
-        _compare_step(torch, eng, ora, act, stats)
-        f, i, ei = ora.get_state()
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
+    stats = parity.new_stats()
+    for _ in parity.teacher_forced(eng, ora, stats, 150, lambda t: util.driving_actions(rng, n_envs)):
+        pass
     print("detector parity:", stats)
-    _report("detector parity", stats)
+    parity.report("detector parity", stats)
     assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL
     assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
     assert stats["det_grazing"] <= 1e-4 * stats["det_beams"] + 2
@@ -856,8 +421,9 @@ def test_side_and_lane_line_detector_parity(descs, side, lane_line, num_lasers):
 def test_action_modes_respawn_traffic_auto_termination(descs, discrete):
     """discrete_action (env_input_policy.py:17-31, converted after the clip as upstream), increment_steering
     (base_vehicle.py:351-358), TrafficMode.Respawn (traffic_manager.py:236-239) and auto_termination (base_env.py:318)."""
+    import torch
     n_envs = 64
-    torch, eng, ora, cfg = _engines(descs, n_envs, discrete_action=discrete, increment_steering=True,
+    eng, ora, cfg = parity.engines(descs, n_envs, discrete_action=discrete, increment_steering=True,
                                     traffic_mode="respawn", auto_termination=True, num_lasers=60)
     scen_ids = np.arange(n_envs) % 8
     o0 = ora.reset(scen_ids)
@@ -870,7 +436,7 @@ def test_action_modes_respawn_traffic_auto_termination(descs, discrete):
     ora.set_state(f, i, ei)
     eng.set_state(util.round_state_f32(f), i, ei)
     rng = np.random.default_rng(11)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    stats = parity.new_stats()
     n_max_step = 0
     for t in range(120):
         if discrete:  # MultiDiscrete([5, 5]) samples; upstream clips them to [-1, 1] BEFORE the conversion, so the
@@ -899,78 +465,43 @@ def test_action_modes_respawn_traffic_auto_termination(descs, discrete):
     assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
 
 
-def _teleport_to_objects(mb, sb, scen_ids, f, i, back=9.0):
-    """Put every env's ego `back` metres (along the lane) behind a traffic object that sits on a road of its route."""
-    from pgdrive_amd import mapdata
-    V = sb.V
-    moved = 0
-    for e, sc in enumerate(scen_ids):
-        sp = sb.spawns[sc * V:(sc + 1) * V]
-        d = mb.descs[int(sb.scenarios["map"][sc])]
-        route = list(sp[0]["ckpt_road"][:sp[0]["n_ckpt"] - 1])
-        for k in range(1, V):
-            if sp[k]["lane"] < 0 or sp[k]["group"] != -2:
-                continue
-            lane = d["lanes"][int(sp[k]["lane"])]
-            if lane["road"] not in route:
-                continue
-            lon, lat = mapdata.lane_local_coordinates(lane, (float(sp[k]["x"]), float(sp[k]["y"])))
-            if lon < back + 3:
-                continue
-            x, y = mapdata.lane_position(lane, lon - back, lat)
-            th = mapdata.lane_heading_at(lane, lon - back)
-            ck = route.index(lane["road"])
-            f[_abi.SF["X"], e, 0], f[_abi.SF["Y"], e, 0], f[_abi.SF["THETA"], e, 0] = x, y, th
-            f[_abi.SF["LASTX"], e, 0], f[_abi.SF["LASTY"], e, 0] = x, y
-            f[_abi.SF["LASTHX"], e, 0], f[_abi.SF["LASTHY"], e, 0] = np.cos(th), np.sin(th)
-            f[_abi.SF["SPEED"], e, 0] = 8.0
-            i[_abi.SI["LANE"], e, 0] = int(sp[k]["lane"])
-            i[_abi.SI["CK0"], e, 0] = ck
-            i[_abi.SI["CK1"], e, 0] = ck + 1 if ck + 1 < sp[0]["n_ckpt"] - 1 else ck
-            moved += 1
-            break
-    return moved
-
-
 @pytest.mark.parametrize("safe", [False, True])
 def test_traffic_objects_parity(descs, safe):
     """Traffic cones / warning tripods (circles), barriers and broken-down vehicles (object_manager.py:40-124) as static
     bodies: crash_object on first contact only (collision_callback.py:27-32), lidar hits, IDM obstacles, no neighbour-info
     rows; SafePGDriveEnv termination rule (safe_pgdrive_env.py:49-56)."""
     n_envs = 64
-    torch, eng, ora, cfg = _engines(descs, n_envs, n_maps=16, num_traffic=46, accident_prob=1.0, safe_rl_env=safe,
+    eng, ora, cfg = parity.engines(descs, n_envs, n_maps=16, num_traffic=46, accident_prob=1.0, safe_rl_env=safe,
                                     auto_reset=0)
     scen_ids = np.arange(n_envs) % 16
     o0 = ora.reset(scen_ids)
     g0 = eng.reset(scen_ids).cpu().numpy()
-    _check_reset_rows(eng, ora, g0, o0, 2)
+    parity.check_reset_rows(eng, ora, g0, o0, 2)
     f, i, ei = ora.get_state()
-    moved = _teleport_to_objects(ora.map_bank, ora.scen_bank, scen_ids, f, i)
+    moved = parity.teleport_to_objects(ora.map_bank, ora.scen_bank, scen_ids, f, i)
     assert moved >= n_envs // 2
     f32 = util.round_state_f32(f)
     ora.set_state(f32, i, ei)
     eng.set_state(f32, i, ei)
     rng = np.random.default_rng(9)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
-    n_obj = n_hit_state = 0
-    for t in range(60):
+    stats = parity.new_stats()
+    n_hit_state = 0
+
+    def actions(t):
         act = util.driving_actions(rng, n_envs)
         act[..., 1] = 0.4
-        o_done = _compare_step(torch, eng, ora, act, stats)
-        f, i, ei = ora.get_state()
-        gf, gi, gei = eng.get_state()
+        return act
+
+    for s in parity.teacher_forced(eng, ora, stats, 60, actions):
         # incl. the objects' own "crashed" bits: differing only as margin-verified ties, at most the two allowed before
-        vf_bad = gi[_abi.SI["VFLAGS"]] != i[_abi.SI["VFLAGS"]]
-        vf_tie = vf_bad & (util.admitted_slots(stats["ties"].mg, ("CONTACT", "LANE")) |   # its own line / lane decisions, or the ego's
-                           util.admitted_slots(stats["ties"].mg, ("CONTACT",))[:, :1])       # contact with it (noted on the ego)
-        stats["ties"].add_slots("CONTACT", vf_tie, stats["ties"].mg)
+        vf_bad = s.gi[_abi.SI["VFLAGS"]] != s.i[_abi.SI["VFLAGS"]]
+        vf_tie = vf_bad & (util.admitted_slots(s.mg, ("CONTACT", "LANE")) |   # its own line / lane decisions, or the ego's
+                           util.admitted_slots(s.mg, ("CONTACT",))[:, :1])       # contact with it (noted on the ego)
+        s.ties.add_slots("CONTACT", vf_tie, s.mg)
         assert (vf_bad & ~vf_tie).sum() == 0 and vf_tie.sum() <= 2
-        n_hit_state = max(n_hit_state, int((i[_abi.SI["VFLAGS"]][:, 1:] & _abi.F_OBJECT_HIT != 0).sum()))
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
+        n_hit_state = max(n_hit_state, int((s.i[_abi.SI["VFLAGS"]][:, 1:] & _abi.F_OBJECT_HIT != 0).sum()))
     print("objects parity:", stats, "objects hit", n_hit_state)
-    _report("objects parity", stats)
+    parity.report("objects parity", stats)
     assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
     assert n_hit_state >= 8 and stats["n_crash_object"] >= 8
     assert stats.get("grazing", 0) <= 1e-5 * stats.get("beams", 1) + 3
@@ -979,40 +510,36 @@ def test_traffic_objects_parity(descs, safe):
 def test_lidar_noise_parity(descs):
     """Lidar noise / dropout (state_obs.py:172-182) from the counter-based stream: device and oracle draw the same numbers."""
     n_envs = 32
-    torch, eng, ora, cfg = _engines(descs, n_envs, lidar_gaussian_noise=0.05, lidar_dropout_prob=0.1, seed=77)
+    eng, ora, cfg = parity.engines(descs, n_envs, lidar_gaussian_noise=0.05, lidar_dropout_prob=0.1, seed=77)
     scen_ids = np.arange(n_envs) % 8
     o0 = ora.reset(scen_ids)
     g0 = eng.reset(scen_ids).cpu().numpy()
-    _check_reset_rows(eng, ora, g0, o0, 2)
+    parity.check_reset_rows(eng, ora, g0, o0, 2)
     assert (o0[:, 0, -240:] == 0.0).mean() > 0.05
     rng = np.random.default_rng(8)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
-    for t in range(60):
-        act = util.driving_actions(rng, n_envs)
-        _compare_step(torch, eng, ora, act, stats)
-        f, i, ei = ora.get_state()
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
+    stats = parity.new_stats()
+    for _ in parity.teacher_forced(eng, ora, stats, 60, lambda t: util.driving_actions(rng, n_envs)):
+        pass
     print("noise parity:", stats)
-    _report("noise parity", stats)
+    parity.report("noise parity", stats)
     assert stats["obs"] < OBS_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and stats["grazing"] <= 1e-4 * stats["beams"] + 3
 
 
 def test_maximum_sizes(descs):
     """The largest configuration the slot layout allows: 64 vehicle slots per env (1 ego + 63 traffic, dense traffic so
     that they are used), 16 neighbour rows, 500 lidar beams; one vehicle per lane (SUB = 1), observation not fused."""
+    import torch
     n_envs = 32
-    torch, eng, ora, cfg = _engines(descs, n_envs, num_traffic=63, density=0.6, num_lasers=500, num_others=16)
+    eng, ora, cfg = parity.engines(descs, n_envs, num_traffic=63, density=0.6, num_lasers=500, num_others=16)
     assert eng.D == 2 + 6 + 10 + 64 + 500
     used = [i["n_traffic"] for i in ora.scen_bank.info]
     assert max(used) >= 50
     scen_ids = np.arange(n_envs) % 8
     o0 = ora.reset(scen_ids)
     g0 = eng.reset(scen_ids).cpu().numpy()
-    _check_reset_rows(eng, ora, g0, o0, 2)
+    parity.check_reset_rows(eng, ora, g0, o0, 2)
     rng = np.random.default_rng(21)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    stats = parity.new_stats()
     ties = stats.setdefault("ties", util.Ties("test_maximum_sizes"))
     tie_rows = rows = 0
     for t in range(80):
@@ -1048,14 +575,14 @@ def test_maximum_sizes(descs):
             else:
                 stats["obs"] = max(stats["obs"], float(np.abs(g_obs - o_obs)[e, 0][vel].max()))
         stats["obs"] = max(stats["obs"], float(d[:, :82][:, ~vel[:82]].max()))
-        _compare_rows(eng, ora, stats, np.where(vel[None, None, :], o_obs, g_obs), o_obs, same, mg)  # beams: margin-verified grazing only
+        parity.compare_rows(eng, ora, stats, np.where(vel[None, None, :], o_obs, g_obs), o_obs, same, mg)  # beams: margin-verified grazing only
         stats["rew"] = max(stats["rew"], float(np.abs(g_rew.cpu().numpy() - o_rew)[same].max()))
         f, i, ei = ora.get_state()
         f32 = util.round_state_f32(f)
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("max sizes parity:", stats, "rows with a tie-flipped neighbour velocity", tie_rows, "of", rows)
-    _report("max sizes parity", stats)
+    parity.report("max sizes parity", stats)
     assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0
     assert stats["grazing"] <= 1e-4 * stats["beams"] + 3 and tie_rows <= 0.01 * rows
 
@@ -1063,8 +590,9 @@ def test_maximum_sizes(descs):
 def test_free_running_rollout(descs):
     """No teacher forcing: 60 steps from reset with identical actions; trajectories stay within tolerance until the first
     discrete disagreement of an env (after which that env is ignored)."""
+    import torch
     n_envs = 64
-    torch, eng, ora, cfg = _engines(descs, n_envs)
+    eng, ora, cfg = parity.engines(descs, n_envs)
     scen_ids = np.arange(n_envs) % 8
     ora.reset(scen_ids)
     eng.reset(scen_ids)
@@ -1101,8 +629,9 @@ def test_free_running_1000_steps(descs, num_traffic, num_lasers):
     a traffic vehicle into up to 6e-2 m within 140 steps before it contracts again (measured oracle-vs-oracle, DESIGN.md
     section 7) -- no fp32 engine can track it pose by pose over 1000 steps, so the traffic is compared statistically: the
     number of vehicles still driving, their mean speed and the median pose difference."""
+    import torch
     n_envs = 64
-    torch, eng, ora, cfg = _engines(descs, n_envs, num_traffic=num_traffic, num_lasers=num_lasers, auto_reset=0)
+    eng, ora, cfg = parity.engines(descs, n_envs, num_traffic=num_traffic, num_lasers=num_lasers, auto_reset=0)
     A = cfg.num_agents
     scen_ids = np.arange(n_envs) % 8
     obs = ora.reset(scen_ids)
@@ -1170,8 +699,9 @@ def test_free_running_1000_steps(descs, num_traffic, num_lasers):
 
 def test_empty_and_edge_slots(descs):
     """Scenario with zero traffic slots used (density 0) and a NaN action: obs stay finite and in [0,1]."""
+    import torch
     n_envs = 16
-    torch, eng, ora, cfg = _engines(descs, n_envs, density=0.0)
+    eng, ora, cfg = parity.engines(descs, n_envs, density=0.0)
     scen_ids = np.arange(n_envs) % 8
     eng.reset(scen_ids)
     ora.reset(scen_ids)
@@ -1188,69 +718,27 @@ def test_empty_and_edge_slots(descs):
 
 
 @pytest.mark.parametrize("num_agents,capacity", [(2, 2), (3, 4), (8, 8), (12, 16), (40, 40)])
-def test_marl_roundabout_parity(num_agents, capacity, kind="roundabout", **cfg_kw):
+def test_marl_roundabout_parity(num_agents, capacity):
     """BASELINE config 5: multi-agent roundabout (envs/marl_envs/marl_inout_roundabout.py) — per-agent done, delay-done
     queue, respawn into free 8 m x 3 m places, __all__, agent ids; teacher-forced against the oracle."""
-    import torch
-    from oracle import orc
-    from pgdrive_amd.engine import Engine
-    d, mb, sb = util.make_marl_banks(num_agents=num_agents, capacity=capacity, kind=kind)
-    n_envs = 32
-    cfg = util.marl_config(n_envs, sb, horizon=120, **cfg_kw)  # short horizon so that the episode end / reset path is exercised
-    eng = Engine(cfg, mb, sb)
-    ora = orc.Oracle(cfg, mb, sb)
-    ora.enable_margins()
-    ids = np.arange(n_envs) % 8
-    o0 = ora.reset(ids)
-    g0 = eng.reset(ids).cpu().numpy()
-    assert np.abs(g0 - o0).max() < OBS_TOL
-    rng = np.random.default_rng(5)
-    A = sb.A
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
-    seen = dict(new=0, dying=0, all_done=0, report=0)
-    worst = {}
-    for t in range(300):
-        act = util.marl_actions(rng, n_envs, A)
-        _compare_step(torch, eng, ora, act, stats)
-        f, i, ei = ora.get_state()
-        gf, gi, gei = eng.get_state()
-        # discrete state (status / lanes / ids / counters) must be bit-exact, up to box-overlap tests that sit on an fp32
-        # rounding boundary (measured: 1 line-contact flip in ~77 k agent-steps); every step restarts from the oracle state
-        _int_ties(gi, i, gei, ei, stats["ties"].mg, stats, stats["ties"].flag_tie)
-        seen["id_mismatch"] = seen.get("id_mismatch", 0) + int((gf[_abi.SF["AGENT_ID"]] != f[_abi.SF["AGENT_ID"]].astype(np.float32)).sum())
-        seen["dying"] += int((i[_abi.SI["STATUS"]] == _abi.ST_DYING).sum())
-        util.compare_state(gf, f, (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None], worst)
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
-    print("marl parity:", stats, seen, "state fields (x tolerance):", {k: round(v, 3) for k, v in worst.items()})
-    _report("marl parity", stats)
-    assert not util.state_failures(worst), util.state_failures(worst)
-    assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL
-    # the only tie class seen in the multi-agent runs: a car whose box touches a line box exactly (fp32 vs fp64 SAT), one
-    # agent-step in 153,600 of the 12-of-16 configuration; every other configuration is bit-exact.  Such a row is admitted only where the
-    # oracle's CONTACT / ROUTE / LANE margin confirms the near-tie (at most the one seen before); anything else: 0
-    assert stats["flag_mismatch"] == 0 and stats["flag_ties"] <= 1
-    assert stats["int_mismatch"] == 0 and seen["id_mismatch"] == 0
-    assert stats["int_ties"] <= 1
-    assert seen["dying"] > 0 and stats["n_new"] > 0 and stats["n_all_done"] > 0 and stats["n_report"] > 1000
+    parity.marl_teacher_forced(num_agents, capacity)
 
 
 @pytest.mark.parametrize("kind,num_others", [("roundabout", 4), ("intersection", 8)])
 def test_marl_neighbour_state_rows_parity(kind, num_others):
     """LidarStateObservationMARound with lidar.num_others > 0 (marl_inout_roundabout.py:82-105): every neighbour row is the
     neighbour's own state vector (19 floats here), finished static neighbours included, zeros when absent."""
-    test_marl_roundabout_parity(12, 16, kind=kind, num_others=num_others, others_state=True)
+    parity.marl_teacher_forced(12, 16, kind=kind, num_others=num_others, others_state=True)
 
 
 def test_marl_generic_pg_maps_parity():
     """MultiAgentPGDrive itself (multi_agent_pgdrive.py:12-213): 15 agents on the first straight of four generated maps."""
-    test_marl_roundabout_parity(15, 15, kind="pg")
+    parity.marl_teacher_forced(15, 15, kind="pg")
 
 
 def test_marl_intersection_parity():
     """MultiAgentIntersectionEnv (envs/marl_envs/marl_intersection.py): 4-way intersection with u-turns, 30 agents."""
-    test_marl_roundabout_parity(30, 30, kind="intersection")
+    parity.marl_teacher_forced(30, 30, kind="intersection")
 
 
 @pytest.mark.parametrize("detectors", [True, False])
@@ -1259,7 +747,7 @@ def test_marl_bottleneck_parity(detectors):
     the multi-agent observation, plain reward, Navigation's own destinations.  Without the side detector obs[0:2] are the
     lateral distances, whose right part is ray-measured on Merge / Split blocks (navigation.py:306-320,346-362)."""
     kw = dict(side_lasers=4, side_dist=50.0, lane_line_lasers=4, lane_line_dist=20.0) if detectors else {}
-    test_marl_roundabout_parity(20, 20, kind="bottleneck", plain_reward=True, **kw)
+    parity.marl_teacher_forced(20, 20, kind="bottleneck", plain_reward=True, **kw)
 
 
 TOLL = dict(tollgate=True, plain_reward=True, side_lasers=72, side_dist=20.0, lane_line_lasers=4, lane_line_dist=20.0,
@@ -1271,20 +759,17 @@ def test_marl_tollgate_parity():
     observation without navigation block + 2 toll floats, overspeed reward, sidewalk-only out-of-road, stay-time rule.
     Half of the agents are teleported to the mouth of the toll plaza, some too fast to pass legally."""
     import torch
-    from oracle import orc
     from pgdrive_amd import mapdata
-    from pgdrive_amd.engine import Engine
     d, mb, sb = util.make_marl_banks(num_agents=40, n_variants=4, kind="tollgate")
     assert sb.B == 8 and sb.V == 48
     n_envs = 16
     cfg = util.marl_config(n_envs, sb, horizon=400, **TOLL)
-    eng, ora = Engine(cfg, mb, sb), orc.Oracle(cfg, mb, sb)
-    ora.enable_margins()
+    eng, ora = parity.engine(cfg, mb, sb), parity.oracle(cfg, mb, sb)
     assert eng.D == 156
     ids = np.arange(n_envs) % 4
     o0 = ora.reset(ids)
     g0 = eng.reset(ids).cpu().numpy()
-    _check_reset_rows(eng, ora, g0, o0, 4)
+    parity.check_reset_rows(eng, ora, g0, o0, 4)
     f, i, ei = ora.get_state()
     SF, SI = _abi.SF, _abi.SI
     rng = np.random.default_rng(3)
@@ -1314,7 +799,7 @@ def test_marl_tollgate_parity():
     f32 = util.round_state_f32(f)
     ora.set_state(f32, i, ei)
     eng.set_state(f32, i, ei)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    stats = parity.new_stats()
     seen = dict(toll_obs=0, long_stay=0, building=0, fast_exit=0, entries=0, exits=0, int_mismatch=0)
     for t in range(160):
         act = np.zeros((n_envs, 40, 2), dtype=np.float32)
@@ -1330,7 +815,7 @@ def test_marl_tollgate_parity():
         stats["steps"] += same.size
         stats["flag_mismatch"] += int((~same).sum())
         # ray-cast columns (side fan 0:72, lane-line fan 78:82, lidar 82:154) over OBS_TOL: margin-verified grazing or stats["obs"]
-        _compare_rows(eng, ora, stats, g_obs, o_obs, same, mg)
+        parity.compare_rows(eng, ora, stats, g_obs, o_obs, same, mg)
         stats["rew"] = max(stats["rew"], float(np.abs(g_rew.cpu().numpy() - o_rew)[same].max()))
         rep = (o_flags & _abi.F_REPORT) != 0
         seen["toll_obs"] += int((o_obs[..., -2][rep] > 0).sum())
@@ -1350,7 +835,7 @@ def test_marl_tollgate_parity():
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
     print("tollgate parity:", stats, seen)
-    _report("tollgate parity", stats)
+    parity.report("tollgate parity", stats)
     stats["grazing"], stats["beams"] = stats["grazing"] + stats["det_grazing"], stats["beams"] + stats["det_beams"]  # all three fans, as before
     assert stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL and stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and seen["int_mismatch"] == 0
     assert stats["grazing"] <= 1e-4 * stats["beams"] + 5
@@ -1362,7 +847,7 @@ def test_marl_parking_lot_parity():
     """MultiAgentParkingLotEnv (envs/marl_envs/marl_parking_lot.py): ParkingLot block, reverse driving (enable_reverse),
     destinations handed out from the pool of free parking spaces (released when an agent is done, respawn from the access
     roads only while a space is free), white lines may be crossed."""
-    test_marl_roundabout_parity(10, 10, kind="parking", parking=True, enable_reverse=True)
+    parity.marl_teacher_forced(10, 10, kind="parking", parking=True, enable_reverse=True)
 
 
 @pytest.mark.parametrize("kind,kw", [("intersection", {}), ("bottleneck", dict(plain_reward=True, side_lasers=4, side_dist=50.0,
@@ -1372,7 +857,7 @@ def test_marl_eight_agents_parity(kind, kw):
     """Every multi-agent map once more with 8 agents (few slots, quick respawn turnover).  (Fusing the multi-agent
     observation into k_step for <= 8 slots was built and measured: 93.9 us fused vs 41 + 57 us separate at 4096 envs x 8
     agents -- no gain, the 8 rows are serial in one wave -- so the stand-alone k_observe stays.)"""
-    test_marl_roundabout_parity(8, 8, kind=kind, **kw)
+    parity.marl_teacher_forced(8, 8, kind=kind, **kw)
 
 
 def test_full_size_properties():
@@ -1382,14 +867,13 @@ def test_full_size_properties():
     scenarios and actions; the run is reproducible; a checkpoint (get_state -> set_state) resumes bit-identically."""
     import torch
     from pgdrive_amd import bank, mapdata, scenario
-    from pgdrive_amd.engine import Engine
     descs = bank.get_descriptions(range(1000, 1100))
     mb = mapdata.MapBank(descs)
     sb = scenario.ScenarioBank(descs, [d["seed"] for d in descs], num_agents=1, num_traffic=16)
     N, n = 4096, 32
 
     def make(n_envs):
-        return Engine(_abi.make_config(n_envs, num_agents=1, num_traffic=16, num_lasers=240, auto_reset=1, seed=99), mb, sb)
+        return parity.engine(_abi.make_config(n_envs, num_agents=1, num_traffic=16, num_lasers=240, auto_reset=1, seed=99), mb, sb)
 
     big, small, twin = make(N), make(n), make(N)
     ids = (np.arange(N) * 7) % 100
@@ -1433,8 +917,6 @@ def test_full_size_properties():
         o4 = resumed.step(act)[0]
         resumed.sync()
         assert torch.equal(o4, o_ref)
-    for e in (big, small, twin, resumed):
-        e.close()
 
 
 def test_throughput_mode_at_32768_envs_properties():
@@ -1448,14 +930,13 @@ def test_throughput_mode_at_32768_envs_properties():
     power-of-two size leaves throughput mode: ADVICE r03) gives the same rows as whole-engine steps of a default-mode engine."""
     import torch
     from pgdrive_amd import bank, mapdata, scenario
-    from pgdrive_amd.engine import Engine
     descs = bank.get_descriptions(range(1000, 1100))
     mb = mapdata.MapBank(descs)
     sb = scenario.ScenarioBank(descs, [d["seed"] for d in descs], num_agents=1, num_traffic=16)
     N = 32768
 
     def make(n_envs, base=0):
-        return Engine(_abi.make_config(n_envs, num_agents=1, num_traffic=16, num_lasers=240, auto_reset=1, resample_scenario=1,
+        return parity.engine(_abi.make_config(n_envs, num_agents=1, num_traffic=16, num_lasers=240, auto_reset=1, resample_scenario=1,
                                        seed=77, env_base=base), mb, sb)
 
     big, twin = make(N), make(N)
@@ -1531,12 +1012,10 @@ def test_throughput_mode_at_32768_envs_properties():
     dd = (twin.obs - o_ref).abs()
     assert torch.equal(twin.done, d_ref) and torch.equal(twin.flags, f_ref)
     assert float(dd.max()) < 2e-6  # (every column, as above)
-    for e in [big, twin, resumed] + small:
-        e.close()
 
 
 @pytest.mark.parametrize("num_traffic", [16, 24, 40])  # 3, 2, 1 sub-lanes per vehicle slot
-def test_record_cache_matches_plain_records(descs, num_traffic, monkeypatch):
+def test_record_cache_matches_plain_records(descs, num_traffic):
     """The step kernel skips the write of a record that did not change and reads never-written slots from the scenario's
     reset image (the throughput mode's default; with one env per wave the image reads are off by default since round 5 -- the mask
     is a memory round trip in front of the records -- and PGD_IMASK=1 switches them on: this test).  Engine A runs freely with both short cuts; engine B gets A's complete state through get_state /
@@ -1544,11 +1023,10 @@ def test_record_cache_matches_plain_records(descs, num_traffic, monkeypatch):
     every output must be bit-identical, through terminations, auto-resets with re-drawn scenarios, a partial pgd_reset
     and a scenario re-upload in the middle of the run.  (A free-running env also keeps its own copy of the map header, which
     set_state rebuilds: with fewer than four sub-lanes per slot the copy used to follow a re-drawn scenario only in part.)"""
+    import torch
     n_envs = 96
-    monkeypatch.setenv("PGD_IMASK", "1")
-    torch, eng_a, ora, cfg = _engines(descs, n_envs, seed=5, num_traffic=num_traffic, resample_scenario=1)
-    _, eng_b, _, _ = _engines(descs, n_envs, seed=5, num_traffic=num_traffic, resample_scenario=1)
-    monkeypatch.delenv("PGD_IMASK")
+    eng_a, _, _ = parity.engines(descs, n_envs, env=dict(PGD_IMASK="1"), seed=5, num_traffic=num_traffic, resample_scenario=1)
+    eng_b, _, _ = parity.engines(descs, n_envs, env=dict(PGD_IMASK="1"), seed=5, num_traffic=num_traffic, resample_scenario=1)
     scen_ids = np.arange(n_envs) % 8
     eng_a.reset(scen_ids)
     eng_b.reset(scen_ids)
@@ -1572,11 +1050,7 @@ def test_record_cache_matches_plain_records(descs, num_traffic, monkeypatch):
         ga = [x.clone() for x in eng_a.step(torch.from_numpy(act).to(eng_a.device))]
         gb = [x.clone() for x in eng_b.step(torch.from_numpy(act).to(eng_b.device))]
         eng_a.sync(); eng_b.sync()
-        for xa, xb, name in zip(ga, gb, ("obs", "reward", "done", "flags")):
-            assert torch.equal(xa.cpu(), xb.cpu()), "%s differs at step %d" % (name, t)
-        fa, ia, eia = eng_a.get_state()
-        fb, ib, eib = eng_b.get_state()
-        assert (ia == ib).all() and (eia == eib).all() and (fa.view(np.int32) == fb.view(np.int32)).all(), "state differs at step %d" % t
+        parity.same_bits(t, ga, gb, eng_a, eng_b)
         n_done += int(ga[2].sum().item())
     print("record cache: episodes ended", n_done, "waiting-traffic rows seen", n_pending_rows)
     assert n_done > 50 and n_pending_rows > 10000
@@ -1591,24 +1065,22 @@ def test_contact_hint_with_long_steps_and_short_lidar(descs, decision_repeat, li
     set_state before every step (which forces the contact tests on): crash flags, done and state must be bit-identical."""
     n_envs = 96
     kw = dict(seed=5, decision_repeat=decision_repeat, lidar_dist=lidar_dist, density=0.3)
-    torch, eng_a, ora, cfg = _engines(descs, n_envs, **kw)
-    _, eng_b, _, _ = _engines(descs, n_envs, **kw)
+    eng_a, _, _ = parity.engines(descs, n_envs, **kw)
+    eng_b, _, _ = parity.engines(descs, n_envs, **kw)
     scen_ids = np.arange(n_envs) % 8
     eng_a.reset(scen_ids)
     eng_b.reset(scen_ids)
     rng = np.random.default_rng(4)
     n_crash = n_done = 0
-    for t in range(300):
+
+    def actions(t):
         act = util.driving_actions(rng, n_envs)
         act[:, 0, 0] *= 0.2
         act[:, 0, 1] = 1.0  # straight on at full throttle: the ego runs into the traffic ahead of it at speed
-        f, i, ei = eng_a.get_state()
-        eng_b.set_state(f, i, ei)
-        ga = [x.clone() for x in eng_a.step(torch.from_numpy(act).to(eng_a.device))]
-        gb = [x.clone() for x in eng_b.step(torch.from_numpy(act).to(eng_b.device))]
-        eng_a.sync(); eng_b.sync()
-        for xa, xb, name in zip(ga, gb, ("obs", "reward", "done", "flags")):
-            assert torch.equal(xa.cpu(), xb.cpu()), "%s differs at step %d" % (name, t)
+        return act
+
+    for t, ga, gb in parity.twins(eng_a, eng_b, 300, actions, copy_state=eng_a):
+        parity.same_bits(t, ga, gb)
         n_crash += int(((ga[3].cpu().numpy().astype(np.uint32) & _abi.F_CRASH_VEHICLE) != 0).sum())
         n_done += int(ga[2].sum().item())
     print("contact hint A/B, decision_repeat %d, lidar %.0f m: crashes %d, episodes %d" % (decision_repeat, lidar_dist, n_crash, n_done))
@@ -1636,25 +1108,20 @@ def test_config_combinations_fuzz(descs):
         if kw["num_lasers"] == 0:
             kw.update(num_others=0, lidar_gaussian_noise=0.0, lidar_dropout_prob=0.0)
         n_envs = 32
-        torch, eng, ora, cfg = _engines(descs, n_envs, n_maps=8, **kw)
+        eng, ora, cfg = parity.engines(descs, n_envs, n_maps=8, **kw)
         ids = np.arange(n_envs) % 8
         o0 = ora.reset(ids)
         g0 = eng.reset(ids).cpu().numpy()
         assert np.abs(g0 - o0).max() < OBS_TOL, kw
         rng = np.random.default_rng(trial)
-        st = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
-        for t in range(100):
-            act = rng.integers(0, 5, size=(n_envs, 1, 2)).astype(np.float32) if kw["discrete_action"] else \
-                util.driving_actions(rng, n_envs)
-            _compare_step(torch, eng, ora, act, st)
-            f, i, ei = ora.get_state()
-            f32 = util.round_state_f32(f)
-            ora.set_state(f32, i, ei)
-            eng.set_state(f32, i, ei)
-        _report("fuzz trial %d" % trial, st)
+        st = parity.new_stats()
+        for _ in parity.teacher_forced(eng, ora, st, 100, lambda t: rng.integers(0, 5, size=(n_envs, 1, 2)).astype(np.float32)
+                                       if kw["discrete_action"] else util.driving_actions(rng, n_envs)):
+            pass
+        parity.report("fuzz trial %d" % trial, st)
         # (flags that differ: only margin-verified CONTACT / ROUTE / LANE ties, at most the two a trial was allowed before)
         assert st["obs"] < OBS_TOL and st["rew"] < REW_TOL and st["flag_mismatch"] == 0 and st["flag_ties"] <= 2, (kw, st)
-        eng.close()
+        parity.close_engines()
 
 
 def test_marl_config_combinations_fuzz():
@@ -1662,9 +1129,6 @@ def test_marl_config_combinations_fuzz():
     allow_respawn, delay_done, horizon, neighbour-state rows, detector fans), 16 teacher-forced runs against the oracle.
     (120 such combinations were run once: clean apart from ties of the kind profiles/r01_parity_campaign.md lists -- two
     neighbours at the same distance ranked by the last bit, the engine-force cut-off exactly at max_speed.)"""
-    import torch
-    from oracle import orc
-    from pgdrive_amd.engine import Engine
     r = np.random.default_rng(1)
     for trial in range(int(os.environ.get("PGD_FUZZ_TRIALS", "16"))):  # (PGD_FUZZ_TRIALS=120: the one-off campaign of the docstring)
         kind = str(r.choice(["roundabout", "intersection", "bottleneck", "parking", "pg"]))
@@ -1687,36 +1151,18 @@ def test_marl_config_combinations_fuzz():
         d, mb, sb = util.make_marl_banks(num_agents=na, capacity=cap, kind=kind)
         n_envs = 24
         cfg = util.marl_config(n_envs, sb, **kw)
-        eng, ora = Engine(cfg, mb, sb), orc.Oracle(cfg, mb, sb)
-        ora.enable_margins()
+        eng, ora = parity.engine(cfg, mb, sb), parity.oracle(cfg, mb, sb)
         ids = np.arange(n_envs) % len(sb.scenarios)
         assert np.abs(eng.reset(ids).cpu().numpy() - ora.reset(ids)).max() < OBS_TOL
         rng = np.random.default_rng(trial)
-        st = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
-        for t in range(200):
-            _compare_step(torch, eng, ora, util.marl_actions(rng, n_envs, sb.A), st)
-            f, i, ei = ora.get_state()
-            gf, gi, gei = eng.get_state()
-            _int_ties(gi, i, gei, ei, st["ties"].mg, st, st["ties"].flag_tie)
-            f32 = util.round_state_f32(f)
-            ora.set_state(f32, i, ei)
-            eng.set_state(f32, i, ei)
-        _report("marl fuzz trial %d" % trial, st)
+        st = parity.new_stats()
+        for s in parity.teacher_forced(eng, ora, st, 200, lambda t: util.marl_actions(rng, n_envs, sb.A)):
+            s.int_ties()
+        parity.report("marl fuzz trial %d" % trial, st)
         assert st["obs"] < OBS_TOL and st["rew"] < REW_TOL and st["flag_mismatch"] == 0 and st["flag_ties"] <= 2, (kind, na, cap, kw, st)
         assert st["int_mismatch"] == 0, (kind, na, cap, kw, st)
         assert st["int_ties"] <= 2, (kind, na, cap, kw, st)
-        eng.close()
-
-
-def _np_obb_overlap(ax, ay, ath, al, aw, bx, by, bth, bl, bw):
-    """Closed-rectangle SAT on arrays (chassis boxes length x width at heading th)."""
-    dx, dy = bx - ax, by - ay
-    aux, auy, bux, buy = np.cos(ath), np.sin(ath), np.cos(bth), np.sin(bth)
-    ac, as_ = np.abs(aux * bux + auy * buy), np.abs(aux * buy - auy * bux)
-    ahl, ahw, bhl, bhw = al / 2, aw / 2, bl / 2, bw / 2
-    sep = (np.abs(dx * aux + dy * auy) > ahl + bhl * ac + bhw * as_) | (np.abs(dy * aux - dx * auy) > ahw + bhl * as_ + bhw * ac) | \
-          (np.abs(dx * bux + dy * buy) > bhl + ahl * ac + ahw * as_) | (np.abs(dy * bux - dx * buy) > bhw + ahl * as_ + ahw * ac)
-    return ~sep
+        parity.close_engines()
 
 
 def test_contacts_inside_the_sub_steps(descs):
@@ -1725,7 +1171,7 @@ def test_contacts_inside_the_sub_steps(descs):
     to a waiting traffic vehicle at 10-25 m/s with random headings / steering; GPU and oracle must agree flag for flag, and
     some of the crash_vehicle flags must belong to pairs whose END-of-step boxes do not overlap."""
     n_envs = 512
-    torch, eng, ora, cfg = _engines(descs, n_envs, seed=21, auto_reset=0)  # no auto-reset: the state after the crash stays
+    eng, ora, cfg = parity.engines(descs, n_envs, seed=21, auto_reset=0)  # no auto-reset: the state after the crash stays
     scen_ids = np.arange(n_envs) % 8
     ora.reset(scen_ids)
     eng.reset(scen_ids)
@@ -1733,7 +1179,7 @@ def test_contacts_inside_the_sub_steps(descs):
     V = sb.V
     rng = np.random.default_rng(31)
     SF, SI = _abi.SF, _abi.SI
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    stats = parity.new_stats()
     n_crash = n_mid_only = 0
     f0, i0, ei0 = ora.get_state()
     for rnd in range(8):
@@ -1753,7 +1199,7 @@ def test_contacts_inside_the_sub_steps(descs):
         ora.set_state(f32, i, ei)
         eng.set_state(f32, i, ei)
         act = rng.uniform(-1, 1, size=(n_envs, 1, 2)).astype(np.float32)
-        _compare_step(torch, eng, ora, act, stats)
+        parity.compare_step(eng, ora, act, stats)
         gf, gi, gei = eng.get_state()
         fl = eng.flags.cpu().numpy().astype(np.uint32)[:, 0]
         crash = (fl & _abi.F_CRASH_VEHICLE) != 0
@@ -1765,7 +1211,7 @@ def test_contacts_inside_the_sub_steps(descs):
         end_any = np.zeros(n_envs, dtype=bool)
         for k in range(1, V):
             pres = np.isin(gi[SI["STATUS"], :, k], (_abi.ST_PENDING, _abi.ST_ACTIVE))
-            end_any |= pres & _np_obb_overlap(gf[SF["X"], :, 0], gf[SF["Y"], :, 0], gf[SF["THETA"], :, 0], sp_e["length"][:, 0],
+            end_any |= pres & parity.np_obb_overlap(gf[SF["X"], :, 0], gf[SF["Y"], :, 0], gf[SF["THETA"], :, 0], sp_e["length"][:, 0],
                                               sp_e["width"][:, 0], gf[SF["X"], :, k], gf[SF["Y"], :, k], gf[SF["THETA"], :, k],
                                               sp_e["length"][:, k], sp_e["width"][:, k])
         n_crash += int(crash.sum())
@@ -1791,50 +1237,26 @@ def test_env_observation_kernel_equals_row_kernel(kind, num_agents, capacity, kw
     oracle parity tests were first run with: free-running engines, same actions.  Reward, done and flags come from the same
     k_step and must be bit-identical; the two observation kernels contract their multiply-adds differently, so the rows agree
     to an fp32 ulp or two (1e-6), up to a beam that grazes a box corner."""
-    import os
-    import torch
-    from pgdrive_amd.engine import Engine
     d, mb, sb = util.make_marl_banks(num_agents=num_agents, capacity=capacity, kind=kind)
     n_envs = 48
     cfg = util.marl_config(n_envs, sb, horizon=150, resample_scenario=1, seed=9, **kw)
-    eng_a = Engine(cfg, mb, sb)
-    os.environ["PGD_ROW_OBSERVE"] = "1"
-    try:
-        eng_b = Engine(cfg, mb, sb)
-    finally:
-        del os.environ["PGD_ROW_OBSERVE"]
+    eng_a = parity.engine(cfg, mb, sb)
+    eng_b = parity.engine(cfg, mb, sb, env=dict(PGD_ROW_OBSERVE="1"))
     ids = np.arange(n_envs) % len(sb.scenarios)
     nl = cfg.num_lasers
     tail = 2 if kw.get("tollgate") else 0  # the toll floats follow the lidar
     st = dict(beams=0, grazing=0, worst=0.0)
-
-    def close(xa, xb):
-        dd = np.abs(xa.cpu().numpy().astype(np.float64) - xb.cpu().numpy())
-        D = dd.shape[-1]
-        beams = dd[..., D - tail - nl:D - tail]
-        st["beams"] += beams.size
-        st["grazing"] += int((beams > 1e-6).sum())
-        beams[beams > 1e-6] = 0.0
-        st["worst"] = max(st["worst"], float(dd.max()))
-
-    close(eng_a.reset(ids), eng_b.reset(ids))
+    parity.rows_close(eng_a.reset(ids), eng_b.reset(ids), st, nl, 1e-6, tail)
     rng = np.random.default_rng(4)
     n_rows = n_new = 0
-    for t in range(260):
-        act = torch.from_numpy(util.marl_actions(rng, n_envs, sb.A))
-        ga = [x.clone() for x in eng_a.step(act.to(eng_a.device))]
-        gb = [x.clone() for x in eng_b.step(act.to(eng_b.device))]
-        eng_a.sync(); eng_b.sync()
-        close(ga[0], gb[0])
-        for xa, xb, name in zip(ga[1:], gb[1:], ("reward", "done", "flags")):
-            assert torch.equal(xa.cpu(), xb.cpu()), "%s differs at step %d" % (name, t)
+    for t, ga, gb in parity.twins(eng_a, eng_b, 260, lambda t: util.marl_actions(rng, n_envs, sb.A)):
+        parity.same_rows(t, ga, gb, st, nl, 1e-6, tail)
         fl = ga[3].cpu().numpy()
         n_rows += int(((fl & _abi.F_REPORT) != 0).sum())
         n_new += int(((fl & _abi.F_NEW) != 0).sum())
     print("env vs row observation kernel:", st, "rows", n_rows, "new agents", n_new)
     assert st["worst"] < 1e-6 and st["grazing"] <= 1e-5 * st["beams"] + 2
     assert n_rows > 5000 and n_new > 20
-    eng_a.close(); eng_b.close()
 
 
 def test_maround_rows_against_the_reference_fixture(descs):
@@ -1842,8 +1264,6 @@ def test_maround_rows_against_the_reference_fixture(descs):
     vectors of the four nearest detected vehicles, 240 beams) computed by the reference's Python on scenes where every vehicle
     is an agent: the engine's PGD_MA_OTHERS_STATE observation (k_observe<.., OTH>) must reproduce them from the same state."""
     import json
-    import os
-    from pgdrive_amd.engine import Engine
     from tests.test_oracle_golden import GOLD, agents_scene_banks, agents_scene_state, compare_maround_rows
     with open(os.path.join(GOLD, "maround_v0.json")) as fh:
         gold = json.load(fh)
@@ -1851,7 +1271,7 @@ def test_maround_rows_against_the_reference_fixture(descs):
     flips = 0
     for sc in gold["cases"]:
         mb, sb, cfg = agents_scene_banks(descs, sc, num_lasers=240, lidar_dist=50.0, num_others=gold["num_others"], others_state=True)
-        eng = Engine(cfg, mb, sb)
+        eng = parity.engine(cfg, mb, sb)
         eng.reset(np.zeros(1, dtype=np.int32))
         f, i, ei = eng.get_state()
         agents_scene_state(sc, f, i)
@@ -1860,7 +1280,7 @@ def test_maround_rows_against_the_reference_fixture(descs):
         eng.sync()
         # corner beams: the reference helper pads box edges by 1e-5, fp32 adds its own grazing cases (bounded below)
         flips += compare_maround_rows(sc, obs.cpu().numpy()[0], worst, beam_tol=OBS_TOL)
-        eng.close()
+        parity.close_engines()
     print("MARound rows on the GPU:", worst, "corner beams", flips)
     assert worst["rows"] >= 50 and worst["state"] < OBS_TOL and worst["others"] < OBS_TOL and worst["lidar"] <= OBS_TOL and flips <= 4
 
@@ -1871,9 +1291,6 @@ def test_fused_observation_equals_stand_alone_kernels(descs, case):
     multi-agent rows (observe_env_body appended to k_step) are written by the step kernel.  PGD_NO_FUSE keeps the stand-alone
     observation kernels after k_step: same engine otherwise, free-running with the same actions -- reward / done / flags
     bit-identical, rows equal up to the contraction of multiply-adds in the two code instances (1e-6; grazing beams counted)."""
-    import os
-    import torch
-    from pgdrive_amd.engine import Engine
     n_envs = 64
     if case.startswith("marl"):
         d, mb, sb = util.make_marl_banks(num_agents=8, capacity=8, kind="roundabout")
@@ -1886,36 +1303,18 @@ def test_fused_observation_equals_stand_alone_kernels(descs, case):
         fans = dict(side_lasers=6, side_dist=50.0, lane_line_lasers=4, lane_line_dist=20.0) if case == "c2_fans" else {}
         cfg = _abi.make_config(n_envs, num_agents=1, num_traffic=nt, num_lasers=nl, auto_reset=1, seed=2, resample_scenario=1, **fans)
         A = 1
-    eng_a = Engine(cfg, mb, sb)
-    os.environ["PGD_NO_FUSE"] = "1"
-    try:
-        eng_b = Engine(cfg, mb, sb)
-    finally:
-        del os.environ["PGD_NO_FUSE"]
+    eng_a = parity.engine(cfg, mb, sb)
+    eng_b = parity.engine(cfg, mb, sb, env=dict(PGD_NO_FUSE="1"))
     ids = np.arange(n_envs) % len(sb.scenarios)
     eng_a.reset(ids); eng_b.reset(ids)
     rng = np.random.default_rng(8)
-    nl = cfg.num_lasers
-    worst, grazing, beams, n_done = 0.0, 0, 0, 0
-    for t in range(240):
-        act = util.marl_actions(rng, n_envs, A) if A > 1 else util.driving_actions(rng, n_envs)
-        act = torch.from_numpy(act)
-        ga = [x.clone() for x in eng_a.step(act.to(eng_a.device))]
-        gb = [x.clone() for x in eng_b.step(act.to(eng_b.device))]
-        eng_a.sync(); eng_b.sync()
-        for xa, xb, name in zip(ga[1:], gb[1:], ("reward", "done", "flags")):
-            assert torch.equal(xa.cpu(), xb.cpu()), "%s differs at step %d" % (name, t)
-        dd = np.abs(ga[0].cpu().numpy().astype(np.float64) - gb[0].cpu().numpy())
-        if nl:
-            b = dd[..., -nl:]
-            beams += b.size
-            grazing += int((b > 1e-6).sum())
-            b[b > 1e-6] = 0.0
-        worst = max(worst, float(dd.max()))
+    st = dict(beams=0, grazing=0, worst=0.0)
+    n_done = 0
+    for t, ga, gb in parity.twins(eng_a, eng_b, 240, lambda t: util.marl_actions(rng, n_envs, A) if A > 1 else util.driving_actions(rng, n_envs)):
+        parity.same_rows(t, ga, gb, st, cfg.num_lasers, 1e-6)
         n_done += int(ga[2].sum().item())
-    print("fused vs stand-alone observation", case, "worst", worst, "grazing", grazing, "of", beams, "episodes", n_done)
-    assert worst < 1e-6 and grazing <= 1e-5 * beams + 2 and n_done > 10
-    eng_a.close(); eng_b.close()
+    print("fused vs stand-alone observation", case, "worst", st["worst"], "grazing", st["grazing"], "of", st["beams"], "episodes", n_done)
+    assert st["worst"] < 1e-6 and st["grazing"] <= 1e-5 * st["beams"] + 2 and n_done > 10
 
 
 LARGE_RUNS = pytest.mark.skipif(bool(os.environ.get("PGD_SKIP_LARGE_RUNS")), reason="PGD_SKIP_LARGE_RUNS is set")
@@ -1936,11 +1335,12 @@ def test_free_running_timed_path_through_episode_ends(descs, size):
         both sides to the observation tolerance -- no divergence begins at a reset;
       * observations in the common prefix stay within the teacher-forced tolerance while the env's traffic is parked and
         within a loose bound after it drives (the IDM traffic is a chaotic closed loop: DESIGN.md section 7)."""
+    import torch
     n_envs, n_steps = (256, 600) if size == "suite" else (1024, 1000)
     big = os.environ.get("PGD_FREE_RUN")  # "envs,steps": another size for the large run
     if big and size == "large":
         n_envs, n_steps = (int(x) for x in big.split(","))
-    torch, eng, ora, cfg = _engines(descs, n_envs, seed=11, resample_scenario=1, auto_reset=1)
+    eng, ora, cfg = parity.engines(descs, n_envs, seed=11, resample_scenario=1, auto_reset=1)
     ids = np.arange(n_envs) % 8
     o0 = ora.reset(ids)
     g0 = eng.reset(ids).cpu().numpy()
@@ -2027,7 +1427,6 @@ def test_free_running_timed_path_through_episode_ends(descs, size):
         assert int(alive.sum()) >= n_envs - 4
         assert parked_flips <= 2 and parked_nb_rows <= 2 and parked_ck_rows <= 5
         assert worst_driving < 5e-3
-    eng.close()
 
 
 @pytest.mark.parametrize("size", ["suite", pytest.param("large", marks=LARGE_RUNS)])
@@ -2045,13 +1444,12 @@ def test_marl_free_running_through_finishes_and_respawns(size):
         passes a box corner within that drift (counted, bounded)."""
     import torch
     from oracle import orc
-    from pgdrive_amd.engine import Engine
     d, mb, sb = util.make_marl_banks(num_agents=40, capacity=40, kind="roundabout")
     n_envs, n_steps = (48, 400) if size == "suite" else (256, 600)
     if os.environ.get("PGD_FREE_RUN_MA") and size == "large":  # "envs,steps": another size for the large run
         n_envs, n_steps = (int(x) for x in os.environ["PGD_FREE_RUN_MA"].split(","))
     cfg = util.marl_config(n_envs, sb, horizon=150, resample_scenario=1, seed=7)
-    eng = Engine(cfg, mb, sb)
+    eng = parity.engine(cfg, mb, sb)
     ora = orc.Oracle(cfg, mb, sb)
     ids = np.arange(n_envs) % 8
     o0 = ora.reset(ids)
@@ -2112,7 +1510,6 @@ def test_marl_free_running_through_finishes_and_respawns(size):
         assert alive.mean() >= 0.93
         assert n_fin_alive >= 30000 and n_fin_alive >= 0.95 * n_fin and n_new_alive >= 0.95 * n_new and n_reset_alive >= 0.9 * n_reset
         assert worst < 4 * OBS_TOL and beams_off <= 2e-5 * beams
-    eng.close()
 
 
 @pytest.mark.parametrize("traffic_mode", ["trigger", "respawn"])
@@ -2124,52 +1521,44 @@ def test_idm_agent_parity_and_arrivals(descs, traffic_mode):
     policy does its job: free-running without traffic in the way the IDM ego follows its route to the destination -- most
     episodes end with arrive_dest, none by leaving the road -- and the garbage actions it is handed change nothing."""
     n_envs = 64
-    torch, eng, ora, cfg = _engines(descs, n_envs, seed=4, idm_agent=True, traffic_mode=traffic_mode, resample_scenario=1)
+    eng, ora, cfg = parity.engines(descs, n_envs, seed=4, idm_agent=True, traffic_mode=traffic_mode, resample_scenario=1)
     assert cfg.idm_agent == 1
     ids = np.arange(n_envs) % 8
     o0 = ora.reset(ids)
     g0 = eng.reset(ids).cpu().numpy()
     assert np.abs(g0 - o0).max() < OBS_TOL
     rng = np.random.default_rng(2)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    stats = parity.new_stats()
     worst, ties, traffic_steps, n_done, arrive = {}, 0, 0, 0, 0
     SI = _abi.SI
     int_ties = 0
-    for t in range(260):
-        act = rng.uniform(-1, 1, size=(n_envs, 1, 2)).astype(np.float32)  # ignored by both sides
-        o_done = _compare_step(torch, eng, ora, act, stats)
-        f, i, ei = ora.get_state()
-        gf, gi, gei = eng.get_state()
-        agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
-        mg = stats["ties"].mg
-        int_ties += _int_ties(gi, i, gei, ei, mg, stats, stats["ties"].flag_tie)[0]
-        tie = util.idm_tie(gf, f, mg)  # (the ego is an IDM vehicle here: its leader can sit on the 30 m search range as well)
-        stats["ties"].add_slots("LEADER", tie & agree, mg)
+    # (the actions are ignored by both sides)
+    for s in parity.teacher_forced(eng, ora, stats, 260, lambda t: rng.uniform(-1, 1, size=(n_envs, 1, 2)).astype(np.float32)):
+        agree = s.agree
+        int_ties += s.int_ties()[0]
+        tie = s.idm_tie(agree)  # (the ego is an IDM vehicle here: its leader can sit on the 30 m search range as well)
         ties += int((tie & agree).sum())
-        traffic_steps += int((i[SI["STATUS"]] == _abi.ST_ACTIVE).sum())
-        util.compare_state(gf, f, agree & ~tie, worst)
-        n_done += int(o_done.sum())
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
+        traffic_steps += int((s.i[SI["STATUS"]] == _abi.ST_ACTIVE).sum())
+        s.compare_state(agree & ~tie, worst)
+        n_done += int(s.o_done.sum())
     print("IDM agent, teacher-forced:", stats, "integer-state ties", int_ties, "idm ties", ties, "of", traffic_steps,
           "episodes ended", n_done, {k: round(v, 3) for k, v in worst.items()})
-    _report("IDM agent parity", stats)
+    parity.report("IDM agent parity", stats)
     # integer state that differs is a margin-verified tie (LANE / CONTACT / ROUTE / LEADER), at most the two seen before; anything else: 0
     assert stats["int_mismatch"] == 0 and n_done > 0
     assert int_ties <= 2
     assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and stats["obs"] < OBS_TOL and stats["rew"] < REW_TOL, stats
     assert not util.state_failures(worst), util.state_failures(worst)
     assert ties <= 0.002 * traffic_steps + 2
-    eng.close()
     # (2) free-running without traffic: the actions are ignored (two engines fed different garbage stay bit-identical) and the
     # policy drives the route: episodes last, and the driving reward (= longitudinal progress along the route) adds up.
     # How they END is the dynamics' business: under the kinematic bicycle the reference's steering PID (kp 1.7, kd 3.5 per 0.1 s
     # decision, tuned on Bullet's raycast vehicle) weaves by a few decimetres, and an ego that starts on the lane next to the
     # centre line ends most episodes by touching the yellow line (out_of_road) after 100 - 200 m -- the oracle does the same,
     # flag for flag; what Bullet would do is the unpinned part of DESIGN.md section 3.
-    torch, eng, _, cfg = _engines(descs, 128, seed=5, idm_agent=True, num_traffic=0, num_lasers=0, resample_scenario=1)
-    _, twin, _, _ = _engines(descs, 128, seed=5, idm_agent=True, num_traffic=0, num_lasers=0, resample_scenario=1)
+    import torch
+    eng, _, cfg = parity.engines(descs, 128, seed=5, idm_agent=True, num_traffic=0, num_lasers=0, resample_scenario=1)
+    twin, _, _ = parity.engines(descs, 128, seed=5, idm_agent=True, num_traffic=0, num_lasers=0, resample_scenario=1)
     eng.reset(np.arange(128) % 8); twin.reset(np.arange(128) % 8)
     done_n = arrive_n = 0
     ep_rewards = []
@@ -2191,7 +1580,6 @@ def test_idm_agent_parity_and_arrivals(descs, traffic_mode):
     print("IDM ego, free-running, no traffic: %d episodes ended (%d by arrival), mean length %.0f steps, mean running episode "
           "reward %.1f" % (done_n, arrive_n, mean_len, float(np.mean(ep_rewards))))
     assert mean_len > 100 and float(np.mean(ep_rewards)) > 40.0
-    eng.close(); twin.close()
 
 
 def test_state_with_spawn_records_of_other_slots(descs):
@@ -2201,11 +1589,10 @@ def test_state_with_spawn_records_of_other_slots(descs):
     parameters) must step like the oracle's."""
     import torch
     from oracle import orc
-    from pgdrive_amd.engine import Engine
     mb, sb = util.make_banks(descs, n_maps=8, traffic_mode="respawn")  # every traffic vehicle drives from the first step
     n = 64
     cfg = _abi.make_config(n, num_agents=1, num_traffic=16, num_lasers=240, auto_reset=0, seed=5)
-    eng = Engine(cfg, mb, sb)
+    eng = parity.engine(cfg, mb, sb)
     ora = orc.Oracle(cfg, mb, sb)
     ids = np.arange(n) % 8
     ora.reset(ids)
@@ -2246,4 +1633,3 @@ def test_state_with_spawn_records_of_other_slots(descs):
         assert np.array_equal(gi[_abi.SI["SPAWN"]], ora.get_state()[1][_abi.SI["SPAWN"]])
         ora.set_state(*eng.get_state())  # teacher forcing
     assert worst < OBS_TOL, worst
-    eng.close()

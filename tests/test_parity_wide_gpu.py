@@ -9,22 +9,11 @@ import numpy as np
 import pytest
 
 from pgdrive_amd import _abi
-from tests import util
-from tests.test_parity_gpu import OBS_TOL, REW_TOL, STATE_OBS_TOL, _compare_rows, _compare_step, _flag_ties, _int_ties, _report
+from tests import parity, util
+from tests.parity import OBS_TOL, REW_TOL, STATE_OBS_TOL, closed_engines  # noqa: F401 (the fixture closes every engine a test made)
 
 pytestmark = pytest.mark.gpu
 THREADS = min(64, len(os.sched_getaffinity(0)))
-
-
-def _actions(mode, rng, n):
-    if mode == "driving":
-        return util.driving_actions(rng, n)
-    if mode == "uniform":
-        return rng.uniform(-1, 1, size=(n, 1, 2)).astype(np.float32)
-    act = np.zeros((n, 1, 2), np.float32)  # drive straight, full throttle
-    act[..., 1] = 1.0
-    act[..., 0] = rng.normal(0, 0.05, size=(n, 1))
-    return act
 
 
 @pytest.mark.timeout(1500)
@@ -36,70 +25,18 @@ def test_all_maps_campaign(mode, steps):
     counted by class, as in the one-off campaign of round 1 (profiles/r01_parity_campaign.md, 3.07 M env-steps, 0 flag
     mismatches): grazing lidar beams, a body exactly on the 50 m neighbour radius, an IDM leader exactly MAX_DIST = 30 m
     ahead on the 10 m spawn grid."""
-    import torch
-    from oracle import orc
     from pgdrive_amd import bank
-    from pgdrive_amd.engine import Engine
     descs = bank.get_descriptions(range(1000, 1100))
     n_envs = 800
-    mb, sb = util.make_banks(descs, n_maps=100)
-    cfg = _abi.make_config(n_envs, num_agents=1, num_traffic=16, num_lasers=240, auto_reset=1, seed=11, resample_scenario=1)
-    eng = Engine(cfg, mb, sb)
-    ora = orc.Oracle(cfg, mb, sb)
-    ora.enable_margins()
+    eng, ora, cfg = parity.engines(descs, n_envs, n_maps=100, seed=11, resample_scenario=1)
     ids = np.arange(n_envs) % 100
     o0 = ora.reset(ids)
     g0 = eng.reset(ids).cpu().numpy()
     assert np.abs(g0 - o0).max() < OBS_TOL
     rng = np.random.default_rng(17)
-    st = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0, pose=0.0, beams=0, grazing=0, int_mismatch=0, int_ties=0, done=0, active=0,
-              radius_rows=0, idm_ties=0)
-    ties = st.setdefault("ties", util.Ties("test_all_maps_campaign[%s]" % mode))
-    worst = {}
-    for t in range(steps):
-        act = _actions(mode, rng, n_envs)
-        oo, orw, od, ofl = ora.step(act, threads=THREADS)
-        mg = ora.margins()
-        go, grw, gd, gfl = eng.step(torch.from_numpy(act).to(eng.device))
-        eng.sync()
-        go = go.cpu().numpy().astype(np.float64)
-        grw = grw.cpu().numpy().astype(np.float64)
-        gd, gfl = gd.cpu().numpy(), gfl.cpu().numpy().astype(np.uint32)
-        same = (gfl == ofl) & (gd == od)
-        st["steps"] += same.size
-        flag_tie = _flag_ties(eng, st, same, mg)  # (done / flags that differ: verified ties or flag_mismatch; both asserted 0 below)
-        st["done"] += int(od.sum())
-        head = np.where(same[:, :, None], np.abs(go - oo), 0.0)[:, 0, :34]
-        # neighbour block alone differs: a body on the 50 m radius or two equally distant ones -- only where the oracle's NEIGHBOUR
-        # margin of the row confirms it; any other such row stays in the comparison
-        flip = (head[:, 18:].max(axis=1) > OBS_TOL) & (head[:, :18].max(axis=1) <= OBS_TOL)
-        flip &= util.admissible("NEIGHBOUR", mg[util.MG["NEIGHBOUR"]][:, 0])
-        ties.add_slots("NEIGHBOUR", np.pad(flip[:, None], ((0, 0), (0, mg.shape[2] - 1))), mg)
-        st["radius_rows"] += int(flip.sum())
-        go_cmp = go.copy()
-        go_cmp[flip, 0, 18:34] = oo[flip, 0, 18:34]
-        _compare_rows(eng, ora, st, go_cmp, oo, same, mg)  # beams over OBS_TOL: margin-verified grazing or st["obs"]
-        st["rew"] = max(st["rew"], float(np.abs(grw - orw)[same].max()))
-        f, i, ei = ora.get_state()
-        gf, gi, gei = eng.get_state()
-        agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
-        _int_ties(gi, i, gei, ei, mg, st, flag_tie)
-        st["active"] += int((i[0, :, 1:] == 2).sum())
-        tie = util.idm_tie(gf, f, mg)
-        ties.add_slots("LEADER", tie & agree, mg)
-        st["idm_ties"] += int((tie & agree).sum())
-        for fld in ("X", "Y", "THETA", "SPEED"):
-            dd = np.abs(gf[_abi.SF[fld]].astype(np.float64) - f[_abi.SF[fld]])[agree & ~tie]
-            if fld == "THETA":
-                dd = np.minimum(dd, np.abs(dd - 2 * np.pi))
-            st["pose"] = max(st["pose"], float(dd.max()))
-        util.compare_state(gf, f, agree & ~tie, worst)  # all 26 float fields, not the pose alone
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
+    st, worst = parity.campaign(eng, ora, "test_all_maps_campaign[%s]" % mode, steps, lambda t: parity.stream_actions(mode, rng, n_envs), THREADS)
     print("campaign", mode, st, "state fields (x tolerance):", {k: round(v, 3) for k, v in worst.items()})
-    _report("campaign " + mode, st)
-    eng.close()
+    parity.report("campaign " + mode, st)
     assert not util.state_failures(worst), util.state_failures(worst)
     assert st["flag_mismatch"] == 0 and st.get("flag_ties", 0) == 0  # bit-exact done / collision / line / sidewalk / arrive flags
     assert st["int_mismatch"] == 0   # integer state: bit-exact, or a margin-verified tie (LANE / CONTACT / ROUTE / LEADER) ...
@@ -114,46 +51,33 @@ def test_all_maps_campaign(mode, steps):
 def test_c2_1024_envs_parity():
     """BASELINE C2: 1024 envs, 1 ego, no traffic, no lidar (D = 18) on all 100 maps -- the engine then packs several envs
     into a wave (k_step<ONE_ENV = false>) and runs the stand-alone observation kernel."""
-    import torch
-    from oracle import orc
     from pgdrive_amd import bank
-    from pgdrive_amd.engine import Engine
     descs = bank.get_descriptions(range(1000, 1100))
     n_envs = 1024
-    mb, sb = util.make_banks(descs, n_maps=100, num_traffic=0)
-    cfg = _abi.make_config(n_envs, num_agents=1, num_traffic=0, num_lasers=0, auto_reset=1, seed=3, resample_scenario=1)
-    eng = Engine(cfg, mb, sb)
-    ora = orc.Oracle(cfg, mb, sb)
+    eng, ora, cfg = parity.engines(descs, n_envs, n_maps=100, num_traffic=0, num_lasers=0, seed=3, resample_scenario=1)
     assert eng.D == 18
     ids = np.arange(n_envs) % 100
     assert np.abs(eng.reset(ids).cpu().numpy() - ora.reset(ids)).max() < OBS_TOL
     rng = np.random.default_rng(2)
-    stats = dict(steps=0, flag_mismatch=0, obs=0.0, rew=0.0)
+    stats = parity.new_stats()
     pose = 0.0
     n_done = 0
     worst = {}
-    for t in range(220):
-        act = util.driving_actions(rng, n_envs) if t % 2 else _actions("straight", rng, n_envs)
-        n_done += int(_compare_step(torch, eng, ora, act, stats).sum())
-        f, i, ei = ora.get_state()
-        gf, gi, gei = eng.get_state()
-        assert (gi == i).all() and (gei == ei).all()
+    for s in parity.teacher_forced(eng, ora, stats, 220, lambda t: util.driving_actions(rng, n_envs) if t % 2 else
+                                   parity.stream_actions("straight", rng, n_envs)):
+        n_done += int(s.o_done.sum())
+        assert (s.gi == s.i).all() and (s.gei == s.ei).all()
         for fld in ("X", "Y", "SPEED"):
-            pose = max(pose, float(np.abs(gf[_abi.SF[fld]].astype(np.float64) - f[_abi.SF[fld]]).max()))
-        util.compare_state(gf, f, np.ones(gi.shape[1:], dtype=bool), worst)
-        f32 = util.round_state_f32(f)
-        ora.set_state(f32, i, ei)
-        eng.set_state(f32, i, ei)
+            pose = max(pose, float(np.abs(s.gf[_abi.SF[fld]].astype(np.float64) - s.f[_abi.SF[fld]]).max()))
+        s.compare_state(np.ones(s.gi.shape[1:], dtype=bool), worst)
     print("C2 parity:", stats, "pose", pose, "episodes", n_done, "state fields (x tolerance):", {k: round(v, 3) for k, v in worst.items()})
-    eng.close()
     assert not util.state_failures(worst), util.state_failures(worst)
     assert stats["flag_mismatch"] == 0 and stats.get("flag_ties", 0) == 0 and stats["obs"] < STATE_OBS_TOL and stats["rew"] < REW_TOL and pose < 1e-3 and n_done > 300
 
 
 def test_c5_marl_240_beams_parity():
     """BASELINE C5's row: 8 agents on the multi-agent roundabout with the single-agent lidar (240 beams x 50 m, D = 258)."""
-    from tests.test_parity_gpu import test_marl_roundabout_parity
-    test_marl_roundabout_parity(8, 8, num_lasers=240, lidar_dist=50.0)
+    parity.marl_teacher_forced(8, 8, num_lasers=240, lidar_dist=50.0)
 
 
 @pytest.mark.timeout(900)
@@ -163,12 +87,11 @@ def test_c5_full_size_properties():
     run is reproducible; REPORT rows are exactly the agents that were active, NEW rows carry reward 0 and are not done;
     ALL_DONE comes with RESET; agent ids grow monotonically per env."""
     import torch
-    from pgdrive_amd.engine import Engine
     d, mb, sb = util.make_marl_banks(num_agents=8, n_variants=16, seed=2)
     N, n, A = 4096, 16, 8
 
     def make(n_envs):
-        return Engine(util.marl_config(n_envs, sb, horizon=150, resample_scenario=1, seed=77), mb, sb)
+        return parity.engine(util.marl_config(n_envs, sb, horizon=150, resample_scenario=1, seed=77), mb, sb)
 
     big, small, twin = make(N), make(n), make(N)
     ids = (np.arange(N) * 5) % len(sb.scenarios)
@@ -204,8 +127,6 @@ def test_c5_full_size_properties():
             assert (act_ids.max(axis=1) < nxt).all()
     print("C5 full size:", seen)
     assert seen["report"] > 3_000_000 and seen["new"] > 10000 and seen["all_done"] > 1000 and seen["done"] > 10000
-    for e in (big, small, twin):
-        e.close()
 
 
 @pytest.mark.timeout(900)
@@ -224,8 +145,8 @@ def test_ieee_build_gives_the_same_discrete_outcomes(descs):
     n_envs = 256
     mb, sb = util.make_banks(descs, n_maps=8)
     cfg = _abi.make_config(n_envs, num_agents=1, num_traffic=16, num_lasers=240, auto_reset=1, seed=4)
-    fast = engine.Engine(cfg, mb, sb)
-    ieee = engine.Engine(cfg, mb, sb, lib=L_ieee)
+    fast = parity.engine(cfg, mb, sb)
+    ieee = parity.engine(cfg, mb, sb, lib=L_ieee)
     ora = orc.Oracle(cfg, mb, sb)
     ids = np.arange(n_envs) % 8
     ora.reset(ids); fast.reset(ids); ieee.reset(ids)
@@ -233,7 +154,7 @@ def test_ieee_build_gives_the_same_discrete_outcomes(descs):
     diff_flags = diff_ints = vs_oracle = n_done = 0
     worst = 0.0
     for t in range(300):
-        act = util.driving_actions(rng, n_envs) if t % 3 else _actions("straight", rng, n_envs)
+        act = util.driving_actions(rng, n_envs) if t % 3 else parity.stream_actions("straight", rng, n_envs)
         oo, orw, od, ofl = ora.step(act, threads=THREADS)
         a = torch.from_numpy(act).to(fast.device)
         fo, frw, fd, ffl = [x.clone() for x in fast.step(a)]
@@ -253,7 +174,6 @@ def test_ieee_build_gives_the_same_discrete_outcomes(descs):
             e.set_state(f32, i, ei)
     print("fast-math vs IEEE build: flag diffs", diff_flags, "int-state diffs", diff_ints, "vs oracle", vs_oracle,
           "max |obs_fast - obs_ieee| (state block)", worst, "episodes", n_done)
-    fast.close(); ieee.close()
     assert diff_flags == 0 and diff_ints == 0 and vs_oracle == 0 and worst < 5e-6 and n_done > 100
 
 
@@ -280,24 +200,23 @@ def test_culling_is_result_neutral(descs):
     cases.append(("40 slots", util.marl_config(64, msb, horizon=150, seed=3), mmb, msb, msb.A, 250))
     for name, cfg, mb_, sb_, A, steps in cases:
         n = cfg.num_envs
-        a_eng = engine.Engine(cfg, mb_, sb_)
-        b_eng = engine.Engine(cfg, mb_, sb_, lib=L_all)
+        a_eng = parity.engine(cfg, mb_, sb_)
+        b_eng = parity.engine(cfg, mb_, sb_, lib=L_all)
         ids = np.arange(n) % 8
         assert torch.equal(a_eng.reset(ids), b_eng.reset(ids))
         rng = np.random.default_rng(12)
         hits = lines = 0
-        for t in range(steps):
+
+        def actions(t):
             act = util.driving_actions(rng, n) if A == 1 else util.marl_actions(rng, n, A)
             if name == "swerving ego":  # crosses lane lines and leaves the road: the single-agent line / sidewalk test
                 act[:, 0, 0] = np.clip(0.6 * np.sin(0.07 * t + np.arange(n)) + rng.normal(0, 0.1, size=n), -1, 1)
-            a = torch.from_numpy(act).to(a_eng.device)
-            ra = [x.clone() for x in a_eng.step(a)]
-            rb = [x.clone() for x in b_eng.step(a)]
-            a_eng.sync(); b_eng.sync()
-            for x, y, what in zip(ra, rb, ("obs", "reward", "done", "flags")):
-                assert torch.equal(x, y), "%s: %s differs at step %d" % (name, what, t)
+            return act
+
+        for t, ra, rb in parity.twins(a_eng, b_eng, steps, actions):
+            parity.same_bits(t, ra, rb, names=["%s: %s" % (name, what) for what in parity.OUTPUTS])
             hits += int((ra[0][..., -cfg.num_lasers:] < 1.0).sum().item())
             lines += int(((ra[3].to(torch.int64) & (_abi.F_ON_BROKEN | _abi.F_ON_WHITE | _abi.F_ON_YELLOW | _abi.F_CRASH_SIDEWALK)) != 0).sum().item())
         print("culling off vs on, %s: %d steps x %d envs bit-identical (%d beam hits, %d line / sidewalk contacts on the way)" % (name, steps, n, hits, lines))
         assert hits > 1000 and (lines > 10 or name == "respawn traffic")  # (dense traffic ends an episode within a few steps: no line is reached)
-        a_eng.close(); b_eng.close()
+        parity.close_engines()

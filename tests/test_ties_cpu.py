@@ -16,7 +16,8 @@ import pytest
 
 from pgdrive_amd import _abi
 from tests import util
-from tests.test_parity_gpu import (OBS_TOL, REW_TOL, PARKED_HIT_SHARE, _compare_step, _int_ties)
+from tests import parity
+from tests.parity import OBS_TOL, REW_TOL, PARKED_HIT_SHARE, compare_step, int_ties
 
 SF, SI = _abi.SF, _abi.SI
 PERTURBED = ("X", "Y", "THETA", "SPEED")  # the continuous inputs of a step; every other field is a copy, a sum or integer-valued bookkeeping
@@ -123,7 +124,6 @@ class Surrogate:
 def _run(make, cfg, n_steps, actions, plant=None, seed=0, park_ego=False):
     """The teacher-forced loop of the GPU tests with the surrogate in the engine's place.  Returns the statistics of the strict form
     (stats, worst, idm_ties, active) and the counts the count-only form of the suite looked at (old)."""
-    import torch
     ora, eng = make(), Surrogate(make, cfg, seed=seed, plant=plant)
     ora.enable_margins()
     n = cfg.num_envs
@@ -137,12 +137,12 @@ def _run(make, cfg, n_steps, actions, plant=None, seed=0, park_ego=False):
     A = cfg.num_agents
     for t in range(n_steps):
         act = actions(rng, n, A) * (0.0 if park_ego else 1.0)
-        _compare_step(torch, eng, ora, act, stats)
+        compare_step(eng, ora, act, stats)
         mg = stats["ties"].mg
         f, i, ei = ora.get_state()
         gf, gi, gei = eng.get_state()
         agree = (gi == i).all(axis=0) & (gei == ei).all(axis=0)[:, None]
-        _int_ties(gi, i, gei, ei, mg, stats, stats["ties"].flag_tie)
+        int_ties(gi, i, gei, ei, mg, stats, stats["ties"].flag_tie)
         tie = util.idm_tie(gf, f, mg)
         if not cfg.idm_agent:
             tie[:, :A] = False
@@ -451,7 +451,7 @@ def test_share_of_items_the_predicates_flag(descs, traffic_mode):
 
 
 def test_parked_respawn_hit_share(descs):
-    """The figure the GPU test's floor for the parked-ego respawn case is half of (tests/test_parity_gpu.py PARKED_HIT_SHARE): the
+    """The figure the GPU test's floor for the parked-ego respawn case is half of (tests/parity.py PARKED_HIT_SHARE): the
     oracle alone on the inputs of test_teacher_forced_parity[16-240-respawn-parked]."""
     cfg, mb, sb, make = _single(descs, 64, traffic_mode="respawn")
     ora = make()
@@ -464,3 +464,24 @@ def test_parked_respawn_hit_share(descs):
         ora.set_state(util.round_state_f32(f), i, ei)
     print("parked ego, respawn traffic: %d of %d beams hit (%.4f)" % (hits, beams, hits / beams))
     assert abs(hits / beams - PARKED_HIT_SHARE) < 5e-4
+
+
+def test_engine_keywords_are_split_strictly(descs):
+    """parity.banks_and_config (the half of parity.engines that needs no GPU): a key that neither the scenario bank nor make_config
+    takes is an error -- it used to be dropped, and the test then ran the default configuration --, and for keyword sets of the suite
+    the PgdConfig is _abi.make_config's byte for byte and the scenarios are util.make_banks', with the keys both take handed to both."""
+    for bad in (dict(lidar_range=40.0), dict(seed=3, crash_vehicle_penalti=1.0)):
+        with pytest.raises(TypeError, match=sorted(bad)[0]):
+            parity.banks_and_config(descs, 16, **bad)
+    for n_maps, bank_kw, cfg_kw in [
+            (8, dict(traffic_mode="respawn"), dict(seed=3, resample_scenario=1)),
+            (16, dict(num_traffic=56, accident_prob=0.8, density=0.05), dict(num_traffic=56, safe_rl_env=True, use_lateral=False, seed=3)),
+            (16, dict(traffic_mode="respawn", idm_agent=1), dict(seed=4, idm_steer_lag=0.2, idm_agent=1)),
+            (8, dict(random_agent_model=True), dict(num_lasers=16, lane_line_lasers=33, lane_line_dist=20.0, random_agent_model=True)),
+            (8, dict(auto_termination=True, traffic_mode="respawn"), dict(discrete_action=True, increment_steering=True, num_lasers=60)),
+            (8, {}, {})]:
+        mb, sb, cfg = parity.banks_and_config(descs, 16, n_maps=n_maps, **dict(bank_kw, **cfg_kw))
+        assert bytes(cfg) == bytes(_abi.make_config(16, **cfg_kw)), cfg_kw
+        mb_ref, sb_ref = util.make_banks(descs, n_maps=n_maps, **bank_kw)
+        assert sb.scenarios.tobytes() == sb_ref.scenarios.tobytes() and sb.spawns.tobytes() == sb_ref.spawns.tobytes(), bank_kw
+        assert len(mb.descs) == n_maps

@@ -2,7 +2,7 @@
 import sys, os; sys.path.insert(0,'.')
 import numpy as np, torch
 from tests import util
-from tests.test_parity_gpu import OBS_TOL
+from tests.parity import OBS_TOL
 from oracle import orc
 from pgdrive_amd import _abi
 from pgdrive_amd.engine import Engine
