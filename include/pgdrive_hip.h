@@ -235,7 +235,19 @@ typedef struct pgd_engine* pgd_handle;
  * absent and 2 toll floats follow the lidar (marl_tollgate.py:63-105). */
 int pgd_obs_dim(const pgd_config* cfg);
 
-/* Replaces PGDriveEnv.__init__ / lazy_init (envs/base_env.py:100-178): allocates device state for N x V slots. */
+/* Replaces PGDriveEnv.__init__ / lazy_init (envs/base_env.py:100-178): allocates device state for N x V slots.
+ * The call also reads the library's environment switches (A/B runs and debugging, never needed in production), once, into the handle;
+ * a later change of the environment does not reach an existing engine.  Set = present with any value, unless stated otherwise:
+ *   PGD_NO_FUSE            the stand-alone observation kernels run after k_step instead of the fused paths
+ *   PGD_NO_FIX             never launch an instantiation specialised for one configuration (nor a run-time kernel)
+ *   PGD_JIT_FORCE          a run-time kernel (pgd_set_step_module) also takes the place of a specialised instantiation
+ *   PGD_ROW_OBSERVE        multi-agent observation by one block per row (k_observe) instead of one block per env (k_observe_env)
+ *   PGD_NO_STATE_IN_STEP   many agent seats: the rows' state blocks stay in k_observe_env instead of being written by k_step
+ *   PGD_PACK=0 / 1         throughput mode (several whole envs per wave) off / on, whatever the env count (default: from 32768 envs on)
+ *   PGD_NO_ROWZ            multi-agent engines keep no zero-row marks (pgd_step); a value that starts with '0' counts as not set
+ *   PGD_NO_IMASK / PGD_IMASK   never-written slots are never / always read from the scenario's reset image (default: in throughput mode)
+ *   PGD_NO_UNI             an upload never records one body size for all vehicles (read here, not by pgd_upload_scenarios: Engine()
+ *                          creates and uploads inside one constructor, and nothing sets the variable in between) */
 int pgd_create(const pgd_config* cfg, int device, void* hip_stream, pgd_handle* out);
 
 /* Replaces MapManager.update_map + block._create_in_world (manager/map_manager.py:98-155, blocks/base_block.py:142-179):

@@ -1,5 +1,5 @@
 // pgd_dynamics.h -- bicycle dynamics, vehicle reset, reward / done.
-// Part of the single translation unit pgd_engine.hip (included there, in this order, after pgd_device.h).
+// Part of the single translation unit pgd_engine.hip (included by pgd_step.h, in this order, after pgd_device.h).
 #ifndef PGD_DYNAMICS_H
 #define PGD_DYNAMICS_H
 

@@ -1,5 +1,5 @@
 // pgd_idm.h -- IDM traffic policy: routing, neighbour search, lane change, PID steering, IDM law.
-// Part of the single translation unit pgd_engine.hip (included there, in this order, after pgd_device.h).
+// Part of the single translation unit pgd_engine.hip (included by pgd_step.h, in this order, after pgd_device.h).
 #ifndef PGD_IDM_H
 #define PGD_IDM_H
 

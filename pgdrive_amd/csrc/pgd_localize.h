@@ -1,5 +1,5 @@
 // pgd_localize.h -- lane localisation, checkpoints, line / sidewalk contacts, route context, after_step.
-// Part of the single translation unit pgd_engine.hip (included there, in this order, after pgd_device.h).
+// Part of the single translation unit pgd_engine.hip (included by pgd_step.h, in this order, after pgd_device.h).
 #ifndef PGD_LOCALIZE_H
 #define PGD_LOCALIZE_H
 

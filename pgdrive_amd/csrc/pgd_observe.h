@@ -1,5 +1,5 @@
 // pgd_observe.h -- observation: state + navigation block, detector fans, neighbour rows, lidar.
-// Part of the single translation unit pgd_engine.hip (included there, in this order, after pgd_device.h).
+// Part of the single translation unit pgd_engine.hip (included by pgd_step.h, in this order, after pgd_device.h).
 #ifndef PGD_OBSERVE_H
 #define PGD_OBSERVE_H
 #ifdef PGD_NT_OBS

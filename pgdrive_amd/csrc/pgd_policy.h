@@ -1,5 +1,5 @@
 // pgd_policy.h -- the policy network of the closed loop as ONE launch: actions = MLP(observation rows).
-// Part of the single translation unit pgd_engine.hip.
+// Part of the single translation unit pgd_engine.hip (included by pgd_step.h, last of the device headers).
 //
 // What it mirrors: pgdrive/examples/ppo_expert/numpy_expert.py:25-44 (`expert(obs)`): a three-layer tanh MLP
 //   x = tanh(obs @ fc_1/kernel + fc_1/bias); x = tanh(x @ fc_2/kernel + fc_2/bias); out = x @ fc_out/kernel + fc_out/bias

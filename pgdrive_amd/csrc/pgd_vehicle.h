@@ -1,5 +1,5 @@
 // pgd_vehicle.h -- per-lane vehicle registers, the LDS snapshot of an env's vehicles, sub-lane groups.
-// Part of the single translation unit pgd_engine.hip (included there, in this order, after pgd_device.h).
+// Part of the single translation unit pgd_engine.hip (included by pgd_step.h, in this order, after pgd_device.h).
 #ifndef PGD_VEHICLE_H
 #define PGD_VEHICLE_H
 

@@ -151,6 +151,19 @@ class Engine:
         self._seen_out = []  # caller-supplied observation tensors of the last steps, kept alive (see step)
         torch.cuda.synchronize(dev)
 
+    def _follow_stream(self):
+        """The engine follows the caller's current stream (like a torch op): no events, no cross-stream waits per call; pgd_set_stream
+        orders the hand-over when the stream changes.  (Calls on an env group run on the group's stream and do not come here.)"""
+        cur = self.torch.cuda.current_stream(self.device).cuda_stream
+        if cur != self._bound_stream:
+            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
+            self._bound_stream = cur
+
+    def _check_actions(self, actions):
+        """An action tensor (or a buffer for one): float32 cuda, contiguous, [N, A, 2]."""
+        assert actions.is_cuda and actions.dtype == self.torch.float32 and actions.is_contiguous()
+        assert actions.numel() == self.N * self.A * 2
+
     # -- reference surface ------------------------------------------------------------------------------------------
     def reset(self, scen_ids, env_ids=None):
         scen_ids = np.ascontiguousarray(scen_ids, dtype=np.int32)
@@ -177,8 +190,7 @@ class Engine:
         (normalisation, clamp_, noise) would see its edits persist in the rows of empty seats -- clone first, or create the engine
         with PGD_NO_ROWZ=1 in the environment (the zero rows are then rewritten by every call).  `out` tensors need not be long-lived
         or zero-initialised: a tensor the engine has not seen alive makes it forget its marks (pgd_forget_rows) before the step."""
-        assert actions.is_cuda and actions.dtype == self.torch.float32 and actions.is_contiguous()
-        assert actions.numel() == self.N * self.A * 2
+        self._check_actions(actions)
         forget_first = False
         if out is None:  # the engine's own output buffers: their addresses never change
             obs, reward, done, flags = self.obs, self.reward, self.done, self.flags
@@ -195,12 +207,7 @@ class Engine:
                 forget_first = True
                 self._seen_out.append(obs)
                 del self._seen_out[:-4]
-        # the engine follows the caller's current stream (like a torch op): no events, no cross-stream waits per step;
-        # pgd_set_stream orders the hand-over when the stream changes
-        cur = self.torch.cuda.current_stream(self.device).cuda_stream
-        if cur != self._bound_stream:
-            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-            self._bound_stream = cur
+        self._follow_stream()
         if forget_first:
             _chk(self.L.pgd_forget_rows(self.h), "pgd_forget_rows")
         _chk(
@@ -212,13 +219,10 @@ class Engine:
     def step_packed(self, actions, rows):
         """Like step(), but the env's results go into `rows` [N, >= A*(D+2)] fp32 as [A*D obs | A reward | A done]: the
         row a per-step gather sends (pgdrive_amd/dist.py); `rows` may be a slice of the gather's receive buffer."""
-        assert actions.is_cuda and actions.dtype == self.torch.float32 and actions.is_contiguous()
+        self._check_actions(actions)
         assert rows.is_cuda and rows.dtype == self.torch.float32 and rows.dim() == 2 and rows.shape[0] == self.N
         assert rows.stride(1) == 1 and rows.stride(0) >= self.A * (self.D + 2)
-        cur = self.torch.cuda.current_stream(self.device).cuda_stream
-        if cur != self._bound_stream:
-            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-            self._bound_stream = cur
+        self._follow_stream()
         p_obs, p_rew, p_done, p_flags = self._own_ptrs
         _chk(self.L.pgd_step_packed(self.h, C.c_void_p(actions.data_ptr()), C.c_void_p(rows.data_ptr()),
                                     int(rows.stride(0)), p_rew, p_done, p_flags), "pgd_step_packed")
@@ -230,10 +234,7 @@ class Engine:
         t = self.torch
         assert action_ring.is_cuda and action_ring.dtype == t.float32 and action_ring.is_contiguous() and action_ring.dim() == 4
         assert tuple(action_ring.shape[1:]) == (self.N, self.A, 2)
-        cur = t.cuda.current_stream(self.device).cuda_stream
-        if cur != self._bound_stream:
-            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-            self._bound_stream = cur
+        self._follow_stream()
         rew = t.empty((n_steps, self.N, self.A), dtype=t.float32, device=self.obs.device)
         done = t.empty((n_steps, self.N, self.A), dtype=t.uint8, device=self.obs.device)
         flags = t.empty((n_steps, self.N, self.A), dtype=t.int32, device=self.obs.device)
@@ -252,10 +253,7 @@ class Engine:
         k = int(w1.shape[0])
         assert w1.shape == (k, 256) and w2.shape == (256, 256) and w3.shape[0] == 256 and w3.shape[1] >= 2
         buf = t.empty(int(self.L.pgd_mlp_prepared_bytes(k)), dtype=t.uint8, device=self.device)
-        cur = t.cuda.current_stream(self.device).cuda_stream
-        if cur != self._bound_stream:
-            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-            self._bound_stream = cur
+        self._follow_stream()
         _chk(self.L.pgd_mlp_prepare(self.h, k, 256, C.c_void_p(w1.data_ptr()), C.c_void_p(b1.data_ptr()), C.c_void_p(w2.data_ptr()),
                                     C.c_void_p(b2.data_ptr()), C.c_void_p(w3.data_ptr()), C.c_void_p(b3.data_ptr()), int(w3.shape[1]),
                                     C.c_void_p(buf.data_ptr())), "pgd_mlp_prepare")
@@ -279,10 +277,7 @@ class Engine:
         """Scripted lane-keeping actions for the ego from the last observation (pgd_lane_keep_actions): an action stream that
         keeps the ego driving (bench.py --actions expert).  `out` = float32 cuda tensor [N, 1, 2]."""
         assert out.is_cuda and out.dtype == self.torch.float32 and out.is_contiguous() and out.numel() == self.N * 2
-        cur = self.torch.cuda.current_stream(self.device).cuda_stream
-        if cur != self._bound_stream:
-            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-            self._bound_stream = cur
+        self._follow_stream()
         o = self.obs if obs is None else obs
         _chk(self.L.pgd_lane_keep_actions(self.h, C.c_void_p(o.data_ptr()), C.c_void_p(out.data_ptr()), k_lat, k_head,
                                           v_target_kmh, noise, int(tick) & 0xffffffff), "pgd_lane_keep_actions")
@@ -294,35 +289,23 @@ class Engine:
         `obs`: [rows, stride] float32 cuda (default: the engine's own observation buffer); `out`: float32 cuda [N, A, 2].
         group >= 0: only the rows of that env group, on the group's stream (then `obs` / `out` are still the FULL buffers)."""
         t = self.torch
+        o = self.obs if obs is None else obs
+        o2 = o.view(-1, o.shape[-1])
+        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == self.N * self.A
+        self._check_actions(out)
+        if group < 0:
+            self._follow_stream()
         if prepared is not None:  # split-bf16 kernel on weights prepared by mlp_prepare (`weights` is then ignored)
-            o = self.obs if obs is None else obs
-            o2 = o.view(-1, o.shape[-1])
-            assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == self.N * self.A
-            assert out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and out.numel() == self.N * self.A * 2
             k = int(in_dim if in_dim is not None else prepared._pgd_in_dim)
-            if group < 0:
-                cur = t.cuda.current_stream(self.device).cuda_stream
-                if cur != self._bound_stream:
-                    _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-                    self._bound_stream = cur
             _chk(self.L.pgd_mlp_policy_prepared(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k,
                                                 C.c_void_p(prepared.data_ptr()), int(bool(final_tanh)), C.c_void_p(out.data_ptr())),
                  "pgd_mlp_policy_prepared")
             return out
         w1, b1, w2, b2, w3, b3 = weights
-        o = self.obs if obs is None else obs
-        o2 = o.view(-1, o.shape[-1])
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == self.N * self.A
         for w in weights:
             assert w.is_cuda and w.dtype == t.float32 and w.is_contiguous()
         k = int(in_dim if in_dim is not None else w1.shape[0])
         assert w1.shape == (k, 256) and w2.shape == (256, 256) and w3.shape[0] == 256 and w3.shape[1] >= 2 and k <= o2.shape[1]
-        assert out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and out.numel() == self.N * self.A * 2
-        if group < 0:
-            cur = t.cuda.current_stream(self.device).cuda_stream
-            if cur != self._bound_stream:
-                _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-                self._bound_stream = cur
         _chk(self.L.pgd_mlp_policy(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k, 256,
                                    C.c_void_p(w1.data_ptr()), C.c_void_p(b1.data_ptr()), C.c_void_p(w2.data_ptr()), C.c_void_p(b2.data_ptr()),
                                    C.c_void_p(w3.data_ptr()), C.c_void_p(b3.data_ptr()), int(w3.shape[1]), int(bool(final_tanh)),
@@ -333,10 +316,7 @@ class Engine:
         """One closed-loop step under the scripted lane-keeping policy (pgd_step_lane_keep): the policy reads the engine's own
         observation buffer (what the previous step / reset wrote), the step rewrites it -- one launch on engines with one env per
         wave.  Same results as lane_keep_actions(...) followed by step(...)."""
-        cur = self.torch.cuda.current_stream(self.device).cuda_stream
-        if cur != self._bound_stream:
-            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-            self._bound_stream = cur
+        self._follow_stream()
         p_obs, p_rew, p_done, p_flags = self._own_ptrs
         _chk(self.L.pgd_step_lane_keep(self.h, k_lat, k_head, v_target_kmh, noise, int(tick) & 0xffffffff, p_obs, p_rew, p_done, p_flags),
              "pgd_step_lane_keep")
@@ -356,10 +336,7 @@ class Engine:
         own) is a uint8 tensor; call once after every step / reset (it advances the frame history)."""
         img = self.img if out is None else out
         assert img.is_cuda and img.is_contiguous() and img.dtype in (self.torch.float32, self.torch.uint8) and img.numel() == self.img.numel()
-        cur = self.torch.cuda.current_stream(self.device).cuda_stream
-        if cur != self._bound_stream:
-            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-            self._bound_stream = cur
+        self._follow_stream()
         if img.dtype == self.torch.uint8:
             _chk(self.L.pgd_observe_topdown_u8(self.h, C.c_void_p(img.data_ptr())), "pgd_observe_topdown_u8")
         else:
@@ -390,10 +367,7 @@ class Engine:
         if out is None:
             out = t.empty(shape, dtype=t.uint8, device=self.device)
         assert out.is_cuda and out.dtype == t.uint8 and out.is_contiguous() and tuple(out.shape) == shape
-        cur = t.cuda.current_stream(self.device).cuda_stream
-        if cur != self._bound_stream:
-            _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
-            self._bound_stream = cur
+        self._follow_stream()
         _chk(self.L.pgd_render_topdown(self.h, _np_p(ids), n, C.c_void_p(out.data_ptr())), "pgd_render_topdown")
         return out
 
@@ -422,8 +396,7 @@ class Engine:
     def step_group(self, g, actions):
         """Step only the envs of group g, asynchronously on the group's stream; `actions` is the full [N, A, 2] tensor.
         Returns views of the group's rows of the engine's output buffers."""
-        assert actions.is_cuda and actions.dtype == self.torch.float32 and actions.is_contiguous()
-        assert actions.numel() == self.N * self.A * 2
+        self._check_actions(actions)
         p_obs, p_rew, p_done, p_flags = self._own_ptrs
         _chk(self.L.pgd_step_group(self.h, int(g), C.c_void_p(actions.data_ptr()), p_obs, p_rew, p_done, p_flags), "pgd_step_group")
         sl = self.group_slice(g)

@@ -327,6 +327,28 @@ def test_run_time_kernel_builds_without_a_gpu(tmp_path, monkeypatch):
     assert jit.header_text(cfg2, dict(geom, D=_abi.obs_dim(cfg2)), False, True) != text
 
 
+def test_build_deps_cover_every_included_file():
+    """build.DEPS is what source_sha() stamps and needs_build() watches: every file the translation unit reaches through quoted
+    #includes (followed transitively from build.SRC, next to the including file and under include/) must be listed in it."""
+    import os
+    import re
+    from pgdrive_amd import build
+    deps = {os.path.realpath(d) for d in build.DEPS}
+    dirs = [os.path.realpath(os.path.join(build.HERE, "..", "include"))]
+    seen, todo = set(), [os.path.realpath(build.SRC)]
+    while todo:
+        path = todo.pop()
+        if path in seen:
+            continue
+        seen.add(path)
+        for name in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(path).read(), re.M):
+            found = [p for p in (os.path.realpath(os.path.join(d, name)) for d in [os.path.dirname(path)] + dirs) if os.path.exists(p)]
+            assert found, "%s includes %s, which is not in the tree" % (path, name)
+            todo.append(found[0])
+    assert len(seen) > 10  # (the engine, its csrc headers and the two ABI headers: the walk found the unit)
+    assert seen <= deps, "not in build.DEPS: %s" % sorted(os.path.relpath(p, build.HERE) for p in seen - deps)
+
+
 def test_bench_rows_are_well_formed():
     """bench.py's ROWS: names unique, every override names an option parse_args knows (a typo would silently time the default
     workload), and a row that replays per-group HIP graphs times a whole number of replays per window."""
