@@ -471,6 +471,58 @@ int pgd_render_enable(pgd_handle h, const pgd_render_config* cfg, const double* 
 int pgd_render_topdown(pgd_handle h, const int32_t* h_env_ids, int n, uint8_t* d_frames);
 int pgd_render_palette(uint8_t* out /* [10][3] */);
 
+/* Step info on the device: what the reference returns in the `info` dict of env.step (base_env.py:303-344) and what a trainer needs of
+ * a finished episode, written by one more kernel (k_step_info, pgdrive_amd/csrc/pgd_step_info.h) right after the step kernel on the
+ * same stream.  OPT-IN; single-agent engines only (PGD_ERR_ARG on a multi-agent engine: its terminal rows survive the step anyway).
+ * While it is enabled the step kernel itself never restarts an env: the step leaves the state the episode ended in and its row in
+ * d_obs, and k_step_info, per env and from memory,
+ *   1. writes the info values of that state (every env, every step),
+ *   2. where done: copies the row to final_obs (SB3's terminal_observation, gymnasium's final_observation),
+ *   3. where done: adds the episode to the per-env statistics,
+ *   4. where done and pgd_config.auto_reset: restarts the env exactly as the step kernel would have -- the same re-drawn scenario, the
+ *      same reset image, counters and hints -- writes the first row of the new episode into d_obs and sets PGD_F_RESET.
+ * State, reward, done, flags and the rows of envs that did not restart are bit-identical to those of an engine without step info; the
+ * row of a restarted env comes from the stand-alone row code (as after pgd_reset) instead of the fused one: equal to rounding.
+ * No host synchronisation, no allocation: a step with info is two launches in sequence and can be captured in a HIP graph.
+ * Every pointer is a caller-owned DEVICE array that must stay valid while the info is enabled; NULL = not written.
+ * Not provided: `step_reward` (pgdrive_env.py:248, the shaping reward before the terminal override): it needs the lane formulas of the
+ * reward function, which live in the step kernel only.
+ * pgd_step, pgd_step_group (on the group's stream, over the group's envs) and pgd_step_lane_keep are supported; pgd_step_n and
+ * pgd_step_packed return PGD_ERR_STATE while the info is enabled (terminal rows through the multi-GPU gather: not built).  pgd_reset
+ * clears total_cost and the base of step_energy of the envs it resets, pgd_set_state leaves them.  Enabling or disabling unloads a
+ * run-time step kernel (pgd_set_step_module): it has auto_reset compiled in; build it again afterwards (Engine.specialise does). */
+typedef struct pgd_step_info {
+  float out_of_road_cost, crash_vehicle_cost, crash_object_cost;  /* pgdrive_env.py:105-107, 197-207 */
+  int32_t pad;
+  float* final_obs;         /* [N, D]: the row of the state the episode ended in; written only where done (base_env.py:303-344 returns
+                               it as the step's observation; the auto-reset replaces it in d_obs) */
+  float* velocity;          /* [N] |SF_SPEED| * 3.6 [km/h]                    base_vehicle.py:265, 394-401 */
+  float* steering;          /* [N] SF_STEER                                   base_vehicle.py:266 */
+  float* acceleration;      /* [N] SF_ACT1T (throttle_brake)                  base_vehicle.py:267 */
+  float* episode_energy;    /* [N] SF_ENERGY                                  base_vehicle.py:269, 289-290 */
+  float* step_energy;       /* [N] episode_energy - the previous step's (0 at the start of an episode)  base_vehicle.py:268, 286-288 */
+  float* episode_reward;    /* [N] SF_EP_REWARD                               base_env.py:336-337 */
+  int32_t* episode_length;  /* [N] EI_EP_STEPS                                base_env.py:338-339 */
+  float* cost;              /* [N] out_of_road, else crash_vehicle, else crash_object cost, else 0  pgdrive_env.py:197-207 */
+  float* total_cost;        /* [N] sum of cost over the running episode      safe_pgdrive_env.py:36-40 */
+  /* statistics of the episodes that ended, per env (no atomics: deterministic); the caller reduces them.  No reference counterpart
+   * (the reference's trainers accumulate them from the info dicts) */
+  int32_t* ep_count;        /* [N] episodes ended */
+  float* ep_return_sum;     /* [N] sum of their episode_reward */
+  int32_t* ep_length_sum;   /* [N] sum of their episode_length */
+  float* ep_cost_sum;       /* [N] sum of their total_cost */
+  int32_t* ep_arrive;       /* [N] ended with PGD_F_ARRIVE set */
+  int32_t* ep_out_of_road;  /* [N] ... PGD_F_OUT_OF_ROAD */
+  int32_t* ep_crash;        /* [N] ... PGD_F_CRASH_VEHICLE, PGD_F_CRASH_OBJECT or PGD_F_CRASH_BUILDING */
+  int32_t* ep_max_step;     /* [N] ... PGD_F_MAX_STEP */
+} pgd_step_info;
+int pgd_step_info_enable(pgd_handle h, const pgd_step_info* info /* NULL: disable */);
+/* Zeroes the eight ep_* arrays of the enabled info (asynchronous on the engine's stream). */
+int pgd_step_info_clear_stats(pgd_handle h);
+/* One empty launch of k_step_info's shape (N workgroups of one wave) on the engine's stream: the launch floor that tools/step_info_ab.py
+ * measures beside the plain step and the step with info.  For measurements only; no reference counterpart. */
+int pgd_step_info_empty_launch(pgd_handle h);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * Per-step gather by direct peer writes (multi-GPU, one process per GPU).  The reference has no distributed layer (one env
  * per process, engine_utils.py:8-15); BASELINE.json's north star shards the envs over the GPUs of a node with one gather of

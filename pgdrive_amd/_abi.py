@@ -33,6 +33,21 @@ class RenderConfig(C.Structure):
                 ("light_background", C.c_int32), ("road_rgb", C.c_int32 * 3), ("draw_traffic", C.c_int32)]
 
 
+class StepInfo(C.Structure):
+    """pgd_step_info: three costs and caller-owned device pointers (None = not written)."""
+    _fields_ = [("out_of_road_cost", C.c_float), ("crash_vehicle_cost", C.c_float), ("crash_object_cost", C.c_float), ("pad", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("final_obs", "velocity", "steering", "acceleration", "episode_energy", "step_energy", "episode_reward",
+                                   "episode_length", "cost", "total_cost", "ep_count", "ep_return_sum", "ep_length_sum", "ep_cost_sum",
+                                   "ep_arrive", "ep_out_of_road", "ep_crash", "ep_max_step")]
+
+
+# the tensors of Engine.enable_step_info by pgd_step_info field: (dtype name, key in Engine.step_info)
+STEP_INFO_FIELDS = dict(
+    velocity="float32", steering="float32", acceleration="float32", episode_energy="float32", step_energy="float32",
+    episode_reward="float32", episode_length="int32", cost="float32", total_cost="float32", ep_count="int32", ep_return_sum="float32",
+    ep_length_sum="int32", ep_cost_sum="float32", ep_arrive="int32", ep_out_of_road="int32", ep_crash="int32", ep_max_step="int32")
+
+
 def make_topdown_config(resolution=84, distance=30.0, frame_stack=3, post_stack=5, frame_skip=5, mode=0):
     """mode 1: the single RGB frame of TopDownObservation (obs/top_down_obs.py; reference default resolution 200)."""
     return TopDownConfig(int(resolution), float(distance), int(frame_stack), int(post_stack), int(frame_skip), int(mode))

@@ -1,7 +1,7 @@
 // pgd_engine.hip — the single translation unit of the MI355X-native batched PGDrive step engine and its host side: the engine handle, the
 // launch plan of a step and the C ABI (include/pgdrive_hip.h).  The device code is in the headers included here, in this order: pgd_device.h,
 // pgd_step.h (k_step; it includes pgd_vehicle.h ... pgd_policy.h), pgd_kernels.h (reset / derive / refresh / observe) and, at the end,
-// pgd_topdown.h, pgd_render.h and pgd_gather.h with their own entry points.
+// pgd_topdown.h, pgd_render.h, pgd_gather.h and pgd_step_info.h with their own entry points.
 // The reference call stack this replaces: envs/base_env.py:184-224,303-344.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -69,6 +69,7 @@ struct pgd_engine {
   bool prof_grouped;
   struct pgd_topdown_state* topdown;  // top-down observation (pgd_topdown.h), null until pgd_topdown_enable
   struct pgd_render_state* render;    // top-down scene rendering (pgd_render.h), null until pgd_render_enable
+  struct pgd_step_info_state* sinfo;  // step info (pgd_step_info.h), null unless pgd_step_info_enable switched it on
   int n_groups;          // env groups of pgd_set_groups (1 = none)
   hipStream_t* gstreams; // [n_groups] internal streams
   bool derive_pending;  // records were written through the ABI or the tables changed: k_derive has to run
@@ -297,6 +298,9 @@ static int launch_observe(pgd_engine* h, const ObsLaunch& o, const PgdDev& dv, f
 
 static void topdown_free(pgd_engine* h);
 static void render_free(pgd_engine* h);
+static void step_info_free(pgd_engine* h);
+static int step_info_forget(pgd_engine* h, const int32_t* d_env, int n);
+static int step_info_launch(pgd_engine* h, const EnvGroup& g, const uint8_t* d_done, uint32_t* d_flags, float* d_obs);
 static void render_mark_stale(pgd_engine* h);
 static int render_forget(pgd_engine* h, const int32_t* d_env, int n);
 
@@ -688,6 +692,7 @@ int pgd_reset(pgd_handle h, const int32_t* env_ids, const int32_t* scen_ids, int
   hipLaunchKernelGGL(k_reset, dim3(blocks), dim3(WAVE), 0, h->stream, h->d, d_env, h->d_ids + h->d.N, n);
   HIPCHK(hipGetLastError());
   { int rc = render_forget(h, d_env, n); if (rc) return rc; }  // rendered trails and deads end with the episode
+  { int rc = step_info_forget(h, d_env, n); if (rc) return rc; }  // and so do the running cost and the energy base of the step info
   if (d_obs) return launch_observe(h, observe_launch(h, h->d.N, false), h->d, d_obs, nullptr, h->stream);
   return PGD_OK;
 }
@@ -698,6 +703,7 @@ static int step_impl(pgd_handle h, const float* d_actions, float* d_obs, float* 
   if (!h || !d_actions || !d_reward || !d_done || !d_flags) return PGD_ERR_ARG;
   if (!h->have_maps || !h->have_scen) return PGD_ERR_STATE;
   if (h->img_dirty) return PGD_ERR_STATE;  // the reset image is built by the upload calls
+  if (h->sinfo && packed) return PGD_ERR_STATE;  // step info: no terminal rows through the packed rows of the gather (pgdrive_hip.h)
   HIPCHK(hipSetDevice(h->device));
   StepPlan p;
   { int rc = plan_step(h, d_obs != nullptr, group, p); if (rc) return rc; }
@@ -720,6 +726,7 @@ static int step_impl(pgd_handle h, const float* d_actions, float* d_obs, float* 
   dv.obs_g = observers_per_round(h->d, h->d.A, 1, 0, STEP_MINB_WORDS);  // fused multi-agent observation: what the step's LDS holds
   dv.unit_off = p.g.first / h->d.epw;
   dv.state_rows = p.state_in_step ? d_obs : nullptr;
+  if (h->sinfo) dv.cfg.auto_reset = 0;  // step info: the step leaves the terminal state and row, k_step_info restarts the env (pgd_step_info.h)
   PgdCold cold_arg{dv.scen_map, dv.bev_fill, dv.spawn_hv, dv.respawn_img, dv.n_scen, dv.cfg.seed, dv.cfg.env_base,
                    h->lk.obs, h->lk.k_lat, h->lk.k_head, h->lk.v_target, h->lk.noise, h->lk.tick};
   float* obs_arg = p.fuse ? d_obs : (float*)nullptr;
@@ -739,6 +746,7 @@ static int step_impl(pgd_handle h, const float* d_actions, float* d_obs, float* 
     int rc = launch_observe(h, p.obs, dv, d_obs, is_marl(h) ? d_flags : (const uint32_t*)nullptr, p.g.stream);
     if (rc) return rc;
   }
+  if (h->sinfo) { int rc = step_info_launch(h, p.g, d_done, d_flags, d_obs); if (rc) return rc; }
   h->prof_fused = p.fuse;
   h->prof_grouped = grouped;
   if ((prof && !p.fuse) || timing) HIPCHK(hipEventRecord(prof ? pe[2] : h->ev1, h->stream));  // fused: [0],[1] bracket the only kernel
@@ -755,6 +763,7 @@ int pgd_step(pgd_handle h, const float* d_actions, float* d_obs, float* d_reward
 int pgd_step_n(pgd_handle h, const float* d_action_ring, int ring_len, int first, int n_steps, float* d_obs, float* d_reward,
                uint8_t* d_done, uint32_t* d_flags) {
   if (!h || !d_action_ring || ring_len < 1 || first < 0 || n_steps < 1) return PGD_ERR_ARG;
+  if (h->sinfo) return PGD_ERR_STATE;  // step info is per step: one slice of reward / done / flags, one terminal row (pgdrive_hip.h)
   const size_t na = (size_t)h->d.N * h->d.A;
   for (int k = 0; k < n_steps; ++k) {
     const float* act = d_action_ring + (size_t)((first + k) % ring_len) * na * 2;
@@ -931,7 +940,8 @@ int pgd_forget_rows(pgd_handle h) {
 
 int pgd_describe_step(pgd_handle h, char* buf, int cap) {
   if (!h || !buf || cap <= 0) return PGD_ERR_ARG;
-  snprintf(buf, (size_t)cap, "%s%s", h->last_step_kernel ? h->last_step_kernel : "",
+  snprintf(buf, (size_t)cap, "%s%s%s", h->last_step_kernel ? h->last_step_kernel : "",
+           (h->sinfo && h->last_step_kernel) ? " + k_step_info (step info: the step kernel never restarts an env, this kernel does)" : "",
            h->left_pack_mode ? " [throughput mode switched off by pgd_set_groups: the group size is not a whole number of three-env waves]" : "");
   return PGD_OK;
 }
@@ -1199,6 +1209,7 @@ int pgd_destroy(pgd_handle h) {
   }
   topdown_free(h);
   render_free(h);
+  step_info_free(h);
   delete h->h_maps;
   delete h->h_scen;
   if (h->own_stream) (void)hipStreamDestroy(h->stream);
@@ -1212,4 +1223,5 @@ int pgd_destroy(pgd_handle h) {
 #include "pgd_topdown.h"
 #include "pgd_render.h"
 #include "pgd_gather.h"
+#include "pgd_step_info.h"
 #endif  // !PGD_JIT

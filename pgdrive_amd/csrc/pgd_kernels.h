@@ -140,17 +140,13 @@ __global__ __launch_bounds__(WAVE) void k_refresh(PgdDev d) {
 // BLOCK threads produce one row.  BLOCK = 64: the block holds OBS_RPB independent rows, one per wave (a block per 64-lane
 // row made the launch dispatch-bound: 32768 workgroups that each live ~5 us); BLOCK = 256: one row per block.
 #define OBS_RPB 1
+// The row of (env e, agent a) by the BLOCK threads `tid` of one row: k_observe's body, shared with k_step_info (pgd_step_info.h: the
+// first row of an episode it has just started).  `L`: the row's compaction scratch in LDS.
 template <int BLOCK, bool OTH>
-__global__ __launch_bounds__(BLOCK == WAVE ? WAVE * OBS_RPB : BLOCK) void k_observe(PgdDev d, float* __restrict__ obs,
-                                                                                 const uint32_t* __restrict__ flags, int n_rows) {
+DEV void observe_row(const PgdDev& d, float* __restrict__ obs, const uint32_t* __restrict__ flags, int e, int a, int tid, ObsLds& L,
+                     int scen_known = -1) {  // (scen_known >= 0: the env's scenario, where the caller has just written EI_SCEN itself)
   constexpr bool WROW = BLOCK == WAVE;
-  __shared__ ObsLds Ls[WROW ? OBS_RPB : 1];
   const int V = d.V, A = d.A, D = d.D;
-  const int rowi = WROW ? (int)blockIdx.x * OBS_RPB + (int)(threadIdx.x / WAVE) : (int)blockIdx.x;
-  if (rowi >= n_rows) return;
-  ObsLds& L = Ls[WROW ? threadIdx.x / WAVE : 0];
-  const int e = rowi / A + d.unit_off * d.epw, a = rowi % A;
-  const int tid = WROW ? (int)(threadIdx.x % WAVE) : (int)threadIdx.x;
   const RecPiece* recs = rec_block(d.rec, (size_t)e, V);  // the env's vehicle records
   float* row = obs + (size_t)e * d.ostride + (size_t)a * D;
   PHASE_INIT();
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(BLOCK == WAVE ? WAVE * OBS_RPB : BLOCK) void k_obse
 #pragma unroll
   for (int k = 0; k < 4; ++k) bw[k] = recs[k * V + ob].q;
   const uint32_t fa = flags ? flags[(size_t)e * A + a] : 0u, fo = flags ? flags[(size_t)e * A + (tid < A ? tid : 0)] : 0u;
-  const int scen = d.ei[(size_t)(e) * PGD_NEI + EI_SCEN];
+  const int scen = scen_known >= 0 ? scen_known : d.ei[(size_t)(e) * PGD_NEI + EI_SCEN];
   const uint32_t tick = (uint32_t)d.ei[(size_t)(e) * PGD_NEI + EI_STEPS_TOTAL];
   Veh body;  // only the first 64 bytes are filled
 #pragma unroll
@@ -228,6 +224,17 @@ __global__ __launch_bounds__(BLOCK == WAVE ? WAVE * OBS_RPB : BLOCK) void k_obse
   if (OTH) observe_agent<true, false, true, false, WROW>(d, mv, msp, ag, L, row, tid, BLOCK, recs, spb);
   else observe_agent<true, false, false, false, WROW>(d, mv, msp, ag, L, row, tid, BLOCK);
   PHASE_END_AT(29);
+}
+
+template <int BLOCK, bool OTH>
+__global__ __launch_bounds__(BLOCK == WAVE ? WAVE * OBS_RPB : BLOCK) void k_observe(PgdDev d, float* __restrict__ obs,
+                                                                                 const uint32_t* __restrict__ flags, int n_rows) {
+  constexpr bool WROW = BLOCK == WAVE;
+  __shared__ ObsLds Ls[WROW ? OBS_RPB : 1];
+  const int rowi = WROW ? (int)blockIdx.x * OBS_RPB + (int)(threadIdx.x / WAVE) : (int)blockIdx.x;
+  if (rowi >= n_rows) return;
+  observe_row<BLOCK, OTH>(d, obs, flags, rowi / d.A + d.unit_off * d.epw, rowi % d.A, WROW ? (int)(threadIdx.x % WAVE) : (int)threadIdx.x,
+                          Ls[WROW ? threadIdx.x / WAVE : 0]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

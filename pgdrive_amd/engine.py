@@ -40,6 +40,9 @@ _SIGS = {
     "pgd_topdown_enable": (C.c_int, [C.c_void_p, C.POINTER(_abi.TopDownConfig)]),
     "pgd_observe_topdown": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pgd_observe_topdown_u8": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pgd_step_info_enable": (C.c_int, [C.c_void_p, C.POINTER(_abi.StepInfo)]),
+    "pgd_step_info_clear_stats": (C.c_int, [C.c_void_p]),
+    "pgd_step_info_empty_launch": (C.c_int, [C.c_void_p]),
     "pgd_render_enable": (C.c_int, [C.c_void_p, C.POINTER(_abi.RenderConfig), C.c_void_p]),
     "pgd_render_topdown": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pgd_render_palette": (C.c_int, [C.c_void_p]),
@@ -149,6 +152,7 @@ class Engine:
         self._bound_stream = self.stream.cuda_stream  # the stream pgd_create was given
         self._own_ptrs = tuple(C.c_void_p(t.data_ptr()) for t in (self.obs, self.reward, self.done, self.flags))
         self._seen_out = []  # caller-supplied observation tensors of the last steps, kept alive (see step)
+        self.step_info = None  # the dict of enable_step_info while the step info is on
         torch.cuda.synchronize(dev)
 
     def _follow_stream(self):
@@ -342,6 +346,49 @@ class Engine:
         else:
             _chk(self.L.pgd_observe_topdown(self.h, C.c_void_p(img.data_ptr())), "pgd_observe_topdown")
         return img
+
+    # -- step info on the device (pgd_step_info: terminal observation, the reference's info floats, episode statistics) ---------------
+    def enable_step_info(self, costs=(1.0, 1.0, 1.0), final_obs=True):
+        """Switch on the step info (include/pgdrive_hip.h, pgd_step_info_enable): one more launch per step writes, for every env, the
+        reference's info floats, and for every env whose episode ended the terminal row and the episode's statistics; the env is then
+        restarted by that launch instead of by the step kernel (same state, reward, done, flags).  `costs` = (out_of_road_cost,
+        crash_vehicle_cost, crash_object_cost); final_obs=False: no terminal row (engines whose observation is an image).  Allocates the
+        tensors once and returns them as a dict (also `self.step_info`): [N] each, "final_observation" [N, D] or None.  The values of
+        a step are valid until the next step; the ep_* statistics accumulate until episode_stats(clear=True)."""
+        t = self.torch
+        info = {k: t.zeros((self.N, ), dtype=getattr(t, dt), device=self.device) for k, dt in _abi.STEP_INFO_FIELDS.items()}
+        info["final_observation"] = t.zeros((self.N, self.D), dtype=t.float32, device=self.device) if final_obs else None
+        si = _abi.StepInfo()
+        si.out_of_road_cost, si.crash_vehicle_cost, si.crash_object_cost = (float(c) for c in costs)
+        for k in _abi.STEP_INFO_FIELDS:
+            setattr(si, k, info[k].data_ptr())
+        si.final_obs = info["final_observation"].data_ptr() if final_obs else None
+        self.torch.cuda.synchronize(self.device)
+        _chk(self.L.pgd_step_info_enable(self.h, C.byref(si)), "pgd_step_info_enable")
+        self.step_info = info
+        return info
+
+    def disable_step_info(self):
+        """Back to the plain step (pgd_step_info_enable with NULL): the step kernel restarts finished envs itself again."""
+        self.torch.cuda.synchronize(self.device)
+        _chk(self.L.pgd_step_info_enable(self.h, None), "pgd_step_info_enable")
+        self.step_info = None
+
+    def episode_stats(self, clear=True):
+        """The per-env statistics of the episodes that ended since the last clear, reduced with torch (one synchronisation): episodes,
+        mean return, mean length, mean cost and the rates of the four outcomes (None where no episode ended)."""
+        if self.step_info is None:
+            raise PgdError("episode_stats needs enable_step_info")
+        s = self.step_info
+        self._follow_stream()
+        sums = self.torch.stack([s[k].sum(dtype=self.torch.float64) for k in (
+            "ep_count", "ep_return_sum", "ep_length_sum", "ep_cost_sum", "ep_arrive", "ep_out_of_road", "ep_crash", "ep_max_step")]).cpu().numpy()
+        if clear:
+            _chk(self.L.pgd_step_info_clear_stats(self.h), "pgd_step_info_clear_stats")
+        n = int(round(float(sums[0])))
+        mean = (lambda x: float(x) / n) if n else (lambda x: None)
+        return dict(episodes=n, mean_return=mean(sums[1]), mean_length=mean(sums[2]), mean_cost=mean(sums[3]), arrive_rate=mean(sums[4]),
+                    out_of_road_rate=mean(sums[5]), crash_rate=mean(sums[6]), max_step_rate=mean(sums[7]))
 
     # -- top-down scene rendering (env.render(mode="top_down"), obs/top_down_renderer.py) --------------------------------------------
     def enable_render(self, cfg=None):

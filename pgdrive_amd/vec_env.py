@@ -74,6 +74,9 @@ DEFAULT_CONFIG = dict(
     jit_step_kernel=False,  # NOT a reference key: True builds, in a background thread, a step kernel with this env's configuration
                             # compiled in (pgdrive_amd/jit.py; ~8 s of hipcc once per configuration, cached): configurations
                             # without an instantiation in the library then step 12 - 17 % faster
+    step_info=False,  # NOT a reference key: True keeps the reference's step-info floats, the terminal observation of every episode that ends
+                      # and per-env episode statistics on the device (env.last_info, env.episode_stats(); include/pgdrive_hip.h
+                      # pgd_step_info) at one more launch per step; step() keeps its 4-tuple
     IDM_agent=False,  # the ego is driven by IDMPolicy along its route, step()'s actions are ignored (base_env.py:30, agent_manager.py:79)
     map_bank=None,  # path of a pre-generated description bank; None -> generate with our BIG (pgdrive_amd/mapgen.py)
 )
@@ -245,8 +248,15 @@ class PGDriveVecEnv:
         from .engine import Engine
         self.engine = Engine(self.cfg, self.map_bank, self.scen_bank, device=c["device"])
         self.obs_dim = self.engine.D
-        self._jit_thread = self.engine.specialise(wait=False) if c["jit_step_kernel"] else None  # (join() it to wait for the module)
         self.topdown = bool(c["use_topdown"])
+        # step info on the device: the costs are the env's own *_cost keys; with the top-down observation no terminal IMAGE is built
+        # (last_info["final_observation"] is None), the info tensors and the statistics work as with the vector observation.
+        # Before the run-time kernel is asked for: that kernel is generated for an engine whose step never restarts an env
+        self.last_info = None
+        if c["step_info"]:
+            self.last_info = self.engine.enable_step_info(
+                costs=(c["out_of_road_cost"], c["crash_vehicle_cost"], c["crash_object_cost"]), final_obs=not self.topdown)
+        self._jit_thread = self.engine.specialise(wait=False) if c["jit_step_kernel"] else None  # (join() it to wait for the module)
         if self.topdown:
             # rgb_clip=False (pgdrive_env.py:133-141): the images as uint8 in [0, 255] (pgd_observe_topdown_u8) instead of float32 / 255
             # (the single-frame observation is built without a `resolution` argument upstream: TopDownObservation.RESOLUTION = 200,
@@ -283,7 +293,12 @@ class PGDriveVecEnv:
         return obs.view(self.num_envs, self.obs_dim)
 
     def step(self, actions):
-        """actions: cuda float32 tensor [N, 2] -> (obs [N,D], reward [N], done [N] uint8, flags [N] int32) on the GPU."""
+        """actions: cuda float32 tensor [N, 2] -> (obs [N,D], reward [N], done [N] uint8, flags [N] int32) on the GPU.
+        With step_info=True, `self.last_info` (a dict of device tensors, the same tensors every step) then holds the step's info:
+        velocity, steering, acceleration, step_energy, episode_energy, episode_reward, episode_length, cost, total_cost [N] of the state
+        the step ended in -- the terminal state where done -- and "final_observation" [N, D], whose row e is the terminal row of the
+        last episode env e finished (written only where done; obs[e] is then the first row of the next episode).  Valid until the
+        next step, like obs."""
         if self.config["vehicle_config"]["action_check"]:  # opt-in: costs a device round trip
             a = actions.reshape(self.num_envs, 2)
             if self.config["discrete_action"]:
@@ -335,6 +350,11 @@ class PGDriveVecEnv:
 
     def group_slice(self, g):
         return self.engine.group_slice(g)
+
+    def episode_stats(self, clear=True):
+        """Statistics of the episodes that ended since the last clear (step_info=True; Engine.episode_stats): episodes, mean return /
+        length / cost, arrive / out_of_road / crash / max_step rates.  One device synchronisation."""
+        return self.engine.episode_stats(clear=clear)
 
     def info_from_flags(self, flags):
         """Host-side decode of the flag bit-field into the reference's info keys (pgdrive_env.py:165-194)."""
