@@ -260,8 +260,15 @@ int pgd_upload_maps(pgd_handle h, const pgd_map* h_maps, int n_maps, const pgd_l
  * traffic_manager.py:48-69,239-290): a bank of scenarios, each with V spawn slots.  HOST arrays, copied. */
 int pgd_upload_scenarios(pgd_handle h, const pgd_scenario* h_scen, int n_scen, const pgd_spawn* h_spawns /*[n_scen*V]*/);
 
-/* Replaces env.reset(force_seed) (envs/base_env.py:269-301) for the listed envs (h_env_ids == NULL -> all):
- * env e starts scenario h_scen_ids[i]; writes the first observation.  d_obs may be NULL. */
+/* Replaces env.reset(force_seed) (envs/base_env.py:269-301) for the listed envs (h_env_ids == NULL -> envs 0 .. n - 1):
+ * env h_env_ids[i] starts scenario h_scen_ids[i].  1 <= n <= N; an id outside [0, N), an id listed twice or a scenario that was not
+ * uploaded is PGD_ERR_ARG and leaves the engine as it was.  Both HOST lists are copied before the call returns; the call is
+ * asynchronous on the stream.  d_obs may be NULL.  Which rows of d_obs are written:
+ *   h_env_ids == NULL   every row of every env (those of envs n .. N - 1 from their present state);
+ *   an id list          the rows of the listed envs and no others.  Every other row keeps its bytes -- the terminal rows the last
+ *                       step wrote for envs that are not restarted are still there --, and the zero-row marks of the other envs
+ *                       (pgd_step) go on describing the buffer they were made for.
+ * The restart does not count as an episode of EI_EPISODES and does not touch EI_STEPS_TOTAL (counters of the device RNG streams). */
 int pgd_reset(pgd_handle h, const int32_t* h_env_ids, const int32_t* h_scen_ids, int n, float* d_obs /*[N,A,D]*/);
 
 /* Replaces env.step(action) (envs/base_env.py:184-224, 303-344) for all N envs.  Asynchronous on the stream.

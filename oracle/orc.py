@@ -130,10 +130,14 @@ class Oracle:
                 sp64 = np.ascontiguousarray(sp64, dtype=np.float64)
                 assert sp64.shape == (len(scen.spawns), 12) and self.L.orc_upload_spawns_f64(self.h, _p(sp64), len(sp64)) == 0
 
-    def reset(self, scen_ids, env_ids=None):
+    def reset(self, scen_ids, env_ids=None, out=None):
+        """With `env_ids` only the rows of the listed envs are written (into `out`, a float64 [N, A, D] array; default: a new one of
+        zeros): every other row keeps its bytes."""
         scen_ids = np.ascontiguousarray(scen_ids, dtype=np.int32)
         env_ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32)
-        obs = np.zeros((self.N, self.A, self.D), dtype=np.float64)
+        assert env_ids is None or len(env_ids) == len(scen_ids)
+        obs = np.zeros((self.N, self.A, self.D), dtype=np.float64) if out is None else out
+        assert obs.dtype == np.float64 and obs.shape == (self.N, self.A, self.D) and obs.flags.c_contiguous
         self.L.orc_reset(self.h, _p(env_ids), _p(scen_ids), C.c_int(len(scen_ids)), _p(obs))
         return obs
 

@@ -114,20 +114,21 @@ static int env_group(const pgd_engine* h, int group, EnvGroup& g) {
 
 using StepFn = void (*)(PgdDev, const float*, float*, uint8_t*, uint32_t*, float*, PgdCold);
 using ObsFn = void (*)(PgdDev, float*, const uint32_t*, int);
+using ObsIdsFn = void (*)(PgdDev, float*, const int32_t*, int);  // k_observe_ids / k_observe_env_ids: pgd_reset with an id list
 // The multi-agent instantiations with the seat count folded (PGD_FIXM_SEAT_FIELDS; code = seats x 1000 + beams).  40 and 44 seats
 // observe with k_observe_env<4> after the step (before / after k_step wrote the state blocks); 8 seats fuse the observation into k_step.
-struct SeatKernels { int code; StepFn step; const char* name; ObsFn observe, observe_after_state; };
+struct SeatKernels { int code; StepFn step; const char* name; ObsFn observe, observe_after_state; ObsIdsFn observe_ids; };
 static const SeatKernels SEAT_KERNELS[] = {
     {40072, k_step<true, true, false, false, 40072>,
      "k_step: one env per wave, specialised for the default multi-agent configuration with 40 agent seats x 72 beams",
-     k_observe_env<4, true, true, 40072>, k_observe_env<4, true, false, 40072>},
+     k_observe_env<4, true, true, 40072>, k_observe_env<4, true, false, 40072>, k_observe_env_ids<4, true, 40072>},
     {44072, k_step<true, true, false, false, 44072>,
      "k_step: one env per wave, specialised for the default multi-agent configuration with 44 agent seats x 72 beams",
-     k_observe_env<4, true, true, 44072>, k_observe_env<4, true, false, 44072>},
+     k_observe_env<4, true, true, 44072>, k_observe_env<4, true, false, 44072>, k_observe_env_ids<4, true, 44072>},
     {8072, k_step<true, true, false, false, 8072>,
-     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 72 beams", nullptr, nullptr},
+     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 72 beams", nullptr, nullptr, nullptr},
     {8240, k_step<true, true, false, false, 8240>,
-     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 240 beams", nullptr, nullptr},
+     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 240 beams", nullptr, nullptr, nullptr},
 };
 // which of them (null = none) an engine that passed FIXK_MARL can run
 static const SeatKernels* marl_fix_seats(const PgdDev& d) {
@@ -248,6 +249,26 @@ static ObsLaunch observe_launch(const pgd_engine* h, int envs, bool state_done) 
   const SeatKernels* seats = (fix && four) ? marl_fix_seats(h->d) : nullptr;
   if (seats && seats->observe) ke = state_done ? seats->observe_after_state : seats->observe;
   return {ke, dim3(envs), dim3(WAVE * p.nw), p.dyn, p.G, false};
+}
+
+// observe_launch(h, n, false) for the n envs of an id list (pgd_reset): the same choice of kernel, geometry and LDS, unit k = env ids[k]
+struct ObsIdsLaunch { ObsIdsFn fn; dim3 grid, block; size_t lds; int arg; bool forget_marks; };
+static ObsIdsLaunch observe_ids_launch(const pgd_engine* h, int n) {
+  const ObsLaunch o = observe_launch(h, n, false);
+  const ObsEnvPlan p = observe_env_plan(h);
+  ObsIdsFn kern;
+  if (!p.use) {
+    const bool oth = others_state_rows(h);
+    kern = h->d.cfg.num_lasers > 128 ? (oth ? k_observe_ids<256, true> : k_observe_ids<256, false>)
+                                     : (oth ? k_observe_ids<64, true> : k_observe_ids<64, false>);
+  } else {
+    const bool four = p.nw == 4, fix = marl_fix_ok(h);
+    kern = four ? k_observe_env_ids<4> : k_observe_env_ids<1>;
+    if (fix) kern = four ? k_observe_env_ids<4, true> : k_observe_env_ids<1, true>;
+    const SeatKernels* seats = (fix && four) ? marl_fix_seats(h->d) : nullptr;
+    if (seats && seats->observe_ids) kern = seats->observe_ids;
+  }
+  return {kern, o.grid, o.block, o.lds, o.arg, o.forget_marks};
 }
 
 // What one step launches, decided once per step (pgd_set_groups, the uploads and pgd_set_step_module change what it reads): the env group,
@@ -669,9 +690,15 @@ int pgd_reset(pgd_handle h, const int32_t* env_ids, const int32_t* scen_ids, int
   if (!h || !scen_ids || n <= 0 || n > h->d.N) return PGD_ERR_ARG;
   if (!h->have_maps || !h->have_scen) return PGD_ERR_STATE;
   HIPCHK(hipSetDevice(h->device));
-  for (int k = 0; k < n; ++k) {
+  for (int k = 0; k < n; ++k)
     if (scen_ids[k] < 0 || scen_ids[k] >= h->d.n_scen) return PGD_ERR_ARG;
-    if (env_ids && (env_ids[k] < 0 || env_ids[k] >= h->d.N)) return PGD_ERR_ARG;
+  if (env_ids) {  // in range and no env twice (two units of k_reset would write one env at the same time)
+    std::vector<uint8_t> seen((size_t)h->d.N, 0);
+    for (int k = 0; k < n; ++k) {
+      const int e = env_ids[k];
+      if (e < 0 || e >= h->d.N || seen[(size_t)e]) return PGD_ERR_ARG;
+      seen[(size_t)e] = 1;
+    }
   }
   // the caller's id lists are copied into pinned staging here, so they may be reused as soon as this call returns and the
   // stream is not synchronised (a partial reset between two steps does not stall the device); the staging buffer itself
@@ -693,6 +720,13 @@ int pgd_reset(pgd_handle h, const int32_t* env_ids, const int32_t* scen_ids, int
   HIPCHK(hipGetLastError());
   { int rc = render_forget(h, d_env, n); if (rc) return rc; }  // rendered trails and deads end with the episode
   { int rc = step_info_forget(h, d_env, n); if (rc) return rc; }  // and so do the running cost and the energy base of the step info
+  if (d_obs && d_env) {  // an id list: the rows of the listed envs and no others (the rest of d_obs keeps its bytes)
+    const ObsIdsLaunch o = observe_ids_launch(h, n);
+    if (o.forget_marks) { int rc = obs_rows_forget(h, h->stream); if (rc) return rc; }
+    hipLaunchKernelGGL(o.fn, o.grid, o.block, o.lds, h->stream, h->d, d_obs, d_env, o.arg);
+    HIPCHK(hipGetLastError());
+    return PGD_OK;
+  }
   if (d_obs) return launch_observe(h, observe_launch(h, h->d.N, false), h->d, d_obs, nullptr, h->stream);
   return PGD_OK;
 }

@@ -268,6 +268,30 @@ __global__ PGD_KOE_ATTR __launch_bounds__(WAVE * NW, (FIX ? 7 : 1)) void k_obser
   observe_env_body<NW, !FIX, false, !FIX, STATE, CAP>(d, (int)blockIdx.x + d.unit_off * d.epw, obs, flags, M, s_minb_dyn, G);  // (the fixed-config kernel: no traffic objects)
 }
 
+// The two kernels above for an id list (pgd_reset with env ids): unit k of the launch observes env env_ids[k] and nothing else -- the
+// rows of every other env keep their bytes, and so do their zero-row marks.  Kernels of their own, so that the ones a step launches stay
+// as they are; no step flags (the state right after a reset).
+template <int BLOCK, bool OTH>
+__global__ __launch_bounds__(BLOCK == WAVE ? WAVE * OBS_RPB : BLOCK) void k_observe_ids(PgdDev d, float* __restrict__ obs,
+                                                                                     const int32_t* __restrict__ env_ids, int n_rows) {
+  constexpr bool WROW = BLOCK == WAVE;
+  __shared__ ObsLds Ls[WROW ? OBS_RPB : 1];
+  const int rowi = WROW ? (int)blockIdx.x * OBS_RPB + (int)(threadIdx.x / WAVE) : (int)blockIdx.x;
+  if (rowi >= n_rows) return;
+  observe_row<BLOCK, OTH>(d, obs, nullptr, env_ids[rowi / d.A], rowi % d.A, WROW ? (int)(threadIdx.x % WAVE) : (int)threadIdx.x,
+                          Ls[WROW ? threadIdx.x / WAVE : 0]);
+}
+
+template <int NW, bool FIX = false, int SEATS = 0>
+__global__ PGD_KOE_ATTR __launch_bounds__(WAVE * NW, (FIX ? 7 : 1)) void k_observe_env_ids(PgdDev d, float* __restrict__ obs, const int32_t* __restrict__ env_ids, int G) {
+  if (FIX) write_fixed_config<true, true, false, (SEATS ? SEATS : 1)>(d);
+  extern __shared__ unsigned s_minb_dyn[];
+  constexpr int CAP = SEATS ? (SEATS / 1000 + 15) / 16 * 16 : WAVE;
+  __shared__ ObsEnvLds<NW, CAP> M;
+  PHASE_INIT();
+  observe_env_body<NW, !FIX, false, !FIX, true, CAP>(d, env_ids[blockIdx.x], obs, nullptr, M, s_minb_dyn, G);
+}
+
 // scripted lane-keeping policy (pgd_lane_keep_actions): one thread per env
 __global__ __launch_bounds__(256) void k_lane_keep(PgdDev d, const float* __restrict__ obs, float* __restrict__ act, float k_lat,
                                                   float k_head, float v_target, float noise, uint32_t tick) {

@@ -169,14 +169,31 @@ class Engine:
         assert actions.numel() == self.N * self.A * 2
 
     # -- reference surface ------------------------------------------------------------------------------------------
-    def reset(self, scen_ids, env_ids=None):
-        scen_ids = np.ascontiguousarray(scen_ids, dtype=np.int32)
-        env_ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32)
+    def reset(self, scen_ids, env_ids=None, out=None):
+        """Restart the envs `env_ids` (None: all N, in order) with the scenarios `scen_ids` and write their first rows into `out`
+        (default: the engine's own observation buffer, which is returned).  With an id list only the rows of the listed envs are
+        written: every other row of the buffer keeps its bytes, e.g. the terminal rows the last step left there."""
+        scen_ids = np.ascontiguousarray(scen_ids, dtype=np.int32).reshape(-1)
+        env_ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
+        if env_ids is not None and len(env_ids) != len(scen_ids):  # (the library reads len(scen_ids) entries of both)
+            raise ValueError("reset: %d env ids for %d scenario ids" % (len(env_ids), len(scen_ids)))
+        obs = self.obs if out is None else out
+        assert obs.is_cuda and obs.dtype == self.torch.float32 and obs.is_contiguous() and obs.numel() == self.obs.numel()
         self.torch.cuda.synchronize(self.device)
-        _chk(self.L.pgd_reset(self.h, _np_p(env_ids), _np_p(scen_ids), len(scen_ids), C.c_void_p(self.obs.data_ptr())),
+        if obs is not self.obs and self._unseen_rows(obs):
+            _chk(self.L.pgd_forget_rows(self.h), "pgd_forget_rows")
+        _chk(self.L.pgd_reset(self.h, _np_p(env_ids), _np_p(scen_ids), len(scen_ids), C.c_void_p(obs.data_ptr())),
              "pgd_reset")
         self.sync()
-        return self.obs
+        return obs
+
+    def _unseen_rows(self, obs):
+        """Is `obs` a caller's observation tensor this multi-agent engine has not seen alive (see step)?  It is kept alive from now on."""
+        if self.A > 1 and not any(t is obs for t in self._seen_out):
+            self._seen_out.append(obs)
+            del self._seen_out[:-4]
+            return True
+        return False
 
     def make_outputs(self):
         """A second set of output buffers (double buffering of the per-step gather, pgdrive_amd/dist.py)."""
@@ -207,10 +224,7 @@ class Engine:
             # (torch's caching allocator; `out=torch.empty(...)` per step) and would inherit "known zero" marks for rows that hold
             # anything.  Tensors seen before are kept alive here (their memory cannot be handed out again); any other tensor makes
             # the engine forget its marks first.
-            if want_obs and self.A > 1 and not any(t is obs for t in self._seen_out):
-                forget_first = True
-                self._seen_out.append(obs)
-                del self._seen_out[:-4]
+            forget_first = want_obs and self._unseen_rows(obs)
         self._follow_stream()
         if forget_first:
             _chk(self.L.pgd_forget_rows(self.h), "pgd_forget_rows")
