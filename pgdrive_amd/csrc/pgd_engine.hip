@@ -114,21 +114,24 @@ static int env_group(const pgd_engine* h, int group, EnvGroup& g) {
 
 using StepFn = void (*)(PgdDev, const float*, float*, uint8_t*, uint32_t*, float*, PgdCold);
 using ObsFn = void (*)(PgdDev, float*, const uint32_t*, int);
-using ObsIdsFn = void (*)(PgdDev, float*, const int32_t*, int);  // k_observe_ids / k_observe_env_ids: pgd_reset with an id list
+using ObsIdsFn = void (*)(PgdDev, float*, const int32_t*, int);
+// One observation kernel in its launch forms: over an env range (pgd_observe, a full pgd_reset, after a step), over an env range after
+// k_step has written the state blocks (null: no such form), and over an id list (pgd_reset with env ids).
+struct ObsKernels { ObsFn range, after_state; ObsIdsFn ids; };
 // The multi-agent instantiations with the seat count folded (PGD_FIXM_SEAT_FIELDS; code = seats x 1000 + beams).  40 and 44 seats
-// observe with k_observe_env<4> after the step (before / after k_step wrote the state blocks); 8 seats fuse the observation into k_step.
-struct SeatKernels { int code; StepFn step; const char* name; ObsFn observe, observe_after_state; ObsIdsFn observe_ids; };
+// observe with k_observe_env<4> after the step; 8 seats fuse the observation into k_step (obs.range null).
+struct SeatKernels { int code; StepFn step; const char* name; ObsKernels obs; };
 static const SeatKernels SEAT_KERNELS[] = {
     {40072, k_step<true, true, false, false, 40072>,
      "k_step: one env per wave, specialised for the default multi-agent configuration with 40 agent seats x 72 beams",
-     k_observe_env<4, true, true, 40072>, k_observe_env<4, true, false, 40072>, k_observe_env_ids<4, true, 40072>},
+     {k_observe_env<4, true, true, 40072>, k_observe_env<4, true, false, 40072>, k_observe_env_ids<4, true, 40072>}},
     {44072, k_step<true, true, false, false, 44072>,
      "k_step: one env per wave, specialised for the default multi-agent configuration with 44 agent seats x 72 beams",
-     k_observe_env<4, true, true, 44072>, k_observe_env<4, true, false, 44072>, k_observe_env_ids<4, true, 44072>},
+     {k_observe_env<4, true, true, 44072>, k_observe_env<4, true, false, 44072>, k_observe_env_ids<4, true, 44072>}},
     {8072, k_step<true, true, false, false, 8072>,
-     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 72 beams", nullptr, nullptr, nullptr},
+     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 72 beams", {}},
     {8240, k_step<true, true, false, false, 8240>,
-     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 240 beams", nullptr, nullptr, nullptr},
+     "k_step: one env per wave, specialised for the default multi-agent configuration with 8 agent seats x 240 beams", {}},
 };
 // which of them (null = none) an engine that passed FIXK_MARL can run
 static const SeatKernels* marl_fix_seats(const PgdDev& d) {
@@ -230,49 +233,34 @@ static bool state_in_step_ok(const pgd_engine* h) {
          !(c.marl_flags & (PGD_MA_TOLLGATE | PGD_MA_OTHERS_STATE)) && c.num_lasers > 0 && !h->sw.no_state_in_step;
 }
 
-// A stand-alone observation launch over `envs` envs (pgd_reset, pgd_observe, a step that does not write the rows itself).  arg: observers
-// per round (k_observe_env) / rows (k_observe, which does not keep the zero-row marks: forget them first).  state_done: see above.
-struct ObsLaunch { ObsFn fn; dim3 grid, block; size_t lds; int arg; bool forget_marks; };
+// A stand-alone observation launch over `envs` envs (pgd_reset, pgd_observe, a step that does not write the rows itself): the kernel
+// -- chosen here and nowhere else -- with the launch geometry that all its forms share.  arg: observers per round (k_observe_env) / rows
+// (k_observe, which does not keep the zero-row marks: forget them first).  state_done: k_step has written the state blocks (see above).
+struct ObsLaunch { ObsKernels k; bool state_done; dim3 grid, block; size_t lds; int arg; bool forget_marks; };
 static ObsLaunch observe_launch(const pgd_engine* h, int envs, bool state_done) {
   const ObsEnvPlan p = observe_env_plan(h);
   if (!p.use) {
     const int rows = envs * h->d.A;
     const bool oth = others_state_rows(h);
     const bool wide = h->d.cfg.num_lasers > 128;  // up to 128 beams one wave does it in two rounds: 4x fewer waves than 256-thread blocks
-    ObsFn kern = wide ? (oth ? k_observe<256, true> : k_observe<256, false>) : (oth ? k_observe<64, true> : k_observe<64, false>);
-    return {kern, dim3(wide ? rows : (rows + OBS_RPB - 1) / OBS_RPB), dim3(wide ? 256 : WAVE * OBS_RPB), 0, rows, true};
+    const ObsKernels k = wide ? (oth ? ObsKernels{k_observe<256, true>, nullptr, k_observe_ids<256, true>}
+                                     : ObsKernels{k_observe<256, false>, nullptr, k_observe_ids<256, false>})
+                              : (oth ? ObsKernels{k_observe<64, true>, nullptr, k_observe_ids<64, true>}
+                                     : ObsKernels{k_observe<64, false>, nullptr, k_observe_ids<64, false>});
+    return {k, false, dim3(wide ? rows : (rows + OBS_RPB - 1) / OBS_RPB), dim3(wide ? 256 : WAVE * OBS_RPB), 0, rows, true};
   }
   const bool four = p.nw == 4, fix = marl_fix_ok(h);
-  ObsFn ke = four ? k_observe_env<4> : k_observe_env<1>;
-  if (fix) ke = four ? k_observe_env<4, true> : k_observe_env<1, true>;
-  if (state_done && four) ke = fix ? k_observe_env<4, true, false> : k_observe_env<4, false, false>;
+  ObsKernels k = four ? ObsKernels{k_observe_env<4>, k_observe_env<4, false, false>, k_observe_env_ids<4>}
+                      : ObsKernels{k_observe_env<1>, nullptr, k_observe_env_ids<1>};
+  if (fix) k = four ? ObsKernels{k_observe_env<4, true>, k_observe_env<4, true, false>, k_observe_env_ids<4, true>}
+                    : ObsKernels{k_observe_env<1, true>, nullptr, k_observe_env_ids<1, true>};
   const SeatKernels* seats = (fix && four) ? marl_fix_seats(h->d) : nullptr;
-  if (seats && seats->observe) ke = state_done ? seats->observe_after_state : seats->observe;
-  return {ke, dim3(envs), dim3(WAVE * p.nw), p.dyn, p.G, false};
-}
-
-// observe_launch(h, n, false) for the n envs of an id list (pgd_reset): the same choice of kernel, geometry and LDS, unit k = env ids[k]
-struct ObsIdsLaunch { ObsIdsFn fn; dim3 grid, block; size_t lds; int arg; bool forget_marks; };
-static ObsIdsLaunch observe_ids_launch(const pgd_engine* h, int n) {
-  const ObsLaunch o = observe_launch(h, n, false);
-  const ObsEnvPlan p = observe_env_plan(h);
-  ObsIdsFn kern;
-  if (!p.use) {
-    const bool oth = others_state_rows(h);
-    kern = h->d.cfg.num_lasers > 128 ? (oth ? k_observe_ids<256, true> : k_observe_ids<256, false>)
-                                     : (oth ? k_observe_ids<64, true> : k_observe_ids<64, false>);
-  } else {
-    const bool four = p.nw == 4, fix = marl_fix_ok(h);
-    kern = four ? k_observe_env_ids<4> : k_observe_env_ids<1>;
-    if (fix) kern = four ? k_observe_env_ids<4, true> : k_observe_env_ids<1, true>;
-    const SeatKernels* seats = (fix && four) ? marl_fix_seats(h->d) : nullptr;
-    if (seats && seats->observe_ids) kern = seats->observe_ids;
-  }
-  return {kern, o.grid, o.block, o.lds, o.arg, o.forget_marks};
+  if (seats && seats->obs.range) k = seats->obs;
+  return {k, state_done && k.after_state != nullptr, dim3(envs), dim3(WAVE * p.nw), p.dyn, p.G, false};
 }
 
 // What one step launches, decided once per step (pgd_set_groups, the uploads and pgd_set_step_module change what it reads): the env group,
-// the step kernel (jit_fn: the handle's run-time module in its place) and the observation launch after it (obs.fn null: none).
+// the step kernel (jit_fn: the handle's run-time module in its place) and the observation launch after it (obs.k.range null: none).
 struct StepPlan { EnvGroup g; StepKernel kernel; hipFunction_t jit_fn; bool fuse, state_in_step; ObsLaunch obs; };
 static int plan_step(const pgd_engine* h, bool want_obs, int group, StepPlan& p) {
   const PgdDev& d = h->d;
@@ -310,9 +298,13 @@ static int obs_rows_forget(pgd_engine* h, hipStream_t stream) {
   return PGD_OK;
 }
 
-static int launch_observe(pgd_engine* h, const ObsLaunch& o, const PgdDev& dv, float* d_obs, const uint32_t* d_flags, hipStream_t stream) {
+// env_ids (device): unit k of the launch observes env env_ids[k], without step flags; null: the envs of dv's range
+static int launch_observe(pgd_engine* h, const ObsLaunch& o, const PgdDev& dv, float* d_obs, const uint32_t* d_flags, const int32_t* env_ids,
+                          hipStream_t stream) {
   if (o.forget_marks) { int rc = obs_rows_forget(h, stream); if (rc) return rc; }
-  hipLaunchKernelGGL(o.fn, o.grid, o.block, o.lds, stream, dv, d_obs, d_flags, o.arg);
+  const ObsFn range = o.state_done ? o.k.after_state : o.k.range;
+  if (env_ids) hipLaunchKernelGGL(o.k.ids, o.grid, o.block, o.lds, stream, dv, d_obs, env_ids, o.arg);
+  else hipLaunchKernelGGL(range, o.grid, o.block, o.lds, stream, dv, d_obs, d_flags, o.arg);
   HIPCHK(hipGetLastError());
   return PGD_OK;
 }
@@ -720,14 +712,8 @@ int pgd_reset(pgd_handle h, const int32_t* env_ids, const int32_t* scen_ids, int
   HIPCHK(hipGetLastError());
   { int rc = render_forget(h, d_env, n); if (rc) return rc; }  // rendered trails and deads end with the episode
   { int rc = step_info_forget(h, d_env, n); if (rc) return rc; }  // and so do the running cost and the energy base of the step info
-  if (d_obs && d_env) {  // an id list: the rows of the listed envs and no others (the rest of d_obs keeps its bytes)
-    const ObsIdsLaunch o = observe_ids_launch(h, n);
-    if (o.forget_marks) { int rc = obs_rows_forget(h, h->stream); if (rc) return rc; }
-    hipLaunchKernelGGL(o.fn, o.grid, o.block, o.lds, h->stream, h->d, d_obs, d_env, o.arg);
-    HIPCHK(hipGetLastError());
-    return PGD_OK;
-  }
-  if (d_obs) return launch_observe(h, observe_launch(h, h->d.N, false), h->d, d_obs, nullptr, h->stream);
+  // an id list: the rows of the listed envs and no others (the rest of d_obs keeps its bytes)
+  if (d_obs) return launch_observe(h, observe_launch(h, d_env ? n : h->d.N, false), h->d, d_obs, nullptr, d_env, h->stream);
   return PGD_OK;
 }
 
@@ -776,8 +762,8 @@ static int step_impl(pgd_handle h, const float* d_actions, float* d_obs, float* 
   HIPCHK(hipGetLastError());
   if (prof || g_close) HIPCHK(hipEventRecord(pe[1], h->stream));
   if (g_close) h->prof_n += 1;
-  if (p.obs.fn) {
-    int rc = launch_observe(h, p.obs, dv, d_obs, is_marl(h) ? d_flags : (const uint32_t*)nullptr, p.g.stream);
+  if (p.obs.k.range) {
+    int rc = launch_observe(h, p.obs, dv, d_obs, is_marl(h) ? d_flags : (const uint32_t*)nullptr, nullptr, p.g.stream);
     if (rc) return rc;
   }
   if (h->sinfo) { int rc = step_info_launch(h, p.g, d_done, d_flags, d_obs); if (rc) return rc; }
@@ -1017,7 +1003,7 @@ int pgd_observe(pgd_handle h, float* d_obs) {
   int blocks = (h->d.N + h->d.epw - 1) / h->d.epw;
   hipLaunchKernelGGL(k_refresh, dim3(blocks), dim3(WAVE), 0, h->stream, h->d);
   HIPCHK(hipGetLastError());
-  return launch_observe(h, observe_launch(h, h->d.N, false), h->d, d_obs, nullptr, h->stream);
+  return launch_observe(h, observe_launch(h, h->d.N, false), h->d, d_obs, nullptr, nullptr, h->stream);
 }
 
 int pgd_state_dims(pgd_handle h, int* nf, int* ni, int* nei) {

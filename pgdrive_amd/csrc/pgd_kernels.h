@@ -140,101 +140,27 @@ __global__ __launch_bounds__(WAVE) void k_refresh(PgdDev d) {
 // BLOCK threads produce one row.  BLOCK = 64: the block holds OBS_RPB independent rows, one per wave (a block per 64-lane
 // row made the launch dispatch-bound: 32768 workgroups that each live ~5 us); BLOCK = 256: one row per block.
 #define OBS_RPB 1
-// The row of (env e, agent a) by the BLOCK threads `tid` of one row: k_observe's body, shared with k_step_info (pgd_step_info.h: the
-// first row of an episode it has just started).  `L`: the row's compaction scratch in LDS.
+#define OBS_BOUNDS(BLOCK) __launch_bounds__((BLOCK) == WAVE ? WAVE * OBS_RPB : (BLOCK))
+// The one body of k_observe and k_observe_ids.  Row `rowi` of the launch belongs to unit u = rowi / A: ENV is the env of unit u, FLAGS the
+// step flags.  A macro, not a function: a function between a kernel and observe_row is optimised on its own before it is inlined, and
+// every kernel then compiles to other instructions (compared per symbol, tools/asm_by_kernel.py).
+#define OBSERVE_ROWS(FLAGS, ENV)                                                                                      \
+  constexpr bool WROW = BLOCK == WAVE;                                                                                \
+  __shared__ ObsLds Ls[WROW ? OBS_RPB : 1];                                                                           \
+  const int rowi = WROW ? (int)blockIdx.x * OBS_RPB + (int)(threadIdx.x / WAVE) : (int)blockIdx.x;                    \
+  if (rowi >= n_rows) return;                                                                                         \
+  const int u = rowi / d.A;                                                                                           \
+  observe_row<BLOCK, OTH>(d, obs, FLAGS, ENV, rowi % d.A, WROW ? (int)(threadIdx.x % WAVE) : (int)threadIdx.x, Ls[WROW ? threadIdx.x / WAVE : 0])
+// unit u = env u of the launch's env range, with the step's flags
 template <int BLOCK, bool OTH>
-DEV void observe_row(const PgdDev& d, float* __restrict__ obs, const uint32_t* __restrict__ flags, int e, int a, int tid, ObsLds& L,
-                     int scen_known = -1) {  // (scen_known >= 0: the env's scenario, where the caller has just written EI_SCEN itself)
-  constexpr bool WROW = BLOCK == WAVE;
-  const int V = d.V, A = d.A, D = d.D;
-  const RecPiece* recs = rec_block(d.rec, (size_t)e, V);  // the env's vehicle records
-  float* row = obs + (size_t)e * d.ostride + (size_t)a * D;
-  PHASE_INIT();
-  // A row lives a few microseconds and almost all of that is load latency, so the reads go out in three batches instead of
-  // one dependent chain.  Batch 1: every address that follows from the block index -- the observer's record, the first half
-  // of body `tid`'s record (pose, speed, status, spawn index, agent id), the step flags, the env's scenario and step count.
-  const int ob = tid < V ? tid : 0;
-  Veh me;
-  load_rec(recs, V, a, me);
-  uint4 bw[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) bw[k] = recs[k * V + ob].q;
-  const uint32_t fa = flags ? flags[(size_t)e * A + a] : 0u, fo = flags ? flags[(size_t)e * A + (tid < A ? tid : 0)] : 0u;
-  const int scen = scen_known >= 0 ? scen_known : d.ei[(size_t)(e) * PGD_NEI + EI_SCEN];
-  const uint32_t tick = (uint32_t)d.ei[(size_t)(e) * PGD_NEI + EI_STEPS_TOTAL];
-  Veh body;  // only the first 64 bytes are filled
-#pragma unroll
-  for (int k = 0; k < 4; ++k) reinterpret_cast<uint4*>(&body)[k] = bw[k];
-  // which slots get a row: after a multi-agent step the ones that reported or were (re)spawned, else the active ones
-  bool want = me.status == ST_ACTIVE;
-  if (flags) want = (fa & PGD_F_RESET) ? want : (fa & (PGD_F_REPORT | PGD_F_NEW)) != 0;  // after a reset only the new episode counts
-  if (!want) {
-    for (int k = tid; k < D; k += BLOCK) row[k] = 0.0f;
-    return;
-  }
-  // batch 2: what the scenario and the spawn indices lead to -- map header, the observer's and the body's static parameters
-  const pgd_spawn* spb = d.spawns + (size_t)scen * d.sstride;
-  const pgd_spawn& msp = spb[me.spawn];
-  const pgd_spawn& so = spb[body.spawn];
-  const float so_len = so.length, so_wid = so.width;
-  const int so_kind = so.kind;
-  MapView mv = map_view_of(d, d.env_map + e);  // the env's own copy of the header: one dependent level less than via `scen`
-  AgentView ag;
-  ag.x = me.x; ag.y = me.y; ag.th = me.th;
-  ag.hx = me.hx; ag.hy = me.hy;
-  ag.dl = me.dl; ag.dr = me.dr; ag.v = me.v; ag.steer = me.steer;
-  ag.a0s = me.a0s; ag.a0t = me.a0t; ag.lhx = me.lasthx; ag.lhy = me.lasthy;
-  ag.cur_first = me.cur_first; ag.cur_n = me.cur_n; ag.next_first = me.next_first;
-  ag.blk = me.blk; ag.toll_time = me.php;
-  ag.env = e; ag.slot = a; ag.tick = tick;
-  // batch 3 (lane records of the route) belongs to the state block, which needs nothing from the other bodies: it runs first
-  // and its reads overlap the spawn reads the compaction waits for
-  state_block<false>(d, mv, msp, ag, row, tid, BLOCK);
-  PHASE_MARK(22);  // obs: state + navi block
-  if (tid < WAVE) {  // wave 0: broad phase r = lidar distance (lidar.py:109-124), compacted into LDS
-    bool present = false, is_vehicle = true;
-    float x = 0, y = 0, ux = 1, uy = 0, hl = 0, hw = 0, spd = 0;
-    if (tid < V && d.cfg.num_lasers > 0) {
-      const int st = body.status;
-      present = st == ST_PENDING || st == ST_ACTIVE || st == ST_DYING;
-      bool still = st == ST_DYING;  // a finished agent is a static body (zero velocity)
-      if (flags && tid < A) {
-        // multi-agent step: rows of agents that drove this step show the world before the finishes / respawns
-        // (base_env.py:303-344 runs before multi_agent_pgdrive.py:128-141); an agent spawned this step sees the world at
-        // its spawn time, i.e. the earlier spawns of the step only
-        if (fa & PGD_F_RESET) {
-        } else if (fa & PGD_F_NEW) {
-          present = present && (!(fo & PGD_F_NEW) || body.agent_id < me.agent_id);
-        } else {
-          present = (fo & PGD_F_REPORT) || (present && !(fo & PGD_F_NEW));
-          still = still && !(fo & PGD_F_REPORT);
-        }
-      }
-      x = body.x; y = body.y;
-      ux = body.hx; uy = body.hy;
-      hl = 0.5f * so_len; hw = so_kind == PGD_OBJ_CYLINDER ? -1.0f : 0.5f * so_wid;
-      is_vehicle = so_kind == PGD_OBJ_VEHICLE;
-      spd = still ? 0.0f : speed_kmh(body.v);
-    }
-    obs_compact<true>(L, tid, a, present, is_vehicle, x, y, ux, uy, hl, hw, spd, ag.x, ag.y, d.cfg.lidar_dist, ag.hx, ag.hy,
-                      d.cfg.num_lasers);
-  }
-  row_sync<WROW>();
-  PHASE_MARK(28);  // k_observe: compaction
-  if (OTH) observe_agent<true, false, true, false, WROW>(d, mv, msp, ag, L, row, tid, BLOCK, recs, spb);
-  else observe_agent<true, false, false, false, WROW>(d, mv, msp, ag, L, row, tid, BLOCK);
-  PHASE_END_AT(29);
+__global__ OBS_BOUNDS(BLOCK) void k_observe(PgdDev d, float* __restrict__ obs, const uint32_t* __restrict__ flags, int n_rows) {
+  OBSERVE_ROWS(flags, u + d.unit_off * d.epw);
 }
-
+// unit u = env env_ids[u] and nothing else (pgd_reset with env ids): the rows of every other env keep their bytes, and so do their
+// zero-row marks.  A kernel of its own, so that the one a step launches stays as it is; no step flags (the state right after a reset).
 template <int BLOCK, bool OTH>
-__global__ __launch_bounds__(BLOCK == WAVE ? WAVE * OBS_RPB : BLOCK) void k_observe(PgdDev d, float* __restrict__ obs,
-                                                                                 const uint32_t* __restrict__ flags, int n_rows) {
-  constexpr bool WROW = BLOCK == WAVE;
-  __shared__ ObsLds Ls[WROW ? OBS_RPB : 1];
-  const int rowi = WROW ? (int)blockIdx.x * OBS_RPB + (int)(threadIdx.x / WAVE) : (int)blockIdx.x;
-  if (rowi >= n_rows) return;
-  observe_row<BLOCK, OTH>(d, obs, flags, rowi / d.A + d.unit_off * d.epw, rowi % d.A, WROW ? (int)(threadIdx.x % WAVE) : (int)threadIdx.x,
-                          Ls[WROW ? threadIdx.x / WAVE : 0]);
+__global__ OBS_BOUNDS(BLOCK) void k_observe_ids(PgdDev d, float* __restrict__ obs, const int32_t* __restrict__ env_ids, int n_rows) {
+  OBSERVE_ROWS(nullptr, env_ids[u]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -252,44 +178,29 @@ __global__ __launch_bounds__(BLOCK == WAVE ? WAVE * OBS_RPB : BLOCK) void k_obse
 // are at least four passes (A >= 4 * (WAVE / V)), else 1.
 // FIX: the engine runs the default multi-agent configuration (same constants as k_step's instantiation for it, PGD_FIXM_FIELDS)
 // STATE = false: k_step has written the state blocks of the rows that are due (PgdDev::state_rows): the pairwise part only
-template <int NW, bool FIX = false, bool STATE = true, int SEATS = 0>  // SEATS: the seat count folded as well (PGD_FIXM_SEAT_FIELDS)
 // (the library is built at -O2 since the end of round 5; this kernel keeps the size-optimised code it had -- 30.0 against 30.7 us for the
 // 40 seats -- and its specialised instantiations seven waves per SIMD: 72 registers, what -Os gave them unasked; at -O2 they took 82 and
 // the observation 32.6 us)
 #ifndef PGD_KOE_ATTR
 #define PGD_KOE_ATTR __attribute__((minsize))
 #endif
-__global__ PGD_KOE_ATTR __launch_bounds__(WAVE * NW, (FIX ? 7 : 1)) void k_observe_env(PgdDev d, float* __restrict__ obs, const uint32_t* __restrict__ flags, int G) {
-  if (FIX) write_fixed_config<true, true, false, (SEATS ? SEATS : 1)>(d);
-  extern __shared__ unsigned s_minb_dyn[];
-  constexpr int CAP = SEATS ? (SEATS / 1000 + 15) / 16 * 16 : WAVE;
-  __shared__ ObsEnvLds<NW, CAP> M;
-  PHASE_INIT();  // (profile builds: the marks of observe_env_body count from here)
-  observe_env_body<NW, !FIX, false, !FIX, STATE, CAP>(d, (int)blockIdx.x + d.unit_off * d.epw, obs, flags, M, s_minb_dyn, G);  // (the fixed-config kernel: no traffic objects)
+#define OBS_ENV_BOUNDS(NW, FIX) PGD_KOE_ATTR __launch_bounds__(WAVE * (NW), ((FIX) ? 7 : 1))
+// The one body of k_observe_env and k_observe_env_ids (a macro for the reason given at OBSERVE_ROWS): block u of the launch observes env ENV
+#define OBSERVE_ENV(STATE, FLAGS, ENV)                                                                                \
+  if (FIX) write_fixed_config<true, true, false, (SEATS ? SEATS : 1)>(d);                                             \
+  extern __shared__ unsigned s_minb_dyn[];                                                                            \
+  constexpr int CAP = SEATS ? (SEATS / 1000 + 15) / 16 * 16 : WAVE;                                                   \
+  __shared__ ObsEnvLds<NW, CAP> M;                                                                                    \
+  PHASE_INIT(); /* (profile builds: the marks of observe_env_body count from here) */                                 \
+  const unsigned u = blockIdx.x;                                                                                      \
+  observe_env_body<NW, !FIX, false, !FIX, STATE, CAP>(d, ENV, obs, FLAGS, M, s_minb_dyn, G) /* (the fixed-config kernel: no traffic objects) */
+template <int NW, bool FIX = false, bool STATE = true, int SEATS = 0>  // SEATS: the seat count folded as well (PGD_FIXM_SEAT_FIELDS)
+__global__ OBS_ENV_BOUNDS(NW, FIX) void k_observe_env(PgdDev d, float* __restrict__ obs, const uint32_t* __restrict__ flags, int G) {
+  OBSERVE_ENV(STATE, flags, (int)u + d.unit_off * d.epw);
 }
-
-// The two kernels above for an id list (pgd_reset with env ids): unit k of the launch observes env env_ids[k] and nothing else -- the
-// rows of every other env keep their bytes, and so do their zero-row marks.  Kernels of their own, so that the ones a step launches stay
-// as they are; no step flags (the state right after a reset).
-template <int BLOCK, bool OTH>
-__global__ __launch_bounds__(BLOCK == WAVE ? WAVE * OBS_RPB : BLOCK) void k_observe_ids(PgdDev d, float* __restrict__ obs,
-                                                                                     const int32_t* __restrict__ env_ids, int n_rows) {
-  constexpr bool WROW = BLOCK == WAVE;
-  __shared__ ObsLds Ls[WROW ? OBS_RPB : 1];
-  const int rowi = WROW ? (int)blockIdx.x * OBS_RPB + (int)(threadIdx.x / WAVE) : (int)blockIdx.x;
-  if (rowi >= n_rows) return;
-  observe_row<BLOCK, OTH>(d, obs, nullptr, env_ids[rowi / d.A], rowi % d.A, WROW ? (int)(threadIdx.x % WAVE) : (int)threadIdx.x,
-                          Ls[WROW ? threadIdx.x / WAVE : 0]);
-}
-
-template <int NW, bool FIX = false, int SEATS = 0>
-__global__ PGD_KOE_ATTR __launch_bounds__(WAVE * NW, (FIX ? 7 : 1)) void k_observe_env_ids(PgdDev d, float* __restrict__ obs, const int32_t* __restrict__ env_ids, int G) {
-  if (FIX) write_fixed_config<true, true, false, (SEATS ? SEATS : 1)>(d);
-  extern __shared__ unsigned s_minb_dyn[];
-  constexpr int CAP = SEATS ? (SEATS / 1000 + 15) / 16 * 16 : WAVE;
-  __shared__ ObsEnvLds<NW, CAP> M;
-  PHASE_INIT();
-  observe_env_body<NW, !FIX, false, !FIX, true, CAP>(d, env_ids[blockIdx.x], obs, nullptr, M, s_minb_dyn, G);
+template <int NW, bool FIX = false, int SEATS = 0>  // an id list: see k_observe_ids
+__global__ OBS_ENV_BOUNDS(NW, FIX) void k_observe_env_ids(PgdDev d, float* __restrict__ obs, const int32_t* __restrict__ env_ids, int G) {
+  OBSERVE_ENV(true, nullptr, env_ids[u]);
 }
 
 // scripted lane-keeping policy (pgd_lane_keep_actions): one thread per env

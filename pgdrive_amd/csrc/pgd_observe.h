@@ -77,6 +77,22 @@ struct AgentView {  // what the observation needs from the observing vehicle
   int env, slot;                     // for the lidar noise stream
   uint32_t tick;                     // steps since pgd_reset
 };
+// the view of vehicle `r`, slot `slot` of env `env`, as the observer of its own row
+DEV void agent_view(AgentView& ag, const Veh& r, int env, int slot, uint32_t tick) {
+  ag.x = r.x; ag.y = r.y; ag.th = r.th; ag.hx = r.hx; ag.hy = r.hy; ag.dl = r.dl; ag.dr = r.dr; ag.v = r.v;
+  ag.steer = r.steer; ag.a0s = r.a0s; ag.a0t = r.a0t; ag.lhx = r.lasthx; ag.lhy = r.lasthy;
+  ag.cur_first = r.cur_first; ag.cur_n = r.cur_n; ag.next_first = r.next_first;
+  ag.blk = r.blk; ag.toll_time = r.php;
+  ag.env = env; ag.slot = slot; ag.tick = tick;
+}
+
+// which slots get a row: after a multi-agent step (have_flags; fl = the slot's step flags) the ones that reported or were (re)spawned
+// -- after a reset only the new episode counts --, else the active ones
+DEV bool row_due(int status, bool have_flags, uint32_t fl) {
+  bool want = status == ST_ACTIVE;
+  if (have_flags) want = (fl & PGD_F_RESET) ? want : (fl & (PGD_F_REPORT | PGD_F_NEW)) != 0;
+  return want;
+}
 
 // one wave compacts the candidates: lane `o` brings vehicle o of the env (present = in the physics world)
 // `near_out` (optional): set when body o can reach the observing agent during the NEXT step -- centre distance within the two
@@ -322,21 +338,11 @@ DEV AgentView view_of_slot(const PgdDev& d, const MapView& mv, const RecPiece* r
   Veh rc;
   load_rec(recs, d.V, o, rc);
   AgentView ag;
-  ag.x = rc.x; ag.y = rc.y; ag.th = rc.th;
-  ag.hx = rc.hx; ag.hy = rc.hy;
-  ag.dl = rc.dl; ag.dr = rc.dr;
-  ag.v = spd_kmh == 0.0f ? 0.0f : rc.v;  // the snapshot says 0: an agent that finished in an EARLIER step (static body)
-  ag.steer = rc.steer; ag.a0s = rc.a0s; ag.a0t = rc.a0t; ag.lhx = rc.lasthx; ag.lhy = rc.lasthy;
-  ag.cur_first = rc.cur_first; ag.cur_n = rc.cur_n; ag.next_first = rc.next_first;
-  ag.blk = rc.blk; ag.toll_time = rc.php;
-  ag.env = env; ag.slot = o; ag.tick = tick;
+  agent_view(ag, rc, env, o, tick);
+  if (spd_kmh == 0.0f) ag.v = 0.0f;  // the snapshot says 0: an agent that finished in an EARLIER step (static body)
   return ag;
 }
 
-// writes the D floats of one agent's row with `nt` cooperating threads (tid in [0, nt))
-// STD: the reference's default row layout (no detector fans, no random_agent_model, no toll floats, no lidar noise) as a
-// compile-time fact: every column offset is a constant and the optional blocks vanish from the benchmark kernel.
-// OTH: PGD_MA_OTHERS_STATE (stand-alone k_observe only: `recs` / `spb` = the env's records and spawn table)
 // gaussian noise / dropout of one lidar value (state_obs.py:172-182), from the counter RNG keyed by (env, agent slot, beam, step)
 DEV float lidar_noise(const PgdDev& d, int env, int slot, uint32_t tick, int i, float best) {
   if (!(d.cfg.lidar_gaussian_noise > 0.0f || d.cfg.lidar_dropout_prob > 0.0f)) return best;
@@ -363,6 +369,10 @@ DEV void row_sync() {
   } else __syncthreads();
 }
 
+// writes the D floats of one agent's row with `nt` cooperating threads (tid in [0, nt))
+// STD: the reference's default row layout (no detector fans, no random_agent_model, no toll floats, no lidar noise) as a
+// compile-time fact: every column offset is a constant and the optional blocks vanish from the benchmark kernel.
+// OTH: PGD_MA_OTHERS_STATE (stand-alone k_observe only: `recs` / `spb` = the env's records and spawn table)
 // STATE = false: the caller has written the state block (and the toll floats' inputs are unchanged) already
 // WAVE_ROW: see row_sync
 template <bool OBJ, bool STD = false, bool OTH = false, bool STATE = true, bool WAVE_ROW = false, class MV>
@@ -555,21 +565,90 @@ DEV void observe_agent(const PgdDev& d, const MV& mv, const pgd_spawn& sp, const
   PHASE_MARK(24);  // obs: lidar
 }
 
+// The row of (env e, agent a) by the BLOCK threads `tid` of one row: the body of k_observe (pgd_kernels.h), shared with k_step_info
+// (pgd_step_info.h: the first row of an episode it has just started).  `L`: the row's compaction scratch in LDS.
+// OTH: PGD_MA_OTHERS_STATE rows.
+template <int BLOCK, bool OTH>
+DEV void observe_row(const PgdDev& d, float* __restrict__ obs, const uint32_t* __restrict__ flags, int e, int a, int tid, ObsLds& L,
+                     int scen_known = -1) {  // (scen_known >= 0: the env's scenario, where the caller has just written EI_SCEN itself)
+  constexpr bool WROW = BLOCK == WAVE;
+  const int V = d.V, A = d.A, D = d.D;
+  const RecPiece* recs = rec_block(d.rec, (size_t)e, V);  // the env's vehicle records
+  float* row = obs + (size_t)e * d.ostride + (size_t)a * D;
+  PHASE_INIT();
+  // A row lives a few microseconds and almost all of that is load latency, so the reads go out in three batches instead of
+  // one dependent chain.  Batch 1: every address that follows from the block index -- the observer's record, the first half
+  // of body `tid`'s record (pose, speed, status, spawn index, agent id), the step flags, the env's scenario and step count.
+  const int ob = tid < V ? tid : 0;
+  Veh me;
+  load_rec(recs, V, a, me);
+  uint4 bw[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) bw[k] = recs[k * V + ob].q;
+  const uint32_t fa = flags ? flags[(size_t)e * A + a] : 0u, fo = flags ? flags[(size_t)e * A + (tid < A ? tid : 0)] : 0u;
+  const int scen = scen_known >= 0 ? scen_known : d.ei[(size_t)(e) * PGD_NEI + EI_SCEN];
+  const uint32_t tick = (uint32_t)d.ei[(size_t)(e) * PGD_NEI + EI_STEPS_TOTAL];
+  Veh body;  // only the first 64 bytes are filled
+#pragma unroll
+  for (int k = 0; k < 4; ++k) reinterpret_cast<uint4*>(&body)[k] = bw[k];
+  bool want = me.status == ST_ACTIVE;  // (row_due, written out: through the helper the four k_observe compile to other instructions)
+  if (flags) want = (fa & PGD_F_RESET) ? want : (fa & (PGD_F_REPORT | PGD_F_NEW)) != 0;
+  if (!want) {
+    for (int k = tid; k < D; k += BLOCK) row[k] = 0.0f;
+    return;
+  }
+  // batch 2: what the scenario and the spawn indices lead to -- map header, the observer's and the body's static parameters
+  const pgd_spawn* spb = d.spawns + (size_t)scen * d.sstride;
+  const pgd_spawn& msp = spb[me.spawn];
+  const pgd_spawn& so = spb[body.spawn];
+  const float so_len = so.length, so_wid = so.width;
+  const int so_kind = so.kind;
+  MapView mv = map_view_of(d, d.env_map + e);  // the env's own copy of the header: one dependent level less than via `scen`
+  AgentView ag;
+  agent_view(ag, me, e, a, tick);
+  // batch 3 (lane records of the route) belongs to the state block, which needs nothing from the other bodies: it runs first
+  // and its reads overlap the spawn reads the compaction waits for
+  state_block<false>(d, mv, msp, ag, row, tid, BLOCK);
+  PHASE_MARK(22);  // obs: state + navi block
+  if (tid < WAVE) {  // wave 0: broad phase r = lidar distance (lidar.py:109-124), compacted into LDS
+    bool present = false, is_vehicle = true;
+    float x = 0, y = 0, ux = 1, uy = 0, hl = 0, hw = 0, spd = 0;
+    if (tid < V && d.cfg.num_lasers > 0) {
+      const int st = body.status;
+      present = st == ST_PENDING || st == ST_ACTIVE || st == ST_DYING;
+      bool still = st == ST_DYING;  // a finished agent is a static body (zero velocity)
+      if (flags && tid < A) {
+        // multi-agent step: rows of agents that drove this step show the world before the finishes / respawns
+        // (base_env.py:303-344 runs before multi_agent_pgdrive.py:128-141); an agent spawned this step sees the world at
+        // its spawn time, i.e. the earlier spawns of the step only
+        if (fa & PGD_F_RESET) {
+        } else if (fa & PGD_F_NEW) {
+          present = present && (!(fo & PGD_F_NEW) || body.agent_id < me.agent_id);
+        } else {
+          present = (fo & PGD_F_REPORT) || (present && !(fo & PGD_F_NEW));
+          still = still && !(fo & PGD_F_REPORT);
+        }
+      }
+      x = body.x; y = body.y;
+      ux = body.hx; uy = body.hy;
+      hl = 0.5f * so_len; hw = so_kind == PGD_OBJ_CYLINDER ? -1.0f : 0.5f * so_wid;
+      is_vehicle = so_kind == PGD_OBJ_VEHICLE;
+      spd = still ? 0.0f : speed_kmh(body.v);
+    }
+    obs_compact<true>(L, tid, a, present, is_vehicle, x, y, ux, uy, hl, hw, spd, ag.x, ag.y, d.cfg.lidar_dist, ag.hx, ag.hy,
+                      d.cfg.num_lasers);
+  }
+  row_sync<WROW>();
+  PHASE_MARK(28);  // k_observe: compaction
+  if (OTH) observe_agent<true, false, true, false, WROW>(d, mv, msp, ag, L, row, tid, BLOCK, recs, spb);
+  else observe_agent<true, false, false, false, WROW>(d, mv, msp, ag, L, row, tid, BLOCK);
+  PHASE_END_AT(29);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
-// observe_env_body (kernel k_observe_env, and the tail of the multi-agent k_step): the rows of ALL agents of an env by one wave (multi-agent engines; same results as k_observe, row by row).
-// A block per row spends its life waiting for a handful of loads, 8 x A of them per env.  Here the env's records are read
-// once, and the work is laid out by what there is to do instead of by row:
-//   state blocks   WAVE / A lanes per agent, every agent at once (state_block with few threads);
-//   pairs          lane = (observer, body): broad phase, beam window, neighbour rank -- WAVE / V observers per pass;
-//   lidar          the (observer, body, beam-inside-the-window) incidences of the pass, flattened by a prefix sum over the
-//                  pairs' window sizes and dealt out to the lanes 64 at a time: a body is tested against the few beams that
-//                  can reach it and nothing else; the nearest hit per beam is an unsigned min in LDS (fractions are >= 0).
+// observe_env_body: the rows of ALL agents of an env by the waves of one block -- the body of k_observe_env (pgd_kernels.h: how the
+// work is laid out, NW) and the tail of the multi-agent k_step
 // ---------------------------------------------------------------------------------------------------------------------
-// NW waves per env: the state blocks get NW * WAVE / A lanes per agent and the passes of the pair phase are dealt out to the waves
-// (wave w takes passes w, w + NW, ...; each wave has its own scratch and synchronises with itself only).  NW = 4 when there
-// are at least four passes (A >= 4 * (WAVE / V)), else 1.
-// NW waves per env: the state blocks get NW * WAVE / A lanes per agent and the passes of the pair phase are dealt out to the waves
-// (wave w takes passes w, w + NW, ...; each wave has its own scratch and synchronises with itself only).
 // LDS words one wave needs for rounds of g observers
 // per observer of a round: the per-beam minima, the candidate pairs (two to a word), and -- engines that observe neighbour rows --
 // centre distance and speed of every pair
@@ -661,13 +740,8 @@ DEV void observe_env_body(const PgdDev& d, int e, float* __restrict__ obs, const
   }
   const pgd_spawn* spb = d.spawns + (size_t)scen * d.sstride;
   const pgd_spawn& msp = FUSED ? *in_wave->sp : spb[STATE ? me.spawn : 0];
-  // which slots get a row: after a multi-agent step the ones that reported or were (re)spawned, else the active ones
   bool want = false;  // (STATE = false: the rows' state blocks are there already; `aWant` comes from the bodies' own lanes below)
-  if (STATE) {
-    want = me.status == ST_ACTIVE;
-    if (flags) want = (f_me & PGD_F_RESET) ? want : (f_me & (PGD_F_REPORT | PGD_F_NEW)) != 0;
-    want = want && s_on;
-  }
+  if (STATE) want = row_due(me.status, flags != nullptr, f_me) && s_on;
   // ---- publish the bodies and the observers
   if (FUSED) {  // V == A: the first lane of every agent publishes its own vehicle
     if (s_on && st == 0) {
@@ -697,15 +771,13 @@ DEV void observe_env_body(const PgdDev& d, int e, float* __restrict__ obs, const
   if (STATE) {
     if (s_on && st == 0) { aMS[sa] = msp.max_speed; aWant[sa] = want ? 1 : 0; }
   } else if (tid < A) {  // the same rule from the body's own status and flags (its lane holds both)
-    bool w = body.status == ST_ACTIVE;
-    if (flags) w = (f_body & PGD_F_RESET) ? w : (f_body & (PGD_F_REPORT | PGD_F_NEW)) != 0;
-    aWant[tid] = w ? 1 : 0;
+    aWant[tid] = row_due(body.status, flags != nullptr, f_body) ? 1 : 0;
     aMS[tid] = 0.0f;  // (only read for neighbour rows, which the STATE = false kernels do not write)
   }
   // ---- state blocks: every agent at once, LPA lanes each
   float* row = obs + (size_t)e * d.ostride + (size_t)(s_on ? sa : 0) * D;
   if (want) {
-    AgentView ag;
+    AgentView ag;  // (agent_view's field list, written out: through the helper the five k_step that fuse this body compile to three more instructions)
     ag.x = me.x; ag.y = me.y; ag.th = me.th;
     ag.hx = me.hx; ag.hy = me.hy;
     ag.dl = me.dl; ag.dr = me.dr; ag.v = me.v; ag.steer = me.steer;
@@ -806,9 +878,7 @@ DEV void observe_env_body(const PgdDev& d, int e, float* __restrict__ obs, const
         bool present = stt == ST_PENDING || stt == ST_ACTIVE || stt == ST_DYING;
         bool still = stt == ST_DYING;  // a finished agent is a static body (zero velocity)
         if (flags && o < A) {
-          // multi-agent step: rows of agents that drove this step show the world before the finishes / respawns
-          // (base_env.py:303-344 runs before multi_agent_pgdrive.py:128-141); an agent spawned this step sees the world at
-          // its spawn time, i.e. the earlier spawns of the step only
+          // multi-agent step: what the row shows of another agent -- the rule of observe_row, here from the tables in LDS
           const uint32_t fa = bFL[a], fo = bFL[o];
           if (fa & PGD_F_RESET) {
           } else if (fa & PGD_F_NEW) {

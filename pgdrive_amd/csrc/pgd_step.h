@@ -965,11 +965,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
       S.present[slot] = present ? 1 : 0;
       if (s < A) {
         AgentView& ag = s_ag[s];
-        ag.x = r.x; ag.y = r.y; ag.th = r.th; ag.hx = r.hx; ag.hy = r.hy; ag.dl = r.dl; ag.dr = r.dr; ag.v = r.v;
-        ag.steer = r.steer; ag.a0s = r.a0s; ag.a0t = r.a0t; ag.lhx = r.lasthx; ag.lhy = r.lasthy;
-        ag.cur_first = r.cur_first; ag.cur_n = r.cur_n; ag.next_first = r.next_first;
-        ag.blk = r.blk; ag.toll_time = r.php;
-        ag.env = e; ag.slot = s; ag.tick = steps_total;
+        agent_view(ag, r, e, s, steps_total);
       }
     }
     step_sync();
@@ -1014,11 +1010,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
     const bool due = resetting ? r.status == ST_ACTIVE : (my_fl & (PGD_F_REPORT | PGD_F_NEW)) != 0u;
     if (due) {
       AgentView ag;
-      ag.x = r.x; ag.y = r.y; ag.th = r.th; ag.hx = r.hx; ag.hy = r.hy; ag.dl = r.dl; ag.dr = r.dr; ag.v = r.v;
-      ag.steer = r.steer; ag.a0s = r.a0s; ag.a0t = r.a0t; ag.lhx = r.lasthx; ag.lhy = r.lasthy;
-      ag.cur_first = r.cur_first; ag.cur_n = r.cur_n; ag.next_first = r.next_first;
-      ag.blk = r.blk; ag.toll_time = r.php;
-      ag.env = e; ag.slot = s; ag.tick = steps_total;
+      agent_view(ag, r, e, s, steps_total);
       state_block_one(d, mv, SPV, ag, d.state_rows + (size_t)e * d.ostride + (size_t)s * d.D);  // (state_in_step_ok: the plain row layout)
     }
   }
@@ -1052,11 +1044,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
       S.present[slot] = present ? 1 : 0;
       if (s == 0) {
         AgentView& ag = s_ag[el];
-        ag.x = r.x; ag.y = r.y; ag.th = r.th; ag.hx = r.hx; ag.hy = r.hy; ag.dl = r.dl; ag.dr = r.dr; ag.v = r.v;
-        ag.steer = r.steer; ag.a0s = r.a0s; ag.a0t = r.a0t; ag.lhx = r.lasthx; ag.lhy = r.lasthy;
-        ag.cur_first = r.cur_first; ag.cur_n = r.cur_n; ag.next_first = r.next_first;
-        ag.blk = r.blk; ag.toll_time = r.php;
-        ag.env = e; ag.slot = 0; ag.tick = steps_total;
+        agent_view(ag, r, e, 0, steps_total);
         ag.cur_n |= scen << 8;  // the env's (possibly re-drawn) scenario travels with the view
       }
     }
@@ -1099,11 +1087,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
       for (int k = g.sub; k < d.D; k += g.SUB) row[k] = 0.0f;
     } else {
       AgentView ag;
-      ag.x = r.x; ag.y = r.y; ag.th = r.th; ag.hx = r.hx; ag.hy = r.hy; ag.dl = r.dl; ag.dr = r.dr; ag.v = r.v;
-      ag.steer = r.steer; ag.a0s = r.a0s; ag.a0t = r.a0t; ag.lhx = r.lasthx; ag.lhy = r.lasthy;
-      ag.cur_first = r.cur_first; ag.cur_n = r.cur_n; ag.next_first = r.next_first;
-      ag.blk = r.blk; ag.toll_time = r.php;
-      ag.env = e; ag.slot = s; ag.tick = steps_total;
+      agent_view(ag, r, e, s, steps_total);
       state_block<false>(d, mv, SPV, ag, row, g.sub, g.SUB);
     }
   }

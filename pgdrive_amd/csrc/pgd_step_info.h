@@ -1,6 +1,6 @@
 // pgd_step_info.h -- step info on the device (include/pgdrive_hip.h, pgd_step_info): the info values of every env, the terminal row
 // and the statistics of every episode that ended, and the restart of those envs, by ONE kernel after the step.  Part of the single
-// translation unit pgd_engine.hip (included at its end; uses observe_row of pgd_kernels.h and the engine handle).
+// translation unit pgd_engine.hip (included at its end; uses observe_row of pgd_observe.h and the engine handle).
 //
 // While the info is enabled, step_impl clears cfg.auto_reset in the by-value PgdDev it hands to k_step: phase (8) of the step (the
 // restart) is then never taken -- auto_reset is read nowhere else on the single-agent path and is in none of the PGD_FIX*_FIELDS
