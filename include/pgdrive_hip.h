@@ -406,6 +406,42 @@ int pgd_set_step_module(pgd_handle h, const char* code_object_path, int built_wi
 int pgd_mlp_policy(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, int hidden, const float* d_w1,
                    const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3, int out_cols,
                    int final_tanh, float* d_actions);
+/* Actor and critic of a PPO rollout in one launch: a sampled action, its log-probability and the value estimate for every (env,
+ * agent) row of the engine (rows and `group` as for pgd_mlp_policy).  Replaces pgdrive/examples/ppo_expert/numpy_expert.py:38-45
+ * (`expert(obs, deterministic=False)`: mean, log_std = split(fc_out's four outputs); action = normal(mean, exp(log_std))) and
+ * numpy_expert.py:62-78 (`value(obs)`: fc_value_1, fc_value_2, value_out -- a second network of the same shape with one output), plus
+ * the log-probability a trainer computes from both.  Layout: as pgd_mlp_policy -- fp32 device arrays, row-major [in][out]; hidden is 256;
+ * w1, b1, w2, b2 of each network 16-byte aligned; in_dim 4 .. 416 (the head's four weight rows take 2 KB more of the workgroup's 64 KB
+ * of LDS than pgd_mlp_policy's two: PGD_ERR_ARG above); obs_stride >= in_dim; out_cols >= 4 (columns at or beyond 4 are never read).
+ * The value network's six pointers are all set or all null; null: no critic, d_value is not touched (and may be null).
+ * Arithmetic (fp32; the 256-wide layers on the f32 matrix cores, as pgd_mlp_policy), per row with g = (env_base + env) * A + agent:
+ *   r1 = rng(seed ^ 0xac7012c1, g, 0x5a3b1e0d, tick), r2 = rng(seed ^ 0xac7012c1, g, 0x5a3b1e0d, tick ^ 0x80000000)   (the counter hash)
+ *   u = ((r >> 9) + 0.5) * 2^-23 (exact in fp32, never 0 or 1);  R = sqrt(-2 log u1), z0 = R cos(2 pi u2), z1 = R sin(2 pi u2)
+ *   action[i] = mean[i] + exp(log_std[i]) z[i]   -- unclipped, [rows][2], the buffer pgd_step reads and clips (numpy_expert.py:44)
+ *   logp = -0.5 (z0^2 + z1^2) - log_std0 - log_std1 - log(2 pi);   value = the critic's output
+ * PGD_AC_DETERMINISTIC: z = 0 (the action is the mean, logp the density at the mean).  `seed` is the caller's, not the engine's.
+ * Asynchronous on the engine's stream (group >= 0: the group's); may be captured in a HIP graph.  A captured launch replays with the
+ * `tick` it was captured with: pgd_actor_critic_tick gives the engine a uint32 counter in DEVICE memory that every later launch adds to
+ * its `tick` argument (modulo 2^32; read by the kernel when it runs), so that a replayed rollout draws new noise once the caller has
+ * advanced the counter on the same stream; null (the default): the argument alone. */
+typedef struct pgd_actor_critic {      /* device pointers, fp32, row-major [in][out] as the reference's `kernel` arrays */
+  const float *w1, *b1, *w2, *b2, *w3, *b3;  int32_t out_cols;   /* policy; out_cols >= 4: mean 0..1, log_std 2..3 */
+  const float *vw1, *vb1, *vw2, *vb2, *vw3, *vb3;                /* value net, vw3 [256][1]; all six null = no critic */
+} pgd_actor_critic;
+#define PGD_AC_DETERMINISTIC 1u
+int pgd_mlp_actor_critic(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets,
+                         uint32_t seed, uint32_t tick, uint32_t flags,
+                         float* d_actions /*[rows][2]*/, float* d_logp /*[rows]*/, float* d_value /*[rows], may be null without critic*/);
+int pgd_actor_critic_tick(pgd_handle h, const uint32_t* d_tick /* device memory, or null */);
+/* Generalised advantage estimation behind a rollout of T steps (what RL libraries compute on the host from the arrays the reference's
+ * env.step returned; no counterpart inside the reference).  Time-major device arrays: reward, done (the uint8 pgd_step writes), adv,
+ * ret [T][rows]; value [T + 1][rows], row T the bootstrap.  One thread per row, t from T - 1 down to 0, fp32:
+ *   nonterminal = 1 - done[t][r];  delta = reward[t][r] + gamma value[t+1][r] nonterminal - value[t][r]
+ *   adv[t][r] = delta + gamma lam nonterminal adv[t+1][r]  (adv[T] = 0);   ret[t][r] = adv[t][r] + value[t][r]
+ * A done ends the episode for GAE whatever ended it: no bootstrap through a horizon truncation.  T >= 1, rows >= 1 (PGD_ERR_ARG).
+ * Asynchronous on the engine's stream; may be captured in a HIP graph. */
+int pgd_gae(pgd_handle h, const float* d_reward, const float* d_value /*[T+1][rows]*/, const uint8_t* d_done, int T, int rows,
+            float gamma, float lam, float* d_adv, float* d_ret);
 /* Multi-agent engines remember, per env, which rows of the LAST observation buffer they were given already hold the zeros of a seat
  * that is not due (identified by the buffer's address and row stride), and do not write them again.  A caller that hands pgd_step
  * a buffer whose address a FORMER buffer had (a caching allocator re-using a freed block: torch.empty per step) calls this first:

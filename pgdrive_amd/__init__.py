@@ -21,6 +21,9 @@ def __getattr__(name):
     if name.startswith("MultiAgent"):  # MultiAgent{Roundabout,Intersection,Bottleneck,Tollgate,ParkingLot}[Vec]Env, MultiAgentPGDrive[VecEnv]
         from . import marl_env
         return getattr(marl_env, name)
+    if name == "RolloutCollector":
+        from .rollout import RolloutCollector
+        return RolloutCollector
     if name == "Engine":
         from .engine import Engine
         return Engine

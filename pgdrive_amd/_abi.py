@@ -41,6 +41,15 @@ class StepInfo(C.Structure):
                                    "ep_arrive", "ep_out_of_road", "ep_crash", "ep_max_step")]
 
 
+class ActorCritic(C.Structure):
+    """pgd_actor_critic: the device pointers of the policy network (out_cols >= 4: mean 0..1, log_std 2..3) and of the value network
+    (all six None = no critic)."""
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")] + [("out_cols", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("vw1", "vb1", "vw2", "vb2", "vw3", "vb3")]
+
+
+AC_DETERMINISTIC = 1
+
 # the tensors of Engine.enable_step_info by pgd_step_info field: (dtype name, key in Engine.step_info)
 STEP_INFO_FIELDS = dict(
     velocity="float32", steering="float32", acceleration="float32", episode_energy="float32", step_energy="float32",

@@ -1,0 +1,199 @@
+// pgd_actor_critic.h -- what a PPO rollout needs from its networks at every step, as ONE launch, and GAE behind the rollout.
+// Part of the single translation unit pgd_engine.hip (included by pgd_step.h behind pgd_policy.h, whose layer code it uses).
+//
+// What it mirrors: pgdrive/examples/ppo_expert/numpy_expert.py:38-45 (`expert(obs, deterministic=False)`: the four outputs of fc_out are
+//   mean, log_std = split(out, 2);  action = normal(mean, exp(log_std))
+// ) and numpy_expert.py:62-78 (`value(obs)`: a second network of the same shape, fc_value_1 / fc_value_2 / value_out, one output).  A
+// trainer evaluates both at every step and needs the log-probability of the sample for PPO's ratio: as framework ops two times three
+// GEMMs, a randn and a handful of elementwise launches.  Here: k_mlp_actor_critic, grid (ceil(rows / 16), 2).  Workgroup (x, 0) is the
+// actor for 16 observation rows, workgroup (x, 1) the critic for the same rows (their second read comes from L2); both are
+// k_mlp_policy's workgroup -- 16-row tile, 4 waves, the same LDS strides, the same row prologue, mlp_layer / mlp_store_hidden /
+// mlp_tanh -- with another head.  Two workgroups of 256 threads and at most 64 KB fit a CU side by side, so the critic runs NEXT to the
+// actor, not behind it.  A null value network launches gridDim.y = 1.
+//
+// LDS per workgroup: X tile | H1 | H2 | the head's weights [4][256] (the critic uses the first 256): 2 KB more than k_mlp_policy, hence
+// the largest accepted in_dim is 416 (x stride 418), not 448 (x stride 450: 65,920 bytes); ac_lds_bytes is the formula.
+//
+// Actor head: four dot products of 256 per row (columns 0..3 of w3 / b3: mean0, mean1, log_std0, log_std1; columns at or beyond 4 are
+// never read), four lanes each (lane p takes k = p, p + 4, ...), a butterfly sum.  Then, per row:
+//   g  = (env_base + env) * A + agent                      the global row: ranks of a multi-GPU run draw different noise
+//   r1 = pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick),  r2 = pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick ^ 0x80000000)
+//   u  = ((r >> 9) + 0.5) * 2^-23                          23 bits: exact in f32, never 0 or 1 (with 24 bits the sum needs 25 bits of
+//                                                          significand above 2^23, and the largest draw would round to u = 1)
+//   R = sqrtf(-2 logf(u1)),  z0 = R cosf(2 pi u2),  z1 = R sinf(2 pi u2)        Box-Muller, the library functions (not __logf / __cosf)
+//   action[i] = mean[i] + expf(log_std[i]) z[i]            unclipped: pgd_step clips (numpy_expert.py:44)
+//   logp = -0.5 (z0^2 + z1^2) - log_std0 - log_std1 - log(2 pi)                 from z itself: (a - mean) / std would divide a rounding
+//                                                                               error by std
+// PGD_AC_DETERMINISTIC: z = 0 -- the action is the mean, logp the density at the mean.
+// `tick`: the argument plus, when the engine has been given one (pgd_actor_critic_tick), a counter in device memory read by the kernel:
+// a captured graph replays with the argument it was captured with, the counter is what advances between replays.
+// Critic head: one dot product of 256 per row, sixteen lanes each, value[row] = sum + vb3[0].
+//
+// k_gae: one thread per row, a reverse scan over t (pgd_gae in include/pgdrive_hip.h states the recursion); arrays are time-major
+// [T][rows], so the reads and writes of a wave are consecutive.
+#ifndef PGD_ACTOR_CRITIC_H
+#define PGD_ACTOR_CRITIC_H
+
+#define AC_HEAD 4
+#define AC_KEY_SEED 0xac7012c1u
+#define AC_KEY_STREAM 0x5a3b1e0du
+
+DEV_HOST size_t ac_lds_bytes(int in_dim) {  // X tile | H1 | H2 | the head's weights [4][256]
+  return sizeof(float) * ((size_t)MLP_ROWS * ((size_t)mlp_x_stride(in_dim) + 2 * MLP_HS) + AC_HEAD * MLP_H);
+}
+
+// u in (0, 1) from the top 23 bits of a draw: exact in f32
+DEV float ac_unit(const uint32_t r) { return ((float)(r >> 9) + 0.5f) * (1.0f / 8388608.0f); }
+
+// k_mlp_policy's row prologue as a function (that kernel keeps its own copy inline: its code object stays what it was).
+// The 16 observation rows of a workgroup into its X tile (row stride xs): rows row0 + r0 + [0, 16) of `obs`, as far as they lie below
+// row0 + n_rows; wave w takes rows w, w + 4, ...  Whole rows, coalesced (a row is contiguous in memory); padding columns and rows past the end read zero.
+// Every read of the wave's four rows goes out before the first LDS store (rows of up to 320 floats: five chunks of 64 per row) --
+// as a read-then-store loop the prologue was twenty memory round trips in a row, a third of the launch (round 6)
+DEV void ac_load_rows(const float* obs, const int row0, const int r0, const int n_rows, const int obs_stride, const int in_dim, const int kp,
+                       const int xs, const int wave, const int lane, float* X) {
+  constexpr int XCH = 5;
+  if (kp <= WAVE * XCH) {
+    float v[MLP_ROWS / MLP_WAVES][XCH];
+#pragma unroll
+    for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i) {
+      const int r = wave + i * MLP_WAVES;
+      const bool row_in = r0 + r < n_rows;
+      const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
+#pragma unroll
+      for (int j = 0; j < XCH; ++j) {
+        const int k = lane + WAVE * j;
+        v[i][j] = src[k < in_dim ? k : in_dim - 1];
+        if (!(row_in && k < in_dim)) v[i][j] = 0.0f;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i)
+#pragma unroll
+      for (int j = 0; j < XCH; ++j) {
+        const int k = lane + WAVE * j;
+        if (k < kp) X[(wave + i * MLP_WAVES) * xs + k] = v[i][j];
+      }
+  } else
+  for (int r = wave; r < MLP_ROWS; r += MLP_WAVES) {
+    const bool row_in = r0 + r < n_rows;
+    const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
+    for (int k = lane; k < kp; k += WAVE) X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
+  }
+}
+
+// rows [row0, row0 + n_rows) of `obs` -> act[row][0..1], logp[row] (blockIdx.y == 0) and value[row] (blockIdx.y == 1)
+__global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic(const float* __restrict__ obs, const int row0, const int n_rows,
+                                                                       const int obs_stride, const int in_dim, const pgd_actor_critic nets,
+                                                                       const uint32_t seed, const uint32_t tick_arg,
+                                                                       const uint32_t* __restrict__ tick_dev, const uint32_t row_base,
+                                                                       const uint32_t flags, float* __restrict__ act, float* __restrict__ logp,
+                                                                       float* __restrict__ value) {
+  extern __shared__ float mlp_lds[];
+  const bool critic = blockIdx.y != 0;
+  const float* __restrict__ W1 = critic ? nets.vw1 : nets.w1;
+  const float* __restrict__ b1 = critic ? nets.vb1 : nets.b1;
+  const float* __restrict__ W2 = critic ? nets.vw2 : nets.w2;
+  const float* __restrict__ b2 = critic ? nets.vb2 : nets.b2;
+  const float* __restrict__ W3 = critic ? nets.vw3 : nets.w3;
+  const float* __restrict__ b3 = critic ? nets.vb3 : nets.b3;
+  const int kp = (in_dim + 3) & ~3, xs = mlp_x_stride(in_dim);
+  float* X = mlp_lds;
+  float* H1 = X + MLP_ROWS * xs;
+  float* H2 = H1 + MLP_ROWS * MLP_HS;
+  float* W3s = H2 + MLP_ROWS * MLP_HS;  // [4][256]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int r0 = (int)blockIdx.x * MLP_ROWS;  // (relative to row0)
+  // the head's weights go to LDS with the observation rows, as in k_mlp_policy: actor 256 x 4 of w3 (its first four columns, index =
+  // 4 k + o), critic the 256 of vw3 (index = k)
+  const int heads = critic ? 1 : AC_HEAD, w3_ld = critic ? 1 : nets.out_cols;
+  float w3v[AC_HEAD];
+#pragma unroll
+  for (int q = 0; q < AC_HEAD; ++q) {
+    const int idx = tid + q * WAVE * MLP_WAVES;
+    const int k = critic ? idx : idx >> 2, o = critic ? 0 : idx & 3;
+    w3v[q] = q < heads ? W3[(size_t)k * w3_ld + o] : 0.0f;
+  }
+  ac_load_rows(obs, row0, r0, n_rows, obs_stride, in_dim, kp, xs, wave, lane, X);
+#pragma unroll
+  for (int q = 0; q < AC_HEAD; ++q) {
+    const int idx = tid + q * WAVE * MLP_WAVES;
+    const int k = critic ? idx : idx >> 2, o = critic ? 0 : idx & 3;
+    if (q < heads) W3s[o * MLP_H + k] = w3v[q];
+  }
+  __syncthreads();
+  const int c0 = wave * 64;
+  mlp_f32x4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = mlp_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  mlp_layer(X, xs, W1, kp, in_dim, lane, c0, acc);
+  mlp_store_hidden(H1, b1, lane, c0, acc);
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = mlp_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  mlp_layer(H1, MLP_HS, W2, MLP_H, MLP_H, lane, c0, acc);
+  mlp_store_hidden(H2, b2, lane, c0, acc);
+  __syncthreads();
+  if (critic) {  // 16 dot products of 256, sixteen lanes each
+    const int r = tid >> 4, part = tid & 15;
+    float s = 0.0f;
+#pragma unroll 4
+    for (int k = part; k < MLP_H; k += 16) s = fmaf(H2[r * MLP_HS + k], W3s[k], s);
+    s += __shfl_xor(s, 8);
+    s += __shfl_xor(s, 4);
+    s += __shfl_xor(s, 2);
+    s += __shfl_xor(s, 1);
+    if (part == 0 && r0 + r < n_rows) value[(size_t)(row0 + r0 + r)] = s + b3[0];
+    return;
+  }
+  // 16 rows x 4 outputs = 64 dot products of 256, four lanes each; the sixteen lanes of a row sit in one wave
+  const int r = tid >> 4, o = (tid >> 2) & 3, part = tid & 3;
+  float s = 0.0f;
+#pragma unroll 4
+  for (int k = part; k < MLP_H; k += 4) s = fmaf(H2[r * MLP_HS + k], W3s[o * MLP_H + k], s);
+  s += __shfl_xor(s, 2);
+  s += __shfl_xor(s, 1);
+  const float v = s + b3[o];
+  const int l0 = lane & ~15;
+  const float m0 = __shfl(v, l0), m1 = __shfl(v, l0 + 4), ls0 = __shfl(v, l0 + 8), ls1 = __shfl(v, l0 + 12);
+  if ((lane & 15) == 0 && r0 + r < n_rows) {
+    const int row = row0 + r0 + r;
+    float z0 = 0.0f, z1 = 0.0f;
+    if (!(flags & PGD_AC_DETERMINISTIC)) {
+      const uint32_t tick = tick_arg + (tick_dev ? *tick_dev : 0u), g = row_base + (uint32_t)row;
+      const float u1 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick));
+      const float u2 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick ^ 0x80000000u));
+      const float R = sqrtf(-2.0f * logf(u1));
+      float sn, cs;
+      sincosf(2.0f * PGD_PI * u2, &sn, &cs);
+      z0 = R * cs;
+      z1 = R * sn;
+    }
+    act[(size_t)row * 2 + 0] = fmaf(expf(ls0), z0, m0);
+    act[(size_t)row * 2 + 1] = fmaf(expf(ls1), z1, m1);
+    logp[row] = fmaf(-0.5f, fmaf(z0, z0, z1 * z1), -ls0 - ls1) - 1.8378770664093453f;  // log(2 pi)
+  }
+}
+
+// adv[t][r] = delta + gamma lam nonterminal adv[t + 1][r], delta = reward[t][r] + gamma value[t + 1][r] nonterminal - value[t][r],
+// ret = adv + value; nonterminal = 1 - done[t][r]; one thread per row r, t from T - 1 down to 0
+__global__ __launch_bounds__(WAVE) void k_gae(const float* __restrict__ reward, const float* __restrict__ value, const uint8_t* __restrict__ done,
+                                              const int T, const int rows, const float gamma, const float lam, float* __restrict__ adv,
+                                              float* __restrict__ ret) {
+  const int r = (int)blockIdx.x * WAVE + (int)threadIdx.x;
+  if (r >= rows) return;
+  const float gl = gamma * lam;
+  float a = 0.0f, vn = value[(size_t)T * rows + r];
+#pragma unroll 4
+  for (int t = T - 1; t >= 0; --t) {
+    const size_t i = (size_t)t * rows + r;
+    const float v = value[i], nt = done[i] ? 0.0f : 1.0f;
+    const float delta = fmaf(gamma * nt, vn, reward[i]) - v;
+    a = fmaf(gl * nt, a, delta);
+    adv[i] = a;
+    ret[i] = a + v;
+    vn = v;
+  }
+}
+
+#endif

@@ -1,6 +1,6 @@
 // pgd_engine.hip — the single translation unit of the MI355X-native batched PGDrive step engine and its host side: the engine handle, the
 // launch plan of a step and the C ABI (include/pgdrive_hip.h).  The device code is in the headers included here, in this order: pgd_device.h,
-// pgd_step.h (k_step; it includes pgd_vehicle.h ... pgd_policy.h), pgd_kernels.h (reset / derive / refresh / observe) and, at the end,
+// pgd_step.h (k_step; it includes pgd_vehicle.h ... pgd_policy.h, pgd_actor_critic.h), pgd_kernels.h (reset / derive / refresh / observe) and, at the end,
 // pgd_topdown.h, pgd_render.h, pgd_gather.h and pgd_step_info.h with their own entry points.
 // The reference call stack this replaces: envs/base_env.py:184-224,303-344.
 #include <hip/hip_runtime.h>
@@ -81,6 +81,8 @@ struct pgd_engine {
   hipModule_t jit_mod;
   hipFunction_t jit_fn;
   bool jit_obj;
+  bool ac_attr;      // pgd_mlp_actor_critic: likewise
+  const uint32_t* ac_tick;  // pgd_actor_critic_tick: the device counter added to every launch's tick (null: none)
   bool mlp_attr[4];  // pgd_mlp_policy / pgd_mlp_policy_prepared: the kernel's dynamic LDS limit has been raised on this engine's device
   int jit_geom[4];   // sub, epw, pack_obs, use_imask at the time of the build
   char jit_name[96];
@@ -911,6 +913,51 @@ int pgd_mlp_policy_prepared(pgd_handle h, int group, const float* d_obs, int obs
   }
   hipLaunchKernelGGL(kern, dim3((rows + MLP_ROWS - 1) / MLP_ROWS), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs, row0, rows, obs_stride, in_dim,
                      reinterpret_cast<const uint4*>(d_prepared), d_actions);
+  HIPCHK(hipGetLastError());
+  return PGD_OK;
+}
+
+/* ---- actor + critic of a rollout in one launch, and GAE behind it (pgd_actor_critic.h) -------------------------------------------- */
+int pgd_actor_critic_tick(pgd_handle h, const uint32_t* d_tick) {
+  if (!h || (reinterpret_cast<uintptr_t>(d_tick) & 3u) != 0u) return PGD_ERR_ARG;
+  h->ac_tick = d_tick;
+  return PGD_OK;
+}
+
+int pgd_mlp_actor_critic(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets, uint32_t seed,
+                         uint32_t tick, uint32_t flags, float* d_actions, float* d_logp, float* d_value) {
+  if (!h || !d_obs || !nets || !d_actions || !d_logp || (flags & ~PGD_AC_DETERMINISTIC) != 0u) return PGD_ERR_ARG;
+  if (!nets->w1 || !nets->b1 || !nets->w2 || !nets->b2 || !nets->w3 || !nets->b3) return PGD_ERR_ARG;
+  const float* vp[6] = {nets->vw1, nets->vb1, nets->vw2, nets->vb2, nets->vw3, nets->vb3};
+  int n_value = 0;
+  for (const float* p : vp) n_value += p ? 1 : 0;
+  if ((n_value != 0 && n_value != 6) || (n_value == 6 && !d_value)) return PGD_ERR_ARG;
+  if (in_dim < 4 || in_dim > 4096 || obs_stride < in_dim || nets->out_cols < AC_HEAD) return PGD_ERR_ARG;
+  if ((((uintptr_t)nets->w1 | (uintptr_t)nets->w2 | (uintptr_t)nets->b1 | (uintptr_t)nets->b2 | (uintptr_t)nets->vw1 | (uintptr_t)nets->vw2 |
+        (uintptr_t)nets->vb1 | (uintptr_t)nets->vb2) & 15u) != 0u) return PGD_ERR_ARG;  // 16-byte reads
+  const size_t lds = ac_lds_bytes(in_dim);
+  if (lds > 65536) return PGD_ERR_ARG;
+  HIPCHK(hipSetDevice(h->device));
+  EnvGroup g;
+  { int rc = env_group(h, group, g); if (rc) return rc; }
+  const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
+  if (lds > 49152 && !h->ac_attr) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_actor_critic), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    h->ac_attr = true;
+  }
+  hipLaunchKernelGGL(k_mlp_actor_critic, dim3((rows + MLP_ROWS - 1) / MLP_ROWS, n_value ? 2 : 1), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs,
+                     row0, rows, obs_stride, in_dim, *nets, seed, tick, h->ac_tick, (uint32_t)h->d.cfg.env_base * (uint32_t)h->d.A, flags,
+                     d_actions, d_logp, d_value);
+  HIPCHK(hipGetLastError());
+  return PGD_OK;
+}
+
+int pgd_gae(pgd_handle h, const float* d_reward, const float* d_value, const uint8_t* d_done, int T, int rows, float gamma, float lam,
+            float* d_adv, float* d_ret) {
+  if (!h || !d_reward || !d_value || !d_done || !d_adv || !d_ret || T < 1 || rows < 1) return PGD_ERR_ARG;
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_gae, dim3((rows + WAVE - 1) / WAVE), dim3(WAVE), 0, h->stream, d_reward, d_value, d_done, T, rows, gamma, lam, d_adv,
+                     d_ret);
   HIPCHK(hipGetLastError());
   return PGD_OK;
 }

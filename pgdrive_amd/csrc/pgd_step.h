@@ -1,7 +1,7 @@
 // pgd_step.h -- k_step, one env.step() for every environment, and everything that specialises it: the lane mapping, the step's LDS,
 // the PGD_FIX*_FIELDS lists that device (write_fixed_config) and host (fix_config_matches) both read, and the phase macros of the
 // profile builds.  Part of the single translation unit pgd_engine.hip (included there after pgd_device.h; it includes pgd_vehicle.h,
-// pgd_localize.h, pgd_idm.h, pgd_dynamics.h, pgd_observe.h and pgd_policy.h itself, in this order, after the macros they use).
+// pgd_localize.h, pgd_idm.h, pgd_dynamics.h, pgd_observe.h, pgd_policy.h and pgd_actor_critic.h itself, in this order, after the macros they use).
 // With -DPGD_JIT the unit ends with this header: the block at its end is the one kernel of a run-time build.
 //
 // Execution model (gfx950, wave64):
@@ -62,6 +62,7 @@ __shared__ long long s_prof_t0, s_prof_w0;
 #include "pgd_dynamics.h"
 #include "pgd_observe.h"
 #include "pgd_policy.h"
+#include "pgd_actor_critic.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_step: one env.step() for every environment (base_env.py:184-224)

@@ -34,6 +34,10 @@ _SIGS = {
     "pgd_step_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pgd_set_step_module": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int]),
     "pgd_mlp_policy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
+    "pgd_mlp_actor_critic": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ActorCritic), C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgd_actor_critic_tick": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pgd_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "pgd_step_lane_keep": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 4),
     "pgd_lane_keep_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32]),
     "pgd_topdown_channels": (C.c_int, [C.POINTER(_abi.TopDownConfig)]),
@@ -329,6 +333,74 @@ class Engine:
                                    C.c_void_p(w3.data_ptr()), C.c_void_p(b3.data_ptr()), int(w3.shape[1]), int(bool(final_tanh)),
                                    C.c_void_p(out.data_ptr())), "pgd_mlp_policy")
         return out
+
+    def _network(self, weights, k, heads):
+        """The six tensors of one network checked (float32 cuda, contiguous, [k, 256] / [256, 256] / [256, >= heads]) -> their pointers."""
+        t = self.torch
+        w1, b1, w2, b2, w3, b3 = weights
+        for w in weights:
+            assert w.is_cuda and w.dtype == t.float32 and w.is_contiguous()
+        assert w1.shape == (k, 256) and w2.shape == (256, 256) and w3.dim() == 2 and w3.shape[0] == 256 and w3.shape[1] >= heads
+        assert b1.numel() == 256 and b2.numel() == 256 and b3.numel() == w3.shape[1]
+        return [w.data_ptr() for w in weights]
+
+    def mlp_actor_critic(self, policy_weights, value_weights, out, logp, value, seed, tick, obs=None, group=-1, deterministic=False,
+                         in_dim=None):
+        """A sampled action, its log-probability and the value estimate of every observation row in one launch (pgd_mlp_actor_critic).
+        `policy_weights` = (w1 [in, 256], b1, w2 [256, 256], b2, w3 [256, >= 4], b3): the head's columns are mean0, mean1, log_std0,
+        log_std1; `value_weights` the same shapes with a head of one column, or None (no critic: `value` is not written and may be None).
+        `out` [N, A, 2] (unclipped: step clips), `logp` and `value` [N, A]: float32 cuda.  The noise is a function of (seed, global row,
+        tick); `tick` is added to the device counter of actor_critic_tick, if one is set.  deterministic: the action is the mean.
+        `obs`, `group`, `in_dim` as for mlp_policy."""
+        t = self.torch
+        o = self.obs if obs is None else obs
+        o2 = o.view(-1, o.shape[-1])
+        rows = self.N * self.A
+        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == rows
+        self._check_actions(out)
+        for v in (logp, ) if value_weights is None else (logp, value):
+            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == rows
+        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
+        assert k <= o2.shape[1]
+        nets = _abi.ActorCritic()
+        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
+        nets.out_cols = int(policy_weights[4].shape[1])
+        if value_weights is not None:
+            nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
+            assert value_weights[4].shape[1] == 1
+        if group < 0:
+            self._follow_stream()
+        _chk(self.L.pgd_mlp_actor_critic(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k, C.byref(nets),
+                                         int(seed) & 0xffffffff, int(tick) & 0xffffffff, _abi.AC_DETERMINISTIC if deterministic else 0,
+                                         C.c_void_p(out.data_ptr()), C.c_void_p(logp.data_ptr()),
+                                         C.c_void_p(value.data_ptr()) if value_weights is not None else None), "pgd_mlp_actor_critic")
+        return out, logp, value
+
+    def actor_critic_tick(self, counter):
+        """Give the engine a tick counter in device memory (pgd_actor_critic_tick): a cuda int32 tensor of one element that every later
+        mlp_actor_critic launch adds to its `tick` (modulo 2^32) when it RUNS -- what lets a captured rollout draw new noise at every
+        replay.  None: back to the argument alone.  The engine keeps the tensor alive."""
+        if counter is not None:
+            assert counter.is_cuda and counter.dtype == self.torch.int32 and counter.numel() == 1
+        _chk(self.L.pgd_actor_critic_tick(self.h, C.c_void_p(counter.data_ptr()) if counter is not None else None), "pgd_actor_critic_tick")
+        self._ac_tick = counter
+
+    def gae(self, reward, value, done, gamma, lam, adv=None, ret=None):
+        """Advantages and returns of a rollout (pgd_gae): reward, done (uint8) [T, rows...], value [T + 1, rows...] (the last row is the
+        bootstrap), time-major contiguous cuda tensors; a done cuts the episode.  Returns (adv, ret), float32 of reward's shape (`adv`,
+        `ret`: buffers to write).  Asynchronous on the caller's current stream."""
+        t = self.torch
+        T = int(reward.shape[0])
+        rows = reward.numel() // max(T, 1)
+        adv = t.empty_like(reward) if adv is None else adv
+        ret = t.empty_like(reward) if ret is None else ret
+        for v, dt, n in ((reward, t.float32, T * rows), (value, t.float32, (T + 1) * rows), (done, t.uint8, T * rows), (adv, t.float32, T * rows),
+                         (ret, t.float32, T * rows)):
+            assert v.is_cuda and v.dtype == dt and v.is_contiguous() and v.numel() == n
+        self._follow_stream()
+        _chk(self.L.pgd_gae(self.h, C.c_void_p(reward.data_ptr()), C.c_void_p(value.data_ptr()), C.c_void_p(done.data_ptr()), T, rows,
+                            float(gamma), float(lam), C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr())), "pgd_gae")
+        return adv, ret
 
     def step_lane_keep(self, tick, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):
         """One closed-loop step under the scripted lane-keeping policy (pgd_step_lane_keep): the policy reads the engine's own

@@ -1,0 +1,94 @@
+"""On-device PPO rollouts of a single-agent engine: T steps of policy -> step with the sampled action, its log-probability and the
+value estimate from one launch per step (Engine.mlp_actor_critic), then advantages and returns (Engine.gae).
+
+What a trainer otherwise composes per step from framework ops -- two networks of three GEMMs, a randn, the log-probability, and a
+python loop over T for GAE -- around env.step (the reference: `expert(obs, deterministic=False)` and `value(obs)` of
+pgdrive/examples/ppo_expert/numpy_expert.py:38-78 per env and step, GAE in the RL library).
+
+    col = RolloutCollector(env, policy_weights, value_weights, T=128)
+    while training:
+        batch = col.collect()                 # a dict of cuda tensors, valid until the next collect()
+        ... update the networks from batch ...
+        col.set_weights(new_policy_weights, new_value_weights)
+
+Layout: every tensor is time-major and preallocated once; row t + 1 of the observation, action, log-probability and value arrays is what
+the step of row t produced and what the networks made of it, so the step writes its observation, reward and done STRAIGHT into the
+rollout (Engine.step(out=...)) and the networks read and write it in place: no copy per step.  Row T (the observation behind the last
+step, its action, log-probability and value -- the bootstrap of GAE) is carried into row 0 of the next rollout by four row copies per
+collect(): every observation is evaluated exactly once, with the weights of the rollout it was observed in, and the action stream
+stays the sampled one.  Nothing in collect() waits for the device.
+
+The noise of evaluation j (counted over the collector's life) is that of tick j: the kernel adds its `tick` argument (the row, 0 .. T)
+to a counter in device memory that collect() advances by T on the stream, so a collect() captured in a HIP graph draws new noise at every
+replay and equals the eager call bit for bit.
+
+A done ends the episode for GAE, whatever ended it: there is no bootstrap through a horizon truncation from the terminal observation.
+"""
+
+
+class RolloutCollector:
+    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0):
+        eng = getattr(env_or_engine, "engine", env_or_engine)
+        if eng.A != 1:
+            raise NotImplementedError(
+                "RolloutCollector serves single-agent engines: with %d agent seats per env the rows of seats that are not due need a mask "
+                "that is not defined yet -- call Engine.mlp_actor_critic and Engine.gae directly (rows = N * A)" % eng.A)
+        if int(T) < 1:
+            raise ValueError("RolloutCollector: T = %r" % (T, ))
+        t = eng.torch
+        self.engine, self.T, self.gamma, self.lam, self.seed = eng, int(T), float(gamma), float(lam), int(seed)
+        T, N, D, dev = self.T, eng.N, eng.D, eng.device
+        f32 = dict(dtype=t.float32, device=dev)
+        self._obs = t.zeros((T + 1, N, D), **f32)
+        self._actions = t.zeros((T + 1, N, 2), **f32)
+        self._logp = t.zeros((T + 1, N), **f32)
+        self.values = t.zeros((T + 1, N), **f32)
+        self.rewards = t.zeros((T, N), **f32)
+        self.dones = t.zeros((T, N), dtype=t.uint8, device=dev)
+        self.flags = t.zeros((T, N), dtype=t.int32, device=dev)
+        self.advantages = t.zeros((T, N), **f32)
+        self.returns = t.zeros((T, N), **f32)
+        self._tick = t.zeros((1, ), dtype=t.int32, device=dev)  # evaluations before this rollout (modulo 2^32)
+        self._carry = (self._obs, self._actions, self._logp, self.values)
+        self._primed = False
+        self.set_weights(policy_weights, value_weights)
+        self.batch = dict(obs=self._obs[:T], actions=self._actions[:T], logp=self._logp[:T], values=self.values, rewards=self.rewards,
+                          dones=self.dones, flags=self.flags, advantages=self.advantages, returns=self.returns)
+
+    def set_weights(self, policy_weights, value_weights):
+        """The networks of the rollouts from now on (between two collect() calls): tuples as for Engine.mlp_actor_critic."""
+        self.policy_weights, self.value_weights = tuple(policy_weights), tuple(value_weights)
+
+    def _evaluate(self, row):
+        self.engine.mlp_actor_critic(self.policy_weights, self.value_weights, self._actions[row], self._logp[row], self.values[row], self.seed,
+                                     row, obs=self._obs[row])
+
+    def prime(self):
+        """Take the engine's present observation (what reset wrote into Engine.obs) as the start of the first rollout.  collect() calls
+        it once by itself; call it before capturing collect() in a graph."""
+        eng, T = self.engine, self.T
+        self._obs[T].copy_(eng.obs.view(eng.N, eng.D))
+        self._tick.sub_(T)  # (this evaluation is number 0: row T, counter -T)
+        eng.actor_critic_tick(self._tick)
+        self._evaluate(T)
+        eng.actor_critic_tick(None)
+        self._tick.add_(T)
+        self._primed = True
+
+    def collect(self):
+        """T steps.  Returns the dict of the collector's tensors (the same objects every time, valid until the next call):
+        obs [T, N, D], actions [T, N, 2] (as sampled; the step clips), logp [T, N], values [T + 1, N], rewards, dones (uint8), flags,
+        advantages, returns [T, N]."""
+        eng, T = self.engine, self.T
+        if not self._primed:
+            self.prime()
+        for buf in self._carry:
+            buf[0].copy_(buf[T])
+        eng.actor_critic_tick(self._tick)  # (the engine's launches add the counter only while the collector is at work)
+        for t in range(T):
+            eng.step(self._actions[t], out=(self._obs[t + 1], self.rewards[t], self.dones[t], self.flags[t]))
+            self._evaluate(t + 1)
+        eng.actor_critic_tick(None)
+        eng.gae(self.rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
+        self._tick.add_(T)
+        return self.batch
