@@ -442,6 +442,59 @@ int pgd_actor_critic_tick(pgd_handle h, const uint32_t* d_tick /* device memory,
  * Asynchronous on the engine's stream; may be captured in a HIP graph. */
 int pgd_gae(pgd_handle h, const float* d_reward, const float* d_value /*[T+1][rows]*/, const uint8_t* d_done, int T, int rows,
             float gamma, float lam, float* d_adv, float* d_ret);
+/* ---- Rollouts of multi-agent engines: which seat rows count, the networks over those rows only, GAE per agent ----------------------
+ * (No reference counterpart: the reference returns dicts keyed by agent name, multi_agent_pgdrive.py:109-213, and an RL library batches
+ * the agents that are present.  Here a seat is a row of fixed arrays and the flags pgd_step wrote say what the row means.)
+ * For seat row r = env * A + seat and step t, let f = flags[t][r] and d = done[t][r], as pgd_step wrote them:
+ *   acted(t) = f & PGD_F_REPORT                        an agent held the seat and acted in step t: obs[t], action[t], logp[t], value[t],
+ *                                                      reward[t], done[t] are its
+ *   cont(t)  = acted(t) && !d && !(f & PGD_F_RESET)    the same agent holds the seat after the step: obs[t + 1] is its next observation
+ *   live(t)  = (f & PGD_F_NEW) || cont(t)              row t + 1 of the seat holds an observation that an agent will act on
+ * On the engine acted(t + 1) == live(t) (held by tests/test_marl_rollout_gpu.py, not assumed by the kernels).
+ *
+ * pgd_live_rows: the ascending list of the rows at which `live` holds -> d_rows, their number -> *d_count (device memory, int32).
+ * Rows: all N x A of the engine (group < 0, the engine's stream) or those of env group `group` (the group's stream); the entries are
+ * the engine's own row numbers env * A + seat in either case, so d_rows needs room for as many entries as the range has rows.  d_flags,
+ * d_done: the FULL [N][A] arrays of a step.  Any engine is accepted (a single-agent engine never sets PGD_F_REPORT: its list is empty).
+ * pgd_rollout_index: the same for the predicate `acted` over a time-major flag array [T][rows]: entries t * rows + r, ascending, into
+ * d_index (room for T * rows entries; T * rows <= PGD_ROLLOUT_INDEX_MAX, PGD_ERR_ARG above), their number into *d_count.  What a trainer draws minibatches from.
+ * Both: three small launches (per-block counts by ballot and popcount; one workgroup scans the block counts and writes the total; a
+ * scatter) -- the order does not rest on atomics, no workgroup waits for another, the same input gives the same bytes, and entries at
+ * and beyond the count are not written.  Asynchronous; capturable in a HIP graph.  The block counts are the engine's scratch:
+ * pgd_live_rows' is allocated by pgd_create, with a segment for the whole-engine form and one for every env group, so the whole-engine
+ * call and the groups' calls may be in flight together (two calls of the SAME form and group share a segment: order them on one stream);
+ * pgd_rollout_index allocates on the first call and whenever T * rows exceeds every earlier call's, which a stream that is being
+ * captured cannot do (PGD_ERR_STATE): call it once with the rollout's shape before the capture.  Scratch that was outgrown is kept
+ * until pgd_destroy, so a graph captured with it can still be replayed; calls of pgd_rollout_index share the current scratch and
+ * are ordered by the engine's stream. */
+#define PGD_ROLLOUT_INDEX_MAX 2147482623 /* 2^31 - 1 - 1024: the last workgroup's block of 1024 indices stays below 2^31 */
+int pgd_live_rows(pgd_handle h, int group, const uint32_t* d_flags, const uint8_t* d_done, int32_t* d_rows, int32_t* d_count);
+int pgd_rollout_index(pgd_handle h, const uint32_t* d_flags /*[T][rows]*/, int T, int rows, int32_t* d_index, int32_t* d_count);
+/* pgd_mlp_actor_critic over a row list: every argument of pgd_mlp_actor_critic, plus d_rows / d_count as pgd_live_rows wrote them (or
+ * any ascending or unordered list of distinct rows of the range).  Tile j of 16 rows takes list entries 16 j .. 16 j + 15 and gathers
+ * their observation rows; outputs go to the rows' own places in d_actions, d_logp, d_value; the noise is that of the TRUE row (g =
+ * (env_base + env) * A + agent, same seed and tick rule, the device counter of pgd_actor_critic_tick included): a listed row gets bit for
+ * bit what pgd_mlp_actor_critic gives it on the same inputs.  The host never reads *d_count: the grid covers every row of the range and
+ * a workgroup whose tile starts at or beyond the count ends before it reads a weight.  An entry that is no row of the range is skipped.
+ * Rows of the range that are NOT listed get action 0, 0, logp 0 and (with a critic) value 0, written by THIS call (a clearing launch
+ * in front of the networks; pgd_live_rows writes the list only), so a seat that was live in the last rollout does not keep its old
+ * numbers; their observations are never used (a NaN there reaches no output).  in_dim 4 .. 416, the refusals, PGD_AC_DETERMINISTIC and the null critic (d_value
+ * untouched) as for pgd_mlp_actor_critic.  Two launches, asynchronous on the engine's stream (group >= 0: the group's); capturable. */
+int pgd_mlp_actor_critic_rows(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets,
+                              uint32_t seed, uint32_t tick, uint32_t flags, const int32_t* d_rows, const int32_t* d_count,
+                              float* d_actions /*[rows][2]*/, float* d_logp /*[rows]*/, float* d_value /*[rows], may be null without critic*/);
+/* pgd_gae for seats that change hands.  Arrays as for pgd_gae, plus flags [T][rows] (the uint32 pgd_step writes) and mask [T][rows]
+ * uint8 (written).  One thread per seat row, t from T - 1 down to 0, fp32, the fma forms of pgd_gae:
+ *   acted(t):   delta = reward[t] + gamma cont(t) value[t+1] - value[t];   a = delta + gamma lam cont(t) a;   adv[t] = a, ret[t] = a + value[t]
+ *   otherwise:  a = 0, adv[t] = 0, ret[t] = 0
+ *   mask[t] = acted(t)
+ * cont(t) and acted(t) select, they do not multiply: reward and value of a row that did not act, and value[t + 1] behind an agent that
+ * does not continue, may hold anything, NaN included.  A done, and a PGD_F_RESET without done (the env-wide restart at 5 x horizon or when
+ * no agent is left), end the agent's episode for GAE with no bootstrap, as pgd_gae does with a done; value[T] is read only by an agent
+ * that is still in its seat behind step T - 1.  With every flag PGD_F_REPORT and no PGD_F_RESET the results are pgd_gae's bit for bit.
+ * T >= 1, rows >= 1 (PGD_ERR_ARG).  Asynchronous on the engine's stream; may be captured in a HIP graph. */
+int pgd_gae_masked(pgd_handle h, const float* d_reward, const float* d_value /*[T+1][rows]*/, const uint8_t* d_done, const uint32_t* d_flags,
+                   int T, int rows, float gamma, float lam, float* d_adv, float* d_ret, uint8_t* d_mask);
 /* Multi-agent engines remember, per env, which rows of the LAST observation buffer they were given already hold the zeros of a seat
  * that is not due (identified by the buffer's address and row stride), and do not write them again.  A caller that hands pgd_step
  * a buffer whose address a FORMER buffer had (a caching allocator re-using a freed block: torch.empty per step) calls this first:

@@ -18,6 +18,9 @@ def __getattr__(name):
     if name in ("PGDriveEnv", "SafePGDriveEnv", "TopDownPGDriveEnv", "TopDownPGDriveEnvV2", "TopDownSingleFramePGDriveEnv", "make"):
         from . import env
         return getattr(env, name)
+    if name == "MultiAgentRolloutCollector":
+        from .rollout import MultiAgentRolloutCollector
+        return MultiAgentRolloutCollector
     if name.startswith("MultiAgent"):  # MultiAgent{Roundabout,Intersection,Bottleneck,Tollgate,ParkingLot}[Vec]Env, MultiAgentPGDrive[VecEnv]
         from . import marl_env
         return getattr(marl_env, name)

@@ -1,6 +1,7 @@
 // pgd_engine.hip — the single translation unit of the MI355X-native batched PGDrive step engine and its host side: the engine handle, the
 // launch plan of a step and the C ABI (include/pgdrive_hip.h).  The device code is in the headers included here, in this order: pgd_device.h,
-// pgd_step.h (k_step; it includes pgd_vehicle.h ... pgd_policy.h, pgd_actor_critic.h), pgd_kernels.h (reset / derive / refresh / observe) and, at the end,
+// pgd_step.h (k_step; it includes pgd_vehicle.h ... pgd_policy.h, pgd_actor_critic.h), pgd_kernels.h (reset / derive / refresh / observe),
+// pgd_marl_rollout.h (live rows, the networks over a row list, masked GAE) and, at the end,
 // pgd_topdown.h, pgd_render.h, pgd_gather.h and pgd_step_info.h with their own entry points.
 // The reference call stack this replaces: envs/base_env.py:184-224,303-344.
 #include <hip/hip_runtime.h>
@@ -25,6 +26,7 @@
 #include "pgd_step.h"
 #ifndef PGD_JIT  // (a run-time build, pgdrive_amd/jit.py, is the device code above and nothing else)
 #include "pgd_kernels.h"
+#include "pgd_marl_rollout.h"
 
 // The library's environment switches (include/pgdrive_hip.h lists them), read once, by pgd_create.  pack / imask: -1 = not forced.
 struct Switches { bool no_fuse, no_fix, jit_force, row_observe, no_state_in_step, no_rowz, no_uni; int pack, imask; };
@@ -83,6 +85,11 @@ struct pgd_engine {
   bool jit_obj;
   bool ac_attr;      // pgd_mlp_actor_critic: likewise
   const uint32_t* ac_tick;  // pgd_actor_critic_tick: the device counter added to every launch's tick (null: none)
+  bool acr_attr;     // pgd_mlp_actor_critic_rows: as ac_attr, for its own kernel
+  uint32_t* cmp_live;   // pgd_live_rows: block counts of the compaction, a segment for the whole engine and one per env group (pgd_create allocates it)
+  uint32_t* cmp_index;  // pgd_rollout_index: block counts [cmp_index_cap], grown outside graph captures
+  size_t cmp_index_cap;
+  std::vector<uint32_t*>* cmp_retired;  // cmp_index of smaller rollouts: graphs captured with them may still be replayed (freed by pgd_destroy)
   bool mlp_attr[4];  // pgd_mlp_policy / pgd_mlp_policy_prepared: the kernel's dynamic LDS limit has been raised on this engine's device
   int jit_geom[4];   // sub, epw, pack_obs, use_imask at the time of the build
   char jit_name[96];
@@ -380,6 +387,25 @@ static int build_reset_image(pgd_engine* h) {
   return PGD_OK;
 }
 
+// pgd_live_rows' scratch: the whole-engine call (group < 0) owns the first N A / CMP_BLOCK + 1 entries; behind them env group g of
+// n_groups (<= N) owns the entries from (its first row) / CMP_BLOCK + g on: its ceil(rows / CMP_BLOCK) blocks end before the next
+// group's first entry, and the last group's before N A / CMP_BLOCK + n_groups.  No two forms share an entry: a whole-engine call on the
+// engine's stream and group calls on their streams may be in flight together.
+static size_t live_scratch_whole(int N, int A) { return (size_t)N * (size_t)A / CMP_BLOCK + 1; }
+static size_t live_scratch_entries(int N, int A) { return 2 * live_scratch_whole(N, A) + (size_t)N; }
+
+// The three launches of the ordered compaction over indices first + [0, n) on `stream`; `counts`: ceil(n / CMP_BLOCK) entries of scratch
+template <int PRED>
+static int compact_launch(const uint32_t* d_flags, const uint8_t* d_done, int first, int n, uint32_t* counts, int32_t* d_list, int32_t* d_count,
+                          hipStream_t stream) {
+  const int n_blocks = (int)(((size_t)n + CMP_BLOCK - 1) / CMP_BLOCK);
+  hipLaunchKernelGGL((k_compact<PRED, false>), dim3(n_blocks), dim3(CMP_THREADS), 0, stream, d_flags, d_done, first, n, counts, d_list);
+  hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(CMP_THREADS), 0, stream, counts, n_blocks, d_count);
+  hipLaunchKernelGGL((k_compact<PRED, true>), dim3(n_blocks), dim3(CMP_THREADS), 0, stream, d_flags, d_done, first, n, counts, d_list);
+  HIPCHK(hipGetLastError());
+  return PGD_OK;
+}
+
 extern "C" {
 
 const char* pgd_version(void) { return "pgdrive_hip 0.1 (gfx950)"; }
@@ -445,6 +471,7 @@ int pgd_create(const pgd_config* cfg, int device, void* hip_stream, pgd_handle* 
     HIPCHK(hipMemsetAsync(h->rowz, 0, sizeof(ulonglong2) * (size_t)h->d.N, h->stream));
     h->d.rowz = h->rowz;
   }
+  HIPCHK(hipMalloc(&h->cmp_live, sizeof(uint32_t) * live_scratch_entries(h->d.N, h->d.A)));
   HIPCHK(hipMalloc(&h->d.env_map, sizeof(pgd_map) * (size_t)h->d.N));
   HIPCHK(hipMemsetAsync(h->d.env_map, 0, sizeof(pgd_map) * (size_t)h->d.N, h->stream));
   // never-written slots are read from the scenario's reset image (cache resident, shared by every env of the scenario) instead
@@ -962,6 +989,81 @@ int pgd_gae(pgd_handle h, const float* d_reward, const float* d_value, const uin
   return PGD_OK;
 }
 
+/* ---- rollouts of multi-agent engines: live rows, the networks over a row list, masked GAE (pgd_marl_rollout.h) --------------------- */
+int pgd_live_rows(pgd_handle h, int group, const uint32_t* d_flags, const uint8_t* d_done, int32_t* d_rows, int32_t* d_count) {
+  if (!h || !d_flags || !d_done || !d_rows || !d_count) return PGD_ERR_ARG;
+  HIPCHK(hipSetDevice(h->device));
+  EnvGroup g;
+  { int rc = env_group(h, group, g); if (rc) return rc; }
+  const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
+  uint32_t* counts = group < 0 ? h->cmp_live : h->cmp_live + live_scratch_whole(h->d.N, h->d.A) + (size_t)(row0 / CMP_BLOCK + group);
+  return compact_launch<CMP_LIVE>(d_flags, d_done, row0, rows, counts, d_rows, d_count, g.stream);
+}
+
+int pgd_rollout_index(pgd_handle h, const uint32_t* d_flags, int T, int rows, int32_t* d_index, int32_t* d_count) {
+  if (!h || !d_flags || !d_index || !d_count || T < 1 || rows < 1 || (long long)T * rows > PGD_ROLLOUT_INDEX_MAX) return PGD_ERR_ARG;
+  HIPCHK(hipSetDevice(h->device));
+  const int n = T * rows;
+  const size_t n_blocks = ((size_t)n + CMP_BLOCK - 1) / CMP_BLOCK;
+  if (n_blocks > h->cmp_index_cap) {  // (a larger rollout than any before: new scratch, which a capture cannot take)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(h->stream, &cap);
+    if (cap != hipStreamCaptureStatusNone) return PGD_ERR_STATE;
+    // the old scratch stays until pgd_destroy: launches in flight read it, and a graph captured with it may be replayed at any time
+    uint32_t* grown = nullptr;
+    HIPCHK(hipMalloc(&grown, sizeof(uint32_t) * n_blocks));
+    if (h->cmp_index) {
+      if (!h->cmp_retired) h->cmp_retired = new std::vector<uint32_t*>();
+      h->cmp_retired->push_back(h->cmp_index);
+    }
+    h->cmp_index = grown;
+    h->cmp_index_cap = n_blocks;
+  }
+  return compact_launch<CMP_ACTED>(d_flags, nullptr, 0, n, h->cmp_index, d_index, d_count, h->stream);
+}
+
+int pgd_mlp_actor_critic_rows(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets, uint32_t seed,
+                              uint32_t tick, uint32_t flags, const int32_t* d_rows, const int32_t* d_count, float* d_actions, float* d_logp,
+                              float* d_value) {
+  if (!h || !d_obs || !nets || !d_rows || !d_count || !d_actions || !d_logp || (flags & ~PGD_AC_DETERMINISTIC) != 0u) return PGD_ERR_ARG;
+  if (!nets->w1 || !nets->b1 || !nets->w2 || !nets->b2 || !nets->w3 || !nets->b3) return PGD_ERR_ARG;
+  const float* vp[6] = {nets->vw1, nets->vb1, nets->vw2, nets->vb2, nets->vw3, nets->vb3};
+  int n_value = 0;
+  for (const float* p : vp) n_value += p ? 1 : 0;
+  if ((n_value != 0 && n_value != 6) || (n_value == 6 && !d_value)) return PGD_ERR_ARG;
+  if (in_dim < 4 || in_dim > 4096 || obs_stride < in_dim || nets->out_cols < AC_HEAD) return PGD_ERR_ARG;
+  if ((((uintptr_t)nets->w1 | (uintptr_t)nets->w2 | (uintptr_t)nets->b1 | (uintptr_t)nets->b2 | (uintptr_t)nets->vw1 | (uintptr_t)nets->vw2 |
+        (uintptr_t)nets->vb1 | (uintptr_t)nets->vb2) & 15u) != 0u) return PGD_ERR_ARG;  // 16-byte reads
+  const size_t lds = ac_lds_bytes(in_dim);
+  if (lds > 65536) return PGD_ERR_ARG;
+  HIPCHK(hipSetDevice(h->device));
+  EnvGroup g;
+  { int rc = env_group(h, group, g); if (rc) return rc; }
+  const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
+  if (lds > 49152 && !h->acr_attr) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_actor_critic_rows), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    h->acr_attr = true;
+  }
+  // the defined outputs of the rows that are not listed, then the listed rows (the host does not know how many: a grid for all)
+  hipLaunchKernelGGL(k_ac_clear_rows, dim3((rows + CMP_THREADS - 1) / CMP_THREADS), dim3(CMP_THREADS), 0, g.stream, row0, rows, d_actions, d_logp,
+                     n_value ? d_value : nullptr);
+  hipLaunchKernelGGL(k_mlp_actor_critic_rows, dim3((rows + MLP_ROWS - 1) / MLP_ROWS, n_value ? 2 : 1), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs,
+                     d_rows, d_count, row0, rows, obs_stride, in_dim, *nets, seed, tick, h->ac_tick,
+                     (uint32_t)h->d.cfg.env_base * (uint32_t)h->d.A, flags, d_actions, d_logp, d_value);
+  HIPCHK(hipGetLastError());
+  return PGD_OK;
+}
+
+int pgd_gae_masked(pgd_handle h, const float* d_reward, const float* d_value, const uint8_t* d_done, const uint32_t* d_flags, int T, int rows,
+                   float gamma, float lam, float* d_adv, float* d_ret, uint8_t* d_mask) {
+  if (!h || !d_reward || !d_value || !d_done || !d_flags || !d_adv || !d_ret || !d_mask || T < 1 || rows < 1) return PGD_ERR_ARG;
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_gae_masked, dim3((rows + WAVE - 1) / WAVE), dim3(WAVE), 0, h->stream, d_reward, d_value, d_done, d_flags, T, rows, gamma,
+                     lam, d_adv, d_ret, d_mask);
+  HIPCHK(hipGetLastError());
+  return PGD_OK;
+}
+
 /* ---- run-time specialisation (pgdrive_amd/jit.py builds the code object with hipcc; see include/pgdrive_hip.h) -------------- */
 int pgd_step_geometry(pgd_handle h, int32_t* out12) {
   if (!h || !out12) return PGD_ERR_ARG;
@@ -1257,7 +1359,7 @@ int pgd_destroy(pgd_handle h) {
   if (!h) return PGD_ERR_ARG;
   (void)hipStreamSynchronize(h->stream);
   if (h->jit_mod) { (void)hipModuleUnload(h->jit_mod); h->jit_mod = nullptr; h->jit_fn = nullptr; }
-  void* bufs[] = {h->lk_act, h->rowz, h->d.rec, h->d.ei, h->d.imask, h->d.env_map, h->d_ids, h->maps, h->lanes, h->roads, h->boxes, h->cell_start,
+  void* bufs[] = {h->cmp_live, h->cmp_index, h->lk_act, h->rowz, h->d.rec, h->d.ei, h->d.imask, h->d.env_map, h->d_ids, h->maps, h->lanes, h->roads, h->boxes, h->cell_start,
                   h->cell_items, h->cell_boxes, h->cell_ext, h->lane_nav, h->scen_map, h->scen, h->spawns, h->spawn_hv, h->beam, h->reset_img, h->respawn_img};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1273,6 +1375,10 @@ int pgd_destroy(pgd_handle h) {
   if (h->gstreams) {
     for (int g = 0; g < h->n_groups; ++g) { (void)hipStreamSynchronize(h->gstreams[g]); (void)hipStreamDestroy(h->gstreams[g]); }
     free(h->gstreams);
+  }
+  if (h->cmp_retired) {
+    for (uint32_t* b : *h->cmp_retired) (void)hipFree(b);
+    delete h->cmp_retired;
   }
   topdown_free(h);
   render_free(h);

@@ -38,6 +38,12 @@ _SIGS = {
                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pgd_actor_critic_tick": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pgd_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "pgd_live_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgd_rollout_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pgd_mlp_actor_critic_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ActorCritic), C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgd_gae_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
     "pgd_step_lane_keep": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 4),
     "pgd_lane_keep_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32]),
     "pgd_topdown_channels": (C.c_int, [C.POINTER(_abi.TopDownConfig)]),
@@ -227,7 +233,9 @@ class Engine:
             # The zero-row marks of a multi-agent engine name a buffer by its address: a NEW tensor may sit where a freed one sat
             # (torch's caching allocator; `out=torch.empty(...)` per step) and would inherit "known zero" marks for rows that hold
             # anything.  Tensors seen before are kept alive here (their memory cannot be handed out again); any other tensor makes
-            # the engine forget its marks first.
+            # the engine forget its marks first.  The test is by IDENTITY of the tensor object, not by address, and the
+            # rollout collectors rely on that: they pass a fresh view (`obs[t + 1]`) per step, whose address recurs in every rollout
+            # while another row was written in between -- keyed by data_ptr, stale marks would get through.
             forget_first = want_obs and self._unseen_rows(obs)
         self._follow_stream()
         if forget_first:
@@ -401,6 +409,97 @@ class Engine:
         _chk(self.L.pgd_gae(self.h, C.c_void_p(reward.data_ptr()), C.c_void_p(value.data_ptr()), C.c_void_p(done.data_ptr()), T, rows,
                             float(gamma), float(lam), C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr())), "pgd_gae")
         return adv, ret
+
+    # -- rollouts of multi-agent engines (include/pgdrive_hip.h states the predicates acted / cont / live) -------------------------
+    def live_rows(self, flags, done, rows=None, count=None, group=-1):
+        """The seat rows that hold an observation an agent will act on, from the flags and dones of the step that wrote it
+        (pgd_live_rows): `rows` int32 [N * A] receives their ascending row numbers env * A + seat, `count` int32 [1] their number
+        (both cuda; allocated when None).  Entries at and beyond the count are not written.  group >= 0: the rows of that env group, on
+        the group's stream (`flags` / `done` are still the full [N, A] tensors).  Three small launches; nothing waits for the device."""
+        t = self.torch
+        n = self.N * self.A
+        rows = t.empty((n, ), dtype=t.int32, device=self.device) if rows is None else rows
+        count = t.zeros((1, ), dtype=t.int32, device=self.device) if count is None else count
+        assert flags.is_cuda and flags.dtype == t.int32 and flags.is_contiguous() and flags.numel() == n
+        assert done.is_cuda and done.dtype == t.uint8 and done.is_contiguous() and done.numel() == n
+        assert rows.is_cuda and rows.dtype == t.int32 and rows.is_contiguous() and rows.numel() >= (n if group < 0 else n // self._n_groups())
+        assert count.is_cuda and count.dtype == t.int32 and count.numel() == 1
+        if group < 0:
+            self._follow_stream()
+        _chk(self.L.pgd_live_rows(self.h, int(group), C.c_void_p(flags.data_ptr()), C.c_void_p(done.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                  C.c_void_p(count.data_ptr())), "pgd_live_rows")
+        return rows, count
+
+    def _n_groups(self):
+        return max(1, int(getattr(self, "n_groups", 1) or 1))
+
+    def rollout_index(self, flags, index=None, count=None):
+        """The entries t * rows + r of a time-major flag tensor [T, rows...] at which an agent acted (PGD_F_REPORT), ascending, into
+        `index` int32 [T * rows], their number into `count` int32 [1] (pgd_rollout_index): a trainer draws minibatches from
+        index[:count].  The first call of a shape allocates scratch and cannot be captured in a graph: call it once before."""
+        t = self.torch
+        T = int(flags.shape[0])
+        rows = flags.numel() // max(T, 1)
+        index = t.empty((T * rows, ), dtype=t.int32, device=self.device) if index is None else index
+        count = t.zeros((1, ), dtype=t.int32, device=self.device) if count is None else count
+        assert flags.is_cuda and flags.dtype == t.int32 and flags.is_contiguous()
+        assert index.is_cuda and index.dtype == t.int32 and index.is_contiguous() and index.numel() >= T * rows
+        assert count.is_cuda and count.dtype == t.int32 and count.numel() == 1
+        self._follow_stream()
+        _chk(self.L.pgd_rollout_index(self.h, C.c_void_p(flags.data_ptr()), T, rows, C.c_void_p(index.data_ptr()), C.c_void_p(count.data_ptr())),
+             "pgd_rollout_index")
+        return index, count
+
+    def mlp_actor_critic_rows(self, policy_weights, value_weights, rows, count, out, logp, value, seed, tick, obs=None, group=-1,
+                              deterministic=False, in_dim=None):
+        """mlp_actor_critic over the rows of a list (pgd_mlp_actor_critic_rows): `rows` / `count` as live_rows returns them.  A listed
+        row gets bit for bit what mlp_actor_critic gives it; every other row of the range gets action 0, 0, logp 0, value 0 (written by
+        this call) and its observation is never used (it may hold NaN).  The other arguments as for mlp_actor_critic."""
+        t = self.torch
+        o = self.obs if obs is None else obs
+        o2 = o.view(-1, o.shape[-1])
+        n = self.N * self.A
+        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == n
+        self._check_actions(out)
+        for v in (logp, ) if value_weights is None else (logp, value):
+            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == n
+        assert rows.is_cuda and rows.dtype == t.int32 and rows.is_contiguous() and rows.numel() >= (n if group < 0 else n // self._n_groups())
+        assert count.is_cuda and count.dtype == t.int32 and count.numel() == 1
+        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
+        assert k <= o2.shape[1]
+        nets = _abi.ActorCritic()
+        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
+        nets.out_cols = int(policy_weights[4].shape[1])
+        if value_weights is not None:
+            nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
+            assert value_weights[4].shape[1] == 1
+        if group < 0:
+            self._follow_stream()
+        _chk(self.L.pgd_mlp_actor_critic_rows(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k, C.byref(nets),
+                                              int(seed) & 0xffffffff, int(tick) & 0xffffffff, _abi.AC_DETERMINISTIC if deterministic else 0,
+                                              C.c_void_p(rows.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(logp.data_ptr()), C.c_void_p(value.data_ptr()) if value_weights is not None else None),
+             "pgd_mlp_actor_critic_rows")
+        return out, logp, value
+
+    def gae_masked(self, reward, value, done, flags, gamma, lam, adv=None, ret=None, mask=None):
+        """Advantages and returns of a multi-agent rollout (pgd_gae_masked): as gae(), with the step flags [T, rows...] (int32) deciding
+        where an agent acted and whether it continues; rows that did not act get adv = ret = 0 whatever their reward and value hold.
+        Returns (adv, ret, mask): mask uint8 of reward's shape, 1 where an agent acted."""
+        t = self.torch
+        T = int(reward.shape[0])
+        rows = reward.numel() // max(T, 1)
+        adv = t.empty_like(reward) if adv is None else adv
+        ret = t.empty_like(reward) if ret is None else ret
+        mask = t.empty(reward.shape, dtype=t.uint8, device=reward.device) if mask is None else mask
+        for v, dt, n in ((reward, t.float32, T * rows), (value, t.float32, (T + 1) * rows), (done, t.uint8, T * rows), (flags, t.int32, T * rows),
+                         (adv, t.float32, T * rows), (ret, t.float32, T * rows), (mask, t.uint8, T * rows)):
+            assert v.is_cuda and v.dtype == dt and v.is_contiguous() and v.numel() == n
+        self._follow_stream()
+        _chk(self.L.pgd_gae_masked(self.h, C.c_void_p(reward.data_ptr()), C.c_void_p(value.data_ptr()), C.c_void_p(done.data_ptr()),
+                                   C.c_void_p(flags.data_ptr()), T, rows, float(gamma), float(lam), C.c_void_p(adv.data_ptr()),
+                                   C.c_void_p(ret.data_ptr()), C.c_void_p(mask.data_ptr())), "pgd_gae_masked")
+        return adv, ret, mask
 
     def step_lane_keep(self, tick, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):
         """One closed-loop step under the scripted lane-keeping policy (pgd_step_lane_keep): the policy reads the engine's own

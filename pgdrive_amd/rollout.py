@@ -23,7 +23,11 @@ to a counter in device memory that collect() advances by T on the stream, so a c
 replay and equals the eager call bit for bit.
 
 A done ends the episode for GAE, whatever ended it: there is no bootstrap through a horizon truncation from the terminal observation.
+
+Multi-agent engines: MultiAgentRolloutCollector, below -- the same layout and carry with a seat axis, the networks over the rows of live
+seats only, GAE per agent and not per seat, and the index of the transitions a trainer may use.
 """
+import numpy as np
 
 
 class RolloutCollector:
@@ -32,7 +36,7 @@ class RolloutCollector:
         if eng.A != 1:
             raise NotImplementedError(
                 "RolloutCollector serves single-agent engines: with %d agent seats per env the rows of seats that are not due need a mask "
-                "that is not defined yet -- call Engine.mlp_actor_critic and Engine.gae directly (rows = N * A)" % eng.A)
+                "that this class does not know -- use MultiAgentRolloutCollector" % eng.A)
         if int(T) < 1:
             raise ValueError("RolloutCollector: T = %r" % (T, ))
         t = eng.torch
@@ -90,5 +94,111 @@ class RolloutCollector:
             self._evaluate(t + 1)
         eng.actor_critic_tick(None)
         eng.gae(self.rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
+        self._tick.add_(T)
+        return self.batch
+
+
+class MultiAgentRolloutCollector:
+    """RolloutCollector for multi-agent engines (A seats per env; include/pgdrive_hip.h states acted / cont / live):
+
+        col = MultiAgentRolloutCollector(env, policy_weights, value_weights, T=128)
+        batch = col.collect()
+        idx = batch["index"][:int(batch["count"])]      # the (t, env, seat) transitions of agents, flattened; minibatches come from here
+
+    Per step t: Engine.step(actions[t]) writes obs[t + 1], rewards[t], dones[t], flags[t]; Engine.live_rows lists the seats whose row
+    t + 1 holds an observation an agent will act on; Engine.mlp_actor_critic_rows evaluates the networks on those rows and writes row
+    t + 1 of actions, logp and values (zeros in every other seat -- the step ignores the action of a seat without an agent).  Behind the T
+    steps: Engine.gae_masked (an agent's episode ends at its done or at an env-wide restart; a seat's next agent starts afresh) and
+    Engine.rollout_index.  Row T is carried into row 0 of the next rollout and the tick counter advances by T, as in RolloutCollector;
+    nothing in collect() waits for the device.
+
+    prime() takes the live seats of the FIRST observation from the engine's state (status == ACTIVE): one host read, and the first call
+    of rollout_index allocates its scratch -- so prime() is called (by the first collect(), or explicitly) BEFORE collect() is captured
+    in a HIP graph.
+
+    The step is handed another observation row at every step, so the engine's marks of seats whose zero row is already in place
+    (pgd_forget_rows) never carry over: every step of a rollout writes the zero row of every seat that is not due."""
+    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0):
+        eng = getattr(env_or_engine, "engine", env_or_engine)
+        if eng.A == 1:
+            raise NotImplementedError("MultiAgentRolloutCollector serves multi-agent engines: this one has a single agent seat per env and "
+                                      "never reports PGD_F_REPORT -- use RolloutCollector")
+        if int(T) < 1:
+            raise ValueError("MultiAgentRolloutCollector: T = %r" % (T, ))
+        t = eng.torch
+        self.engine, self.T, self.gamma, self.lam, self.seed = eng, int(T), float(gamma), float(lam), int(seed)
+        T, N, A, D, dev = self.T, eng.N, eng.A, eng.D, eng.device
+        f32 = dict(dtype=t.float32, device=dev)
+        i32 = dict(dtype=t.int32, device=dev)
+        self._obs = t.zeros((T + 1, N, A, D), **f32)
+        self._actions = t.zeros((T + 1, N, A, 2), **f32)
+        self._logp = t.zeros((T + 1, N, A), **f32)
+        self.values = t.zeros((T + 1, N, A), **f32)
+        self.rewards = t.zeros((T, N, A), **f32)
+        self.dones = t.zeros((T, N, A), dtype=t.uint8, device=dev)
+        self.flags = t.zeros((T, N, A), **i32)
+        self.advantages = t.zeros((T, N, A), **f32)
+        self.returns = t.zeros((T, N, A), **f32)
+        self.mask = t.zeros((T, N, A), dtype=t.uint8, device=dev)
+        self.index = t.zeros((T * N * A, ), **i32)
+        self.count = t.zeros((1, ), **i32)
+        self._rows = t.zeros((N * A, ), **i32)    # the live rows of the observation just written
+        self._n_rows = t.zeros((1, ), **i32)
+        self._tick = t.zeros((1, ), **i32)  # evaluations before this rollout (modulo 2^32)
+        self._carry = (self._obs, self._actions, self._logp, self.values)
+        self._primed = False
+        self.set_weights(policy_weights, value_weights)
+        self.batch = dict(obs=self._obs[:T], actions=self._actions[:T], logp=self._logp[:T], values=self.values, rewards=self.rewards,
+                          dones=self.dones, flags=self.flags, advantages=self.advantages, returns=self.returns, mask=self.mask,
+                          index=self.index, count=self.count)
+
+    def set_weights(self, policy_weights, value_weights):
+        """The networks of the rollouts from now on (between two collect() calls): tuples as for Engine.mlp_actor_critic."""
+        self.policy_weights, self.value_weights = tuple(policy_weights), tuple(value_weights)
+
+    def _evaluate(self, row):
+        self.engine.mlp_actor_critic_rows(self.policy_weights, self.value_weights, self._rows, self._n_rows, self._actions[row], self._logp[row],
+                                          self.values[row], self.seed, row, obs=self._obs[row])
+
+    def prime(self):
+        """Take the engine's present observation (what reset wrote into Engine.obs) as the start of the first rollout; its live seats
+        are those whose agent is ACTIVE in the engine's state (a host read).  collect() calls it once by itself; call it before
+        capturing collect() in a graph."""
+        from . import _abi
+        eng, T = self.engine, self.T
+        t = eng.torch
+        eng.sync()
+        _, si, _ = eng.get_state()
+        live = np.flatnonzero(si[_abi.SI["STATUS"], :, :eng.A].reshape(-1) == _abi.ST_ACTIVE).astype(np.int32)
+        self._rows[:len(live)].copy_(t.from_numpy(live))
+        self._n_rows.fill_(len(live))
+        self._obs[T].copy_(eng.obs.view(eng.N, eng.A, eng.D))
+        self._tick.sub_(T)  # (this evaluation is number 0: row T, counter -T)
+        eng.actor_critic_tick(self._tick)
+        self._evaluate(T)
+        eng.actor_critic_tick(None)
+        self._tick.add_(T)
+        eng.rollout_index(self.flags, index=self.index, count=self.count)  # (its scratch, allocated outside any capture; flags are zero)
+        self._primed = True
+
+    def collect(self):
+        """T steps.  Returns the dict of the collector's tensors (the same objects every time, valid until the next call):
+        obs [T, N, A, D], actions [T, N, A, 2] (as sampled; the step clips), logp [T, N, A], values [T + 1, N, A], rewards, dones (uint8),
+        flags, advantages, returns [T, N, A] -- as RolloutCollector's with a seat axis -- and mask [T, N, A] uint8 (an agent acted),
+        index [T * N * A] int32 (the flattened positions where mask is 1, ascending; valid up to count), count [1] int32."""
+        eng, T = self.engine, self.T
+        if not self._primed:
+            self.prime()
+        for buf in self._carry:
+            buf[0].copy_(buf[T])
+        eng.actor_critic_tick(self._tick)  # (the engine's launches add the counter only while the collector is at work)
+        for t in range(T):
+            eng.step(self._actions[t], out=(self._obs[t + 1], self.rewards[t], self.dones[t], self.flags[t]))
+            eng.live_rows(self.flags[t], self.dones[t], rows=self._rows, count=self._n_rows)
+            self._evaluate(t + 1)
+        eng.actor_critic_tick(None)
+        eng.gae_masked(self.rewards, self.values, self.dones, self.flags, self.gamma, self.lam, adv=self.advantages, ret=self.returns,
+                       mask=self.mask)
+        eng.rollout_index(self.flags, index=self.index, count=self.count)
         self._tick.add_(T)
         return self.batch
