@@ -495,6 +495,77 @@ int pgd_mlp_actor_critic_rows(pgd_handle h, int group, const float* d_obs, int o
  * T >= 1, rows >= 1 (PGD_ERR_ARG).  Asynchronous on the engine's stream; may be captured in a HIP graph. */
 int pgd_gae_masked(pgd_handle h, const float* d_reward, const float* d_value /*[T+1][rows]*/, const uint8_t* d_done, const uint32_t* d_flags,
                    int T, int rows, float gamma, float lam, float* d_adv, float* d_ret, uint8_t* d_mask);
+/* ---- The PPO update behind a rollout: loss, the gradients of both networks, Adam ------------------------------------------------------
+ * (No reference counterpart: the reference hands its arrays to an RL library, which runs autograd over the two networks of
+ * pgdrive/examples/ppo_expert/numpy_expert.py:25-78 and an optimiser step, all as framework ops.)
+ * The networks are pgd_mlp_actor_critic's as they stand: fp32, row-major [in][out], hidden 256, tanh; actor head columns 0..3 = mean0,
+ * mean1, log_std0, log_std1 (columns at or beyond 4 are never read); a critic head of one column; all six critic pointers null = no
+ * critic; in_dim 4 .. 416, w1, b1, w2, b2 of each network 16-byte aligned, obs_stride >= in_dim, out_cols >= 4 (PGD_ERR_ARG otherwise).
+ *
+ * pgd_ppo_grad: one minibatch in, loss statistics and the gradient of every weight out.  The minibatch is the list positions
+ *   q_i = start + i * stride,  i = 0 .. rows - 1;   position i is LIVE iff q_i < count;   its rollout row is p_i = index[q_i]
+ * with count = *batch->count, read by the kernels from device memory and held within [0, n_list] (null: n_list), and index null: p_i =
+ * q_i.  n = the number of live positions.  The host never reads the count: the grids cover `rows`, and a tile of 16 positions with no live
+ * one ends before it reads a weight.  stride = n_mb, start = j: the n_mb minibatches partition the list with no shuffle tensor;
+ * stride = 1 and a shuffled index: the usual random minibatch.  An index entry is a row of the rollout arrays, [0, n_rows): one that is
+ * not is a caller's error; it is held within the arrays, never followed outside them.
+ * Per live row p the kernels read obs[p] (the first in_dim floats of a row of obs_stride), action[p][0..1], logp_old[p], adv[p] and
+ * (with a critic) ret[p], evaluate both networks -- mean, ls (log_std), v -- and form
+ *   A     = (adv - s[0]) * s[1], s = batch->adv_stats (two floats in device memory, as pgd_adv_stats writes them); null: A = adv
+ *   z_k   = (a_k - mean_k) exp(-ls_k);   logp = -0.5 (z0^2 + z1^2) - ls0 - ls1 - log 2 pi;   r = exp(logp - logp_old)
+ *   L_pi  = -(1/n) sum min(r A, clamp(r, 1 - clip, 1 + clip) A);   the gradient flows through a row iff r A <= clamp(r) A: then
+ *           dL/dlogp = -A r / n, else 0;   dlogp/dmean_k = z_k exp(-ls_k),   dlogp/dls_k = z_k^2 - 1
+ *   L_v   = (1/n) sum 0.5 (v - ret)^2 (no value clipping);   dL/dv = vf_coef (v - ret) / n
+ *   H     = ls0 + ls1 + log(2 pi e);   L = L_pi + vf_coef L_v - ent_coef mean(H): the entropy term adds -ent_coef / n to dL/dls_k
+ * and the backward pass through the two tanh layers of each network.  The gradients dW1, db1, dW2, db2, dW3, db3 of actor and critic
+ * are WRITTEN (not accumulated) into the buffers of `grads`, which have the weights' own shapes; head columns at or beyond 4 are
+ * written as zero.  n = 0: every gradient and statistic is zero (no NaN, no division by zero).  Null critic: the critic's gradient
+ * buffers are not touched (they may be null) and L_v = 0.
+ * d_stats, 8 floats: 0 n; 1 L_pi; 2 L_v; 3 mean H; 4 mean (logp_old - logp); 5 the share of live rows whose gradient is cut; 6 mean r;
+ * 7 zero.
+ * Rows that are not listed, list entries at or beyond the count, positions that are not live and observation columns at or beyond
+ * in_dim may hold anything, NaN included: they reach no output (they are selected away, never multiplied by zero).
+ * Deterministic: the same inputs give the same bytes -- no atomics; a sum over the minibatch's rows is taken by one owner in a fixed
+ * order (weight gradients: rows in order within partitions of 1024, the partitions in order).  Arithmetic: fp32 -- the 256-wide
+ * products (both forward layers, dZ2 W2^T, X^T dZ1, H1^T dZ2) on the f32 matrix cores --, except the per-row loss terms and
+ * dL/d(mean, log_std, v) and the factor 1 / n, which one lane per row forms in double from the fp32 head outputs and rounds to fp32 once.
+ * Scratch is the caller's: d_work, 16-byte aligned, work_bytes >= pgd_ppo_work_bytes(in_dim, rows, has_critic) (PGD_ERR_ARG below
+ * it; the function returns 0 for an in_dim or rows the call refuses; rows 1 .. PGD_PPO_ROWS_MAX).  Nothing is allocated inside the
+ * call: five launches (six with out_cols > 4), asynchronous on the engine's stream, capturable in a HIP graph from the first call. */
+typedef struct pgd_ppo_batch {
+  const float *obs, *action, *logp_old, *adv, *ret;   /* the rollout's arrays by row: [n_rows][obs_stride], [n_rows][2], [n_rows] x 3 */
+  const float* adv_stats;                             /* two device floats (mean, 1 / (std + 1e-8)), or null */
+  const int32_t* index;                               /* [n_list] rows, or null: position = row */
+  const int32_t* count;                               /* device int32, or null: n_list */
+  int32_t obs_stride, in_dim, n_rows, n_list, start, stride, rows;
+} pgd_ppo_batch;
+typedef struct pgd_ppo_hyper { float clip, vf_coef, ent_coef; } pgd_ppo_hyper;
+typedef struct pgd_ppo_grads {                        /* device buffers of the weights' own shapes, written by pgd_ppo_grad */
+  float *w1, *b1, *w2, *b2, *w3, *b3;
+  float *vw1, *vb1, *vw2, *vb2, *vw3, *vb3;           /* untouched (and may be null) without a critic */
+} pgd_ppo_grads;
+#define PGD_PPO_ROWS_MAX 16777216
+size_t pgd_ppo_work_bytes(int in_dim, int rows, int has_critic);
+int pgd_ppo_grad(pgd_handle h, const pgd_actor_critic* nets, const pgd_ppo_batch* batch, const pgd_ppo_hyper* hyper,
+                 const pgd_ppo_grads* grads, float* d_stats /*[8]*/, void* d_work, size_t work_bytes);
+/* Population mean and 1 / (std + 1e-8) of adv over the live entries of a list -- adv[index[q]] (index null: adv[q]) for q < count, the
+ * count as for pgd_ppo_grad -- into two device floats.  One workgroup, a fixed summation order: deterministic.  n = 0: (0, 1).
+ * Entries that are not listed may hold NaN.  The call is not told how long d_adv is: every index entry below the count must be a valid
+ * position of it (the caller's contract; pgd_rollout_index's entries are) -- unlike pgd_ppo_grad, which knows n_rows, it cannot hold an entry
+ * within the array.  The final quotients are formed in double.  Asynchronous on the engine's stream; capturable. */
+int pgd_adv_stats(pgd_handle h, const float* d_adv, const int32_t* d_index, const int32_t* d_count, int n_list, float* d_out /*[2]*/);
+/* One Adam step on a flat parameter buffer of n_elem floats; d_grad, d_m, d_v of the same length.
+ *   max_grad_norm > 0:  g = grad * min(1, max_grad_norm / (|grad| + 1e-6)), |grad| over all n_elem (a deterministic reduction); else g = grad
+ *   m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g^2;   p -= lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps)
+ * The step number t lives in DEVICE memory: d_step, four 32-bit words, 4-byte aligned, owned by the caller and zero before the first
+ * step.  Word 0 is the int32 count of steps taken; the call advances it by one when its kernels RUN and uses the new value, so a
+ * captured call replayed takes step t + 1, not the captured one (the reasoning of pgd_actor_critic_tick).  Words 1..3 are the call's
+ * record -- the clipping scale and the two bias corrections as floats --, written with the counter by a one-workgroup launch and read by
+ * the elementwise launch behind it: no kernel reads the counter while another workgroup of its launch writes it.  m and v are updated in
+ * fp32; the record and the quotient of the parameter step are formed in double and rounded to fp32 once.  0 <= beta < 1,
+ * n_elem >= 1 (PGD_ERR_ARG).  Two launches, asynchronous on the engine's stream; capturable. */
+int pgd_adam(pgd_handle h, float* d_param, const float* d_grad, float* d_m, float* d_v, int n_elem, int32_t* d_step /*[4]*/, float lr,
+             float beta1, float beta2, float eps, float max_grad_norm);
 /* Multi-agent engines remember, per env, which rows of the LAST observation buffer they were given already hold the zeros of a seat
  * that is not due (identified by the buffer's address and row stride), and do not write them again.  A caller that hands pgd_step
  * a buffer whose address a FORMER buffer had (a caching allocator re-using a freed block: torch.empty per step) calls this first:

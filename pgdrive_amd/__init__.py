@@ -27,6 +27,9 @@ def __getattr__(name):
     if name == "RolloutCollector":
         from .rollout import RolloutCollector
         return RolloutCollector
+    if name == "PPOLearner":
+        from .learner import PPOLearner
+        return PPOLearner
     if name == "Engine":
         from .engine import Engine
         return Engine

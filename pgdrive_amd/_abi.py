@@ -50,6 +50,27 @@ class ActorCritic(C.Structure):
 
 AC_DETERMINISTIC = 1
 
+
+class PPOBatch(C.Structure):
+    """pgd_ppo_batch: the rollout's arrays by row, the row list (index / count null: position = row, n_list entries) and the minibatch
+    (start, stride, rows)."""
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "action", "logp_old", "adv", "ret", "adv_stats", "index", "count")] + \
+        [(n, C.c_int32) for n in ("obs_stride", "in_dim", "n_rows", "n_list", "start", "stride", "rows")]
+
+
+class PPOHyper(C.Structure):
+    """pgd_ppo_hyper"""
+    _fields_ = [("clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float)]
+
+
+class PPOGrads(C.Structure):
+    """pgd_ppo_grads: gradient buffers of the weights' own shapes (the critic's six None without a critic)."""
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "vw1", "vb1", "vw2", "vb2", "vw3", "vb3")]
+
+
+PPO_ROWS_MAX = 16777216
+PPO_STATS = ("n", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "ratio", "reserved")  # d_stats of pgd_ppo_grad
+
 # the tensors of Engine.enable_step_info by pgd_step_info field: (dtype name, key in Engine.step_info)
 STEP_INFO_FIELDS = dict(
     velocity="float32", steering="float32", acceleration="float32", episode_energy="float32", step_energy="float32",

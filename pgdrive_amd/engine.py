@@ -44,6 +44,12 @@ _SIGS = {
                                             C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pgd_gae_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
+    "pgd_ppo_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "pgd_ppo_grad": (C.c_int, [C.c_void_p, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.PPOBatch), C.POINTER(_abi.PPOHyper), C.POINTER(_abi.PPOGrads),
+                               C.c_void_p, C.c_void_p, C.c_size_t]),
+    "pgd_adv_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pgd_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                           C.c_float, C.c_float]),
     "pgd_step_lane_keep": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 4),
     "pgd_lane_keep_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32]),
     "pgd_topdown_channels": (C.c_int, [C.POINTER(_abi.TopDownConfig)]),
@@ -500,6 +506,97 @@ class Engine:
                                    C.c_void_p(flags.data_ptr()), T, rows, float(gamma), float(lam), C.c_void_p(adv.data_ptr()),
                                    C.c_void_p(ret.data_ptr()), C.c_void_p(mask.data_ptr())), "pgd_gae_masked")
         return adv, ret, mask
+
+    # -- the PPO update behind a rollout (include/pgdrive_hip.h states the formulas) ---------------------------------------------
+    def ppo_work_bytes(self, in_dim, rows, has_critic=True):
+        """The scratch pgd_ppo_grad needs for minibatches of up to `rows` positions (pgd_ppo_work_bytes); 0: the call would refuse them."""
+        return int(self.L.pgd_ppo_work_bytes(int(in_dim), int(rows), int(bool(has_critic))))
+
+    def _list_args(self, index, count, n_list):
+        """A row list checked: `index` int32 cuda [>= n_list] or None, `count` int32 cuda [1] or None -> their pointers."""
+        t = self.torch
+        if index is not None:
+            assert index.is_cuda and index.dtype == t.int32 and index.is_contiguous() and index.numel() >= n_list
+        if count is not None:
+            assert count.is_cuda and count.dtype == t.int32 and count.numel() == 1
+        return (C.c_void_p(index.data_ptr()) if index is not None else None, C.c_void_p(count.data_ptr()) if count is not None else None)
+
+    def adv_stats(self, adv, out=None, index=None, count=None, n_list=None):
+        """Population mean and 1 / (std + 1e-8) of the advantages over a row list (pgd_adv_stats) -> `out`, float32 cuda [2].  The list:
+        adv.view(-1)[index[q]] for q < count (`index` None: entry q itself; `count` None: n_list; n_list None: every entry of `adv`, or of
+        `index`); `count` is read on the device.  No entries: (0, 1)."""
+        t = self.torch
+        assert adv.is_cuda and adv.dtype == t.float32 and adv.is_contiguous()
+        n_list = int((index if index is not None else adv).numel() if n_list is None else n_list)
+        assert 0 <= n_list and (index is not None or n_list <= adv.numel())
+        out = t.empty((2, ), dtype=t.float32, device=self.device) if out is None else out
+        assert out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and out.numel() == 2
+        ip, cp = self._list_args(index, count, n_list)
+        self._follow_stream()
+        _chk(self.L.pgd_adv_stats(self.h, C.c_void_p(adv.data_ptr()), ip, cp, n_list, C.c_void_p(out.data_ptr())), "pgd_adv_stats")
+        return out
+
+    def ppo_grad(self, policy_weights, value_weights, policy_grads, value_grads, obs, actions, logp_old, adv, ret, stats, work, start=0, stride=1,
+                 rows=None, index=None, count=None, n_list=None, adv_stats=None, clip=0.2, vf_coef=0.5, ent_coef=0.0, in_dim=None):
+        """Loss statistics and the gradient of every weight for one minibatch (pgd_ppo_grad).  `obs` [..., D], `actions` [..., 2],
+        `logp_old`, `adv`, `ret` [...]: the rollout's tensors, float32 cuda, flattened to rows.  The minibatch: list positions start + i
+        stride, i < rows, live below `count` (int32 cuda [1], read on the device; None: n_list; n_list None: every row, or every entry
+        of `index`); position q is row index[q] (`index` None: q).  `adv_stats`: the two floats of adv_stats(), or None.  Gradients are
+        written into `policy_grads` / `value_grads`, tuples of the weights' shapes (value_weights None: no critic, value_grads ignored);
+        `stats` float32 cuda [8] (_abi.PPO_STATS); `work` a cuda tensor of at least ppo_work_bytes(in_dim, rows) bytes.  Asynchronous."""
+        t = self.torch
+        o2 = obs.view(-1, obs.shape[-1])
+        n_rows = int(o2.shape[0])
+        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1
+        assert actions.is_cuda and actions.dtype == t.float32 and actions.is_contiguous() and actions.numel() == 2 * n_rows
+        for v in (logp_old, adv) if value_weights is None else (logp_old, adv, ret):
+            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == n_rows
+        n_list = int((index.numel() if index is not None else n_rows) if n_list is None else n_list)
+        assert 0 <= n_list and (index is not None or n_list <= n_rows)
+        rows = int(max(1, -(-(n_list - int(start)) // int(stride))) if rows is None else rows)
+        assert int(start) >= 0 and int(stride) >= 1 and 1 <= rows <= _abi.PPO_ROWS_MAX
+        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
+        assert k <= o2.shape[1]
+        assert stats.is_cuda and stats.dtype == t.float32 and stats.is_contiguous() and stats.numel() == 8
+        need = self.ppo_work_bytes(k, rows, value_weights is not None)
+        assert need > 0 and work.is_cuda and work.is_contiguous() and work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
+        if adv_stats is not None:
+            assert adv_stats.is_cuda and adv_stats.dtype == t.float32 and adv_stats.is_contiguous() and adv_stats.numel() == 2
+        nets, grads = _abi.ActorCritic(), _abi.PPOGrads()
+        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
+        nets.out_cols = int(policy_weights[4].shape[1])
+        grads.w1, grads.b1, grads.w2, grads.b2, grads.w3, grads.b3 = self._network(policy_grads, k, 4)
+        assert all(g.shape == w.shape for g, w in zip(policy_grads, policy_weights))
+        if value_weights is not None:
+            nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
+            grads.vw1, grads.vb1, grads.vw2, grads.vb2, grads.vw3, grads.vb3 = self._network(value_grads, k, 1)
+            assert value_weights[4].shape[1] == 1 and value_grads[4].shape[1] == 1
+        b = _abi.PPOBatch()
+        b.obs, b.action, b.logp_old, b.adv = o2.data_ptr(), actions.data_ptr(), logp_old.data_ptr(), adv.data_ptr()
+        b.ret = ret.data_ptr() if value_weights is not None else None
+        b.adv_stats = adv_stats.data_ptr() if adv_stats is not None else None
+        ip, cp = self._list_args(index, count, n_list)
+        b.index, b.count = ip, cp
+        b.obs_stride, b.in_dim, b.n_rows, b.n_list, b.start, b.stride, b.rows = int(o2.stride(0)), k, n_rows, n_list, int(start), int(stride), rows
+        hp = _abi.PPOHyper(float(clip), float(vf_coef), float(ent_coef))
+        self._follow_stream()
+        _chk(self.L.pgd_ppo_grad(self.h, C.byref(nets), C.byref(b), C.byref(hp), C.byref(grads), C.c_void_p(stats.data_ptr()),
+                                 C.c_void_p(work.data_ptr()), work.numel() * work.element_size()), "pgd_ppo_grad")
+        return stats
+
+    def adam(self, param, grad, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0):
+        """One Adam step on the flat float32 cuda buffer `param` (pgd_adam), `grad`, `m`, `v` of its length; max_grad_norm > 0 clips by the
+        global gradient norm first.  `step`: int32 cuda [4], zero before the first step -- entry 0 counts the steps ON THE DEVICE (a
+        replayed graph takes the next step), entries 1..3 are the call's record.  Asynchronous."""
+        t = self.torch
+        n = int(param.numel())
+        for x in (param, grad, m, v):
+            assert x.is_cuda and x.dtype == t.float32 and x.is_contiguous() and x.numel() == n
+        assert n >= 1 and step.is_cuda and step.dtype == t.int32 and step.is_contiguous() and step.numel() == 4
+        self._follow_stream()
+        _chk(self.L.pgd_adam(self.h, C.c_void_p(param.data_ptr()), C.c_void_p(grad.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), n,
+                             C.c_void_p(step.data_ptr()), float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm)), "pgd_adam")
+        return param
 
     def step_lane_keep(self, tick, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):
         """One closed-loop step under the scripted lane-keeping policy (pgd_step_lane_keep): the policy reads the engine's own

@@ -1,0 +1,112 @@
+"""The PPO update behind an on-device rollout: `collect() -> update()` is a complete training iteration made of the engine's own launches.
+
+    col = RolloutCollector(env, policy_weights, value_weights, T=128)      # or MultiAgentRolloutCollector
+    learner = PPOLearner(col, lr=3e-4)
+    while training:
+        batch = col.collect()
+        stats = learner.update(batch)       # [epochs * minibatches, 8] on the device: _abi.PPO_STATS
+
+What a trainer otherwise writes as framework code: an autograd pass over two 3-layer networks, an optimiser step, a gather of minibatch
+rows out of the time-major rollout and -- for the multi-agent collector -- a host read of batch["count"] before a minibatch can be sized.
+Here: Engine.adv_stats once, then Engine.ppo_grad + Engine.adam for every epoch and minibatch.  Nothing in update() waits for the device
+or reads a device scalar, so one `collect(); update()` can be captured in a HIP graph and replayed: the Adam step number and the tick of
+the rollout's noise live in device memory and advance with every replay.
+
+Minibatch j of n takes the list positions j, j + n, j + 2 n, ...: the n minibatches partition the rollout's transitions whatever their
+number is, with no shuffle tensor.  For RolloutCollector the list is every (t, env) row; for MultiAgentRolloutCollector it is
+batch["index"] / batch["count"] as they lie on the device (the transitions at which an agent acted).
+
+The learner owns ONE flat parameter buffer; the twelve weight tensors are views into it (every offset a multiple of 4 floats: the
+16-byte alignment the network kernels demand).  It hands the views to collector.set_weights once; updates are in place, so the collector
+sees them without another call.  As rollout.py documents, the carried row T of a rollout was evaluated with the weights of the rollout
+it was observed in and is not evaluated again.
+"""
+
+NAMES = ("w1", "b1", "w2", "b2", "w3", "b3")
+H = 256
+
+
+def flat_layout(in_dim, out_cols, has_critic=True):
+    """[(name, shape, offset)] of the weight tensors in the flat buffer, and its length in floats; offsets are multiples of 4."""
+    shapes = [("w1", (in_dim, H)), ("b1", (H, )), ("w2", (H, H)), ("b2", (H, )), ("w3", (H, out_cols)), ("b3", (out_cols, ))]
+    if has_critic:
+        shapes += [("vw1", (in_dim, H)), ("vb1", (H, )), ("vw2", (H, H)), ("vb2", (H, )), ("vw3", (H, 1)), ("vb3", (1, ))]
+    out, o = [], 0
+    for name, shape in shapes:
+        n = 1
+        for d in shape:
+            n *= d
+        out.append((name, shape, o))
+        o += (n + 3) & ~3
+    return out, o
+
+
+def minibatch_plan(n_list, minibatches):
+    """[(start, stride, rows)] of the strided minibatches over a list of up to n_list entries: minibatch j takes the positions j + i *
+    minibatches, i < rows, of which those below the list's count are live."""
+    n_mb = int(minibatches)
+    return [(j, n_mb, max(1, -(-(int(n_list) - j) // n_mb))) for j in range(n_mb)]
+
+
+def live_positions(start, stride, rows, count):
+    """The live list positions of a minibatch (what the kernels do with the count they read on the device), in plain Python."""
+    return [start + i * stride for i in range(rows) if start + i * stride < count]
+
+
+class PPOLearner:
+    def __init__(self, collector, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.0, epochs=4, minibatches=4, max_grad_norm=0.5, betas=(0.9, 0.999),
+                 eps=1e-5, normalise_advantages=True):
+        eng = collector.engine
+        t = eng.torch
+        if int(epochs) < 1 or int(minibatches) < 1:
+            raise ValueError("PPOLearner: epochs = %r, minibatches = %r" % (epochs, minibatches))
+        self.collector, self.engine = collector, eng
+        self.lr, self.clip, self.vf_coef, self.ent_coef = float(lr), float(clip), float(vf_coef), float(ent_coef)
+        self.epochs, self.minibatches, self.max_grad_norm = int(epochs), int(minibatches), float(max_grad_norm)
+        self.betas, self.eps, self.normalise_advantages = (float(betas[0]), float(betas[1])), float(eps), bool(normalise_advantages)
+        pw, vw = collector.policy_weights, collector.value_weights
+        self.in_dim, self.out_cols = int(pw[0].shape[0]), int(pw[4].shape[1])
+        layout, total = flat_layout(self.in_dim, self.out_cols)
+        f32 = dict(dtype=t.float32, device=eng.device)
+        self.params, self.grads = t.zeros((total, ), **f32), t.zeros((total, ), **f32)
+        self.m, self.v = t.zeros((total, ), **f32), t.zeros((total, ), **f32)
+        self.step = t.zeros((4, ), dtype=t.int32, device=eng.device)  # pgd_adam's counter and record
+
+        def views(flat):
+            return tuple(flat[o:o + int(t.Size(shape).numel())].view(shape) for _, shape, o in layout)
+
+        wv, gv = views(self.params), views(self.grads)
+        for dst, src in zip(wv, tuple(pw) + tuple(vw)):
+            dst.copy_(src.view(dst.shape))
+        self.policy_weights, self.value_weights = wv[:6], wv[6:]
+        self.policy_grads, self.value_grads = gv[:6], gv[6:]
+        collector.set_weights(self.policy_weights, self.value_weights)
+        self.n_list = int(collector.rewards.numel())  # T * N (* A): every row of the rollout
+        self.plan = minibatch_plan(self.n_list, self.minibatches)
+        need = eng.ppo_work_bytes(self.in_dim, max(rows for _, _, rows in self.plan), True)
+        if need == 0:
+            raise ValueError("PPOLearner: the networks' input width %d is outside what pgd_ppo_grad accepts" % self.in_dim)
+        self.work = t.empty(((need + 3) // 4, ), **f32)
+        self.adv_stats = t.zeros((2, ), **f32)
+        self.stats = t.zeros((self.epochs * self.minibatches, 8), **f32)
+
+    def update(self, batch):
+        """epochs x minibatches gradient steps on the rollout `batch` (what collector.collect() returned).  Returns the statistics
+        tensor [epochs * minibatches, 8] (the same object every time).  Asynchronous: nothing here waits for the device."""
+        eng = self.engine
+        index, count = batch.get("index"), batch.get("count")  # (the multi-agent collector's list; None: every row)
+        adv = batch["advantages"]
+        norm = None
+        if self.normalise_advantages:
+            norm = eng.adv_stats(adv, out=self.adv_stats, index=index, count=count, n_list=self.n_list)
+        k = 0
+        for _ in range(self.epochs):
+            for start, stride, rows in self.plan:
+                eng.ppo_grad(self.policy_weights, self.value_weights, self.policy_grads, self.value_grads, batch["obs"], batch["actions"],
+                             batch["logp"], adv, batch["returns"], self.stats[k], self.work, start=start, stride=stride, rows=rows, index=index,
+                             count=count, n_list=self.n_list, adv_stats=norm, clip=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
+                             in_dim=self.in_dim)
+                eng.adam(self.params, self.grads, self.m, self.v, self.step, self.lr, betas=self.betas, eps=self.eps,
+                         max_grad_norm=self.max_grad_norm)
+                k += 1
+        return self.stats
