@@ -9,6 +9,10 @@
 #ifndef PGD_RELMASK_MIN
 #define PGD_RELMASK_MIN 3  // bodies in some vehicle's broad phase from which the related-lane pass of find_front_back runs
 #endif
+#ifndef PGD_BROAD_BATCH
+#define PGD_BROAD_BATCH 6  // rounds of the IDM broad phase whose LDS reads are issued as one batch (the default configuration has six
+                           // rounds; batches of three measured 0.4 % behind on the metric's row, profiles/xlane_notes.md)
+#endif
 struct Fbo {
   int front[3], back[3];
   float fd[3], bd[3];
@@ -70,6 +74,8 @@ DEV void find_front_back(const MapView& mv, const Grp& g, const Snap& S, int bas
     }
 #endif
     // only the vehicles inside the broad phase, in slot order (ties keep the first one like the reference's loop)
+    // (the four LDS reads of a body issued one body ahead, before the selects of the current one, cost eight registers and made
+    // every row SLOWER: metric 17.07 -> 17.13 us, respawn 24.10 -> 24.28, profiles/xlane_notes.md)
     for (unsigned long long m = rel_objs; m != 0ull; m &= m - 1ull) {
       const int o = __builtin_ctzll(m);
       const int ol = S.lane[base + o];
@@ -167,16 +173,29 @@ DEV void idm_act(const PgdDev& d, const MapView& mv, const Grp& g, const pgd_spa
 #ifdef PGD_EXITAT
   if (!PGD_DBG_SKIP(0))
 #endif
-  // a trip count that does not depend on the sub-lane (a constant in the kernels specialised for a default configuration): the
-  // rounds unroll, their LDS reads go out together and the distance tests of different slots overlap
+  // a trip count that does not depend on the sub-lane (a constant in the kernels specialised for a default configuration).  The
+  // rounds go in batches of PGD_BROAD_BATCH: a batch reads `present` and the box of every slot it covers without looking at a
+  // verdict, and the conditions are combined with `&` -- so the reads of a slot are in flight while the distance test of the slot
+  // before it runs.  As a short-circuit chain (present && distance) each round's two reads stayed behind the previous round's
+  // verdict and were waited for on the spot: twelve LDS round trips in a row in the default configuration (profiles/xlane_notes.md).
+  // Rounds past the last one read the last slot again and drop out at `o < V`; a slot that is not present costs its distance test.
   {
     const int rounds = (V + g.SUB - 1) / g.SUB;
-#pragma unroll 6
-    for (int j = 0; j < rounds; ++j) {
-      const int o = g.sub + j * g.SUB, oc = min(o, V - 1);
-      const Obb ob = snap_obb(S, base + oc);
-      const bool in = o < V && o != s && S.present[base + oc] && shape_point_dist<OBJ>(ob, px, py) <= 50.0f;
-      objs |= in ? (1ull << oc) : 0ull;
+    for (int j0 = 0; j0 < rounds; j0 += PGD_BROAD_BATCH) {
+      Obb ob[PGD_BROAD_BATCH];
+      int pres[PGD_BROAD_BATCH];
+#pragma unroll
+      for (int k = 0; k < PGD_BROAD_BATCH; ++k) {
+        const int oc = min(g.sub + (j0 + k) * g.SUB, V - 1);
+        ob[k] = snap_obb(S, base + oc);
+        pres[k] = S.present[base + oc];
+      }
+#pragma unroll
+      for (int k = 0; k < PGD_BROAD_BATCH; ++k) {
+        const int o = g.sub + (j0 + k) * g.SUB, oc = min(o, V - 1);
+        const bool in = (o < V) & (o != s) & (pres[k] != 0) & (shape_point_dist<OBJ>(ob[k], px, py) <= 50.0f);
+        objs |= in ? (1ull << oc) : 0ull;
+      }
     }
   }
   {
