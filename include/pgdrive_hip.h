@@ -278,7 +278,12 @@ int pgd_reset(pgd_handle h, const int32_t* h_env_ids, const int32_t* h_scen_ids,
  * and env groups on their own streams all see marks that belong to the buffer they write (the same rule for pgd_reset /
  * pgd_observe / pgd_step_packed).  A caller that scribbles over rows it was handed (in-place normalisation, noise) must not expect
  * them to be zeroed again while it keeps passing the same buffer: copy first, pass another buffer, or create the engine with
- * PGD_NO_ROWZ=1 in the environment (every row that is not due is then zero-filled by every call). */
+ * PGD_NO_ROWZ=1 in the environment (every row that is not due is then zero-filled by every call).
+ * d_actions must be 8-byte aligned: the kernel reads an agent's (steering, throttle) pair with one 8-byte load.  The same holds for
+ * the action pointer of pgd_step_packed and pgd_step_group and for d_action_ring of pgd_step_n (its slices are N*A*8 bytes apart, so
+ * the base decides); a pointer that is not is PGD_ERR_ARG before anything is launched, and the engine is as it was.
+ * pgd_step_lane_keep takes no action pointer: its actions come from the row (which it reads in place only where the row buffer is
+ * 8-byte aligned) or from a buffer of the engine's own. */
 int pgd_step(pgd_handle h, const float* d_actions /*[N,A,2]*/, float* d_obs /*[N,A,D]*/, float* d_reward /*[N,A]*/,
              uint8_t* d_done /*[N,A]*/, uint32_t* d_flags /*[N,A]*/);
 
@@ -296,7 +301,12 @@ int pgd_step_n(pgd_handle h, const float* d_action_ring, int ring_len, int first
  * BASELINE.json's north star names (envs shard across GPUs, one gather of (obs, reward, done) per step):
  *   d_rows[e * row_stride + ...] = [A*D observation floats | A rewards | A done flags as 0.0 / 1.0], row_stride >= A*(D+2).
  * The kernel writes the row itself -- d_rows is typically this rank's slice of the gather's receive buffer, so no copy
- * kernel packs anything.  d_reward / d_done / d_flags are written as by pgd_step (rank-local bookkeeping). */
+ * kernel packs anything.  d_reward / d_done / d_flags are written as by pgd_step (rank-local bookkeeping).
+ * Multi-agent engines keep the zero-row marks of pgd_step for d_rows as well, keyed by (d_rows, row_stride): a row that is not due
+ * is zeroed once and left alone while the same buffer keeps coming.  The key is an address, not an allocation: a caller that hands
+ * in NEW memory which may sit where a freed buffer sat with the same row stride (a caching allocator; a receive buffer allocated
+ * per step) calls pgd_forget_rows first, or keeps every buffer it has passed alive for as long as it steps.  pgdrive_amd's
+ * Engine.step_packed does the former for every tensor it has not seen alive, as Engine.step does for `out`. */
 int pgd_step_packed(pgd_handle h, const float* d_actions, float* d_rows /*[N,row_stride]*/, int row_stride,
                     float* d_reward /*[N,A]*/, uint8_t* d_done /*[N,A]*/, uint32_t* d_flags /*[N,A]*/);
 

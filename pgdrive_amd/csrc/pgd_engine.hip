@@ -751,6 +751,7 @@ int pgd_reset(pgd_handle h, const int32_t* env_ids, const int32_t* scen_ids, int
 static int step_impl(pgd_handle h, const float* d_actions, float* d_obs, float* d_reward, uint8_t* d_done, uint32_t* d_flags,
                      int ostride, bool packed, int group = -1) {
   if (!h || !d_actions || !d_reward || !d_done || !d_flags) return PGD_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(d_actions) & 7u) != 0u) return PGD_ERR_ARG;  // k_step reads an agent's action pair with one 8-byte load
   if (!h->have_maps || !h->have_scen) return PGD_ERR_STATE;
   if (h->img_dirty) return PGD_ERR_STATE;  // the reset image is built by the upload calls
   if (h->sinfo && packed) return PGD_ERR_STATE;  // step info: no terminal rows through the packed rows of the gather (pgdrive_hip.h)

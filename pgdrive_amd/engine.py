@@ -180,9 +180,11 @@ class Engine:
             self._bound_stream = cur
 
     def _check_actions(self, actions):
-        """An action tensor (or a buffer for one): float32 cuda, contiguous, [N, A, 2]."""
+        """An action tensor (or a buffer for one): float32 cuda, contiguous, [N, A, 2], 8-byte aligned (the step kernel reads an agent's
+        pair with one 8-byte load; pgd_step* refuse any other pointer with PGD_ERR_ARG)."""
         assert actions.is_cuda and actions.dtype == self.torch.float32 and actions.is_contiguous()
         assert actions.numel() == self.N * self.A * 2
+        assert actions.data_ptr() % 8 == 0, "actions must be 8-byte aligned (a view that starts at an odd float of its buffer is not)"
 
     # -- reference surface ------------------------------------------------------------------------------------------
     def reset(self, scen_ids, env_ids=None, out=None):
@@ -254,11 +256,16 @@ class Engine:
 
     def step_packed(self, actions, rows):
         """Like step(), but the env's results go into `rows` [N, >= A*(D+2)] fp32 as [A*D obs | A reward | A done]: the
-        row a per-step gather sends (pgdrive_amd/dist.py); `rows` may be a slice of the gather's receive buffer."""
+        row a per-step gather sends (pgdrive_amd/dist.py); `rows` may be a slice of the gather's receive buffer.  The zero-row marks
+        of a multi-agent engine name `rows` by address and stride: as for step(out=...), a tensor the engine has not seen alive makes
+        it forget its marks first (by identity of the tensor object: pass the same view while its rows are to be trusted)."""
         self._check_actions(actions)
         assert rows.is_cuda and rows.dtype == self.torch.float32 and rows.dim() == 2 and rows.shape[0] == self.N
         assert rows.stride(1) == 1 and rows.stride(0) >= self.A * (self.D + 2)
+        forget_first = self._unseen_rows(rows)
         self._follow_stream()
+        if forget_first:
+            _chk(self.L.pgd_forget_rows(self.h), "pgd_forget_rows")
         p_obs, p_rew, p_done, p_flags = self._own_ptrs
         _chk(self.L.pgd_step_packed(self.h, C.c_void_p(actions.data_ptr()), C.c_void_p(rows.data_ptr()),
                                     int(rows.stride(0)), p_rew, p_done, p_flags), "pgd_step_packed")
@@ -269,7 +276,7 @@ class Engine:
         (obs after the last step or None, reward [n_steps, N, A], done, flags); the intermediate steps skip the observation."""
         t = self.torch
         assert action_ring.is_cuda and action_ring.dtype == t.float32 and action_ring.is_contiguous() and action_ring.dim() == 4
-        assert tuple(action_ring.shape[1:]) == (self.N, self.A, 2)
+        assert tuple(action_ring.shape[1:]) == (self.N, self.A, 2) and action_ring.data_ptr() % 8 == 0  # (alignment: see _check_actions)
         self._follow_stream()
         rew = t.empty((n_steps, self.N, self.A), dtype=t.float32, device=self.obs.device)
         done = t.empty((n_steps, self.N, self.A), dtype=t.uint8, device=self.obs.device)

@@ -19,7 +19,9 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("num_traffic,num_lasers,traffic_mode,ego", [
     pytest.param(16, 240, "trigger", "driving", id="16-240"), pytest.param(0, 0, "trigger", "driving", id="0-0"),
     pytest.param(16, 240, "respawn", "driving", id="16-240-respawn-driving"),
-    pytest.param(16, 240, "respawn", "parked", id="16-240-respawn-parked")])
+    pytest.param(16, 240, "respawn", "parked", id="16-240-respawn-parked"),
+    # odd row widths (D = 275 and 105): the 4-byte side of the observation code's store-width guards
+    pytest.param(16, 241, "trigger", "driving", id="16-241"), pytest.param(12, 71, "respawn", "driving", id="12-71-respawn-driving")])
 def test_teacher_forced_parity(descs, num_traffic, num_lasers, traffic_mode, ego):
     """Each step starts from the same fp32-rounded state on both sides; outputs and the next state must agree.  In trigger mode almost
     no beam hits anything; respawn traffic (every IDM vehicle drives from step 0) exercises the lidar: once with the ego parked (long
@@ -392,7 +394,8 @@ def test_random_lane_width_and_num_maps_parity():
 
 
 @pytest.mark.parametrize("side,lane_line,num_lasers", [((12, 50.0), (6, 20.0), 240), ((2, 50.0), (2, 50.0), 0),
-                                                       ((0, 50.0), (33, 20.0), 16), ((70, 30.0), (0, 20.0), 0)])
+                                                       ((0, 50.0), (33, 20.0), 16), ((70, 30.0), (0, 20.0), 0),
+                                                       ((5, 50.0), (3, 20.0), 71)])  # every fan odd, D = 111
 def test_side_and_lane_line_detector_parity(descs, side, lane_line, num_lasers):
     """SideDetector / LaneLineDetector fans (distance_detector.py:137-152) spliced into the state block
     (state_obs.py:64-71,96-105): device grid walk vs the oracle's brute force over every line box."""
@@ -717,11 +720,15 @@ def test_empty_and_edge_slots(descs):
     assert (obs[:, 0, 34:] == 1.0).all()  # empty scene -> every beam 1.0 (known answer)
 
 
-@pytest.mark.parametrize("num_agents,capacity", [(2, 2), (3, 4), (8, 8), (12, 16), (40, 40)])
-def test_marl_roundabout_parity(num_agents, capacity):
+@pytest.mark.parametrize("num_agents,capacity,kw", [
+    pytest.param(2, 2, {}, id="2-2"), pytest.param(3, 4, {}, id="3-4"), pytest.param(8, 8, {}, id="8-8"), pytest.param(12, 16, {}, id="12-16"),
+    pytest.param(40, 40, {}, id="40-40"),
+    # an odd beam count (D = 91): rows appended to the step at 8 seats, the four-wave k_observe_env behind it at 40
+    pytest.param(8, 8, dict(num_lasers=73), id="8-8-73beams"), pytest.param(40, 40, dict(num_lasers=73), id="40-40-73beams")])
+def test_marl_roundabout_parity(num_agents, capacity, kw):
     """BASELINE config 5: multi-agent roundabout (envs/marl_envs/marl_inout_roundabout.py) — per-agent done, delay-done
     queue, respawn into free 8 m x 3 m places, __all__, agent ids; teacher-forced against the oracle."""
-    parity.marl_teacher_forced(num_agents, capacity)
+    parity.marl_teacher_forced(num_agents, capacity, **kw)
 
 
 @pytest.mark.parametrize("kind,num_others", [("roundabout", 4), ("intersection", 8)])
@@ -1230,6 +1237,8 @@ def test_contacts_inside_the_sub_steps(descs):
     ("bottleneck", 20, 20, dict(plain_reward=True, side_lasers=4, side_dist=50.0, lane_line_lasers=4, lane_line_dist=20.0)),
     ("roundabout", 12, 16, dict(num_others=4, others_state=True)),  # neighbour rows = the neighbours' own state vectors
     ("intersection", 30, 30, dict(num_others=8, others_state=True)),
+    ("roundabout", 8, 8, dict(num_lasers=73)),  # an odd row width, D = 91
+    ("roundabout", 40, 40, dict(num_lasers=73)),
 ])
 def test_env_observation_kernel_equals_row_kernel(kind, num_agents, capacity, kw):
     """The multi-agent observation comes from k_observe_env (one wave per env: all agents' state blocks at once, lidar

@@ -7,14 +7,15 @@ auto_reset=0 restarts the envs that finished, in every engine mode.
   protocol 3   the rows and the integer state a partial reset leaves, against the oracle's orc_reset of the same list.
 
 tests/test_partial_reset_cpu.py states protocol 1 on the oracle alone.  48 - 66 envs, at most 200 steps, horizon 60.
-The modes are those of MODES below; step info, top-down images and env groups have tests of their own in the default mode."""
+The modes are RESET_MODES of the table in tests/modes.py; step info, top-down images and env groups have tests of their own in the default mode."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from pgdrive_amd import _abi
-from tests import parity, util
+from tests import parity
+from tests.modes import MODES, Setup, assert_same_state, mask_of, state_of, step_all  # noqa: F401
 from tests.parity import OBS_TOL, STATE_OBS_TOL, closed_engines  # noqa: F401 (the fixture closes every engine a test made)
 
 pytestmark = pytest.mark.gpu
@@ -24,106 +25,10 @@ PGD_ERR_ARG = 1  # include/pgdrive_hip.h
 SENTINEL = -7.0  # no observation value: rows are zero or lie in [0, 1]
 RESTARTS_FLOOR = {1: 100}  # by agent seats; any multi-agent mode: 30 (the floors of tests/test_partial_reset_cpu.py)
 
-TOLL = dict(tollgate=True, plain_reward=True, side_lasers=72, side_dist=20.0, lane_line_lasers=4, lane_line_dist=20.0,
-            num_lasers=72, lidar_dist=20.0, speed_reward=0.0, overspeed_penalty=0.5, min_pass_steps=30)
-ONE_ENV = "k_step: one env per wave"
-# mode -> envs, what Engine() is built from, and the pgd_describe_step text that names the mode's step kernel
-MODES = dict(
-    default=dict(n=64, kw=dict(num_traffic=16, num_lasers=240), name=ONE_ENV + ", specialised for the default single-agent configuration"),
-    general=dict(n=64, kw=dict(num_traffic=12, num_lasers=72, side_lasers=6, side_dist=50.0, lane_line_lasers=4, lane_line_dist=20.0,
-                               discrete_action=True), name=ONE_ENV, general=True),
-    pack=dict(n=65, env=dict(PGD_PACK="1"), kw=dict(), name="throughput mode"),  # three envs per wave: 65 leaves the last wave partly empty
-    ego_only=dict(n=66, kw=dict(num_traffic=0, num_lasers=0), name="specialised for the ego-only"),  # four envs per wave
-    imask_40=dict(n=48, env=dict(PGD_IMASK="1"), kw=dict(num_traffic=40), name=ONE_ENV, general=True),
-    safe=dict(n=48, n_maps=16, kw=dict(num_traffic=56, accident_prob=0.8, safe_rl_env=True, density=0.05, use_lateral=False),
-              name="specialised for the SafePGDriveEnv"),
-    marl8=dict(n=48, marl=(8, "roundabout"), kw=dict(), name="multi-agent configuration with 8 agent seats x 72 beams"),
-    marl40=dict(n=48, marl=(40, "roundabout"), kw=dict(), name="multi-agent configuration with 40 agent seats x 72 beams"),
-    # neighbour rows that are state vectors, one block per row (PGD_ROW_OBSERVE): k_observe after the step, which forgets the zero-row marks
-    marl8_rows=dict(n=48, marl=(8, "roundabout"), env=dict(PGD_ROW_OBSERVE="1"), kw=dict(others_state=True, num_others=4), name=ONE_ENV,
-                    general=True),
-    parking=dict(n=48, marl=(8, "parking"), kw=dict(parking=True, enable_reverse=True), name=ONE_ENV, general=True),
-    tollgate=dict(n=48, marl=(8, "tollgate"), kw=dict(TOLL), name=ONE_ENV, general=True),
-)
+# the modes of tests/modes.py this module runs (the table has grown since: the launch-form tests sweep all of it)
+RESET_MODES = ("default", "general", "pack", "ego_only", "imask_40", "safe", "marl8", "marl40", "marl8_rows", "parking", "tollgate")
 ORACLE_MODES = ("default", "general", "pack", "safe", "marl8", "marl40")
 SHAPE_MODES = ("default", "pack", "marl8")
-
-
-class Setup:
-    """The banks of a mode and engines of its configuration (every engine is closed when the test ends)."""
-    def __init__(self, descs, mode):
-        m = self.m = MODES[mode]
-        self.mode, self.n = mode, m["n"]
-        base = dict(dict(horizon=60, seed=7), **m["kw"])
-        if "marl" in m:
-            seats, kind = m["marl"]
-            _, self.mb, self.sb = util.make_marl_banks(num_agents=seats, capacity=seats, kind=kind)
-            self.make = lambda **kw: util.marl_config(self.n, self.sb, **dict(base, **kw))
-        else:
-            self.mb, self.sb, _ = parity.banks_and_config(descs, self.n, m.get("n_maps", 8), **base)
-            self.make = lambda **kw: _abi.make_config(self.n, **{k: v for k, v in dict(base, **kw).items() if k in parity.CONFIG_KEYS})
-        self.n_scen = len(self.sb.scenarios)
-        self.A = self.sb.A if "marl" in m else 1
-
-    def engine(self, env=None, **cfg_kw):
-        return parity.engine(self.make(**cfg_kw), self.mb, self.sb, env=dict(self.m.get("env", {}), **(env or {})))
-
-    def oracle(self, **cfg_kw):
-        return parity.oracle(self.make(**cfg_kw), self.mb, self.sb)
-
-    def actions(self, seed=17):
-        rng = np.random.default_rng(seed)
-        if self.A > 1:
-            return lambda t: util.marl_actions(rng, self.n, self.A)
-        if self.m["kw"].get("discrete_action"):
-            return lambda t: rng.integers(0, 5, size=(self.n, 1, 2)).astype(np.float32)
-        return parity.driving_with_bursts(rng, self.n)
-
-    def stagger(self, *engines):
-        """The discrete actions of the `general` mode only ever brake (upstream clips them before the conversion): its episodes end
-        by the horizon alone, all in the same step.  Give the envs different step counts so that the lists differ from step to step."""
-        if self.m["kw"].get("discrete_action"):
-            f, i, ei = engines[0].get_state()
-            ei[EI["EP_STEPS"]] = np.arange(self.n) % 37
-            for e in engines:
-                e.set_state(f, i, ei)
-
-    def check_name(self, eng):
-        """the step kernel the mode is about has run (a case cannot silently test another one)"""
-        desc = eng.describe_step()
-        assert self.m["name"] in desc and ("specialised" not in desc) == bool(self.m.get("general")), desc
-
-    @property
-    def tail(self):
-        return 2 if self.m["kw"].get("tollgate") else 0  # the toll floats stand behind the lidar
-
-
-def step_all(engines, act):
-    """One step of every engine on the same actions: the four outputs of each, cloned, after a sync."""
-    import torch
-    at = torch.from_numpy(act).to(engines[0].device)
-    outs = [[x.clone() for x in e.step(at)] for e in engines]
-    for e in engines:
-        e.sync()
-    return outs
-
-
-def state_of(eng, skip=("EPISODES", )):
-    """(float state as int32 bits, integer state, env counters without `skip`); pgd_get_state masks EI_NEAR itself"""
-    f, i, ei = eng.get_state()
-    return f.view(np.int32), i, ei[[k for name, k in EI.items() if name not in skip]]
-
-
-def assert_same_state(sa, sb, envs, what):
-    """bit-identical state of the envs `envs` (bool [N])"""
-    for xa, xb, name in zip(sa, sb, ("float state", "integer state", "env counters")):
-        assert np.array_equal(xa[:, envs], xb[:, envs]), "%s: %s differs in envs %s" % (what, name, np.nonzero((xa != xb).reshape(len(xa), len(envs), -1).any(axis=(0, 2)) & envs)[0][:8])
-
-
-def mask_of(n, ids):
-    m = np.zeros(n, dtype=bool)
-    m[np.asarray(ids, dtype=np.int64)] = True
-    return m
 
 
 def raw_reset(eng, scen_ids, env_ids, obs, n=None):
@@ -135,7 +40,7 @@ def raw_reset(eng, scen_ids, env_ids, obs, n=None):
 # ---------------------------------------------------------------------------------------------------------------------
 # Protocol 1
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("mode", RESET_MODES)
 def test_manual_restart_equals_the_automatic_one(descs, mode):
     """Twin A: auto_reset=1, resample_scenario=1.  Twin B: auto_reset=0; after every step the envs whose flags carry F_RESET in A are
     restarted by id with the scenario A's EI_SCEN names, into the buffer B's step wrote.  Every step: reward and done bit-identical,
@@ -228,7 +133,7 @@ def run_on(s, b, c, actions, t0, n_steps, touched):
     return t0 + n_steps
 
 
-@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("mode", RESET_MODES)
 def test_envs_are_independent(descs, mode):
     """Engines B and C: one configuration (auto_reset=0), one state, one action stream.  B restarts a list of envs after steps 12, 30
     and 48 -- every fifth env from 1, a descending list that straddles the waves of the modes with several envs per wave, and a
