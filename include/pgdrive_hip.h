@@ -576,6 +576,72 @@ int pgd_adv_stats(pgd_handle h, const float* d_adv, const int32_t* d_index, cons
  * n_elem >= 1 (PGD_ERR_ARG).  Two launches, asynchronous on the engine's stream; capturable. */
 int pgd_adam(pgd_handle h, float* d_param, const float* d_grad, float* d_m, float* d_v, int n_elem, int32_t* d_step /*[4]*/, float lr,
              float beta1, float beta2, float eps, float max_grad_norm);
+/* ---- Safe RL behind a rollout: cost critic, cost GAE, the Lagrange multiplier, PPO-Lagrangian gradients -------------------------------
+ * (No reference counterpart: the reference hands info["cost"] to an RL library; safe_pgdrive_env.py:7-60.  With safe_rl_env a crash is a
+ * cost and not a termination; these entry points keep a policy under a cost limit without leaving the device.)
+ * A cost critic is a third network of the value network's shapes (pgd_value_net: w3 [256][1]; w1, b1, w2, b2 16-byte aligned).
+ *
+ * pgd_mlp_actor_critic_cost: pgd_mlp_actor_critic with the cost critic beside actor and critic in the same launch, grid (ceil(rows / 16),
+ * 3).  Every argument, the arithmetic, PGD_AC_DETERMINISTIC, the device tick and the refusals (in_dim 4 .. 416, alignment) as there;
+ * in addition both critics are required: all six value pointers of `nets`, all six of `cost_net`, d_value and d_cost_value
+ * (PGD_ERR_ARG).  d_actions, d_logp, d_value are bit for bit what pgd_mlp_actor_critic writes on the same inputs; d_cost_value is bit for
+ * bit what it writes into d_value when cost_net is handed to it as the value network.  One launch, asynchronous, capturable.
+ *
+ * pgd_cost_gae: the costs of a rollout from its flags, their GAE and the episode-cost bookkeeping.  flags, done, cost, cadv, cret
+ * [T][rows], cost_value [T + 1][rows], time-major.  One thread per row, fp32:
+ *   cost[t][r] = out_of_road ? costs[0] : crash_vehicle ? costs[1] : crash_object ? costs[2] : 0      (PGD_F_OUT_OF_ROAD, PGD_F_CRASH_VEHICLE,
+ *                PGD_F_CRASH_OBJECT of flags[t][r]; the precedence of pgd_step_info's cost and of PGDriveEnv.cost_function,
+ *                pgdrive_env.py:197-207; a selection of the three floats, no other flag bit matters)
+ *   forward, t = 0 .. T - 1 in order:  run += cost;  at done[t][r]:  ep_sum += run, ep_count += 1, run = 0
+ *   reverse: pgd_gae's recursion in its fma forms with cost as the reward, gamma and lam the call's own
+ * d_run [rows] is read and written: it carries the cost of the unfinished episode into the next rollout (zero it before the first call,
+ * and for every env that is reset by hand).  d_ep_sum and d_ep_count [rows] are WRITTEN: the finished episodes of this rollout only.  A
+ * done finishes an episode whatever ended it, a horizon truncation included, as for GAE.  d_cadv and d_cret are bit for bit what pgd_gae
+ * gives on d_cost, d_cost_value, d_done.  T >= 1, rows >= 1 (PGD_ERR_ARG).  One launch, asynchronous, capturable.
+ *
+ * pgd_lagrange: one step of the multiplier from the finished episodes of a rollout.  d_state: four device floats -- 0 lambda, 1 J_c (the
+ * mean episode cost last seen), 2 the number of episodes behind it, 3 unused --, zero (or lambda's first value in slot 0) before the
+ * first call.  One workgroup: thread i takes rows i, i + 256, ... in order, a butterfly per wave, the four waves in order (the order of
+ * pgd_adv_stats), the sums in double and the counts as integers: the same input gives the same bytes.
+ *   E = sum ep_count.   E > 0:  J_c = sum ep_sum / E;   lambda <- min(lambda_max, max(0, lambda + lr (J_c - cost_limit)));  slots 1, 2 written
+ *   E == 0: the state keeps every byte.
+ * The quotient and the step are formed in double and rounded to fp32 once.  A captured call replayed takes the next step from the lambda
+ * it finds (the reasoning of pgd_adam's counter).  rows >= 1, lambda_max >= 0 (PGD_ERR_ARG).  Rows with ep_count 0 hold ep_sum 0.
+ *
+ * pgd_adv_mix: the advantage the policy sees, per entry i < n:
+ *   out = ((adv - m) s - lambda (cadv - m_c)) / (1 + lambda)
+ * (m, s) = d_adv_stats, null: (0, 1); m_c = d_cadv_stats[0], null: 0 (both as pgd_adv_stats writes them); lambda = d_state[0].  The cost
+ * advantage is centred, NOT rescaled: its scale is the cost's magnitude, which lambda is there to price.  Formed in double, rounded to
+ * fp32 once; lambda = 0 gives (adv - m) s.  One read of two arrays, one write.  n >= 1 (PGD_ERR_ARG).  One launch, asynchronous, capturable.
+ *
+ * pgd_ppo_grad_cost: pgd_ppo_grad with three networks.  Network 2 is a critic with ret = cost->cost_ret and vf_coef = cost->cvf_coef:
+ *   L_c = (1/n) sum 0.5 (v_c - cost_ret)^2;   dL/dv_c = cvf_coef (v_c - cost_ret) / n
+ * batch->adv is normally pgd_adv_mix's output with batch->adv_stats null; the actor's formulas are pgd_ppo_grad's.  d_stats: slots 0..6 as
+ * pgd_ppo_grad, slot 7 = L_c.  The minibatch rule (start / stride / rows / index / count), the determinism and its summation orders, what
+ * may hold NaN (cost_ret as ret: rows that are not listed reach no output), n = 0 -> every gradient and statistic zero, and the refusals
+ * are pgd_ppo_grad's; both critics and every gradient buffer are required.  Actor and critic gradients and d_stats[0..6] are bit for bit
+ * pgd_ppo_grad's on the same inputs; the cost critic's gradients and d_stats[7] are bit for bit the critic gradients and d_stats[2] of a
+ * pgd_ppo_grad call that is handed cost_net as value network, cost_ret as ret and cvf_coef as vf_coef.  Scratch: the caller's, 16-byte
+ * aligned, work_bytes >= pgd_ppo_cost_work_bytes(in_dim, rows) (0: the call refuses the shape).  The launches are pgd_ppo_grad's with a
+ * third network in their grids: five (six with out_cols > 4), asynchronous, capturable from the first call. */
+typedef struct pgd_value_net { const float *w1, *b1, *w2, *b2, *w3, *b3; } pgd_value_net;  /* a critic's shapes: w3 [256][1] */
+typedef struct pgd_ppo_cost { const float* cost_ret; float cvf_coef; } pgd_ppo_cost;
+typedef struct pgd_value_grads { float *w1, *b1, *w2, *b2, *w3, *b3; } pgd_value_grads;
+int pgd_mlp_actor_critic_cost(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets,
+                              const pgd_value_net* cost_net, uint32_t seed, uint32_t tick, uint32_t flags, float* d_actions /*[rows][2]*/,
+                              float* d_logp /*[rows]*/, float* d_value /*[rows]*/, float* d_cost_value /*[rows]*/);
+int pgd_cost_gae(pgd_handle h, const uint32_t* d_flags /*[T][rows]*/, const uint8_t* d_done, const float* d_cost_value /*[T+1][rows]*/, int T,
+                 int rows, const float costs[3] /* out_of_road, crash_vehicle, crash_object */, float gamma, float lam,
+                 float* d_cost /*[T][rows]*/, float* d_cadv, float* d_cret, float* d_run /*[rows], in/out*/, float* d_ep_sum /*[rows]*/,
+                 int32_t* d_ep_count /*[rows]*/);
+int pgd_lagrange(pgd_handle h, const float* d_ep_sum, const int32_t* d_ep_count, int rows, float cost_limit, float lr, float lambda_max,
+                 float* d_state /*[4]: lambda, J_c, episodes, 0*/);
+int pgd_adv_mix(pgd_handle h, const float* d_adv, const float* d_cadv, int n, const float* d_adv_stats /*[2] or null*/,
+                const float* d_cadv_stats /*[2] or null*/, const float* d_state /* pgd_lagrange's */, float* d_out /*[n]*/);
+size_t pgd_ppo_cost_work_bytes(int in_dim, int rows);
+int pgd_ppo_grad_cost(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
+                      const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
+                      float* d_stats /*[8]*/, void* d_work, size_t work_bytes);
 /* Multi-agent engines remember, per env, which rows of the LAST observation buffer they were given already hold the zeros of a seat
  * that is not due (identified by the buffer's address and row stride), and do not write them again.  A caller that hands pgd_step
  * a buffer whose address a FORMER buffer had (a caching allocator re-using a freed block: torch.empty per step) calls this first:

@@ -27,9 +27,15 @@ def __getattr__(name):
     if name == "RolloutCollector":
         from .rollout import RolloutCollector
         return RolloutCollector
+    if name == "SafeRolloutCollector":
+        from .rollout import SafeRolloutCollector
+        return SafeRolloutCollector
     if name == "PPOLearner":
         from .learner import PPOLearner
         return PPOLearner
+    if name == "PPOLagLearner":
+        from .learner import PPOLagLearner
+        return PPOLagLearner
     if name == "Engine":
         from .engine import Engine
         return Engine

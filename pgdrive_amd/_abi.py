@@ -68,8 +68,25 @@ class PPOGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "vw1", "vb1", "vw2", "vb2", "vw3", "vb3")]
 
 
+class ValueNet(C.Structure):
+    """pgd_value_net: the device pointers of a critic-shaped network (w3 [256][1]) -- the cost critic."""
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
+class PPOCost(C.Structure):
+    """pgd_ppo_cost: the cost critic's targets by rollout row and its loss coefficient."""
+    _fields_ = [("cost_ret", C.c_void_p), ("cvf_coef", C.c_float)]
+
+
+class ValueGrads(C.Structure):
+    """pgd_value_grads: the cost critic's gradient buffers, of its weights' shapes."""
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
 PPO_ROWS_MAX = 16777216
 PPO_STATS = ("n", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "ratio", "reserved")  # d_stats of pgd_ppo_grad
+PPO_COST_STATS = PPO_STATS[:7] + ("cost_value_loss", )  # d_stats of pgd_ppo_grad_cost
+LAGRANGE_STATE = ("lambda", "episode_cost", "episodes", "reserved")  # d_state of pgd_lagrange
 
 # the tensors of Engine.enable_step_info by pgd_step_info field: (dtype name, key in Engine.step_info)
 STEP_INFO_FIELDS = dict(

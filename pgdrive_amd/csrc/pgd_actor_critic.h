@@ -9,7 +9,8 @@
 // actor for 16 observation rows, workgroup (x, 1) the critic for the same rows (their second read comes from L2); both are
 // k_mlp_policy's workgroup -- 16-row tile, 4 waves, the same LDS strides, the same row prologue, mlp_layer / mlp_store_hidden /
 // mlp_tanh -- with another head.  Two workgroups of 256 threads and at most 64 KB fit a CU side by side, so the critic runs NEXT to the
-// actor, not behind it.  A null value network launches gridDim.y = 1.
+// actor, not behind it.  A null value network launches gridDim.y = 1.  The workgroup's code is ac_tile, which is handed the chosen
+// network's pointers: k_mlp_actor_critic_cost (pgd_safe.h) calls it with a third network, the cost critic, at blockIdx.y = 2.
 //
 // LDS per workgroup: X tile | H1 | H2 | the head's weights [4][256] (the critic uses the first 256): 2 KB more than k_mlp_policy, hence
 // the largest accepted in_dim is 416 (x stride 418), not 448 (x stride 450: 65,920 bytes); ac_lds_bytes is the formula.
@@ -82,21 +83,14 @@ DEV void ac_load_rows(const float* obs, const int row0, const int r0, const int 
   }
 }
 
-// rows [row0, row0 + n_rows) of `obs` -> act[row][0..1], logp[row] (blockIdx.y == 0) and value[row] (blockIdx.y == 1)
-__global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic(const float* __restrict__ obs, const int row0, const int n_rows,
-                                                                       const int obs_stride, const int in_dim, const pgd_actor_critic nets,
-                                                                       const uint32_t seed, const uint32_t tick_arg,
-                                                                       const uint32_t* __restrict__ tick_dev, const uint32_t row_base,
-                                                                       const uint32_t flags, float* __restrict__ act, float* __restrict__ logp,
-                                                                       float* __restrict__ value) {
+// One workgroup of k_mlp_actor_critic on the network (W1 .. b3): the actor (critic false: act, logp) or a critic (value) for the 16 rows
+// row0 + blockIdx.x * 16 + [0, 16) of `obs`.  The kernels below and k_mlp_actor_critic_cost (pgd_safe.h) choose the network and call it.
+DEV void ac_tile(const float* obs, const int row0, const int n_rows, const int obs_stride, const int in_dim, const bool critic,
+                 const float* W1, const float* b1, const float* W2, const float* b2,
+                 const float* W3, const float* b3, const int out_cols, const uint32_t seed, const uint32_t tick_arg,
+                 const uint32_t* tick_dev, const uint32_t row_base, const uint32_t flags, float* act,
+                 float* logp, float* value) {
   extern __shared__ float mlp_lds[];
-  const bool critic = blockIdx.y != 0;
-  const float* __restrict__ W1 = critic ? nets.vw1 : nets.w1;
-  const float* __restrict__ b1 = critic ? nets.vb1 : nets.b1;
-  const float* __restrict__ W2 = critic ? nets.vw2 : nets.w2;
-  const float* __restrict__ b2 = critic ? nets.vb2 : nets.b2;
-  const float* __restrict__ W3 = critic ? nets.vw3 : nets.w3;
-  const float* __restrict__ b3 = critic ? nets.vb3 : nets.b3;
   const int kp = (in_dim + 3) & ~3, xs = mlp_x_stride(in_dim);
   float* X = mlp_lds;
   float* H1 = X + MLP_ROWS * xs;
@@ -106,7 +100,7 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic(const 
   const int r0 = (int)blockIdx.x * MLP_ROWS;  // (relative to row0)
   // the head's weights go to LDS with the observation rows, as in k_mlp_policy: actor 256 x 4 of w3 (its first four columns, index =
   // 4 k + o), critic the 256 of vw3 (index = k)
-  const int heads = critic ? 1 : AC_HEAD, w3_ld = critic ? 1 : nets.out_cols;
+  const int heads = critic ? 1 : AC_HEAD, w3_ld = critic ? 1 : out_cols;
   float w3v[AC_HEAD];
 #pragma unroll
   for (int q = 0; q < AC_HEAD; ++q) {
@@ -173,6 +167,19 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic(const 
     act[(size_t)row * 2 + 1] = fmaf(expf(ls1), z1, m1);
     logp[row] = fmaf(-0.5f, fmaf(z0, z0, z1 * z1), -ls0 - ls1) - 1.8378770664093453f;  // log(2 pi)
   }
+}
+
+// rows [row0, row0 + n_rows) of `obs` -> act[row][0..1], logp[row] (blockIdx.y == 0) and value[row] (blockIdx.y == 1)
+__global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic(const float* __restrict__ obs, const int row0, const int n_rows,
+                                                                       const int obs_stride, const int in_dim, const pgd_actor_critic nets,
+                                                                       const uint32_t seed, const uint32_t tick_arg,
+                                                                       const uint32_t* __restrict__ tick_dev, const uint32_t row_base,
+                                                                       const uint32_t flags, float* __restrict__ act, float* __restrict__ logp,
+                                                                       float* __restrict__ value) {
+  const bool critic = blockIdx.y != 0;
+  ac_tile(obs, row0, n_rows, obs_stride, in_dim, critic, critic ? nets.vw1 : nets.w1, critic ? nets.vb1 : nets.b1, critic ? nets.vw2 : nets.w2,
+          critic ? nets.vb2 : nets.b2, critic ? nets.vw3 : nets.w3, critic ? nets.vb3 : nets.b3, nets.out_cols, seed, tick_arg, tick_dev, row_base,
+          flags, act, logp, value);
 }
 
 // adv[t][r] = delta + gamma lam nonterminal adv[t + 1][r], delta = reward[t][r] + gamma value[t + 1][r] nonterminal - value[t][r],

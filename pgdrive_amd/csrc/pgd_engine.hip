@@ -2,7 +2,8 @@
 // launch plan of a step and the C ABI (include/pgdrive_hip.h).  The device code is in the headers included here, in this order: pgd_device.h,
 // pgd_step.h (k_step; it includes pgd_vehicle.h ... pgd_policy.h, pgd_actor_critic.h), pgd_kernels.h (reset / derive / refresh / observe),
 // pgd_marl_rollout.h (live rows, the networks over a row list, masked GAE) and, at the end,
-// pgd_topdown.h, pgd_render.h, pgd_gather.h, pgd_step_info.h and pgd_ppo.h (the PPO update) with their own entry points.
+// pgd_topdown.h, pgd_render.h, pgd_gather.h, pgd_step_info.h, pgd_ppo.h (the PPO update) and pgd_safe.h (its cost side) with their own
+// entry points.
 // The reference call stack this replaces: envs/base_env.py:184-224,303-344.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -99,6 +100,7 @@ struct pgd_engine {
   struct { const float* obs; float k_lat, k_head, v_target, noise; uint32_t tick; } lk;  // pgd_step_lane_keep: this launch's scripted policy (obs null: none)
   float* lk_act;     // pgd_step_lane_keep on engines that cannot take the policy into the step kernel: the actions in between
   bool ppo_attr;     // pgd_ppo_grad: as ac_attr, for k_ppo_rows
+  bool safe_attr[2]; // pgd_mlp_actor_critic_cost, pgd_ppo_grad_cost: as ac_attr, for their kernels
 };
 
 // The default row layout (see observe_agent): the STD instantiations of k_step
@@ -1400,4 +1402,5 @@ int pgd_destroy(pgd_handle h) {
 #include "pgd_gather.h"
 #include "pgd_step_info.h"
 #include "pgd_ppo.h"
+#include "pgd_safe.h"
 #endif  // !PGD_JIT

@@ -22,6 +22,8 @@
 //   k_ppo_reduce  every gradient entry = its partials summed over the live partitions in partition order, written in the weights' own
 //                 shapes; head columns at or beyond 4 are written as zero
 //   k_ppo_stats   ONE workgroup: the tile sums over the live tiles in a fixed order -> d_stats and db3
+// k_ppo_rows, k_ppo_reduce and k_ppo_stats choose their network's pointers from blockIdx.y and hand them to a body (ppo_rows_tile,
+// ppo_reduce_entry, ppo_stats_block) that pgd_safe.h's three-network kernels call as well; k_ppo_wgrad takes its network count from its grid.
 // Deterministic: no atomics; a row's numbers never depend on its tile neighbours; every sum over rows has one owner and a fixed order
 // (rows within a partition, partitions in order; rows within a tile, tiles 16-strided, the sixteen strides in order).
 //
@@ -40,7 +42,7 @@
 
 #define PPO_PART 1024   // rows per partial sum of a weight gradient
 #define PPO_CHUNK 256   // rows of A^T staged in LDS at a time
-#define PPO_TS 16       // floats per tile-sum record: 0 L_pi, 1 H, 2 logp_old - logp, 3 cut, 4 r, 5..8 dOut (actor); 9 L_v, 10 dv (critic)
+#define PPO_TS 16       // floats per tile-sum record: 0 L_pi, 1 H, 2 logp_old - logp, 3 cut, 4 r, 5..8 dOut (actor); 9 L_v, 10 dv (critic); 11 L_c, 12 dv_c (cost critic, pgd_safe.h)
 #define PPO_ST 12       // loss terms per row in LDS (the record's first eleven slots)
 #define PPO_BATCH 8     // reads a thread of a one-workgroup reduction keeps in flight: the loop waits for memory once per batch, the sum keeps its order
 #define PPO_LOG_2PI 1.8378770664093453f
@@ -123,19 +125,17 @@ __global__ __launch_bounds__(MLP_H) void k_ppo_prep(const pgd_actor_critic nets,
   W2T[(size_t)k * MLP_H + c] = W2[(size_t)c * MLP_H + k];
 }
 
-__global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows(const pgd_actor_critic nets, const pgd_ppo_batch b, const pgd_ppo_hyper hp,
-                                                               float* __restrict__ work) {
+// One workgroup of k_ppo_rows: network blockIdx.y of gridDim.y -- the actor (critic false) or a critic on (W1 .. b3) with the target `ret` and
+// the coefficient `vf_coef`, whose two tile sums go to slots 9 + ts_shift and 10 + ts_shift of the tile's record -- for the 16 minibatch
+// positions blockIdx.x * 16 + [0, 16).  k_ppo_rows and k_ppo_rows_cost (pgd_safe.h) choose the network and call it.
+DEV void ppo_rows_tile(const bool critic, const float* W1, const float* b1, const float* W2,
+                       const float* b2, const float* W3, const float* b3, const int out_cols,
+                       const float* ret, const float vf_coef, const int ts_shift, const pgd_ppo_batch& b, const pgd_ppo_hyper& hp,
+                       float* work) {
   extern __shared__ float mlp_lds[];
   const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
   const int i0 = (int)blockIdx.x * MLP_ROWS;  // (the tile's first minibatch position)
   if (i0 >= n) return;
-  const bool critic = blockIdx.y != 0;
-  const float* __restrict__ W1 = critic ? nets.vw1 : nets.w1;
-  const float* __restrict__ b1 = critic ? nets.vb1 : nets.b1;
-  const float* __restrict__ W2 = critic ? nets.vw2 : nets.w2;
-  const float* __restrict__ b2 = critic ? nets.vb2 : nets.b2;
-  const float* __restrict__ W3 = critic ? nets.vw3 : nets.w3;
-  const float* __restrict__ b3 = critic ? nets.vb3 : nets.b3;
   const int in_dim = b.in_dim, kp = (in_dim + 3) & ~3, xs = mlp_x_stride(in_dim);
   const PpoWork wk = ppo_work(in_dim, b.rows, (int)gridDim.y);
   const size_t plane = (size_t)wk.R16 * MLP_H;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows(const pgd_acto
   float* dO = W3s + AC_HEAD * MLP_H;    // [16][4]
   float* st = dO + MLP_ROWS * 4;        // [16][PPO_ST]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int heads = critic ? 1 : AC_HEAD, w3_ld = critic ? 1 : nets.out_cols;
+  const int heads = critic ? 1 : AC_HEAD, w3_ld = critic ? 1 : out_cols;
   float w3v[AC_HEAD];
 #pragma unroll
   for (int q = 0; q < AC_HEAD; ++q) {
@@ -196,9 +196,9 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows(const pgd_acto
     if (part == 0) {
       float lv = 0.0f, dv = 0.0f;
       if (row >= 0) {
-        const float e = s + b3[0] - b.ret[row];
+        const float e = s + b3[0] - ret[row];
         lv = 0.5f * e * e;
-        dv = hp.vf_coef * e * inv_n;
+        dv = vf_coef * e * inv_n;
       }
       dO[r * 4 + 0] = dv;
       dO[r * 4 + 1] = 0.0f;
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows(const pgd_acto
   if (tid < 11 && (critic ? tid >= 9 : tid < 9)) {
     float s = 0.0f;
     for (int q = 0; q < MLP_ROWS; ++q) s += st[q * PPO_ST + tid];
-    tsum[tid] = s;
+    tsum[critic ? tid + ts_shift : tid] = s;
   }
   if (tid < MLP_ROWS * 4) dOg[(size_t)i0 * 4 + tid] = dO[tid];
   // H1, H2 out; dZ2 = (dOut W3^T)(1 - H2^2) in H2's place and out
@@ -287,6 +287,13 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows(const pgd_acto
       *reinterpret_cast<float4*>(dZ1g + (size_t)(i0 + r4 + i) * MLP_H + col) = dz;
     }
   }
+}
+
+__global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows(const pgd_actor_critic nets, const pgd_ppo_batch b, const pgd_ppo_hyper hp,
+                                                               float* __restrict__ work) {
+  const bool critic = blockIdx.y != 0;
+  ppo_rows_tile(critic, critic ? nets.vw1 : nets.w1, critic ? nets.vb1 : nets.b1, critic ? nets.vw2 : nets.w2, critic ? nets.vb2 : nets.b2,
+                critic ? nets.vw3 : nets.w3, critic ? nets.vb3 : nets.b3, nets.out_cols, b.ret, hp.vf_coef, 0, b, hp, work);
 }
 
 // what output tile `tile` of a network is: 0 dW1 (m0 = its first weight row), 1 db1, 2 dW2, 3 db2, 4 dW3^T
@@ -349,7 +356,8 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad(const pgd_ppo
 }
 
 // grid (16 mt, networks): block (16 tile + m, net), thread c: the partials of entry (m, c) of the tile over the live partitions, in order
-__global__ __launch_bounds__(MLP_H) void k_ppo_reduce(const pgd_ppo_batch b, const pgd_ppo_grads gr, const int out_cols, const float* __restrict__ work) {
+DEV void ppo_reduce_entry(const pgd_ppo_batch& b, const bool critic, float* dW1, float* db1, float* dW2,
+                          float* db2, float* dW3, const int out_cols, const float* work) {
   const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
   const int p_live = (((n + 15) & ~15) + PPO_PART - 1) / PPO_PART;
   const int in_dim = b.in_dim, net = (int)blockIdx.y;
@@ -360,11 +368,6 @@ __global__ __launch_bounds__(MLP_H) void k_ppo_reduce(const pgd_ppo_batch b, con
   const float* __restrict__ part = work + wk.part + ((((size_t)net * wk.P) * wk.mt + tile) * 16 + m) * MLP_H + c;
   float s = 0.0f;
   for (int p = 0; p < p_live; ++p) s += part[(size_t)p * wk.mt * 16 * MLP_H];
-  float* __restrict__ dW1 = net ? gr.vw1 : gr.w1;
-  float* __restrict__ db1 = net ? gr.vb1 : gr.b1;
-  float* __restrict__ dW2 = net ? gr.vw2 : gr.w2;
-  float* __restrict__ db2 = net ? gr.vb2 : gr.b2;
-  float* __restrict__ dW3 = net ? gr.vw3 : gr.w3;
   if (kind == 0) {
     if (m0 + m < in_dim) dW1[(size_t)(m0 + m) * MLP_H + c] = s;
   } else if (kind == 1) {
@@ -373,12 +376,18 @@ __global__ __launch_bounds__(MLP_H) void k_ppo_reduce(const pgd_ppo_batch b, con
     dW2[(size_t)(m0 + m) * MLP_H + c] = s;
   } else if (kind == 3) {
     if (m == 0) db2[c] = s;
-  } else if (net) {
+  } else if (critic) {
     if (m == 0) dW3[c] = s;
   } else {
     if (m < 4) dW3[(size_t)c * out_cols + m] = s;
     else if (m < out_cols) dW3[(size_t)c * out_cols + m] = 0.0f;  // (head columns that are never read; those from 16 on: k_ppo_zero_head)
   }
+}
+
+__global__ __launch_bounds__(MLP_H) void k_ppo_reduce(const pgd_ppo_batch b, const pgd_ppo_grads gr, const int out_cols, const float* __restrict__ work) {
+  const bool critic = blockIdx.y != 0;
+  ppo_reduce_entry(b, critic, critic ? gr.vw1 : gr.w1, critic ? gr.vb1 : gr.b1, critic ? gr.vw2 : gr.w2, critic ? gr.vb2 : gr.b2,
+                   critic ? gr.vw3 : gr.w3, out_cols, work);
 }
 
 // head columns [16, out_cols) of dW3 and [4, out_cols) of db3: zero
@@ -391,16 +400,17 @@ __global__ __launch_bounds__(MLP_H) void k_ppo_zero_head(float* __restrict__ dW3
 
 // ONE workgroup: slot s of the tile sums over the live tiles -- thread (s, u) takes tiles u, u + 16, ... in order, then the sixteen u in
 // order -- -> d_stats and db3
-__global__ __launch_bounds__(256) void k_ppo_stats(const pgd_ppo_batch b, const pgd_ppo_grads gr, const int has_critic, const float* __restrict__ work,
-                                                   float* __restrict__ stats) {
+// (cost_b3 set: three networks, the cost critic's sums in slots 11 and 12 -> stats[7] and cost_b3[0]; k_ppo_stats_cost, pgd_safe.h)
+DEV void ppo_stats_block(const pgd_ppo_batch& b, const pgd_ppo_grads& gr, const int has_critic, float* cost_b3,
+                         const float* work, float* stats) {
   __shared__ float red[16][PPO_TS];
   __shared__ float tot[PPO_TS];
   const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
   const int tiles = (n + 15) >> 4;
-  const PpoWork wk = ppo_work(b.in_dim, b.rows, has_critic ? 2 : 1);
+  const PpoWork wk = ppo_work(b.in_dim, b.rows, cost_b3 ? 3 : (has_critic ? 2 : 1));
   const float* __restrict__ tsum = work + wk.tsum;
   const int s = threadIdx.x & 15, u = threadIdx.x >> 4;
-  const bool used = s < 9 || (has_critic && s < 11);
+  const bool used = s < 9 || (has_critic && s < 11) || (cost_b3 && s < 13);
   float a = 0.0f;
   if (used)
     for (int t0 = u; t0 < tiles; t0 += 16 * PPO_BATCH) {  // (PPO_BATCH reads in flight, then their sum in the same order)
@@ -430,13 +440,19 @@ __global__ __launch_bounds__(256) void k_ppo_stats(const pgd_ppo_batch b, const 
     stats[4] = tot[2] * inv;
     stats[5] = tot[3] * inv;
     stats[6] = tot[4] * inv;
-    stats[7] = 0.0f;
+    stats[7] = cost_b3 ? tot[11] * inv : 0.0f;
     gr.b3[0] = tot[5];
     gr.b3[1] = tot[6];
     gr.b3[2] = tot[7];
     gr.b3[3] = tot[8];
     if (has_critic) gr.vb3[0] = tot[10];
+    if (cost_b3) cost_b3[0] = tot[12];
   }
+}
+
+__global__ __launch_bounds__(256) void k_ppo_stats(const pgd_ppo_batch b, const pgd_ppo_grads gr, const int has_critic, const float* __restrict__ work,
+                                                   float* __restrict__ stats) {
+  ppo_stats_block(b, gr, has_critic, nullptr, work, stats);
 }
 
 // ---- pgd_adv_stats: ONE workgroup; thread i takes entries i, i + 256, ... in order, a butterfly per wave, the four waves in order ----

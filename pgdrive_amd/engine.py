@@ -50,6 +50,16 @@ _SIGS = {
     "pgd_adv_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pgd_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float,
                            C.c_float, C.c_float]),
+    "pgd_mlp_actor_critic_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.ValueNet),
+                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgd_cost_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float] +
+                     [C.c_void_p] * 6),
+    "pgd_lagrange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "pgd_adv_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgd_ppo_cost_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "pgd_ppo_grad_cost": (C.c_int, [C.c_void_p, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.ValueNet), C.POINTER(_abi.PPOBatch),
+                                    C.POINTER(_abi.PPOCost), C.POINTER(_abi.PPOHyper), C.POINTER(_abi.PPOGrads), C.POINTER(_abi.ValueGrads),
+                                    C.c_void_p, C.c_void_p, C.c_size_t]),
     "pgd_step_lane_keep": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 4),
     "pgd_lane_keep_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32]),
     "pgd_topdown_channels": (C.c_int, [C.POINTER(_abi.TopDownConfig)]),
@@ -604,6 +614,151 @@ class Engine:
         _chk(self.L.pgd_adam(self.h, C.c_void_p(param.data_ptr()), C.c_void_p(grad.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), n,
                              C.c_void_p(step.data_ptr()), float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm)), "pgd_adam")
         return param
+
+    # -- safe RL behind a rollout: the cost side of the loop (include/pgdrive_hip.h states the formulas) ---------------------------
+    def mlp_actor_critic_cost(self, policy_weights, value_weights, cost_weights, out, logp, value, cost_value, seed, tick, obs=None, group=-1,
+                              deterministic=False, in_dim=None):
+        """mlp_actor_critic with a cost critic beside actor and critic in the same launch (pgd_mlp_actor_critic_cost): `cost_weights` has
+        the shapes of `value_weights` (both are required), `cost_value` [N, A] float32 cuda receives its output.  Every other argument,
+        the noise and the tick rule as for mlp_actor_critic, whose bits `out`, `logp` and `value` are."""
+        t = self.torch
+        o = self.obs if obs is None else obs
+        o2 = o.view(-1, o.shape[-1])
+        rows = self.N * self.A
+        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == rows
+        self._check_actions(out)
+        for v in (logp, value, cost_value):
+            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == rows
+        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
+        assert k <= o2.shape[1]
+        nets, cnet = _abi.ActorCritic(), _abi.ValueNet()
+        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
+        nets.out_cols = int(policy_weights[4].shape[1])
+        nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
+        cnet.w1, cnet.b1, cnet.w2, cnet.b2, cnet.w3, cnet.b3 = self._network(cost_weights, k, 1)
+        assert value_weights[4].shape[1] == 1 and cost_weights[4].shape[1] == 1
+        if group < 0:
+            self._follow_stream()
+        _chk(self.L.pgd_mlp_actor_critic_cost(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k, C.byref(nets), C.byref(cnet),
+                                              int(seed) & 0xffffffff, int(tick) & 0xffffffff, _abi.AC_DETERMINISTIC if deterministic else 0,
+                                              C.c_void_p(out.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(value.data_ptr()),
+                                              C.c_void_p(cost_value.data_ptr())), "pgd_mlp_actor_critic_cost")
+        return out, logp, value, cost_value
+
+    def cost_gae(self, flags, done, cost_value, costs, gamma, lam, run, cost=None, adv=None, ret=None, ep_sum=None, ep_count=None):
+        """The costs of a rollout from its flags, their advantages and returns, and the episode-cost bookkeeping (pgd_cost_gae): flags
+        (int32), done (uint8) [T, rows...], cost_value [T + 1, rows...], time-major contiguous cuda tensors; `costs` = (out_of_road,
+        crash_vehicle, crash_object); `run` float32 [rows], read and written: the cost of every row's unfinished episode, carried from
+        rollout to rollout.  Returns (cost, adv, ret, ep_sum, ep_count): the first three float32 of flags' shape, ep_sum float32 and
+        ep_count int32 [rows] -- the episodes that finished in THIS rollout (each a buffer to write, allocated when None).  Asynchronous."""
+        t = self.torch
+        T = int(flags.shape[0])
+        rows = flags.numel() // max(T, 1)
+        f32 = dict(dtype=t.float32, device=flags.device)
+        cost = t.empty(flags.shape, **f32) if cost is None else cost
+        adv = t.empty(flags.shape, **f32) if adv is None else adv
+        ret = t.empty(flags.shape, **f32) if ret is None else ret
+        ep_sum = t.empty((rows, ), **f32) if ep_sum is None else ep_sum
+        ep_count = t.empty((rows, ), dtype=t.int32, device=flags.device) if ep_count is None else ep_count
+        for v, dt, n in ((flags, t.int32, T * rows), (done, t.uint8, T * rows), (cost_value, t.float32, (T + 1) * rows), (cost, t.float32, T * rows),
+                         (adv, t.float32, T * rows), (ret, t.float32, T * rows), (run, t.float32, rows), (ep_sum, t.float32, rows),
+                         (ep_count, t.int32, rows)):
+            assert v.is_cuda and v.dtype == dt and v.is_contiguous() and v.numel() == n
+        c3 = (C.c_float * 3)(*[float(c) for c in costs])
+        self._follow_stream()
+        _chk(self.L.pgd_cost_gae(self.h, C.c_void_p(flags.data_ptr()), C.c_void_p(done.data_ptr()), C.c_void_p(cost_value.data_ptr()), T, rows, c3,
+                                 float(gamma), float(lam), C.c_void_p(cost.data_ptr()), C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr()),
+                                 C.c_void_p(run.data_ptr()), C.c_void_p(ep_sum.data_ptr()), C.c_void_p(ep_count.data_ptr())), "pgd_cost_gae")
+        return cost, adv, ret, ep_sum, ep_count
+
+    def lagrange(self, ep_sum, ep_count, state, cost_limit, lr, lambda_max=100.0):
+        """One step of the Lagrange multiplier from a rollout's finished episodes (pgd_lagrange): `ep_sum` float32, `ep_count` int32 [rows]
+        as cost_gae wrote them; `state` float32 cuda [4] (_abi.LAGRANGE_STATE), zero before the first step, updated in place ON THE
+        DEVICE: lambda <- clamp(lambda + lr (J_c - cost_limit), 0, lambda_max) with J_c the mean cost of the episodes; no finished
+        episode: unchanged.  Asynchronous."""
+        t = self.torch
+        rows = int(ep_sum.numel())
+        assert ep_sum.is_cuda and ep_sum.dtype == t.float32 and ep_sum.is_contiguous() and rows >= 1
+        assert ep_count.is_cuda and ep_count.dtype == t.int32 and ep_count.is_contiguous() and ep_count.numel() == rows
+        assert state.is_cuda and state.dtype == t.float32 and state.is_contiguous() and state.numel() == 4
+        self._follow_stream()
+        _chk(self.L.pgd_lagrange(self.h, C.c_void_p(ep_sum.data_ptr()), C.c_void_p(ep_count.data_ptr()), rows, float(cost_limit), float(lr),
+                                 float(lambda_max), C.c_void_p(state.data_ptr())), "pgd_lagrange")
+        return state
+
+    def adv_mix(self, adv, cadv, state, out=None, adv_stats=None, cadv_stats=None):
+        """The advantage a PPO-Lagrangian policy sees (pgd_adv_mix): ((adv - m) s - lambda (cadv - m_c)) / (1 + lambda) -> `out`, with
+        (m, s) = `adv_stats` and m_c = cadv_stats[0] as adv_stats() wrote them (None: (0, 1) and 0) and lambda = state[0] (lagrange's
+        tensor), all read on the device.  `adv`, `cadv`, `out`: float32 cuda of one size.  Asynchronous."""
+        t = self.torch
+        n = int(adv.numel())
+        out = t.empty_like(adv) if out is None else out
+        for v in (adv, cadv, out):
+            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == n
+        assert n >= 1 and state.is_cuda and state.dtype == t.float32 and state.is_contiguous() and state.numel() == 4
+        for v in (adv_stats, cadv_stats):
+            assert v is None or (v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == 2)
+        self._follow_stream()
+        _chk(self.L.pgd_adv_mix(self.h, C.c_void_p(adv.data_ptr()), C.c_void_p(cadv.data_ptr()), n,
+                                C.c_void_p(adv_stats.data_ptr()) if adv_stats is not None else None,
+                                C.c_void_p(cadv_stats.data_ptr()) if cadv_stats is not None else None, C.c_void_p(state.data_ptr()),
+                                C.c_void_p(out.data_ptr())), "pgd_adv_mix")
+        return out
+
+    def ppo_cost_work_bytes(self, in_dim, rows):
+        """The scratch pgd_ppo_grad_cost needs for minibatches of up to `rows` positions (pgd_ppo_cost_work_bytes); 0: the call would
+        refuse them."""
+        return int(self.L.pgd_ppo_cost_work_bytes(int(in_dim), int(rows)))
+
+    def ppo_grad_cost(self, policy_weights, value_weights, cost_weights, policy_grads, value_grads, cost_grads, obs, actions, logp_old, adv, ret,
+                      cost_ret, stats, work, start=0, stride=1, rows=None, index=None, count=None, n_list=None, adv_stats=None, clip=0.2,
+                      vf_coef=0.5, cvf_coef=0.5, ent_coef=0.0, in_dim=None):
+        """ppo_grad with the cost critic as a third network (pgd_ppo_grad_cost): `cost_weights` / `cost_grads` of the value network's
+        shapes, `cost_ret` its targets by row, `cvf_coef` its loss coefficient; `adv` is normally adv_mix's output (`adv_stats` None).
+        `stats` float32 cuda [8] (_abi.PPO_COST_STATS: entry 7 is the cost critic's loss); `work` a cuda tensor of at least
+        ppo_cost_work_bytes(in_dim, rows) bytes.  Every other argument as for ppo_grad, whose bits the actor's and the critic's
+        gradients and stats[0..6] are.  Asynchronous."""
+        t = self.torch
+        o2 = obs.view(-1, obs.shape[-1])
+        n_rows = int(o2.shape[0])
+        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1
+        assert actions.is_cuda and actions.dtype == t.float32 and actions.is_contiguous() and actions.numel() == 2 * n_rows
+        for v in (logp_old, adv, ret, cost_ret):
+            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == n_rows
+        n_list = int((index.numel() if index is not None else n_rows) if n_list is None else n_list)
+        assert 0 <= n_list and (index is not None or n_list <= n_rows)
+        rows = int(max(1, -(-(n_list - int(start)) // int(stride))) if rows is None else rows)
+        assert int(start) >= 0 and int(stride) >= 1 and 1 <= rows <= _abi.PPO_ROWS_MAX
+        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
+        assert k <= o2.shape[1]
+        assert stats.is_cuda and stats.dtype == t.float32 and stats.is_contiguous() and stats.numel() == 8
+        need = self.ppo_cost_work_bytes(k, rows)
+        assert need > 0 and work.is_cuda and work.is_contiguous() and work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
+        if adv_stats is not None:
+            assert adv_stats.is_cuda and adv_stats.dtype == t.float32 and adv_stats.is_contiguous() and adv_stats.numel() == 2
+        nets, grads, cnet, cgrads = _abi.ActorCritic(), _abi.PPOGrads(), _abi.ValueNet(), _abi.ValueGrads()
+        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
+        nets.out_cols = int(policy_weights[4].shape[1])
+        grads.w1, grads.b1, grads.w2, grads.b2, grads.w3, grads.b3 = self._network(policy_grads, k, 4)
+        assert all(g.shape == w.shape for g, w in zip(policy_grads, policy_weights))
+        nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
+        grads.vw1, grads.vb1, grads.vw2, grads.vb2, grads.vw3, grads.vb3 = self._network(value_grads, k, 1)
+        cnet.w1, cnet.b1, cnet.w2, cnet.b2, cnet.w3, cnet.b3 = self._network(cost_weights, k, 1)
+        cgrads.w1, cgrads.b1, cgrads.w2, cgrads.b2, cgrads.w3, cgrads.b3 = self._network(cost_grads, k, 1)
+        assert all(w[4].shape[1] == 1 for w in (value_weights, value_grads, cost_weights, cost_grads))
+        b = _abi.PPOBatch()
+        b.obs, b.action, b.logp_old, b.adv, b.ret = o2.data_ptr(), actions.data_ptr(), logp_old.data_ptr(), adv.data_ptr(), ret.data_ptr()
+        b.adv_stats = adv_stats.data_ptr() if adv_stats is not None else None
+        ip, cp = self._list_args(index, count, n_list)
+        b.index, b.count = ip, cp
+        b.obs_stride, b.in_dim, b.n_rows, b.n_list, b.start, b.stride, b.rows = int(o2.stride(0)), k, n_rows, n_list, int(start), int(stride), rows
+        hp = _abi.PPOHyper(float(clip), float(vf_coef), float(ent_coef))
+        pc = _abi.PPOCost(cost_ret.data_ptr(), float(cvf_coef))
+        self._follow_stream()
+        _chk(self.L.pgd_ppo_grad_cost(self.h, C.byref(nets), C.byref(cnet), C.byref(b), C.byref(pc), C.byref(hp), C.byref(grads), C.byref(cgrads),
+                                      C.c_void_p(stats.data_ptr()), C.c_void_p(work.data_ptr()), work.numel() * work.element_size()),
+             "pgd_ppo_grad_cost")
+        return stats
 
     def step_lane_keep(self, tick, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):
         """One closed-loop step under the scripted lane-keeping policy (pgd_step_lane_keep): the policy reads the engine's own

@@ -7,7 +7,8 @@
         stats = learner.update(batch)       # [epochs * minibatches, 8] on the device: _abi.PPO_STATS
 
 What a trainer otherwise writes as framework code: an autograd pass over two 3-layer networks, an optimiser step, a gather of minibatch
-rows out of the time-major rollout and -- for the multi-agent collector -- a host read of batch["count"] before a minibatch can be sized.
+rows out of the time-major rollout and -- for the multi-agent collector -- a host read of batch["count"] before a minibatch can be sized.  (Constrained RL on the safe env: PPOLagLearner,
+below, the same update with a cost critic and a Lagrange multiplier.)
 Here: Engine.adv_stats once, then Engine.ppo_grad + Engine.adam for every epoch and minibatch.  Nothing in update() waits for the device
 or reads a device scalar, so one `collect(); update()` can be captured in a HIP graph and replayed: the Adam step number and the tick of
 the rollout's noise live in device memory and advance with every replay.
@@ -26,11 +27,14 @@ NAMES = ("w1", "b1", "w2", "b2", "w3", "b3")
 H = 256
 
 
-def flat_layout(in_dim, out_cols, has_critic=True):
-    """[(name, shape, offset)] of the weight tensors in the flat buffer, and its length in floats; offsets are multiples of 4."""
+def flat_layout(in_dim, out_cols, has_critic=True, has_cost_critic=False):
+    """[(name, shape, offset)] of the weight tensors in the flat buffer, and its length in floats; offsets are multiples of 4.  The cost
+    critic's six (cw1 .. cb3) lie behind the others."""
     shapes = [("w1", (in_dim, H)), ("b1", (H, )), ("w2", (H, H)), ("b2", (H, )), ("w3", (H, out_cols)), ("b3", (out_cols, ))]
     if has_critic:
         shapes += [("vw1", (in_dim, H)), ("vb1", (H, )), ("vw2", (H, H)), ("vb2", (H, )), ("vw3", (H, 1)), ("vb3", (1, ))]
+    if has_cost_critic:
+        shapes += [("cw1", (in_dim, H)), ("cb1", (H, )), ("cw2", (H, H)), ("cb2", (H, )), ("cw3", (H, 1)), ("cb3", (1, ))]
     out, o = [], 0
     for name, shape in shapes:
         n = 1
@@ -106,6 +110,90 @@ class PPOLearner:
                              batch["logp"], adv, batch["returns"], self.stats[k], self.work, start=start, stride=stride, rows=rows, index=index,
                              count=count, n_list=self.n_list, adv_stats=norm, clip=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
                              in_dim=self.in_dim)
+                eng.adam(self.params, self.grads, self.m, self.v, self.step, self.lr, betas=self.betas, eps=self.eps,
+                         max_grad_norm=self.max_grad_norm)
+                k += 1
+        return self.stats
+
+
+class PPOLagLearner:
+    """PPO-Lagrangian behind a SafeRolloutCollector: PPOLearner's update with a cost critic and a multiplier that holds the policy under
+    `cost_limit` (the mean cost of an episode), all on the device:
+
+        col = SafeRolloutCollector(env, policy_weights, value_weights, cost_weights, T=128)
+        learner = PPOLagLearner(col, cost_limit=1.0)
+        while training:
+            stats = learner.update(col.collect())     # [epochs * minibatches, 8]: _abi.PPO_COST_STATS
+        learner.lagrange_state                        # 4 floats on the device: _abi.LAGRANGE_STATE
+
+    update(batch) runs, in order: Engine.lagrange (lambda <- clamp(lambda + lambda_lr (J_c - cost_limit), 0, lambda_max) from the
+    episodes that finished in the rollout; none: unchanged), Engine.adv_stats for the reward and for the cost advantages, Engine.adv_mix
+    (((adv - m) s - lambda (cadv - m_c)) / (1 + lambda): the cost advantage centred, not rescaled), then Engine.ppo_grad_cost +
+    Engine.adam for every epoch and minibatch.  No host read: `collect(); update()` is capturable in one HIP graph, and a replay takes
+    the next multiplier step from the lambda it finds.  ONE flat buffer holds the eighteen weight tensors (flat_layout(...,
+    has_cost_critic=True)); the collector is handed the views.  `ppo_kwargs`: PPOLearner's arguments (normalise_advantages False: no
+    scaling of the reward advantage and no centring of either)."""
+    def __init__(self, collector, cost_limit, lambda_lr=0.05, lambda_init=0.0, lambda_max=100.0, cvf_coef=0.5, lr=3e-4, clip=0.2, vf_coef=0.5,
+                 ent_coef=0.0, epochs=4, minibatches=4, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-5, normalise_advantages=True):
+        eng = collector.engine
+        t = eng.torch
+        if int(epochs) < 1 or int(minibatches) < 1:
+            raise ValueError("PPOLagLearner: epochs = %r, minibatches = %r" % (epochs, minibatches))
+        if not (0.0 <= float(lambda_init) <= float(lambda_max)):
+            raise ValueError("PPOLagLearner: lambda_init = %r outside [0, lambda_max = %r]" % (lambda_init, lambda_max))
+        self.collector, self.engine = collector, eng
+        self.cost_limit, self.lambda_lr, self.lambda_max, self.cvf_coef = float(cost_limit), float(lambda_lr), float(lambda_max), float(cvf_coef)
+        self.lr, self.clip, self.vf_coef, self.ent_coef = float(lr), float(clip), float(vf_coef), float(ent_coef)
+        self.epochs, self.minibatches, self.max_grad_norm = int(epochs), int(minibatches), float(max_grad_norm)
+        self.betas, self.eps, self.normalise_advantages = (float(betas[0]), float(betas[1])), float(eps), bool(normalise_advantages)
+        pw, vw, cw = collector.policy_weights, collector.value_weights, collector.cost_weights
+        self.in_dim, self.out_cols = int(pw[0].shape[0]), int(pw[4].shape[1])
+        layout, total = flat_layout(self.in_dim, self.out_cols, has_cost_critic=True)
+        f32 = dict(dtype=t.float32, device=eng.device)
+        self.params, self.grads = t.zeros((total, ), **f32), t.zeros((total, ), **f32)
+        self.m, self.v = t.zeros((total, ), **f32), t.zeros((total, ), **f32)
+        self.step = t.zeros((4, ), dtype=t.int32, device=eng.device)  # pgd_adam's counter and record
+
+        def views(flat):
+            return tuple(flat[o:o + int(t.Size(shape).numel())].view(shape) for _, shape, o in layout)
+
+        wv, gv = views(self.params), views(self.grads)
+        for dst, src in zip(wv, tuple(pw) + tuple(vw) + tuple(cw)):
+            dst.copy_(src.view(dst.shape))
+        self.policy_weights, self.value_weights, self.cost_weights = wv[:6], wv[6:12], wv[12:]
+        self.policy_grads, self.value_grads, self.cost_grads = gv[:6], gv[6:12], gv[12:]
+        collector.set_weights(self.policy_weights, self.value_weights, self.cost_weights)
+        self.n_list = int(collector.rewards.numel())  # T * N: every row of the rollout
+        self.plan = minibatch_plan(self.n_list, self.minibatches)
+        need = eng.ppo_cost_work_bytes(self.in_dim, max(rows for _, _, rows in self.plan))
+        if need == 0:
+            raise ValueError("PPOLagLearner: the networks' input width %d is outside what pgd_ppo_grad_cost accepts" % self.in_dim)
+        self.work = t.empty(((need + 3) // 4, ), **f32)
+        self.adv_stats, self.cadv_stats = t.zeros((2, ), **f32), t.zeros((2, ), **f32)
+        self.mixed = t.zeros((self.n_list, ), **f32)  # the advantage the policy sees
+        self.lagrange_state = t.zeros((4, ), **f32)
+        self.lagrange_state[0] = float(lambda_init)
+        self.stats = t.zeros((self.epochs * self.minibatches, 8), **f32)
+
+    def update(self, batch):
+        """One multiplier step, then epochs x minibatches gradient steps on the rollout `batch` (what collector.collect() returned).
+        Returns the statistics tensor [epochs * minibatches, 8] (the same object every time).  Asynchronous: nothing here waits for the
+        device."""
+        eng = self.engine
+        eng.lagrange(batch["ep_cost_sum"], batch["ep_cost_count"], self.lagrange_state, self.cost_limit, self.lambda_lr, self.lambda_max)
+        adv, cadv = batch["advantages"], batch["cost_advantages"]
+        norm = cnorm = None
+        if self.normalise_advantages:
+            norm = eng.adv_stats(adv, out=self.adv_stats, n_list=self.n_list)
+            cnorm = eng.adv_stats(cadv, out=self.cadv_stats, n_list=self.n_list)
+        eng.adv_mix(adv, cadv, self.lagrange_state, out=self.mixed, adv_stats=norm, cadv_stats=cnorm)
+        k = 0
+        for _ in range(self.epochs):
+            for start, stride, rows in self.plan:
+                eng.ppo_grad_cost(self.policy_weights, self.value_weights, self.cost_weights, self.policy_grads, self.value_grads, self.cost_grads,
+                                  batch["obs"], batch["actions"], batch["logp"], self.mixed, batch["returns"], batch["cost_returns"], self.stats[k],
+                                  self.work, start=start, stride=stride, rows=rows, n_list=self.n_list, clip=self.clip, vf_coef=self.vf_coef,
+                                  cvf_coef=self.cvf_coef, ent_coef=self.ent_coef, in_dim=self.in_dim)
                 eng.adam(self.params, self.grads, self.m, self.v, self.step, self.lr, betas=self.betas, eps=self.eps,
                          max_grad_norm=self.max_grad_norm)
                 k += 1

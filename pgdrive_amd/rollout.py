@@ -24,6 +24,9 @@ replay and equals the eager call bit for bit.
 
 A done ends the episode for GAE, whatever ended it: there is no bootstrap through a horizon truncation from the terminal observation.
 
+Constrained RL on the safe env: SafeRolloutCollector, below -- this collector with a cost critic in the step's launch, the costs
+from the flags, their GAE and the books of episode costs.
+
 Multi-agent engines: MultiAgentRolloutCollector, below -- the same layout and carry with a seat axis, the networks over the rows of live
 seats only, GAE per agent and not per seat, and the index of the transitions a trainer may use.
 """
@@ -95,6 +98,71 @@ class RolloutCollector:
         eng.actor_critic_tick(None)
         eng.gae(self.rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
         self._tick.add_(T)
+        return self.batch
+
+
+class SafeRolloutCollector(RolloutCollector):
+    """RolloutCollector for constrained RL on the safe env (SafePGDriveEnv: a crash is a cost, not a termination):
+
+        col = SafeRolloutCollector(env, policy_weights, value_weights, cost_weights, T=128)
+        batch = col.collect()        # RolloutCollector's batch plus the cost side
+
+    A cost critic (a third network of the value network's shapes) is evaluated beside actor and critic by the ONE launch of every step
+    (Engine.mlp_actor_critic_cost); its stream `cost_values` [T + 1, N] is carried from rollout to rollout like `values`.  Behind the T
+    steps Engine.cost_gae turns the flags into costs -- out_of_road ? c0 : crash_vehicle ? c1 : crash_object ? c2 : 0, the precedence of
+    PGDriveEnv.cost_function --, forms their advantages and returns (cost_gamma, cost_lam) and keeps the books of episode costs.
+    `costs` = (out_of_road, crash_vehicle, crash_object); None: the three `*_cost` keys of the env's config, (1, 1, 1) for a bare engine.
+
+    Batch additions: costs, cost_advantages, cost_returns [T, N]; cost_values [T + 1, N]; ep_cost_sum float32 and ep_cost_count int32 [N]
+    -- the summed costs and the number of the episodes that FINISHED in this rollout, per env (what PPOLagLearner's multiplier reads).
+    The cost of an env's unfinished episode is carried in the collector's `running_cost` [N]: a caller who resets envs by hand (rather
+    than by the engine's auto reset, which reports a done) zeroes their entries.  A done finishes an episode for this bookkeeping
+    whatever ended it, a horizon truncation included, as it does for GAE.  Nothing in collect() waits for the device, and a captured
+    collect() equals the eager call bit for bit."""
+    def __init__(self, env_or_engine, policy_weights, value_weights, cost_weights, T, costs=None, gamma=0.99, lam=0.95, cost_gamma=0.99,
+                 cost_lam=0.95, seed=0):
+        self.cost_weights = tuple(cost_weights)
+        super().__init__(env_or_engine, policy_weights, value_weights, T, gamma=gamma, lam=lam, seed=seed)
+        eng = self.engine
+        t = eng.torch
+        if costs is None:
+            cfg = getattr(env_or_engine, "config", None)
+            costs = (1.0, 1.0, 1.0) if cfg is None or not hasattr(env_or_engine, "engine") else \
+                (cfg["out_of_road_cost"], cfg["crash_vehicle_cost"], cfg["crash_object_cost"])
+        self.costs = tuple(float(c) for c in costs)
+        if len(self.costs) != 3:
+            raise ValueError("SafeRolloutCollector: costs = %r" % (costs, ))
+        self.cost_gamma, self.cost_lam = float(cost_gamma), float(cost_lam)
+        T, N = self.T, eng.N
+        f32 = dict(dtype=t.float32, device=eng.device)
+        self.cost_values = t.zeros((T + 1, N), **f32)
+        self.cost = t.zeros((T, N), **f32)
+        self.cost_advantages = t.zeros((T, N), **f32)
+        self.cost_returns = t.zeros((T, N), **f32)
+        self.running_cost = t.zeros((N, ), **f32)
+        self.ep_cost_sum = t.zeros((N, ), **f32)
+        self.ep_cost_count = t.zeros((N, ), dtype=t.int32, device=eng.device)
+        self._carry = self._carry + (self.cost_values, )
+        self.batch.update(costs=self.cost, cost_values=self.cost_values, cost_advantages=self.cost_advantages, cost_returns=self.cost_returns,
+                          ep_cost_sum=self.ep_cost_sum, ep_cost_count=self.ep_cost_count)
+
+    def set_weights(self, policy_weights, value_weights, cost_weights=None):
+        """The networks of the rollouts from now on; cost_weights None: the cost critic stays what it is."""
+        super().set_weights(policy_weights, value_weights)
+        if cost_weights is not None:
+            self.cost_weights = tuple(cost_weights)
+
+    def _evaluate(self, row):
+        self.engine.mlp_actor_critic_cost(self.policy_weights, self.value_weights, self.cost_weights, self._actions[row], self._logp[row],
+                                          self.values[row], self.cost_values[row], self.seed, row, obs=self._obs[row])
+
+    def collect(self):
+        """T steps.  Returns RolloutCollector's dict with costs, cost_values, cost_advantages, cost_returns, ep_cost_sum, ep_cost_count
+        (the same objects every time, valid until the next call)."""
+        super().collect()
+        self.engine.cost_gae(self.flags, self.dones, self.cost_values, self.costs, self.cost_gamma, self.cost_lam, self.running_cost,
+                             cost=self.cost, adv=self.cost_advantages, ret=self.cost_returns, ep_sum=self.ep_cost_sum,
+                             ep_count=self.ep_cost_count)
         return self.batch
 
 

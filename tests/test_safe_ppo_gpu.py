@@ -1,0 +1,650 @@
+"""pgdrive_amd/csrc/pgd_safe.h on the device -- pgd_mlp_actor_critic_cost, pgd_cost_gae, pgd_lagrange, pgd_adv_mix, pgd_ppo_grad_cost --
+and pgdrive_amd.SafeRolloutCollector / PPOLagLearner, against the entry points they extend (bit for bit) and the float64 restatements of
+tests/safe_ppo_ref.py:
+
+* the forward launch with a third network: actions, log-probabilities and values are pgd_mlp_actor_critic's bits, the cost value is what
+  that call gives with the cost network as value network; eagerly and from a graph with a device tick; the refusals;
+* costs from flags, their GAE (pgd_gae's bits on the costs) and the episode-cost bookkeeping, exact with dyadic costs, carried over two
+  calls, and within TOL_EP of float64 otherwise;
+* the multiplier (one float32 ulp of float64; no episodes: every byte kept; replays of a one-call graph) and the mixed advantage (one
+  float32 rounding);
+* the gradients of three networks: pgd_ppo_grad's bits for actor and critic, the bits of a pgd_ppo_grad call with the cost network as
+  critic for the cost critic, float64 at ppo_ref.tolerances; listed rows, NaN where nothing is listed, n = 0, refusals;
+* the costs against the engine's own step info, and the closed loop on the safe env with traffic objects.
+
+Measured on the device (fractions of the tolerances): see the prints of each test.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import actor_critic_ref as ar
+from tests import ppo_ref as rf
+from tests import safe_ppo_ref as sr
+
+pytestmark = pytest.mark.gpu
+
+SENT = 7.0
+ERR_ARG = 1
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _bits(t):
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return a.view(np.int32) if a.dtype == np.float32 else a
+
+
+def _same(a, b):
+    return np.array_equal(_bits(a), _bits(b))
+
+
+def _ego_engine(descs, n):
+    """n envs, ego only, no lidar: the kernels under test need the engine for its rows, device and stream only."""
+    from pgdrive_amd import _abi
+    from pgdrive_amd.engine import Engine
+    from tests import util
+    mb, sb = util.make_banks(descs, n_maps=4, num_traffic=0)
+    return Engine(_abi.make_config(n, num_agents=1, num_traffic=0, num_lasers=0, seed=2), mb, sb)
+
+
+@pytest.fixture(scope="module")
+def eng(descs):
+    e = _ego_engine(descs, 1)
+    yield e
+    e.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. forward
+# ---------------------------------------------------------------------------------------------------------------------
+FWD_WIDTHS = (4, 5, 274, 416)
+FWD_ROWS = (1, 15, 16, 17, 33)
+
+
+def _fwd_case(in_dim, rows):
+    c = dict(name="safe_fwd", in_dim=in_dim, rows=rows, scaling=("unit", "normalised")[in_dim % 2], out_cols=4 + in_dim % 3, seed=in_dim + rows,
+             tick=3)
+    x, p, v = ar.build_case(**c)
+    assert x.shape[1] > in_dim and np.isnan(x[:, in_dim:]).all(), "the case has no NaN padding behind in_dim"
+    _, cw = ar.make_networks(np.random.default_rng([in_dim, rows, 99]), in_dim, 4)
+    return c, x, p, v, cw
+
+
+def _buffers(rows):
+    import torch
+    f = lambda *s: torch.full(s, SENT, dtype=torch.float32, device="cuda")  # noqa: E731
+    return f(rows, 1, 2), f(rows, 1), f(rows, 1)
+
+
+@pytest.mark.parametrize("rows", FWD_ROWS)
+def test_forward_is_the_two_network_launch_plus_a_critic_on_the_cost_network(descs, rows):
+    import torch
+    e = _ego_engine(descs, rows)
+    try:
+        for in_dim in FWD_WIDTHS:
+            c, x, p, v, cw = _fwd_case(in_dim, rows)
+            xd, pw, vw, cwd = _dev(x), tuple(_dev(w) for w in p), tuple(_dev(w) for w in v), tuple(_dev(w) for w in cw)
+            for det in (False, True):
+                a0, l0, v0 = _buffers(rows)
+                e.mlp_actor_critic(pw, vw, a0, l0, v0, c["seed"], c["tick"], obs=xd, in_dim=in_dim, deterministic=det)
+                a1, l1, c1 = _buffers(rows)
+                e.mlp_actor_critic(pw, cwd, a1, l1, c1, c["seed"], c["tick"], obs=xd, in_dim=in_dim, deterministic=det)
+                a2, l2, v2 = _buffers(rows)
+                cv = torch.full((rows, 1), SENT, dtype=torch.float32, device="cuda")
+                e.mlp_actor_critic_cost(pw, vw, cwd, a2, l2, v2, cv, c["seed"], c["tick"], obs=xd, in_dim=in_dim, deterministic=det)
+                e.sync()
+                assert _same(a2, a0) and _same(l2, l0) and _same(v2, v0), (in_dim, rows, det, "actor / critic differ from pgd_mlp_actor_critic")
+                assert _same(cv, c1), (in_dim, rows, det, "the cost value is not the critic's kernel on the cost network")
+                assert np.isfinite(cv.cpu().numpy()).all() and not _same(cv, v2)
+    finally:
+        e.close()
+
+
+def test_forward_from_a_graph_with_a_device_tick_and_the_refusals(descs):
+    import torch
+    from pgdrive_amd import _abi
+    rows, in_dim = 17, 274
+    e = _ego_engine(descs, rows)
+    try:
+        c, x, p, v, cw = _fwd_case(in_dim, rows)
+        xd, pw, vw, cwd = _dev(x), tuple(_dev(w) for w in p), tuple(_dev(w) for w in v), tuple(_dev(w) for w in cw)
+        tick = torch.zeros(1, dtype=torch.int32, device="cuda")
+        e.actor_critic_tick(tick)
+        eager = []
+        for k in range(3):
+            a, l, vv = _buffers(rows)
+            cv = torch.full((rows, 1), SENT, device="cuda")
+            tick.fill_(5 * k)
+            e.mlp_actor_critic_cost(pw, vw, cwd, a, l, vv, cv, 11, 2, obs=xd, in_dim=in_dim)
+            e.sync()
+            eager.append([t.clone() for t in (a, l, vv, cv)])
+        assert not _same(eager[0][0], eager[1][0]), "the device tick does not reach the noise"
+        a, l, vv = _buffers(rows)
+        cv = torch.full((rows, 1), SENT, device="cuda")
+        torch.cuda.synchronize()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=s):
+            e.mlp_actor_critic_cost(pw, vw, cwd, a, l, vv, cv, 11, 2, obs=xd, in_dim=in_dim)
+        torch.cuda.synchronize()
+        assert bool((cv == SENT).all()), "the capture itself ran the kernel"
+        with torch.cuda.stream(s):
+            for k in range(3):
+                tick.fill_(5 * k)
+                graph.replay()
+                torch.cuda.synchronize()
+                for got, want in zip((a, l, vv, cv), eager[k]):
+                    assert torch.equal(got, want), "replay %d differs from the eager call" % k
+        del graph
+        e.actor_critic_tick(None)
+
+        # refusals: PGD_ERR_ARG, every output keeps its sentinel
+        def call(nets, cnet, k=in_dim):
+            out = _buffers(rows) + (torch.full((rows, 1), SENT, device="cuda"), )
+            e._follow_stream()
+            rc = e.L.pgd_mlp_actor_critic_cost(e.h, -1, C.c_void_p(xd.data_ptr()), int(xd.stride(0)), k, C.byref(nets), C.byref(cnet), 1, 0, 0,
+                                               *[C.c_void_p(t.data_ptr()) for t in out])
+            e.sync()
+            torch.cuda.synchronize()
+            return rc, all(bool((t == SENT).all()) for t in out)
+
+        def structs():
+            nets, cnet = _abi.ActorCritic(), _abi.ValueNet()
+            nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = [w.data_ptr() for w in pw]
+            nets.out_cols = int(pw[4].shape[1])
+            nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = [w.data_ptr() for w in vw]
+            cnet.w1, cnet.b1, cnet.w2, cnet.b2, cnet.w3, cnet.b3 = [w.data_ptr() for w in cwd]
+            return nets, cnet
+
+        nets, cnet = structs()
+        rc, clean = call(nets, cnet)
+        assert rc == 0 and not clean, "the accepted call did not run"
+        for name in ("w1", "b1", "w2", "b2", "w3", "b3"):
+            nets, cnet = structs()
+            setattr(cnet, name, None)
+            assert call(nets, cnet) == (ERR_ARG, True), "null cost pointer %s" % name
+        nets, cnet = structs()
+        nets.vw2 = None
+        assert call(nets, cnet) == (ERR_ARG, True), "a missing value network is refused: both critics are required"
+        nets, cnet = structs()
+        assert call(nets, cnet, k=417) == (ERR_ARG, True)
+        nets, cnet = structs()
+        cnet.w1 = cwd[0].data_ptr() + 4
+        assert call(nets, cnet) == (ERR_ARG, True), "misaligned cost w1"
+        nets, cnet = structs()
+        nets.w1 = pw[0].data_ptr() + 4
+        assert call(nets, cnet) == (ERR_ARG, True), "misaligned w1"
+    finally:
+        e.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. pgd_cost_gae
+# ---------------------------------------------------------------------------------------------------------------------
+def _cost_gae(eng, flags, done, cv, costs, run, gamma=0.99, lam=0.95):
+    import torch
+    T, rows = flags.shape
+    f = lambda *s: torch.full(s, SENT, dtype=torch.float32, device="cuda")  # noqa: E731
+    run_d = _dev(run).clone()
+    out = eng.cost_gae(_dev(flags), _dev(done), _dev(cv), costs, gamma, lam, run_d, cost=f(T, rows), adv=f(T, rows), ret=f(T, rows), ep_sum=f(rows),
+                       ep_count=torch.full((rows, ), 77, dtype=torch.int32, device="cuda"))
+    eng.sync()
+    return dict(cost=out[0], cadv=out[1], cret=out[2], ep_sum=out[3], ep_count=out[4], run=run_d)
+
+
+@pytest.mark.parametrize("T", sr.COST_T)
+def test_cost_gae(eng, T):
+    for T_, rows, mode in sr.cost_gae_cases():
+        if T_ != T:
+            continue
+        # dyadic costs: everything exact
+        flags, done, cv, run = sr.build_cost_rollout(T, rows, mode, True)
+        ref = sr.cost_gae_f64(flags, done, cv, sr.DYADIC, 0.99, 0.95, run)
+        got = _cost_gae(eng, flags, done, cv, sr.DYADIC, run)
+        assert _same(got["cost"], ref["cost"]), (T, rows, mode, "cost")
+        adv, ret = eng.gae(got["cost"], _dev(cv), _dev(done), 0.99, 0.95)
+        eng.sync()
+        assert _same(got["cadv"], adv) and _same(got["cret"], ret), (T, rows, mode, "not pgd_gae's bits on the costs")
+        assert np.array_equal(got["ep_sum"].cpu().numpy().astype(np.float64), ref["ep_sum"]), (T, rows, mode)
+        assert np.array_equal(got["ep_count"].cpu().numpy(), ref["ep_count"]) and np.array_equal(got["run"].cpu().numpy().astype(np.float64), ref["run"])
+        if mode == "every":
+            assert (got["ep_count"].cpu().numpy() == T).all() and (got["run"].cpu().numpy() == 0).all()
+        if mode == "none":
+            assert (got["ep_count"].cpu().numpy() == 0).all() and (got["ep_sum"].cpu().numpy() == 0).all()
+        if T >= 2:   # two calls over halves with the carried running cost
+            h = T // 2
+            a = _cost_gae(eng, flags[:h], done[:h], cv[:h + 1], sr.DYADIC, run)
+            b = _cost_gae(eng, flags[h:], done[h:], cv[h:], sr.DYADIC, a["run"].cpu().numpy())
+            assert _same(b["run"], got["run"]) and _same(a["ep_sum"] + b["ep_sum"], got["ep_sum"])
+            assert _same(a["ep_count"] + b["ep_count"], got["ep_count"])
+        # costs that are no dyadic numbers: the emulation's bits, float64 within TOL_EP
+        flags, done, cv, run = sr.build_cost_rollout(T, rows, mode, False)
+        ref = sr.cost_gae_f64(flags, done, cv, sr.NONDYADIC, 0.99, 0.95, run)
+        got = _cost_gae(eng, flags, done, cv, sr.NONDYADIC, run)
+        rn, es, ec = sr.emulate_bookkeeping(ref["cost"], done, run)
+        assert _same(got["cost"], ref["cost"]) and _same(got["run"], rn) and _same(got["ep_sum"], es) and _same(got["ep_count"], ec), (T, rows, mode)
+        err = sr.bookkeeping_error(got["run"].cpu().numpy(), got["ep_sum"].cpu().numpy(), ref)
+        print("cost_gae T %d rows %d %s: sums %.3f of TOL_EP" % (T, rows, mode, err / sr.TOL_EP))
+        assert err < sr.TOL_EP
+        adv, ret = eng.gae(got["cost"], _dev(cv), _dev(done), 0.99, 0.95)
+        eng.sync()
+        assert _same(got["cadv"], adv) and _same(got["cret"], ret)
+
+
+def test_cost_gae_refuses_empty_shapes(eng):
+    import torch
+    z = torch.zeros(4, device="cuda")
+    zi = torch.zeros(4, dtype=torch.int32, device="cuda")
+    c3 = (C.c_float * 3)(1, 1, 1)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    for T, rows in ((0, 1), (1, 0)):
+        assert eng.L.pgd_cost_gae(eng.h, p(zi), p(zi), p(z), T, rows, c3, 0.99, 0.95, p(z), p(z), p(z), p(z), p(z), p(zi)) == ERR_ARG
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. pgd_lagrange
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows", sr.LAG_ROWS)
+def test_lagrange(eng, rows):
+    import torch
+    # no finished episode: every byte of the state stays, the NaN in slot 1 included
+    state = _dev(np.array([0.7, np.nan, 3.0, -2.0], dtype=np.float32))
+    before = state.clone()
+    eng.lagrange(_dev(np.full(rows, 5.0, dtype=np.float32)), torch.zeros(rows, dtype=torch.int32, device="cuda"), state, 1.0, 0.05, sr.LAG_MAX)
+    eng.sync()
+    assert _same(state, before)
+    for move in sr.LAG_MOVES:
+        ep_sum, count, st, limit, lr = sr.build_lagrange(rows, move)
+        want = sr.lagrange_f64(ep_sum, count, st, limit, lr, sr.LAG_MAX)
+        state = _dev(st)
+        eng.lagrange(_dev(ep_sum), _dev(count), state, limit, lr, sr.LAG_MAX)
+        eng.sync()
+        got = state.cpu().numpy()
+        assert abs(float(got[0]) - want[0]) <= sr.ulp32(want[0]) and abs(float(got[1]) - want[1]) <= sr.ulp32(want[1]), (rows, move, got, want)
+        assert got[2] == want[2] and got[3] == 0.0
+        if move == "clamp_zero":
+            assert got[0] == 0.0
+        if move == "clamp_max":
+            assert got[0] == np.float32(sr.LAG_MAX)
+        if move == "up":
+            assert got[0] > st[0]
+        if move == "down":
+            assert 0.0 < got[0] < st[0]
+    # three replays of a one-call graph against three eager calls
+    ep_sum, count, st, limit, lr = sr.build_lagrange(rows, "up")
+    es, ec = _dev(ep_sum), _dev(count)
+    eager, cap = _dev(st), _dev(st)
+    for _ in range(3):
+        eng.lagrange(es, ec, eager, limit, lr, 100.0)
+    eng.sync()
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=s):
+        eng.lagrange(es, ec, cap, limit, lr, 100.0)
+    torch.cuda.synchronize()
+    assert _same(cap, _dev(st)), "the capture itself took a step"
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            graph.replay()
+    torch.cuda.synchronize()
+    assert _same(cap, eager) and float(cap[0]) > float(st[0]) + 2.5 * lr * (float(cap[1]) - limit)
+    del graph
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. pgd_adv_mix
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", sr.MIX_N)
+def test_adv_mix(eng, n):
+    import torch
+    adv, cadv, s, cs = sr.build_mix(n)
+    worst = 0.0
+    for lam in sr.MIX_LAMBDA:
+        state = _dev(np.array([lam, 0.0, 0.0, 0.0], dtype=np.float32))
+        for given, given_c in ((True, True), (True, False), (False, True), (False, False)):
+            out = torch.full((n, ), SENT, dtype=torch.float32, device="cuda")
+            eng.adv_mix(_dev(adv), _dev(cadv), state, out=out, adv_stats=_dev(s) if given else None, cadv_stats=_dev(cs) if given_c else None)
+            eng.sync()
+            got = out.cpu().numpy()
+            want, bound = sr.adv_mix_f64(adv, cadv, s if given else None, cs if given_c else None, lam)
+            if lam == 0.0 and not given_c:
+                m, sc = (float(s[0]), float(s[1])) if given else (0.0, 1.0)
+                exact = ((adv.astype(np.float64) - m) * sc).astype(np.float32)
+                assert _same(got, exact), (n, given, "lambda = 0 is not (adv - m) s rounded once")
+            err = np.abs(got.astype(np.float64) - want)
+            assert (err <= bound).all(), (n, lam, given, given_c, float((err / bound).max()))
+            worst = max(worst, float((err / bound).max()))
+    print("adv_mix n %d: %.3f of one float32 ulp" % (n, worst))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. pgd_ppo_grad_cost
+# ---------------------------------------------------------------------------------------------------------------------
+def _shapes(in_dim, out_cols):
+    v = [(in_dim, 256), (256, ), (256, 256), (256, ), (256, 1), (1, )]
+    return [(in_dim, 256), (256, ), (256, 256), (256, ), (256, out_cols), (out_cols, )], v, list(v)
+
+
+class _Problem:
+    """The rollout arrays of a ppo_ref case and its cost side on the device: n_rows rows of which `where` hold the case's rows in
+    minibatch order, NaN in every array everywhere else; optionally a list over them."""
+    def __init__(self, c, listed=False):
+        case, ref = rf.case_and_reference(c)
+        cw, cost_ret = sr.cost_side(c)
+        rows = case["x"].shape[0]
+        self.c, self.case, self.ref, self.cw_np, self.cost_ret_np = c, case, ref, cw, cost_ret
+        if listed:
+            rng = np.random.default_rng(rows)
+            n_rows = 2 * rows + 5
+            where = rng.permutation(n_rows)[:rows]
+            index = np.concatenate([where, [0x7fffffff, -5, n_rows, 1 << 20, -(1 << 30), 3, 0, 1, 2]]).astype(np.int32)
+            self.index, self.count, self.n_list = _dev(index), _dev(np.array([rows], dtype=np.int32)), len(index)
+        else:
+            n_rows, where = rows, np.arange(rows)
+            self.index, self.count, self.n_list = None, None, rows
+        self.t = {}
+        for key, src, width in (("x", case["x"], case["x"].shape[1]), ("action", case["action"], 2), ("logp_old", case["logp_old"], 0),
+                                ("adv", case["adv"], 0), ("ret", case["ret"], 0), ("cost_ret", cost_ret, 0)):
+            a = np.full((n_rows, width) if width else (n_rows, ), np.nan, dtype=np.float32)
+            a[where] = src
+            self.t[key] = _dev(a)
+        self.n_rows = n_rows
+        self.stats_in = _dev(case["adv_stats"]) if case["adv_stats"] is not None else None
+        self.pw, self.vw, self.cw = [tuple(_dev(w) for w in net) for net in (case["policy"], case["value"], cw)]
+        self.k, self.oc = case["in_dim"], case["policy"][4].shape[1]
+
+
+def _fill(shapes):
+    import torch
+    return [torch.full(s, SENT, dtype=torch.float32, device="cuda") for s in shapes]
+
+
+def _two(eng, P, value, ret, vf_coef, count=None):
+    """pgd_ppo_grad (Engine.ppo_grad) with `value` as the value network -> [stats, six policy gradients, six value gradients]."""
+    import torch
+    ps, vs, _ = _shapes(P.k, P.oc)
+    pg, vg = _fill(ps), _fill(vs)
+    stats = torch.full((8, ), SENT, device="cuda")
+    work = torch.full((eng.ppo_work_bytes(P.k, P.n_list) // 4 + 1, ), float("nan"), device="cuda")
+    eng.ppo_grad(P.pw, value, pg, vg, P.t["x"], P.t["action"], P.t["logp_old"], P.t["adv"], ret, stats, work, rows=P.n_list, index=P.index,
+                 count=P.count if count is None else count, n_list=P.n_list, adv_stats=P.stats_in, clip=rf.CLIP, vf_coef=vf_coef,
+                 ent_coef=rf.ENT_COEF, in_dim=P.k)
+    eng.sync()
+    return [stats] + pg + vg
+
+
+def _three(eng, P, count=None, short_by=0, shift=0, expect=0):
+    """pgd_ppo_grad_cost through ctypes into sentinel-filled buffers -> [stats, 6 policy, 6 value, 6 cost gradients]; short_by / shift /
+    expect as in tests/test_ppo_update_gpu.py."""
+    import torch
+    from pgdrive_amd import _abi
+    ps, vs, cs = _shapes(P.k, P.oc)
+    pg, vg, cg = _fill(ps), _fill(vs), _fill(cs)
+    stats = torch.full((8, ), SENT, device="cuda")
+    need = eng.L.pgd_ppo_cost_work_bytes(P.k, P.n_list)
+    assert need > 0
+    work = torch.full(((need + 3) // 4 + shift, ), float("nan"), dtype=torch.float32, device="cuda")
+    nets, grads, cnet, cgr, b = _abi.ActorCritic(), _abi.PPOGrads(), _abi.ValueNet(), _abi.ValueGrads(), _abi.PPOBatch()
+    nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = [w.data_ptr() for w in P.pw]
+    nets.out_cols = P.oc
+    nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = [w.data_ptr() for w in P.vw]
+    cnet.w1, cnet.b1, cnet.w2, cnet.b2, cnet.w3, cnet.b3 = [w.data_ptr() for w in P.cw]
+    grads.w1, grads.b1, grads.w2, grads.b2, grads.w3, grads.b3 = [g.data_ptr() for g in pg]
+    grads.vw1, grads.vb1, grads.vw2, grads.vb2, grads.vw3, grads.vb3 = [g.data_ptr() for g in vg]
+    cgr.w1, cgr.b1, cgr.w2, cgr.b2, cgr.w3, cgr.b3 = [g.data_ptr() for g in cg]
+    b.obs, b.action, b.logp_old, b.adv, b.ret = [P.t[q].data_ptr() for q in ("x", "action", "logp_old", "adv", "ret")]
+    b.adv_stats = P.stats_in.data_ptr() if P.stats_in is not None else None
+    cnt = P.count if count is None else count
+    b.index = P.index.data_ptr() if P.index is not None else None
+    b.count = cnt.data_ptr() if cnt is not None else None
+    b.obs_stride, b.in_dim, b.n_rows, b.n_list, b.start, b.stride, b.rows = P.case["x"].shape[1], P.k, P.n_rows, P.n_list, 0, 1, P.n_list
+    hp = _abi.PPOHyper(rf.CLIP, rf.VF_COEF, rf.ENT_COEF)
+    pc = _abi.PPOCost(P.t["cost_ret"].data_ptr(), sr.CVF_COEF)
+    torch.cuda.synchronize()
+    eng._follow_stream()
+    rc = eng.L.pgd_ppo_grad_cost(eng.h, C.byref(nets), C.byref(cnet), C.byref(b), C.byref(pc), C.byref(hp), C.byref(grads), C.byref(cgr),
+                                 C.c_void_p(stats.data_ptr()), C.c_void_p(work.data_ptr() + 4 * shift), need - short_by)
+    assert rc == expect, rc
+    eng.sync()
+    torch.cuda.synchronize()
+    out = [stats] + pg + vg + cg
+    if expect:
+        assert all(bool((t == SENT).all()) for t in out), "a refused call wrote"
+        return None
+    assert not any(bool((t == SENT).any()) for t in out), "an output entry was not written"
+    return out
+
+
+def _contracts(eng, P, what, count=None):
+    """The two bit-for-bit contracts of pgd_ppo_grad_cost; returns its outputs."""
+    got = _three(eng, P, count=count)
+    main = _two(eng, P, P.vw, P.t["ret"], rf.VF_COEF, count=count)
+    cost = _two(eng, P, P.cw, P.t["cost_ret"], sr.CVF_COEF, count=count)
+    assert _same(got[0][:7], main[0][:7]), (what, "stats[0..6]")
+    for i in range(1, 13):
+        assert _same(got[i], main[i]), (what, "actor / critic gradient %d is not pgd_ppo_grad's" % i)
+    assert _same(got[0][7:], cost[0][2:3]), (what, "stats[7] is not L_v of the call with the cost network")
+    for i in range(6):
+        assert _same(got[13 + i], cost[7 + i]), (what, "cost critic gradient %d" % i)
+    return got
+
+
+def _check_f64(got, P, what):
+    g = [t.cpu().numpy() for t in got]
+    k = P.k
+    main64, cost64 = sr.loss_and_grads3_f64(P.case["x"][:, :k], P.case["action"], P.case["logp_old"], P.case["adv"], P.case["ret"], P.cost_ret_np,
+                                            P.case["policy"], P.case["value"], P.cw_np, adv_stats=P.case["adv_stats"])
+    gm, gc = sr.split_outputs(g[0], g[1:7], g[7:13], g[13:19])
+    tol_g, tol_s = rf.tolerances(int(main64["stats"][0]))
+    (eg, es), (egc, esc) = rf.grad_errors(gm, main64), rf.grad_errors(gc, cost64)
+    print("%s: gradients %.3f / cost critic %.3f of %.2e, statistics %.3f / %.3f of %.2e" % (what, eg / tol_g, egc / tol_g, tol_g, es / tol_s,
+                                                                                           esc / tol_s, tol_s))
+    assert max(eg, egc) < tol_g and max(es, esc) < tol_s, (what, eg, egc, tol_g, es, esc, tol_s)
+
+
+@pytest.mark.parametrize("in_dim", sr.GRAD_WIDTHS)
+def test_three_network_gradients(eng, in_dim):
+    """Every case of the width: the two contracts, plain; the 274-wide row counts (1 .. 1027) also behind a permuted index with a device
+    count, NaN in every unlisted row (cost_ret included) and garbage behind the count -- the same bits; float64 once per width and at
+    the largest row count."""
+    cases = [c for c in sr.grad_cases() if c["in_dim"] == in_dim]
+    assert cases and {c["out_cols"] for c in sr.grad_cases()} >= {4, 6}
+    for j, c in enumerate(cases):
+        P = _Problem(c)
+        plain = _contracts(eng, P, "plain %s" % c)
+        if c in sr.f64_cases():
+            _check_f64(plain, P, str(c))
+        if c["name"] == "rows":
+            Pl = _Problem(c, listed=True)
+            assert bool(Pl.t["cost_ret"].isnan().any()) or c["rows"] == 0
+            listed = _contracts(eng, Pl, "listed %s" % c)
+            for a, b in zip(plain, listed):
+                assert _same(a, b), (c, "the listed rows give other bits")
+
+
+def test_three_networks_empty_twice_and_refusals(eng):
+    import torch
+    c = [q for q in sr.grad_cases() if q["name"] == "rows" and q["rows"] == 33][0]
+    P = _Problem(c, listed=True)
+    zero = _three(eng, P, count=_dev(np.array([0], dtype=np.int32)))
+    for t in zero:
+        assert bool((t == 0).all()), "n = 0 leaves a nonzero output"
+    a, b = _three(eng, P), _three(eng, P)
+    for x, y in zip(a, b):
+        assert torch.equal(x, y), "not the same bytes twice"
+    assert _three(eng, P, short_by=1, expect=ERR_ARG) is None
+    assert _three(eng, P, shift=1, expect=ERR_ARG) is None
+    assert eng.ppo_cost_work_bytes(417, 16) == 0 and eng.ppo_cost_work_bytes(416, 16) > eng.ppo_work_bytes(416, 16, True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. / 7. the safe env with traffic objects
+# ---------------------------------------------------------------------------------------------------------------------
+SAFE_N = 16
+
+
+def _safe_env(horizon=None, step_info=False):
+    """16 safe envs at the seeds 1000 .. 1015 with an accident scene on every eligible block, each ego put 9 m behind a traffic object of
+    its route (the set-up of tests/test_env_gpu.py::test_safe_env_cost_to_reward_and_object_contact, all seeds at once)."""
+    import torch
+    from pgdrive_amd.vec_env import PGDriveVecEnv
+    from tests.parity import teleport_to_objects
+    env = PGDriveVecEnv(dict(num_envs=SAFE_N, start_seed=1000, environment_num=SAFE_N, accident_prob=1.0, traffic_density=0.05, safe_rl_env=True,
+                             horizon=horizon, step_info=step_info))
+    env.reset(force_seed=np.arange(1000, 1000 + SAFE_N))
+    f, i, ei = env.engine.get_state()
+    assert teleport_to_objects(env.map_bank, env.scen_bank, np.arange(SAFE_N), f, i) >= 3
+    env.engine.set_state(f, i, ei)
+    env.engine.sync()
+    torch.cuda.synchronize()
+    return env
+
+
+def test_costs_are_the_step_infos_own():
+    import torch
+    env = _safe_env(step_info=True)
+    try:
+        eng = env.engine
+        T = 30
+        act = torch.tensor([0.0, 0.3], device="cuda").repeat(SAFE_N, 1).contiguous()
+        flags = torch.zeros((T, SAFE_N), dtype=torch.int32, device="cuda")
+        dones = torch.zeros((T, SAFE_N), dtype=torch.uint8, device="cuda")
+        info_cost = torch.zeros((T, SAFE_N), device="cuda")
+        for t in range(T):
+            _, _, d, fl = env.step(act)
+            flags[t].copy_(fl.view(-1))
+            dones[t].copy_(d.view(-1))
+            info_cost[t].copy_(env.last_info["cost"].view(-1))
+        cfg = env.config
+        costs = (cfg["out_of_road_cost"], cfg["crash_vehicle_cost"], cfg["crash_object_cost"])
+        cost, _, _, ep_sum, ep_count = eng.cost_gae(flags, dones, torch.zeros((T + 1, SAFE_N), device="cuda"), costs, 0.99, 0.95,
+                                                    torch.zeros(SAFE_N, device="cuda"))
+        eng.sync()
+        torch.cuda.synchronize()
+        assert torch.equal(cost, info_cost), "pgd_cost_gae's costs are not step info's"
+        assert float(cost.sum()) > 0, "no cost in 30 steps towards the traffic objects"
+        assert np.array_equal(cost.cpu().numpy().astype(np.float64), env.cost_from_flags(flags))
+    finally:
+        env.close()
+
+
+def _safe_networks(D):
+    p, v = ar.make_networks(np.random.default_rng(0), D, 4)
+    _, cw = ar.make_networks(np.random.default_rng(1), D, 4)
+    p[4][:] = 0.0
+    p[5][:] = (0.0, 0.3, -5.0, -5.0)
+    return [tuple(_dev(w) for w in net) for net in (p, v, cw)]
+
+
+SAFE_T = 32
+SAFE_KW = dict(lr=3e-4, epochs=2, minibatches=2, lambda_lr=0.05)
+
+
+def _state(L):
+    import torch
+    torch.cuda.synchronize()
+    return dict(params=L.params.clone(), m=L.m.clone(), v=L.v.clone(), step=L.step.clone(), stats=L.stats.clone(), grads=L.grads.clone(),
+                lagrange=L.lagrange_state.clone(), mixed=L.mixed.clone())
+
+
+def test_closed_loop_on_the_safe_env():
+    import torch
+    from pgdrive_amd import PPOLagLearner, SafeRolloutCollector
+    env, env_g = _safe_env(horizon=20), _safe_env(horizon=20)
+    try:
+        eng = env.engine
+        pw, vw, cw = _safe_networks(eng.D)
+        col = SafeRolloutCollector(env, pw, vw, cw, SAFE_T, seed=3)
+        assert col.costs == (1.0, 1.0, 1.0)
+        LC = PPOLagLearner(col, cost_limit=1e6, **SAFE_KW)       # (each learner hands its views to the collector: the last one's are used)
+        LB = PPOLagLearner(col, cost_limit=-1.0, **SAFE_KW)      # the by-hand twin's buffers
+        LA = PPOLagLearner(col, cost_limit=-1.0, **SAFE_KW)
+        assert col.policy_weights[0].data_ptr() == LA.params.data_ptr() and col.cost_weights[0].data_ptr() == LA.cost_weights[0].data_ptr()
+        assert torch.equal(LA.params, LB.params) and torch.equal(LA.params, LC.params)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        want = []
+        run = np.zeros(SAFE_N)
+        with torch.cuda.stream(s), torch.no_grad():
+            for it in range(3):
+                batch = col.collect()
+                torch.cuda.synchronize()
+                # the rollout: costs from the flags, the books against a host recomputation with the carried running cost
+                flags, dones = batch["flags"].cpu().numpy(), batch["dones"].cpu().numpy()
+                assert np.array_equal(batch["costs"].cpu().numpy().astype(np.float64), env.cost_from_flags(batch["flags"]))
+                rn, es, ec, _, _ = sr.bookkeeping(batch["costs"].cpu().numpy(), dones, run)
+                assert np.array_equal(batch["ep_cost_sum"].cpu().numpy().astype(np.float64), es) and np.array_equal(batch["ep_cost_count"].cpu().numpy(), ec)
+                assert np.array_equal(col.running_cost.cpu().numpy().astype(np.float64), rn)
+                run = rn
+                assert int(ec.sum()) >= SAFE_N, "an env did not end an episode within the horizon"
+                if it == 0:
+                    acts = batch["actions"].cpu().numpy()   # (before the first update: w3 = 0, the action is b3's up to e^-5 noise)
+                    assert np.abs(acts - np.array([0.0, 0.3])).max() < 0.05, "the policy is not the constant action"
+                    assert float(batch["costs"].sum()) > 0, "no cost in the first rollout towards the traffic objects"
+                    cadv, cret = eng.gae(batch["costs"], batch["cost_values"], batch["dones"], 0.99, 0.95)
+                    torch.cuda.synchronize()
+                    assert torch.equal(cadv, batch["cost_advantages"]) and torch.equal(cret, batch["cost_returns"])
+                    # cost_limit 1e6: lambda stays at 0 (and update() leaves the batch alone: the twins below see the same rollout)
+                    LC.update(batch)
+                    torch.cuda.synchronize()
+                    assert float(LC.lagrange_state[0]) == 0.0 and float(LC.lagrange_state[2]) == float(ec.sum())
+                    # the same Engine calls by hand, on LB's buffers
+                    eng.lagrange(batch["ep_cost_sum"], batch["ep_cost_count"], LB.lagrange_state, -1.0, 0.05, 100.0)
+                    norm = eng.adv_stats(batch["advantages"], out=LB.adv_stats)
+                    cnorm = eng.adv_stats(batch["cost_advantages"], out=LB.cadv_stats)
+                    eng.adv_mix(batch["advantages"], batch["cost_advantages"], LB.lagrange_state, out=LB.mixed, adv_stats=norm, cadv_stats=cnorm)
+                    k = 0
+                    for _ in range(2):
+                        for j in range(2):
+                            eng.ppo_grad_cost(LB.policy_weights, LB.value_weights, LB.cost_weights, LB.policy_grads, LB.value_grads, LB.cost_grads,
+                                              batch["obs"], batch["actions"], batch["logp"], LB.mixed, batch["returns"], batch["cost_returns"],
+                                              LB.stats[k], LB.work, start=j, stride=2, rows=SAFE_T * SAFE_N // 2, cvf_coef=0.5)
+                            eng.adam(LB.params, LB.grads, LB.m, LB.v, LB.step, 3e-4, eps=1e-5, max_grad_norm=0.5)
+                            k += 1
+                lam_before = float(LA.lagrange_state[0])
+                stats = LA.update(batch)
+                assert stats.shape == (4, 8)
+                want.append(_state(LA))
+                st = stats.cpu().numpy()
+                assert np.isfinite(st).all() and (st[:, 0] == SAFE_T * SAFE_N // 2).all() and (st[:, 7] > 0).all()
+                lam, jc = float(LA.lagrange_state[0]), float(LA.lagrange_state[1])
+                assert lam > lam_before, "cost_limit -1: lambda does not grow"
+                if it == 0:
+                    hand = _state(LB)
+                    for key in hand:
+                        assert torch.equal(want[0][key], hand[key]), "%s differs from the calls made by hand" % key
+                    w = float(np.float32(0.05)) * (float(es.sum()) / int(ec.sum()) + 1.0)
+                    assert abs(lam - w) <= sr.ulp32(w) and abs(jc - es.sum() / ec.sum()) <= sr.ulp32(jc), (lam, w, jc)
+        # collect(); update() captured in one graph behind one eager iteration, replayed twice, from the same start on a second env
+        pw, vw, cw = _safe_networks(env_g.engine.D)
+        col_g = SafeRolloutCollector(env_g, pw, vw, cw, SAFE_T, seed=3)
+        LG = PPOLagLearner(col_g, cost_limit=-1.0, **SAFE_KW)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s), torch.no_grad():
+            LG.update(col_g.collect())
+            got = _state(LG)
+            for key in got:
+                assert torch.equal(got[key], want[0][key]), "second env, eager iteration: %s" % key
+            graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(graph, stream=s):
+            LG.update(col_g.collect())
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s), torch.no_grad():
+            for it in (1, 2):
+                graph.replay()
+                got = _state(LG)
+                for key in got:
+                    assert torch.equal(got[key], want[it][key]), "graph replay %d: %s differs from the eager iteration" % (it, key)
+        del graph
+    finally:
+        env.close()
+        env_g.close()
