@@ -38,6 +38,8 @@ static Switches read_switches() {
   return {on("PGD_NO_FUSE"), on("PGD_NO_FIX"), on("PGD_JIT_FORCE"), on("PGD_ROW_OBSERVE"), on("PGD_NO_STATE_IN_STEP"),
           rowz && rowz[0] != '0', on("PGD_NO_UNI"), pack ? (atoi(pack) != 0 ? 1 : 0) : -1, on("PGD_NO_IMASK") ? 0 : (on("PGD_IMASK") ? 1 : -1)};
 }
+// The kernels that take more than 48 KB of dynamic LDS at wide inputs: their limit is raised once per engine (raise_lds_limit)
+enum LdsKernel { LDS_MLP, LDS_MLP_TANH, LDS_MLP_BF, LDS_MLP_BF_TANH, LDS_AC, LDS_AC_ROWS, LDS_AC_COST, LDS_PPO_ROWS, LDS_PPO_ROWS_COST, LDS_KERNELS };
 struct pgd_engine {
   PgdDev d;
   Switches sw;
@@ -84,14 +86,12 @@ struct pgd_engine {
   hipModule_t jit_mod;
   hipFunction_t jit_fn;
   bool jit_obj;
-  bool ac_attr;      // pgd_mlp_actor_critic: likewise
   const uint32_t* ac_tick;  // pgd_actor_critic_tick: the device counter added to every launch's tick (null: none)
-  bool acr_attr;     // pgd_mlp_actor_critic_rows: as ac_attr, for its own kernel
   uint32_t* cmp_live;   // pgd_live_rows: block counts of the compaction, a segment for the whole engine and one per env group (pgd_create allocates it)
   uint32_t* cmp_index;  // pgd_rollout_index: block counts [cmp_index_cap], grown outside graph captures
   size_t cmp_index_cap;
   std::vector<uint32_t*>* cmp_retired;  // cmp_index of smaller rollouts: graphs captured with them may still be replayed (freed by pgd_destroy)
-  bool mlp_attr[4];  // pgd_mlp_policy / pgd_mlp_policy_prepared: the kernel's dynamic LDS limit has been raised on this engine's device
+  bool lds_raised[LDS_KERNELS];  // raise_lds_limit: the kernel's dynamic LDS limit has been raised on this engine's device
   int jit_geom[4];   // sub, epw, pack_obs, use_imask at the time of the build
   char jit_name[96];
   bool prof_fused;
@@ -99,8 +99,6 @@ struct pgd_engine {
   ulonglong2* rowz;  // multi-agent engines: PgdDev::rowz (zero-row marks + the tag of the buffer they describe, per env)
   struct { const float* obs; float k_lat, k_head, v_target, noise; uint32_t tick; } lk;  // pgd_step_lane_keep: this launch's scripted policy (obs null: none)
   float* lk_act;     // pgd_step_lane_keep on engines that cannot take the policy into the step kernel: the actions in between
-  bool ppo_attr;     // pgd_ppo_grad: as ac_attr, for k_ppo_rows
-  bool safe_attr[2]; // pgd_mlp_actor_critic_cost, pgd_ppo_grad_cost: as ac_attr, for their kernels
 };
 
 // The default row layout (see observe_agent): the STD instantiations of k_step
@@ -121,6 +119,51 @@ static int env_group(const pgd_engine* h, int group, EnvGroup& g) {
   g.count = h->d.N / h->n_groups;
   g.first = group * g.count;
   g.stream = h->gstreams[group];
+  return PGD_OK;
+}
+
+// A launch with `lds` bytes of dynamic LDS: above 48 KB the kernel's limit has to be raised first, once per engine and kernel (per engine =
+// per device: a process may hold engines on several GPUs)
+static int raise_lds_limit(pgd_engine* h, LdsKernel which, const void* kernel, size_t lds) {
+  if (lds <= 49152 || h->lds_raised[which]) return PGD_OK;
+  HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+  h->lds_raised[which] = true;
+  return PGD_OK;
+}
+
+// The networks of a training entry point (the three pgd_mlp_actor_critic*, the two pgd_ppo_grad*), checked before any HIP call: every
+// pointer of the actor and of the cost critic (null: the call has none), the critic's six all set or -- where the call allows it -- all
+// null, the widths, and the 16-byte reads of every present network's w1 / b1 / w2 / b2.  *has_critic: whether the critic is there.
+static bool six_set(const float* a, const float* b, const float* c, const float* d, const float* e, const float* f) { return a && b && c && d && e && f; }
+static bool reads_16(const float* w1, const float* b1, const float* w2, const float* b2) {
+  return (((uintptr_t)w1 | (uintptr_t)b1 | (uintptr_t)w2 | (uintptr_t)b2) & 15u) == 0u;
+}
+static bool nets_ok(const pgd_actor_critic* a, const pgd_value_net* cost, bool critic_optional, int in_dim, int obs_stride, bool* has_critic) {
+  if (!a || !six_set(a->w1, a->b1, a->w2, a->b2, a->w3, a->b3)) return false;
+  *has_critic = six_set(a->vw1, a->vb1, a->vw2, a->vb2, a->vw3, a->vb3);
+  if (!*has_critic && !(critic_optional && !a->vw1 && !a->vb1 && !a->vw2 && !a->vb2 && !a->vw3 && !a->vb3)) return false;
+  if (cost && !six_set(cost->w1, cost->b1, cost->w2, cost->b2, cost->w3, cost->b3)) return false;
+  if (in_dim < 4 || in_dim > 4096 || obs_stride < in_dim || a->out_cols < AC_HEAD) return false;
+  return reads_16(a->w1, a->b1, a->w2, a->b2) && reads_16(a->vw1, a->vb1, a->vw2, a->vb2) && (!cost || reads_16(cost->w1, cost->b1, cost->w2, cost->b2));
+}
+// ... and the buffers their gradients go to (pgd_ppo_grad*): the critic's only with a critic
+static bool grads_ok(const pgd_ppo_grads* g, const pgd_value_grads* cost, bool has_critic) {
+  return g && six_set(g->w1, g->b1, g->w2, g->b2, g->w3, g->b3) && (!has_critic || six_set(g->vw1, g->vb1, g->vw2, g->vb2, g->vw3, g->vb3)) &&
+         (!cost || six_set(cost->w1, cost->b1, cost->w2, cost->b2, cost->w3, cost->b3));
+}
+
+// The shared tail of the actor-critic forward family, behind the caller's refusals: the rows of the env group (or of all envs) on its
+// stream, the raised LDS limit of `kernel`, then the caller's launch(es) over those rows
+struct AcRows { int row0, rows; uint32_t row_base; size_t lds; hipStream_t stream; };
+template <typename Launch>
+static int ac_forward(pgd_engine* h, int group, LdsKernel which, const void* kernel, int in_dim, Launch launch) {
+  HIPCHK(hipSetDevice(h->device));
+  EnvGroup g;
+  { int rc = env_group(h, group, g); if (rc) return rc; }
+  const size_t lds = ac_lds_bytes(in_dim);
+  { int rc = raise_lds_limit(h, which, kernel, lds); if (rc) return rc; }
+  launch(AcRows{g.first * h->d.A, g.count * h->d.A, (uint32_t)h->d.cfg.env_base * (uint32_t)h->d.A, lds, g.stream});
+  HIPCHK(hipGetLastError());
   return PGD_OK;
 }
 
@@ -902,10 +945,7 @@ int pgd_mlp_policy(pgd_handle h, int group, const float* d_obs, int obs_stride, 
   { int rc = env_group(h, group, g); if (rc) return rc; }
   const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
   auto kern = final_tanh ? k_mlp_policy<true> : k_mlp_policy<false>;
-  if (lds > 49152 && !h->mlp_attr[final_tanh ? 1 : 0]) {  // (per engine = per device: a process may hold engines on several GPUs)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    h->mlp_attr[final_tanh ? 1 : 0] = true;
-  }
+  { int rc = raise_lds_limit(h, final_tanh ? LDS_MLP_TANH : LDS_MLP, reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3((rows + MLP_ROWS - 1) / MLP_ROWS), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs, row0, rows, obs_stride, in_dim,
                      d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, out_cols, d_actions);
   HIPCHK(hipGetLastError());
@@ -938,10 +978,7 @@ int pgd_mlp_policy_prepared(pgd_handle h, int group, const float* d_obs, int obs
   { int rc = env_group(h, group, g); if (rc) return rc; }
   const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
   auto kern = final_tanh ? k_mlp_policy_bf<true> : k_mlp_policy_bf<false>;
-  if (lds > 49152 && !h->mlp_attr[2 + (final_tanh ? 1 : 0)]) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    h->mlp_attr[2 + (final_tanh ? 1 : 0)] = true;
-  }
+  { int rc = raise_lds_limit(h, final_tanh ? LDS_MLP_BF_TANH : LDS_MLP_BF, reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3((rows + MLP_ROWS - 1) / MLP_ROWS), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs, row0, rows, obs_stride, in_dim,
                      reinterpret_cast<const uint4*>(d_prepared), d_actions);
   HIPCHK(hipGetLastError());
@@ -957,30 +994,13 @@ int pgd_actor_critic_tick(pgd_handle h, const uint32_t* d_tick) {
 
 int pgd_mlp_actor_critic(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets, uint32_t seed,
                          uint32_t tick, uint32_t flags, float* d_actions, float* d_logp, float* d_value) {
-  if (!h || !d_obs || !nets || !d_actions || !d_logp || (flags & ~PGD_AC_DETERMINISTIC) != 0u) return PGD_ERR_ARG;
-  if (!nets->w1 || !nets->b1 || !nets->w2 || !nets->b2 || !nets->w3 || !nets->b3) return PGD_ERR_ARG;
-  const float* vp[6] = {nets->vw1, nets->vb1, nets->vw2, nets->vb2, nets->vw3, nets->vb3};
-  int n_value = 0;
-  for (const float* p : vp) n_value += p ? 1 : 0;
-  if ((n_value != 0 && n_value != 6) || (n_value == 6 && !d_value)) return PGD_ERR_ARG;
-  if (in_dim < 4 || in_dim > 4096 || obs_stride < in_dim || nets->out_cols < AC_HEAD) return PGD_ERR_ARG;
-  if ((((uintptr_t)nets->w1 | (uintptr_t)nets->w2 | (uintptr_t)nets->b1 | (uintptr_t)nets->b2 | (uintptr_t)nets->vw1 | (uintptr_t)nets->vw2 |
-        (uintptr_t)nets->vb1 | (uintptr_t)nets->vb2) & 15u) != 0u) return PGD_ERR_ARG;  // 16-byte reads
-  const size_t lds = ac_lds_bytes(in_dim);
-  if (lds > 65536) return PGD_ERR_ARG;
-  HIPCHK(hipSetDevice(h->device));
-  EnvGroup g;
-  { int rc = env_group(h, group, g); if (rc) return rc; }
-  const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
-  if (lds > 49152 && !h->ac_attr) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_actor_critic), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    h->ac_attr = true;
-  }
-  hipLaunchKernelGGL(k_mlp_actor_critic, dim3((rows + MLP_ROWS - 1) / MLP_ROWS, n_value ? 2 : 1), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs,
-                     row0, rows, obs_stride, in_dim, *nets, seed, tick, h->ac_tick, (uint32_t)h->d.cfg.env_base * (uint32_t)h->d.A, flags,
-                     d_actions, d_logp, d_value);
-  HIPCHK(hipGetLastError());
-  return PGD_OK;
+  bool critic;
+  if (!h || !d_obs || !d_actions || !d_logp || (flags & ~PGD_AC_DETERMINISTIC) != 0u || !nets_ok(nets, nullptr, true, in_dim, obs_stride, &critic) ||
+      (critic && !d_value) || ac_lds_bytes(in_dim) > 65536) return PGD_ERR_ARG;
+  return ac_forward(h, group, LDS_AC, reinterpret_cast<const void*>(k_mlp_actor_critic), in_dim, [&](const AcRows& r) {
+    hipLaunchKernelGGL(k_mlp_actor_critic, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream, d_obs,
+                       r.row0, r.rows, obs_stride, in_dim, *nets, seed, tick, h->ac_tick, r.row_base, flags, d_actions, d_logp, d_value);
+  });
 }
 
 int pgd_gae(pgd_handle h, const float* d_reward, const float* d_value, const uint8_t* d_done, int T, int rows, float gamma, float lam,
@@ -1029,33 +1049,17 @@ int pgd_rollout_index(pgd_handle h, const uint32_t* d_flags, int T, int rows, in
 int pgd_mlp_actor_critic_rows(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets, uint32_t seed,
                               uint32_t tick, uint32_t flags, const int32_t* d_rows, const int32_t* d_count, float* d_actions, float* d_logp,
                               float* d_value) {
-  if (!h || !d_obs || !nets || !d_rows || !d_count || !d_actions || !d_logp || (flags & ~PGD_AC_DETERMINISTIC) != 0u) return PGD_ERR_ARG;
-  if (!nets->w1 || !nets->b1 || !nets->w2 || !nets->b2 || !nets->w3 || !nets->b3) return PGD_ERR_ARG;
-  const float* vp[6] = {nets->vw1, nets->vb1, nets->vw2, nets->vb2, nets->vw3, nets->vb3};
-  int n_value = 0;
-  for (const float* p : vp) n_value += p ? 1 : 0;
-  if ((n_value != 0 && n_value != 6) || (n_value == 6 && !d_value)) return PGD_ERR_ARG;
-  if (in_dim < 4 || in_dim > 4096 || obs_stride < in_dim || nets->out_cols < AC_HEAD) return PGD_ERR_ARG;
-  if ((((uintptr_t)nets->w1 | (uintptr_t)nets->w2 | (uintptr_t)nets->b1 | (uintptr_t)nets->b2 | (uintptr_t)nets->vw1 | (uintptr_t)nets->vw2 |
-        (uintptr_t)nets->vb1 | (uintptr_t)nets->vb2) & 15u) != 0u) return PGD_ERR_ARG;  // 16-byte reads
-  const size_t lds = ac_lds_bytes(in_dim);
-  if (lds > 65536) return PGD_ERR_ARG;
-  HIPCHK(hipSetDevice(h->device));
-  EnvGroup g;
-  { int rc = env_group(h, group, g); if (rc) return rc; }
-  const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
-  if (lds > 49152 && !h->acr_attr) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_actor_critic_rows), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    h->acr_attr = true;
-  }
-  // the defined outputs of the rows that are not listed, then the listed rows (the host does not know how many: a grid for all)
-  hipLaunchKernelGGL(k_ac_clear_rows, dim3((rows + CMP_THREADS - 1) / CMP_THREADS), dim3(CMP_THREADS), 0, g.stream, row0, rows, d_actions, d_logp,
-                     n_value ? d_value : nullptr);
-  hipLaunchKernelGGL(k_mlp_actor_critic_rows, dim3((rows + MLP_ROWS - 1) / MLP_ROWS, n_value ? 2 : 1), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs,
-                     d_rows, d_count, row0, rows, obs_stride, in_dim, *nets, seed, tick, h->ac_tick,
-                     (uint32_t)h->d.cfg.env_base * (uint32_t)h->d.A, flags, d_actions, d_logp, d_value);
-  HIPCHK(hipGetLastError());
-  return PGD_OK;
+  bool critic;
+  if (!h || !d_obs || !d_rows || !d_count || !d_actions || !d_logp || (flags & ~PGD_AC_DETERMINISTIC) != 0u ||
+      !nets_ok(nets, nullptr, true, in_dim, obs_stride, &critic) || (critic && !d_value) || ac_lds_bytes(in_dim) > 65536) return PGD_ERR_ARG;
+  return ac_forward(h, group, LDS_AC_ROWS, reinterpret_cast<const void*>(k_mlp_actor_critic_rows), in_dim, [&](const AcRows& r) {
+    // the defined outputs of the rows that are not listed, then the listed rows (the host does not know how many: a grid for all)
+    hipLaunchKernelGGL(k_ac_clear_rows, dim3((r.rows + CMP_THREADS - 1) / CMP_THREADS), dim3(CMP_THREADS), 0, r.stream, r.row0, r.rows, d_actions,
+                       d_logp, critic ? d_value : nullptr);
+    hipLaunchKernelGGL(k_mlp_actor_critic_rows, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream,
+                       d_obs, d_rows, d_count, r.row0, r.rows, obs_stride, in_dim, *nets, seed, tick, h->ac_tick, r.row_base, flags, d_actions,
+                       d_logp, d_value);
+  });
 }
 
 int pgd_gae_masked(pgd_handle h, const float* d_reward, const float* d_value, const uint8_t* d_done, const uint32_t* d_flags, int T, int rows,

@@ -543,56 +543,24 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ param, const f
   param[i] = (float)((double)param[i] - (double)lr * ((double)mi * (double)f[2]) / (sqrt((double)vi * (double)f[3]) + (double)eps));
 }
 
+// scratch of a gradient call over n_nets networks (0: in_dim or rows out of range)
+static size_t ppo_work_bytes(int in_dim, int rows, int n_nets) {
+  if (in_dim < 4 || in_dim > 4096 || ppo_lds_bytes(in_dim) > 65536 || rows < 1 || rows > PGD_PPO_ROWS_MAX) return 0;
+  return sizeof(float) * ppo_work(in_dim, rows, n_nets).total;
+}
+
+// pgd_ppo_grad and pgd_ppo_grad_cost are one body: pgd_safe.h, behind the three-network kernels
+static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
+                           const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
+                           float* d_stats, void* d_work, size_t work_bytes);
+
 extern "C" {
 
-size_t pgd_ppo_work_bytes(int in_dim, int rows, int has_critic) {
-  if (in_dim < 4 || in_dim > 4096 || ppo_lds_bytes(in_dim) > 65536 || rows < 1 || rows > PGD_PPO_ROWS_MAX) return 0;
-  return sizeof(float) * ppo_work(in_dim, rows, has_critic ? 2 : 1).total;
-}
+size_t pgd_ppo_work_bytes(int in_dim, int rows, int has_critic) { return ppo_work_bytes(in_dim, rows, has_critic ? 2 : 1); }
 
 int pgd_ppo_grad(pgd_handle h, const pgd_actor_critic* nets, const pgd_ppo_batch* batch, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads,
                  float* d_stats, void* d_work, size_t work_bytes) {
-  if (!h || !nets || !batch || !hyper || !grads || !d_stats || !d_work) return PGD_ERR_ARG;
-  if (!nets->w1 || !nets->b1 || !nets->w2 || !nets->b2 || !nets->w3 || !nets->b3) return PGD_ERR_ARG;
-  if (!grads->w1 || !grads->b1 || !grads->w2 || !grads->b2 || !grads->w3 || !grads->b3) return PGD_ERR_ARG;
-  const float* vp[6] = {nets->vw1, nets->vb1, nets->vw2, nets->vb2, nets->vw3, nets->vb3};
-  float* const gp[6] = {grads->vw1, grads->vb1, grads->vw2, grads->vb2, grads->vw3, grads->vb3};
-  int n_value = 0;
-  for (const float* p : vp) n_value += p ? 1 : 0;
-  if (n_value != 0 && n_value != 6) return PGD_ERR_ARG;
-  if (n_value == 6)
-    for (float* p : gp)
-      if (!p) return PGD_ERR_ARG;
-  const pgd_ppo_batch& b = *batch;
-  if (!b.obs || !b.action || !b.logp_old || !b.adv || (n_value && !b.ret)) return PGD_ERR_ARG;
-  if (b.in_dim < 4 || b.in_dim > 4096 || b.obs_stride < b.in_dim || nets->out_cols < AC_HEAD) return PGD_ERR_ARG;
-  if ((((uintptr_t)nets->w1 | (uintptr_t)nets->w2 | (uintptr_t)nets->b1 | (uintptr_t)nets->b2 | (uintptr_t)nets->vw1 | (uintptr_t)nets->vw2 |
-        (uintptr_t)nets->vb1 | (uintptr_t)nets->vb2 | (uintptr_t)d_work) & 15u) != 0u) return PGD_ERR_ARG;  // 16-byte reads
-  const size_t lds = ppo_lds_bytes(b.in_dim);
-  if (lds > 65536) return PGD_ERR_ARG;
-  if (b.rows < 1 || b.rows > PGD_PPO_ROWS_MAX || b.n_list < 0 || b.n_rows < 1 || b.start < 0 || b.stride < 1) return PGD_ERR_ARG;
-  if ((long long)b.start + (long long)(b.rows - 1) * b.stride > 2147483647ll) return PGD_ERR_ARG;
-  if (!b.index && b.n_list > b.n_rows) return PGD_ERR_ARG;  // (without an index a list position IS a row)
-  const int n_nets = n_value ? 2 : 1;
-  const PpoWork wk = ppo_work(b.in_dim, b.rows, n_nets);
-  if (work_bytes < sizeof(float) * wk.total) return PGD_ERR_ARG;
-  HIPCHK(hipSetDevice(h->device));
-  if (lds > 49152 && !h->ppo_attr) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ppo_rows), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    h->ppo_attr = true;
-  }
-  float* work = static_cast<float*>(d_work);
-  hipStream_t s = h->stream;
-  hipLaunchKernelGGL(k_ppo_prep, dim3(MLP_H, n_nets), dim3(MLP_H), 0, s, *nets, work);
-  hipLaunchKernelGGL(k_ppo_rows, dim3(wk.R16 / 16, n_nets), dim3(WAVE * MLP_WAVES), lds, s, *nets, b, *hyper, work);
-  hipLaunchKernelGGL(k_ppo_wgrad, dim3(wk.mt, wk.P, n_nets), dim3(WAVE * MLP_WAVES), 0, s, b, work);
-  hipLaunchKernelGGL(k_ppo_reduce, dim3(16 * wk.mt, n_nets), dim3(MLP_H), 0, s, b, *grads, (int)nets->out_cols, work);
-  if (nets->out_cols > 4)
-    hipLaunchKernelGGL(k_ppo_zero_head, dim3(std::max(1, std::min((int)nets->out_cols - 16, 64))), dim3(MLP_H), 0, s, grads->w3, grads->b3,
-                       (int)nets->out_cols);
-  hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, b, *grads, n_value ? 1 : 0, work, d_stats);
-  HIPCHK(hipGetLastError());
-  return PGD_OK;
+  return ppo_grad_launch(h, nets, nullptr, batch, nullptr, hyper, grads, nullptr, d_stats, d_work, work_bytes);
 }
 
 int pgd_adv_stats(pgd_handle h, const float* d_adv, const int32_t* d_index, const int32_t* d_count, int n_list, float* d_out) {

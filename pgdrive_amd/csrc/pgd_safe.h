@@ -190,36 +190,66 @@ __global__ __launch_bounds__(256) void k_ppo_stats_cost(const pgd_ppo_batch b, c
   ppo_stats_block(b, gr, 1, cost_b3, work, stats);
 }
 
+// ---- the one body of pgd_ppo_grad (cost_net, cost, cost_grads null) and pgd_ppo_grad_cost: one, two or three networks -------------------
+static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
+                           const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
+                           float* d_stats, void* d_work, size_t work_bytes) {
+  bool critic;
+  if (!h || !batch || !hyper || !d_stats || !d_work || (reinterpret_cast<uintptr_t>(d_work) & 15u) != 0u) return PGD_ERR_ARG;
+  const pgd_ppo_batch& b = *batch;
+  if (!nets_ok(nets, cost_net, !cost_net, b.in_dim, b.obs_stride, &critic) || !grads_ok(grads, cost_grads, critic)) return PGD_ERR_ARG;
+  if (!b.obs || !b.action || !b.logp_old || !b.adv || (critic && !b.ret) || (cost && !cost->cost_ret)) return PGD_ERR_ARG;
+  const size_t lds = ppo_lds_bytes(b.in_dim);
+  if (lds > 65536) return PGD_ERR_ARG;
+  if (b.rows < 1 || b.rows > PGD_PPO_ROWS_MAX || b.n_list < 0 || b.n_rows < 1 || b.start < 0 || b.stride < 1) return PGD_ERR_ARG;
+  if ((long long)b.start + (long long)(b.rows - 1) * b.stride > 2147483647ll) return PGD_ERR_ARG;
+  if (!b.index && b.n_list > b.n_rows) return PGD_ERR_ARG;  // (without an index a list position IS a row)
+  const int n_nets = cost_net ? 3 : (critic ? 2 : 1), out_cols = (int)nets->out_cols;
+  const PpoWork wk = ppo_work(b.in_dim, b.rows, n_nets);
+  if (work_bytes < sizeof(float) * wk.total) return PGD_ERR_ARG;
+  HIPCHK(hipSetDevice(h->device));
+  { int rc = cost_net ? raise_lds_limit(h, LDS_PPO_ROWS_COST, reinterpret_cast<const void*>(k_ppo_rows_cost), lds)
+                      : raise_lds_limit(h, LDS_PPO_ROWS, reinterpret_cast<const void*>(k_ppo_rows), lds);
+    if (rc) return rc; }
+  float* work = static_cast<float*>(d_work);
+  hipStream_t s = h->stream;
+  const dim3 prep(MLP_H, n_nets), rows(wk.R16 / 16, n_nets), reduce(16 * wk.mt, n_nets), tile(WAVE * MLP_WAVES);
+  if (cost_net) {
+    const SafeNets sn = {*nets, *cost_net};
+    hipLaunchKernelGGL(k_ppo_prep_cost, prep, dim3(MLP_H), 0, s, sn, work);
+    hipLaunchKernelGGL(k_ppo_rows_cost, rows, tile, lds, s, sn, b, *hyper, *cost, work);
+  } else {
+    hipLaunchKernelGGL(k_ppo_prep, prep, dim3(MLP_H), 0, s, *nets, work);
+    hipLaunchKernelGGL(k_ppo_rows, rows, tile, lds, s, *nets, b, *hyper, work);
+  }
+  hipLaunchKernelGGL(k_ppo_wgrad, dim3(wk.mt, wk.P, n_nets), tile, 0, s, b, work);
+  if (cost_net) {
+    const SafeGrads sg = {*grads, *cost_grads};
+    hipLaunchKernelGGL(k_ppo_reduce_cost, reduce, dim3(MLP_H), 0, s, b, sg, out_cols, work);
+  } else {
+    hipLaunchKernelGGL(k_ppo_reduce, reduce, dim3(MLP_H), 0, s, b, *grads, out_cols, work);
+  }
+  if (out_cols > 4)
+    hipLaunchKernelGGL(k_ppo_zero_head, dim3(std::max(1, std::min(out_cols - 16, 64))), dim3(MLP_H), 0, s, grads->w3, grads->b3, out_cols);
+  if (cost_net) hipLaunchKernelGGL(k_ppo_stats_cost, dim3(1), dim3(256), 0, s, b, *grads, cost_grads->b3, work, d_stats);
+  else hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, b, *grads, critic ? 1 : 0, work, d_stats);
+  HIPCHK(hipGetLastError());
+  return PGD_OK;
+}
+
 extern "C" {
 
 int pgd_mlp_actor_critic_cost(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets,
                               const pgd_value_net* cost_net, uint32_t seed, uint32_t tick, uint32_t flags, float* d_actions, float* d_logp,
                               float* d_value, float* d_cost_value) {
-  if (!h || !d_obs || !nets || !cost_net || !d_actions || !d_logp || !d_value || !d_cost_value || (flags & ~PGD_AC_DETERMINISTIC) != 0u)
-    return PGD_ERR_ARG;
-  if (!nets->w1 || !nets->b1 || !nets->w2 || !nets->b2 || !nets->w3 || !nets->b3) return PGD_ERR_ARG;
-  if (!nets->vw1 || !nets->vb1 || !nets->vw2 || !nets->vb2 || !nets->vw3 || !nets->vb3) return PGD_ERR_ARG;
-  if (!cost_net->w1 || !cost_net->b1 || !cost_net->w2 || !cost_net->b2 || !cost_net->w3 || !cost_net->b3) return PGD_ERR_ARG;
-  if (in_dim < 4 || in_dim > 4096 || obs_stride < in_dim || nets->out_cols < AC_HEAD) return PGD_ERR_ARG;
-  if ((((uintptr_t)nets->w1 | (uintptr_t)nets->w2 | (uintptr_t)nets->b1 | (uintptr_t)nets->b2 | (uintptr_t)nets->vw1 | (uintptr_t)nets->vw2 |
-        (uintptr_t)nets->vb1 | (uintptr_t)nets->vb2 | (uintptr_t)cost_net->w1 | (uintptr_t)cost_net->w2 | (uintptr_t)cost_net->b1 |
-        (uintptr_t)cost_net->b2) & 15u) != 0u) return PGD_ERR_ARG;  // 16-byte reads
-  const size_t lds = ac_lds_bytes(in_dim);
-  if (lds > 65536) return PGD_ERR_ARG;
-  HIPCHK(hipSetDevice(h->device));
-  EnvGroup g;
-  { int rc = env_group(h, group, g); if (rc) return rc; }
-  const int rows = g.count * h->d.A, row0 = g.first * h->d.A;
-  if (lds > 49152 && !h->safe_attr[0]) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_actor_critic_cost), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    h->safe_attr[0] = true;
-  }
-  const SafeNets sn = {*nets, *cost_net};
-  hipLaunchKernelGGL(k_mlp_actor_critic_cost, dim3((rows + MLP_ROWS - 1) / MLP_ROWS, 3), dim3(WAVE * MLP_WAVES), lds, g.stream, d_obs, row0, rows,
-                     obs_stride, in_dim, sn, seed, tick, h->ac_tick, (uint32_t)h->d.cfg.env_base * (uint32_t)h->d.A, flags, d_actions, d_logp,
-                     d_value, d_cost_value);
-  HIPCHK(hipGetLastError());
-  return PGD_OK;
+  bool critic;
+  if (!h || !d_obs || !cost_net || !d_actions || !d_logp || !d_value || !d_cost_value || (flags & ~PGD_AC_DETERMINISTIC) != 0u ||
+      !nets_ok(nets, cost_net, false, in_dim, obs_stride, &critic) || ac_lds_bytes(in_dim) > 65536) return PGD_ERR_ARG;
+  return ac_forward(h, group, LDS_AC_COST, reinterpret_cast<const void*>(k_mlp_actor_critic_cost), in_dim, [&](const AcRows& r) {
+    const SafeNets sn = {*nets, *cost_net};
+    hipLaunchKernelGGL(k_mlp_actor_critic_cost, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, 3), dim3(WAVE * MLP_WAVES), r.lds, r.stream, d_obs, r.row0,
+                       r.rows, obs_stride, in_dim, sn, seed, tick, h->ac_tick, r.row_base, flags, d_actions, d_logp, d_value, d_cost_value);
+  });
 }
 
 int pgd_cost_gae(pgd_handle h, const uint32_t* d_flags, const uint8_t* d_done, const float* d_cost_value, int T, int rows, const float costs[3],
@@ -251,53 +281,13 @@ int pgd_adv_mix(pgd_handle h, const float* d_adv, const float* d_cadv, int n, co
   return PGD_OK;
 }
 
-size_t pgd_ppo_cost_work_bytes(int in_dim, int rows) {
-  if (in_dim < 4 || in_dim > 4096 || ppo_lds_bytes(in_dim) > 65536 || rows < 1 || rows > PGD_PPO_ROWS_MAX) return 0;
-  return sizeof(float) * ppo_work(in_dim, rows, 3).total;
-}
+size_t pgd_ppo_cost_work_bytes(int in_dim, int rows) { return ppo_work_bytes(in_dim, rows, 3); }
 
 int pgd_ppo_grad_cost(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
                       const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
                       float* d_stats, void* d_work, size_t work_bytes) {
-  if (!h || !nets || !cost_net || !batch || !cost || !hyper || !grads || !cost_grads || !d_stats || !d_work) return PGD_ERR_ARG;
-  if (!nets->w1 || !nets->b1 || !nets->w2 || !nets->b2 || !nets->w3 || !nets->b3) return PGD_ERR_ARG;
-  if (!nets->vw1 || !nets->vb1 || !nets->vw2 || !nets->vb2 || !nets->vw3 || !nets->vb3) return PGD_ERR_ARG;
-  if (!cost_net->w1 || !cost_net->b1 || !cost_net->w2 || !cost_net->b2 || !cost_net->w3 || !cost_net->b3) return PGD_ERR_ARG;
-  if (!grads->w1 || !grads->b1 || !grads->w2 || !grads->b2 || !grads->w3 || !grads->b3) return PGD_ERR_ARG;
-  if (!grads->vw1 || !grads->vb1 || !grads->vw2 || !grads->vb2 || !grads->vw3 || !grads->vb3) return PGD_ERR_ARG;
-  if (!cost_grads->w1 || !cost_grads->b1 || !cost_grads->w2 || !cost_grads->b2 || !cost_grads->w3 || !cost_grads->b3) return PGD_ERR_ARG;
-  const pgd_ppo_batch& b = *batch;
-  if (!b.obs || !b.action || !b.logp_old || !b.adv || !b.ret || !cost->cost_ret) return PGD_ERR_ARG;
-  if (b.in_dim < 4 || b.in_dim > 4096 || b.obs_stride < b.in_dim || nets->out_cols < AC_HEAD) return PGD_ERR_ARG;
-  if ((((uintptr_t)nets->w1 | (uintptr_t)nets->w2 | (uintptr_t)nets->b1 | (uintptr_t)nets->b2 | (uintptr_t)nets->vw1 | (uintptr_t)nets->vw2 |
-        (uintptr_t)nets->vb1 | (uintptr_t)nets->vb2 | (uintptr_t)cost_net->w1 | (uintptr_t)cost_net->w2 | (uintptr_t)cost_net->b1 |
-        (uintptr_t)cost_net->b2 | (uintptr_t)d_work) & 15u) != 0u) return PGD_ERR_ARG;  // 16-byte reads
-  const size_t lds = ppo_lds_bytes(b.in_dim);
-  if (lds > 65536) return PGD_ERR_ARG;
-  if (b.rows < 1 || b.rows > PGD_PPO_ROWS_MAX || b.n_list < 0 || b.n_rows < 1 || b.start < 0 || b.stride < 1) return PGD_ERR_ARG;
-  if ((long long)b.start + (long long)(b.rows - 1) * b.stride > 2147483647ll) return PGD_ERR_ARG;
-  if (!b.index && b.n_list > b.n_rows) return PGD_ERR_ARG;  // (without an index a list position IS a row)
-  const PpoWork wk = ppo_work(b.in_dim, b.rows, 3);
-  if (work_bytes < sizeof(float) * wk.total) return PGD_ERR_ARG;
-  HIPCHK(hipSetDevice(h->device));
-  if (lds > 49152 && !h->safe_attr[1]) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ppo_rows_cost), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
-    h->safe_attr[1] = true;
-  }
-  const SafeNets sn = {*nets, *cost_net};
-  const SafeGrads sg = {*grads, *cost_grads};
-  float* work = static_cast<float*>(d_work);
-  hipStream_t s = h->stream;
-  hipLaunchKernelGGL(k_ppo_prep_cost, dim3(MLP_H, 3), dim3(MLP_H), 0, s, sn, work);
-  hipLaunchKernelGGL(k_ppo_rows_cost, dim3(wk.R16 / 16, 3), dim3(WAVE * MLP_WAVES), lds, s, sn, b, *hyper, *cost, work);
-  hipLaunchKernelGGL(k_ppo_wgrad, dim3(wk.mt, wk.P, 3), dim3(WAVE * MLP_WAVES), 0, s, b, work);
-  hipLaunchKernelGGL(k_ppo_reduce_cost, dim3(16 * wk.mt, 3), dim3(MLP_H), 0, s, b, sg, (int)nets->out_cols, work);
-  if (nets->out_cols > 4)
-    hipLaunchKernelGGL(k_ppo_zero_head, dim3(std::max(1, std::min((int)nets->out_cols - 16, 64))), dim3(MLP_H), 0, s, grads->w3, grads->b3,
-                       (int)nets->out_cols);
-  hipLaunchKernelGGL(k_ppo_stats_cost, dim3(1), dim3(256), 0, s, b, *grads, cost_grads->b3, work, d_stats);
-  HIPCHK(hipGetLastError());
-  return PGD_OK;
+  if (!cost_net || !cost || !cost_grads) return PGD_ERR_ARG;
+  return ppo_grad_launch(h, nets, cost_net, batch, cost, hyper, grads, cost_grads, d_stats, d_work, work_bytes);
 }
 
 }  // extern "C"

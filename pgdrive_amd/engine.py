@@ -130,6 +130,11 @@ def _np_p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _p(t):
+    """The device pointer of a tensor, as an argument of the C ABI."""
+    return C.c_void_p(t.data_ptr())
+
+
 class PgdError(RuntimeError):
     pass
 
@@ -179,6 +184,7 @@ class Engine:
         self._own_ptrs = tuple(C.c_void_p(t.data_ptr()) for t in (self.obs, self.reward, self.done, self.flags))
         self._seen_out = []  # caller-supplied observation tensors of the last steps, kept alive (see step)
         self.step_info = None  # the dict of enable_step_info while the step info is on
+        self.n_groups = 1  # env groups of set_groups (1 = none)
         torch.cuda.synchronize(dev)
 
     def _follow_stream(self):
@@ -375,6 +381,59 @@ class Engine:
         assert b1.numel() == 256 and b2.numel() == 256 and b3.numel() == w3.shape[1]
         return [w.data_ptr() for w in weights]
 
+    def _nets(self, st, policy, value, k):
+        """`st` (ActorCritic of weights, PPOGrads of gradient buffers) with the checked pointers of the policy's six tensors and, unless
+        `value` is None, of the critic's."""
+        st.w1, st.b1, st.w2, st.b2, st.w3, st.b3 = self._network(policy, k, 4)
+        if value is not None:
+            st.vw1, st.vb1, st.vw2, st.vb2, st.vw3, st.vb3 = self._network(value, k, 1)
+            assert value[4].shape[1] == 1
+        return st
+
+    def _value_net(self, st, weights, k):
+        """`st` (ValueNet, ValueGrads) with the checked pointers of a critic-shaped network's six tensors."""
+        st.w1, st.b1, st.w2, st.b2, st.w3, st.b3 = self._network(weights, k, 1)
+        assert weights[4].shape[1] == 1
+        return st
+
+    def _ac_args(self, policy_weights, value_weights, cost_weights, out, per_row, seed, tick, obs, group, deterministic, in_dim):
+        """What the mlp_actor_critic* calls share, checked: the observation rows, `out`, the `per_row` outputs, the networks (value_weights
+        and cost_weights None: none) -> the leading arguments of the C call, up to its flags.  Follows the caller's stream (group < 0)."""
+        t = self.torch
+        o = self.obs if obs is None else obs
+        o2 = o.view(-1, o.shape[-1])
+        rows = self.N * self.A
+        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == rows
+        self._check_actions(out)
+        assert cost_weights is None or value_weights is not None, "the cost critic comes with a critic"
+        for v in per_row:
+            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == rows
+        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
+        assert k <= o2.shape[1]
+        nets = self._nets(_abi.ActorCritic(), policy_weights, value_weights, k)
+        nets.out_cols = int(policy_weights[4].shape[1])
+        cnet = () if cost_weights is None else (C.byref(self._value_net(_abi.ValueNet(), cost_weights, k)), )
+        if group < 0:
+            self._follow_stream()
+        return (self.h, int(group), _p(o2), int(o2.stride(0)), k, C.byref(nets), *cnet, int(seed) & 0xffffffff, int(tick) & 0xffffffff,
+                _abi.AC_DETERMINISTIC if deterministic else 0)
+
+    def _rollout_buffers(self, lead, table):
+        """The tensors of a rollout call checked: `lead` is [T, rows...]; `table` rows are (tensor, dtype, extra) with extra 0: T * rows
+        entries, 1: (T + 1) * rows, None: rows; a tensor that is None is allocated (of lead's shape, or [rows]).  Follows the caller's
+        stream.  -> T, rows, the tensors."""
+        t = self.torch
+        T = int(lead.shape[0])
+        rows = lead.numel() // max(T, 1)
+        out = []
+        for v, dt, extra in table:
+            if v is None:
+                v = t.empty(lead.shape if extra == 0 else (rows, ), dtype=dt, device=lead.device)
+            assert v.is_cuda and v.dtype == dt and v.is_contiguous() and v.numel() == (rows if extra is None else (T + extra) * rows)
+            out.append(v)
+        self._follow_stream()
+        return T, rows, out
+
     def mlp_actor_critic(self, policy_weights, value_weights, out, logp, value, seed, tick, obs=None, group=-1, deterministic=False,
                          in_dim=None):
         """A sampled action, its log-probability and the value estimate of every observation row in one launch (pgd_mlp_actor_critic).
@@ -383,28 +442,9 @@ class Engine:
         `out` [N, A, 2] (unclipped: step clips), `logp` and `value` [N, A]: float32 cuda.  The noise is a function of (seed, global row,
         tick); `tick` is added to the device counter of actor_critic_tick, if one is set.  deterministic: the action is the mean.
         `obs`, `group`, `in_dim` as for mlp_policy."""
-        t = self.torch
-        o = self.obs if obs is None else obs
-        o2 = o.view(-1, o.shape[-1])
-        rows = self.N * self.A
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == rows
-        self._check_actions(out)
-        for v in (logp, ) if value_weights is None else (logp, value):
-            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == rows
-        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
-        assert k <= o2.shape[1]
-        nets = _abi.ActorCritic()
-        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
-        nets.out_cols = int(policy_weights[4].shape[1])
-        if value_weights is not None:
-            nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
-            assert value_weights[4].shape[1] == 1
-        if group < 0:
-            self._follow_stream()
-        _chk(self.L.pgd_mlp_actor_critic(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k, C.byref(nets),
-                                         int(seed) & 0xffffffff, int(tick) & 0xffffffff, _abi.AC_DETERMINISTIC if deterministic else 0,
-                                         C.c_void_p(out.data_ptr()), C.c_void_p(logp.data_ptr()),
-                                         C.c_void_p(value.data_ptr()) if value_weights is not None else None), "pgd_mlp_actor_critic")
+        a = self._ac_args(policy_weights, value_weights, None, out, (logp, ) if value_weights is None else (logp, value), seed, tick, obs, group,
+                          deterministic, in_dim)
+        _chk(self.L.pgd_mlp_actor_critic(*a, _p(out), _p(logp), _p(value) if value_weights is not None else None), "pgd_mlp_actor_critic")
         return out, logp, value
 
     def actor_critic_tick(self, counter):
@@ -421,16 +461,9 @@ class Engine:
         bootstrap), time-major contiguous cuda tensors; a done cuts the episode.  Returns (adv, ret), float32 of reward's shape (`adv`,
         `ret`: buffers to write).  Asynchronous on the caller's current stream."""
         t = self.torch
-        T = int(reward.shape[0])
-        rows = reward.numel() // max(T, 1)
-        adv = t.empty_like(reward) if adv is None else adv
-        ret = t.empty_like(reward) if ret is None else ret
-        for v, dt, n in ((reward, t.float32, T * rows), (value, t.float32, (T + 1) * rows), (done, t.uint8, T * rows), (adv, t.float32, T * rows),
-                         (ret, t.float32, T * rows)):
-            assert v.is_cuda and v.dtype == dt and v.is_contiguous() and v.numel() == n
-        self._follow_stream()
-        _chk(self.L.pgd_gae(self.h, C.c_void_p(reward.data_ptr()), C.c_void_p(value.data_ptr()), C.c_void_p(done.data_ptr()), T, rows,
-                            float(gamma), float(lam), C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr())), "pgd_gae")
+        T, rows, (reward, value, done, adv, ret) = self._rollout_buffers(
+            reward, ((reward, t.float32, 0), (value, t.float32, 1), (done, t.uint8, 0), (adv, t.float32, 0), (ret, t.float32, 0)))
+        _chk(self.L.pgd_gae(self.h, _p(reward), _p(value), _p(done), T, rows, float(gamma), float(lam), _p(adv), _p(ret)), "pgd_gae")
         return adv, ret
 
     # -- rollouts of multi-agent engines (include/pgdrive_hip.h states the predicates acted / cont / live) -------------------------
@@ -454,7 +487,7 @@ class Engine:
         return rows, count
 
     def _n_groups(self):
-        return max(1, int(getattr(self, "n_groups", 1) or 1))
+        return max(1, int(self.n_groups or 1))
 
     def rollout_index(self, flags, index=None, count=None):
         """The entries t * rows + r of a time-major flag tensor [T, rows...] at which an agent acted (PGD_F_REPORT), ascending, into
@@ -479,29 +512,12 @@ class Engine:
         row gets bit for bit what mlp_actor_critic gives it; every other row of the range gets action 0, 0, logp 0, value 0 (written by
         this call) and its observation is never used (it may hold NaN).  The other arguments as for mlp_actor_critic."""
         t = self.torch
-        o = self.obs if obs is None else obs
-        o2 = o.view(-1, o.shape[-1])
         n = self.N * self.A
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == n
-        self._check_actions(out)
-        for v in (logp, ) if value_weights is None else (logp, value):
-            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == n
         assert rows.is_cuda and rows.dtype == t.int32 and rows.is_contiguous() and rows.numel() >= (n if group < 0 else n // self._n_groups())
         assert count.is_cuda and count.dtype == t.int32 and count.numel() == 1
-        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
-        assert k <= o2.shape[1]
-        nets = _abi.ActorCritic()
-        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
-        nets.out_cols = int(policy_weights[4].shape[1])
-        if value_weights is not None:
-            nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
-            assert value_weights[4].shape[1] == 1
-        if group < 0:
-            self._follow_stream()
-        _chk(self.L.pgd_mlp_actor_critic_rows(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k, C.byref(nets),
-                                              int(seed) & 0xffffffff, int(tick) & 0xffffffff, _abi.AC_DETERMINISTIC if deterministic else 0,
-                                              C.c_void_p(rows.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(out.data_ptr()),
-                                              C.c_void_p(logp.data_ptr()), C.c_void_p(value.data_ptr()) if value_weights is not None else None),
+        a = self._ac_args(policy_weights, value_weights, None, out, (logp, ) if value_weights is None else (logp, value), seed, tick, obs, group,
+                          deterministic, in_dim)
+        _chk(self.L.pgd_mlp_actor_critic_rows(*a, _p(rows), _p(count), _p(out), _p(logp), _p(value) if value_weights is not None else None),
              "pgd_mlp_actor_critic_rows")
         return out, logp, value
 
@@ -510,18 +526,11 @@ class Engine:
         where an agent acted and whether it continues; rows that did not act get adv = ret = 0 whatever their reward and value hold.
         Returns (adv, ret, mask): mask uint8 of reward's shape, 1 where an agent acted."""
         t = self.torch
-        T = int(reward.shape[0])
-        rows = reward.numel() // max(T, 1)
-        adv = t.empty_like(reward) if adv is None else adv
-        ret = t.empty_like(reward) if ret is None else ret
-        mask = t.empty(reward.shape, dtype=t.uint8, device=reward.device) if mask is None else mask
-        for v, dt, n in ((reward, t.float32, T * rows), (value, t.float32, (T + 1) * rows), (done, t.uint8, T * rows), (flags, t.int32, T * rows),
-                         (adv, t.float32, T * rows), (ret, t.float32, T * rows), (mask, t.uint8, T * rows)):
-            assert v.is_cuda and v.dtype == dt and v.is_contiguous() and v.numel() == n
-        self._follow_stream()
-        _chk(self.L.pgd_gae_masked(self.h, C.c_void_p(reward.data_ptr()), C.c_void_p(value.data_ptr()), C.c_void_p(done.data_ptr()),
-                                   C.c_void_p(flags.data_ptr()), T, rows, float(gamma), float(lam), C.c_void_p(adv.data_ptr()),
-                                   C.c_void_p(ret.data_ptr()), C.c_void_p(mask.data_ptr())), "pgd_gae_masked")
+        T, rows, (reward, value, done, flags, adv, ret, mask) = self._rollout_buffers(
+            reward, ((reward, t.float32, 0), (value, t.float32, 1), (done, t.uint8, 0), (flags, t.int32, 0), (adv, t.float32, 0), (ret, t.float32, 0),
+                     (mask, t.uint8, 0)))
+        _chk(self.L.pgd_gae_masked(self.h, _p(reward), _p(value), _p(done), _p(flags), T, rows, float(gamma), float(lam), _p(adv), _p(ret),
+                                   _p(mask)), "pgd_gae_masked")
         return adv, ret, mask
 
     # -- the PPO update behind a rollout (include/pgdrive_hip.h states the formulas) ---------------------------------------------
@@ -561,45 +570,52 @@ class Engine:
         of `index`); position q is row index[q] (`index` None: q).  `adv_stats`: the two floats of adv_stats(), or None.  Gradients are
         written into `policy_grads` / `value_grads`, tuples of the weights' shapes (value_weights None: no critic, value_grads ignored);
         `stats` float32 cuda [8] (_abi.PPO_STATS); `work` a cuda tensor of at least ppo_work_bytes(in_dim, rows) bytes.  Asynchronous."""
+        nets, _, b, grads, _ = self._ppo_batch((policy_weights, value_weights, None), (policy_grads, value_grads, None), obs, actions, logp_old, adv,
+                                               ret, None, stats, work, start, stride, rows, index, count, n_list, adv_stats, in_dim)
+        hp = _abi.PPOHyper(float(clip), float(vf_coef), float(ent_coef))
+        _chk(self.L.pgd_ppo_grad(self.h, C.byref(nets), C.byref(b), C.byref(hp), C.byref(grads), _p(stats), _p(work),
+                                 work.numel() * work.element_size()), "pgd_ppo_grad")
+        return stats
+
+    def _ppo_batch(self, weights, grad_bufs, obs, actions, logp_old, adv, ret, cost_ret, stats, work, start, stride, rows, index, count, n_list,
+                   adv_stats, in_dim):
+        """What ppo_grad and ppo_grad_cost share, checked: the rollout's tensors, the minibatch, `stats`, `work`, and the networks with their
+        gradient buffers -- `weights` and `grad_bufs` are (policy, value or None, cost or None) -> ActorCritic, ValueNet (or None),
+        PPOBatch, PPOGrads, ValueGrads (or None).  Follows the caller's stream."""
         t = self.torch
+        (pw, vw, cw), (pg, vg, cg) = weights, grad_bufs
+        assert cw is None or vw is not None, "the cost critic comes with a critic"
         o2 = obs.view(-1, obs.shape[-1])
         n_rows = int(o2.shape[0])
         assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1
         assert actions.is_cuda and actions.dtype == t.float32 and actions.is_contiguous() and actions.numel() == 2 * n_rows
-        for v in (logp_old, adv) if value_weights is None else (logp_old, adv, ret):
+        for v in (logp_old, adv) + (() if vw is None else (ret, )) + (() if cw is None else (cost_ret, )):
             assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == n_rows
         n_list = int((index.numel() if index is not None else n_rows) if n_list is None else n_list)
         assert 0 <= n_list and (index is not None or n_list <= n_rows)
         rows = int(max(1, -(-(n_list - int(start)) // int(stride))) if rows is None else rows)
         assert int(start) >= 0 and int(stride) >= 1 and 1 <= rows <= _abi.PPO_ROWS_MAX
-        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
+        k = int(in_dim if in_dim is not None else pw[0].shape[0])
         assert k <= o2.shape[1]
         assert stats.is_cuda and stats.dtype == t.float32 and stats.is_contiguous() and stats.numel() == 8
-        need = self.ppo_work_bytes(k, rows, value_weights is not None)
+        need = self.ppo_work_bytes(k, rows, vw is not None) if cw is None else self.ppo_cost_work_bytes(k, rows)
         assert need > 0 and work.is_cuda and work.is_contiguous() and work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
         if adv_stats is not None:
             assert adv_stats.is_cuda and adv_stats.dtype == t.float32 and adv_stats.is_contiguous() and adv_stats.numel() == 2
-        nets, grads = _abi.ActorCritic(), _abi.PPOGrads()
-        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
-        nets.out_cols = int(policy_weights[4].shape[1])
-        grads.w1, grads.b1, grads.w2, grads.b2, grads.w3, grads.b3 = self._network(policy_grads, k, 4)
-        assert all(g.shape == w.shape for g, w in zip(policy_grads, policy_weights))
-        if value_weights is not None:
-            nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
-            grads.vw1, grads.vb1, grads.vw2, grads.vb2, grads.vw3, grads.vb3 = self._network(value_grads, k, 1)
-            assert value_weights[4].shape[1] == 1 and value_grads[4].shape[1] == 1
+        nets = self._nets(_abi.ActorCritic(), pw, vw, k)
+        nets.out_cols = int(pw[4].shape[1])
+        grads = self._nets(_abi.PPOGrads(), pg, None if vw is None else vg, k)
+        assert all(g.shape == w.shape for g, w in zip(pg, pw))
+        cnet = None if cw is None else self._value_net(_abi.ValueNet(), cw, k)
+        cgrads = None if cw is None else self._value_net(_abi.ValueGrads(), cg, k)
         b = _abi.PPOBatch()
         b.obs, b.action, b.logp_old, b.adv = o2.data_ptr(), actions.data_ptr(), logp_old.data_ptr(), adv.data_ptr()
-        b.ret = ret.data_ptr() if value_weights is not None else None
+        b.ret = ret.data_ptr() if vw is not None else None
         b.adv_stats = adv_stats.data_ptr() if adv_stats is not None else None
-        ip, cp = self._list_args(index, count, n_list)
-        b.index, b.count = ip, cp
+        b.index, b.count = self._list_args(index, count, n_list)
         b.obs_stride, b.in_dim, b.n_rows, b.n_list, b.start, b.stride, b.rows = int(o2.stride(0)), k, n_rows, n_list, int(start), int(stride), rows
-        hp = _abi.PPOHyper(float(clip), float(vf_coef), float(ent_coef))
         self._follow_stream()
-        _chk(self.L.pgd_ppo_grad(self.h, C.byref(nets), C.byref(b), C.byref(hp), C.byref(grads), C.c_void_p(stats.data_ptr()),
-                                 C.c_void_p(work.data_ptr()), work.numel() * work.element_size()), "pgd_ppo_grad")
-        return stats
+        return nets, cnet, b, grads, cgrads
 
     def adam(self, param, grad, m, v, step, lr, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0):
         """One Adam step on the flat float32 cuda buffer `param` (pgd_adam), `grad`, `m`, `v` of its length; max_grad_norm > 0 clips by the
@@ -621,28 +637,8 @@ class Engine:
         """mlp_actor_critic with a cost critic beside actor and critic in the same launch (pgd_mlp_actor_critic_cost): `cost_weights` has
         the shapes of `value_weights` (both are required), `cost_value` [N, A] float32 cuda receives its output.  Every other argument,
         the noise and the tick rule as for mlp_actor_critic, whose bits `out`, `logp` and `value` are."""
-        t = self.torch
-        o = self.obs if obs is None else obs
-        o2 = o.view(-1, o.shape[-1])
-        rows = self.N * self.A
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == rows
-        self._check_actions(out)
-        for v in (logp, value, cost_value):
-            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == rows
-        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
-        assert k <= o2.shape[1]
-        nets, cnet = _abi.ActorCritic(), _abi.ValueNet()
-        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
-        nets.out_cols = int(policy_weights[4].shape[1])
-        nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
-        cnet.w1, cnet.b1, cnet.w2, cnet.b2, cnet.w3, cnet.b3 = self._network(cost_weights, k, 1)
-        assert value_weights[4].shape[1] == 1 and cost_weights[4].shape[1] == 1
-        if group < 0:
-            self._follow_stream()
-        _chk(self.L.pgd_mlp_actor_critic_cost(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k, C.byref(nets), C.byref(cnet),
-                                              int(seed) & 0xffffffff, int(tick) & 0xffffffff, _abi.AC_DETERMINISTIC if deterministic else 0,
-                                              C.c_void_p(out.data_ptr()), C.c_void_p(logp.data_ptr()), C.c_void_p(value.data_ptr()),
-                                              C.c_void_p(cost_value.data_ptr())), "pgd_mlp_actor_critic_cost")
+        a = self._ac_args(policy_weights, value_weights, cost_weights, out, (logp, value, cost_value), seed, tick, obs, group, deterministic, in_dim)
+        _chk(self.L.pgd_mlp_actor_critic_cost(*a, _p(out), _p(logp), _p(value), _p(cost_value)), "pgd_mlp_actor_critic_cost")
         return out, logp, value, cost_value
 
     def cost_gae(self, flags, done, cost_value, costs, gamma, lam, run, cost=None, adv=None, ret=None, ep_sum=None, ep_count=None):
@@ -652,23 +648,12 @@ class Engine:
         rollout to rollout.  Returns (cost, adv, ret, ep_sum, ep_count): the first three float32 of flags' shape, ep_sum float32 and
         ep_count int32 [rows] -- the episodes that finished in THIS rollout (each a buffer to write, allocated when None).  Asynchronous."""
         t = self.torch
-        T = int(flags.shape[0])
-        rows = flags.numel() // max(T, 1)
-        f32 = dict(dtype=t.float32, device=flags.device)
-        cost = t.empty(flags.shape, **f32) if cost is None else cost
-        adv = t.empty(flags.shape, **f32) if adv is None else adv
-        ret = t.empty(flags.shape, **f32) if ret is None else ret
-        ep_sum = t.empty((rows, ), **f32) if ep_sum is None else ep_sum
-        ep_count = t.empty((rows, ), dtype=t.int32, device=flags.device) if ep_count is None else ep_count
-        for v, dt, n in ((flags, t.int32, T * rows), (done, t.uint8, T * rows), (cost_value, t.float32, (T + 1) * rows), (cost, t.float32, T * rows),
-                         (adv, t.float32, T * rows), (ret, t.float32, T * rows), (run, t.float32, rows), (ep_sum, t.float32, rows),
-                         (ep_count, t.int32, rows)):
-            assert v.is_cuda and v.dtype == dt and v.is_contiguous() and v.numel() == n
+        T, rows, (flags, done, cost_value, cost, adv, ret, run, ep_sum, ep_count) = self._rollout_buffers(
+            flags, ((flags, t.int32, 0), (done, t.uint8, 0), (cost_value, t.float32, 1), (cost, t.float32, 0), (adv, t.float32, 0),
+                    (ret, t.float32, 0), (run, t.float32, None), (ep_sum, t.float32, None), (ep_count, t.int32, None)))
         c3 = (C.c_float * 3)(*[float(c) for c in costs])
-        self._follow_stream()
-        _chk(self.L.pgd_cost_gae(self.h, C.c_void_p(flags.data_ptr()), C.c_void_p(done.data_ptr()), C.c_void_p(cost_value.data_ptr()), T, rows, c3,
-                                 float(gamma), float(lam), C.c_void_p(cost.data_ptr()), C.c_void_p(adv.data_ptr()), C.c_void_p(ret.data_ptr()),
-                                 C.c_void_p(run.data_ptr()), C.c_void_p(ep_sum.data_ptr()), C.c_void_p(ep_count.data_ptr())), "pgd_cost_gae")
+        _chk(self.L.pgd_cost_gae(self.h, _p(flags), _p(done), _p(cost_value), T, rows, c3, float(gamma), float(lam), _p(cost), _p(adv), _p(ret),
+                                 _p(run), _p(ep_sum), _p(ep_count)), "pgd_cost_gae")
         return cost, adv, ret, ep_sum, ep_count
 
     def lagrange(self, ep_sum, ep_count, state, cost_limit, lr, lambda_max=100.0):
@@ -718,46 +703,13 @@ class Engine:
         `stats` float32 cuda [8] (_abi.PPO_COST_STATS: entry 7 is the cost critic's loss); `work` a cuda tensor of at least
         ppo_cost_work_bytes(in_dim, rows) bytes.  Every other argument as for ppo_grad, whose bits the actor's and the critic's
         gradients and stats[0..6] are.  Asynchronous."""
-        t = self.torch
-        o2 = obs.view(-1, obs.shape[-1])
-        n_rows = int(o2.shape[0])
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1
-        assert actions.is_cuda and actions.dtype == t.float32 and actions.is_contiguous() and actions.numel() == 2 * n_rows
-        for v in (logp_old, adv, ret, cost_ret):
-            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == n_rows
-        n_list = int((index.numel() if index is not None else n_rows) if n_list is None else n_list)
-        assert 0 <= n_list and (index is not None or n_list <= n_rows)
-        rows = int(max(1, -(-(n_list - int(start)) // int(stride))) if rows is None else rows)
-        assert int(start) >= 0 and int(stride) >= 1 and 1 <= rows <= _abi.PPO_ROWS_MAX
-        k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
-        assert k <= o2.shape[1]
-        assert stats.is_cuda and stats.dtype == t.float32 and stats.is_contiguous() and stats.numel() == 8
-        need = self.ppo_cost_work_bytes(k, rows)
-        assert need > 0 and work.is_cuda and work.is_contiguous() and work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
-        if adv_stats is not None:
-            assert adv_stats.is_cuda and adv_stats.dtype == t.float32 and adv_stats.is_contiguous() and adv_stats.numel() == 2
-        nets, grads, cnet, cgrads = _abi.ActorCritic(), _abi.PPOGrads(), _abi.ValueNet(), _abi.ValueGrads()
-        nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = self._network(policy_weights, k, 4)
-        nets.out_cols = int(policy_weights[4].shape[1])
-        grads.w1, grads.b1, grads.w2, grads.b2, grads.w3, grads.b3 = self._network(policy_grads, k, 4)
-        assert all(g.shape == w.shape for g, w in zip(policy_grads, policy_weights))
-        nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = self._network(value_weights, k, 1)
-        grads.vw1, grads.vb1, grads.vw2, grads.vb2, grads.vw3, grads.vb3 = self._network(value_grads, k, 1)
-        cnet.w1, cnet.b1, cnet.w2, cnet.b2, cnet.w3, cnet.b3 = self._network(cost_weights, k, 1)
-        cgrads.w1, cgrads.b1, cgrads.w2, cgrads.b2, cgrads.w3, cgrads.b3 = self._network(cost_grads, k, 1)
-        assert all(w[4].shape[1] == 1 for w in (value_weights, value_grads, cost_weights, cost_grads))
-        b = _abi.PPOBatch()
-        b.obs, b.action, b.logp_old, b.adv, b.ret = o2.data_ptr(), actions.data_ptr(), logp_old.data_ptr(), adv.data_ptr(), ret.data_ptr()
-        b.adv_stats = adv_stats.data_ptr() if adv_stats is not None else None
-        ip, cp = self._list_args(index, count, n_list)
-        b.index, b.count = ip, cp
-        b.obs_stride, b.in_dim, b.n_rows, b.n_list, b.start, b.stride, b.rows = int(o2.stride(0)), k, n_rows, n_list, int(start), int(stride), rows
+        nets, cnet, b, grads, cgrads = self._ppo_batch((policy_weights, value_weights, cost_weights), (policy_grads, value_grads, cost_grads), obs,
+                                                       actions, logp_old, adv, ret, cost_ret, stats, work, start, stride, rows, index, count, n_list,
+                                                       adv_stats, in_dim)
         hp = _abi.PPOHyper(float(clip), float(vf_coef), float(ent_coef))
         pc = _abi.PPOCost(cost_ret.data_ptr(), float(cvf_coef))
-        self._follow_stream()
         _chk(self.L.pgd_ppo_grad_cost(self.h, C.byref(nets), C.byref(cnet), C.byref(b), C.byref(pc), C.byref(hp), C.byref(grads), C.byref(cgrads),
-                                      C.c_void_p(stats.data_ptr()), C.c_void_p(work.data_ptr()), work.numel() * work.element_size()),
-             "pgd_ppo_grad_cost")
+                                      _p(stats), _p(work), work.numel() * work.element_size()), "pgd_ppo_grad_cost")
         return stats
 
     def step_lane_keep(self, tick, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):

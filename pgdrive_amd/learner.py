@@ -58,19 +58,23 @@ def live_positions(start, stride, rows, count):
 
 
 class PPOLearner:
+    NETS = ("policy", "value")  # the collector's networks, in flat_layout's order
+    GRAD = "pgd_ppo_grad"
+
     def __init__(self, collector, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.0, epochs=4, minibatches=4, max_grad_norm=0.5, betas=(0.9, 0.999),
                  eps=1e-5, normalise_advantages=True):
         eng = collector.engine
         t = eng.torch
+        name, cost = type(self).__name__, len(self.NETS) == 3
         if int(epochs) < 1 or int(minibatches) < 1:
-            raise ValueError("PPOLearner: epochs = %r, minibatches = %r" % (epochs, minibatches))
+            raise ValueError("%s: epochs = %r, minibatches = %r" % (name, epochs, minibatches))
         self.collector, self.engine = collector, eng
         self.lr, self.clip, self.vf_coef, self.ent_coef = float(lr), float(clip), float(vf_coef), float(ent_coef)
         self.epochs, self.minibatches, self.max_grad_norm = int(epochs), int(minibatches), float(max_grad_norm)
         self.betas, self.eps, self.normalise_advantages = (float(betas[0]), float(betas[1])), float(eps), bool(normalise_advantages)
-        pw, vw = collector.policy_weights, collector.value_weights
-        self.in_dim, self.out_cols = int(pw[0].shape[0]), int(pw[4].shape[1])
-        layout, total = flat_layout(self.in_dim, self.out_cols)
+        nets = [getattr(collector, n + "_weights") for n in self.NETS]
+        self.in_dim, self.out_cols = int(nets[0][0].shape[0]), int(nets[0][4].shape[1])
+        layout, total = flat_layout(self.in_dim, self.out_cols, has_cost_critic=cost)
         f32 = dict(dtype=t.float32, device=eng.device)
         self.params, self.grads = t.zeros((total, ), **f32), t.zeros((total, ), **f32)
         self.m, self.v = t.zeros((total, ), **f32), t.zeros((total, ), **f32)
@@ -80,43 +84,51 @@ class PPOLearner:
             return tuple(flat[o:o + int(t.Size(shape).numel())].view(shape) for _, shape, o in layout)
 
         wv, gv = views(self.params), views(self.grads)
-        for dst, src in zip(wv, tuple(pw) + tuple(vw)):
+        for dst, src in zip(wv, [w for net in nets for w in net]):
             dst.copy_(src.view(dst.shape))
-        self.policy_weights, self.value_weights = wv[:6], wv[6:]
-        self.policy_grads, self.value_grads = gv[:6], gv[6:]
-        collector.set_weights(self.policy_weights, self.value_weights)
+        for i, n in enumerate(self.NETS):  # policy_weights, policy_grads, value_weights, ...
+            setattr(self, n + "_weights", wv[6 * i:6 * i + 6])
+            setattr(self, n + "_grads", gv[6 * i:6 * i + 6])
+        collector.set_weights(*[getattr(self, n + "_weights") for n in self.NETS])
         self.n_list = int(collector.rewards.numel())  # T * N (* A): every row of the rollout
         self.plan = minibatch_plan(self.n_list, self.minibatches)
-        need = eng.ppo_work_bytes(self.in_dim, max(rows for _, _, rows in self.plan), True)
+        rows = max(rows for _, _, rows in self.plan)
+        need = eng.ppo_cost_work_bytes(self.in_dim, rows) if cost else eng.ppo_work_bytes(self.in_dim, rows, True)
         if need == 0:
-            raise ValueError("PPOLearner: the networks' input width %d is outside what pgd_ppo_grad accepts" % self.in_dim)
+            raise ValueError("%s: the networks' input width %d is outside what %s accepts" % (name, self.in_dim, self.GRAD))
         self.work = t.empty(((need + 3) // 4, ), **f32)
         self.adv_stats = t.zeros((2, ), **f32)
         self.stats = t.zeros((self.epochs * self.minibatches, 8), **f32)
+
+    def _advantages(self, batch, index, count):
+        """The advantage tensor the gradient calls read and the statistics they normalise it with (None: as it is)."""
+        adv = batch["advantages"]
+        if not self.normalise_advantages:
+            return adv, None
+        return adv, self.engine.adv_stats(adv, out=self.adv_stats, index=index, count=count, n_list=self.n_list)
+
+    def _grad(self, batch, adv, stats, **minibatch):
+        self.engine.ppo_grad(self.policy_weights, self.value_weights, self.policy_grads, self.value_grads, batch["obs"], batch["actions"],
+                             batch["logp"], adv, batch["returns"], stats, self.work, vf_coef=self.vf_coef, **minibatch)
 
     def update(self, batch):
         """epochs x minibatches gradient steps on the rollout `batch` (what collector.collect() returned).  Returns the statistics
         tensor [epochs * minibatches, 8] (the same object every time).  Asynchronous: nothing here waits for the device."""
         eng = self.engine
         index, count = batch.get("index"), batch.get("count")  # (the multi-agent collector's list; None: every row)
-        adv = batch["advantages"]
-        norm = None
-        if self.normalise_advantages:
-            norm = eng.adv_stats(adv, out=self.adv_stats, index=index, count=count, n_list=self.n_list)
+        adv, norm = self._advantages(batch, index, count)
         k = 0
         for _ in range(self.epochs):
             for start, stride, rows in self.plan:
-                eng.ppo_grad(self.policy_weights, self.value_weights, self.policy_grads, self.value_grads, batch["obs"], batch["actions"],
-                             batch["logp"], adv, batch["returns"], self.stats[k], self.work, start=start, stride=stride, rows=rows, index=index,
-                             count=count, n_list=self.n_list, adv_stats=norm, clip=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
-                             in_dim=self.in_dim)
+                self._grad(batch, adv, self.stats[k], start=start, stride=stride, rows=rows, index=index, count=count, n_list=self.n_list,
+                           adv_stats=norm, clip=self.clip, ent_coef=self.ent_coef, in_dim=self.in_dim)
                 eng.adam(self.params, self.grads, self.m, self.v, self.step, self.lr, betas=self.betas, eps=self.eps,
                          max_grad_norm=self.max_grad_norm)
                 k += 1
         return self.stats
 
 
-class PPOLagLearner:
+class PPOLagLearner(PPOLearner):
     """PPO-Lagrangian behind a SafeRolloutCollector: PPOLearner's update with a cost critic and a multiplier that holds the policy under
     `cost_limit` (the mean cost of an episode), all on the device:
 
@@ -133,52 +145,24 @@ class PPOLagLearner:
     the next multiplier step from the lambda it finds.  ONE flat buffer holds the eighteen weight tensors (flat_layout(...,
     has_cost_critic=True)); the collector is handed the views.  `ppo_kwargs`: PPOLearner's arguments (normalise_advantages False: no
     scaling of the reward advantage and no centring of either)."""
+    NETS = ("policy", "value", "cost")
+    GRAD = "pgd_ppo_grad_cost"
+
     def __init__(self, collector, cost_limit, lambda_lr=0.05, lambda_init=0.0, lambda_max=100.0, cvf_coef=0.5, lr=3e-4, clip=0.2, vf_coef=0.5,
                  ent_coef=0.0, epochs=4, minibatches=4, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-5, normalise_advantages=True):
-        eng = collector.engine
-        t = eng.torch
-        if int(epochs) < 1 or int(minibatches) < 1:
-            raise ValueError("PPOLagLearner: epochs = %r, minibatches = %r" % (epochs, minibatches))
         if not (0.0 <= float(lambda_init) <= float(lambda_max)):
             raise ValueError("PPOLagLearner: lambda_init = %r outside [0, lambda_max = %r]" % (lambda_init, lambda_max))
-        self.collector, self.engine = collector, eng
+        super().__init__(collector, lr, clip, vf_coef, ent_coef, epochs, minibatches, max_grad_norm, betas, eps, normalise_advantages)
         self.cost_limit, self.lambda_lr, self.lambda_max, self.cvf_coef = float(cost_limit), float(lambda_lr), float(lambda_max), float(cvf_coef)
-        self.lr, self.clip, self.vf_coef, self.ent_coef = float(lr), float(clip), float(vf_coef), float(ent_coef)
-        self.epochs, self.minibatches, self.max_grad_norm = int(epochs), int(minibatches), float(max_grad_norm)
-        self.betas, self.eps, self.normalise_advantages = (float(betas[0]), float(betas[1])), float(eps), bool(normalise_advantages)
-        pw, vw, cw = collector.policy_weights, collector.value_weights, collector.cost_weights
-        self.in_dim, self.out_cols = int(pw[0].shape[0]), int(pw[4].shape[1])
-        layout, total = flat_layout(self.in_dim, self.out_cols, has_cost_critic=True)
-        f32 = dict(dtype=t.float32, device=eng.device)
-        self.params, self.grads = t.zeros((total, ), **f32), t.zeros((total, ), **f32)
-        self.m, self.v = t.zeros((total, ), **f32), t.zeros((total, ), **f32)
-        self.step = t.zeros((4, ), dtype=t.int32, device=eng.device)  # pgd_adam's counter and record
-
-        def views(flat):
-            return tuple(flat[o:o + int(t.Size(shape).numel())].view(shape) for _, shape, o in layout)
-
-        wv, gv = views(self.params), views(self.grads)
-        for dst, src in zip(wv, tuple(pw) + tuple(vw) + tuple(cw)):
-            dst.copy_(src.view(dst.shape))
-        self.policy_weights, self.value_weights, self.cost_weights = wv[:6], wv[6:12], wv[12:]
-        self.policy_grads, self.value_grads, self.cost_grads = gv[:6], gv[6:12], gv[12:]
-        collector.set_weights(self.policy_weights, self.value_weights, self.cost_weights)
-        self.n_list = int(collector.rewards.numel())  # T * N: every row of the rollout
-        self.plan = minibatch_plan(self.n_list, self.minibatches)
-        need = eng.ppo_cost_work_bytes(self.in_dim, max(rows for _, _, rows in self.plan))
-        if need == 0:
-            raise ValueError("PPOLagLearner: the networks' input width %d is outside what pgd_ppo_grad_cost accepts" % self.in_dim)
-        self.work = t.empty(((need + 3) // 4, ), **f32)
-        self.adv_stats, self.cadv_stats = t.zeros((2, ), **f32), t.zeros((2, ), **f32)
+        t = self.engine.torch
+        f32 = dict(dtype=t.float32, device=self.engine.device)
+        self.cadv_stats = t.zeros((2, ), **f32)
         self.mixed = t.zeros((self.n_list, ), **f32)  # the advantage the policy sees
         self.lagrange_state = t.zeros((4, ), **f32)
         self.lagrange_state[0] = float(lambda_init)
-        self.stats = t.zeros((self.epochs * self.minibatches, 8), **f32)
 
-    def update(self, batch):
-        """One multiplier step, then epochs x minibatches gradient steps on the rollout `batch` (what collector.collect() returned).
-        Returns the statistics tensor [epochs * minibatches, 8] (the same object every time).  Asynchronous: nothing here waits for the
-        device."""
+    def _advantages(self, batch, index, count):
+        """One multiplier step, then the mixed advantage (already normalised: no statistics for the gradient calls)."""
         eng = self.engine
         eng.lagrange(batch["ep_cost_sum"], batch["ep_cost_count"], self.lagrange_state, self.cost_limit, self.lambda_lr, self.lambda_max)
         adv, cadv = batch["advantages"], batch["cost_advantages"]
@@ -187,14 +171,9 @@ class PPOLagLearner:
             norm = eng.adv_stats(adv, out=self.adv_stats, n_list=self.n_list)
             cnorm = eng.adv_stats(cadv, out=self.cadv_stats, n_list=self.n_list)
         eng.adv_mix(adv, cadv, self.lagrange_state, out=self.mixed, adv_stats=norm, cadv_stats=cnorm)
-        k = 0
-        for _ in range(self.epochs):
-            for start, stride, rows in self.plan:
-                eng.ppo_grad_cost(self.policy_weights, self.value_weights, self.cost_weights, self.policy_grads, self.value_grads, self.cost_grads,
-                                  batch["obs"], batch["actions"], batch["logp"], self.mixed, batch["returns"], batch["cost_returns"], self.stats[k],
-                                  self.work, start=start, stride=stride, rows=rows, n_list=self.n_list, clip=self.clip, vf_coef=self.vf_coef,
-                                  cvf_coef=self.cvf_coef, ent_coef=self.ent_coef, in_dim=self.in_dim)
-                eng.adam(self.params, self.grads, self.m, self.v, self.step, self.lr, betas=self.betas, eps=self.eps,
-                         max_grad_norm=self.max_grad_norm)
-                k += 1
-        return self.stats
+        return self.mixed, None
+
+    def _grad(self, batch, adv, stats, **minibatch):
+        self.engine.ppo_grad_cost(self.policy_weights, self.value_weights, self.cost_weights, self.policy_grads, self.value_grads, self.cost_grads,
+                                  batch["obs"], batch["actions"], batch["logp"], adv, batch["returns"], batch["cost_returns"], stats, self.work,
+                                  vf_coef=self.vf_coef, cvf_coef=self.cvf_coef, **minibatch)

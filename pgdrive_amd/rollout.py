@@ -33,28 +33,25 @@ seats only, GAE per agent and not per seat, and the index of the transitions a t
 import numpy as np
 
 
-class RolloutCollector:
-    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0):
-        eng = getattr(env_or_engine, "engine", env_or_engine)
-        if eng.A != 1:
-            raise NotImplementedError(
-                "RolloutCollector serves single-agent engines: with %d agent seats per env the rows of seats that are not due need a mask "
-                "that this class does not know -- use MultiAgentRolloutCollector" % eng.A)
-        if int(T) < 1:
-            raise ValueError("RolloutCollector: T = %r" % (T, ))
+class _Collector:
+    """What the collectors share: the time-major buffers over rows of shape (N, ) or (N, A), the carry of row T into row 0, the tick
+    protocol around the engine's launches and the step loop.  A subclass refuses the engines it does not serve and gives
+    _evaluate(row) -- the networks on observation row `row` --, _stepped(t) -- between step t and that evaluation -- and _finish() --
+    GAE and what follows it."""
+    def _allocate(self, eng, rows, policy_weights, value_weights, T, gamma, lam, seed):
         t = eng.torch
         self.engine, self.T, self.gamma, self.lam, self.seed = eng, int(T), float(gamma), float(lam), int(seed)
-        T, N, D, dev = self.T, eng.N, eng.D, eng.device
+        T, D, dev = self.T, eng.D, eng.device
         f32 = dict(dtype=t.float32, device=dev)
-        self._obs = t.zeros((T + 1, N, D), **f32)
-        self._actions = t.zeros((T + 1, N, 2), **f32)
-        self._logp = t.zeros((T + 1, N), **f32)
-        self.values = t.zeros((T + 1, N), **f32)
-        self.rewards = t.zeros((T, N), **f32)
-        self.dones = t.zeros((T, N), dtype=t.uint8, device=dev)
-        self.flags = t.zeros((T, N), dtype=t.int32, device=dev)
-        self.advantages = t.zeros((T, N), **f32)
-        self.returns = t.zeros((T, N), **f32)
+        self._obs = t.zeros((T + 1, *rows, D), **f32)
+        self._actions = t.zeros((T + 1, *rows, 2), **f32)
+        self._logp = t.zeros((T + 1, *rows), **f32)
+        self.values = t.zeros((T + 1, *rows), **f32)
+        self.rewards = t.zeros((T, *rows), **f32)
+        self.dones = t.zeros((T, *rows), dtype=t.uint8, device=dev)
+        self.flags = t.zeros((T, *rows), dtype=t.int32, device=dev)
+        self.advantages = t.zeros((T, *rows), **f32)
+        self.returns = t.zeros((T, *rows), **f32)
         self._tick = t.zeros((1, ), dtype=t.int32, device=dev)  # evaluations before this rollout (modulo 2^32)
         self._carry = (self._obs, self._actions, self._logp, self.values)
         self._primed = False
@@ -66,15 +63,14 @@ class RolloutCollector:
         """The networks of the rollouts from now on (between two collect() calls): tuples as for Engine.mlp_actor_critic."""
         self.policy_weights, self.value_weights = tuple(policy_weights), tuple(value_weights)
 
-    def _evaluate(self, row):
-        self.engine.mlp_actor_critic(self.policy_weights, self.value_weights, self._actions[row], self._logp[row], self.values[row], self.seed,
-                                     row, obs=self._obs[row])
+    def _stepped(self, t):
+        pass
 
     def prime(self):
         """Take the engine's present observation (what reset wrote into Engine.obs) as the start of the first rollout.  collect() calls
         it once by itself; call it before capturing collect() in a graph."""
         eng, T = self.engine, self.T
-        self._obs[T].copy_(eng.obs.view(eng.N, eng.D))
+        self._obs[T].copy_(eng.obs.view(self._obs[T].shape))
         self._tick.sub_(T)  # (this evaluation is number 0: row T, counter -T)
         eng.actor_critic_tick(self._tick)
         self._evaluate(T)
@@ -94,11 +90,31 @@ class RolloutCollector:
         eng.actor_critic_tick(self._tick)  # (the engine's launches add the counter only while the collector is at work)
         for t in range(T):
             eng.step(self._actions[t], out=(self._obs[t + 1], self.rewards[t], self.dones[t], self.flags[t]))
+            self._stepped(t)
             self._evaluate(t + 1)
         eng.actor_critic_tick(None)
-        eng.gae(self.rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
+        self._finish()
         self._tick.add_(T)
         return self.batch
+
+
+class RolloutCollector(_Collector):
+    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0):
+        eng = getattr(env_or_engine, "engine", env_or_engine)
+        if eng.A != 1:
+            raise NotImplementedError(
+                "RolloutCollector serves single-agent engines: with %d agent seats per env the rows of seats that are not due need a mask "
+                "that this class does not know -- use MultiAgentRolloutCollector" % eng.A)
+        if int(T) < 1:
+            raise ValueError("RolloutCollector: T = %r" % (T, ))
+        self._allocate(eng, (eng.N, ), policy_weights, value_weights, T, gamma, lam, seed)
+
+    def _evaluate(self, row):
+        self.engine.mlp_actor_critic(self.policy_weights, self.value_weights, self._actions[row], self._logp[row], self.values[row], self.seed,
+                                     row, obs=self._obs[row])
+
+    def _finish(self):
+        self.engine.gae(self.rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
 
 
 class SafeRolloutCollector(RolloutCollector):
@@ -166,7 +182,7 @@ class SafeRolloutCollector(RolloutCollector):
         return self.batch
 
 
-class MultiAgentRolloutCollector:
+class MultiAgentRolloutCollector(_Collector):
     """RolloutCollector for multi-agent engines (A seats per env; include/pgdrive_hip.h states acted / cont / live):
 
         col = MultiAgentRolloutCollector(env, policy_weights, value_weights, T=128)
@@ -193,80 +209,45 @@ class MultiAgentRolloutCollector:
                                       "never reports PGD_F_REPORT -- use RolloutCollector")
         if int(T) < 1:
             raise ValueError("MultiAgentRolloutCollector: T = %r" % (T, ))
+        self._allocate(eng, (eng.N, eng.A), policy_weights, value_weights, T, gamma, lam, seed)
         t = eng.torch
-        self.engine, self.T, self.gamma, self.lam, self.seed = eng, int(T), float(gamma), float(lam), int(seed)
-        T, N, A, D, dev = self.T, eng.N, eng.A, eng.D, eng.device
-        f32 = dict(dtype=t.float32, device=dev)
-        i32 = dict(dtype=t.int32, device=dev)
-        self._obs = t.zeros((T + 1, N, A, D), **f32)
-        self._actions = t.zeros((T + 1, N, A, 2), **f32)
-        self._logp = t.zeros((T + 1, N, A), **f32)
-        self.values = t.zeros((T + 1, N, A), **f32)
-        self.rewards = t.zeros((T, N, A), **f32)
-        self.dones = t.zeros((T, N, A), dtype=t.uint8, device=dev)
-        self.flags = t.zeros((T, N, A), **i32)
-        self.advantages = t.zeros((T, N, A), **f32)
-        self.returns = t.zeros((T, N, A), **f32)
-        self.mask = t.zeros((T, N, A), dtype=t.uint8, device=dev)
-        self.index = t.zeros((T * N * A, ), **i32)
+        i32 = dict(dtype=t.int32, device=eng.device)
+        self.mask = t.zeros(self.flags.shape, dtype=t.uint8, device=eng.device)
+        self.index = t.zeros((self.flags.numel(), ), **i32)
         self.count = t.zeros((1, ), **i32)
-        self._rows = t.zeros((N * A, ), **i32)    # the live rows of the observation just written
+        self._rows = t.zeros((eng.N * eng.A, ), **i32)    # the live rows of the observation just written
         self._n_rows = t.zeros((1, ), **i32)
-        self._tick = t.zeros((1, ), **i32)  # evaluations before this rollout (modulo 2^32)
-        self._carry = (self._obs, self._actions, self._logp, self.values)
-        self._primed = False
-        self.set_weights(policy_weights, value_weights)
-        self.batch = dict(obs=self._obs[:T], actions=self._actions[:T], logp=self._logp[:T], values=self.values, rewards=self.rewards,
-                          dones=self.dones, flags=self.flags, advantages=self.advantages, returns=self.returns, mask=self.mask,
-                          index=self.index, count=self.count)
-
-    def set_weights(self, policy_weights, value_weights):
-        """The networks of the rollouts from now on (between two collect() calls): tuples as for Engine.mlp_actor_critic."""
-        self.policy_weights, self.value_weights = tuple(policy_weights), tuple(value_weights)
+        self.batch.update(mask=self.mask, index=self.index, count=self.count)
 
     def _evaluate(self, row):
         self.engine.mlp_actor_critic_rows(self.policy_weights, self.value_weights, self._rows, self._n_rows, self._actions[row], self._logp[row],
                                           self.values[row], self.seed, row, obs=self._obs[row])
+
+    def _stepped(self, t):
+        self.engine.live_rows(self.flags[t], self.dones[t], rows=self._rows, count=self._n_rows)
+
+    def _finish(self):
+        self.engine.gae_masked(self.rewards, self.values, self.dones, self.flags, self.gamma, self.lam, adv=self.advantages, ret=self.returns,
+                               mask=self.mask)
+        self.engine.rollout_index(self.flags, index=self.index, count=self.count)
 
     def prime(self):
         """Take the engine's present observation (what reset wrote into Engine.obs) as the start of the first rollout; its live seats
         are those whose agent is ACTIVE in the engine's state (a host read).  collect() calls it once by itself; call it before
         capturing collect() in a graph."""
         from . import _abi
-        eng, T = self.engine, self.T
-        t = eng.torch
+        eng = self.engine
         eng.sync()
         _, si, _ = eng.get_state()
         live = np.flatnonzero(si[_abi.SI["STATUS"], :, :eng.A].reshape(-1) == _abi.ST_ACTIVE).astype(np.int32)
-        self._rows[:len(live)].copy_(t.from_numpy(live))
+        self._rows[:len(live)].copy_(eng.torch.from_numpy(live))
         self._n_rows.fill_(len(live))
-        self._obs[T].copy_(eng.obs.view(eng.N, eng.A, eng.D))
-        self._tick.sub_(T)  # (this evaluation is number 0: row T, counter -T)
-        eng.actor_critic_tick(self._tick)
-        self._evaluate(T)
-        eng.actor_critic_tick(None)
-        self._tick.add_(T)
+        super().prime()
         eng.rollout_index(self.flags, index=self.index, count=self.count)  # (its scratch, allocated outside any capture; flags are zero)
-        self._primed = True
 
     def collect(self):
         """T steps.  Returns the dict of the collector's tensors (the same objects every time, valid until the next call):
         obs [T, N, A, D], actions [T, N, A, 2] (as sampled; the step clips), logp [T, N, A], values [T + 1, N, A], rewards, dones (uint8),
         flags, advantages, returns [T, N, A] -- as RolloutCollector's with a seat axis -- and mask [T, N, A] uint8 (an agent acted),
         index [T * N * A] int32 (the flattened positions where mask is 1, ascending; valid up to count), count [1] int32."""
-        eng, T = self.engine, self.T
-        if not self._primed:
-            self.prime()
-        for buf in self._carry:
-            buf[0].copy_(buf[T])
-        eng.actor_critic_tick(self._tick)  # (the engine's launches add the counter only while the collector is at work)
-        for t in range(T):
-            eng.step(self._actions[t], out=(self._obs[t + 1], self.rewards[t], self.dones[t], self.flags[t]))
-            eng.live_rows(self.flags[t], self.dones[t], rows=self._rows, count=self._n_rows)
-            self._evaluate(t + 1)
-        eng.actor_critic_tick(None)
-        eng.gae_masked(self.rewards, self.values, self.dones, self.flags, self.gamma, self.lam, adv=self.advantages, ret=self.returns,
-                       mask=self.mask)
-        eng.rollout_index(self.flags, index=self.index, count=self.count)
-        self._tick.add_(T)
-        return self.batch
+        return super().collect()

@@ -19,27 +19,10 @@ import pytest
 
 from tests import actor_critic_ref as ar
 from tests import policy_ref as pr
+from tests.train_util import ERR_ARG, SENT, ac_nets as _nets, bits_equal as _bits_equal, dev as _dev, ego_engine as _ego_engine, snapshot as _snapshot, \
+    synchronised_rollouts
 
 pytestmark = pytest.mark.gpu
-
-SENT = 7.0
-ERR_ARG = 1
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _ego_engine(descs, n, **kw):
-    """n envs, ego only, no lidar: cheap to create; the network kernel only needs its row count, env_base, groups and streams."""
-    from pgdrive_amd import _abi
-    from pgdrive_amd.engine import Engine
-    from tests import util
-    mb, sb = util.make_banks(descs, n_maps=4, num_traffic=0)
-    args = dict(num_agents=1, num_traffic=0, num_lasers=0, seed=2)
-    args.update(kw)
-    return Engine(_abi.make_config(n, **args), mb, sb)
 
 
 def _run(eng, x, policy, value, seed, tick, in_dim, det=False, group=-1, tail=8):
@@ -269,16 +252,6 @@ def test_multi_agent_rows_and_env_groups():
         eng.close()
 
 
-def _nets(pw, vw, out_cols=None):
-    from pgdrive_amd import _abi
-    nets = _abi.ActorCritic()
-    nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = [t.data_ptr() for t in pw]
-    nets.out_cols = int(pw[4].shape[1]) if out_cols is None else out_cols
-    if vw is not None:
-        nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = [t.data_ptr() for t in vw]
-    return nets
-
-
 def test_no_critic_leaves_the_value_buffer_alone(descs):
     """All six value pointers null: one row of workgroups; d_value is not touched even when it is given."""
     import torch
@@ -423,61 +396,11 @@ class _Col:
         torch.cuda.synchronize()
 
 
-def _snapshot(batch):
-    import torch
-    torch.cuda.synchronize()
-    return {k: batch[k].clone() for k in KEYS}
-
-
-def _bits_equal(a, b):
-    import torch
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
-
-
-def _synchronised_rollouts(S, n_rollouts):
-    """The calls of the collector made one at a time into fresh buffers, a device synchronisation behind each: mlp_actor_critic, step,
-    ..., gae; evaluation j has tick j."""
-    import torch
-    eng, T, N, D = S.eng, COL_T, COL_N, S.eng.D
-
-    def evaluate(obs, tick):
-        a = torch.zeros((N, 1, 2), dtype=torch.float32, device="cuda")
-        lp = torch.zeros((N, 1), dtype=torch.float32, device="cuda")
-        v = torch.zeros((N, 1), dtype=torch.float32, device="cuda")
-        eng.mlp_actor_critic(S.pw, S.vw, a, lp, v, COL_SEED, tick, obs=obs)
-        torch.cuda.synchronize()
-        return a, lp, v
-
-    obs = S.first.clone()
-    a, lp, v = evaluate(obs, 0)
-    out = []
-    for k in range(n_rollouts):
-        rec = {key: [] for key in KEYS}
-        for t in range(T):
-            rec["obs"].append(obs.view(N, D))
-            rec["actions"].append(a.view(N, 2))
-            rec["logp"].append(lp.view(N))
-            rec["values"].append(v.view(N))
-            fresh = eng.make_outputs()
-            obs, rew, done, flags = eng.step(a, out=fresh)
-            torch.cuda.synchronize()
-            rec["rewards"].append(rew.view(N))
-            rec["dones"].append(done.view(N))
-            rec["flags"].append(flags.view(N))
-            a, lp, v = evaluate(obs, k * T + t + 1)
-        rec["values"].append(v.view(N))
-        r = {key: torch.stack(rec[key]) for key in KEYS if rec[key]}
-        r["advantages"], r["returns"] = eng.gae(r["rewards"], r["values"], r["dones"], 0.99, 0.95)
-        torch.cuda.synchronize()
-        out.append(r)
-    return out
-
-
 def test_collector_equals_the_synchronised_loop_eagerly_and_from_a_graph(descs):
     import torch
     from pgdrive_amd.rollout import RolloutCollector
     S = _Col(descs)
-    want = _synchronised_rollouts(S, 3)
+    want = synchronised_rollouts(S, 3, COL_T, COL_SEED, KEYS)
     first_obs = S.first.cpu().numpy()
     S.eng.close()
 
@@ -508,7 +431,7 @@ def test_collector_equals_the_synchronised_loop_eagerly_and_from_a_graph(descs):
     with torch.cuda.stream(s), torch.no_grad():
         for k in range(3):
             batch = col.collect()
-            got = _snapshot(batch)
+            got = _snapshot(batch, KEYS)
             assert tuple(batch["obs"].shape) == (COL_T, COL_N, A.eng.D) and tuple(batch["values"].shape) == (COL_T + 1, COL_N)
             for key in KEYS:
                 assert _bits_equal(got[key], want[k][key]), "eager collect %d: %s differs from the synchronised loop" % (k, key)
@@ -522,7 +445,7 @@ def test_collector_equals_the_synchronised_loop_eagerly_and_from_a_graph(descs):
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s), torch.no_grad():
-        got = _snapshot(col.collect())
+        got = _snapshot(col.collect(), KEYS)
         for key in KEYS:
             assert _bits_equal(got[key], want[0][key]), key
         torch.cuda.synchronize()
@@ -533,7 +456,7 @@ def test_collector_equals_the_synchronised_loop_eagerly_and_from_a_graph(descs):
     with torch.cuda.stream(s), torch.no_grad():
         for k in (1, 2):
             g.replay()
-            got = _snapshot(batch)
+            got = _snapshot(batch, KEYS)
             for key in KEYS:
                 assert _bits_equal(got[key], want[k][key]), "graph replay %d: %s differs from the synchronised loop" % (k, key)
     del g

@@ -19,32 +19,16 @@ import pytest
 
 from tests import actor_critic_ref as ar
 from tests import marl_rollout_ref as mr
+from tests.train_util import ERR_ARG, SENT, ac_nets as _nets, bits_equal as _bits_equal, dev as _dev, ego_engine as _ego_engine, snapshot as _snapshot, \
+    synchronised_rollouts
 
 pytestmark = pytest.mark.gpu
 
-SENT = 7.0
 ISENT = -7
-ERR_ARG = 1
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _flags_dev(f):
     return _dev(np.ascontiguousarray(f).view(np.int32))
-
-
-def _ego_engine(descs, n, **kw):
-    """n envs, ego only, no lidar: cheap to create; these kernels only need its row count, env_base, groups and streams."""
-    from pgdrive_amd import _abi
-    from pgdrive_amd.engine import Engine
-    from tests import util
-    mb, sb = util.make_banks(descs, n_maps=4, num_traffic=0)
-    args = dict(num_agents=1, num_traffic=0, num_lasers=0, seed=2)
-    args.update(kw)
-    return Engine(_abi.make_config(n, **args), mb, sb)
 
 
 def _check_list(call, want, cap, where):
@@ -296,16 +280,6 @@ def test_entries_that_are_no_row_of_the_range_are_skipped(descs):
         eng.close()
 
 
-def _nets(pw, vw):
-    from pgdrive_amd import _abi
-    nets = _abi.ActorCritic()
-    nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = [t.data_ptr() for t in pw]
-    nets.out_cols = int(pw[4].shape[1])
-    if vw is not None:
-        nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = [t.data_ptr() for t in vw]
-    return nets
-
-
 def test_the_multi_agent_row_width_env_groups_and_the_in_dim_limit():
     """6 envs x 5 seats of the roundabout (rows of eng.D floats): the whole engine, then env group 1 alone (rows 15 .. 29; group 0's
     outputs keep their bytes).  in_dim 417, a null list and a null count are refused before any launch."""
@@ -431,64 +405,6 @@ class _Col:
         torch.cuda.synchronize()
 
 
-def _snapshot(batch):
-    import torch
-    torch.cuda.synchronize()
-    return {k: batch[k].clone() for k in KEYS}
-
-
-def _bits_equal(a, b):
-    import torch
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
-
-
-def _synchronised_rollouts(S, n_rollouts):
-    """The calls of the collector made one at a time into fresh buffers, a device synchronisation behind each: live rows (the first
-    time: from the state), mlp_actor_critic_rows, step, ..., gae_masked, rollout_index; evaluation j has tick j."""
-    import torch
-    eng, T, N, A, D = S.eng, COL_T, COL_N, COL_A, S.eng.D
-
-    def evaluate(obs, rows, count, tick):
-        a = torch.full((N, A, 2), SENT, dtype=torch.float32, device="cuda")
-        lp = torch.full((N, A), SENT, dtype=torch.float32, device="cuda")
-        v = torch.full((N, A), SENT, dtype=torch.float32, device="cuda")
-        eng.mlp_actor_critic_rows(S.pw, S.vw, rows, count, a, lp, v, COL_SEED, tick, obs=obs)
-        torch.cuda.synchronize()
-        return a, lp, v
-
-    obs = S.first.clone()
-    live0 = np.flatnonzero(S.active0.reshape(-1)).astype(np.int32)
-    rows = torch.zeros((N * A, ), dtype=torch.int32, device="cuda")
-    rows[:len(live0)] = _dev(live0)
-    a, lp, v = evaluate(obs, rows, _dev(np.array([len(live0)], dtype=np.int32)), 0)
-    out = []
-    for k in range(n_rollouts):
-        rec = {key: [] for key in KEYS}
-        for t in range(T):
-            rec["obs"].append(obs.view(N, A, D))
-            rec["actions"].append(a)
-            rec["logp"].append(lp)
-            rec["values"].append(v)
-            fresh = eng.make_outputs()
-            obs, rew, done, flags = eng.step(a, out=fresh)
-            torch.cuda.synchronize()
-            rec["rewards"].append(rew)
-            rec["dones"].append(done)
-            rec["flags"].append(flags)
-            rows, count = eng.live_rows(flags, done)
-            torch.cuda.synchronize()
-            a, lp, v = evaluate(obs, rows, count, k * T + t + 1)
-        rec["values"].append(v)
-        r = {key: torch.stack(rec[key]) for key in KEYS if rec[key]}
-        r["advantages"], r["returns"], r["mask"] = eng.gae_masked(r["rewards"], r["values"], r["dones"], r["flags"], 0.99, 0.95)
-        torch.cuda.synchronize()
-        index = torch.zeros((T * N * A, ), dtype=torch.int32, device="cuda")
-        r["index"], r["count"] = eng.rollout_index(r["flags"], index=index)
-        torch.cuda.synchronize()
-        out.append(r)
-    return out
-
-
 def _batch_equal(got, want, where):
     n = int(want["count"].item())
     assert int(got["count"].item()) == n, (where, "count")
@@ -511,7 +427,7 @@ def test_collector_on_the_roundabout():
     from pgdrive_amd.rollout import MultiAgentRolloutCollector
     T, N, A = COL_T, COL_N, COL_A
     S = _Col()
-    want = _synchronised_rollouts(S, COL_ROLLOUTS)
+    want = synchronised_rollouts(S, COL_ROLLOUTS, COL_T, COL_SEED, KEYS, live0=np.flatnonzero(S.active0.reshape(-1)).astype(np.int32))
 
     # what the rollouts hold
     fl = np.concatenate([r["flags"].cpu().numpy() for r in want]).view(np.uint32)      # [3 T, N, A]
@@ -562,7 +478,7 @@ def test_collector_on_the_roundabout():
     with torch.cuda.stream(s), torch.no_grad():
         for k in range(COL_ROLLOUTS):
             batch = col.collect()
-            got = _snapshot(batch)
+            got = _snapshot(batch, KEYS)
             assert tuple(batch["obs"].shape) == (T, N, A, E.eng.D) and tuple(batch["values"].shape) == (T + 1, N, A)
             assert tuple(batch["mask"].shape) == (T, N, A) and tuple(batch["index"].shape) == (T * N * A, ) and tuple(batch["count"].shape) == (1, )
             _batch_equal(got, want[k], "eager collect %d" % k)
@@ -576,7 +492,7 @@ def test_collector_on_the_roundabout():
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s), torch.no_grad():
-        _batch_equal(_snapshot(col.collect()), want[0], "warm-up collect")
+        _batch_equal(_snapshot(col.collect(), KEYS), want[0], "warm-up collect")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
     with torch.no_grad(), torch.cuda.graph(g, stream=s):
@@ -585,6 +501,6 @@ def test_collector_on_the_roundabout():
     with torch.cuda.stream(s), torch.no_grad():
         for k in (1, 2):
             g.replay()
-            _batch_equal(_snapshot(batch), want[k], "graph replay %d" % k)
+            _batch_equal(_snapshot(batch, KEYS), want[k], "graph replay %d" % k)
     del g
     B.eng.close()

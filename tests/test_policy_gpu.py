@@ -37,6 +37,7 @@ import numpy as np
 import pytest
 
 from tests import policy_ref as pr
+from tests.train_util import dev as _dev, ego_engine as _ego_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -44,22 +45,6 @@ SENT = 7.0  # what every output buffer holds before a launch
 ERR_ARG, ERR_STATE = 1, 3
 KINDS = ("exact", "bf16")
 TOL = dict(exact=pr.TOL_EXACT, bf16=pr.TOL_BF16)
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _ego_engine(descs, n, **kw):
-    """n envs, ego only, no lidar: cheap to create; the policy kernels only need its row count, groups and streams."""
-    from pgdrive_amd import _abi
-    from pgdrive_amd.engine import Engine
-    from tests import util
-    mb, sb = util.make_banks(descs, n_maps=4, num_traffic=0)
-    args = dict(num_agents=1, num_traffic=0, num_lasers=0, seed=2)
-    args.update(kw)
-    return Engine(_abi.make_config(n, **args), mb, sb)
 
 
 def _launch(eng, kind, obs, wt, out, ft, in_dim, group=-1, prep=None):

@@ -21,26 +21,15 @@ import pytest
 
 from tests import actor_critic_ref as ar
 from tests import ppo_ref as rf
+from tests.train_util import ERR_ARG, SENT, ac_nets, dev as _dev, ego_engine, six
 
 pytestmark = pytest.mark.gpu
-
-SENT = 7.0
-ERR_ARG = 1
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.fixture(scope="module")
 def eng(descs):
     """One env, ego only, no lidar: the update kernels need the engine for its device and stream only."""
-    from pgdrive_amd import _abi
-    from pgdrive_amd.engine import Engine
-    from tests import util
-    mb, sb = util.make_banks(descs, n_maps=4, num_traffic=0)
-    e = Engine(_abi.make_config(1, num_agents=1, num_traffic=0, num_lasers=0, seed=2), mb, sb)
+    e = ego_engine(descs, 1)
     yield e
     e.close()
 
@@ -86,13 +75,9 @@ def _grad(eng, P, start=0, stride=1, rows=None, critic=True, ent_coef=rf.ENT_COE
     need = eng.L.pgd_ppo_work_bytes(k, rows, int(critic))
     assert need > 0
     work = torch.full(((need + 3) // 4 + shift, ), float("nan"), dtype=torch.float32, device="cuda")
-    nets, grads, b = _abi.ActorCritic(), _abi.PPOGrads(), _abi.PPOBatch()
-    nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = [w.data_ptr() for w in P.pw]
-    nets.out_cols = oc
-    grads.w1, grads.b1, grads.w2, grads.b2, grads.w3, grads.b3 = [g.data_ptr() for g in pg]
+    nets, grads, b = ac_nets(P.pw, P.vw if critic else None, oc), six(_abi.PPOGrads(), pg), _abi.PPOBatch()
     if critic:
-        nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = [w.data_ptr() for w in P.vw]
-        grads.vw1, grads.vb1, grads.vw2, grads.vb2, grads.vw3, grads.vb3 = [g.data_ptr() for g in vg]
+        six(grads, vg, "v")
     b.obs, b.action, b.logp_old, b.adv, b.ret = [P.t[q].data_ptr() for q in ("x", "action", "logp_old", "adv", "ret")]
     b.adv_stats = P.stats_in.data_ptr() if P.stats_in is not None else None
     b.index = P.index.data_ptr() if P.index is not None else None

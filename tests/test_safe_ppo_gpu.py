@@ -22,16 +22,9 @@ import pytest
 from tests import actor_critic_ref as ar
 from tests import ppo_ref as rf
 from tests import safe_ppo_ref as sr
+from tests.train_util import ERR_ARG, SENT, ac_nets, dev as _dev, ego_engine as _ego_engine, six
 
 pytestmark = pytest.mark.gpu
-
-SENT = 7.0
-ERR_ARG = 1
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _bits(t):
@@ -41,15 +34,6 @@ def _bits(t):
 
 def _same(a, b):
     return np.array_equal(_bits(a), _bits(b))
-
-
-def _ego_engine(descs, n):
-    """n envs, ego only, no lidar: the kernels under test need the engine for its rows, device and stream only."""
-    from pgdrive_amd import _abi
-    from pgdrive_amd.engine import Engine
-    from tests import util
-    mb, sb = util.make_banks(descs, n_maps=4, num_traffic=0)
-    return Engine(_abi.make_config(n, num_agents=1, num_traffic=0, num_lasers=0, seed=2), mb, sb)
 
 
 @pytest.fixture(scope="module")
@@ -155,12 +139,7 @@ def test_forward_from_a_graph_with_a_device_tick_and_the_refusals(descs):
             return rc, all(bool((t == SENT).all()) for t in out)
 
         def structs():
-            nets, cnet = _abi.ActorCritic(), _abi.ValueNet()
-            nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = [w.data_ptr() for w in pw]
-            nets.out_cols = int(pw[4].shape[1])
-            nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = [w.data_ptr() for w in vw]
-            cnet.w1, cnet.b1, cnet.w2, cnet.b2, cnet.w3, cnet.b3 = [w.data_ptr() for w in cwd]
-            return nets, cnet
+            return ac_nets(pw, vw), six(_abi.ValueNet(), cwd)
 
         nets, cnet = structs()
         rc, clean = call(nets, cnet)
@@ -392,14 +371,8 @@ def _three(eng, P, count=None, short_by=0, shift=0, expect=0):
     need = eng.L.pgd_ppo_cost_work_bytes(P.k, P.n_list)
     assert need > 0
     work = torch.full(((need + 3) // 4 + shift, ), float("nan"), dtype=torch.float32, device="cuda")
-    nets, grads, cnet, cgr, b = _abi.ActorCritic(), _abi.PPOGrads(), _abi.ValueNet(), _abi.ValueGrads(), _abi.PPOBatch()
-    nets.w1, nets.b1, nets.w2, nets.b2, nets.w3, nets.b3 = [w.data_ptr() for w in P.pw]
-    nets.out_cols = P.oc
-    nets.vw1, nets.vb1, nets.vw2, nets.vb2, nets.vw3, nets.vb3 = [w.data_ptr() for w in P.vw]
-    cnet.w1, cnet.b1, cnet.w2, cnet.b2, cnet.w3, cnet.b3 = [w.data_ptr() for w in P.cw]
-    grads.w1, grads.b1, grads.w2, grads.b2, grads.w3, grads.b3 = [g.data_ptr() for g in pg]
-    grads.vw1, grads.vb1, grads.vw2, grads.vb2, grads.vw3, grads.vb3 = [g.data_ptr() for g in vg]
-    cgr.w1, cgr.b1, cgr.w2, cgr.b2, cgr.w3, cgr.b3 = [g.data_ptr() for g in cg]
+    nets, cnet, b = ac_nets(P.pw, P.vw, P.oc), six(_abi.ValueNet(), P.cw), _abi.PPOBatch()
+    grads, cgr = six(six(_abi.PPOGrads(), pg), vg, "v"), six(_abi.ValueGrads(), cg)
     b.obs, b.action, b.logp_old, b.adv, b.ret = [P.t[q].data_ptr() for q in ("x", "action", "logp_old", "adv", "ret")]
     b.adv_stats = P.stats_in.data_ptr() if P.stats_in is not None else None
     cnt = P.count if count is None else count
