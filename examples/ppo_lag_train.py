@@ -4,6 +4,7 @@ then pgd_lagrange, pgd_adv_stats twice, pgd_adv_mix and pgd_ppo_grad_cost + pgd_
 
     python examples/ppo_lag_train.py --envs 256 --T 32 --eager 3 --replays 20 [--cost-limit 1.0] [--every 5]
     python examples/ppo_lag_train.py --time --envs 4096 --T 128 [--windows 7] [--calls 3] [--plain]
+    python examples/ppo_lag_train.py --horizon 100 --bootstrap-truncations     # an episode that ends at the horizon is bootstrapped, not cut
 
 The env is PGDriveVecEnv configured as SafePGDriveEnv (pgdrive/envs/safe_pgdrive_env.py:7-60): accident scenes on the road, crashes are
 costs and not terminations.  A few iterations run eagerly; then one `collect(); update()` is captured in a HIP graph and replayed.
@@ -47,11 +48,11 @@ def make(args):
     env.reset()
     if getattr(args, "plain", False):
         from pgdrive_amd import PPOLearner, RolloutCollector
-        col = RolloutCollector(env, pw, vw, args.T, seed=0)
+        col = RolloutCollector(env, pw, vw, args.T, seed=0, bootstrap_truncations=args.bootstrap_truncations)
         learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches)
     else:
         from pgdrive_amd import PPOLagLearner, SafeRolloutCollector
-        col = SafeRolloutCollector(env, pw, vw, cw, args.T, seed=0)
+        col = SafeRolloutCollector(env, pw, vw, cw, args.T, seed=0, bootstrap_truncations=args.bootstrap_truncations)
         learner = PPOLagLearner(col, cost_limit=args.cost_limit, lambda_lr=args.lambda_lr, lr=args.lr, epochs=args.epochs,
                                 minibatches=args.minibatches)
     return env, col, learner
@@ -119,6 +120,8 @@ def main():
     ap.add_argument("--plain", action="store_true", help="--time: RolloutCollector + PPOLearner instead of the safe pair")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--calls", type=int, default=3, help="calls per timed window")
+    ap.add_argument("--bootstrap-truncations", action="store_true",
+                    help="GAE and cost GAE bootstrap through the horizon from the critics' values of the terminal observation (DESIGN.md section 24)")
     args = ap.parse_args()
     if args.time:
         return time_pair(args)

@@ -150,19 +150,26 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--updates", type=int, default=3, help="updates per timed window")
     ap.add_argument("--only", default="", help="--time: only the forms whose name contains this")
+    ap.add_argument("--horizon", type=int, default=None, help="the time limit of an episode (default: none)")
+    ap.add_argument("--bootstrap-truncations", action="store_true",
+                    help="GAE bootstraps through the horizon from the critic's value of the terminal observation (DESIGN.md section 24)")
     args = ap.parse_args()
     if args.time:
         return time_update(args)
     if args.marl:
         env = MultiAgentRoundaboutVecEnv(dict(num_envs=args.envs, num_agents=args.agents, seed=3))
     else:
-        env = PGDriveVecEnv(dict(num_envs=args.envs, start_seed=1000, environment_num=100, auto_reset=True))
+        env = PGDriveVecEnv(dict(num_envs=args.envs, start_seed=1000, environment_num=100, auto_reset=True, horizon=args.horizon))
     eng = env.engine
     print("pgd_source_sha %s; %d envs x %d seats x T = %d, %d epochs x %d minibatches, %s" % (
         eng.L.pgd_source_sha().decode(), args.envs, eng.A, args.T, args.epochs, args.minibatches, "HIP graph" if args.graph else "eager"))
     pw, vw = random_networks(env.obs_dim, np.random.default_rng(0))
     env.reset()
-    col = (MultiAgentRolloutCollector if args.marl else RolloutCollector)(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0)
+    if args.marl:   # (no such switch: the cause of a done cannot be read from a multi-agent step's flags)
+        assert not args.bootstrap_truncations, "--bootstrap-truncations serves single-agent engines"
+        col = MultiAgentRolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0)
+    else:
+        col = RolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, bootstrap_truncations=args.bootstrap_truncations)
     learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, ent_coef=0.0)
 
     def iteration():

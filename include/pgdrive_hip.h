@@ -448,7 +448,8 @@ int pgd_actor_critic_tick(pgd_handle h, const uint32_t* d_tick /* device memory,
  * ret [T][rows]; value [T + 1][rows], row T the bootstrap.  One thread per row, t from T - 1 down to 0, fp32:
  *   nonterminal = 1 - done[t][r];  delta = reward[t][r] + gamma value[t+1][r] nonterminal - value[t][r]
  *   adv[t][r] = delta + gamma lam nonterminal adv[t+1][r]  (adv[T] = 0);   ret[t][r] = adv[t][r] + value[t][r]
- * A done ends the episode for GAE whatever ended it: no bootstrap through a horizon truncation.  T >= 1, rows >= 1 (PGD_ERR_ARG).
+ * A done ends the episode for GAE whatever ended it: no bootstrap through a horizon truncation (pgd_gae_bootstrap, below, has one).
+ * T >= 1, rows >= 1 (PGD_ERR_ARG).
  * Asynchronous on the engine's stream; may be captured in a HIP graph. */
 int pgd_gae(pgd_handle h, const float* d_reward, const float* d_value /*[T+1][rows]*/, const uint8_t* d_done, int T, int rows,
             float gamma, float lam, float* d_adv, float* d_ret);
@@ -642,6 +643,51 @@ size_t pgd_ppo_cost_work_bytes(int in_dim, int rows);
 int pgd_ppo_grad_cost(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
                       const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
                       float* d_stats /*[8]*/, void* d_work, size_t work_bytes);
+/* ---- GAE that bootstraps through a time limit: terminal values on the device (single-agent engines) -------------------------------------
+ * (No reference counterpart: the reference returns the terminal observation from env.step, base_env.py:303-344, and `max_step` in its
+ * info, base_env.py:190-192; an RL library evaluates its critic on it on the host and patches the reward.)
+ * pgd_gae and pgd_cost_gae end the episode at every done with a one-step target of 0.  A time limit is no property of the task and the
+ * observation holds no clock; the entry points below give a truncated episode the critic's value of its terminal observation instead.
+ * For row r of a single-agent engine and step t, let f = flags[t][r] and d = done[t][r], as pgd_step wrote them, and safe =
+ * pgd_config.safe_rl_env of the engine:
+ *   natural(t)   = f & (PGD_F_ARRIVE | PGD_F_OUT_OF_ROAD | PGD_F_CRASH_VEHICLE | PGD_F_CRASH_OBJECT | PGD_F_CRASH_BUILDING),
+ *                  and false when safe && f & (PGD_F_CRASH_VEHICLE | PGD_F_CRASH_OBJECT)      the step's own done rule (pgdrive_env.py:162-194,
+ *                                                                                             safe_pgdrive_env.py:49-56)
+ *   truncated(t) = d && (f & PGD_F_MAX_STEP) && !natural(t)                                   the clock alone ended the episode
+ * Both pgd_config.horizon and a scenario's max_steps set PGD_F_MAX_STEP and count; where a termination falls on the same step it wins:
+ * no bootstrap.  On a multi-agent engine the cause of a done cannot be read from the flags alone (the tollgate's stay-time rule, the
+ * env-wide cut at 5 x horizon): not served.
+ *
+ * pgd_mlp_terminal_value: the value of the terminal observation of every truncated row, 0 for every other row.  d_term_obs: the final_obs
+ * array of the step info (pgd_step_info), or any [rows][obs_stride] array; rows and `group` as for pgd_mlp_actor_critic; d_flags, d_done
+ * the FULL arrays of the step; d_term_value [rows] and, with cost_critic, d_term_cost_value [rows] are written at every row of the range:
+ *   term_value[r] = truncated ? critic(term_obs[r]) : 0          term_cost_value[r] = truncated ? cost_critic(term_obs[r]) : 0
+ * One launch, grid (ceil(rows / 16), 1 or 2): a workgroup reads the flags and dones of its 16 rows first and, when none is truncated,
+ * writes its zeros and ends before it reads a weight or an observation (a NaN there reaches no output); otherwise it is the critic
+ * workgroup of pgd_mlp_actor_critic with the rows that are not truncated entered as zeros (their term_obs row is stale or was never
+ * written and may hold NaN).  A truncated row receives bit for bit what pgd_mlp_actor_critic writes into d_value for the same
+ * observation row and weights, and d_term_cost_value what a second call writes that is handed cost_critic as `critic`.  No noise, no
+ * tick.  in_dim 4 .. 416, obs_stride >= in_dim, all six pointers of `critic` (and of `cost_critic` when given) set, w1, b1, w2, b2
+ * 16-byte aligned, d_term_cost_value with cost_critic, a single-agent engine (PGD_ERR_ARG otherwise).  Asynchronous on the engine's stream
+ * (group >= 0: the group's); capturable in a HIP graph.
+ *
+ * pgd_gae_bootstrap: pgd_gae with one more time-major input term_value [T][rows], fp32, the fma forms of pgd_gae:
+ *   vb = done[t] ? term_value[t] : value[t + 1];   delta = reward[t] + gamma vb - value[t]
+ *   adv[t] = delta + gamma lam (done[t] ? 0 : adv[t + 1]);   ret[t] = adv[t] + value[t]
+ * done SELECTS: value[t + 1] behind a done may hold anything, NaN included.  The trace still ends at every done; only the one-step
+ * target changes.  With term_value zero everywhere and finite inputs, adv and ret equal pgd_gae's as float values.
+ * pgd_cost_gae_bootstrap: pgd_cost_gae with term_cost_value [T][rows]: the forward pass (cost, run, ep_sum, ep_count) is pgd_cost_gae's
+ * bit for bit -- a truncated episode still finishes for the multiplier's books --, the reverse pass the recursion above with cost as
+ * the reward.  Refusals, launches and streams as for pgd_gae and pgd_cost_gae. */
+int pgd_mlp_terminal_value(pgd_handle h, int group, const float* d_term_obs, int obs_stride, int in_dim, const pgd_value_net* critic,
+                           const pgd_value_net* cost_critic /* or null */, const uint32_t* d_flags /*[rows]*/, const uint8_t* d_done /*[rows]*/,
+                           float* d_term_value /*[rows]*/, float* d_term_cost_value /*[rows], with cost_critic*/);
+int pgd_gae_bootstrap(pgd_handle h, const float* d_reward, const float* d_value /*[T+1][rows]*/, const uint8_t* d_done,
+                      const float* d_term_value /*[T][rows]*/, int T, int rows, float gamma, float lam, float* d_adv, float* d_ret);
+int pgd_cost_gae_bootstrap(pgd_handle h, const uint32_t* d_flags /*[T][rows]*/, const uint8_t* d_done, const float* d_cost_value /*[T+1][rows]*/,
+                           const float* d_term_cost_value /*[T][rows]*/, int T, int rows, const float costs[3], float gamma, float lam,
+                           float* d_cost /*[T][rows]*/, float* d_cadv, float* d_cret, float* d_run /*[rows], in/out*/,
+                           float* d_ep_sum /*[rows]*/, int32_t* d_ep_count /*[rows]*/);
 /* Multi-agent engines remember, per env, which rows of the LAST observation buffer they were given already hold the zeros of a seat
  * that is not due (identified by the buffer's address and row stride), and do not write them again.  A caller that hands pgd_step
  * a buffer whose address a FORMER buffer had (a caching allocator re-using a freed block: torch.empty per step) calls this first:

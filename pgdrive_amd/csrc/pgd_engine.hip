@@ -39,7 +39,7 @@ static Switches read_switches() {
           rowz && rowz[0] != '0', on("PGD_NO_UNI"), pack ? (atoi(pack) != 0 ? 1 : 0) : -1, on("PGD_NO_IMASK") ? 0 : (on("PGD_IMASK") ? 1 : -1)};
 }
 // The kernels that take more than 48 KB of dynamic LDS at wide inputs: their limit is raised once per engine (raise_lds_limit)
-enum LdsKernel { LDS_MLP, LDS_MLP_TANH, LDS_MLP_BF, LDS_MLP_BF_TANH, LDS_AC, LDS_AC_ROWS, LDS_AC_COST, LDS_PPO_ROWS, LDS_PPO_ROWS_COST, LDS_KERNELS };
+enum LdsKernel { LDS_MLP, LDS_MLP_TANH, LDS_MLP_BF, LDS_MLP_BF_TANH, LDS_AC, LDS_AC_ROWS, LDS_AC_COST, LDS_PPO_ROWS, LDS_PPO_ROWS_COST, LDS_TERM_VALUE, LDS_KERNELS };
 struct pgd_engine {
   PgdDev d;
   Switches sw;
@@ -1407,4 +1407,5 @@ int pgd_destroy(pgd_handle h) {
 #include "pgd_step_info.h"
 #include "pgd_ppo.h"
 #include "pgd_safe.h"
+#include "pgd_timelimit.h"
 #endif  // !PGD_JIT

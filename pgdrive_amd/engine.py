@@ -60,6 +60,12 @@ _SIGS = {
     "pgd_ppo_grad_cost": (C.c_int, [C.c_void_p, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.ValueNet), C.POINTER(_abi.PPOBatch),
                                     C.POINTER(_abi.PPOCost), C.POINTER(_abi.PPOHyper), C.POINTER(_abi.PPOGrads), C.POINTER(_abi.ValueGrads),
                                     C.c_void_p, C.c_void_p, C.c_size_t]),
+    "pgd_mlp_terminal_value": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ValueNet), C.POINTER(_abi.ValueNet),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgd_gae_bootstrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                    C.c_void_p]),
+    "pgd_cost_gae_bootstrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float,
+                                         C.c_float] + [C.c_void_p] * 6),
     "pgd_step_lane_keep": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 4),
     "pgd_lane_keep_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32]),
     "pgd_topdown_channels": (C.c_int, [C.POINTER(_abi.TopDownConfig)]),
@@ -711,6 +717,59 @@ class Engine:
         _chk(self.L.pgd_ppo_grad_cost(self.h, C.byref(nets), C.byref(cnet), C.byref(b), C.byref(pc), C.byref(hp), C.byref(grads), C.byref(cgrads),
                                       _p(stats), _p(work), work.numel() * work.element_size()), "pgd_ppo_grad_cost")
         return stats
+
+    # -- GAE that bootstraps through a time limit (include/pgdrive_hip.h states `truncated` and the formulas) ---------------------------
+    def mlp_terminal_value(self, value_weights, cost_weights, term_obs, flags, done, term_value, term_cost_value=None, group=-1, in_dim=None):
+        """The critic's value of the terminal observation of every env the step truncated, 0 for every other env, in one launch
+        (pgd_mlp_terminal_value): `term_obs` [N, >= in_dim] float32 cuda with unit column stride -- step_info["final_observation"] --,
+        `flags` (int32) and `done` (uint8) [N] as the step wrote them, `term_value` [N] float32 (written at every row).  `cost_weights`
+        (None: no cost critic) has the shapes of `value_weights`; its values go to `term_cost_value` [N].  A truncated row gets the bits
+        mlp_actor_critic's `value` has for the same row and weights.  Single-agent engines.  `group`, `in_dim` as for mlp_policy.
+        Asynchronous."""
+        t = self.torch
+        rows = self.N * self.A
+        o2 = term_obs.view(-1, term_obs.shape[-1])
+        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == rows
+        assert flags.is_cuda and flags.dtype == t.int32 and flags.is_contiguous() and flags.numel() == rows
+        assert done.is_cuda and done.dtype == t.uint8 and done.is_contiguous() and done.numel() == rows
+        assert (cost_weights is None) == (term_cost_value is None), "term_cost_value comes with the cost critic"
+        for v in (term_value, term_cost_value):
+            assert v is None or (v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == rows)
+        k = int(in_dim if in_dim is not None else value_weights[0].shape[0])
+        assert k <= o2.shape[1]
+        critic = self._value_net(_abi.ValueNet(), value_weights, k)
+        cost = None if cost_weights is None else C.byref(self._value_net(_abi.ValueNet(), cost_weights, k))
+        if group < 0:
+            self._follow_stream()
+        _chk(self.L.pgd_mlp_terminal_value(self.h, int(group), _p(o2), int(o2.stride(0)), k, C.byref(critic), cost, _p(flags), _p(done),
+                                           _p(term_value), _p(term_cost_value) if term_cost_value is not None else None),
+             "pgd_mlp_terminal_value")
+        return term_value, term_cost_value
+
+    def gae_bootstrap(self, reward, value, done, term_value, gamma, lam, adv=None, ret=None):
+        """gae with the one-step target of a done row taken from `term_value` [T, rows...] (pgd_gae_bootstrap): the critic's value of the
+        terminal observation where the episode was truncated, 0 where it terminated, as mlp_terminal_value writes it.  Every other
+        argument and the result as for gae."""
+        t = self.torch
+        T, rows, (reward, value, done, term_value, adv, ret) = self._rollout_buffers(
+            reward, ((reward, t.float32, 0), (value, t.float32, 1), (done, t.uint8, 0), (term_value, t.float32, 0), (adv, t.float32, 0),
+                     (ret, t.float32, 0)))
+        _chk(self.L.pgd_gae_bootstrap(self.h, _p(reward), _p(value), _p(done), _p(term_value), T, rows, float(gamma), float(lam), _p(adv), _p(ret)),
+             "pgd_gae_bootstrap")
+        return adv, ret
+
+    def cost_gae_bootstrap(self, flags, done, cost_value, term_cost_value, costs, gamma, lam, run, cost=None, adv=None, ret=None, ep_sum=None,
+                           ep_count=None):
+        """cost_gae with the one-step target of a done row taken from `term_cost_value` [T, rows...] (pgd_cost_gae_bootstrap); the costs
+        and the books of episode costs are cost_gae's.  Every other argument and the result as for cost_gae."""
+        t = self.torch
+        T, rows, (flags, done, cost_value, term_cost_value, cost, adv, ret, run, ep_sum, ep_count) = self._rollout_buffers(
+            flags, ((flags, t.int32, 0), (done, t.uint8, 0), (cost_value, t.float32, 1), (term_cost_value, t.float32, 0), (cost, t.float32, 0),
+                    (adv, t.float32, 0), (ret, t.float32, 0), (run, t.float32, None), (ep_sum, t.float32, None), (ep_count, t.int32, None)))
+        c3 = (C.c_float * 3)(*[float(c) for c in costs])
+        _chk(self.L.pgd_cost_gae_bootstrap(self.h, _p(flags), _p(done), _p(cost_value), _p(term_cost_value), T, rows, c3, float(gamma), float(lam),
+                                           _p(cost), _p(adv), _p(ret), _p(run), _p(ep_sum), _p(ep_count)), "pgd_cost_gae_bootstrap")
+        return cost, adv, ret, ep_sum, ep_count
 
     def step_lane_keep(self, tick, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):
         """One closed-loop step under the scripted lane-keeping policy (pgd_step_lane_keep): the policy reads the engine's own

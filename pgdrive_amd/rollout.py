@@ -23,6 +23,8 @@ to a counter in device memory that collect() advances by T on the stream, so a c
 replay and equals the eager call bit for bit.
 
 A done ends the episode for GAE, whatever ended it: there is no bootstrap through a horizon truncation from the terminal observation.
+bootstrap_truncations=True (RolloutCollector, SafeRolloutCollector) changes that: the critic's value of the terminal observation of every
+env a step truncated is computed in that step and GAE takes it as the one-step target (`truncated`, below).
 
 Constrained RL on the safe env: SafeRolloutCollector, below -- this collector with a cost critic in the step's launch, the costs
 from the flags, their GAE and the books of episode costs.
@@ -31,6 +33,20 @@ Multi-agent engines: MultiAgentRolloutCollector, below -- the same layout and ca
 seats only, GAE per agent and not per seat, and the index of the transitions a trainer may use.
 """
 import numpy as np
+
+F_NATURAL = 1 | 2 | 4 | 8 | 16   # PGD_F_ARRIVE | OUT_OF_ROAD | CRASH_VEHICLE | CRASH_OBJECT | CRASH_BUILDING
+F_CRASH_COST = 4 | 8             # PGD_F_CRASH_VEHICLE | CRASH_OBJECT: with safe_rl_env a cost, not a termination
+F_MAX_STEP = 32                  # PGD_F_MAX_STEP
+
+
+def truncated(flags, done, safe_rl_env=False):
+    """Which dones of a single-agent step are truncations (include/pgdrive_hip.h, `truncated`): the step set PGD_F_MAX_STEP (horizon or
+    the scenario's max_steps) and none of its own causes of a done; a termination on the same step wins.  `flags`, `done`: numpy arrays
+    or torch tensors of one shape (or python ints) -> a bool array / tensor of that shape."""
+    natural = (flags & F_NATURAL) != 0
+    if safe_rl_env:
+        natural = natural & ((flags & F_CRASH_COST) == 0)
+    return (done != 0) & ((flags & F_MAX_STEP) != 0) & ~natural
 
 
 class _Collector:
@@ -99,7 +115,12 @@ class _Collector:
 
 
 class RolloutCollector(_Collector):
-    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0):
+    """bootstrap_truncations=True: GAE bootstraps through a time limit.  The collector uses the engine's step info (it enables it with
+    final_obs=True when it is off; an engine whose step info has no final_observation -- image observations -- is refused).  After every
+    step one more launch (Engine.mlp_terminal_value) writes `term_values[t]`: the critic's value, with the weights of this rollout, of
+    step_info["final_observation"] where the step truncated the env, 0 elsewhere; Engine.gae_bootstrap takes it as the one-step target
+    of the done rows.  The batch gains term_values [T, N].  False (the default): the calls and the batch of before."""
+    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, bootstrap_truncations=False):
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A != 1:
             raise NotImplementedError(
@@ -107,14 +128,38 @@ class RolloutCollector(_Collector):
                 "that this class does not know -- use MultiAgentRolloutCollector" % eng.A)
         if int(T) < 1:
             raise ValueError("RolloutCollector: T = %r" % (T, ))
+        self.bootstrap_truncations = bool(bootstrap_truncations)
+        if self.bootstrap_truncations:
+            if eng.step_info is None:
+                eng.enable_step_info(final_obs=True)
+            if eng.step_info.get("final_observation") is None:
+                raise ValueError("bootstrap_truncations needs the terminal observation of the step info, and this engine's step info has no "
+                                 "final_observation (image observations: enable_step_info(final_obs=False))")
         self._allocate(eng, (eng.N, ), policy_weights, value_weights, T, gamma, lam, seed)
+        if self.bootstrap_truncations:
+            self.term_values = eng.torch.zeros((self.T, eng.N), dtype=eng.torch.float32, device=eng.device)
+            self.batch.update(term_values=self.term_values)
 
     def _evaluate(self, row):
         self.engine.mlp_actor_critic(self.policy_weights, self.value_weights, self._actions[row], self._logp[row], self.values[row], self.seed,
                                      row, obs=self._obs[row])
 
+    def _cost_side(self, t):
+        """(cost_weights, term_cost_values[t]) of the terminal-value launch: none here."""
+        return None, None
+
+    def _stepped(self, t):
+        if self.bootstrap_truncations:
+            cw, tcv = self._cost_side(t)
+            self.engine.mlp_terminal_value(self.value_weights, cw, self.engine.step_info["final_observation"], self.flags[t], self.dones[t],
+                                           self.term_values[t], tcv)
+
     def _finish(self):
-        self.engine.gae(self.rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
+        if self.bootstrap_truncations:
+            self.engine.gae_bootstrap(self.rewards, self.values, self.dones, self.term_values, self.gamma, self.lam, adv=self.advantages,
+                                      ret=self.returns)
+        else:
+            self.engine.gae(self.rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
 
 
 class SafeRolloutCollector(RolloutCollector):
@@ -134,11 +179,16 @@ class SafeRolloutCollector(RolloutCollector):
     The cost of an env's unfinished episode is carried in the collector's `running_cost` [N]: a caller who resets envs by hand (rather
     than by the engine's auto reset, which reports a done) zeroes their entries.  A done finishes an episode for this bookkeeping
     whatever ended it, a horizon truncation included, as it does for GAE.  Nothing in collect() waits for the device, and a captured
-    collect() equals the eager call bit for bit."""
+    collect() equals the eager call bit for bit.
+
+    bootstrap_truncations=True: as for RolloutCollector, with the cost critic in the same terminal-value launch; the batch gains
+    term_values and term_cost_values [T, N], and Engine.cost_gae_bootstrap takes the latter as the cost side's one-step target.  The
+    books of episode costs are unchanged: a truncated episode still finishes for them."""
     def __init__(self, env_or_engine, policy_weights, value_weights, cost_weights, T, costs=None, gamma=0.99, lam=0.95, cost_gamma=0.99,
-                 cost_lam=0.95, seed=0):
+                 cost_lam=0.95, seed=0, bootstrap_truncations=False):
         self.cost_weights = tuple(cost_weights)
-        super().__init__(env_or_engine, policy_weights, value_weights, T, gamma=gamma, lam=lam, seed=seed)
+        super().__init__(env_or_engine, policy_weights, value_weights, T, gamma=gamma, lam=lam, seed=seed,
+                         bootstrap_truncations=bootstrap_truncations)
         eng = self.engine
         t = eng.torch
         if costs is None:
@@ -161,6 +211,9 @@ class SafeRolloutCollector(RolloutCollector):
         self._carry = self._carry + (self.cost_values, )
         self.batch.update(costs=self.cost, cost_values=self.cost_values, cost_advantages=self.cost_advantages, cost_returns=self.cost_returns,
                           ep_cost_sum=self.ep_cost_sum, ep_cost_count=self.ep_cost_count)
+        if self.bootstrap_truncations:
+            self.term_cost_values = t.zeros((T, N), **f32)
+            self.batch.update(term_cost_values=self.term_cost_values)
 
     def set_weights(self, policy_weights, value_weights, cost_weights=None):
         """The networks of the rollouts from now on; cost_weights None: the cost critic stays what it is."""
@@ -172,10 +225,18 @@ class SafeRolloutCollector(RolloutCollector):
         self.engine.mlp_actor_critic_cost(self.policy_weights, self.value_weights, self.cost_weights, self._actions[row], self._logp[row],
                                           self.values[row], self.cost_values[row], self.seed, row, obs=self._obs[row])
 
+    def _cost_side(self, t):
+        return self.cost_weights, self.term_cost_values[t]
+
     def collect(self):
         """T steps.  Returns RolloutCollector's dict with costs, cost_values, cost_advantages, cost_returns, ep_cost_sum, ep_cost_count
         (the same objects every time, valid until the next call)."""
         super().collect()
+        if self.bootstrap_truncations:
+            self.engine.cost_gae_bootstrap(self.flags, self.dones, self.cost_values, self.term_cost_values, self.costs, self.cost_gamma,
+                                           self.cost_lam, self.running_cost, cost=self.cost, adv=self.cost_advantages, ret=self.cost_returns,
+                                           ep_sum=self.ep_cost_sum, ep_count=self.ep_cost_count)
+            return self.batch
         self.engine.cost_gae(self.flags, self.dones, self.cost_values, self.costs, self.cost_gamma, self.cost_lam, self.running_cost,
                              cost=self.cost, adv=self.cost_advantages, ret=self.cost_returns, ep_sum=self.ep_cost_sum,
                              ep_count=self.ep_cost_count)
