@@ -153,6 +153,8 @@ def main():
     ap.add_argument("--horizon", type=int, default=None, help="the time limit of an episode (default: none)")
     ap.add_argument("--bootstrap-truncations", action="store_true",
                     help="GAE bootstraps through the horizon from the critic's value of the terminal observation (DESIGN.md section 24)")
+    ap.add_argument("--normalise-rewards", action="store_true",
+                    help="GAE reads the rewards divided by the standard deviation of the running discounted return (DESIGN.md section 25)")
     args = ap.parse_args()
     if args.time:
         return time_update(args)
@@ -167,9 +169,10 @@ def main():
     env.reset()
     if args.marl:   # (no such switch: the cause of a done cannot be read from a multi-agent step's flags)
         assert not args.bootstrap_truncations, "--bootstrap-truncations serves single-agent engines"
-        col = MultiAgentRolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0)
+        col = MultiAgentRolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, normalise_rewards=args.normalise_rewards)
     else:
-        col = RolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, bootstrap_truncations=args.bootstrap_truncations)
+        col = RolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, bootstrap_truncations=args.bootstrap_truncations,
+                               normalise_rewards=args.normalise_rewards)
     learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, ent_coef=0.0)
 
     def iteration():
@@ -201,8 +204,9 @@ def main():
                     reward = float(b["rewards"].view(-1)[b["index"][:n].long()].mean()) if n else 0.0
                 else:
                     reward = float(b["rewards"].mean())
+                scale = "  reward scale %.4g" % float(b["return_norm"][3]) if args.normalise_rewards else ""
                 print("iteration %4d  Adam step %5d  mean reward %8.4f  " % (it, int(learner.step[0]), reward) +
-                      "  ".join("%s %.4g" % (k, x) for k, x in zip(_abi.PPO_STATS[:7], st)))
+                      "  ".join("%s %.4g" % (k, x) for k, x in zip(_abi.PPO_STATS[:7], st)) + scale)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print("%d iterations in %.2f s: %.1f k env-steps/s including the prints" % (args.iters, dt, args.iters * args.envs * args.T / dt / 1e3))

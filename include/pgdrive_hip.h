@@ -688,6 +688,42 @@ int pgd_cost_gae_bootstrap(pgd_handle h, const uint32_t* d_flags /*[T][rows]*/, 
                            const float* d_term_cost_value /*[T][rows]*/, int T, int rows, const float costs[3], float gamma, float lam,
                            float* d_cost /*[T][rows]*/, float* d_cadv, float* d_cret, float* d_run /*[rows], in/out*/,
                            float* d_ep_sum /*[rows]*/, int32_t* d_ep_count /*[rows]*/);
+/* ---- Reward scaling by the running return, in front of GAE (every engine) ---------------------------------------------------------------
+ * (No reference counterpart: the reference hands its rewards to an RL library; this is the norm_reward half of Stable-Baselines3's
+ * VecNormalize -- the reward divided by the standard deviation of the running discounted return -- as one call over a rollout.)
+ * Time-major device arrays: reward (float), done (the uint8 pgd_step writes) [T][rows]; flags [T][rows] (the uint32 pgd_step writes) or
+ * null; scaled [T][rows] float, WRITTEN.  Two caller-owned device objects live across calls:
+ *   carry  [rows] floats: the discounted return of each row's running episode; zero before the first call
+ *   record four doubles, 8-byte aligned: count, mean, m2, scale; 1e-4, 0, 1e-4, 1 before the first call (VecNormalize's RunningMeanStd:
+ *          mean 0, variance 1, count 1e-4; m2 = variance * count)
+ * Per row r, with R = carry[r], for t = 0 .. T - 1 in order, fp32:
+ *   flags null:   R = fma(gamma, R, reward[t][r]);  R is a SAMPLE;  then R = 0 where done[t][r]
+ *   flags given:  acted(t) (as for pgd_gae_masked):  the same update and sample, then R = 0 unless cont(t)
+ *                 otherwise:  no sample, R = 0           (a seat that changes hands starts from 0)
+ * and carry[r] = R behind the loop.  acted and cont SELECT: the reward of a row that did not act may be NaN and reaches nothing.
+ * The statistics, in double: n, bmean and bm2 = the number, the mean and the sum of squared deviations of ALL samples of the call, merged
+ * into the record by Chan's parallel update
+ *   delta = bmean - mean;  tot = count + n;  mean += delta n / tot;  m2 += bm2 + delta^2 count n / tot;  count = tot
+ * and then scale = 1 / sqrt(m2 / count + eps).  A call without a sample leaves count, mean and m2 their bytes (the scale is formed anew,
+ * with this call's eps).
+ * The scaled reward uses the UPDATED scale -- the whole rollout is divided by the standard deviation that already includes the rollout's
+ * own samples, as VecNormalize updates first and then normalises:
+ *   scaled[t][r] = clamp(reward[t][r] * (float)scale, -clip, clip)     (clip <= 0: no clamp);   0 for a row that did not act
+ * The rewards are scaled, not centred.
+ * mode & PGD_RN_FREEZE (evaluation): carry and record are read and not written; only `scaled` is produced, from the scale that stands in
+ * the record.
+ * Deterministic: no atomics; a row's samples are summed in the order of t, the rows of a wave, the waves' partials and the record in a
+ * fixed order: the same inputs give the same bytes.  Scratch is the caller's: d_work, 8-byte aligned, work_bytes >=
+ * pgd_return_norm_work_bytes(rows) (three doubles per 64 rows; 0 for rows < 1).  Nothing is allocated inside the call: three launches (a
+ * row scan, one workgroup that merges the partials and writes the record, an elementwise scaling; PGD_RN_FREEZE: the last alone),
+ * asynchronous on the engine's stream, capturable in a HIP graph from the first call; a replay continues from the carry and the record
+ * it finds.  T >= 1, rows >= 1, 0 <= gamma <= 1, eps >= 0, no other mode bit, every pointer but d_flags set, d_record and d_work 8-byte
+ * aligned, work_bytes as above (PGD_ERR_ARG otherwise, before anything is launched). */
+#define PGD_RN_FREEZE 1u
+size_t pgd_return_norm_work_bytes(int rows);
+int pgd_return_norm(pgd_handle h, const float* d_reward /*[T][rows]*/, const uint8_t* d_done, const uint32_t* d_flags /* or null */, int T,
+                    int rows, float gamma, double eps, float clip, uint32_t mode, float* d_carry /*[rows], in/out*/,
+                    double* d_record /*[4], in/out*/, float* d_scaled /*[T][rows]*/, void* d_work, size_t work_bytes);
 /* Multi-agent engines remember, per env, which rows of the LAST observation buffer they were given already hold the zeros of a seat
  * that is not due (identified by the buffer's address and row stride), and do not write them again.  A caller that hands pgd_step
  * a buffer whose address a FORMER buffer had (a caching allocator re-using a freed block: torch.empty per step) calls this first:

@@ -87,6 +87,9 @@ PPO_ROWS_MAX = 16777216
 PPO_STATS = ("n", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "ratio", "reserved")  # d_stats of pgd_ppo_grad
 PPO_COST_STATS = PPO_STATS[:7] + ("cost_value_loss", )  # d_stats of pgd_ppo_grad_cost
 LAGRANGE_STATE = ("lambda", "episode_cost", "episodes", "reserved")  # d_state of pgd_lagrange
+RN_FREEZE = 1  # PGD_RN_FREEZE, a mode bit of pgd_return_norm
+RETURN_NORM_RECORD = ("count", "mean", "m2", "scale")  # d_record of pgd_return_norm, four doubles
+RETURN_NORM_INIT = (1e-4, 0.0, 1e-4, 1.0)  # the record before the first call: VecNormalize's RunningMeanStd (mean 0, variance 1, count 1e-4)
 
 # the tensors of Engine.enable_step_info by pgd_step_info field: (dtype name, key in Engine.step_info)
 STEP_INFO_FIELDS = dict(

@@ -1408,4 +1408,5 @@ int pgd_destroy(pgd_handle h) {
 #include "pgd_ppo.h"
 #include "pgd_safe.h"
 #include "pgd_timelimit.h"
+#include "pgd_return_norm.h"
 #endif  // !PGD_JIT

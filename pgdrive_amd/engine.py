@@ -66,6 +66,9 @@ _SIGS = {
                                     C.c_void_p]),
     "pgd_cost_gae_bootstrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float,
                                          C.c_float] + [C.c_void_p] * 6),
+    "pgd_return_norm_work_bytes": (C.c_size_t, [C.c_int]),
+    "pgd_return_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_double, C.c_float, C.c_uint32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "pgd_step_lane_keep": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 4),
     "pgd_lane_keep_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32]),
     "pgd_topdown_channels": (C.c_int, [C.POINTER(_abi.TopDownConfig)]),
@@ -770,6 +773,42 @@ class Engine:
         _chk(self.L.pgd_cost_gae_bootstrap(self.h, _p(flags), _p(done), _p(cost_value), _p(term_cost_value), T, rows, c3, float(gamma), float(lam),
                                            _p(cost), _p(adv), _p(ret), _p(run), _p(ep_sum), _p(ep_count)), "pgd_cost_gae_bootstrap")
         return cost, adv, ret, ep_sum, ep_count
+
+    # -- reward scaling by the running return, in front of GAE (include/pgdrive_hip.h states the rule) -------------------------------------
+    def return_norm_work_bytes(self, rows):
+        """The scratch pgd_return_norm needs for `rows` rows (pgd_return_norm_work_bytes)."""
+        return int(self.L.pgd_return_norm_work_bytes(int(rows)))
+
+    def return_norm_state(self, rows):
+        """(carry, record) as pgd_return_norm wants them before its first call: float32 zeros [rows] and the float64 record
+        _abi.RETURN_NORM_INIT (count, mean, m2, scale), on the engine's device."""
+        t = self.torch
+        return (t.zeros((int(rows), ), dtype=t.float32, device=self.device),
+                t.tensor(_abi.RETURN_NORM_INIT, dtype=t.float64, device=self.device))
+
+    def return_norm(self, reward, done, gamma, carry, record, flags=None, eps=1e-8, clip=10.0, freeze=False, out=None, work=None):
+        """The rewards of a rollout divided by the standard deviation of the running discounted return (pgd_return_norm; the norm_reward
+        half of VecNormalize): reward, done (uint8) [T, rows...], time-major contiguous cuda tensors; `flags` (int32, of reward's shape):
+        the step flags of a multi-agent rollout -- only rows at which an agent acted are samples, and they alone are scaled (every other
+        entry of the result is 0).  `carry` float32 [rows] and `record` float64 [4] (_abi.RETURN_NORM_RECORD) are read and written: the
+        discounted return of every row's running episode and the running count, mean, sum of squared deviations and scale; they start as
+        return_norm_state() gives them.  The rollout is scaled by the scale that already includes its own samples, then clamped to
+        [-clip, clip] (clip <= 0: no clamp).  freeze: carry and record are read, not written.  Returns the scaled rewards, float32 of
+        reward's shape (`out`: the buffer to write).  `work`: a cuda tensor of at least return_norm_work_bytes(rows) bytes, allocated when
+        None.  Three launches (freeze: one), asynchronous on the caller's current stream."""
+        t = self.torch
+        T, rows, (reward, done, out, carry) = self._rollout_buffers(
+            reward, ((reward, t.float32, 0), (done, t.uint8, 0), (out, t.float32, 0), (carry, t.float32, None)))
+        assert flags is None or (flags.is_cuda and flags.dtype == t.int32 and flags.is_contiguous() and flags.numel() == T * rows)
+        assert record.is_cuda and record.dtype == t.float64 and record.is_contiguous() and record.numel() == 4
+        need = self.return_norm_work_bytes(rows)
+        if work is None:
+            work = t.empty(((need + 7) // 8, ), dtype=t.float64, device=reward.device)
+        assert work.is_cuda and work.is_contiguous()
+        _chk(self.L.pgd_return_norm(self.h, _p(reward), _p(done), _p(flags) if flags is not None else None, T, rows, float(gamma), float(eps),
+                                    float(clip), _abi.RN_FREEZE if freeze else 0, _p(carry), _p(record), _p(out), _p(work),
+                                    work.numel() * work.element_size()), "pgd_return_norm")
+        return out
 
     def step_lane_keep(self, tick, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):
         """One closed-loop step under the scripted lane-keeping policy (pgd_step_lane_keep): the policy reads the engine's own

@@ -31,6 +31,15 @@ from the flags, their GAE and the books of episode costs.
 
 Multi-agent engines: MultiAgentRolloutCollector, below -- the same layout and carry with a seat axis, the networks over the rows of live
 seats only, GAE per agent and not per seat, and the index of the transitions a trainer may use.
+
+normalise_rewards=True (every collector): GAE reads the rewards divided by the standard deviation of the running discounted return -- the
+norm_reward half of Stable-Baselines3's VecNormalize, one call behind the T steps (Engine.return_norm).  The collector
+owns the running return of every row and the record (count, mean, m2, scale) on the device; a rollout is divided by the scale that
+already includes its own samples, then clamped to [-clip_reward, clip_reward].  The batch gains scaled_rewards [T, ...] and return_norm
+(the record, float64 [4]); `rewards` stays raw.  The critic then learns in scaled units (with bootstrap_truncations its terminal values
+are in those units already: they are its own outputs).  The safe collector's costs are not scaled: the cost limit is in raw cost units.
+state_dict() / load_state_dict() hold the running returns and the record for a checkpoint; freeze_return_norm(True) stops both from
+moving, for evaluation rollouts.  False (the default): the calls and the batch of before.
 """
 import numpy as np
 
@@ -79,6 +88,57 @@ class _Collector:
         """The networks of the rollouts from now on (between two collect() calls): tuples as for Engine.mlp_actor_critic."""
         self.policy_weights, self.value_weights = tuple(policy_weights), tuple(value_weights)
 
+    def _normalise(self, normalise_rewards, clip_reward, reward_eps):
+        """The reward side of VecNormalize (behind _allocate): switched on, the collector owns the running returns, the record, the
+        scratch and scaled_rewards, and the batch gains scaled_rewards and return_norm."""
+        self.normalise_rewards, self.clip_reward, self.reward_eps = bool(normalise_rewards), float(clip_reward), float(reward_eps)
+        self._rn_frozen = False
+        if not self.normalise_rewards:
+            return
+        if not self.reward_eps >= 0.0:
+            raise ValueError("%s: reward_eps = %r" % (type(self).__name__, reward_eps))
+        eng, t = self.engine, self.engine.torch
+        rows = self.rewards[0].numel()
+        self.scaled_rewards = t.zeros_like(self.rewards)
+        self._rn_carry, self.return_norm = eng.return_norm_state(rows)
+        self._rn_work = t.empty(((eng.return_norm_work_bytes(rows) + 7) // 8, ), dtype=t.float64, device=eng.device)
+        self.batch.update(scaled_rewards=self.scaled_rewards, return_norm=self.return_norm)
+
+    def _gae_rewards(self, flags=None):
+        """The rewards GAE reads: the rollout's own, or (normalise_rewards) scaled by the running return -- one Engine.return_norm call."""
+        if not self.normalise_rewards:
+            return self.rewards
+        return self.engine.return_norm(self.rewards, self.dones, self.gamma, self._rn_carry, self.return_norm, flags=flags, eps=self.reward_eps,
+                                       clip=self.clip_reward, freeze=self._rn_frozen, out=self.scaled_rewards, work=self._rn_work)
+
+    def freeze_return_norm(self, frozen=True):
+        """Evaluation rollouts: from the next collect() on the running returns and the record are read and not written (True), or move
+        again (False).  Call it between two collect() calls; a captured collect() keeps the mode it was captured with."""
+        self._rn_frozen = bool(frozen)
+
+    def state_dict(self):
+        """Host copies of what reward normalisation carries from rollout to rollout, for a checkpoint: return_norm_carry (float32, one
+        entry per row) and return_norm (float64 [4]: count, mean, m2, scale).  Empty with the switch off.  Waits for the device: call it
+        outside collect() and outside a graph capture."""
+        if not self.normalise_rewards:
+            return {}
+        self.engine.sync()
+        return dict(return_norm_carry=self._rn_carry.cpu().numpy().copy(), return_norm=self.return_norm.cpu().numpy().copy())
+
+    def load_state_dict(self, state):
+        """Put back what state_dict() returned (into the collector's own tensors: a captured collect() continues from them)."""
+        if not self.normalise_rewards:
+            if state:
+                raise ValueError("%s: a reward normalisation state for a collector built with normalise_rewards=False" % type(self).__name__)
+            return
+        t = self.engine.torch
+        carry = np.ascontiguousarray(state["return_norm_carry"], dtype=np.float32).reshape(-1)
+        record = np.ascontiguousarray(state["return_norm"], dtype=np.float64).reshape(-1)
+        if carry.size != self._rn_carry.numel() or record.size != 4:
+            raise ValueError("%s: a state of %d rows for a collector of %d" % (type(self).__name__, carry.size, self._rn_carry.numel()))
+        self._rn_carry.copy_(t.from_numpy(carry))
+        self.return_norm.copy_(t.from_numpy(record))
+
     def _stepped(self, t):
         pass
 
@@ -119,8 +179,11 @@ class RolloutCollector(_Collector):
     final_obs=True when it is off; an engine whose step info has no final_observation -- image observations -- is refused).  After every
     step one more launch (Engine.mlp_terminal_value) writes `term_values[t]`: the critic's value, with the weights of this rollout, of
     step_info["final_observation"] where the step truncated the env, 0 elsewhere; Engine.gae_bootstrap takes it as the one-step target
-    of the done rows.  The batch gains term_values [T, N].  False (the default): the calls and the batch of before."""
-    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, bootstrap_truncations=False):
+    of the done rows.  The batch gains term_values [T, N].  False (the default): the calls and the batch of before.
+    normalise_rewards=True, clip_reward, reward_eps: GAE reads the rewards scaled by the running return (the module's docstring); the
+    batch gains scaled_rewards [T, N] and return_norm (float64 [4])."""
+    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, bootstrap_truncations=False,
+                 normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8):
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A != 1:
             raise NotImplementedError(
@@ -136,6 +199,7 @@ class RolloutCollector(_Collector):
                 raise ValueError("bootstrap_truncations needs the terminal observation of the step info, and this engine's step info has no "
                                  "final_observation (image observations: enable_step_info(final_obs=False))")
         self._allocate(eng, (eng.N, ), policy_weights, value_weights, T, gamma, lam, seed)
+        self._normalise(normalise_rewards, clip_reward, reward_eps)
         if self.bootstrap_truncations:
             self.term_values = eng.torch.zeros((self.T, eng.N), dtype=eng.torch.float32, device=eng.device)
             self.batch.update(term_values=self.term_values)
@@ -155,11 +219,12 @@ class RolloutCollector(_Collector):
                                            self.term_values[t], tcv)
 
     def _finish(self):
+        rewards = self._gae_rewards()
         if self.bootstrap_truncations:
-            self.engine.gae_bootstrap(self.rewards, self.values, self.dones, self.term_values, self.gamma, self.lam, adv=self.advantages,
+            self.engine.gae_bootstrap(rewards, self.values, self.dones, self.term_values, self.gamma, self.lam, adv=self.advantages,
                                       ret=self.returns)
         else:
-            self.engine.gae(self.rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
+            self.engine.gae(rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
 
 
 class SafeRolloutCollector(RolloutCollector):
@@ -185,10 +250,11 @@ class SafeRolloutCollector(RolloutCollector):
     term_values and term_cost_values [T, N], and Engine.cost_gae_bootstrap takes the latter as the cost side's one-step target.  The
     books of episode costs are unchanged: a truncated episode still finishes for them."""
     def __init__(self, env_or_engine, policy_weights, value_weights, cost_weights, T, costs=None, gamma=0.99, lam=0.95, cost_gamma=0.99,
-                 cost_lam=0.95, seed=0, bootstrap_truncations=False):
+                 cost_lam=0.95, seed=0, bootstrap_truncations=False, normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8):
         self.cost_weights = tuple(cost_weights)
         super().__init__(env_or_engine, policy_weights, value_weights, T, gamma=gamma, lam=lam, seed=seed,
-                         bootstrap_truncations=bootstrap_truncations)
+                         bootstrap_truncations=bootstrap_truncations, normalise_rewards=normalise_rewards, clip_reward=clip_reward,
+                         reward_eps=reward_eps)
         eng = self.engine
         t = eng.torch
         if costs is None:
@@ -263,7 +329,8 @@ class MultiAgentRolloutCollector(_Collector):
 
     The step is handed another observation row at every step, so the engine's marks of seats whose zero row is already in place
     (pgd_forget_rows) never carry over: every step of a rollout writes the zero row of every seat that is not due."""
-    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0):
+    def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, normalise_rewards=False, clip_reward=10.0,
+                 reward_eps=1e-8):
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A == 1:
             raise NotImplementedError("MultiAgentRolloutCollector serves multi-agent engines: this one has a single agent seat per env and "
@@ -271,6 +338,7 @@ class MultiAgentRolloutCollector(_Collector):
         if int(T) < 1:
             raise ValueError("MultiAgentRolloutCollector: T = %r" % (T, ))
         self._allocate(eng, (eng.N, eng.A), policy_weights, value_weights, T, gamma, lam, seed)
+        self._normalise(normalise_rewards, clip_reward, reward_eps)
         t = eng.torch
         i32 = dict(dtype=t.int32, device=eng.device)
         self.mask = t.zeros(self.flags.shape, dtype=t.uint8, device=eng.device)
@@ -288,8 +356,8 @@ class MultiAgentRolloutCollector(_Collector):
         self.engine.live_rows(self.flags[t], self.dones[t], rows=self._rows, count=self._n_rows)
 
     def _finish(self):
-        self.engine.gae_masked(self.rewards, self.values, self.dones, self.flags, self.gamma, self.lam, adv=self.advantages, ret=self.returns,
-                               mask=self.mask)
+        self.engine.gae_masked(self._gae_rewards(flags=self.flags), self.values, self.dones, self.flags, self.gamma, self.lam, adv=self.advantages,
+                               ret=self.returns, mask=self.mask)
         self.engine.rollout_index(self.flags, index=self.index, count=self.count)
 
     def prime(self):
