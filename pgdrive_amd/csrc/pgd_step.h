@@ -366,7 +366,16 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
   constexpr bool LATE_WORDS = MARL && FIX != 0;
   int hint_early = 0;
   if (LATE_WORDS && (one_env || valid)) hint_early = d.ei[(size_t)e * PGD_NEI + EI_NEAR];
-  if (valid && !own_first) load_rec(((ONE_ENV || packed) && ((im >> s) & 1ull)) ? rec_block(d.reset_img, (size_t)scen, V) : rec_block(d.rec, (size_t)e, V), V, s, r);
+  // the single-agent kernels of the default geometry (17 slots, image off: the block's address follows from the block index alone):
+  // the whole block in three full-width reads, through LDS (rec_stage_issue).  The image lies in the sub-step poses, which nothing
+  // touches before the physics.
+  constexpr bool STAGED = ONE_ENV && !MARL && !OBJ && STD && FIX >= 1 && FIX <= 3 && fix_spec(FIX).V == PGD_FIX_V;
+  uint4 stg[REC_STAGE_ROUNDS(PGD_FIX_V)];
+  static_assert(sizeof(SUBP.p) >= sizeof(uint4) * WAVE * REC_STAGE_ROUNDS(PGD_FIX_V), "the block's image fits the sub-step poses, short of beta / trav");
+  if constexpr (STAGED) {
+    rec_stage_issue<PGD_FIX_V>(rec_block(d.rec, (size_t)e, PGD_FIX_V), lane, stg);
+    __builtin_amdgcn_sched_barrier(0);  // the records' reads stay the wave's first: left to itself the scheduler put the action and the spawn heads in front
+  } else if (valid && !own_first) load_rec(((ONE_ENV || packed) && ((im >> s) & 1ull)) ? rec_block(d.reset_img, (size_t)scen, V) : rec_block(d.rec, (size_t)e, V), V, s, r);
   // the agent's action: its address follows from the block index as well -- read here, used by the policy phase (read there it cost
   // every wave a memory latency of its own right after the snapshot: 1.5 k cycles of the metric's row).  BEHIND the record's reads:
   // issued ahead of the mask / scenario / record chain it delays that chain (17.76 -> 17.99 us), and so does a speculative read
@@ -385,6 +394,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
   // with the record's instead of waiting for them (17.48 -> 17.40 us on the metric's row, now that the records' reads are short)
   constexpr bool EARLY_HEAD = !MARL && REGSP && FIX != 0 && !OBJ;  // (the general kernels have no registers for it: 19.5 -> 19.9 us there; nor has the object kernel)
   if (EARLY_HEAD && valid) { sp = d.spawns + (size_t)scen * d.sstride + s; spawn_head_load<false>(sp, sl); }
+  if constexpr (STAGED) rec_stage_take<PGD_FIX_V>(reinterpret_cast<uint4*>(&SUBP.p[0][0]), lane, stg, valid, s, r);
   const int key0 = valid ? (r.status ^ (r.vflags << 3)) : 0;  // what a vehicle that does not drive can change: status, flags
   // the env's counters.  The multi-agent kernels are out of scalar registers: read here, the compiler fetched the words one after the
   // other through the same register -- three scalar-memory round trips in a row between the records and the spawn heads (a word that

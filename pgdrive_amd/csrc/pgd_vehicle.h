@@ -14,6 +14,41 @@ DEV void load_rec(const RecPiece* blk, int n, int s, Veh& r) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) dst[k] = blk[k * n + s].q;
 }
+// Block-wise, for a wave that owns the whole block of N records (N a literal): the block is contiguous, so ceil(8 N / 64) reads with all
+// 64 lanes on consecutive pieces fetch it -- 3 vector-memory instructions instead of load_rec's 8 for N = 17 -- into an LDS image of
+// the block, from which every lane then takes the eight pieces of its slot (profiles/burst_notes.md).  Two halves, so that the caller
+// can issue its other first reads between them: rec_stage_issue puts the reads in flight, rec_stage_take writes the image and fills r.
+// Lanes past the block's end read its last piece again: no lane reads outside the block, and no read is masked (a masked last read
+// made the compiler split the wave into two paths, two flights of reads).  `img` holds REC_STAGE_ROUNDS(N) * 64 pieces.
+#define REC_STAGE_ROUNDS(N) ((8 * (N) + WAVE - 1) / WAVE)
+// (rounds by recursion and through a local value: copied piece by piece from memory in an unrolled loop, `t` stayed an array in
+// scratch memory once the caller put a scheduling barrier behind the reads)
+template <int N, int J = 0> DEV void rec_stage_issue(const RecPiece* blk, int lane, uint4 (&t)[REC_STAGE_ROUNDS(N)]) {
+  static_assert(WAVE == 64, "one piece per lane and round");
+  if constexpr (J < REC_STAGE_ROUNDS(N)) {
+    const uint4 v = blk[(J + 1) * WAVE <= 8 * N ? J * WAVE + lane : min(J * WAVE + lane, 8 * N - 1)].q;
+    t[J] = v;
+    rec_stage_issue<N, J + 1>(blk, lane, t);
+  }
+}
+template <int N, int J = 0> DEV void rec_stage_write(uint4* img, int lane, const uint4 (&t)[REC_STAGE_ROUNDS(N)]) {
+  if constexpr (J < REC_STAGE_ROUNDS(N)) {
+    const uint4 v = t[J];
+    img[J * WAVE + lane] = v;
+    rec_stage_write<N, J + 1>(img, lane, t);
+  }
+}
+template <int N> DEV void rec_stage_take(uint4* img, int lane, const uint4 (&t)[REC_STAGE_ROUNDS(N)], bool valid, int s, Veh& r) {
+  rec_stage_write<N>(img, lane, t);
+  // one wave: its LDS accesses execute in order, only the compiler has to keep the order
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  if (valid) {
+    uint4* dst = reinterpret_cast<uint4*>(&r);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dst[k] = img[k * N + s];
+  }
+}
 // the first 64 bytes: pose, speed, heading vector, lane | spawn, status / flags, route words (what an observer needs of a body)
 DEV void load_rec_head(const RecPiece* blk, int n, int s, Veh& r) {
   uint4* dst = reinterpret_cast<uint4*>(&r);
