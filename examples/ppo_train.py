@@ -2,12 +2,14 @@
 (pgdrive_amd.RolloutCollector / MultiAgentRolloutCollector and pgdrive_amd.PPOLearner: pgd_adv_stats, then pgd_ppo_grad + pgd_adam per
 epoch and minibatch).
 
-    python examples/ppo_train.py --envs 256 --T 32 --iters 20 [--graph] [--marl [--agents 40]] [--every 5]
+    python examples/ppo_train.py --envs 256 --T 32 --iters 20 [--graph] [--marl [--agents 40]] [--every 5] [--episode-stats]
     python examples/ppo_train.py --time --envs 4096 --T 64 [--windows 7] [--updates 3]
 
 Random initial weights of the shape of the reference's shipped PPO expert (pgdrive/examples/ppo_expert/numpy_expert.py).  Printed every
 `--every` iterations: the mean reward of the rollout and the statistics of the update's last minibatch (pgdrive_amd._abi.PPO_STATS); these
-prints read the device, the iteration itself does not.
+prints read the device, the iteration itself does not.  --episode-stats: a second line per print with the episodes that finished since
+the last print -- their number, the success rate (arrive_dest at the episode's end), mean and standard deviation of the return and the
+mean length (the collector's episode_stats switch) -- and the number of episodes so far.
 
 --time: update() alone on one fixed batch in three forms on the same build -- the engine's kernels, the same update composed from torch
 ops with autograd and torch.optim.Adam eagerly, and that composition captured in a HIP graph --, each warmed up, then `--windows` windows
@@ -155,6 +157,8 @@ def main():
                     help="GAE bootstraps through the horizon from the critic's value of the terminal observation (DESIGN.md section 24)")
     ap.add_argument("--normalise-rewards", action="store_true",
                     help="GAE reads the rewards divided by the standard deviation of the running discounted return (DESIGN.md section 25)")
+    ap.add_argument("--episode-stats", action="store_true",
+                    help="print the statistics of the episodes that finished since the last print (DESIGN.md section 26)")
     args = ap.parse_args()
     if args.time:
         return time_update(args)
@@ -169,10 +173,11 @@ def main():
     env.reset()
     if args.marl:   # (no such switch: the cause of a done cannot be read from a multi-agent step's flags)
         assert not args.bootstrap_truncations, "--bootstrap-truncations serves single-agent engines"
-        col = MultiAgentRolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, normalise_rewards=args.normalise_rewards)
+        col = MultiAgentRolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, normalise_rewards=args.normalise_rewards,
+                                         episode_stats=args.episode_stats)
     else:
         col = RolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, bootstrap_truncations=args.bootstrap_truncations,
-                               normalise_rewards=args.normalise_rewards)
+                               normalise_rewards=args.normalise_rewards, episode_stats=args.episode_stats)
     learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, ent_coef=0.0)
 
     def iteration():
@@ -191,6 +196,9 @@ def main():
         call = g.replay
     else:
         call = iteration
+    episodes = 0
+    if args.episode_stats:
+        col.clear_episode_stats()  # (the statistics start behind the warm-up iterations; the unfinished episodes stay)
     t0 = time.perf_counter()
     with torch.cuda.stream(s), torch.no_grad():
         for it in range(1, args.iters + 1):
@@ -207,6 +215,13 @@ def main():
                 scale = "  reward scale %.4g" % float(b["return_norm"][3]) if args.normalise_rewards else ""
                 print("iteration %4d  Adam step %5d  mean reward %8.4f  " % (it, int(learner.step[0]), reward) +
                       "  ".join("%s %.4g" % (k, x) for k, x in zip(_abi.PPO_STATS[:7], st)) + scale)
+                if args.episode_stats:
+                    e = col.episode_summary()
+                    col.clear_episode_stats()
+                    episodes += e["episodes"]
+                    print("                episodes %6d (so far %7d)  " % (e["episodes"], episodes) + ("none ended" if not e["episodes"] else
+                          "success rate %.3f  out of road %.3f  return %.3f +- %.3f  mean length %.1f" % (
+                              e["arrive_rate"], e["out_of_road_rate"], e["mean_return"], e["std_return"], e["mean_length"])))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print("%d iterations in %.2f s: %.1f k env-steps/s including the prints" % (args.iters, dt, args.iters * args.envs * args.T / dt / 1e3))

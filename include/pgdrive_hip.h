@@ -724,6 +724,47 @@ size_t pgd_return_norm_work_bytes(int rows);
 int pgd_return_norm(pgd_handle h, const float* d_reward /*[T][rows]*/, const uint8_t* d_done, const uint32_t* d_flags /* or null */, int T,
                     int rows, float gamma, double eps, float clip, uint32_t mode, float* d_carry /*[rows], in/out*/,
                     double* d_record /*[4], in/out*/, float* d_scaled /*[T][rows]*/, void* d_work, size_t work_bytes);
+/* ---- Episode statistics of a rollout (every engine) ------------------------------------------------------------------------------------
+ * (No reference counterpart: the reference reports an episode in the info dict of the step that ends it; this is gym's
+ * RecordEpisodeStatistics -- return, length and the causes of the end of every episode that finished -- as one call over a rollout.)
+ * Time-major device arrays, as pgd_step wrote them: reward (float), done (uint8), flags (uint32) [T][rows]; flags is REQUIRED in both
+ * modes: the causes are read from it.  Two caller-owned carries per row live across calls and hold a row's unfinished episode:
+ *   ret_carry [rows] float, len_carry [rows] int32; zero before the first call
+ * Per row r, with R = ret_carry[r], L = len_carry[r], for t = 0 .. T - 1 in order, f = flags[t][r], d = done[t][r]:
+ *   mode 0 (single-agent rows):  acted = true;  ends = d != 0
+ *   mode PGD_EP_SEATS:           acted = f & PGD_F_REPORT;  cont = acted && !d && !(f & PGD_F_RESET);  ends = acted && !cont
+ *                                (the predicates of pgd_gae_masked, above)
+ *   acted:  R = R + reward[t][r] (ONE plain fp32 add, in the order of t, contracted with nothing);  L = L + 1
+ *   ends:   the episode (R, L, f, d) is a SAMPLE (below);  then R = 0, L = 0
+ * and ret_carry[r] = R, len_carry[r] = L behind the loop.  acted and ends SELECT: the reward of a row that did not act may be NaN and
+ * reaches nothing.  A sample feeds
+ *   count, mean and m2 (the sum of squared deviations) of the returns, in double;  the least and the greatest return;
+ *   the sum and the maximum of the lengths;
+ *   one count per bit of PGD_F_ARRIVE, OUT_OF_ROAD, CRASH_VEHICLE, CRASH_OBJECT, CRASH_BUILDING, MAX_STEP set in f -- bit counts, not
+ *   exclusive classes: they report what the step reported, no more;
+ *   `cut`: the ends with d == 0 (an env-wide restart took the agent out: PGD_EP_SEATS only).
+ * `steps` counts the entries with acted.  A record is 16 doubles (the counts are integers held in doubles: exact), 8-byte aligned:
+ *   0 episodes  1 return_mean  2 return_m2  3 return_min  4 return_max  5 length_sum  6 length_max  7 arrive  8 out_of_road
+ *   9 crash_vehicle  10 crash_object  11 crash_building  12 max_step  13 cut  14 steps  15 calls
+ * and starts as all zero but return_min = +inf, return_max = -inf.  Two record outputs, either may be null:
+ *   d_call    WRITTEN: this call's own statistics, calls = 1
+ *   d_record  read and written: the call merged into what the record held (Chan's update of mean and m2 as for pgd_return_norm, min,
+ *             max, sums).  A call in which no episode ended adds to steps and calls and leaves slots 0 .. 13 their bytes.
+ * Dense outputs, either may be null: ep_return (float) and ep_length (int32) [T][rows] hold (R, L) of the finished episode at the entry
+ * where it ended and 0 at EVERY other entry (every entry is written: SB3's info["episode"] as arrays).
+ * Deterministic: no atomics; a row's samples are summed in the order of t, the rows of a wave, the waves' partials and the record in a
+ * fixed order: the same inputs give the same bytes.  Scratch is the caller's: d_work, 8-byte aligned, work_bytes >=
+ * pgd_rollout_episodes_work_bytes(rows) (16 doubles per 64 rows; 0 for rows < 1).  Nothing is allocated inside the call: two launches (a
+ * row scan; one workgroup that merges the partials and writes the records -- left out when d_record and d_call are both null),
+ * asynchronous on the engine's stream, capturable in a HIP graph from the first call; a replay continues from the carries and the record
+ * it finds.  T >= 1, rows >= 1, no other mode bit, every pointer but d_record, d_call, d_ep_return, d_ep_length set, records and d_work
+ * 8-byte aligned, work_bytes as above (PGD_ERR_ARG otherwise, before anything is launched). */
+#define PGD_EP_SEATS 1u
+size_t pgd_rollout_episodes_work_bytes(int rows);
+int pgd_rollout_episodes(pgd_handle h, const float* d_reward /*[T][rows]*/, const uint8_t* d_done, const uint32_t* d_flags, int T, int rows,
+                         uint32_t mode, float* d_ret_carry /*[rows], in/out*/, int32_t* d_len_carry /*[rows], in/out*/,
+                         double* d_record /*[16] in/out, or null*/, double* d_call /*[16] or null*/, float* d_ep_return /*[T][rows] or null*/,
+                         int32_t* d_ep_length /*[T][rows] or null*/, void* d_work, size_t work_bytes);
 /* Multi-agent engines remember, per env, which rows of the LAST observation buffer they were given already hold the zeros of a seat
  * that is not due (identified by the buffer's address and row stride), and do not write them again.  A caller that hands pgd_step
  * a buffer whose address a FORMER buffer had (a caching allocator re-using a freed block: torch.empty per step) calls this first:

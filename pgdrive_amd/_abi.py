@@ -90,6 +90,10 @@ LAGRANGE_STATE = ("lambda", "episode_cost", "episodes", "reserved")  # d_state o
 RN_FREEZE = 1  # PGD_RN_FREEZE, a mode bit of pgd_return_norm
 RETURN_NORM_RECORD = ("count", "mean", "m2", "scale")  # d_record of pgd_return_norm, four doubles
 RETURN_NORM_INIT = (1e-4, 0.0, 1e-4, 1.0)  # the record before the first call: VecNormalize's RunningMeanStd (mean 0, variance 1, count 1e-4)
+EP_SEATS = 1  # PGD_EP_SEATS, a mode bit of pgd_rollout_episodes
+ROLLOUT_EPISODES = ("episodes", "return_mean", "return_m2", "return_min", "return_max", "length_sum", "length_max", "arrive", "out_of_road",
+                    "crash_vehicle", "crash_object", "crash_building", "max_step", "cut", "steps", "calls")  # a record of pgd_rollout_episodes, 16 doubles
+ROLLOUT_EPISODES_INIT = (0.0, 0.0, 0.0, float("inf"), float("-inf")) + (0.0, ) * 11  # the record before the first call
 
 # the tensors of Engine.enable_step_info by pgd_step_info field: (dtype name, key in Engine.step_info)
 STEP_INFO_FIELDS = dict(

@@ -1409,4 +1409,5 @@ int pgd_destroy(pgd_handle h) {
 #include "pgd_safe.h"
 #include "pgd_timelimit.h"
 #include "pgd_return_norm.h"
+#include "pgd_rollout_episodes.h"
 #endif  // !PGD_JIT

@@ -69,6 +69,8 @@ _SIGS = {
     "pgd_return_norm_work_bytes": (C.c_size_t, [C.c_int]),
     "pgd_return_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_double, C.c_float, C.c_uint32,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "pgd_rollout_episodes_work_bytes": (C.c_size_t, [C.c_int]),
+    "pgd_rollout_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32] + [C.c_void_p] * 7 + [C.c_size_t]),
     "pgd_step_lane_keep": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 4),
     "pgd_lane_keep_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32]),
     "pgd_topdown_channels": (C.c_int, [C.POINTER(_abi.TopDownConfig)]),
@@ -809,6 +811,46 @@ class Engine:
                                     float(clip), _abi.RN_FREEZE if freeze else 0, _p(carry), _p(record), _p(out), _p(work),
                                     work.numel() * work.element_size()), "pgd_return_norm")
         return out
+
+    # -- episode statistics of a rollout (include/pgdrive_hip.h states the rule) ---------------------------------------------------------
+    def rollout_episodes_work_bytes(self, rows):
+        """The scratch pgd_rollout_episodes needs for `rows` rows (pgd_rollout_episodes_work_bytes)."""
+        return int(self.L.pgd_rollout_episodes_work_bytes(int(rows)))
+
+    def rollout_episodes_state(self, rows):
+        """(ret_carry, len_carry, record) as pgd_rollout_episodes wants them before its first call: float32 and int32 zeros [rows] and the
+        float64 record _abi.ROLLOUT_EPISODES_INIT, on the engine's device."""
+        t = self.torch
+        return (t.zeros((int(rows), ), dtype=t.float32, device=self.device), t.zeros((int(rows), ), dtype=t.int32, device=self.device),
+                t.tensor(_abi.ROLLOUT_EPISODES_INIT, dtype=t.float64, device=self.device))
+
+    def rollout_episodes(self, reward, done, flags, ret_carry, len_carry, record=None, call=None, seats=False, ep_return=None, ep_length=None,
+                         work=None):
+        """The statistics of the episodes that ended in a rollout (pgd_rollout_episodes; gym's RecordEpisodeStatistics): reward, done
+        (uint8) and flags (int32) [T, rows...], time-major contiguous cuda tensors as the step wrote them.  seats: the rows are the seats of
+        a multi-agent engine -- only entries at which an agent acted count, and an agent's episode ends at its done or at an env-wide
+        restart.  `ret_carry` float32 and `len_carry` int32 [rows] are read and written: the return and the length of every row's
+        unfinished episode; they and `record` start as rollout_episodes_state() gives them.  `record` (float64 [16],
+        _abi.ROLLOUT_EPISODES) is read and written: the call merged into the running statistics; `call` (float64 [16]) is written: this
+        call's own.  `ep_return` float32 / `ep_length` int32 of reward's shape are written when given: the finished episode's return and
+        length at the entry where it ended, 0 everywhere else.  `work`: a cuda tensor of at least rollout_episodes_work_bytes(rows) bytes,
+        allocated when None.  Two launches, asynchronous on the caller's current stream.  Returns (record, call)."""
+        t = self.torch
+        assert not any(x is None for x in (reward, done, flags, ret_carry, len_carry))
+        T, rows, (reward, done, flags, ret_carry, len_carry) = self._rollout_buffers(
+            reward, ((reward, t.float32, 0), (done, t.uint8, 0), (flags, t.int32, 0), (ret_carry, t.float32, None), (len_carry, t.int32, None)))
+        for rec in (record, call):
+            assert rec is None or (rec.is_cuda and rec.dtype == t.float64 and rec.is_contiguous() and rec.numel() == len(_abi.ROLLOUT_EPISODES))
+        for dense, dt in ((ep_return, t.float32), (ep_length, t.int32)):
+            assert dense is None or (dense.is_cuda and dense.dtype == dt and dense.is_contiguous() and dense.numel() == T * rows)
+        if work is None:
+            work = t.empty(((self.rollout_episodes_work_bytes(rows) + 7) // 8, ), dtype=t.float64, device=reward.device)
+        assert work.is_cuda and work.is_contiguous()
+        opt = lambda x: _p(x) if x is not None else None
+        _chk(self.L.pgd_rollout_episodes(self.h, _p(reward), _p(done), _p(flags), T, rows, _abi.EP_SEATS if seats else 0, _p(ret_carry),
+                                         _p(len_carry), opt(record), opt(call), opt(ep_return), opt(ep_length), _p(work),
+                                         work.numel() * work.element_size()), "pgd_rollout_episodes")
+        return record, call
 
     def step_lane_keep(self, tick, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):
         """One closed-loop step under the scripted lane-keeping policy (pgd_step_lane_keep): the policy reads the engine's own

@@ -40,6 +40,16 @@ already includes its own samples, then clamped to [-clip_reward, clip_reward].  
 are in those units already: they are its own outputs).  The safe collector's costs are not scaled: the cost limit is in raw cost units.
 state_dict() / load_state_dict() hold the running returns and the record for a checkpoint; freeze_return_norm(True) stops both from
 moving, for evaluation rollouts.  False (the default): the calls and the batch of before.
+
+episode_stats=True (every collector): how the policy is doing -- return, length and the causes of the end of every episode that finished,
+gym's RecordEpisodeStatistics as one call behind the T steps (Engine.rollout_episodes).  The collector owns the return
+and the length of every row's unfinished episode and two records of 16 doubles (_abi.ROLLOUT_EPISODES) on the device: the running one
+and the last rollout's.  The call reads the RAW rewards, whatever normalise_rewards says; the multi-agent collector makes it per seat
+(an agent's episode ends at its done or at an env-wide restart).  The batch gains episode_stats (the running record, float64 [16]),
+episode_stats_rollout, and ep_returns float32 / ep_lengths int32 [T, ...]: the finished episode's return and length at the entry where it
+ended, 0 everywhere else.  episode_summary() reads a record as a dict (one synchronisation), clear_episode_stats() starts the running
+record afresh and keeps the unfinished episodes; state_dict() holds the carries and the running record.  False (the default): no new
+tensor, batch key or engine call.
 """
 import numpy as np
 
@@ -111,33 +121,102 @@ class _Collector:
         return self.engine.return_norm(self.rewards, self.dones, self.gamma, self._rn_carry, self.return_norm, flags=flags, eps=self.reward_eps,
                                        clip=self.clip_reward, freeze=self._rn_frozen, out=self.scaled_rewards, work=self._rn_work)
 
+    def _episodes(self, episode_stats, seats=False):
+        """The episode statistics (behind _normalise): switched on, the collector owns the carries, the two records, the scratch and
+        ep_returns / ep_lengths, and the batch gains episode_stats, episode_stats_rollout, ep_returns and ep_lengths."""
+        self.episode_stats, self._ep_seats = bool(episode_stats), bool(seats)
+        if not self.episode_stats:
+            return
+        eng, t = self.engine, self.engine.torch
+        rows = self.rewards[0].numel()
+        self._ep_ret_carry, self._ep_len_carry, self.episode_record = eng.rollout_episodes_state(rows)
+        self._ep_init = self.episode_record.clone()
+        self.episode_record_rollout = self.episode_record.clone()
+        self.ep_returns = t.zeros_like(self.rewards)
+        self.ep_lengths = t.zeros_like(self.flags)
+        self._ep_work = t.empty(((eng.rollout_episodes_work_bytes(rows) + 7) // 8, ), dtype=t.float64, device=eng.device)
+        self.batch.update(episode_stats=self.episode_record, episode_stats_rollout=self.episode_record_rollout, ep_returns=self.ep_returns,
+                          ep_lengths=self.ep_lengths)
+
+    def _episode_call(self):
+        """The one call of episode_stats, on the raw rewards (in _finish())."""
+        if self.episode_stats:
+            self.engine.rollout_episodes(self.rewards, self.dones, self.flags, self._ep_ret_carry, self._ep_len_carry, record=self.episode_record,
+                                         call=self.episode_record_rollout, seats=self._ep_seats, ep_return=self.ep_returns,
+                                         ep_length=self.ep_lengths, work=self._ep_work)
+
+    def episode_summary(self, rollout=False):
+        """The running record (rollout: the last rollout's) as a dict, with the key names of Engine.episode_stats(): episodes,
+        mean_return, std_return, min_return, max_return, mean_length, max_length, the rates arrive_rate, out_of_road_rate,
+        crash_vehicle_rate, crash_object_rate, max_step_rate and cut_rate (the share of the episodes that ended with that flag set; cut:
+        ended by an env-wide restart, without a done), and steps.  None where no episode ended.  One synchronisation: call it outside
+        collect() and outside a graph capture."""
+        if not self.episode_stats:
+            raise ValueError("%s: episode_summary needs episode_stats=True" % type(self).__name__)
+        from . import _abi
+        rec = dict(zip(_abi.ROLLOUT_EPISODES, (self.episode_record_rollout if rollout else self.episode_record).cpu().numpy().tolist()))
+        n = int(rec["episodes"])
+        val = (lambda x: float(x)) if n else (lambda x: None)
+        rate = (lambda k: rec[k] / n) if n else (lambda k: None)
+        return dict(episodes=n, mean_return=val(rec["return_mean"]), std_return=val(np.sqrt(rec["return_m2"] / max(n, 1))),
+                    min_return=val(rec["return_min"]), max_return=val(rec["return_max"]), mean_length=rate("length_sum"),
+                    max_length=int(rec["length_max"]) if n else None, arrive_rate=rate("arrive"), out_of_road_rate=rate("out_of_road"),
+                    crash_vehicle_rate=rate("crash_vehicle"), crash_object_rate=rate("crash_object"), max_step_rate=rate("max_step"),
+                    cut_rate=rate("cut"), steps=int(rec["steps"]))
+
+    def clear_episode_stats(self):
+        """The running record starts afresh (a device copy; call it between two collect() calls, a captured collect() continues from
+        it).  The carries stay: an unfinished episode is not lost."""
+        if not self.episode_stats:
+            raise ValueError("%s: clear_episode_stats needs episode_stats=True" % type(self).__name__)
+        self.episode_record.copy_(self._ep_init)
+
     def freeze_return_norm(self, frozen=True):
         """Evaluation rollouts: from the next collect() on the running returns and the record are read and not written (True), or move
         again (False).  Call it between two collect() calls; a captured collect() keeps the mode it was captured with."""
         self._rn_frozen = bool(frozen)
 
     def state_dict(self):
-        """Host copies of what reward normalisation carries from rollout to rollout, for a checkpoint: return_norm_carry (float32, one
-        entry per row) and return_norm (float64 [4]: count, mean, m2, scale).  Empty with the switch off.  Waits for the device: call it
-        outside collect() and outside a graph capture."""
-        if not self.normalise_rewards:
+        """Host copies of what the collector carries from rollout to rollout beside the engine's state, for a checkpoint.
+        normalise_rewards: return_norm_carry (float32, one entry per row) and return_norm (float64 [4]: count, mean, m2, scale).
+        episode_stats: episode_return_carry (float32) and episode_length_carry (int32), one entry per row, and episode_stats (the running
+        record, float64 [16]).  Empty with both switches off.  Waits for the device: call it outside collect() and outside a graph
+        capture."""
+        if not (self.normalise_rewards or self.episode_stats):
             return {}
         self.engine.sync()
-        return dict(return_norm_carry=self._rn_carry.cpu().numpy().copy(), return_norm=self.return_norm.cpu().numpy().copy())
+        host = lambda x: x.cpu().numpy().copy()
+        state = {}
+        if self.normalise_rewards:
+            state.update(return_norm_carry=host(self._rn_carry), return_norm=host(self.return_norm))
+        if self.episode_stats:
+            state.update(episode_return_carry=host(self._ep_ret_carry), episode_length_carry=host(self._ep_len_carry),
+                         episode_stats=host(self.episode_record))
+        return state
 
     def load_state_dict(self, state):
         """Put back what state_dict() returned (into the collector's own tensors: a captured collect() continues from them)."""
-        if not self.normalise_rewards:
-            if state:
-                raise ValueError("%s: a reward normalisation state for a collector built with normalise_rewards=False" % type(self).__name__)
-            return
-        t = self.engine.torch
-        carry = np.ascontiguousarray(state["return_norm_carry"], dtype=np.float32).reshape(-1)
-        record = np.ascontiguousarray(state["return_norm"], dtype=np.float64).reshape(-1)
-        if carry.size != self._rn_carry.numel() or record.size != 4:
-            raise ValueError("%s: a state of %d rows for a collector of %d" % (type(self).__name__, carry.size, self._rn_carry.numel()))
-        self._rn_carry.copy_(t.from_numpy(carry))
-        self.return_norm.copy_(t.from_numpy(record))
+        t, name = self.engine.torch, type(self).__name__
+        if not self.normalise_rewards and any(k in state for k in ("return_norm_carry", "return_norm")):
+            raise ValueError("%s: a reward normalisation state for a collector built with normalise_rewards=False" % name)
+        if not self.episode_stats and any(k in state for k in ("episode_return_carry", "episode_length_carry", "episode_stats")):
+            raise ValueError("%s: an episode statistics state for a collector built with episode_stats=False" % name)
+        if self.normalise_rewards:
+            carry = np.ascontiguousarray(state["return_norm_carry"], dtype=np.float32).reshape(-1)
+            record = np.ascontiguousarray(state["return_norm"], dtype=np.float64).reshape(-1)
+            if carry.size != self._rn_carry.numel() or record.size != 4:
+                raise ValueError("%s: a state of %d rows for a collector of %d" % (name, carry.size, self._rn_carry.numel()))
+            self._rn_carry.copy_(t.from_numpy(carry))
+            self.return_norm.copy_(t.from_numpy(record))
+        if self.episode_stats:
+            ret = np.ascontiguousarray(state["episode_return_carry"], dtype=np.float32).reshape(-1)
+            length = np.ascontiguousarray(state["episode_length_carry"], dtype=np.int32).reshape(-1)
+            record = np.ascontiguousarray(state["episode_stats"], dtype=np.float64).reshape(-1)
+            if ret.size != self._ep_ret_carry.numel() or length.size != ret.size or record.size != self.episode_record.numel():
+                raise ValueError("%s: a state of %d rows for a collector of %d" % (name, ret.size, self._ep_ret_carry.numel()))
+            self._ep_ret_carry.copy_(t.from_numpy(ret))
+            self._ep_len_carry.copy_(t.from_numpy(length))
+            self.episode_record.copy_(t.from_numpy(record))
 
     def _stepped(self, t):
         pass
@@ -181,9 +260,11 @@ class RolloutCollector(_Collector):
     step_info["final_observation"] where the step truncated the env, 0 elsewhere; Engine.gae_bootstrap takes it as the one-step target
     of the done rows.  The batch gains term_values [T, N].  False (the default): the calls and the batch of before.
     normalise_rewards=True, clip_reward, reward_eps: GAE reads the rewards scaled by the running return (the module's docstring); the
-    batch gains scaled_rewards [T, N] and return_norm (float64 [4])."""
+    batch gains scaled_rewards [T, N] and return_norm (float64 [4]).
+    episode_stats=True: the statistics of the episodes that finished (the module's docstring); the batch gains episode_stats,
+    episode_stats_rollout (float64 [16]), ep_returns and ep_lengths [T, N]."""
     def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, bootstrap_truncations=False,
-                 normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8):
+                 normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8, episode_stats=False):
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A != 1:
             raise NotImplementedError(
@@ -200,6 +281,7 @@ class RolloutCollector(_Collector):
                                  "final_observation (image observations: enable_step_info(final_obs=False))")
         self._allocate(eng, (eng.N, ), policy_weights, value_weights, T, gamma, lam, seed)
         self._normalise(normalise_rewards, clip_reward, reward_eps)
+        self._episodes(episode_stats)
         if self.bootstrap_truncations:
             self.term_values = eng.torch.zeros((self.T, eng.N), dtype=eng.torch.float32, device=eng.device)
             self.batch.update(term_values=self.term_values)
@@ -219,6 +301,7 @@ class RolloutCollector(_Collector):
                                            self.term_values[t], tcv)
 
     def _finish(self):
+        self._episode_call()
         rewards = self._gae_rewards()
         if self.bootstrap_truncations:
             self.engine.gae_bootstrap(rewards, self.values, self.dones, self.term_values, self.gamma, self.lam, adv=self.advantages,
@@ -250,11 +333,12 @@ class SafeRolloutCollector(RolloutCollector):
     term_values and term_cost_values [T, N], and Engine.cost_gae_bootstrap takes the latter as the cost side's one-step target.  The
     books of episode costs are unchanged: a truncated episode still finishes for them."""
     def __init__(self, env_or_engine, policy_weights, value_weights, cost_weights, T, costs=None, gamma=0.99, lam=0.95, cost_gamma=0.99,
-                 cost_lam=0.95, seed=0, bootstrap_truncations=False, normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8):
+                 cost_lam=0.95, seed=0, bootstrap_truncations=False, normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8,
+                 episode_stats=False):
         self.cost_weights = tuple(cost_weights)
         super().__init__(env_or_engine, policy_weights, value_weights, T, gamma=gamma, lam=lam, seed=seed,
                          bootstrap_truncations=bootstrap_truncations, normalise_rewards=normalise_rewards, clip_reward=clip_reward,
-                         reward_eps=reward_eps)
+                         reward_eps=reward_eps, episode_stats=episode_stats)
         eng = self.engine
         t = eng.torch
         if costs is None:
@@ -328,9 +412,12 @@ class MultiAgentRolloutCollector(_Collector):
     in a HIP graph.
 
     The step is handed another observation row at every step, so the engine's marks of seats whose zero row is already in place
-    (pgd_forget_rows) never carry over: every step of a rollout writes the zero row of every seat that is not due."""
+    (pgd_forget_rows) never carry over: every step of a rollout writes the zero row of every seat that is not due.
+
+    episode_stats=True: the statistics of the agents' episodes, per seat (the module's docstring); cut_rate of episode_summary() is the
+    share of the agents an env-wide restart took out."""
     def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, normalise_rewards=False, clip_reward=10.0,
-                 reward_eps=1e-8):
+                 reward_eps=1e-8, episode_stats=False):
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A == 1:
             raise NotImplementedError("MultiAgentRolloutCollector serves multi-agent engines: this one has a single agent seat per env and "
@@ -339,6 +426,7 @@ class MultiAgentRolloutCollector(_Collector):
             raise ValueError("MultiAgentRolloutCollector: T = %r" % (T, ))
         self._allocate(eng, (eng.N, eng.A), policy_weights, value_weights, T, gamma, lam, seed)
         self._normalise(normalise_rewards, clip_reward, reward_eps)
+        self._episodes(episode_stats, seats=True)
         t = eng.torch
         i32 = dict(dtype=t.int32, device=eng.device)
         self.mask = t.zeros(self.flags.shape, dtype=t.uint8, device=eng.device)
@@ -356,6 +444,7 @@ class MultiAgentRolloutCollector(_Collector):
         self.engine.live_rows(self.flags[t], self.dones[t], rows=self._rows, count=self._n_rows)
 
     def _finish(self):
+        self._episode_call()
         self.engine.gae_masked(self._gae_rewards(flags=self.flags), self.values, self.dones, self.flags, self.gamma, self.lam, adv=self.advantages,
                                ret=self.returns, mask=self.mask)
         self.engine.rollout_index(self.flags, index=self.index, count=self.count)
