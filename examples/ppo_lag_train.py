@@ -48,11 +48,12 @@ def make(args):
     env.reset()
     if getattr(args, "plain", False):
         from pgdrive_amd import PPOLearner, RolloutCollector
-        col = RolloutCollector(env, pw, vw, args.T, seed=0, bootstrap_truncations=args.bootstrap_truncations)
+        col = RolloutCollector(env, pw, vw, args.T, seed=0, bootstrap_truncations=args.bootstrap_truncations, normalise_obs=args.normalise_obs)
         learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches)
     else:
         from pgdrive_amd import PPOLagLearner, SafeRolloutCollector
-        col = SafeRolloutCollector(env, pw, vw, cw, args.T, seed=0, bootstrap_truncations=args.bootstrap_truncations)
+        col = SafeRolloutCollector(env, pw, vw, cw, args.T, seed=0, bootstrap_truncations=args.bootstrap_truncations,
+                                   normalise_obs=args.normalise_obs)
         learner = PPOLagLearner(col, cost_limit=args.cost_limit, lambda_lr=args.lambda_lr, lr=args.lr, epochs=args.epochs,
                                 minibatches=args.minibatches)
     return env, col, learner
@@ -122,6 +123,8 @@ def main():
     ap.add_argument("--calls", type=int, default=3, help="calls per timed window")
     ap.add_argument("--bootstrap-truncations", action="store_true",
                     help="GAE and cost GAE bootstrap through the horizon from the critics' values of the terminal observation (DESIGN.md section 24)")
+    ap.add_argument("--normalise-obs", action="store_true",
+                    help="the networks read the observations normalised by their running mean and variance (DESIGN.md section 27)")
     args = ap.parse_args()
     if args.time:
         return time_pair(args)

@@ -2,7 +2,7 @@
 (pgdrive_amd.RolloutCollector / MultiAgentRolloutCollector and pgdrive_amd.PPOLearner: pgd_adv_stats, then pgd_ppo_grad + pgd_adam per
 epoch and minibatch).
 
-    python examples/ppo_train.py --envs 256 --T 32 --iters 20 [--graph] [--marl [--agents 40]] [--every 5] [--episode-stats]
+    python examples/ppo_train.py --envs 256 --T 32 --iters 20 [--graph] [--marl [--agents 40]] [--every 5] [--episode-stats] [--normalise-obs]
     python examples/ppo_train.py --time --envs 4096 --T 64 [--windows 7] [--updates 3]
 
 Random initial weights of the shape of the reference's shipped PPO expert (pgdrive/examples/ppo_expert/numpy_expert.py).  Printed every
@@ -157,6 +157,8 @@ def main():
                     help="GAE bootstraps through the horizon from the critic's value of the terminal observation (DESIGN.md section 24)")
     ap.add_argument("--normalise-rewards", action="store_true",
                     help="GAE reads the rewards divided by the standard deviation of the running discounted return (DESIGN.md section 25)")
+    ap.add_argument("--normalise-obs", action="store_true",
+                    help="the networks read the observations normalised by their running mean and variance (DESIGN.md section 27)")
     ap.add_argument("--episode-stats", action="store_true",
                     help="print the statistics of the episodes that finished since the last print (DESIGN.md section 26)")
     args = ap.parse_args()
@@ -174,10 +176,10 @@ def main():
     if args.marl:   # (no such switch: the cause of a done cannot be read from a multi-agent step's flags)
         assert not args.bootstrap_truncations, "--bootstrap-truncations serves single-agent engines"
         col = MultiAgentRolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, normalise_rewards=args.normalise_rewards,
-                                         episode_stats=args.episode_stats)
+                                         episode_stats=args.episode_stats, normalise_obs=args.normalise_obs)
     else:
         col = RolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, bootstrap_truncations=args.bootstrap_truncations,
-                               normalise_rewards=args.normalise_rewards, episode_stats=args.episode_stats)
+                               normalise_rewards=args.normalise_rewards, episode_stats=args.episode_stats, normalise_obs=args.normalise_obs)
     learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, ent_coef=0.0)
 
     def iteration():
@@ -213,6 +215,8 @@ def main():
                 else:
                     reward = float(b["rewards"].mean())
                 scale = "  reward scale %.4g" % float(b["return_norm"][3]) if args.normalise_rewards else ""
+                if args.normalise_obs:
+                    scale += "  obs samples %d, largest scale %.4g" % (int(b["obs_norm_record"][0]), float(b["obs_norm"][1].max()))
                 print("iteration %4d  Adam step %5d  mean reward %8.4f  " % (it, int(learner.step[0]), reward) +
                       "  ".join("%s %.4g" % (k, x) for k, x in zip(_abi.PPO_STATS[:7], st)) + scale)
                 if args.episode_stats:

@@ -765,6 +765,53 @@ int pgd_rollout_episodes(pgd_handle h, const float* d_reward /*[T][rows]*/, cons
                          uint32_t mode, float* d_ret_carry /*[rows], in/out*/, int32_t* d_len_carry /*[rows], in/out*/,
                          double* d_record /*[16] in/out, or null*/, double* d_call /*[16] or null*/, float* d_ep_return /*[T][rows] or null*/,
                          int32_t* d_ep_length /*[T][rows] or null*/, void* d_work, size_t work_bytes);
+/* ---- Observation normalisation, fused into the training kernels' row loads (every engine) -----------------------------------------------
+ * (No reference counterpart: the reference hands its observations to an RL library; this is the norm_obs half of Stable-Baselines3's
+ * VecNormalize -- a running mean and variance per observation column, the networks fed clip((obs - mean) / sqrt(var + eps)) -- without a
+ * normalised copy of the rollout: the kernels that read observation rows normalise them as they load them.)
+ * Two caller-owned device objects:
+ *   record  1 + 2 in_dim doubles, 8-byte aligned: slot 0 = n, the number of samples folded; slots 1 .. in_dim the column means; slots
+ *           1 + in_dim .. 2 in_dim the column sums of squared deviations m2.  All zero before the first fold.  There is NO phantom initial
+ *           count as in SB3's RunningMeanStd (mean 0, variance 1, count 1e-4): an empty record is the identity, the first rollout runs on raw
+ *           observations, and the statistics are those of the samples alone.
+ *   table   what the kernels read: float [2][Dp], 16-byte aligned, Dp = (in_dim + 3) & ~3; row 0 `shift`, row 1 `scale`:
+ *             shift[k] = (float) mean[k];   scale[k] = (float)(1 / sqrt(m2[k] / n + eps))
+ *           the quotient and the square root formed in double and rounded to fp32 once; the variance is the population variance.  n == 0:
+ *           the identity (shift 0, scale 1).  The padding entries in_dim .. Dp - 1 are always the identity.
+ * The normalised input of a live row and a column k < in_dim:
+ *   y = min(max((x - shift[k]) * scale[k], -clip), clip)       an fp32 subtraction, then an fp32 multiplication, never contracted into an fma
+ * Padding columns and rows past the end (of the range, of the list, behind a mask) stay exactly 0 in the kernels' tiles, as without a
+ * table: they are not normalised (a column of zeros would otherwise enter layer 1 as -shift * scale).
+ *
+ * pgd_obs_norm_update folds the first in_dim floats of every listed row of the row-major array d_obs [n_rows][obs_stride] into the record.
+ * The list is that of pgd_adv_stats / pgd_ppo_grad: position q < count is row d_index[q] (null: q itself; an entry outside [0, n_rows) is
+ * clamped, never followed); d_count is a device int32 held within [0, n_list] (null: n_list) that the host never reads.  Rows that are
+ * not listed may hold NaN: they are never read, nothing is multiplied by zero.  Per column, in double: partitions of 512 list positions
+ * (K = the partition's first sample, s1 = sum (x - K), s2 = sum (x - K)^2 in list order; mean = K + s1 / n, m2 = max(s2 - s1 (s1 / n), 0)),
+ * the partitions merged in partition order by Chan's update (as for pgd_return_norm), the call's statistic then merged into the record.
+ * No atomics: the same inputs give the same bytes.  A call with no live position leaves every byte of the record.  Scratch is the caller's:
+ * d_work, 8-byte aligned, work_bytes >= pgd_obs_norm_work_bytes(in_dim, n_list) (two doubles, and 2 in_dim doubles per 512 positions; 0
+ * for arguments the call would refuse).  Nothing is allocated inside: two launches, asynchronous on the engine's stream, capturable in a
+ * HIP graph from the first call of a fresh engine.  4 <= in_dim <= 416, obs_stride >= in_dim, n_rows >= 1, n_list >= 1 (without an index
+ * n_list <= n_rows), the pointers set and aligned, work_bytes as above (PGD_ERR_ARG otherwise, before anything is launched).
+ *
+ * pgd_obs_norm_publish: record -> table as defined above, one small launch; eps >= 0.
+ *
+ * pgd_obs_norm_bind is engine state in the manner of pgd_actor_critic_tick.  While a table is bound, every later launch of
+ *   pgd_mlp_actor_critic, pgd_mlp_actor_critic_rows, pgd_mlp_actor_critic_cost, pgd_mlp_terminal_value, pgd_ppo_grad, pgd_ppo_grad_cost
+ * normalises the observation rows as it loads them (pgd_ppo_grad* in both places that read them: the forward tile and the gather of
+ * dW1); every output is what the unbound call gives on an array normalised beforehand by the rule above, bit for bit.  The kernels read
+ * the table when they RUN: a captured graph that is replayed sees what a later pgd_obs_norm_publish wrote.  A call whose in_dim differs
+ * from the bound one is refused (PGD_ERR_ARG).  clip > 0, +inf allowed.  d_table null (the default, and the state after pgd_create)
+ * unbinds: the launches are then the instantiations of before, without an added instruction.  pgd_mlp_policy and
+ * pgd_mlp_policy_prepared IGNORE the binding and their code objects stay what they are: a deployed policy normalises its input itself.
+ * Not served: statistics are per engine (the ranks of a multi-GPU run do not exchange them); image observations. */
+size_t pgd_obs_norm_work_bytes(int in_dim, int n_list);
+int pgd_obs_norm_update(pgd_handle h, const float* d_obs /*[n_rows][obs_stride]*/, int obs_stride, int in_dim, int n_rows,
+                        const int32_t* d_index /* or null */, const int32_t* d_count /* device, or null */, int n_list,
+                        double* d_record /*[1 + 2 in_dim], in/out*/, void* d_work, size_t work_bytes);
+int pgd_obs_norm_publish(pgd_handle h, const double* d_record, int in_dim, double eps, float* d_table /*[2][Dp]*/);
+int pgd_obs_norm_bind(pgd_handle h, const float* d_table /* or null */, int in_dim, float clip);
 /* Multi-agent engines remember, per env, which rows of the LAST observation buffer they were given already hold the zeros of a seat
  * that is not due (identified by the buffer's address and row stride), and do not write them again.  A caller that hands pgd_step
  * a buffer whose address a FORMER buffer had (a caching allocator re-using a freed block: torch.empty per step) calls this first:

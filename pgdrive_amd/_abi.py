@@ -94,6 +94,14 @@ EP_SEATS = 1  # PGD_EP_SEATS, a mode bit of pgd_rollout_episodes
 ROLLOUT_EPISODES = ("episodes", "return_mean", "return_m2", "return_min", "return_max", "length_sum", "length_max", "arrive", "out_of_road",
                     "crash_vehicle", "crash_object", "crash_building", "max_step", "cut", "steps", "calls")  # a record of pgd_rollout_episodes, 16 doubles
 ROLLOUT_EPISODES_INIT = (0.0, 0.0, 0.0, float("inf"), float("-inf")) + (0.0, ) * 11  # the record before the first call
+OBS_NORM_DIMS = (4, 416)  # the input widths pgd_obs_norm_update / _publish / _bind accept, both ends included
+OBS_NORM_PART = 512       # list positions per partition of pgd_obs_norm_update's sums
+
+
+def obs_norm_layout(in_dim):
+    """(record doubles, table shape) of the observation normalisation: d_record of pgd_obs_norm_update is n | means | m2s, d_table of
+    pgd_obs_norm_publish / _bind is float32 [2][Dp], shift | scale, Dp = in_dim rounded up to a multiple of 4."""
+    return 1 + 2 * int(in_dim), (2, (int(in_dim) + 3) & ~3)
 
 # the tensors of Engine.enable_step_info by pgd_step_info field: (dtype name, key in Engine.step_info)
 STEP_INFO_FIELDS = dict(

@@ -46,21 +46,51 @@ DEV_HOST size_t ac_lds_bytes(int in_dim) {  // X tile | H1 | H2 | the head's wei
 // u in (0, 1) from the top 23 bits of a draw: exact in f32
 DEV float ac_unit(const uint32_t r) { return ((float)(r >> 9) + 0.5f) * (1.0f / 8388608.0f); }
 
+// pgd_obs_norm_bind (include/pgdrive_hip.h states the rule; pgd_obs_norm.h holds its moments): the table a bound launch normalises its
+// observation rows with as it loads them, float [2][kp]: shift | scale.  NORM is a template parameter of every loader and of the kernels
+// around them: the false instantiations are the code of before (nm is passed and never read), the host launches them while nothing is bound.
+struct ObsNorm { const float* table; float clip; };
+
+// y = clamp((x - shift) * scale, -clip, clip): one fp32 subtraction, one fp32 multiplication, never an fma
+DEV float on_apply(const float x, const float shift, const float scale, const float clip) {
+#pragma clang fp contract(off) reassociate(off)
+  const float d = x - shift;
+  const float y = d * scale;
+  return fminf(fmaxf(y, -clip), clip);
+}
+
+// the lane's table entries of the fast loader path (columns lane + 64 j; a column past the end reads the last one and is never used):
+// issued with the row reads, before the first LDS store
+template <int XCH>
+DEV void on_lane_table(const ObsNorm nm, const int in_dim, const int kp, const int lane, float (&sh)[XCH], float (&sc)[XCH]) {
+#pragma unroll
+  for (int j = 0; j < XCH; ++j) {
+    const int k = lane + WAVE * j, kk = k < in_dim ? k : in_dim - 1;
+    sh[j] = nm.table[kk];
+    sc[j] = nm.table[kp + kk];
+  }
+}
+
 // k_mlp_policy's row prologue as a function (that kernel keeps its own copy inline: its code object stays what it was).
 // The 16 observation rows of a workgroup into its X tile (row stride xs): rows row0 + r0 + [0, 16) of `obs`, as far as they lie below
 // row0 + n_rows; wave w takes rows w, w + 4, ...  Whole rows, coalesced (a row is contiguous in memory); padding columns and rows past the end read zero.
 // Every read of the wave's four rows goes out before the first LDS store (rows of up to 320 floats: five chunks of 64 per row) --
-// as a read-then-store loop the prologue was twenty memory round trips in a row, a third of the launch (round 6)
+// as a read-then-store loop the prologue was twenty memory round trips in a row, a third of the launch (round 6).
+// NORM: the live entries are normalised on their way (on_apply); padding columns and rows past the end stay exactly 0
+template <bool NORM>
 DEV void ac_load_rows(const float* obs, const int row0, const int r0, const int n_rows, const int obs_stride, const int in_dim, const int kp,
-                       const int xs, const int wave, const int lane, float* X) {
+                       const int xs, const int wave, const int lane, float* X, const ObsNorm nm) {
   constexpr int XCH = 5;
   if (kp <= WAVE * XCH) {
-    float v[MLP_ROWS / MLP_WAVES][XCH];
+    float v[MLP_ROWS / MLP_WAVES][XCH], sh[XCH], sc[XCH];
+    bool live[MLP_ROWS / MLP_WAVES];
+    if (NORM) on_lane_table(nm, in_dim, kp, lane, sh, sc);
 #pragma unroll
     for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i) {
       const int r = wave + i * MLP_WAVES;
       const bool row_in = r0 + r < n_rows;
       const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
+      live[i] = row_in;
 #pragma unroll
       for (int j = 0; j < XCH; ++j) {
         const int k = lane + WAVE * j;
@@ -73,23 +103,28 @@ DEV void ac_load_rows(const float* obs, const int row0, const int r0, const int 
 #pragma unroll
       for (int j = 0; j < XCH; ++j) {
         const int k = lane + WAVE * j;
+        if (NORM) v[i][j] = (live[i] && k < in_dim) ? on_apply(v[i][j], sh[j], sc[j], nm.clip) : 0.0f;
         if (k < kp) X[(wave + i * MLP_WAVES) * xs + k] = v[i][j];
       }
   } else
   for (int r = wave; r < MLP_ROWS; r += MLP_WAVES) {
     const bool row_in = r0 + r < n_rows;
     const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
-    for (int k = lane; k < kp; k += WAVE) X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
+    for (int k = lane; k < kp; k += WAVE) {
+      if (NORM) X[r * xs + k] = (row_in && k < in_dim) ? on_apply(src[k], nm.table[k], nm.table[kp + k], nm.clip) : 0.0f;
+      else X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
+    }
   }
 }
 
 // One workgroup of k_mlp_actor_critic on the network (W1 .. b3): the actor (critic false: act, logp) or a critic (value) for the 16 rows
 // row0 + blockIdx.x * 16 + [0, 16) of `obs`.  The kernels below and k_mlp_actor_critic_cost (pgd_safe.h) choose the network and call it.
+template <bool NORM>
 DEV void ac_tile(const float* obs, const int row0, const int n_rows, const int obs_stride, const int in_dim, const bool critic,
                  const float* W1, const float* b1, const float* W2, const float* b2,
                  const float* W3, const float* b3, const int out_cols, const uint32_t seed, const uint32_t tick_arg,
                  const uint32_t* tick_dev, const uint32_t row_base, const uint32_t flags, float* act,
-                 float* logp, float* value) {
+                 float* logp, float* value, const ObsNorm nm) {
   extern __shared__ float mlp_lds[];
   const int kp = (in_dim + 3) & ~3, xs = mlp_x_stride(in_dim);
   float* X = mlp_lds;
@@ -108,7 +143,7 @@ DEV void ac_tile(const float* obs, const int row0, const int n_rows, const int o
     const int k = critic ? idx : idx >> 2, o = critic ? 0 : idx & 3;
     w3v[q] = q < heads ? W3[(size_t)k * w3_ld + o] : 0.0f;
   }
-  ac_load_rows(obs, row0, r0, n_rows, obs_stride, in_dim, kp, xs, wave, lane, X);
+  ac_load_rows<NORM>(obs, row0, r0, n_rows, obs_stride, in_dim, kp, xs, wave, lane, X, nm);
 #pragma unroll
   for (int q = 0; q < AC_HEAD; ++q) {
     const int idx = tid + q * WAVE * MLP_WAVES;
@@ -170,16 +205,17 @@ DEV void ac_tile(const float* obs, const int row0, const int n_rows, const int o
 }
 
 // rows [row0, row0 + n_rows) of `obs` -> act[row][0..1], logp[row] (blockIdx.y == 0) and value[row] (blockIdx.y == 1)
+template <bool NORM>
 __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic(const float* __restrict__ obs, const int row0, const int n_rows,
                                                                        const int obs_stride, const int in_dim, const pgd_actor_critic nets,
                                                                        const uint32_t seed, const uint32_t tick_arg,
                                                                        const uint32_t* __restrict__ tick_dev, const uint32_t row_base,
                                                                        const uint32_t flags, float* __restrict__ act, float* __restrict__ logp,
-                                                                       float* __restrict__ value) {
+                                                                       float* __restrict__ value, const ObsNorm nm) {
   const bool critic = blockIdx.y != 0;
-  ac_tile(obs, row0, n_rows, obs_stride, in_dim, critic, critic ? nets.vw1 : nets.w1, critic ? nets.vb1 : nets.b1, critic ? nets.vw2 : nets.w2,
+  ac_tile<NORM>(obs, row0, n_rows, obs_stride, in_dim, critic, critic ? nets.vw1 : nets.w1, critic ? nets.vb1 : nets.b1, critic ? nets.vw2 : nets.w2,
           critic ? nets.vb2 : nets.b2, critic ? nets.vw3 : nets.w3, critic ? nets.vb3 : nets.b3, nets.out_cols, seed, tick_arg, tick_dev, row_base,
-          flags, act, logp, value);
+          flags, act, logp, value, nm);
 }
 
 // adv[t][r] = delta + gamma lam nonterminal adv[t + 1][r], delta = reward[t][r] + gamma value[t + 1][r] nonterminal - value[t][r],

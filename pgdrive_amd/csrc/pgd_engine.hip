@@ -39,7 +39,9 @@ static Switches read_switches() {
           rowz && rowz[0] != '0', on("PGD_NO_UNI"), pack ? (atoi(pack) != 0 ? 1 : 0) : -1, on("PGD_NO_IMASK") ? 0 : (on("PGD_IMASK") ? 1 : -1)};
 }
 // The kernels that take more than 48 KB of dynamic LDS at wide inputs: their limit is raised once per engine (raise_lds_limit)
-enum LdsKernel { LDS_MLP, LDS_MLP_TANH, LDS_MLP_BF, LDS_MLP_BF_TANH, LDS_AC, LDS_AC_ROWS, LDS_AC_COST, LDS_PPO_ROWS, LDS_PPO_ROWS_COST, LDS_TERM_VALUE, LDS_KERNELS };
+// (LDS_AC .. LDS_TERM_VALUE: the instantiations that normalise their observation rows, pgd_obs_norm_bind, have slots of their own behind them)
+enum LdsKernel { LDS_MLP, LDS_MLP_TANH, LDS_MLP_BF, LDS_MLP_BF_TANH, LDS_AC, LDS_AC_ROWS, LDS_AC_COST, LDS_PPO_ROWS, LDS_PPO_ROWS_COST, LDS_TERM_VALUE,
+                 LDS_NORM_FIRST, LDS_KERNELS = LDS_NORM_FIRST + (LDS_TERM_VALUE - LDS_AC + 1) };
 struct pgd_engine {
   PgdDev d;
   Switches sw;
@@ -87,6 +89,7 @@ struct pgd_engine {
   hipFunction_t jit_fn;
   bool jit_obj;
   const uint32_t* ac_tick;  // pgd_actor_critic_tick: the device counter added to every launch's tick (null: none)
+  struct { const float* table; int in_dim; float clip; } obs_norm;  // pgd_obs_norm_bind: the table the training launches normalise their rows with (null: none)
   uint32_t* cmp_live;   // pgd_live_rows: block counts of the compaction, a segment for the whole engine and one per env group (pgd_create allocates it)
   uint32_t* cmp_index;  // pgd_rollout_index: block counts [cmp_index_cap], grown outside graph captures
   size_t cmp_index_cap;
@@ -124,6 +127,7 @@ static int env_group(const pgd_engine* h, int group, EnvGroup& g) {
 
 // A launch with `lds` bytes of dynamic LDS: above 48 KB the kernel's limit has to be raised first, once per engine and kernel (per engine =
 // per device: a process may hold engines on several GPUs)
+static LdsKernel lds_slot(LdsKernel which, bool norm) { return norm ? (LdsKernel)(LDS_NORM_FIRST + (which - LDS_AC)) : which; }
 static int raise_lds_limit(pgd_engine* h, LdsKernel which, const void* kernel, size_t lds) {
   if (lds <= 49152 || h->lds_raised[which]) return PGD_OK;
   HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
@@ -152,17 +156,22 @@ static bool grads_ok(const pgd_ppo_grads* g, const pgd_value_grads* cost, bool h
          (!cost || six_set(cost->w1, cost->b1, cost->w2, cost->b2, cost->w3, cost->b3));
 }
 
-// The shared tail of the actor-critic forward family, behind the caller's refusals: the rows of the env group (or of all envs) on its
-// stream, the raised LDS limit of `kernel`, then the caller's launch(es) over those rows
-struct AcRows { int row0, rows; uint32_t row_base; size_t lds; hipStream_t stream; };
-template <typename Launch>
-static int ac_forward(pgd_engine* h, int group, LdsKernel which, const void* kernel, int in_dim, Launch launch) {
+// The shared tail of the actor-critic forward family, behind the caller's refusals: the observation binding (pgd_obs_norm_bind: a bound
+// table of another width refuses the call; `norm` is launched while one is bound, `plain` -- today's code -- otherwise), the rows of the
+// env group (or of all envs) on its stream, the raised LDS limit of the chosen kernel, then the caller's launch(es) over those rows
+struct AcRows { int row0, rows; uint32_t row_base; size_t lds; hipStream_t stream; ObsNorm nm; };
+template <typename Kernel, typename Launch>
+static int ac_forward(pgd_engine* h, int group, LdsKernel which, Kernel plain, Kernel norm, int in_dim, Launch launch) {
+  const bool bound = h->obs_norm.table != nullptr;
+  if (bound && in_dim != h->obs_norm.in_dim) return PGD_ERR_ARG;
+  const Kernel kernel = bound ? norm : plain;
   HIPCHK(hipSetDevice(h->device));
   EnvGroup g;
   { int rc = env_group(h, group, g); if (rc) return rc; }
   const size_t lds = ac_lds_bytes(in_dim);
-  { int rc = raise_lds_limit(h, which, kernel, lds); if (rc) return rc; }
-  launch(AcRows{g.first * h->d.A, g.count * h->d.A, (uint32_t)h->d.cfg.env_base * (uint32_t)h->d.A, lds, g.stream});
+  { int rc = raise_lds_limit(h, lds_slot(which, bound), reinterpret_cast<const void*>(kernel), lds); if (rc) return rc; }
+  launch(AcRows{g.first * h->d.A, g.count * h->d.A, (uint32_t)h->d.cfg.env_base * (uint32_t)h->d.A, lds, g.stream,
+                ObsNorm{h->obs_norm.table, h->obs_norm.clip}}, kernel);
   HIPCHK(hipGetLastError());
   return PGD_OK;
 }
@@ -997,9 +1006,9 @@ int pgd_mlp_actor_critic(pgd_handle h, int group, const float* d_obs, int obs_st
   bool critic;
   if (!h || !d_obs || !d_actions || !d_logp || (flags & ~PGD_AC_DETERMINISTIC) != 0u || !nets_ok(nets, nullptr, true, in_dim, obs_stride, &critic) ||
       (critic && !d_value) || ac_lds_bytes(in_dim) > 65536) return PGD_ERR_ARG;
-  return ac_forward(h, group, LDS_AC, reinterpret_cast<const void*>(k_mlp_actor_critic), in_dim, [&](const AcRows& r) {
-    hipLaunchKernelGGL(k_mlp_actor_critic, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream, d_obs,
-                       r.row0, r.rows, obs_stride, in_dim, *nets, seed, tick, h->ac_tick, r.row_base, flags, d_actions, d_logp, d_value);
+  return ac_forward(h, group, LDS_AC, k_mlp_actor_critic<false>, k_mlp_actor_critic<true>, in_dim, [&](const AcRows& r, auto kern) {
+    hipLaunchKernelGGL(kern, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream, d_obs,
+                       r.row0, r.rows, obs_stride, in_dim, *nets, seed, tick, h->ac_tick, r.row_base, flags, d_actions, d_logp, d_value, r.nm);
   });
 }
 
@@ -1052,13 +1061,13 @@ int pgd_mlp_actor_critic_rows(pgd_handle h, int group, const float* d_obs, int o
   bool critic;
   if (!h || !d_obs || !d_rows || !d_count || !d_actions || !d_logp || (flags & ~PGD_AC_DETERMINISTIC) != 0u ||
       !nets_ok(nets, nullptr, true, in_dim, obs_stride, &critic) || (critic && !d_value) || ac_lds_bytes(in_dim) > 65536) return PGD_ERR_ARG;
-  return ac_forward(h, group, LDS_AC_ROWS, reinterpret_cast<const void*>(k_mlp_actor_critic_rows), in_dim, [&](const AcRows& r) {
+  return ac_forward(h, group, LDS_AC_ROWS, k_mlp_actor_critic_rows<false>, k_mlp_actor_critic_rows<true>, in_dim, [&](const AcRows& r, auto kern) {
     // the defined outputs of the rows that are not listed, then the listed rows (the host does not know how many: a grid for all)
     hipLaunchKernelGGL(k_ac_clear_rows, dim3((r.rows + CMP_THREADS - 1) / CMP_THREADS), dim3(CMP_THREADS), 0, r.stream, r.row0, r.rows, d_actions,
                        d_logp, critic ? d_value : nullptr);
-    hipLaunchKernelGGL(k_mlp_actor_critic_rows, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream,
+    hipLaunchKernelGGL(kern, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream,
                        d_obs, d_rows, d_count, r.row0, r.rows, obs_stride, in_dim, *nets, seed, tick, h->ac_tick, r.row_base, flags, d_actions,
-                       d_logp, d_value);
+                       d_logp, d_value, r.nm);
   });
 }
 
@@ -1409,5 +1418,6 @@ int pgd_destroy(pgd_handle h) {
 #include "pgd_safe.h"
 #include "pgd_timelimit.h"
 #include "pgd_return_norm.h"
+#include "pgd_obs_norm.h"
 #include "pgd_rollout_episodes.h"
 #endif  // !PGD_JIT

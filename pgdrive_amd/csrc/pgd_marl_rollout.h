@@ -139,16 +139,20 @@ DEV int ro_listed_row(const int32_t* list, const int i, const int n, const int r
 // ac_load_rows with an index: the observation rows list[l0 + [0, 16)) into the X tile; entries past n and rows outside the range read zero
 // (the first form loads row row_lo in their place, as ac_load_rows loads its tile's first row, and selects the zero: the observation of
 // a row that is not listed is never USED -- it may hold NaN -- but row_lo's may be read)
+template <bool NORM>
 DEV void ro_load_rows(const float* obs, const int32_t* list, const int l0, const int n, const int row_lo, const int n_rows, const int obs_stride,
-                      const int in_dim, const int kp, const int xs, const int wave, const int lane, float* X) {
+                      const int in_dim, const int kp, const int xs, const int wave, const int lane, float* X, const ObsNorm nm) {
   constexpr int XCH = 5;
   if (kp <= WAVE * XCH) {
-    float v[MLP_ROWS / MLP_WAVES][XCH];
+    float v[MLP_ROWS / MLP_WAVES][XCH], sh[XCH], sc[XCH];
+    bool live[MLP_ROWS / MLP_WAVES];
+    if (NORM) on_lane_table(nm, in_dim, kp, lane, sh, sc);
 #pragma unroll
     for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i) {
       const int row = ro_listed_row(list, l0 + wave + i * MLP_WAVES, n, row_lo, n_rows);
       const bool row_in = row >= 0;
       const float* src = obs + (size_t)(row_in ? row : row_lo) * obs_stride;
+      live[i] = row_in;
 #pragma unroll
       for (int j = 0; j < XCH; ++j) {
         const int k = lane + WAVE * j;
@@ -161,6 +165,7 @@ DEV void ro_load_rows(const float* obs, const int32_t* list, const int l0, const
 #pragma unroll
       for (int j = 0; j < XCH; ++j) {
         const int k = lane + WAVE * j;
+        if (NORM) v[i][j] = (live[i] && k < in_dim) ? on_apply(v[i][j], sh[j], sc[j], nm.clip) : 0.0f;
         if (k < kp) X[(wave + i * MLP_WAVES) * xs + k] = v[i][j];
       }
   } else
@@ -168,19 +173,23 @@ DEV void ro_load_rows(const float* obs, const int32_t* list, const int l0, const
     const int row = ro_listed_row(list, l0 + r, n, row_lo, n_rows);
     const bool row_in = row >= 0;
     const float* src = obs + (size_t)(row_in ? row : row_lo) * obs_stride;
-    for (int k = lane; k < kp; k += WAVE) X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
+    for (int k = lane; k < kp; k += WAVE) {
+      if (NORM) X[r * xs + k] = (row_in && k < in_dim) ? on_apply(src[k], nm.table[k], nm.table[kp + k], nm.clip) : 0.0f;
+      else X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
+    }
   }
 }
 
 // the rows list[0 .. *count) of `obs`, each within [row_lo, row_lo + n_rows) -> act[row][0..1], logp[row] (blockIdx.y == 0) and
 // value[row] (blockIdx.y == 1).  Everything behind the prologue is k_mlp_actor_critic's.
+template <bool NORM>
 __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic_rows(const float* __restrict__ obs, const int32_t* __restrict__ list,
                                                                             const int32_t* __restrict__ count, const int row_lo, const int n_rows,
                                                                             const int obs_stride, const int in_dim, const pgd_actor_critic nets,
                                                                             const uint32_t seed, const uint32_t tick_arg,
                                                                             const uint32_t* __restrict__ tick_dev, const uint32_t row_base,
                                                                             const uint32_t flags, float* __restrict__ act, float* __restrict__ logp,
-                                                                            float* __restrict__ value) {
+                                                                            float* __restrict__ value, const ObsNorm nm) {
   extern __shared__ float mlp_lds[];
   const int l0 = (int)blockIdx.x * MLP_ROWS;  // (the tile's first list entry)
   const int n = min(*count, n_rows);
@@ -206,7 +215,7 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic_rows(c
     const int k = critic ? idx : idx >> 2, o = critic ? 0 : idx & 3;
     w3v[q] = q < heads ? W3[(size_t)k * w3_ld + o] : 0.0f;
   }
-  ro_load_rows(obs, list, l0, n, row_lo, n_rows, obs_stride, in_dim, kp, xs, wave, lane, X);
+  ro_load_rows<NORM>(obs, list, l0, n, row_lo, n_rows, obs_stride, in_dim, kp, xs, wave, lane, X, nm);
 #pragma unroll
   for (int q = 0; q < AC_HEAD; ++q) {
     const int idx = tid + q * WAVE * MLP_WAVES;

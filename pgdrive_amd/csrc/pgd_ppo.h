@@ -84,16 +84,21 @@ DEV int ppo_row(const pgd_ppo_batch& b, const int i, const int n) {
 }
 
 // ro_load_rows for minibatch positions i0 + [0, 16): rows that are not live read zero (row 0 is loaded in their place, never used)
-DEV void ppo_load_rows(const pgd_ppo_batch& b, const int i0, const int n, const int kp, const int xs, const int wave, const int lane, float* X) {
+template <bool NORM>
+DEV void ppo_load_rows(const pgd_ppo_batch& b, const int i0, const int n, const int kp, const int xs, const int wave, const int lane, float* X,
+                       const ObsNorm nm) {
   constexpr int XCH = 5;
   const int in_dim = b.in_dim;
   if (kp <= WAVE * XCH) {
-    float v[MLP_ROWS / MLP_WAVES][XCH];
+    float v[MLP_ROWS / MLP_WAVES][XCH], sh[XCH], sc[XCH];
+    bool live[MLP_ROWS / MLP_WAVES];
+    if (NORM) on_lane_table(nm, in_dim, kp, lane, sh, sc);
 #pragma unroll
     for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i) {
       const int row = ppo_row(b, i0 + wave + i * MLP_WAVES, n);
       const bool row_in = row >= 0;
       const float* src = b.obs + (size_t)(row_in ? row : 0) * b.obs_stride;
+      live[i] = row_in;
 #pragma unroll
       for (int j = 0; j < XCH; ++j) {
         const int k = lane + WAVE * j;
@@ -106,6 +111,7 @@ DEV void ppo_load_rows(const pgd_ppo_batch& b, const int i0, const int n, const 
 #pragma unroll
       for (int j = 0; j < XCH; ++j) {
         const int k = lane + WAVE * j;
+        if (NORM) v[i][j] = (live[i] && k < in_dim) ? on_apply(v[i][j], sh[j], sc[j], nm.clip) : 0.0f;
         if (k < kp) X[(wave + i * MLP_WAVES) * xs + k] = v[i][j];
       }
   } else
@@ -113,7 +119,10 @@ DEV void ppo_load_rows(const pgd_ppo_batch& b, const int i0, const int n, const 
     const int row = ppo_row(b, i0 + r, n);
     const bool row_in = row >= 0;
     const float* src = b.obs + (size_t)(row_in ? row : 0) * b.obs_stride;
-    for (int k = lane; k < kp; k += WAVE) X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
+    for (int k = lane; k < kp; k += WAVE) {
+      if (NORM) X[r * xs + k] = (row_in && k < in_dim) ? on_apply(src[k], nm.table[k], nm.table[kp + k], nm.clip) : 0.0f;
+      else X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
+    }
   }
 }
 
@@ -128,10 +137,11 @@ __global__ __launch_bounds__(MLP_H) void k_ppo_prep(const pgd_actor_critic nets,
 // One workgroup of k_ppo_rows: network blockIdx.y of gridDim.y -- the actor (critic false) or a critic on (W1 .. b3) with the target `ret` and
 // the coefficient `vf_coef`, whose two tile sums go to slots 9 + ts_shift and 10 + ts_shift of the tile's record -- for the 16 minibatch
 // positions blockIdx.x * 16 + [0, 16).  k_ppo_rows and k_ppo_rows_cost (pgd_safe.h) choose the network and call it.
+template <bool NORM>
 DEV void ppo_rows_tile(const bool critic, const float* W1, const float* b1, const float* W2,
                        const float* b2, const float* W3, const float* b3, const int out_cols,
                        const float* ret, const float vf_coef, const int ts_shift, const pgd_ppo_batch& b, const pgd_ppo_hyper& hp,
-                       float* work) {
+                       float* work, const ObsNorm nm) {
   extern __shared__ float mlp_lds[];
   const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
   const int i0 = (int)blockIdx.x * MLP_ROWS;  // (the tile's first minibatch position)
@@ -161,7 +171,7 @@ DEV void ppo_rows_tile(const bool critic, const float* W1, const float* b1, cons
     const int k = critic ? idx : idx >> 2, o = critic ? 0 : idx & 3;
     w3v[q] = q < heads ? W3[(size_t)k * w3_ld + o] : 0.0f;
   }
-  ppo_load_rows(b, i0, n, kp, xs, wave, lane, X);
+  ppo_load_rows<NORM>(b, i0, n, kp, xs, wave, lane, X, nm);
 #pragma unroll
   for (int q = 0; q < AC_HEAD; ++q) {
     const int idx = tid + q * WAVE * MLP_WAVES;
@@ -289,11 +299,12 @@ DEV void ppo_rows_tile(const bool critic, const float* W1, const float* b1, cons
   }
 }
 
+template <bool NORM>
 __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows(const pgd_actor_critic nets, const pgd_ppo_batch b, const pgd_ppo_hyper hp,
-                                                               float* __restrict__ work) {
+                                                               float* __restrict__ work, const ObsNorm nm) {
   const bool critic = blockIdx.y != 0;
-  ppo_rows_tile(critic, critic ? nets.vw1 : nets.w1, critic ? nets.vb1 : nets.b1, critic ? nets.vw2 : nets.w2, critic ? nets.vb2 : nets.b2,
-                critic ? nets.vw3 : nets.w3, critic ? nets.vb3 : nets.b3, nets.out_cols, b.ret, hp.vf_coef, 0, b, hp, work);
+  ppo_rows_tile<NORM>(critic, critic ? nets.vw1 : nets.w1, critic ? nets.vb1 : nets.b1, critic ? nets.vw2 : nets.w2, critic ? nets.vb2 : nets.b2,
+                      critic ? nets.vw3 : nets.w3, critic ? nets.vb3 : nets.b3, nets.out_cols, b.ret, hp.vf_coef, 0, b, hp, work, nm);
 }
 
 // what output tile `tile` of a network is: 0 dW1 (m0 = its first weight row), 1 db1, 2 dW2, 3 db2, 4 dW3^T
@@ -305,7 +316,9 @@ DEV int ppo_tile_kind(const int tile, const int mt1, int& m0) {
   return tile == mt1 + 17 ? 3 : 4;
 }
 
-__global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad(const pgd_ppo_batch b, float* __restrict__ work) {
+// NORM: the X of dW1 is gathered as k_ppo_rows loaded it, normalised by the bound table (the table has not moved in between: one stream)
+template <bool NORM>
+__global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad(const pgd_ppo_batch b, float* __restrict__ work, const ObsNorm nm) {
   __shared__ float At[16 * (PPO_CHUNK + 2)];
   const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
   const int live16 = (n + 15) & ~15;
@@ -334,7 +347,9 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad(const pgd_ppo
       float v;
       if (kind == 0) {
         const int row = ppo_row(b, r0 + j, n);
-        v = (row >= 0 && m0 + m < in_dim) ? b.obs[(size_t)row * b.obs_stride + m0 + m] : 0.0f;
+        const bool in = row >= 0 && m0 + m < in_dim;
+        v = in ? b.obs[(size_t)row * b.obs_stride + m0 + m] : 0.0f;
+        if (NORM) v = in ? on_apply(v, nm.table[m0 + m], nm.table[((in_dim + 3) & ~3) + m0 + m], nm.clip) : 0.0f;
       } else if (kind == 2) {
         v = H1g[(size_t)(r0 + j) * MLP_H + m0 + m];
       } else if (kind == 4) {

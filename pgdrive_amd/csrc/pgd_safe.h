@@ -29,19 +29,20 @@ struct SafeNets { pgd_actor_critic ac; pgd_value_net c; };
 struct SafeGrads { pgd_ppo_grads g; pgd_value_grads c; };
 
 // ---- pgd_mlp_actor_critic_cost: k_mlp_actor_critic with grid.y = 3; workgroup (x, 2) is a critic workgroup on the cost network -------
+template <bool NORM>
 __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic_cost(const float* __restrict__ obs, const int row0, const int n_rows,
                                                                             const int obs_stride, const int in_dim, const SafeNets nets,
                                                                             const uint32_t seed, const uint32_t tick_arg,
                                                                             const uint32_t* __restrict__ tick_dev, const uint32_t row_base,
                                                                             const uint32_t flags, float* __restrict__ act,
                                                                             float* __restrict__ logp, float* __restrict__ value,
-                                                                            float* __restrict__ cost_value) {
+                                                                            float* __restrict__ cost_value, const ObsNorm nm) {
   const int y = (int)blockIdx.y;
   const pgd_actor_critic& a = nets.ac;
   const pgd_value_net& c = nets.c;
-  ac_tile(obs, row0, n_rows, obs_stride, in_dim, y != 0, y == 0 ? a.w1 : (y == 1 ? a.vw1 : c.w1), y == 0 ? a.b1 : (y == 1 ? a.vb1 : c.b1),
+  ac_tile<NORM>(obs, row0, n_rows, obs_stride, in_dim, y != 0, y == 0 ? a.w1 : (y == 1 ? a.vw1 : c.w1), y == 0 ? a.b1 : (y == 1 ? a.vb1 : c.b1),
           y == 0 ? a.w2 : (y == 1 ? a.vw2 : c.w2), y == 0 ? a.b2 : (y == 1 ? a.vb2 : c.b2), y == 0 ? a.w3 : (y == 1 ? a.vw3 : c.w3),
-          y == 0 ? a.b3 : (y == 1 ? a.vb3 : c.b3), a.out_cols, seed, tick_arg, tick_dev, row_base, flags, act, logp, y == 2 ? cost_value : value);
+          y == 0 ? a.b3 : (y == 1 ? a.vb3 : c.b3), a.out_cols, seed, tick_arg, tick_dev, row_base, flags, act, logp, y == 2 ? cost_value : value, nm);
 }
 
 // ---- pgd_cost_gae ---------------------------------------------------------------------------------------------------------------------
@@ -165,14 +166,15 @@ __global__ __launch_bounds__(MLP_H) void k_ppo_prep_cost(const SafeNets nets, fl
   W2T[(size_t)k * MLP_H + c] = W2[(size_t)c * MLP_H + k];
 }
 
+template <bool NORM>
 __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows_cost(const SafeNets nets, const pgd_ppo_batch b, const pgd_ppo_hyper hp,
-                                                                    const pgd_ppo_cost cost, float* __restrict__ work) {
+                                                                    const pgd_ppo_cost cost, float* __restrict__ work, const ObsNorm nm) {
   const int y = (int)blockIdx.y;
   const pgd_actor_critic& a = nets.ac;
   const pgd_value_net& c = nets.c;
-  ppo_rows_tile(y != 0, y == 0 ? a.w1 : (y == 1 ? a.vw1 : c.w1), y == 0 ? a.b1 : (y == 1 ? a.vb1 : c.b1), y == 0 ? a.w2 : (y == 1 ? a.vw2 : c.w2),
+  ppo_rows_tile<NORM>(y != 0, y == 0 ? a.w1 : (y == 1 ? a.vw1 : c.w1), y == 0 ? a.b1 : (y == 1 ? a.vb1 : c.b1), y == 0 ? a.w2 : (y == 1 ? a.vw2 : c.w2),
                 y == 0 ? a.b2 : (y == 1 ? a.vb2 : c.b2), y == 0 ? a.w3 : (y == 1 ? a.vw3 : c.w3), y == 0 ? a.b3 : (y == 1 ? a.vb3 : c.b3),
-                a.out_cols, y == 2 ? cost.cost_ret : b.ret, y == 2 ? cost.cvf_coef : hp.vf_coef, y == 2 ? 2 : 0, b, hp, work);
+                a.out_cols, y == 2 ? cost.cost_ret : b.ret, y == 2 ? cost.cvf_coef : hp.vf_coef, y == 2 ? 2 : 0, b, hp, work, nm);
 }
 
 __global__ __launch_bounds__(MLP_H) void k_ppo_reduce_cost(const pgd_ppo_batch b, const SafeGrads gr, const int out_cols,
@@ -207,9 +209,17 @@ static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd
   const int n_nets = cost_net ? 3 : (critic ? 2 : 1), out_cols = (int)nets->out_cols;
   const PpoWork wk = ppo_work(b.in_dim, b.rows, n_nets);
   if (work_bytes < sizeof(float) * wk.total) return PGD_ERR_ARG;
+  // the observation binding of the family (pgd_obs_norm_bind), resolved here for both entry points: the NORM instantiations of the two
+  // launches that read observation rows
+  const bool bound = h->obs_norm.table != nullptr;
+  if (bound && b.in_dim != h->obs_norm.in_dim) return PGD_ERR_ARG;
+  const ObsNorm nm = {h->obs_norm.table, h->obs_norm.clip};
+  const auto rows_cost = bound ? k_ppo_rows_cost<true> : k_ppo_rows_cost<false>;
+  const auto rows_plain = bound ? k_ppo_rows<true> : k_ppo_rows<false>;
+  const auto wgrad = bound ? k_ppo_wgrad<true> : k_ppo_wgrad<false>;
   HIPCHK(hipSetDevice(h->device));
-  { int rc = cost_net ? raise_lds_limit(h, LDS_PPO_ROWS_COST, reinterpret_cast<const void*>(k_ppo_rows_cost), lds)
-                      : raise_lds_limit(h, LDS_PPO_ROWS, reinterpret_cast<const void*>(k_ppo_rows), lds);
+  { int rc = cost_net ? raise_lds_limit(h, lds_slot(LDS_PPO_ROWS_COST, bound), reinterpret_cast<const void*>(rows_cost), lds)
+                      : raise_lds_limit(h, lds_slot(LDS_PPO_ROWS, bound), reinterpret_cast<const void*>(rows_plain), lds);
     if (rc) return rc; }
   float* work = static_cast<float*>(d_work);
   hipStream_t s = h->stream;
@@ -217,12 +227,12 @@ static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd
   if (cost_net) {
     const SafeNets sn = {*nets, *cost_net};
     hipLaunchKernelGGL(k_ppo_prep_cost, prep, dim3(MLP_H), 0, s, sn, work);
-    hipLaunchKernelGGL(k_ppo_rows_cost, rows, tile, lds, s, sn, b, *hyper, *cost, work);
+    hipLaunchKernelGGL(rows_cost, rows, tile, lds, s, sn, b, *hyper, *cost, work, nm);
   } else {
     hipLaunchKernelGGL(k_ppo_prep, prep, dim3(MLP_H), 0, s, *nets, work);
-    hipLaunchKernelGGL(k_ppo_rows, rows, tile, lds, s, *nets, b, *hyper, work);
+    hipLaunchKernelGGL(rows_plain, rows, tile, lds, s, *nets, b, *hyper, work, nm);
   }
-  hipLaunchKernelGGL(k_ppo_wgrad, dim3(wk.mt, wk.P, n_nets), tile, 0, s, b, work);
+  hipLaunchKernelGGL(wgrad, dim3(wk.mt, wk.P, n_nets), tile, 0, s, b, work, nm);
   if (cost_net) {
     const SafeGrads sg = {*grads, *cost_grads};
     hipLaunchKernelGGL(k_ppo_reduce_cost, reduce, dim3(MLP_H), 0, s, b, sg, out_cols, work);
@@ -245,10 +255,10 @@ int pgd_mlp_actor_critic_cost(pgd_handle h, int group, const float* d_obs, int o
   bool critic;
   if (!h || !d_obs || !cost_net || !d_actions || !d_logp || !d_value || !d_cost_value || (flags & ~PGD_AC_DETERMINISTIC) != 0u ||
       !nets_ok(nets, cost_net, false, in_dim, obs_stride, &critic) || ac_lds_bytes(in_dim) > 65536) return PGD_ERR_ARG;
-  return ac_forward(h, group, LDS_AC_COST, reinterpret_cast<const void*>(k_mlp_actor_critic_cost), in_dim, [&](const AcRows& r) {
+  return ac_forward(h, group, LDS_AC_COST, k_mlp_actor_critic_cost<false>, k_mlp_actor_critic_cost<true>, in_dim, [&](const AcRows& r, auto kern) {
     const SafeNets sn = {*nets, *cost_net};
-    hipLaunchKernelGGL(k_mlp_actor_critic_cost, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, 3), dim3(WAVE * MLP_WAVES), r.lds, r.stream, d_obs, r.row0,
-                       r.rows, obs_stride, in_dim, sn, seed, tick, h->ac_tick, r.row_base, flags, d_actions, d_logp, d_value, d_cost_value);
+    hipLaunchKernelGGL(kern, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, 3), dim3(WAVE * MLP_WAVES), r.lds, r.stream, d_obs, r.row0,
+                       r.rows, obs_stride, in_dim, sn, seed, tick, h->ac_tick, r.row_base, flags, d_actions, d_logp, d_value, d_cost_value, r.nm);
   });
 }
 

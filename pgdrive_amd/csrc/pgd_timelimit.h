@@ -28,16 +28,20 @@ struct TlNets { pgd_value_net v, c; };
 
 // ac_load_rows with a mask: bit r of `mask` set: row row0 + r0 + r of `obs` into row r of the X tile, else zeros (the first form loads
 // the tile's first row in their place and selects the zero: a row that is not truncated is never USED)
+template <bool NORM>
 DEV void tl_load_rows(const float* obs, const int row0, const int r0, const uint32_t mask, const int obs_stride, const int in_dim, const int kp,
-                      const int xs, const int wave, const int lane, float* X) {
+                      const int xs, const int wave, const int lane, float* X, const ObsNorm nm) {
   constexpr int XCH = 5;
   if (kp <= WAVE * XCH) {
-    float v[MLP_ROWS / MLP_WAVES][XCH];
+    float v[MLP_ROWS / MLP_WAVES][XCH], sh[XCH], sc[XCH];
+    bool live[MLP_ROWS / MLP_WAVES];
+    if (NORM) on_lane_table(nm, in_dim, kp, lane, sh, sc);
 #pragma unroll
     for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i) {
       const int r = wave + i * MLP_WAVES;
       const bool row_in = ((mask >> r) & 1u) != 0u;
       const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
+      live[i] = row_in;
 #pragma unroll
       for (int j = 0; j < XCH; ++j) {
         const int k = lane + WAVE * j;
@@ -50,23 +54,28 @@ DEV void tl_load_rows(const float* obs, const int row0, const int r0, const uint
 #pragma unroll
       for (int j = 0; j < XCH; ++j) {
         const int k = lane + WAVE * j;
+        if (NORM) v[i][j] = (live[i] && k < in_dim) ? on_apply(v[i][j], sh[j], sc[j], nm.clip) : 0.0f;
         if (k < kp) X[(wave + i * MLP_WAVES) * xs + k] = v[i][j];
       }
   } else
   for (int r = wave; r < MLP_ROWS; r += MLP_WAVES) {
     const bool row_in = ((mask >> r) & 1u) != 0u;
     const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
-    for (int k = lane; k < kp; k += WAVE) X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
+    for (int k = lane; k < kp; k += WAVE) {
+      if (NORM) X[r * xs + k] = (row_in && k < in_dim) ? on_apply(src[k], nm.table[k], nm.table[kp + k], nm.clip) : 0.0f;
+      else X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
+    }
   }
 }
 
 // rows [row0, row0 + n_rows) of `obs`, `flags`, `done` -> term_value[row] (blockIdx.y == 0) and term_cost_value[row] (blockIdx.y == 1):
 // the network's value of a truncated row, 0 for every other
+template <bool NORM>
 __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_terminal_value(const float* __restrict__ obs, const int row0, const int n_rows,
                                                                          const int obs_stride, const int in_dim, const TlNets nets,
                                                                          const int safe_rl_env, const uint32_t* __restrict__ flags,
                                                                          const uint8_t* __restrict__ done, float* __restrict__ term_value,
-                                                                         float* __restrict__ term_cost_value) {
+                                                                         float* __restrict__ term_cost_value, const ObsNorm nm) {
   extern __shared__ float mlp_lds[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r0 = (int)blockIdx.x * MLP_ROWS;  // (relative to row0)
@@ -97,7 +106,7 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_terminal_value(cons
   float* H2 = H1 + MLP_ROWS * MLP_HS;
   float* W3s = H2 + MLP_ROWS * MLP_HS;  // [4][256], the first 256 used
   const float w3v = W3[tid];
-  tl_load_rows(obs, row0, r0, mask, obs_stride, in_dim, kp, xs, wave, lane, X);
+  tl_load_rows<NORM>(obs, row0, r0, mask, obs_stride, in_dim, kp, xs, wave, lane, X, nm);
   W3s[tid] = w3v;
   __syncthreads();
   const int c0 = wave * 64;
@@ -204,11 +213,11 @@ int pgd_mlp_terminal_value(pgd_handle h, int group, const float* d_term_obs, int
       (cost_critic && !d_term_cost_value) || in_dim < 4 || obs_stride < in_dim || ac_lds_bytes(in_dim) > 65536) return PGD_ERR_ARG;
   if ((((uintptr_t)d_term_obs | (uintptr_t)d_flags | (uintptr_t)d_term_value | (uintptr_t)d_term_cost_value) & 3u) != 0u) return PGD_ERR_ARG;
   if (is_marl(h)) return PGD_ERR_ARG;  // (the cause of a done cannot be read from a multi-agent step's flags alone: pgdrive_hip.h)
-  return ac_forward(h, group, LDS_TERM_VALUE, reinterpret_cast<const void*>(k_mlp_terminal_value), in_dim, [&](const AcRows& r) {
+  return ac_forward(h, group, LDS_TERM_VALUE, k_mlp_terminal_value<false>, k_mlp_terminal_value<true>, in_dim, [&](const AcRows& r, auto kern) {
     const TlNets tn = {*critic, cost_critic ? *cost_critic : *critic};
-    hipLaunchKernelGGL(k_mlp_terminal_value, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, cost_critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream,
+    hipLaunchKernelGGL(kern, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, cost_critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream,
                        d_term_obs, r.row0, r.rows, obs_stride, in_dim, tn, (int)h->d.cfg.safe_rl_env, d_flags, d_done, d_term_value,
-                       d_term_cost_value);
+                       d_term_cost_value, r.nm);
   });
 }
 

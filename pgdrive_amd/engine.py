@@ -69,6 +69,11 @@ _SIGS = {
     "pgd_return_norm_work_bytes": (C.c_size_t, [C.c_int]),
     "pgd_return_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_double, C.c_float, C.c_uint32,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "pgd_obs_norm_work_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "pgd_obs_norm_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_size_t]),
+    "pgd_obs_norm_publish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
+    "pgd_obs_norm_bind": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float]),
     "pgd_rollout_episodes_work_bytes": (C.c_size_t, [C.c_int]),
     "pgd_rollout_episodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32] + [C.c_void_p] * 7 + [C.c_size_t]),
     "pgd_step_lane_keep": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 4),
@@ -811,6 +816,68 @@ class Engine:
                                     float(clip), _abi.RN_FREEZE if freeze else 0, _p(carry), _p(record), _p(out), _p(work),
                                     work.numel() * work.element_size()), "pgd_return_norm")
         return out
+
+    # -- observation normalisation, fused into the training kernels' row loads (include/pgdrive_hip.h states the rule) -------------------
+    def obs_norm_work_bytes(self, in_dim, n_list):
+        """The scratch pgd_obs_norm_update needs for a list of up to `n_list` rows of `in_dim` columns (pgd_obs_norm_work_bytes); 0: the
+        call would refuse them."""
+        return int(self.L.pgd_obs_norm_work_bytes(int(in_dim), int(n_list)))
+
+    def obs_norm_state(self, in_dim=None):
+        """(record, table) as the calls want them before the first fold, on the engine's device: float64 zeros [1 + 2 in_dim] (n, the
+        column means, the column sums of squared deviations) and the identity table float32 [2, (in_dim + 3) & ~3] (shift | scale)."""
+        t = self.torch
+        in_dim = self.D if in_dim is None else int(in_dim)
+        doubles, shape = _abi.obs_norm_layout(in_dim)
+        table = t.zeros(shape, dtype=t.float32, device=self.device)
+        table[1] = 1.0
+        return t.zeros((doubles, ), dtype=t.float64, device=self.device), table
+
+    def obs_norm_update(self, obs, record, index=None, count=None, n_list=None, in_dim=None, work=None):
+        """Fold the first `in_dim` floats (None: the last dimension of `obs`) of every listed row of `obs` [..., stride] (float32 cuda,
+        flattened to rows) into `record` (float64 cuda [1 + 2 in_dim]; pgd_obs_norm_update).  The list as for adv_stats: row index[q] for
+        q < count (`index` None: row q; `count` int32 cuda [1], read on the device, None: n_list; n_list None: every row, or every entry
+        of `index`).  `work`: a cuda tensor of at least obs_norm_work_bytes(in_dim, n_list) bytes, allocated when None.  Two launches,
+        asynchronous on the caller's current stream.  Returns `record`."""
+        t = self.torch
+        assert obs.is_cuda and obs.dtype == t.float32 and obs.is_contiguous()
+        stride = int(obs.shape[-1])
+        in_dim = stride if in_dim is None else int(in_dim)
+        n_rows = obs.numel() // stride
+        n_list = int((index.numel() if index is not None else n_rows) if n_list is None else n_list)
+        assert record.is_cuda and record.dtype == t.float64 and record.is_contiguous() and record.numel() == 1 + 2 * in_dim
+        ip, cp = self._list_args(index, count, n_list)
+        if work is None:
+            work = t.empty(((self.obs_norm_work_bytes(in_dim, n_list) + 7) // 8, ), dtype=t.float64, device=obs.device)
+        assert work.is_cuda and work.is_contiguous()
+        self._follow_stream()
+        _chk(self.L.pgd_obs_norm_update(self.h, _p(obs), stride, in_dim, n_rows, ip, cp, n_list, _p(record), _p(work),
+                                        work.numel() * work.element_size()), "pgd_obs_norm_update")
+        return record
+
+    def obs_norm_publish(self, record, table, eps=1e-8):
+        """`record` -> `table` (float32 cuda [2, Dp]: shift = mean, scale = 1 / sqrt(m2 / n + eps); the identity while the record is
+        empty; pgd_obs_norm_publish).  One small launch, asynchronous.  Returns `table`."""
+        t = self.torch
+        in_dim = (record.numel() - 1) // 2
+        assert record.is_cuda and record.dtype == t.float64 and record.is_contiguous() and record.numel() == 1 + 2 * in_dim
+        assert table.is_cuda and table.dtype == t.float32 and table.is_contiguous() and table.numel() == 2 * ((in_dim + 3) & ~3)
+        self._follow_stream()
+        _chk(self.L.pgd_obs_norm_publish(self.h, _p(record), in_dim, float(eps), _p(table)), "pgd_obs_norm_publish")
+        return table
+
+    def obs_norm_bind(self, table, in_dim=None, clip=10.0):
+        """Bind a table (pgd_obs_norm_bind): every later mlp_actor_critic, mlp_actor_critic_rows, mlp_actor_critic_cost,
+        mlp_terminal_value, ppo_grad and ppo_grad_cost launch feeds its networks clamp((obs - shift) * scale, -clip, clip), read from the
+        table when the launch RUNS; a call of another input width is refused.  None unbinds.  mlp_policy and mlp_policy_prepared ignore
+        the binding.  `in_dim` None: the engine's observation width.  The engine keeps the tensor alive."""
+        if table is None:
+            _chk(self.L.pgd_obs_norm_bind(self.h, None, 0, 0.0), "pgd_obs_norm_bind")
+        else:
+            in_dim = self.D if in_dim is None else int(in_dim)
+            assert table.is_cuda and table.dtype == self.torch.float32 and table.is_contiguous() and table.numel() == 2 * ((in_dim + 3) & ~3)
+            _chk(self.L.pgd_obs_norm_bind(self.h, _p(table), in_dim, float(clip)), "pgd_obs_norm_bind")
+        self._obs_norm_table = table
 
     # -- episode statistics of a rollout (include/pgdrive_hip.h states the rule) ---------------------------------------------------------
     def rollout_episodes_work_bytes(self, rows):

@@ -11,7 +11,9 @@ rows out of the time-major rollout and -- for the multi-agent collector -- a hos
 below, the same update with a cost critic and a Lagrange multiplier.)
 Here: Engine.adv_stats once, then Engine.ppo_grad + Engine.adam for every epoch and minibatch.  Nothing in update() waits for the device
 or reads a device scalar, so one `collect(); update()` can be captured in a HIP graph and replayed: the Adam step number and the tick of
-the rollout's noise live in device memory and advance with every replay.
+the rollout's noise live in device memory and advance with every replay.  A collector built with normalise_obs=True: update() binds the
+collector's table (Engine.obs_norm_bind) before its first ppo_grad and unbinds behind the last adam, so the gradients see the inputs the
+rollout's evaluations saw.
 
 Minibatch j of n takes the list positions j, j + n, j + 2 n, ...: the n minibatches partition the rollout's transitions whatever their
 number is, with no shuffle tensor.  For RolloutCollector the list is every (t, env) row; for MultiAgentRolloutCollector it is
@@ -117,6 +119,9 @@ class PPOLearner:
         eng = self.engine
         index, count = batch.get("index"), batch.get("count")  # (the multi-agent collector's list; None: every row)
         adv, norm = self._advantages(batch, index, count)
+        normalise_obs = getattr(self.collector, "normalise_obs", False)
+        if normalise_obs:  # (the rollout's own table: it moves at the next collect() only)
+            eng.obs_norm_bind(self.collector.obs_norm, self.in_dim, self.collector.clip_obs)
         k = 0
         for _ in range(self.epochs):
             for start, stride, rows in self.plan:
@@ -125,6 +130,8 @@ class PPOLearner:
                 eng.adam(self.params, self.grads, self.m, self.v, self.step, self.lr, betas=self.betas, eps=self.eps,
                          max_grad_norm=self.max_grad_norm)
                 k += 1
+        if normalise_obs:
+            eng.obs_norm_bind(None)
         return self.stats
 
 

@@ -50,6 +50,23 @@ episode_stats_rollout, and ep_returns float32 / ep_lengths int32 [T, ...]: the f
 ended, 0 everywhere else.  episode_summary() reads a record as a dict (one synchronisation), clear_episode_stats() starts the running
 record afresh and keeps the unfinished episodes; state_dict() holds the carries and the running record.  False (the default): no new
 tensor, batch key or engine call.
+
+normalise_obs=True, clip_obs, obs_eps (every collector): the networks are fed clip((obs - mean) / sqrt(var + obs_eps), -clip_obs, clip_obs)
+with the running mean and variance of every observation column -- the norm_obs half of VecNormalize.  No normalised
+copy exists: the collector owns the record (n, means, sums of squared deviations: float64 [1 + 2 D]), the table the kernels read (float32
+[2, Dp]: shift | scale) and the scratch on the device; Engine.obs_norm_bind makes the network launches normalise the rows as they load
+them.  collect() publishes the record into the table first, carries row T into row 0, binds the table around the T steps (the
+terminal-value launch of bootstrap_truncations included), unbinds, and -- unless frozen -- folds obs[:T] into the record with one
+Engine.obs_norm_update behind GAE (the multi-agent collector: the rows of batch["index"] / batch["count"] only, those at which an agent
+acted).  prime() publishes before its evaluation.  So a rollout is collected AND trained on with one table (it changes only at the next
+collect(); PPOLearner.update binds the same table); every observation is folded exactly once, row T as row 0 of the next rollout; and the
+carried row 0 was evaluated under the previous table, exactly as it was evaluated under the previous weights -- it is not evaluated
+again.  Unlike SB3's RunningMeanStd there is no phantom initial count (mean 0, variance 1, count 1e-4): the record starts empty, the
+first rollout runs on raw observations and the statistics are those of the samples alone.  The batch gains obs_norm (the table) and
+obs_norm_record; batch["obs"] stays RAW.  freeze_obs_norm(True) stops the record from moving, for evaluation rollouts; state_dict() holds
+obs_norm_record (the table is republished by the next collect() / prime()).  Not served: the policy-only kernels (Engine.mlp_policy
+ignores the binding), statistics exchanged between the ranks of a multi-GPU run, image observations.  False (the default): no new
+tensor, batch key or engine call.
 """
 import numpy as np
 
@@ -121,6 +138,44 @@ class _Collector:
         return self.engine.return_norm(self.rewards, self.dones, self.gamma, self._rn_carry, self.return_norm, flags=flags, eps=self.reward_eps,
                                        clip=self.clip_reward, freeze=self._rn_frozen, out=self.scaled_rewards, work=self._rn_work)
 
+    def _obs_norm(self, normalise_obs, clip_obs, obs_eps):
+        """The observation side of VecNormalize (behind _allocate): switched on, the collector owns the record, the table and the
+        scratch of the fold, and the batch gains obs_norm and obs_norm_record."""
+        self.normalise_obs, self.clip_obs, self.obs_eps = bool(normalise_obs), float(clip_obs), float(obs_eps)
+        self._on_frozen = False
+        if not self.normalise_obs:
+            return
+        eng, t, name = self.engine, self.engine.torch, type(self).__name__
+        if not (self.clip_obs > 0.0 and self.obs_eps >= 0.0):
+            raise ValueError("%s: clip_obs = %r, obs_eps = %r" % (name, clip_obs, obs_eps))
+        need = eng.obs_norm_work_bytes(eng.D, self.rewards.numel())
+        if need == 0:
+            raise ValueError("%s: the observation width %d is outside what pgd_obs_norm_update accepts" % (name, eng.D))
+        self.obs_norm_record, self.obs_norm = eng.obs_norm_state(eng.D)
+        self._on_work = t.empty(((need + 7) // 8, ), dtype=t.float64, device=eng.device)
+        self.batch.update(obs_norm=self.obs_norm, obs_norm_record=self.obs_norm_record)
+
+    def _publish_obs_norm(self):
+        """The record, as the last fold left it, into the table: in front of everything prime() / collect() evaluates."""
+        if self.normalise_obs:
+            self.engine.obs_norm_publish(self.obs_norm_record, self.obs_norm, eps=self.obs_eps)
+
+    def _bind_obs_norm(self, bound):
+        """The table bound around the network launches of prime() / collect(), as the tick counter is."""
+        if self.normalise_obs:
+            self.engine.obs_norm_bind(self.obs_norm if bound else None, self.engine.D, self.clip_obs)
+
+    def _fold_obs(self, index=None, count=None):
+        """The one fold of normalise_obs (the end of _finish()): obs[:T] into the record, every row or the listed ones."""
+        if self.normalise_obs and not self._on_frozen:
+            self.engine.obs_norm_update(self._obs[:self.T], self.obs_norm_record, index=index, count=count, n_list=self.rewards.numel(),
+                                        work=self._on_work)
+
+    def freeze_obs_norm(self, frozen=True):
+        """Evaluation rollouts: from the next collect() on the record of normalise_obs is read and not written (True), or moves again
+        (False).  Call it between two collect() calls; a captured collect() keeps the mode it was captured with."""
+        self._on_frozen = bool(frozen)
+
     def _episodes(self, episode_stats, seats=False):
         """The episode statistics (behind _normalise): switched on, the collector owns the carries, the two records, the scratch and
         ep_returns / ep_lengths, and the batch gains episode_stats, episode_stats_rollout, ep_returns and ep_lengths."""
@@ -180,9 +235,10 @@ class _Collector:
         """Host copies of what the collector carries from rollout to rollout beside the engine's state, for a checkpoint.
         normalise_rewards: return_norm_carry (float32, one entry per row) and return_norm (float64 [4]: count, mean, m2, scale).
         episode_stats: episode_return_carry (float32) and episode_length_carry (int32), one entry per row, and episode_stats (the running
-        record, float64 [16]).  Empty with both switches off.  Waits for the device: call it outside collect() and outside a graph
+        record, float64 [16]).  normalise_obs: obs_norm_record (float64 [1 + 2 D]; the table is republished from it by the next
+        collect() / prime()).  Empty with every switch off.  Waits for the device: call it outside collect() and outside a graph
         capture."""
-        if not (self.normalise_rewards or self.episode_stats):
+        if not (self.normalise_rewards or self.episode_stats or self.normalise_obs):
             return {}
         self.engine.sync()
         host = lambda x: x.cpu().numpy().copy()
@@ -192,6 +248,8 @@ class _Collector:
         if self.episode_stats:
             state.update(episode_return_carry=host(self._ep_ret_carry), episode_length_carry=host(self._ep_len_carry),
                          episode_stats=host(self.episode_record))
+        if self.normalise_obs:
+            state.update(obs_norm_record=host(self.obs_norm_record))
         return state
 
     def load_state_dict(self, state):
@@ -201,6 +259,8 @@ class _Collector:
             raise ValueError("%s: a reward normalisation state for a collector built with normalise_rewards=False" % name)
         if not self.episode_stats and any(k in state for k in ("episode_return_carry", "episode_length_carry", "episode_stats")):
             raise ValueError("%s: an episode statistics state for a collector built with episode_stats=False" % name)
+        if not self.normalise_obs and "obs_norm_record" in state:
+            raise ValueError("%s: an observation normalisation state for a collector built with normalise_obs=False" % name)
         if self.normalise_rewards:
             carry = np.ascontiguousarray(state["return_norm_carry"], dtype=np.float32).reshape(-1)
             record = np.ascontiguousarray(state["return_norm"], dtype=np.float64).reshape(-1)
@@ -217,6 +277,12 @@ class _Collector:
             self._ep_ret_carry.copy_(t.from_numpy(ret))
             self._ep_len_carry.copy_(t.from_numpy(length))
             self.episode_record.copy_(t.from_numpy(record))
+        if self.normalise_obs:
+            record = np.ascontiguousarray(state["obs_norm_record"], dtype=np.float64).reshape(-1)
+            if record.size != self.obs_norm_record.numel():
+                raise ValueError("%s: a state of %d observation columns for a collector of %d" %
+                                 (name, (record.size - 1) // 2, self.engine.D))
+            self.obs_norm_record.copy_(t.from_numpy(record))
 
     def _stepped(self, t):
         pass
@@ -228,7 +294,10 @@ class _Collector:
         self._obs[T].copy_(eng.obs.view(self._obs[T].shape))
         self._tick.sub_(T)  # (this evaluation is number 0: row T, counter -T)
         eng.actor_critic_tick(self._tick)
+        self._publish_obs_norm()
+        self._bind_obs_norm(True)
         self._evaluate(T)
+        self._bind_obs_norm(False)
         eng.actor_critic_tick(None)
         self._tick.add_(T)
         self._primed = True
@@ -240,13 +309,16 @@ class _Collector:
         eng, T = self.engine, self.T
         if not self._primed:
             self.prime()
+        self._publish_obs_norm()  # (this rollout's table, and the update's behind it)
         for buf in self._carry:
             buf[0].copy_(buf[T])
         eng.actor_critic_tick(self._tick)  # (the engine's launches add the counter only while the collector is at work)
+        self._bind_obs_norm(True)
         for t in range(T):
             eng.step(self._actions[t], out=(self._obs[t + 1], self.rewards[t], self.dones[t], self.flags[t]))
             self._stepped(t)
             self._evaluate(t + 1)
+        self._bind_obs_norm(False)
         eng.actor_critic_tick(None)
         self._finish()
         self._tick.add_(T)
@@ -262,9 +334,13 @@ class RolloutCollector(_Collector):
     normalise_rewards=True, clip_reward, reward_eps: GAE reads the rewards scaled by the running return (the module's docstring); the
     batch gains scaled_rewards [T, N] and return_norm (float64 [4]).
     episode_stats=True: the statistics of the episodes that finished (the module's docstring); the batch gains episode_stats,
-    episode_stats_rollout (float64 [16]), ep_returns and ep_lengths [T, N]."""
+    episode_stats_rollout (float64 [16]), ep_returns and ep_lengths [T, N].
+    normalise_obs=True, clip_obs, obs_eps: the networks (the terminal-value launch included) read the observations normalised by their
+    running mean and variance (the module's docstring); the batch gains obs_norm (float32 [2, Dp]) and obs_norm_record (float64
+    [1 + 2 D]); `obs` stays raw."""
     def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, bootstrap_truncations=False,
-                 normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8, episode_stats=False):
+                 normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8, episode_stats=False, normalise_obs=False, clip_obs=10.0,
+                 obs_eps=1e-8):
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A != 1:
             raise NotImplementedError(
@@ -282,6 +358,7 @@ class RolloutCollector(_Collector):
         self._allocate(eng, (eng.N, ), policy_weights, value_weights, T, gamma, lam, seed)
         self._normalise(normalise_rewards, clip_reward, reward_eps)
         self._episodes(episode_stats)
+        self._obs_norm(normalise_obs, clip_obs, obs_eps)
         if self.bootstrap_truncations:
             self.term_values = eng.torch.zeros((self.T, eng.N), dtype=eng.torch.float32, device=eng.device)
             self.batch.update(term_values=self.term_values)
@@ -308,6 +385,7 @@ class RolloutCollector(_Collector):
                                       ret=self.returns)
         else:
             self.engine.gae(rewards, self.values, self.dones, self.gamma, self.lam, adv=self.advantages, ret=self.returns)
+        self._fold_obs()
 
 
 class SafeRolloutCollector(RolloutCollector):
@@ -334,11 +412,11 @@ class SafeRolloutCollector(RolloutCollector):
     books of episode costs are unchanged: a truncated episode still finishes for them."""
     def __init__(self, env_or_engine, policy_weights, value_weights, cost_weights, T, costs=None, gamma=0.99, lam=0.95, cost_gamma=0.99,
                  cost_lam=0.95, seed=0, bootstrap_truncations=False, normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8,
-                 episode_stats=False):
+                 episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8):
         self.cost_weights = tuple(cost_weights)
         super().__init__(env_or_engine, policy_weights, value_weights, T, gamma=gamma, lam=lam, seed=seed,
                          bootstrap_truncations=bootstrap_truncations, normalise_rewards=normalise_rewards, clip_reward=clip_reward,
-                         reward_eps=reward_eps, episode_stats=episode_stats)
+                         reward_eps=reward_eps, episode_stats=episode_stats, normalise_obs=normalise_obs, clip_obs=clip_obs, obs_eps=obs_eps)
         eng = self.engine
         t = eng.torch
         if costs is None:
@@ -415,9 +493,12 @@ class MultiAgentRolloutCollector(_Collector):
     (pgd_forget_rows) never carry over: every step of a rollout writes the zero row of every seat that is not due.
 
     episode_stats=True: the statistics of the agents' episodes, per seat (the module's docstring); cut_rate of episode_summary() is the
-    share of the agents an env-wide restart took out."""
+    share of the agents an env-wide restart took out.
+
+    normalise_obs=True: as for RolloutCollector (the module's docstring); the fold takes the rows of `index` / `count` only, those at
+    which an agent acted -- the zero rows of seats that are not due are no samples."""
     def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, normalise_rewards=False, clip_reward=10.0,
-                 reward_eps=1e-8, episode_stats=False):
+                 reward_eps=1e-8, episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8):
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A == 1:
             raise NotImplementedError("MultiAgentRolloutCollector serves multi-agent engines: this one has a single agent seat per env and "
@@ -427,6 +508,7 @@ class MultiAgentRolloutCollector(_Collector):
         self._allocate(eng, (eng.N, eng.A), policy_weights, value_weights, T, gamma, lam, seed)
         self._normalise(normalise_rewards, clip_reward, reward_eps)
         self._episodes(episode_stats, seats=True)
+        self._obs_norm(normalise_obs, clip_obs, obs_eps)
         t = eng.torch
         i32 = dict(dtype=t.int32, device=eng.device)
         self.mask = t.zeros(self.flags.shape, dtype=t.uint8, device=eng.device)
@@ -448,6 +530,7 @@ class MultiAgentRolloutCollector(_Collector):
         self.engine.gae_masked(self._gae_rewards(flags=self.flags), self.values, self.dones, self.flags, self.gamma, self.lam, adv=self.advantages,
                                ret=self.returns, mask=self.mask)
         self.engine.rollout_index(self.flags, index=self.index, count=self.count)
+        self._fold_obs(self.index, self.count)
 
     def prime(self):
         """Take the engine's present observation (what reset wrote into Engine.obs) as the start of the first rollout; its live seats
