@@ -688,6 +688,61 @@ int pgd_cost_gae_bootstrap(pgd_handle h, const uint32_t* d_flags /*[T][rows]*/, 
                            const float* d_term_cost_value /*[T][rows]*/, int T, int rows, const float costs[3], float gamma, float lam,
                            float* d_cost /*[T][rows]*/, float* d_cadv, float* d_cret, float* d_run /*[rows], in/out*/,
                            float* d_ep_sum /*[rows]*/, int32_t* d_ep_count /*[rows]*/);
+/* ---- The expert guardian: use_saver / save_level on the device (single-agent engines) ----------------------------------------------------
+ * pgdrive/policy/AI_protect_policy.py:8-59: a second policy, the expert, watches the acting policy and replaces its action where the
+ * car is about to leave the road or to hit something; the step info carries takeover_start / takeover_end / takeover
+ * (agent_manager.py:187).  pgd_guardian is ONE launch between the evaluation of the acting policy and the step: it reads the engine's
+ * state and the observation rows the last step or reset wrote, evaluates the expert, and writes the action buffer the step is to read.
+ * Rows = the envs of a single-agent engine (`group` as for pgd_mlp_actor_critic).
+ *
+ * d_obs / obs_stride: the observation rows ([rows][obs_stride], the first D = pgd_obs_dim floats are the row).  A table bound with
+ * pgd_obs_norm_bind is IGNORED: the expert was trained on raw observations.
+ * expert: the expert's six policy tensors, the value network's six pointers null; layout, alignment and head as pgd_mlp_actor_critic.
+ * cfg->expert_in_dim (4 .. 416): D, or D + 1 with PGD_GUARD_LEGACY_LATERAL.  With that bit the expert's row is
+ *   obs[0..7] | clip((lat * 2 / 4.5 + 1) / 2, 0, 1) | obs[8..]       lat = the lateral coordinate of the vehicle's position on its
+ * current lane (SI_LANE) -- the float the reference's shipped weights were trained with (state_obs.py:97-100, commented out upstream).
+ * The expert's head is pgd_mlp_actor_critic's bit for bit: same key stream, g = env_base + env, cfg->tick plus the device counter of
+ * pgd_actor_critic_tick; PGD_GUARD_DETERMINISTIC: z = 0.  The reference samples (`expert(obs, deterministic=False)`): the default.
+ *
+ * The rule, per row, fp32 (no contraction, no re-association); a = d_agent_actions[row] (raw, unclipped), e = the expert's sample,
+ * s = cfg->save_level, n = num_lasers, lidar[] = the last n floats of the obs row:
+ *   steer = a0, thr = a1
+ *   s > 0.9:   steer = e0, thr = e1
+ *   s > 1e-3:  hd = heading_diff(vehicle.lane) - 0.5;  v = speed [km/h];  f = min(1 + |hd| * v * max_speed, 10 s)   (max_speed: the spawn
+ *              record's; the product from left to right, as upstream)
+ *              out of road:  (obs0 < 0.04 f and hd < 0) or (obs1 < 0.04 f and hd > 0) or obs0 <= 1e-3 or obs1 <= 1e-3:
+ *                            steer = e0, thr = e1, and thr = 0.5 where v < 5
+ *              side:         L = n / 4, R = 3 n / 4 (integers);  min lidar[L - 4 .. L + 5] < (s + 0.1) / 10 or the same around R: steer = e0
+ *              front:        a1 >= 0 and e1 <= 0 and min(lidar[0..9], lidar[n - 10..n - 1]) < s:  thr = e1
+ *   pre = d_state[row] != 0, and 0 where d_prev_flags[row] has PGD_F_RESET (the vehicle was reset: base_vehicle.py:332)
+ *   now = (a0 != steer or a1 != thr), compared as floats;   d_state[row] = now
+ *   takeover_start = !pre & now,  takeover_end = pre & !now,  takeover = pre & now
+ *   d_applied[row] = takeover ? (steer, thr) : a         -- the reference applies the correction from the second consecutive step on
+ *   PGD_GUARD_IMMEDIATE (NOT a reference behaviour): d_applied[row] = now ? (steer, thr) : a; the info bits are unchanged.
+ * The regimes compare s as a double; 10 s and (s + 0.1) / 10 are formed in double from the fp32 s and rounded to fp32 once; 0.04, 1e-3
+ * and 5 are fp32 constants and 0.04 f is an fp32 product: a float64 checker that rounds the same way agrees exactly.  s <= 1e-3 still runs
+ * the bookkeeping: now is false everywhere and d_applied = a.  The fan is the obs row's (the reference reads the un-noised cloud points,
+ * which this engine does not keep: callers refuse lidar noise together with the guardian).
+ *
+ * d_state [rows] uint8, in / out, the caller's: vehicle.takeover.  d_prev_flags [rows]: the flags of the previous step, or null.
+ * d_info [rows] uint8: bit 0 takeover, bit 1 takeover_start, bit 2 takeover_end.  d_applied [rows][2] MAY alias d_agent_actions: a
+ * row's action is read before anything of the row is written, and no row reads another's.  d_trace [rows][4] or null: the expert's
+ * steering and throttle, the lateral float (0 without PGD_GUARD_LEGACY_LATERAL) and f.
+ * Refusals (PGD_ERR_ARG): a multi-agent engine, num_lasers < 40 (the reference's slices need it), expert_in_dim other than D (+ 1), a
+ * value network in `expert`, unknown mode bits, d_agent_actions / d_applied not 8-byte and d_trace not 16-byte aligned; PGD_ERR_STATE
+ * before maps and scenarios are uploaded.  One launch, grid ceil(rows / 16), the workgroup and LDS of pgd_mlp_actor_critic's actor;
+ * asynchronous on the engine's stream (group >= 0: the group's), allocates nothing, capturable in a HIP graph from its first call. */
+typedef struct pgd_guardian_config {
+  int32_t expert_in_dim;
+  float save_level;
+  uint32_t seed, tick, mode;
+} pgd_guardian_config;
+#define PGD_GUARD_LEGACY_LATERAL 1u
+#define PGD_GUARD_DETERMINISTIC 2u
+#define PGD_GUARD_IMMEDIATE 4u
+int pgd_guardian(pgd_handle h, int group, const float* d_obs, int obs_stride, const pgd_actor_critic* expert, const pgd_guardian_config* cfg,
+                 const float* d_agent_actions /*[rows][2]*/, const uint32_t* d_prev_flags /*[rows] or null*/, uint8_t* d_state /*[rows]*/,
+                 float* d_applied /*[rows][2]*/, uint8_t* d_info /*[rows]*/, float* d_trace /*[rows][4] or null*/);
 /* ---- Reward scaling by the running return, in front of GAE (every engine) ---------------------------------------------------------------
  * (No reference counterpart: the reference hands its rewards to an RL library; this is the norm_reward half of Stable-Baselines3's
  * VecNormalize -- the reward divided by the standard deviation of the running discounted return -- as one call over a rollout.)

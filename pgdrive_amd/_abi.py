@@ -51,6 +51,16 @@ class ActorCritic(C.Structure):
 AC_DETERMINISTIC = 1
 
 
+class GuardianConfig(C.Structure):
+    """pgd_guardian_config: the expert's input width, save_level, the noise's seed and tick, the PGD_GUARD_* mode bits."""
+    _fields_ = [("expert_in_dim", C.c_int32), ("save_level", C.c_float), ("seed", C.c_uint32), ("tick", C.c_uint32), ("mode", C.c_uint32)]
+
+
+GUARD_LEGACY_LATERAL, GUARD_DETERMINISTIC, GUARD_IMMEDIATE = 1, 2, 4  # PGD_GUARD_*, mode bits of pgd_guardian
+GUARD_TAKEOVER, GUARD_TAKEOVER_START, GUARD_TAKEOVER_END = 1, 2, 4  # the bits of pgd_guardian's d_info
+GUARD_MIN_LASERS = 40  # the reference's lidar slices need forty beams
+
+
 class PPOBatch(C.Structure):
     """pgd_ppo_batch: the rollout's arrays by row, the row list (index / count null: position = row, n_list entries) and the minibatch
     (start, stride, rows)."""

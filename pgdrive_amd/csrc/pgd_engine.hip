@@ -41,7 +41,7 @@ static Switches read_switches() {
 // The kernels that take more than 48 KB of dynamic LDS at wide inputs: their limit is raised once per engine (raise_lds_limit)
 // (LDS_AC .. LDS_TERM_VALUE: the instantiations that normalise their observation rows, pgd_obs_norm_bind, have slots of their own behind them)
 enum LdsKernel { LDS_MLP, LDS_MLP_TANH, LDS_MLP_BF, LDS_MLP_BF_TANH, LDS_AC, LDS_AC_ROWS, LDS_AC_COST, LDS_PPO_ROWS, LDS_PPO_ROWS_COST, LDS_TERM_VALUE,
-                 LDS_NORM_FIRST, LDS_KERNELS = LDS_NORM_FIRST + (LDS_TERM_VALUE - LDS_AC + 1) };
+                 LDS_NORM_FIRST, LDS_GUARD = LDS_NORM_FIRST + (LDS_TERM_VALUE - LDS_AC + 1), LDS_GUARD_LEGACY, LDS_KERNELS };
 struct pgd_engine {
   PgdDev d;
   Switches sw;
@@ -1417,6 +1417,7 @@ int pgd_destroy(pgd_handle h) {
 #include "pgd_ppo.h"
 #include "pgd_safe.h"
 #include "pgd_timelimit.h"
+#include "pgd_guardian.h"
 #include "pgd_return_norm.h"
 #include "pgd_obs_norm.h"
 #include "pgd_rollout_episodes.h"

@@ -62,6 +62,8 @@ _SIGS = {
                                     C.c_void_p, C.c_void_p, C.c_size_t]),
     "pgd_mlp_terminal_value": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ValueNet), C.POINTER(_abi.ValueNet),
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgd_guardian": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.GuardianConfig)] +
+                     [C.c_void_p] * 6),
     "pgd_gae_bootstrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                     C.c_void_p]),
     "pgd_cost_gae_bootstrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float,
@@ -462,6 +464,43 @@ class Engine:
                           deterministic, in_dim)
         _chk(self.L.pgd_mlp_actor_critic(*a, _p(out), _p(logp), _p(value) if value_weights is not None else None), "pgd_mlp_actor_critic")
         return out, logp, value
+
+    def guardian(self, expert_weights, save_level, actions, state, applied, info, seed, tick, prev_flags=None, trace=None, obs=None, group=-1,
+                 deterministic=False, immediate=False):
+        """The expert guardian in one launch (pgd_guardian; the reference's use_saver / save_level, policy/AI_protect_policy.py), single-agent
+        engines: the expert `expert_weights` -- six policy tensors as for mlp_actor_critic, w1 with D rows, or with D + 1 rows for the
+        reference's shipped weights (the lateral float is then built by the kernel) -- is evaluated on the observation rows and replaces
+        the agent's `actions` [N, 1, 2] where the rule says so.  `state` [N] uint8, in / out: vehicle.takeover; `prev_flags` [N, 1] int32:
+        the flags of the previous step, or None; `applied` [N, 1, 2]: what the step is to read (may be `actions` itself); `info` [N] uint8:
+        bit 0 takeover, 1 takeover_start, 2 takeover_end; `trace` [N, 4] or None: expert steering, throttle, lateral float, f.  The expert
+        samples with (seed, global row, tick + the device counter of actor_critic_tick) unless `deterministic`; `immediate` (not a
+        reference behaviour) applies a correction in the step that raises it.  A bound observation normalisation is ignored."""
+        t = self.torch
+        assert self.A == 1, "the guardian serves single-agent engines"
+        o = self.obs if obs is None else obs
+        o2 = o.view(-1, o.shape[-1])
+        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == self.N and o2.shape[1] >= self.D
+        self._check_actions(actions)
+        self._check_actions(applied)
+        for v in (state, info):
+            assert v.is_cuda and v.dtype == t.uint8 and v.is_contiguous() and v.numel() == self.N
+        if prev_flags is not None:
+            assert prev_flags.is_cuda and prev_flags.dtype == t.int32 and prev_flags.is_contiguous() and prev_flags.numel() == self.N
+        if trace is not None:
+            assert trace.is_cuda and trace.dtype == t.float32 and trace.is_contiguous() and trace.numel() == 4 * self.N
+        k = int(expert_weights[0].shape[0])
+        assert k in (self.D, self.D + 1), "the expert takes %d inputs (or %d with the lateral float), not %d" % (self.D, self.D + 1, k)
+        nets = self._nets(_abi.ActorCritic(), expert_weights, None, k)
+        nets.out_cols = int(expert_weights[4].shape[1])
+        mode = (_abi.GUARD_LEGACY_LATERAL if k == self.D + 1 else 0) | (_abi.GUARD_DETERMINISTIC if deterministic else 0) | \
+            (_abi.GUARD_IMMEDIATE if immediate else 0)
+        cfg = _abi.GuardianConfig(k, float(save_level), int(seed) & 0xffffffff, int(tick) & 0xffffffff, mode)
+        if group < 0:
+            self._follow_stream()
+        _chk(self.L.pgd_guardian(self.h, int(group), _p(o2), int(o2.stride(0)), C.byref(nets), C.byref(cfg), _p(actions),
+                                 _p(prev_flags) if prev_flags is not None else None, _p(state), _p(applied), _p(info),
+                                 _p(trace) if trace is not None else None), "pgd_guardian")
+        return applied, info
 
     def actor_critic_tick(self, counter):
         """Give the engine a tick counter in device memory (pgd_actor_critic_tick): a cuda int32 tensor of one element that every later

@@ -86,6 +86,10 @@ class PGDriveEnv(EnvBase):  # gym.Env when gym is importable (base_env.py:93), e
             episode_length=self.episode_steps, episode_energy=energy, step_energy=energy - self._last_energy,
             raw_action=(float(raw[0]), float(raw[1])), overtake_vehicle_num=0,  # overtake_stat cannot be on (vec_env.py)
         )
+        if self.vec.saver is not None:  # the guardian's step info (AI_protect_policy.py:54-58, agent_manager.py:187)
+            bits = int(self.vec.last_takeover[0].item())
+            info.update(takeover=bool(bits & _abi.GUARD_TAKEOVER), takeover_start=bool(bits & _abi.GUARD_TAKEOVER_START),
+                        takeover_end=bool(bits & _abi.GUARD_TAKEOVER_END))
         self._last_energy = energy
         return obs[0].cpu().numpy(), r, d, info
 

@@ -69,6 +69,10 @@ class MultiAgentRoundaboutVecEnv:
 
     def __init__(self, config=None):
         config = {k: v for k, v in (config or {}).items() if k != "is_multi_agent"}  # always True here (multi_agent_pgdrive.py:14)
+        if config.get("use_saver"):
+            raise NotImplementedError("config['use_saver'] on a multi-agent env: the expert guardian serves single-agent envs only "
+                                      "(pgd_guardian, include/pgdrive_hip.h)")
+        config = {k: v for k, v in config.items() if k not in ("use_saver", "save_level")}
         self.config = c = merge_config(self.DEFAULTS, strip_reference_only_keys(
             config, keep=("num_agents", "allow_respawn", "delay_done")))
         lid = c["vehicle_config"]["lidar"]

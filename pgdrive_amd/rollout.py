@@ -67,8 +67,22 @@ obs_norm_record; batch["obs"] stays RAW.  freeze_obs_norm(True) stops the record
 obs_norm_record (the table is republished by the next collect() / prime()).  Not served: the policy-only kernels (Engine.mlp_policy
 ignores the binding), statistics exchanged between the ranks of a multi-GPU run, image observations.  False (the default): no new
 tensor, batch key or engine call.
+
+guardian=dict(weights=..., save_level=0.5, deterministic=False, immediate=False) (RolloutCollector, SafeRolloutCollector): the expert
+guardian of the reference's use_saver / save_level (policy/AI_protect_policy.py; Engine.guardian) watches the rollout.
+Per step t, behind the evaluation of row t, one more launch reads the sampled action of row t, observation row t and the flags of step
+t - 1 and writes the action the step is to apply into a buffer of its own; the step reads that buffer.  `weights`: the expert's six
+policy tensors (cuda float32), fc_1 with D rows, or with D + 1 rows for the reference's shipped expert.  The expert's noise is drawn with
+seed ^ GUARDIAN_SEED_XOR and the tick of the row's evaluation, so it is not the agent's.  The batch gains applied_actions [T, N, 2],
+takeover uint8 [T, N] (bit 0 takeover, 1 takeover_start, 2 takeover_end) and expert_actions [T, N, 2] (a view of guardian_trace
+[T, N, 4]: expert steering, throttle, lateral float, f).  `actions`, `logp` and `values` stay the agent's OWN -- what it sampled, whatever
+was applied; what a trainer makes of the difference is the trainer's business.  A bound observation normalisation does not reach the
+expert.  The takeover state [N] survives from rollout to rollout and is part of state_dict() (guardian_state).  None (the default): the
+launches and the batch of before.
 """
 import numpy as np
+
+GUARDIAN_SEED_XOR = 0x6a7d1a4b  # the guardian's noise seed = the collector's (the vec env's) seed ^ this: the expert's draws are not the agent's
 
 F_NATURAL = 1 | 2 | 4 | 8 | 16   # PGD_F_ARRIVE | OUT_OF_ROAD | CRASH_VEHICLE | CRASH_OBJECT | CRASH_BUILDING
 F_CRASH_COST = 4 | 8             # PGD_F_CRASH_VEHICLE | CRASH_OBJECT: with safe_rl_env a cost, not a termination
@@ -176,6 +190,46 @@ class _Collector:
         (False).  Call it between two collect() calls; a captured collect() keeps the mode it was captured with."""
         self._on_frozen = bool(frozen)
 
+    def _guardian(self, guardian):
+        """The expert guardian (behind _allocate): switched on, the collector owns the takeover state, the applied actions, the info bits
+        and the trace, and the batch gains applied_actions, takeover, expert_actions and guardian_trace."""
+        self.guardian = None
+        if guardian is None:
+            return
+        eng, t, name = self.engine, self.engine.torch, type(self).__name__
+        g = dict(save_level=0.5, deterministic=False, immediate=False)
+        unknown = set(guardian) - set(g) - {"weights"}
+        if unknown or "weights" not in guardian:
+            raise ValueError("%s: guardian takes weights, save_level, deterministic, immediate (got %s)" % (name, sorted(guardian)))
+        g.update(guardian)
+        g["weights"] = tuple(g["weights"])
+        if eng.cfg.num_lasers < 40 or eng.cfg.lidar_gaussian_noise > 0.0 or eng.cfg.lidar_dropout_prob > 0.0 or eng.cfg.discrete_action or \
+                eng.cfg.idm_agent:
+            raise NotImplementedError("%s: the guardian needs a continuous-action engine with at least 40 lidar beams and no lidar noise "
+                                      "(num_lasers, gaussian_noise / dropout_prob, discrete_action, IDM_agent)" % name)
+        if len(g["weights"]) != 6 or int(g["weights"][0].shape[0]) not in (eng.D, eng.D + 1):
+            raise ValueError("%s: the guardian's expert takes %d inputs (or %d with the lateral float)" % (name, eng.D, eng.D + 1))
+        self.guardian = g
+        T, N, dev = self.T, eng.N, eng.device
+        self.applied_actions = t.zeros((T, N, 2), dtype=t.float32, device=dev)
+        self.takeover = t.zeros((T, N), dtype=t.uint8, device=dev)
+        self.guardian_trace = t.zeros((T, N, 4), dtype=t.float32, device=dev)
+        self._guard_state = t.zeros((N, ), dtype=t.uint8, device=dev)
+        self.batch.update(applied_actions=self.applied_actions, takeover=self.takeover, expert_actions=self.guardian_trace[..., :2],
+                          guardian_trace=self.guardian_trace)
+
+    def _applied(self, t):
+        """The action buffer step t reads: the sampled row, or (guardian) what the guardian makes of it."""
+        if self.guardian is None:
+            return self._actions[t]
+        g, T = self.guardian, self.T
+        # (the flags of step t - 1: at t = 0 row T - 1 still holds the last step of the previous rollout -- zeros before the first)
+        self.engine.guardian(g["weights"], g["save_level"], self._actions[t].view(-1, 1, 2), self._guard_state,
+                             self.applied_actions[t].view(-1, 1, 2), self.takeover[t], self.seed ^ GUARDIAN_SEED_XOR, t,
+                             prev_flags=self.flags[(t - 1) % T], trace=self.guardian_trace[t], obs=self._obs[t],
+                             deterministic=g["deterministic"], immediate=g["immediate"])
+        return self.applied_actions[t]
+
     def _episodes(self, episode_stats, seats=False):
         """The episode statistics (behind _normalise): switched on, the collector owns the carries, the two records, the scratch and
         ep_returns / ep_lengths, and the batch gains episode_stats, episode_stats_rollout, ep_returns and ep_lengths."""
@@ -238,7 +292,7 @@ class _Collector:
         record, float64 [16]).  normalise_obs: obs_norm_record (float64 [1 + 2 D]; the table is republished from it by the next
         collect() / prime()).  Empty with every switch off.  Waits for the device: call it outside collect() and outside a graph
         capture."""
-        if not (self.normalise_rewards or self.episode_stats or self.normalise_obs):
+        if not (self.normalise_rewards or self.episode_stats or self.normalise_obs or self.guardian is not None):
             return {}
         self.engine.sync()
         host = lambda x: x.cpu().numpy().copy()
@@ -250,6 +304,8 @@ class _Collector:
                          episode_stats=host(self.episode_record))
         if self.normalise_obs:
             state.update(obs_norm_record=host(self.obs_norm_record))
+        if self.guardian is not None:  # (with the last flags row: the guardian of the next rollout's first step reads it)
+            state.update(guardian_state=host(self._guard_state), guardian_prev_flags=host(self.flags[self.T - 1]))
         return state
 
     def load_state_dict(self, state):
@@ -261,6 +317,14 @@ class _Collector:
             raise ValueError("%s: an episode statistics state for a collector built with episode_stats=False" % name)
         if not self.normalise_obs and "obs_norm_record" in state:
             raise ValueError("%s: an observation normalisation state for a collector built with normalise_obs=False" % name)
+        if self.guardian is None and "guardian_state" in state:
+            raise ValueError("%s: a guardian state for a collector built with guardian=None" % name)
+        if self.guardian is not None:
+            st = np.ascontiguousarray(state["guardian_state"], dtype=np.uint8).reshape(-1)
+            if st.size != self._guard_state.numel():
+                raise ValueError("%s: a guardian state of %d rows for a collector of %d" % (name, st.size, self._guard_state.numel()))
+            self._guard_state.copy_(t.from_numpy(st))
+            self.flags[self.T - 1].copy_(t.from_numpy(np.ascontiguousarray(state["guardian_prev_flags"], dtype=np.int32).reshape(-1)))
         if self.normalise_rewards:
             carry = np.ascontiguousarray(state["return_norm_carry"], dtype=np.float32).reshape(-1)
             record = np.ascontiguousarray(state["return_norm"], dtype=np.float64).reshape(-1)
@@ -315,7 +379,7 @@ class _Collector:
         eng.actor_critic_tick(self._tick)  # (the engine's launches add the counter only while the collector is at work)
         self._bind_obs_norm(True)
         for t in range(T):
-            eng.step(self._actions[t], out=(self._obs[t + 1], self.rewards[t], self.dones[t], self.flags[t]))
+            eng.step(self._applied(t), out=(self._obs[t + 1], self.rewards[t], self.dones[t], self.flags[t]))
             self._stepped(t)
             self._evaluate(t + 1)
         self._bind_obs_norm(False)
@@ -340,7 +404,7 @@ class RolloutCollector(_Collector):
     [1 + 2 D]); `obs` stays raw."""
     def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, bootstrap_truncations=False,
                  normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8, episode_stats=False, normalise_obs=False, clip_obs=10.0,
-                 obs_eps=1e-8):
+                 obs_eps=1e-8, guardian=None):
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A != 1:
             raise NotImplementedError(
@@ -359,6 +423,7 @@ class RolloutCollector(_Collector):
         self._normalise(normalise_rewards, clip_reward, reward_eps)
         self._episodes(episode_stats)
         self._obs_norm(normalise_obs, clip_obs, obs_eps)
+        self._guardian(guardian)
         if self.bootstrap_truncations:
             self.term_values = eng.torch.zeros((self.T, eng.N), dtype=eng.torch.float32, device=eng.device)
             self.batch.update(term_values=self.term_values)
@@ -412,11 +477,12 @@ class SafeRolloutCollector(RolloutCollector):
     books of episode costs are unchanged: a truncated episode still finishes for them."""
     def __init__(self, env_or_engine, policy_weights, value_weights, cost_weights, T, costs=None, gamma=0.99, lam=0.95, cost_gamma=0.99,
                  cost_lam=0.95, seed=0, bootstrap_truncations=False, normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8,
-                 episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8):
+                 episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8, guardian=None):
         self.cost_weights = tuple(cost_weights)
         super().__init__(env_or_engine, policy_weights, value_weights, T, gamma=gamma, lam=lam, seed=seed,
                          bootstrap_truncations=bootstrap_truncations, normalise_rewards=normalise_rewards, clip_reward=clip_reward,
-                         reward_eps=reward_eps, episode_stats=episode_stats, normalise_obs=normalise_obs, clip_obs=clip_obs, obs_eps=obs_eps)
+                         reward_eps=reward_eps, episode_stats=episode_stats, normalise_obs=normalise_obs, clip_obs=clip_obs, obs_eps=obs_eps,
+                         guardian=guardian)
         eng = self.engine
         t = eng.torch
         if costs is None:
@@ -498,7 +564,10 @@ class MultiAgentRolloutCollector(_Collector):
     normalise_obs=True: as for RolloutCollector (the module's docstring); the fold takes the rows of `index` / `count` only, those at
     which an agent acted -- the zero rows of seats that are not due are no samples."""
     def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, normalise_rewards=False, clip_reward=10.0,
-                 reward_eps=1e-8, episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8):
+                 reward_eps=1e-8, episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8, guardian=None):
+        if guardian is not None:
+            raise NotImplementedError("MultiAgentRolloutCollector: the expert guardian serves single-agent engines only (pgd_guardian)")
+        self.guardian = None
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A == 1:
             raise NotImplementedError("MultiAgentRolloutCollector serves multi-agent engines: this one has a single agent seat per env and "

@@ -79,7 +79,19 @@ DEFAULT_CONFIG = dict(
                       # pgd_step_info) at one more launch per step; step() keeps its 4-tuple
     IDM_agent=False,  # the ego is driven by IDMPolicy along its route, step()'s actions are ignored (base_env.py:30, agent_manager.py:79)
     map_bank=None,  # path of a pre-generated description bank; None -> generate with our BIG (pgdrive_amd/mapgen.py)
+    # the expert guardian (base_env.py:49-50 `use_saver` / `save_level`, policy/AI_protect_policy.py): a second policy watches the actions
+    # handed to step() and takes over where the car is about to leave the road or to hit something -- one more launch in front of the step
+    # (pgd_guardian, include/pgdrive_hip.h)
+    use_saver=False,
+    save_level=0.5,
+    # NOT reference keys: the expert's weights -- the path of an .npz with the reference's key names (default_policy/fc_1/kernel, ...) or
+    # a dict of such arrays; none are shipped --, the mean instead of a sample, and the correction applied in the step that raises it
+    # instead of from the second consecutive step on (the reference's one-step delay)
+    saver_weights=None,
+    saver_deterministic=False,
+    saver_immediate=False,
 )
+SAVER_WEIGHT_KEYS = tuple("default_policy/%s/%s" % (layer, part) for layer in ("fc_1", "fc_2", "fc_out") for part in ("kernel", "bias"))
 
 
 # Reference config keys this engine does not act on (BASE_DEFAULT_CONFIG base_env.py:19-90, PGDriveEnv_DEFAULT_CONFIG
@@ -90,7 +102,7 @@ VISUAL_KEYS = {
     "prefer_track_agent", "draw_map_resolution", "top_down_camera_initial_x", "top_down_camera_initial_y",
     "top_down_camera_initial_z", "window_size", "show_fps", "global_light", "onscreen_message", "debug_physics_world",
     "debug_static_world", "headless_machine_render", "pstats", "max_distance", "_disable_detector_mask",
-    "load_map_from_json", "_load_map_from_json", "save_level",
+    "load_map_from_json", "_load_map_from_json",
     # unused upstream (no reader in the reference's reward function)
     "acceleration_penalty", "low_speed_penalty", "general_penalty",
 }
@@ -101,7 +113,7 @@ VISUAL_VEHICLE_KEYS = {
 # NEUTRAL: features outside the step path (rendering, image observations, manual / scripted ego control, recording); the
 # neutral value is accepted, anything else is refused by name instead of being silently ignored.
 NEUTRAL_KEYS = {
-    "use_render": False, "manual_control": False, "offscreen_render": False, "use_saver": False,
+    "use_render": False, "manual_control": False, "offscreen_render": False,
     "record_episode": False, "_debug_crash_object": False, "is_multi_agent": False, "num_agents": 1,
     "allow_respawn": False, "delay_done": 0, "gaussian_noise": 0.0, "dropout_prob": 0.0,
 }
@@ -139,6 +151,44 @@ def strip_reference_only_keys(user, keep=()):
             continue
         out[k] = v
     return out
+
+
+def load_saver_weights(c, obs_dim):
+    """The six arrays of the guardian's expert (float32, contiguous) from config['saver_weights'], checked against the observation width:
+    fc_1 with obs_dim rows is used as it is, with obs_dim + 1 rows it is the reference's shipped expert (the kernel builds the lateral
+    float of its row)."""
+    w = c["saver_weights"]
+    if w is None:
+        raise ValueError("use_saver=True needs config['saver_weights']: no expert weights are shipped with this package -- pass the path "
+                         "of the reference's examples/ppo_expert/expert_weights.npz (or a dict of its arrays)")
+    if isinstance(w, (str, bytes)) or hasattr(w, "__fspath__"):
+        w = np.load(w)
+    missing = [k for k in SAVER_WEIGHT_KEYS if k not in w]
+    if missing:
+        raise ValueError("saver_weights: missing %s" % ", ".join(missing))
+    arrays = [np.ascontiguousarray(w[k], dtype=np.float32) for k in SAVER_WEIGHT_KEYS]
+    rows = arrays[0].shape[0] if arrays[0].ndim == 2 else -1
+    if rows not in (obs_dim, obs_dim + 1) or arrays[0].shape[1:] != (256, ) or arrays[2].shape != (256, 256) or arrays[4].ndim != 2 or \
+            arrays[4].shape[0] != 256 or arrays[4].shape[1] < 4:
+        raise ValueError("saver_weights: fc_1/kernel has %s rows; this env's observation has %d floats (%d with the lateral float of the "
+                         "reference's expert); hidden width 256, fc_out at least 4 columns" % (rows, obs_dim, obs_dim + 1))
+    return arrays
+
+
+def check_saver_config(c):
+    """use_saver=True next to what the guardian does not serve: refused by name."""
+    lid = c["vehicle_config"]["lidar"]
+    if c["IDM_agent"]:
+        raise NotImplementedError("config['use_saver'] with config['IDM_agent']: the ego is driven by IDMPolicy, there is no action to guard")
+    if c["discrete_action"]:
+        raise NotImplementedError("config['use_saver'] with config['discrete_action']: the guardian compares continuous actions")
+    if lid["gaussian_noise"] != 0.0 or lid["dropout_prob"] != 0.0:
+        raise NotImplementedError("config['use_saver'] with lidar gaussian_noise / dropout_prob: the reference's guardian reads the un-noised "
+                                  "cloud points, which this engine does not keep")
+    if (lid["num_lasers"] if lid["distance"] > 0 else 0) < _abi.GUARD_MIN_LASERS:
+        raise NotImplementedError("config['use_saver'] with fewer than %d lidar beams: the guardian's fan slices need them" % _abi.GUARD_MIN_LASERS)
+    if c.get("use_topdown"):
+        raise NotImplementedError("config['use_saver'] with config['use_topdown']: the expert reads the lidar observation")
 
 
 def resolve_map_choice(c, default_map=3):
@@ -184,6 +234,10 @@ class PGDriveVecEnv:
         self.config = merge_config(DEFAULT_CONFIG, strip_reference_only_keys(config))
         c = self.config
         vc = c["vehicle_config"]
+        if c["use_saver"]:
+            check_saver_config(c)
+            if c["saver_weights"] is None:
+                load_saver_weights(c, 0)  # (raises: before any map is generated)
         # (the noise keys of the side / lane-line detectors exist upstream but are never read: only the lidar cloud is
         # perturbed, state_obs.py:155-170)
         mc = c["map_config"]
@@ -274,6 +328,31 @@ class PGDriveVecEnv:
         self.observation_space = self.single_observation_space
         self.action_space = self.single_action_space
         self._rng = np.random.RandomState(c["seed"])
+        self.saver = None
+        if c["use_saver"]:
+            self._saver_init()
+
+    def _saver_init(self):
+        """The guardian's tensors: the expert on the device, the takeover state, the buffers step() hands out."""
+        import torch
+        c, dev, n = self.config, self.engine.device, self.num_envs
+        self.saver = tuple(torch.from_numpy(a).to(dev) for a in load_saver_weights(c, self.obs_dim))
+        self._saver_state = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self._saver_tick = 0
+        self.last_takeover = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.last_applied_actions = torch.zeros((n, 2), dtype=torch.float32, device=dev)
+        self._saver_prev = torch.zeros((n, 1), dtype=torch.int32, device=dev)  # the flags of the previous step (a copy: step() rewrites them)
+
+    def _guard(self, actions, group=-1):
+        """The guardian in front of a step: `actions` [N, 2] as the caller gave them -> the buffer the step reads.  The expert's noise:
+        seed = config['seed'] ^ GUARDIAN_SEED_XOR (pgdrive_amd/rollout.py), tick = steps since the env was created."""
+        from .rollout import GUARDIAN_SEED_XOR
+        c, n = self.config, self.num_envs
+        a = actions.contiguous().view(n, 1, 2).float()
+        self.engine.guardian(self.saver, c["save_level"], a, self._saver_state, self.last_applied_actions.view(n, 1, 2), self.last_takeover,
+                             int(c["seed"]) ^ GUARDIAN_SEED_XOR, self._saver_tick, prev_flags=self._saver_prev, group=group,
+                             deterministic=c["saver_deterministic"], immediate=c["saver_immediate"])
+        return self.last_applied_actions
 
     def reset(self, force_seed=None):
         """Reset every env; `force_seed` (int or array) pins the map seed(s), else seeds are drawn uniformly from
@@ -288,6 +367,10 @@ class PGDriveVecEnv:
             fs = np.broadcast_to(np.asarray(force_seed), (self.num_envs, ))
             ids = np.array([self.seeds.index(int(s)) for s in fs])
         obs = self.engine.reset(ids.astype(np.int32))
+        if self.saver is not None:  # vehicle.takeover = False (base_vehicle.py:332)
+            self._saver_state.zero_()
+            self._saver_prev.zero_()
+            self.last_takeover.zero_()
         if self.topdown:
             return self.engine.observe_topdown()
         return obs.view(self.num_envs, self.obs_dim)
@@ -307,7 +390,12 @@ class PGDriveVecEnv:
             else:
                 ok = bool(((a >= -1.0) & (a <= 1.0)).all())
             assert ok, "Input actions are not compatible with action space {}!".format(self.single_action_space)
+        if self.saver is not None:
+            actions = self._guard(actions)
+            self._saver_tick += 1
         obs, rew, done, flags = self.engine.step(actions.contiguous().view(self.num_envs, 1, 2))
+        if self.saver is not None:
+            self._saver_prev.copy_(flags)
         if not getattr(self, "_kernel_reported", False):
             # once: a configuration that is not one of the reference's defaults runs the general step kernel, measured 12 % behind
             # the instantiations with the configuration compiled in -- say so instead of paying silently
@@ -342,6 +430,17 @@ class PGDriveVecEnv:
         of the group's rows (obs [n, D], reward, done, flags)."""
         if self.topdown:
             raise NotImplementedError("step_group with the top-down observation")
+        if self.saver is not None:  # on the group's stream, like the step; the tick counts the group's steps
+            import torch
+            sl = self.engine.group_slice(g)
+            ticks = self.__dict__.setdefault("_saver_group_ticks", {})
+            self._saver_tick = ticks.get(g, 0)
+            with torch.cuda.stream(self.engine.group_streams[g]):
+                actions = self._guard(actions, group=g)
+                obs, rew, done, flags = self.engine.step_group(g, actions.view(self.num_envs, 1, 2))
+                self._saver_prev[sl].copy_(flags)
+            ticks[g] = self._saver_tick + 1
+            return obs.view(-1, self.obs_dim), rew.view(-1), done.view(-1), flags.view(-1)
         obs, rew, done, flags = self.engine.step_group(g, actions.contiguous().view(self.num_envs, 1, 2))
         return obs.view(-1, self.obs_dim), rew.view(-1), done.view(-1), flags.view(-1)
 
