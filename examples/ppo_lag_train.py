@@ -5,11 +5,14 @@ then pgd_lagrange, pgd_adv_stats twice, pgd_adv_mix and pgd_ppo_grad_cost + pgd_
     python examples/ppo_lag_train.py --envs 256 --T 32 --eager 3 --replays 20 [--cost-limit 1.0] [--every 5]
     python examples/ppo_lag_train.py --time --envs 4096 --T 128 [--windows 7] [--calls 3] [--plain]
     python examples/ppo_lag_train.py --horizon 100 --bootstrap-truncations     # an episode that ends at the horizon is bootstrapped, not cut
+    python examples/ppo_lag_train.py --shuffle --target-kl 0.015 --anneal-lr   # random minibatches, a KL stop, a learning-rate schedule
 
 The env is PGDriveVecEnv configured as SafePGDriveEnv (pgdrive/envs/safe_pgdrive_env.py:7-60): accident scenes on the road, crashes are
 costs and not terminations.  A few iterations run eagerly; then one `collect(); update()` is captured in a HIP graph and replayed.
 Printed: the multiplier, the mean episode cost J_c it last saw, the losses of the update's last minibatch and env-steps per second; the
-prints read the device, the iteration itself does not.
+prints read the device, the iteration itself does not.  --shuffle, --target-kl, --anneal-lr: the learner's minibatch switches (DESIGN.md
+section 29); with a gate the prints show how many Adam steps the last update applied and skipped (the last minibatch's row is zero
+behind a stop).
 
 --time: collect() and update() timed apart, eagerly and as replays of a graph of each, each warmed up, then `--windows` windows of
 `--calls` calls (host clock around a device synchronisation); the median window and the spread are printed.  --plain times
@@ -46,16 +49,17 @@ def make(args):
     env = PGDriveVecEnv(dict(SAFE, num_envs=args.envs, start_seed=1000, environment_num=100, auto_reset=True, horizon=args.horizon))
     pw, vw, cw = random_networks(env.obs_dim, np.random.default_rng(0))
     env.reset()
+    switches = dict(shuffle=args.shuffle, shuffle_seed=args.shuffle_seed, target_kl=args.target_kl, lr_scale=args.anneal_lr)
     if getattr(args, "plain", False):
         from pgdrive_amd import PPOLearner, RolloutCollector
         col = RolloutCollector(env, pw, vw, args.T, seed=0, bootstrap_truncations=args.bootstrap_truncations, normalise_obs=args.normalise_obs)
-        learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches)
+        learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, **switches)
     else:
         from pgdrive_amd import PPOLagLearner, SafeRolloutCollector
         col = SafeRolloutCollector(env, pw, vw, cw, args.T, seed=0, bootstrap_truncations=args.bootstrap_truncations,
                                    normalise_obs=args.normalise_obs)
         learner = PPOLagLearner(col, cost_limit=args.cost_limit, lambda_lr=args.lambda_lr, lr=args.lr, epochs=args.epochs,
-                                minibatches=args.minibatches)
+                                minibatches=args.minibatches, **switches)
     return env, col, learner
 
 
@@ -125,6 +129,12 @@ def main():
                     help="GAE and cost GAE bootstrap through the horizon from the critics' values of the terminal observation (DESIGN.md section 24)")
     ap.add_argument("--normalise-obs", action="store_true",
                     help="the networks read the observations normalised by their running mean and variance (DESIGN.md section 27)")
+    ap.add_argument("--shuffle", action="store_true", help="a fresh permutation of the rollout's rows per epoch (DESIGN.md section 29)")
+    ap.add_argument("--shuffle-seed", type=int, default=0)
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="stop an update on the device where mean(logp_old - logp) of a minibatch exceeds 1.5 times this (DESIGN.md section 29)")
+    ap.add_argument("--anneal-lr", action="store_true",
+                    help="the learning rate falls linearly to zero over the iterations: a device float written between them (DESIGN.md section 29)")
     args = ap.parse_args()
     if args.time:
         return time_pair(args)
@@ -142,12 +152,21 @@ def main():
         st = dict(zip(_abi.PPO_COST_STATS, learner.stats[-1].cpu().numpy()))
         print("%-12s lambda %7.4f  J_c %7.4f over %4d episodes  mean reward %8.4f  mean cost %.4f  L_pi %.4g  L_v %.4g  L_c %.4g  kl %.3g" % (
             tag, lam, jc, int(episodes), float(col.batch["rewards"].mean()), float(col.batch["costs"].mean()), st["policy_loss"],
-            st["value_loss"], st["cost_value_loss"], st["approx_kl"]))
+            st["value_loss"], st["cost_value_loss"], st["approx_kl"]) + ("" if learner.gate is None else "  steps applied %d, skipped %d" % (
+                int(learner.gate[1]), int(learner.gate[2]))))
+
+    total, done = max(1, args.eager) + args.replays, [0]
+
+    def anneal():  # (a device write between iterations and between replays: the float lr is frozen into the captured graph, this factor is not)
+        if args.anneal_lr:
+            learner.lr_scale.fill_(1.0 - done[0] / total)
+        done[0] += 1
 
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s), torch.no_grad():
         for it in range(1, max(1, args.eager) + 1):  # (the first collect() primes the collector: outside the capture)
+            anneal()
             iteration()
             report("eager %d" % it)
         graph = torch.cuda.CUDAGraph()
@@ -157,6 +176,7 @@ def main():
     t0 = time.perf_counter()
     with torch.cuda.stream(s), torch.no_grad():
         for it in range(1, args.replays + 1):
+            anneal()
             graph.replay()
             if it % args.every == 0 or it == args.replays:
                 report("replay %d" % it)

@@ -3,13 +3,18 @@
 epoch and minibatch).
 
     python examples/ppo_train.py --envs 256 --T 32 --iters 20 [--graph] [--marl [--agents 40]] [--every 5] [--episode-stats] [--normalise-obs]
-    python examples/ppo_train.py --time --envs 4096 --T 64 [--windows 7] [--updates 3]
+                                 [--shuffle] [--target-kl 0.015] [--anneal-lr]
+    python examples/ppo_train.py --time --envs 4096 --T 64 [--windows 7] [--updates 3] [--shuffle] [--target-kl 0.015]
 
 Random initial weights of the shape of the reference's shipped PPO expert (pgdrive/examples/ppo_expert/numpy_expert.py).  Printed every
 `--every` iterations: the mean reward of the rollout and the statistics of the update's last minibatch (pgdrive_amd._abi.PPO_STATS); these
 prints read the device, the iteration itself does not.  --episode-stats: a second line per print with the episodes that finished since
 the last print -- their number, the success rate (arrive_dest at the episode's end), mean and standard deviation of the return and the
-mean length (the collector's episode_stats switch) -- and the number of episodes so far.
+mean length (the collector's episode_stats switch) -- and the number of episodes so far.  --shuffle: a fresh
+permutation of the rollout's rows per epoch; --target-kl: an update stops on the device where a minibatch's KL estimate exceeds 1.5 times
+the value (the prints then show how many Adam steps the last update applied and skipped); --anneal-lr: the learning rate falls linearly
+to zero over --iters through the learner's device float lr_scale, written between iterations and between graph replays alike (DESIGN.md
+section 29).
 
 --time: update() alone on one fixed batch in three forms on the same build -- the engine's kernels, the same update composed from torch
 ops with autograd and torch.optim.Adam eagerly, and that composition captured in a HIP graph --, each warmed up, then `--windows` windows
@@ -118,7 +123,8 @@ def time_update(args):
     col = RolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0)
     with torch.no_grad():
         batch = col.collect()
-    learner = PPOLearner(col, epochs=args.epochs, minibatches=args.minibatches)
+    learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, shuffle=args.shuffle, shuffle_seed=args.shuffle_seed,
+                         target_kl=args.target_kl, lr_scale=args.anneal_lr)
     tu = TorchUpdate(pw, vw, epochs=args.epochs, minibatches=args.minibatches)
     forms = (("engine kernels", lambda: learner.update(batch), False), ("engine kernels, graph", lambda: learner.update(batch), True),
              ("torch autograd + Adam, eager", lambda: tu.update(batch), False), ("torch autograd + Adam, graph", lambda: tu.update(batch), True))
@@ -133,6 +139,8 @@ def time_update(args):
         sys.stdout.flush()
     st = learner.stats.cpu().numpy()
     print("engine, last minibatch: " + ", ".join("%s %.4g" % (n, x) for n, x in zip(_abi.PPO_STATS[:7], st[-1])))
+    if learner.gate is not None:
+        print("engine, last update: " + ", ".join("%s %d" % (n, x) for n, x in zip(_abi.ADAM_GATE, learner.gate.tolist())))
     env.close()
 
 
@@ -161,6 +169,12 @@ def main():
                     help="the networks read the observations normalised by their running mean and variance (DESIGN.md section 27)")
     ap.add_argument("--episode-stats", action="store_true",
                     help="print the statistics of the episodes that finished since the last print (DESIGN.md section 26)")
+    ap.add_argument("--shuffle", action="store_true", help="a fresh permutation of the rollout's rows per epoch (DESIGN.md section 29)")
+    ap.add_argument("--shuffle-seed", type=int, default=0)
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="stop an update on the device where mean(logp_old - logp) of a minibatch exceeds 1.5 times this (DESIGN.md section 29)")
+    ap.add_argument("--anneal-lr", action="store_true",
+                    help="the learning rate falls linearly to zero over --iters: a device float written between iterations (DESIGN.md section 29)")
     args = ap.parse_args()
     if args.time:
         return time_update(args)
@@ -180,7 +194,8 @@ def main():
     else:
         col = RolloutCollector(env, pw, vw, args.T, gamma=GAMMA, lam=LAM, seed=0, bootstrap_truncations=args.bootstrap_truncations,
                                normalise_rewards=args.normalise_rewards, episode_stats=args.episode_stats, normalise_obs=args.normalise_obs)
-    learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, ent_coef=0.0)
+    learner = PPOLearner(col, lr=args.lr, epochs=args.epochs, minibatches=args.minibatches, ent_coef=0.0, shuffle=args.shuffle,
+                         shuffle_seed=args.shuffle_seed, target_kl=args.target_kl, lr_scale=args.anneal_lr)
 
     def iteration():
         return learner.update(col.collect())
@@ -204,6 +219,8 @@ def main():
     t0 = time.perf_counter()
     with torch.cuda.stream(s), torch.no_grad():
         for it in range(1, args.iters + 1):
+            if args.anneal_lr:  # (a device write between two replays: the float lr is frozen into the captured graph, this factor is not)
+                learner.lr_scale.fill_(1.0 - (it - 1) / args.iters)
             call()
             if it % args.every == 0 or it == args.iters:
                 torch.cuda.synchronize()
@@ -217,6 +234,10 @@ def main():
                 scale = "  reward scale %.4g" % float(b["return_norm"][3]) if args.normalise_rewards else ""
                 if args.normalise_obs:
                     scale += "  obs samples %d, largest scale %.4g" % (int(b["obs_norm_record"][0]), float(b["obs_norm"][1].max()))
+                if learner.gate is not None:  # (the last row may lie behind a stop: n = 0)
+                    scale += "  steps applied %d, skipped %d" % (int(learner.gate[1]), int(learner.gate[2]))
+                    if args.anneal_lr:
+                        scale += "  lr %.3g" % (args.lr * float(learner.lr_scale[0]))
                 print("iteration %4d  Adam step %5d  mean reward %8.4f  " % (it, int(learner.step[0]), reward) +
                       "  ".join("%s %.4g" % (k, x) for k, x in zip(_abi.PPO_STATS[:7], st)) + scale)
                 if args.episode_stats:

@@ -577,6 +577,35 @@ int pgd_adv_stats(pgd_handle h, const float* d_adv, const int32_t* d_index, cons
  * n_elem >= 1 (PGD_ERR_ARG).  Two launches, asynchronous on the engine's stream; capturable. */
 int pgd_adam(pgd_handle h, float* d_param, const float* d_grad, float* d_m, float* d_v, int n_elem, int32_t* d_step /*[4]*/, float lr,
              float beta1, float beta2, float eps, float max_grad_norm);
+/* ---- Random minibatches and an early stop of the update, on the device ----------------------------------------------------------------
+ * pgd_shuffle_index: a keyed permutation of a row list, computed per entry.  c = the live count as for pgd_ppo_grad (*d_count within
+ * [0, n_list], n_list without a pointer; read on the device); e = epoch + (d_epoch ? (uint32_t)*d_epoch : 0) -- the rule of
+ * pgd_actor_critic_tick: a captured call replays with its argument, the device counter is what advances.  For every q < c:
+ *   d_out[q] = d_index ? d_index[pi(q)] : pi(q);       entries at and beyond c are not written; d_out must not alias d_index.
+ * pi is a bijection of [0, c): a 6-round unbalanced Feistel network on b = max(2, bit_length(c - 1)) bits, bl = b >> 1 high and
+ * br = b - bl low bits, with cycle walking.  From x = q, repeat until x < c:
+ *   L = x >> br;  R = x & (2^br - 1);  (lb, rb) = (bl, br);
+ *   for r = 0 .. 5:  f = pgd_rng(seed ^ 0x5b0ff1e5, R, r, e) & (2^lb - 1);  (L, R) = (R, L ^ f);  swap(lb, rb);
+ *   x = (L << rb) | R
+ * with pgd_rng(s, a, b, c) = H(s ^ H(a ^ H(b ^ H(c + 0x9e3779b9)))), H the 32-bit PCG output hash -- integers only.  The walk has no
+ * cap (x runs through the cycle that contains q; the domain is below 2 c for c >= 3, so its mean length is below 2).
+ * One thread per q, no atomics, no scratch; asynchronous on the engine's stream, capturable from the first call.  PGD_ERR_ARG: a null
+ * handle or d_out, d_out == d_index, n_list < 0 or above PGD_PPO_ROWS_MAX.
+ *
+ * pgd_adam_gated: pgd_adam behind a gate in device memory.  d_gate, four int32 (4-byte aligned, the caller's, zeroed by the caller
+ * where an update begins): 0 stopped, 1 steps applied since it was cleared, 2 steps skipped, 3 1 iff THIS call skipped.  One thread of
+ * the first launch decides:   stop = gate[0] != 0 || (d_kl && !(*d_kl <= kl_limit))        (a NaN stops)
+ *   skip:   gate[0] = 1, gate[2] += 1, gate[3] = 1, *d_count_gate = 0 where the pointer is given; d_step, d_param, d_m and d_v keep
+ *           their bytes.  (A count that the later pgd_ppo_grad / pgd_shuffle_index calls of the update read: zeroed, they find no live
+ *           row, write zero gradients and a statistics row with n = 0.)
+ *   apply:  gate[1] += 1, gate[3] = 0, then pgd_adam's step with lr_eff = lr * *d_lr_scale (one fp32 product; lr without a pointer).
+ * With d_lr_scale, d_kl and d_count_gate null and a zeroed gate the results are pgd_adam's bit for bit.  The refusals of pgd_adam, and a
+ * null or misaligned d_gate.  Two launches, asynchronous on the engine's stream; capturable. */
+int pgd_shuffle_index(pgd_handle h, const int32_t* d_index /*nullable*/, const int32_t* d_count /*nullable*/, int n_list, uint32_t seed,
+                      uint32_t epoch, const int32_t* d_epoch /*nullable*/, int32_t* d_out /*[n_list]*/);
+int pgd_adam_gated(pgd_handle h, float* d_param, const float* d_grad, float* d_m, float* d_v, int n_elem, int32_t* d_step /*[4]*/, float lr,
+                   float beta1, float beta2, float eps, float max_grad_norm, const float* d_lr_scale /*nullable*/, const float* d_kl /*nullable*/,
+                   float kl_limit, int32_t* d_gate /*[4]*/, int32_t* d_count_gate /*nullable*/);
 /* ---- Safe RL behind a rollout: cost critic, cost GAE, the Lagrange multiplier, PPO-Lagrangian gradients -------------------------------
  * (No reference counterpart: the reference hands info["cost"] to an RL library; safe_pgdrive_env.py:7-60.  With safe_rl_env a crash is a
  * cost and not a termination; these entry points keep a policy under a cost limit without leaving the device.)

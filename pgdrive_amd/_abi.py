@@ -96,6 +96,7 @@ class ValueGrads(C.Structure):
 PPO_ROWS_MAX = 16777216
 PPO_STATS = ("n", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "ratio", "reserved")  # d_stats of pgd_ppo_grad
 PPO_COST_STATS = PPO_STATS[:7] + ("cost_value_loss", )  # d_stats of pgd_ppo_grad_cost
+ADAM_GATE = ("stopped", "applied", "skipped", "skipped_now")  # d_gate of pgd_adam_gated, four int32
 LAGRANGE_STATE = ("lambda", "episode_cost", "episodes", "reserved")  # d_state of pgd_lagrange
 RN_FREEZE = 1  # PGD_RN_FREEZE, a mode bit of pgd_return_norm
 RETURN_NORM_RECORD = ("count", "mean", "m2", "scale")  # d_record of pgd_return_norm, four doubles

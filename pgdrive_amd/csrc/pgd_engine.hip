@@ -1421,4 +1421,5 @@ int pgd_destroy(pgd_handle h) {
 #include "pgd_return_norm.h"
 #include "pgd_obs_norm.h"
 #include "pgd_rollout_episodes.h"
+#include "pgd_minibatch.h"
 #endif  // !PGD_JIT

@@ -50,6 +50,9 @@ _SIGS = {
     "pgd_adv_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pgd_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float,
                            C.c_float, C.c_float]),
+    "pgd_shuffle_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pgd_adam_gated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                 C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "pgd_mlp_actor_critic_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.ValueNet),
                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pgd_cost_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float] +
@@ -684,6 +687,48 @@ class Engine:
         self._follow_stream()
         _chk(self.L.pgd_adam(self.h, C.c_void_p(param.data_ptr()), C.c_void_p(grad.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), n,
                              C.c_void_p(step.data_ptr()), float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm)), "pgd_adam")
+        return param
+
+    def shuffle_index(self, index, count, n_list, seed, epoch, epoch_dev=None, out=None):
+        """A keyed permutation of a row list (pgd_shuffle_index) -> `out`, int32 cuda [n_list]: out[q] = index[pi(q)] (`index` None: pi(q))
+        for q < count (int32 cuda [1], read on the device; None: n_list), pi a bijection of [0, count) drawn from (seed, epoch +
+        epoch_dev[0]) -- `epoch_dev` int32 cuda [1] or None: the counter a replayed graph advances.  Entries at and beyond the count keep
+        what they held.  `out` must not share memory with `index`.  Asynchronous."""
+        t = self.torch
+        n_list = int(n_list)
+        assert 0 <= n_list <= _abi.PPO_ROWS_MAX and 0 <= int(seed) < 2 ** 32 and 0 <= int(epoch) < 2 ** 32
+        out = t.empty((n_list, ), dtype=t.int32, device=self.device) if out is None else out
+        assert out.is_cuda and out.dtype == t.int32 and out.is_contiguous() and out.numel() >= n_list
+        ip, cp = self._list_args(index, count, n_list)
+        if index is not None:
+            lo, hi = index.data_ptr(), index.data_ptr() + 4 * index.numel()
+            assert out.data_ptr() + 4 * out.numel() <= lo or hi <= out.data_ptr(), "shuffle_index: `out` overlaps `index`"
+        if epoch_dev is not None:
+            assert epoch_dev.is_cuda and epoch_dev.dtype == t.int32 and epoch_dev.numel() == 1
+        self._follow_stream()
+        _chk(self.L.pgd_shuffle_index(self.h, ip, cp, n_list, int(seed), int(epoch), _p(epoch_dev) if epoch_dev is not None else None, _p(out)),
+             "pgd_shuffle_index")
+        return out
+
+    def adam_gated(self, param, grad, m, v, step, lr, gate, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, lr_scale=None, kl=None,
+                   kl_limit=0.0, count_gate=None):
+        """adam() behind a gate on the device (pgd_adam_gated).  `gate`: int32 cuda [4] (_abi.ADAM_GATE), zeroed by the caller where an
+        update begins.  The call skips -- `param`, `m`, `v` and `step` keep their bytes, gate = (1, ., +1, 1), `count_gate` (int32 cuda [1]
+        or None) is zeroed -- when gate[0] is set or `kl` (one float32 cuda, or None) is not <= kl_limit; else it applies adam's step with
+        the learning rate lr * lr_scale[0] (`lr_scale`: one float32 cuda, or None) and counts it in gate[1].  Asynchronous."""
+        t = self.torch
+        n = int(param.numel())
+        for x in (param, grad, m, v):
+            assert x.is_cuda and x.dtype == t.float32 and x.is_contiguous() and x.numel() == n
+        assert n >= 1 and step.is_cuda and step.dtype == t.int32 and step.is_contiguous() and step.numel() == 4
+        assert gate.is_cuda and gate.dtype == t.int32 and gate.is_contiguous() and gate.numel() == 4
+        for x in (lr_scale, kl):
+            assert x is None or (x.is_cuda and x.dtype == t.float32 and x.numel() >= 1 and x.data_ptr() % 4 == 0)
+        assert count_gate is None or (count_gate.is_cuda and count_gate.dtype == t.int32 and count_gate.numel() == 1)
+        self._follow_stream()
+        opt = [_p(x) if x is not None else None for x in (lr_scale, kl, count_gate)]
+        _chk(self.L.pgd_adam_gated(self.h, _p(param), _p(grad), _p(m), _p(v), n, _p(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                   float(max_grad_norm), opt[0], opt[1], float(kl_limit), _p(gate), opt[2]), "pgd_adam_gated")
         return param
 
     # -- safe RL behind a rollout: the cost side of the loop (include/pgdrive_hip.h states the formulas) ---------------------------

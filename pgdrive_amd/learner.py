@@ -16,8 +16,19 @@ collector's table (Engine.obs_norm_bind) before its first ppo_grad and unbinds b
 rollout's evaluations saw.
 
 Minibatch j of n takes the list positions j, j + n, j + 2 n, ...: the n minibatches partition the rollout's transitions whatever their
-number is, with no shuffle tensor.  For RolloutCollector the list is every (t, env) row; for MultiAgentRolloutCollector it is
-batch["index"] / batch["count"] as they lie on the device (the transitions at which an agent acted).
+number is.  For RolloutCollector the list is every (t, env) row; for MultiAgentRolloutCollector it is batch["index"] / batch["count"] as
+they lie on the device (the transitions at which an agent acted).  With shuffle=False (the default) that list is followed as it lies,
+with no shuffle tensor: for RolloutCollector with N a multiple of n, minibatch j is then the envs with env % n == j at every t, the same
+in every epoch.  shuffle=True is what SB3, CleanRL and Spinning Up do: every epoch draws a fresh permutation of the live list
+(Engine.shuffle_index into `shuffled`, one small launch per epoch, keyed by shuffle_seed and an epoch counter in device memory, so a
+replayed graph draws new ones) and the same strided plan runs over it.
+
+target_kl=x stops an update early ON THE DEVICE: every Adam call is Engine.adam_gated, which tests the minibatch's statistic
+mean(logp_old - logp) (stats[k, 4], Spinning Up's estimator) against 1.5 x before it applies the step (SB3's granularity).  A stop shuts
+`gate` (_abi.ADAM_GATE) for the rest of the update and zeroes `live_count`, the count every later gradient call reads: their tiles end
+before they read a weight, their statistics rows have n = 0.  lr_scale=True: `lr_scale`, one device float the gated Adam multiplies lr
+with -- a schedule writes it between iterations (a plain device write, legal between the replays of a captured graph, into which the
+float `lr` is frozen).  state_dict() / load_state_dict(): params, m, v, step and, where they exist, the epoch counter and lr_scale.
 
 The learner owns ONE flat parameter buffer; the twelve weight tensors are views into it (every offset a multiple of 4 floats: the
 16-byte alignment the network kernels demand).  It hands the views to collector.set_weights once; updates are in place, so the collector
@@ -59,15 +70,33 @@ def live_positions(start, stride, rows, count):
     return [start + i * stride for i in range(rows) if start + i * stride < count]
 
 
+def minibatch_options(name, shuffle, shuffle_seed, target_kl, lr_scale):
+    """The learner's minibatch switches checked (ValueError) -> (shuffle, shuffle_seed, kl_limit or None, lr_scale).  No device needed."""
+    if not isinstance(shuffle, (bool, int)) or shuffle not in (0, 1):
+        raise ValueError("%s: shuffle = %r is not a bool" % (name, shuffle))
+    if not isinstance(lr_scale, (bool, int)) or lr_scale not in (0, 1):
+        raise ValueError("%s: lr_scale = %r is a switch (the factor is the device tensor learner.lr_scale), not a bool" % (name, lr_scale))
+    if isinstance(shuffle_seed, bool) or not isinstance(shuffle_seed, int) or not (0 <= shuffle_seed < 2 ** 32):
+        raise ValueError("%s: shuffle_seed = %r is not an integer in [0, 2^32)" % (name, shuffle_seed))
+    kl_limit = None
+    if target_kl is not None:
+        kl_limit = 1.5 * float(target_kl)
+        if not (0.0 < kl_limit < float("inf")):
+            raise ValueError("%s: target_kl = %r is not a positive finite number (None: no stop)" % (name, target_kl))
+    return bool(shuffle), int(shuffle_seed), kl_limit, bool(lr_scale)
+
+
 class PPOLearner:
     NETS = ("policy", "value")  # the collector's networks, in flat_layout's order
     GRAD = "pgd_ppo_grad"
 
     def __init__(self, collector, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.0, epochs=4, minibatches=4, max_grad_norm=0.5, betas=(0.9, 0.999),
-                 eps=1e-5, normalise_advantages=True):
+                 eps=1e-5, normalise_advantages=True, shuffle=False, shuffle_seed=0, target_kl=None, lr_scale=False):
+        name, cost = type(self).__name__, len(self.NETS) == 3
+        self.shuffle, self.shuffle_seed, self.kl_limit, scaled = minibatch_options(name, shuffle, shuffle_seed, target_kl, lr_scale)
+        self.target_kl = None if target_kl is None else float(target_kl)
         eng = collector.engine
         t = eng.torch
-        name, cost = type(self).__name__, len(self.NETS) == 3
         if int(epochs) < 1 or int(minibatches) < 1:
             raise ValueError("%s: epochs = %r, minibatches = %r" % (name, epochs, minibatches))
         self.collector, self.engine = collector, eng
@@ -101,6 +130,35 @@ class PPOLearner:
         self.work = t.empty(((need + 3) // 4, ), **f32)
         self.adv_stats = t.zeros((2, ), **f32)
         self.stats = t.zeros((self.epochs * self.minibatches, 8), **f32)
+        # the minibatch switches' device state; None where a switch is off (then update() makes today's calls and no others)
+        i32 = dict(dtype=t.int32, device=eng.device)
+        self.shuffled = t.zeros((self.n_list, ), **i32) if self.shuffle else None
+        self._epoch = t.zeros((1, ), **i32) if self.shuffle else None  # epochs drawn so far: a replayed graph draws new permutations
+        self.live_count = t.zeros((1, ), **i32) if self.shuffle or self.kl_limit is not None else None  # the count the gradient calls read
+        self.gate = t.zeros((4, ), **i32) if scaled or self.kl_limit is not None else None  # _abi.ADAM_GATE
+        self.lr_scale = t.ones((1, ), **f32) if scaled else None
+
+    def state_dict(self):
+        """What a checkpoint of the learner holds (clones on the device): the flat parameters, Adam's moments and step record and, where
+        the switches made them, the epoch counter of the permutations and lr_scale (None otherwise)."""
+        own = {"params": self.params, "m": self.m, "v": self.v, "step": self.step, "_epoch": self._epoch, "lr_scale": self.lr_scale}
+        return {k: (None if x is None else x.clone()) for k, x in own.items()}
+
+    def load_state_dict(self, state):
+        """state_dict()'s tensors copied back IN PLACE (the collector holds views of `params`).  An entry this learner has no tensor for
+        (a checkpoint of a shuffled run loaded into an unshuffled learner) must be None; one it has must be there."""
+        own = {"params": self.params, "m": self.m, "v": self.v, "step": self.step, "_epoch": self._epoch, "lr_scale": self.lr_scale}
+        for k, x in own.items():
+            src = state.get(k)
+            if (x is None) != (src is None):
+                raise ValueError("%s.load_state_dict: %r is %s in the checkpoint and %s here" %
+                                 (type(self).__name__, k, "missing" if src is None else "present", "missing" if x is None else "present"))
+            if x is not None and (tuple(src.shape) != tuple(x.shape) or src.dtype != x.dtype):
+                raise ValueError("%s.load_state_dict: %r is %s %s, expected %s %s" %
+                                 (type(self).__name__, k, tuple(src.shape), src.dtype, tuple(x.shape), x.dtype))
+        for k, x in own.items():
+            if x is not None:
+                x.copy_(state[k])
 
     def _advantages(self, batch, index, count):
         """The advantage tensor the gradient calls read and the statistics they normalise it with (None: as it is)."""
@@ -122,14 +180,33 @@ class PPOLearner:
         normalise_obs = getattr(self.collector, "normalise_obs", False)
         if normalise_obs:  # (the rollout's own table: it moves at the next collect() only)
             eng.obs_norm_bind(self.collector.obs_norm, self.in_dim, self.collector.clip_obs)
+        if self.live_count is not None:  # the learner's own copy of the count: a stop zeroes it, the collector's stays
+            if count is not None:
+                self.live_count.copy_(count.view(1))
+            else:
+                self.live_count.fill_(self.n_list)
+            count = self.live_count
+        if self.gate is not None:
+            self.gate.zero_()
         k = 0
-        for _ in range(self.epochs):
+        for epoch in range(self.epochs):
+            if self.shuffle:  # (adv_stats above read the collector's own list: the same entries in another order)
+                eng.shuffle_index(batch.get("index"), count, self.n_list, self.shuffle_seed, epoch, epoch_dev=self._epoch, out=self.shuffled)
+                index = self.shuffled
             for start, stride, rows in self.plan:
                 self._grad(batch, adv, self.stats[k], start=start, stride=stride, rows=rows, index=index, count=count, n_list=self.n_list,
                            adv_stats=norm, clip=self.clip, ent_coef=self.ent_coef, in_dim=self.in_dim)
-                eng.adam(self.params, self.grads, self.m, self.v, self.step, self.lr, betas=self.betas, eps=self.eps,
-                         max_grad_norm=self.max_grad_norm)
+                if self.gate is None:
+                    eng.adam(self.params, self.grads, self.m, self.v, self.step, self.lr, betas=self.betas, eps=self.eps,
+                             max_grad_norm=self.max_grad_norm)
+                else:
+                    stop = self.kl_limit is not None
+                    eng.adam_gated(self.params, self.grads, self.m, self.v, self.step, self.lr, self.gate, betas=self.betas, eps=self.eps,
+                                   max_grad_norm=self.max_grad_norm, lr_scale=self.lr_scale, kl=self.stats[k, 4:] if stop else None,
+                                   kl_limit=self.kl_limit if stop else 0.0, count_gate=self.live_count if stop else None)
                 k += 1
+        if self.shuffle:
+            self._epoch.add_(self.epochs)
         if normalise_obs:
             eng.obs_norm_bind(None)
         return self.stats
@@ -151,15 +228,18 @@ class PPOLagLearner(PPOLearner):
     Engine.adam for every epoch and minibatch.  No host read: `collect(); update()` is capturable in one HIP graph, and a replay takes
     the next multiplier step from the lambda it finds.  ONE flat buffer holds the eighteen weight tensors (flat_layout(...,
     has_cost_critic=True)); the collector is handed the views.  `ppo_kwargs`: PPOLearner's arguments (normalise_advantages False: no
-    scaling of the reward advantage and no centring of either)."""
+    scaling of the reward advantage and no centring of either; shuffle, shuffle_seed, target_kl, lr_scale as there: the permutation is
+    drawn over every row, the stop reads the same statistics slot, the multiplier step is taken before the gate is looked at)."""
     NETS = ("policy", "value", "cost")
     GRAD = "pgd_ppo_grad_cost"
 
     def __init__(self, collector, cost_limit, lambda_lr=0.05, lambda_init=0.0, lambda_max=100.0, cvf_coef=0.5, lr=3e-4, clip=0.2, vf_coef=0.5,
-                 ent_coef=0.0, epochs=4, minibatches=4, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-5, normalise_advantages=True):
+                 ent_coef=0.0, epochs=4, minibatches=4, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-5, normalise_advantages=True, shuffle=False,
+                 shuffle_seed=0, target_kl=None, lr_scale=False):
         if not (0.0 <= float(lambda_init) <= float(lambda_max)):
             raise ValueError("PPOLagLearner: lambda_init = %r outside [0, lambda_max = %r]" % (lambda_init, lambda_max))
-        super().__init__(collector, lr, clip, vf_coef, ent_coef, epochs, minibatches, max_grad_norm, betas, eps, normalise_advantages)
+        super().__init__(collector, lr, clip, vf_coef, ent_coef, epochs, minibatches, max_grad_norm, betas, eps, normalise_advantages,
+                         shuffle=shuffle, shuffle_seed=shuffle_seed, target_kl=target_kl, lr_scale=lr_scale)
         self.cost_limit, self.lambda_lr, self.lambda_max, self.cvf_coef = float(cost_limit), float(lambda_lr), float(lambda_max), float(cvf_coef)
         t = self.engine.torch
         f32 = dict(dtype=t.float32, device=self.engine.device)
