@@ -61,6 +61,20 @@ GUARD_TAKEOVER, GUARD_TAKEOVER_START, GUARD_TAKEOVER_END = 1, 2, 4  # the bits o
 GUARD_MIN_LASERS = 40  # the reference's lidar slices need forty beams
 
 
+def guardian_unserved(cfg):
+    """What of an engine's config the guardian does not serve, as the end of a refusal's sentence, or None.  `cfg`: the engine's
+    config, or anything with its idm_agent, discrete_action, lidar_gaussian_noise, lidar_dropout_prob and num_lasers."""
+    if cfg.idm_agent:
+        return "IDM_agent: the ego is driven by IDMPolicy, there is no action to guard"
+    if cfg.discrete_action:
+        return "discrete_action: the guardian compares continuous actions"
+    if cfg.lidar_gaussian_noise != 0.0 or cfg.lidar_dropout_prob != 0.0:
+        return "lidar gaussian_noise / dropout_prob: the reference's guardian reads the un-noised cloud points, which this engine does not keep"
+    if cfg.num_lasers < GUARD_MIN_LASERS:
+        return "fewer than %d lidar beams (num_lasers): the guardian's fan slices need them" % GUARD_MIN_LASERS
+    return None
+
+
 class PPOBatch(C.Structure):
     """pgd_ppo_batch: the rollout's arrays by row, the row list (index / count null: position = row, n_list entries) and the minibatch
     (start, stride, rows)."""

@@ -71,15 +71,15 @@ DEV void on_lane_table(const ObsNorm nm, const int in_dim, const int kp, const i
   }
 }
 
-// k_mlp_policy's row prologue as a function (that kernel keeps its own copy inline: its code object stays what it was).
-// The 16 observation rows of a workgroup into its X tile (row stride xs): rows row0 + r0 + [0, 16) of `obs`, as far as they lie below
-// row0 + n_rows; wave w takes rows w, w + 4, ...  Whole rows, coalesced (a row is contiguous in memory); padding columns and rows past the end read zero.
+// k_mlp_policy's row prologue as a function (that kernel keeps its own copy inline: its code object stays what it was), shared by every
+// other network kernel.  The 16 observation rows of a workgroup into its X tile (row stride xs); wave w takes slots w, w + 4, ...
+// `row_of(slot, in)` says what a slot holds: it sets `in` and returns the slot's source row, for an empty slot (in false) a row that may be
+// READ in its place and is never used.  Whole rows, coalesced (a row is contiguous in memory); padding columns and empty slots read zero.
 // Every read of the wave's four rows goes out before the first LDS store (rows of up to 320 floats: five chunks of 64 per row) --
 // as a read-then-store loop the prologue was twenty memory round trips in a row, a third of the launch (round 6).
-// NORM: the live entries are normalised on their way (on_apply); padding columns and rows past the end stay exactly 0
-template <bool NORM>
-DEV void ac_load_rows(const float* obs, const int row0, const int r0, const int n_rows, const int obs_stride, const int in_dim, const int kp,
-                       const int xs, const int wave, const int lane, float* X, const ObsNorm nm) {
+// NORM: the live entries are normalised on their way (on_apply); padding columns and empty slots stay exactly 0
+template <bool NORM, class RowOf>
+DEV void mlp_load_rows(const int in_dim, const int kp, const int xs, const int wave, const int lane, float* X, const ObsNorm nm, const RowOf row_of) {
   constexpr int XCH = 5;
   if (kp <= WAVE * XCH) {
     float v[MLP_ROWS / MLP_WAVES][XCH], sh[XCH], sc[XCH];
@@ -87,9 +87,8 @@ DEV void ac_load_rows(const float* obs, const int row0, const int r0, const int 
     if (NORM) on_lane_table(nm, in_dim, kp, lane, sh, sc);
 #pragma unroll
     for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i) {
-      const int r = wave + i * MLP_WAVES;
-      const bool row_in = r0 + r < n_rows;
-      const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
+      bool row_in;
+      const float* src = row_of(wave + i * MLP_WAVES, row_in);
       live[i] = row_in;
 #pragma unroll
       for (int j = 0; j < XCH; ++j) {
@@ -108,13 +107,42 @@ DEV void ac_load_rows(const float* obs, const int row0, const int r0, const int 
       }
   } else
   for (int r = wave; r < MLP_ROWS; r += MLP_WAVES) {
-    const bool row_in = r0 + r < n_rows;
-    const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
+    bool row_in;
+    const float* src = row_of(r, row_in);
     for (int k = lane; k < kp; k += WAVE) {
       if (NORM) X[r * xs + k] = (row_in && k < in_dim) ? on_apply(src[k], nm.table[k], nm.table[kp + k], nm.clip) : 0.0f;
       else X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
     }
   }
+}
+
+// slot r holds row row0 + r0 + r of `obs` as far as it lies below row0 + n_rows; the tile's first row stands in for the rows past the end
+template <bool NORM>
+DEV void ac_load_rows(const float* obs, const int row0, const int r0, const int n_rows, const int obs_stride, const int in_dim, const int kp,
+                       const int xs, const int wave, const int lane, float* X, const ObsNorm nm) {
+  mlp_load_rows<NORM>(in_dim, kp, xs, wave, lane, X, nm, [&](const int r, bool& in) {
+    in = r0 + r < n_rows;
+    return obs + (size_t)(row0 + r0 + (in ? r : 0)) * obs_stride;
+  });
+}
+
+// the two standard normal draws of global row g at this launch's tick (Box-Muller: the header states it)
+DEV void ac_noise(const uint32_t seed, const uint32_t tick, const uint32_t g, float& z0, float& z1) {
+  const float u1 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick));
+  const float u2 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick ^ 0x80000000u));
+  const float R = sqrtf(-2.0f * logf(u1));
+  float sn, cs;
+  sincosf(2.0f * PGD_PI * u2, &sn, &cs);
+  z0 = R * cs;
+  z1 = R * sn;
+}
+
+// the sample and its log-probability of `row` from the four head outputs and the draws
+DEV void ac_write_sample(const int row, const float m0, const float m1, const float ls0, const float ls1, const float z0, const float z1,
+                         float* act, float* logp) {
+  act[(size_t)row * 2 + 0] = fmaf(expf(ls0), z0, m0);
+  act[(size_t)row * 2 + 1] = fmaf(expf(ls1), z1, m1);
+  logp[row] = fmaf(-0.5f, fmaf(z0, z0, z1 * z1), -ls0 - ls1) - 1.8378770664093453f;  // log(2 pi)
 }
 
 // One workgroup of k_mlp_actor_critic on the network (W1 .. b3): the actor (critic false: act, logp) or a critic (value) for the 16 rows
@@ -188,19 +216,8 @@ DEV void ac_tile(const float* obs, const int row0, const int n_rows, const int o
   if ((lane & 15) == 0 && r0 + r < n_rows) {
     const int row = row0 + r0 + r;
     float z0 = 0.0f, z1 = 0.0f;
-    if (!(flags & PGD_AC_DETERMINISTIC)) {
-      const uint32_t tick = tick_arg + (tick_dev ? *tick_dev : 0u), g = row_base + (uint32_t)row;
-      const float u1 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick));
-      const float u2 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick ^ 0x80000000u));
-      const float R = sqrtf(-2.0f * logf(u1));
-      float sn, cs;
-      sincosf(2.0f * PGD_PI * u2, &sn, &cs);
-      z0 = R * cs;
-      z1 = R * sn;
-    }
-    act[(size_t)row * 2 + 0] = fmaf(expf(ls0), z0, m0);
-    act[(size_t)row * 2 + 1] = fmaf(expf(ls1), z1, m1);
-    logp[row] = fmaf(-0.5f, fmaf(z0, z0, z1 * z1), -ls0 - ls1) - 1.8378770664093453f;  // log(2 pi)
+    if (!(flags & PGD_AC_DETERMINISTIC)) ac_noise(seed, tick_arg + (tick_dev ? *tick_dev : 0u), row_base + (uint32_t)row, z0, z1);
+    ac_write_sample(row, m0, m1, ls0, ls1, z0, z1, act, logp);
   }
 }
 
@@ -219,24 +236,31 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic(const 
 }
 
 // adv[t][r] = delta + gamma lam nonterminal adv[t + 1][r], delta = reward[t][r] + gamma value[t + 1][r] nonterminal - value[t][r],
-// ret = adv + value; nonterminal = 1 - done[t][r]; one thread per row r, t from T - 1 down to 0
-__global__ __launch_bounds__(WAVE) void k_gae(const float* __restrict__ reward, const float* __restrict__ value, const uint8_t* __restrict__ done,
-                                              const int T, const int rows, const float gamma, const float lam, float* __restrict__ adv,
-                                              float* __restrict__ ret) {
-  const int r = (int)blockIdx.x * WAVE + (int)threadIdx.x;
-  if (r >= rows) return;
+// ret = adv + value; nonterminal = 1 - done[t][r]; row r, t from T - 1 down to 0; reward_of(i) is the reward of entry i = t rows + r
+template <class RewardOf>
+DEV void gae_scan(const RewardOf reward_of, const float* value, const uint8_t* done, const int T, const int rows, const int r, const float gamma,
+                  const float lam, float* adv, float* ret) {
   const float gl = gamma * lam;
   float a = 0.0f, vn = value[(size_t)T * rows + r];
 #pragma unroll 4
   for (int t = T - 1; t >= 0; --t) {
     const size_t i = (size_t)t * rows + r;
     const float v = value[i], nt = done[i] ? 0.0f : 1.0f;
-    const float delta = fmaf(gamma * nt, vn, reward[i]) - v;
+    const float delta = fmaf(gamma * nt, vn, reward_of(i)) - v;
     a = fmaf(gl * nt, a, delta);
     adv[i] = a;
     ret[i] = a + v;
     vn = v;
   }
+}
+
+// one thread per row
+__global__ __launch_bounds__(WAVE) void k_gae(const float* __restrict__ reward, const float* __restrict__ value, const uint8_t* __restrict__ done,
+                                              const int T, const int rows, const float gamma, const float lam, float* __restrict__ adv,
+                                              float* __restrict__ ret) {
+  const int r = (int)blockIdx.x * WAVE + (int)threadIdx.x;
+  if (r >= rows) return;
+  gae_scan([&](const size_t i) { return reward[i]; }, value, done, T, rows, r, gamma, lam, adv, ret);
 }
 
 #endif

@@ -7,8 +7,8 @@
 // and the step info says so (takeover_start / takeover_end / takeover; agent_manager.py:187).
 //
 // k_guardian is the actor workgroup of k_mlp_actor_critic -- 16-row tile, 4 waves, ac_lds_bytes, mlp_layer / mlp_store_hidden, the
-// four-lane head and its noise -- between a prologue and a tail of its own, so the existing instantiations of ac_tile / ac_load_rows keep
-// their code:
+// four-lane head and its noise (ac_noise) -- between a prologue and a tail of its own (the rows come through ac_load_rows or, LEGACY, a
+// loader of its own):
 //   prologue  the sixteen lanes that share a row in the head (r = tid >> 4) read the row's engine state at the same addresses (one
 //             transaction per row): the ego's record pieces 0 .. 2 (pose, speed, heading vector, lane | spawn), the env's scenario id
 //             and map header, the agent's action, the previous flags and the takeover state; behind them the lane record and the spawn
@@ -215,16 +215,7 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_guardian(const PgdDev d
   }
   if ((lane & 15) == 0 && row_in) {
     float z0 = 0.0f, z1 = 0.0f;
-    if (!(g.mode & PGD_GUARD_DETERMINISTIC)) {
-      const uint32_t tick = tick_arg + (tick_dev ? *tick_dev : 0u), gr = row_base + (uint32_t)env;
-      const float u1 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, gr, AC_KEY_STREAM, tick));
-      const float u2 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, gr, AC_KEY_STREAM, tick ^ 0x80000000u));
-      const float Rn = sqrtf(-2.0f * logf(u1));
-      float sn, cs;
-      sincosf(2.0f * PGD_PI * u2, &sn, &cs);
-      z0 = Rn * cs;
-      z1 = Rn * sn;
-    }
+    if (!(g.mode & PGD_GUARD_DETERMINISTIC)) ac_noise(seed, tick_arg + (tick_dev ? *tick_dev : 0u), row_base + (uint32_t)env, z0, z1);
     const float e0 = fmaf(expf(ls0), z0, m0), e1 = fmaf(expf(ls1), z1, m1);
     const float obs0 = X[r * xs + 0], obs1 = X[r * xs + 1];
     const float2 c = gd_rule(g, a.x, a.y, e0, e1, hd, v, f, obs0, obs1, side_min, front_min);

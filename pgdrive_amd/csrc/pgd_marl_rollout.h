@@ -27,7 +27,7 @@
 // depended on its tile neighbours.  The host does not know the list's length: the grid is sized for every row, and a workgroup whose
 // tile starts at or beyond *count returns before it reads a weight.  An entry outside [row_lo, row_lo + n_rows) is skipped, never
 // followed.  k_ac_clear_rows, launched in front of it by pgd_mlp_actor_critic_rows, gives the rows that are NOT listed their defined
-// outputs: action 0, 0, logp 0, value 0.  (k_mlp_actor_critic itself is untouched; the prologue is a copy of ac_load_rows with an index.)
+// outputs: action 0, 0, logp 0, value 0.  (The prologue is the shared loader, mlp_load_rows, with an index; the noise draw and the sample's write are ac_tile's functions.)
 //
 // k_gae_masked: k_gae with the predicates; a row that did not act is written by SELECTION (its reward and value may be NaN).
 #ifndef PGD_MARL_ROLLOUT_H
@@ -136,48 +136,16 @@ DEV int ro_listed_row(const int32_t* list, const int i, const int n, const int r
   return (row >= row_lo && row - row_lo < n_rows) ? row : -1;
 }
 
-// ac_load_rows with an index: the observation rows list[l0 + [0, 16)) into the X tile; entries past n and rows outside the range read zero
-// (the first form loads row row_lo in their place, as ac_load_rows loads its tile's first row, and selects the zero: the observation of
-// a row that is not listed is never USED -- it may hold NaN -- but row_lo's may be read)
+// slot r holds the observation row list[l0 + r]; for entries past n and rows outside the range row row_lo stands in: the observation of a
+// row that is not listed is never USED -- it may hold NaN -- but row_lo's may be read
 template <bool NORM>
 DEV void ro_load_rows(const float* obs, const int32_t* list, const int l0, const int n, const int row_lo, const int n_rows, const int obs_stride,
                       const int in_dim, const int kp, const int xs, const int wave, const int lane, float* X, const ObsNorm nm) {
-  constexpr int XCH = 5;
-  if (kp <= WAVE * XCH) {
-    float v[MLP_ROWS / MLP_WAVES][XCH], sh[XCH], sc[XCH];
-    bool live[MLP_ROWS / MLP_WAVES];
-    if (NORM) on_lane_table(nm, in_dim, kp, lane, sh, sc);
-#pragma unroll
-    for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i) {
-      const int row = ro_listed_row(list, l0 + wave + i * MLP_WAVES, n, row_lo, n_rows);
-      const bool row_in = row >= 0;
-      const float* src = obs + (size_t)(row_in ? row : row_lo) * obs_stride;
-      live[i] = row_in;
-#pragma unroll
-      for (int j = 0; j < XCH; ++j) {
-        const int k = lane + WAVE * j;
-        v[i][j] = src[k < in_dim ? k : in_dim - 1];
-        if (!(row_in && k < in_dim)) v[i][j] = 0.0f;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i)
-#pragma unroll
-      for (int j = 0; j < XCH; ++j) {
-        const int k = lane + WAVE * j;
-        if (NORM) v[i][j] = (live[i] && k < in_dim) ? on_apply(v[i][j], sh[j], sc[j], nm.clip) : 0.0f;
-        if (k < kp) X[(wave + i * MLP_WAVES) * xs + k] = v[i][j];
-      }
-  } else
-  for (int r = wave; r < MLP_ROWS; r += MLP_WAVES) {
+  mlp_load_rows<NORM>(in_dim, kp, xs, wave, lane, X, nm, [&](const int r, bool& in) {
     const int row = ro_listed_row(list, l0 + r, n, row_lo, n_rows);
-    const bool row_in = row >= 0;
-    const float* src = obs + (size_t)(row_in ? row : row_lo) * obs_stride;
-    for (int k = lane; k < kp; k += WAVE) {
-      if (NORM) X[r * xs + k] = (row_in && k < in_dim) ? on_apply(src[k], nm.table[k], nm.table[kp + k], nm.clip) : 0.0f;
-      else X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
-    }
-  }
+    in = row >= 0;
+    return obs + (size_t)(in ? row : row_lo) * obs_stride;
+  });
 }
 
 // the rows list[0 .. *count) of `obs`, each within [row_lo, row_lo + n_rows) -> act[row][0..1], logp[row] (blockIdx.y == 0) and
@@ -261,19 +229,8 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_actor_critic_rows(c
   const int row = ro_listed_row(list, l0 + r, n, row_lo, n_rows);
   if ((lane & 15) == 0 && row >= 0) {
     float z0 = 0.0f, z1 = 0.0f;
-    if (!(flags & PGD_AC_DETERMINISTIC)) {
-      const uint32_t tick = tick_arg + (tick_dev ? *tick_dev : 0u), g = row_base + (uint32_t)row;
-      const float u1 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick));
-      const float u2 = ac_unit(pgd_rng(seed ^ AC_KEY_SEED, g, AC_KEY_STREAM, tick ^ 0x80000000u));
-      const float R = sqrtf(-2.0f * logf(u1));
-      float sn, cs;
-      sincosf(2.0f * PGD_PI * u2, &sn, &cs);
-      z0 = R * cs;
-      z1 = R * sn;
-    }
-    act[(size_t)row * 2 + 0] = fmaf(expf(ls0), z0, m0);
-    act[(size_t)row * 2 + 1] = fmaf(expf(ls1), z1, m1);
-    logp[row] = fmaf(-0.5f, fmaf(z0, z0, z1 * z1), -ls0 - ls1) - 1.8378770664093453f;  // log(2 pi)
+    if (!(flags & PGD_AC_DETERMINISTIC)) ac_noise(seed, tick_arg + (tick_dev ? *tick_dev : 0u), row_base + (uint32_t)row, z0, z1);
+    ac_write_sample(row, m0, m1, ls0, ls1, z0, z1, act, logp);
   }
 }
 

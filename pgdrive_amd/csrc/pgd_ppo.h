@@ -83,7 +83,8 @@ DEV int ppo_row(const pgd_ppo_batch& b, const int i, const int n) {
   return max(0, min(p, b.n_rows - 1));
 }
 
-// ro_load_rows for minibatch positions i0 + [0, 16): rows that are not live read zero (row 0 is loaded in their place, never used)
+// mlp_load_rows for minibatch positions i0 + [0, 16): rows that are not live read zero (row 0 is loaded in their place, never used).
+// Its own copy: as a caller of mlp_load_rows (by-reference, by-value and always_inline closures) k_ppo_rows / k_ppo_rows_cost compiled to other code
 template <bool NORM>
 DEV void ppo_load_rows(const pgd_ppo_batch& b, const int i0, const int n, const int kp, const int xs, const int wave, const int lane, float* X,
                        const ObsNorm nm) {

@@ -52,7 +52,7 @@ DEV float safe_cost(const uint32_t fl, const float c0, const float c1, const flo
 }
 
 // one thread per row: forward over t (costs out, the running episode cost, this rollout's finished episodes), then k_gae's reverse scan
-// with the cost as reward
+// (gae_scan) with the cost as reward
 __global__ __launch_bounds__(WAVE) void k_cost_gae(const uint32_t* __restrict__ flags, const uint8_t* __restrict__ done,
                                                    const float* __restrict__ value, const int T, const int rows, const float c0, const float c1,
                                                    const float c2, const float gamma, const float lam, float* __restrict__ cost,
@@ -80,30 +80,13 @@ __global__ __launch_bounds__(WAVE) void k_cost_gae(const uint32_t* __restrict__ 
     ep_sum[r] = es;
     ep_count[r] = ec;
   }
-  const float gl = gamma * lam;
-  float a = 0.0f, vn = value[(size_t)T * rows + r];
-#pragma unroll 4
-  for (int t = T - 1; t >= 0; --t) {
-    const size_t i = (size_t)t * rows + r;
-    const float v = value[i], nt = done[i] ? 0.0f : 1.0f;
-    const float delta = fmaf(gamma * nt, vn, safe_cost(flags[i], c0, c1, c2)) - v;
-    a = fmaf(gl * nt, a, delta);
-    adv[i] = a;
-    ret[i] = a + v;
-    vn = v;
-  }
+  gae_scan([&](const size_t i) { return safe_cost(flags[i], c0, c1, c2); }, value, done, T, rows, r, gamma, lam, adv, ret);
 }
 
 // ---- pgd_lagrange: ONE workgroup ------------------------------------------------------------------------------------------------------
 // ppo_block_sum's order in double, and for the integer counts
-DEV double safe_block_sum(double v, double* wave_sum) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  if ((threadIdx.x & (WAVE - 1)) == 0) wave_sum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
-}
-DEV long long safe_block_count(long long v, long long* wave_sum) {
+template <class V>
+DEV V safe_block_sum(V v, V* wave_sum) {
 #pragma unroll
   for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
   if ((threadIdx.x & (WAVE - 1)) == 0) wave_sum[threadIdx.x >> 6] = v;
@@ -134,7 +117,7 @@ __global__ __launch_bounds__(256) void k_lagrange(const float* __restrict__ ep_s
     }
   }
   s = safe_block_sum(s, wave_sum);
-  e = safe_block_count(e, wave_count);
+  e = safe_block_sum(e, wave_count);
   if (threadIdx.x == 0 && e > 0) {
     const double jc = s / (double)e;
     double l = (double)state[0] + (double)lr * (jc - (double)cost_limit);

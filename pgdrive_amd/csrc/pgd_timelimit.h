@@ -6,8 +6,8 @@
 // info dict (base_env.py:190-192); an RL library evaluates its critic on it on the host.
 //
 // k_mlp_terminal_value is the critic workgroup of k_mlp_actor_critic -- 16-row tile, 4 waves, ac_lds_bytes, mlp_layer / mlp_store_hidden,
-// the sixteen-lane head -- behind a prologue of its own (tl_load_rows: ac_load_rows with a row mask, as k_mlp_actor_critic_rows keeps
-// ro_load_rows), so k_mlp_actor_critic's code object stays what it was.  blockIdx.y chooses the critic (0) or the cost critic (1).  A
+// the sixteen-lane head -- behind the shared row loader with a rule of its own (tl_load_rows: mlp_load_rows with a row mask, as
+// k_mlp_actor_critic_rows' ro_load_rows is with a list).  blockIdx.y chooses the critic (0) or the cost critic (1).  A
 // workgroup first reads the flags and dones of its 16 rows; every wave forms the same 16-bit mask by ballot (no LDS, no barrier).  A
 // tile without a truncated row -- nearly all of them -- writes its zeros and ends before it reads a weight or an observation.  A row's
 // arithmetic in the tile does not depend on its neighbours, so a truncated row receives bit for bit the critic half of
@@ -26,46 +26,15 @@ DEV bool tl_truncated(const uint32_t f, const bool done, const bool safe_rl_env)
 
 struct TlNets { pgd_value_net v, c; };
 
-// ac_load_rows with a mask: bit r of `mask` set: row row0 + r0 + r of `obs` into row r of the X tile, else zeros (the first form loads
-// the tile's first row in their place and selects the zero: a row that is not truncated is never USED)
+// slot r holds row row0 + r0 + r of `obs` where bit r of `mask` is set; the tile's first row stands in for the others (a row that is not
+// truncated is never USED)
 template <bool NORM>
 DEV void tl_load_rows(const float* obs, const int row0, const int r0, const uint32_t mask, const int obs_stride, const int in_dim, const int kp,
                       const int xs, const int wave, const int lane, float* X, const ObsNorm nm) {
-  constexpr int XCH = 5;
-  if (kp <= WAVE * XCH) {
-    float v[MLP_ROWS / MLP_WAVES][XCH], sh[XCH], sc[XCH];
-    bool live[MLP_ROWS / MLP_WAVES];
-    if (NORM) on_lane_table(nm, in_dim, kp, lane, sh, sc);
-#pragma unroll
-    for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i) {
-      const int r = wave + i * MLP_WAVES;
-      const bool row_in = ((mask >> r) & 1u) != 0u;
-      const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
-      live[i] = row_in;
-#pragma unroll
-      for (int j = 0; j < XCH; ++j) {
-        const int k = lane + WAVE * j;
-        v[i][j] = src[k < in_dim ? k : in_dim - 1];
-        if (!(row_in && k < in_dim)) v[i][j] = 0.0f;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < MLP_ROWS / MLP_WAVES; ++i)
-#pragma unroll
-      for (int j = 0; j < XCH; ++j) {
-        const int k = lane + WAVE * j;
-        if (NORM) v[i][j] = (live[i] && k < in_dim) ? on_apply(v[i][j], sh[j], sc[j], nm.clip) : 0.0f;
-        if (k < kp) X[(wave + i * MLP_WAVES) * xs + k] = v[i][j];
-      }
-  } else
-  for (int r = wave; r < MLP_ROWS; r += MLP_WAVES) {
-    const bool row_in = ((mask >> r) & 1u) != 0u;
-    const float* src = obs + (size_t)(row0 + r0 + (row_in ? r : 0)) * obs_stride;
-    for (int k = lane; k < kp; k += WAVE) {
-      if (NORM) X[r * xs + k] = (row_in && k < in_dim) ? on_apply(src[k], nm.table[k], nm.table[kp + k], nm.clip) : 0.0f;
-      else X[r * xs + k] = (row_in && k < in_dim) ? src[k] : 0.0f;
-    }
-  }
+  mlp_load_rows<NORM>(in_dim, kp, xs, wave, lane, X, nm, [&](const int r, bool& in) {
+    in = ((mask >> r) & 1u) != 0u;
+    return obs + (size_t)(row0 + r0 + (in ? r : 0)) * obs_stride;
+  });
 }
 
 // rows [row0, row0 + n_rows) of `obs`, `flags`, `done` -> term_value[row] (blockIdx.y == 0) and term_cost_value[row] (blockIdx.y == 1):
@@ -133,14 +102,11 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_mlp_terminal_value(cons
   if (part == 0 && r0 + r < n_rows) out[(size_t)(row0 + r0 + r)] = ((mask >> r) & 1u) ? s + b3[0] : 0.0f;
 }
 
-// k_gae with the one-step target of a done row taken from term_value (0 where the episode terminated): a SELECT, value[t + 1] behind a
+// gae_scan with the one-step target of a done row taken from term_value (0 where the episode terminated): a SELECT, value[t + 1] behind a
 // done may hold anything; the trace still ends at every done
-__global__ __launch_bounds__(WAVE) void k_gae_bootstrap(const float* __restrict__ reward, const float* __restrict__ value,
-                                                        const uint8_t* __restrict__ done, const float* __restrict__ term_value, const int T,
-                                                        const int rows, const float gamma, const float lam, float* __restrict__ adv,
-                                                        float* __restrict__ ret) {
-  const int r = (int)blockIdx.x * WAVE + (int)threadIdx.x;
-  if (r >= rows) return;
+template <class RewardOf>
+DEV void gae_scan_bootstrap(const RewardOf reward_of, const float* value, const uint8_t* done, const float* term_value, const int T, const int rows,
+                            const int r, const float gamma, const float lam, float* adv, float* ret) {
   const float gl = gamma * lam;
   float a = 0.0f, vn = value[(size_t)T * rows + r];
 #pragma unroll 4
@@ -148,7 +114,7 @@ __global__ __launch_bounds__(WAVE) void k_gae_bootstrap(const float* __restrict_
     const size_t i = (size_t)t * rows + r;
     const bool dn = done[i] != 0;
     const float v = value[i], tv = term_value[i];
-    const float delta = fmaf(gamma, dn ? tv : vn, reward[i]) - v;
+    const float delta = fmaf(gamma, dn ? tv : vn, reward_of(i)) - v;
     a = fmaf(gl, dn ? 0.0f : a, delta);
     adv[i] = a;
     ret[i] = a + v;
@@ -156,7 +122,17 @@ __global__ __launch_bounds__(WAVE) void k_gae_bootstrap(const float* __restrict_
   }
 }
 
-// k_cost_gae with the same select in its reverse pass; the forward pass (costs, run, ep_sum, ep_count) is k_cost_gae's line for line
+// k_gae with that scan
+__global__ __launch_bounds__(WAVE) void k_gae_bootstrap(const float* __restrict__ reward, const float* __restrict__ value,
+                                                        const uint8_t* __restrict__ done, const float* __restrict__ term_value, const int T,
+                                                        const int rows, const float gamma, const float lam, float* __restrict__ adv,
+                                                        float* __restrict__ ret) {
+  const int r = (int)blockIdx.x * WAVE + (int)threadIdx.x;
+  if (r >= rows) return;
+  gae_scan_bootstrap([&](const size_t i) { return reward[i]; }, value, done, term_value, T, rows, r, gamma, lam, adv, ret);
+}
+
+// k_cost_gae with that scan
 __global__ __launch_bounds__(WAVE) void k_cost_gae_bootstrap(const uint32_t* __restrict__ flags, const uint8_t* __restrict__ done,
                                                              const float* __restrict__ value, const float* __restrict__ term_value, const int T,
                                                              const int rows, const float c0, const float c1, const float c2, const float gamma,
@@ -165,7 +141,7 @@ __global__ __launch_bounds__(WAVE) void k_cost_gae_bootstrap(const uint32_t* __r
                                                              int32_t* __restrict__ ep_count) {
   const int r = (int)blockIdx.x * WAVE + (int)threadIdx.x;
   if (r >= rows) return;
-  {  // (the sums in the order of t: the library's build re-associates fp32 sums elsewhere)
+  {  // k_cost_gae's forward pass line for line (the sums in the order of t).  A copy: as one function called by both, both kernels compiled to other code
 #pragma clang fp reassociate(off)
     float rn = run[r], es = 0.0f;
     int ec = 0;
@@ -185,19 +161,7 @@ __global__ __launch_bounds__(WAVE) void k_cost_gae_bootstrap(const uint32_t* __r
     ep_sum[r] = es;
     ep_count[r] = ec;
   }
-  const float gl = gamma * lam;
-  float a = 0.0f, vn = value[(size_t)T * rows + r];
-#pragma unroll 4
-  for (int t = T - 1; t >= 0; --t) {
-    const size_t i = (size_t)t * rows + r;
-    const bool dn = done[i] != 0;
-    const float v = value[i], tv = term_value[i];
-    const float delta = fmaf(gamma, dn ? tv : vn, safe_cost(flags[i], c0, c1, c2)) - v;
-    a = fmaf(gl, dn ? 0.0f : a, delta);
-    adv[i] = a;
-    ret[i] = a + v;
-    vn = v;
-  }
+  gae_scan_bootstrap([&](const size_t i) { return safe_cost(flags[i], c0, c1, c2); }, value, done, term_value, T, rows, r, gamma, lam, adv, ret);
 }
 
 static bool value_net_ok(const pgd_value_net* n) {

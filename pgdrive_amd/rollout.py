@@ -120,6 +120,7 @@ class _Collector:
         self.returns = t.zeros((T, *rows), **f32)
         self._tick = t.zeros((1, ), dtype=t.int32, device=dev)  # evaluations before this rollout (modulo 2^32)
         self._carry = (self._obs, self._actions, self._logp, self.values)
+        self._checkpointed = []  # (key, the attribute that holds its tensor, what the switch's state is called, the switch when off, on)
         self._primed = False
         self.set_weights(policy_weights, value_weights)
         self.batch = dict(obs=self._obs[:T], actions=self._actions[:T], logp=self._logp[:T], values=self.values, rewards=self.rewards,
@@ -129,11 +130,18 @@ class _Collector:
         """The networks of the rollouts from now on (between two collect() calls): tuples as for Engine.mlp_actor_critic."""
         self.policy_weights, self.value_weights = tuple(policy_weights), tuple(value_weights)
 
+    def _checkpoint(self, on, what, off, **entries):
+        """A switch's setup says what state_dict() holds for it -- key=the name of the attribute that holds the tensor -- and what
+        load_state_dict() calls that state and the switch when it refuses its keys."""
+        self._checkpointed += [(key, attr, what, off, bool(on)) for key, attr in entries.items()]
+
     def _normalise(self, normalise_rewards, clip_reward, reward_eps):
         """The reward side of VecNormalize (behind _allocate): switched on, the collector owns the running returns, the record, the
         scratch and scaled_rewards, and the batch gains scaled_rewards and return_norm."""
         self.normalise_rewards, self.clip_reward, self.reward_eps = bool(normalise_rewards), float(clip_reward), float(reward_eps)
         self._rn_frozen = False
+        self._checkpoint(self.normalise_rewards, "a reward normalisation state", "normalise_rewards=False", return_norm_carry="_rn_carry",
+                         return_norm="return_norm")
         if not self.normalise_rewards:
             return
         if not self.reward_eps >= 0.0:
@@ -157,6 +165,7 @@ class _Collector:
         scratch of the fold, and the batch gains obs_norm and obs_norm_record."""
         self.normalise_obs, self.clip_obs, self.obs_eps = bool(normalise_obs), float(clip_obs), float(obs_eps)
         self._on_frozen = False
+        self._checkpoint(self.normalise_obs, "an observation normalisation state", "normalise_obs=False", obs_norm_record="obs_norm_record")
         if not self.normalise_obs:
             return
         eng, t, name = self.engine, self.engine.torch, type(self).__name__
@@ -194,8 +203,12 @@ class _Collector:
         """The expert guardian (behind _allocate): switched on, the collector owns the takeover state, the applied actions, the info bits
         and the trace, and the batch gains applied_actions, takeover, expert_actions and guardian_trace."""
         self.guardian = None
+        # (with the last flags row: the guardian of the next rollout's first step reads it)
+        self._checkpoint(guardian is not None, "a guardian state", "guardian=None", guardian_state="_guard_state",
+                         guardian_prev_flags="_guard_prev_flags")
         if guardian is None:
             return
+        from . import _abi
         eng, t, name = self.engine, self.engine.torch, type(self).__name__
         g = dict(save_level=0.5, deterministic=False, immediate=False)
         unknown = set(guardian) - set(g) - {"weights"}
@@ -203,10 +216,9 @@ class _Collector:
             raise ValueError("%s: guardian takes weights, save_level, deterministic, immediate (got %s)" % (name, sorted(guardian)))
         g.update(guardian)
         g["weights"] = tuple(g["weights"])
-        if eng.cfg.num_lasers < 40 or eng.cfg.lidar_gaussian_noise > 0.0 or eng.cfg.lidar_dropout_prob > 0.0 or eng.cfg.discrete_action or \
-                eng.cfg.idm_agent:
-            raise NotImplementedError("%s: the guardian needs a continuous-action engine with at least 40 lidar beams and no lidar noise "
-                                      "(num_lasers, gaussian_noise / dropout_prob, discrete_action, IDM_agent)" % name)
+        why = _abi.guardian_unserved(eng.cfg)
+        if why:
+            raise NotImplementedError("%s: the guardian with %s" % (name, why))
         if len(g["weights"]) != 6 or int(g["weights"][0].shape[0]) not in (eng.D, eng.D + 1):
             raise ValueError("%s: the guardian's expert takes %d inputs (or %d with the lateral float)" % (name, eng.D, eng.D + 1))
         self.guardian = g
@@ -215,6 +227,7 @@ class _Collector:
         self.takeover = t.zeros((T, N), dtype=t.uint8, device=dev)
         self.guardian_trace = t.zeros((T, N, 4), dtype=t.float32, device=dev)
         self._guard_state = t.zeros((N, ), dtype=t.uint8, device=dev)
+        self._guard_prev_flags = self.flags[T - 1]
         self.batch.update(applied_actions=self.applied_actions, takeover=self.takeover, expert_actions=self.guardian_trace[..., :2],
                           guardian_trace=self.guardian_trace)
 
@@ -234,6 +247,8 @@ class _Collector:
         """The episode statistics (behind _normalise): switched on, the collector owns the carries, the two records, the scratch and
         ep_returns / ep_lengths, and the batch gains episode_stats, episode_stats_rollout, ep_returns and ep_lengths."""
         self.episode_stats, self._ep_seats = bool(episode_stats), bool(seats)
+        self._checkpoint(self.episode_stats, "an episode statistics state", "episode_stats=False", episode_return_carry="_ep_ret_carry",
+                         episode_length_carry="_ep_len_carry", episode_stats="episode_record")
         if not self.episode_stats:
             return
         eng, t = self.engine, self.engine.torch
@@ -292,61 +307,31 @@ class _Collector:
         record, float64 [16]).  normalise_obs: obs_norm_record (float64 [1 + 2 D]; the table is republished from it by the next
         collect() / prime()).  Empty with every switch off.  Waits for the device: call it outside collect() and outside a graph
         capture."""
-        if not (self.normalise_rewards or self.episode_stats or self.normalise_obs or self.guardian is not None):
+        held = [(key, getattr(self, attr)) for key, attr, _, _, on in self._checkpointed if on]
+        if not held:
             return {}
         self.engine.sync()
-        host = lambda x: x.cpu().numpy().copy()
-        state = {}
-        if self.normalise_rewards:
-            state.update(return_norm_carry=host(self._rn_carry), return_norm=host(self.return_norm))
-        if self.episode_stats:
-            state.update(episode_return_carry=host(self._ep_ret_carry), episode_length_carry=host(self._ep_len_carry),
-                         episode_stats=host(self.episode_record))
-        if self.normalise_obs:
-            state.update(obs_norm_record=host(self.obs_norm_record))
-        if self.guardian is not None:  # (with the last flags row: the guardian of the next rollout's first step reads it)
-            state.update(guardian_state=host(self._guard_state), guardian_prev_flags=host(self.flags[self.T - 1]))
-        return state
+        return {key: x.cpu().numpy().copy() for key, x in held}
 
     def load_state_dict(self, state):
-        """Put back what state_dict() returned (into the collector's own tensors: a captured collect() continues from them)."""
+        """Put back what state_dict() returned (into the collector's own tensors: a captured collect() continues from them).  The keys of
+        a switch this collector was built without are refused; those of its own switches must be there, with the collector's sizes."""
         t, name = self.engine.torch, type(self).__name__
-        if not self.normalise_rewards and any(k in state for k in ("return_norm_carry", "return_norm")):
-            raise ValueError("%s: a reward normalisation state for a collector built with normalise_rewards=False" % name)
-        if not self.episode_stats and any(k in state for k in ("episode_return_carry", "episode_length_carry", "episode_stats")):
-            raise ValueError("%s: an episode statistics state for a collector built with episode_stats=False" % name)
-        if not self.normalise_obs and "obs_norm_record" in state:
-            raise ValueError("%s: an observation normalisation state for a collector built with normalise_obs=False" % name)
-        if self.guardian is None and "guardian_state" in state:
-            raise ValueError("%s: a guardian state for a collector built with guardian=None" % name)
-        if self.guardian is not None:
-            st = np.ascontiguousarray(state["guardian_state"], dtype=np.uint8).reshape(-1)
-            if st.size != self._guard_state.numel():
-                raise ValueError("%s: a guardian state of %d rows for a collector of %d" % (name, st.size, self._guard_state.numel()))
-            self._guard_state.copy_(t.from_numpy(st))
-            self.flags[self.T - 1].copy_(t.from_numpy(np.ascontiguousarray(state["guardian_prev_flags"], dtype=np.int32).reshape(-1)))
-        if self.normalise_rewards:
-            carry = np.ascontiguousarray(state["return_norm_carry"], dtype=np.float32).reshape(-1)
-            record = np.ascontiguousarray(state["return_norm"], dtype=np.float64).reshape(-1)
-            if carry.size != self._rn_carry.numel() or record.size != 4:
-                raise ValueError("%s: a state of %d rows for a collector of %d" % (name, carry.size, self._rn_carry.numel()))
-            self._rn_carry.copy_(t.from_numpy(carry))
-            self.return_norm.copy_(t.from_numpy(record))
-        if self.episode_stats:
-            ret = np.ascontiguousarray(state["episode_return_carry"], dtype=np.float32).reshape(-1)
-            length = np.ascontiguousarray(state["episode_length_carry"], dtype=np.int32).reshape(-1)
-            record = np.ascontiguousarray(state["episode_stats"], dtype=np.float64).reshape(-1)
-            if ret.size != self._ep_ret_carry.numel() or length.size != ret.size or record.size != self.episode_record.numel():
-                raise ValueError("%s: a state of %d rows for a collector of %d" % (name, ret.size, self._ep_ret_carry.numel()))
-            self._ep_ret_carry.copy_(t.from_numpy(ret))
-            self._ep_len_carry.copy_(t.from_numpy(length))
-            self.episode_record.copy_(t.from_numpy(record))
-        if self.normalise_obs:
-            record = np.ascontiguousarray(state["obs_norm_record"], dtype=np.float64).reshape(-1)
-            if record.size != self.obs_norm_record.numel():
-                raise ValueError("%s: a state of %d observation columns for a collector of %d" %
-                                 (name, (record.size - 1) // 2, self.engine.D))
-            self.obs_norm_record.copy_(t.from_numpy(record))
+        for key, attr, what, off, on in self._checkpointed:
+            if not on and key in state:
+                raise ValueError("%s: %s for a collector built with %s" % (name, what, off))
+        put = []
+        for key, attr, what, off, on in self._checkpointed:
+            if not on:
+                continue
+            x = getattr(self, attr)
+            src = t.from_numpy(np.ascontiguousarray(state[key]).reshape(-1)).to(x.dtype)
+            if src.numel() != x.numel():
+                raise ValueError("%s: %s whose %s holds %d values, %d here: a collector of other rows or observation columns" %
+                                 (name, what, key, src.numel(), x.numel()))
+            put.append((x, src))
+        for x, src in put:
+            x.view(-1).copy_(src)
 
     def _stepped(self, t):
         pass
@@ -526,14 +511,10 @@ class SafeRolloutCollector(RolloutCollector):
         """T steps.  Returns RolloutCollector's dict with costs, cost_values, cost_advantages, cost_returns, ep_cost_sum, ep_cost_count
         (the same objects every time, valid until the next call)."""
         super().collect()
-        if self.bootstrap_truncations:
-            self.engine.cost_gae_bootstrap(self.flags, self.dones, self.cost_values, self.term_cost_values, self.costs, self.cost_gamma,
-                                           self.cost_lam, self.running_cost, cost=self.cost, adv=self.cost_advantages, ret=self.cost_returns,
-                                           ep_sum=self.ep_cost_sum, ep_count=self.ep_cost_count)
-            return self.batch
-        self.engine.cost_gae(self.flags, self.dones, self.cost_values, self.costs, self.cost_gamma, self.cost_lam, self.running_cost,
-                             cost=self.cost, adv=self.cost_advantages, ret=self.cost_returns, ep_sum=self.ep_cost_sum,
-                             ep_count=self.ep_cost_count)
+        eng = self.engine
+        gae, term = (eng.cost_gae_bootstrap, (self.term_cost_values, )) if self.bootstrap_truncations else (eng.cost_gae, ())
+        gae(self.flags, self.dones, self.cost_values, *term, self.costs, self.cost_gamma, self.cost_lam, self.running_cost, cost=self.cost,
+            adv=self.cost_advantages, ret=self.cost_returns, ep_sum=self.ep_cost_sum, ep_count=self.ep_cost_count)
         return self.batch
 
 
@@ -567,7 +548,6 @@ class MultiAgentRolloutCollector(_Collector):
                  reward_eps=1e-8, episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8, guardian=None):
         if guardian is not None:
             raise NotImplementedError("MultiAgentRolloutCollector: the expert guardian serves single-agent engines only (pgd_guardian)")
-        self.guardian = None
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A == 1:
             raise NotImplementedError("MultiAgentRolloutCollector serves multi-agent engines: this one has a single agent seat per env and "
@@ -578,6 +558,7 @@ class MultiAgentRolloutCollector(_Collector):
         self._normalise(normalise_rewards, clip_reward, reward_eps)
         self._episodes(episode_stats, seats=True)
         self._obs_norm(normalise_obs, clip_obs, obs_eps)
+        self._guardian(None)
         t = eng.torch
         i32 = dict(dtype=t.int32, device=eng.device)
         self.mask = t.zeros(self.flags.shape, dtype=t.uint8, device=eng.device)

@@ -6,6 +6,7 @@ reference layout (obs/state_obs.py), config keys keep the 
 KeyError like Config.update(allow_add_new_key=False) (utils/config.py:115-125).
 """
 import copy
+import types
 
 import numpy as np
 
@@ -176,17 +177,14 @@ def load_saver_weights(c, obs_dim):
 
 
 def check_saver_config(c):
-    """use_saver=True next to what the guardian does not serve: refused by name."""
+    """use_saver=True next to what the guardian does not serve: refused by name.  What the engine's config will say is
+    _abi.guardian_unserved's (the collectors ask it too), from the env's keys: before a map is generated."""
     lid = c["vehicle_config"]["lidar"]
-    if c["IDM_agent"]:
-        raise NotImplementedError("config['use_saver'] with config['IDM_agent']: the ego is driven by IDMPolicy, there is no action to guard")
-    if c["discrete_action"]:
-        raise NotImplementedError("config['use_saver'] with config['discrete_action']: the guardian compares continuous actions")
-    if lid["gaussian_noise"] != 0.0 or lid["dropout_prob"] != 0.0:
-        raise NotImplementedError("config['use_saver'] with lidar gaussian_noise / dropout_prob: the reference's guardian reads the un-noised "
-                                  "cloud points, which this engine does not keep")
-    if (lid["num_lasers"] if lid["distance"] > 0 else 0) < _abi.GUARD_MIN_LASERS:
-        raise NotImplementedError("config['use_saver'] with fewer than %d lidar beams: the guardian's fan slices need them" % _abi.GUARD_MIN_LASERS)
+    why = _abi.guardian_unserved(types.SimpleNamespace(
+        idm_agent=c["IDM_agent"], discrete_action=c["discrete_action"], lidar_gaussian_noise=lid["gaussian_noise"],
+        lidar_dropout_prob=lid["dropout_prob"], num_lasers=lid["num_lasers"] if lid["distance"] > 0 else 0))
+    if why:
+        raise NotImplementedError("config['use_saver'] with " + why)
     if c.get("use_topdown"):
         raise NotImplementedError("config['use_saver'] with config['use_topdown']: the expert reads the lidar observation")
 

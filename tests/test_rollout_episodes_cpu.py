@@ -4,6 +4,7 @@ no device, and the host logic of the three collectors on a recording engine."""
 import ctypes as C
 import os
 import re
+import types
 
 import numpy as np
 import pytest
@@ -249,3 +250,100 @@ def test_switch_on_one_call_on_the_raw_rewards(kind, normalise):
     assert np.array_equal(col._ep_ret_carry.numpy(), ret) and np.array_equal(col._ep_len_carry.numpy(), length)
     none = col.episode_summary()
     assert none["episodes"] == 0 and none["steps"] == 0 and all(none[k] is None for k in none if k not in ("episodes", "steps"))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the checkpoint of a collector with every switch on at once
+# ---------------------------------------------------------------------------------------------------------------------
+class AllSwitchesEngine(RecordingEngine):
+    """RecordingEngine with the two switches it lacks, as recorded calls that move their state: the observation normalisation (the fold
+    counts the rows it was given) and the guardian (the takeover state alternates with the tick)."""
+    cfg = types.SimpleNamespace(idm_agent=False, discrete_action=False, lidar_gaussian_noise=0.0, lidar_dropout_prob=0.0, num_lasers=40)
+
+    def obs_norm_work_bytes(self, D, rows):
+        return 8
+
+    def obs_norm_state(self, D):
+        t = self.torch
+        return t.zeros((1 + 2 * D, ), dtype=t.float64), t.zeros((2, (D + 3) & ~3), dtype=t.float32)
+
+    def obs_norm_publish(self, record, table, eps=1e-8):
+        self.calls.append("obs_norm_publish")
+
+    def obs_norm_bind(self, table, D, clip):
+        self.calls.append("obs_norm_bind")
+
+    def obs_norm_update(self, obs, record, index=None, count=None, n_list=None, work=None):
+        self.calls.append("obs_norm_update")
+        record.add_(float(n_list))
+
+    def guardian(self, weights, save_level, agent, state, applied, info, seed, tick, **kw):
+        self.calls.append("guardian")
+        state.copy_((self.torch.arange(state.numel()) + tick) % 2)
+
+
+SWITCH_KEYS = {"normalise_rewards": {"return_norm_carry", "return_norm"},
+               "episode_stats": {"episode_return_carry", "episode_length_carry", "episode_stats"},
+               "normalise_obs": {"obs_norm_record"},
+               "guardian": {"guardian_state", "guardian_prev_flags"}}
+SWITCH_OFF = {"normalise_rewards": "normalise_rewards=False", "episode_stats": "episode_stats=False", "normalise_obs": "normalise_obs=False",
+              "guardian": "guardian=None"}
+
+
+def _all_switches(kind, **kw):
+    from pgdrive_amd.rollout import MultiAgentRolloutCollector, RolloutCollector, SafeRolloutCollector
+    marl = kind == "marl"
+    eng = AllSwitchesEngine(rc.N, rc.A if marl else 1, rc.D, rc._script((rc.N, rc.A) if marl else (rc.N, ), marl))
+    if kind == "safe":
+        return eng, SafeRolloutCollector(eng, rc.W6, rc.W6, rc.W6, rc.T, gamma=0.5, lam=0.5, **kw)
+    return eng, (MultiAgentRolloutCollector if marl else RolloutCollector)(eng, rc.W6, rc.W6, rc.T, gamma=0.5, lam=0.5, **kw)
+
+
+def _held(col):
+    """state_dict()'s keys -> the collector's own tensors, for the switches that are on."""
+    held = {}
+    if col.normalise_rewards:
+        held.update(return_norm_carry=col._rn_carry, return_norm=col.return_norm)
+    if col.episode_stats:
+        held.update(episode_return_carry=col._ep_ret_carry, episode_length_carry=col._ep_len_carry, episode_stats=col.episode_record)
+    if col.normalise_obs:
+        held.update(obs_norm_record=col.obs_norm_record)
+    if col.guardian is not None:
+        held.update(guardian_state=col._guard_state, guardian_prev_flags=col.flags[col.T - 1])
+    return held
+
+
+@pytest.mark.parametrize("kind", ["single", "safe", "marl"])
+def test_every_switch_at_once_one_checkpoint(kind):
+    """Every switch the collector has, on at once (the multi-agent one has no guardian): state_dict() holds the union of the switches' own
+    keys behind ONE sync; a round trip restores every tensor exactly; a collector built without one switch refuses the state, and each
+    of that switch's keys alone, by the switch's name."""
+    import torch
+    on = dict(normalise_rewards=True, episode_stats=True, normalise_obs=True)
+    if kind != "marl":
+        on["guardian"] = dict(weights=tuple(torch.zeros((rc.D, 1)) for _ in range(6)))
+    eng, col = _all_switches(kind, **on)
+    for _ in range(3):   # (the script's third rollout ends on a row with dones: the guardian's previous flags are not all zero)
+        col.collect()
+    del eng.calls[:]
+    state = col.state_dict()
+    assert eng.calls == ["sync"]
+    assert set(state) == set().union(*(SWITCH_KEYS[s] for s in on))
+    held = _held(col)
+    assert set(held) == set(state)
+    for key, x in held.items():
+        assert state[key].dtype == x.numpy().dtype and np.array_equal(state[key].reshape(-1), x.numpy().reshape(-1)), key
+        assert x.count_nonzero() > 0, "%s never moved: the round trip would prove nothing" % key
+    eng2, col2 = _all_switches(kind, **on)
+    assert not any(torch.equal(x2, held[key]) for key, x2 in _held(col2).items())
+    col2.load_state_dict(state)
+    for key, x2 in _held(col2).items():
+        assert x2.dtype == held[key].dtype and x2.shape == held[key].shape and torch.equal(x2, held[key]), key
+    for switch in on:
+        eng3, col3 = _all_switches(kind, **{s: v for s, v in on.items() if s != switch})
+        assert set(col3.state_dict()) == set(state) - SWITCH_KEYS[switch]
+        with pytest.raises(ValueError, match=SWITCH_OFF[switch]):
+            col3.load_state_dict(state)
+        for key in SWITCH_KEYS[switch]:
+            with pytest.raises(ValueError, match=SWITCH_OFF[switch]):
+                col3.load_state_dict({key: state[key]})
