@@ -19,8 +19,8 @@ import pytest
 
 from tests import actor_critic_ref as ar
 from tests import policy_ref as pr
-from tests.train_util import ERR_ARG, SENT, ac_nets as _nets, bits_equal as _bits_equal, dev as _dev, ego_engine as _ego_engine, snapshot as _snapshot, \
-    synchronised_rollouts
+from tests.train_util import ERR_ARG, KEYS, SENT, Traffic, ac_nets as _nets, bits_equal as _bits_equal, dev as _dev, eager_then_graph, \
+    ego_engine as _ego_engine, make_collector, snapshot as _snapshot, synchronised_rollouts
 
 pytestmark = pytest.mark.gpu
 
@@ -373,34 +373,17 @@ def test_gae(descs, T):
 # the collector
 # ---------------------------------------------------------------------------------------------------------------------
 COL_N, COL_T, COL_HORIZON, COL_SEED = 64, 16, 12, 3
-KEYS = ("obs", "actions", "logp", "values", "rewards", "dones", "flags", "advantages", "returns")
 
 
-class _Col:
+def _Col(descs):
     """64 envs of the default configuration with traffic and a short horizon, freshly reset; random networks of the expert's shape."""
-    def __init__(self, descs):
-        import torch
-        from pgdrive_amd import _abi
-        from pgdrive_amd.engine import Engine
-        from tests import util
-        mb, sb = util.make_banks(descs, n_maps=8)
-        self.eng = eng = Engine(_abi.make_config(COL_N, auto_reset=1, horizon=COL_HORIZON, seed=5), mb, sb)
-        self.first = eng.reset(np.arange(COL_N) % 8).view(COL_N, -1).clone()
-        rng = np.random.default_rng(0)
-        p, v = ar.make_networks(rng, eng.D, 4)
-        p[4][:, 0] *= 0.05   # (steering: the cars stay on the road for a while, tests/test_policy_gpu.py)
-        p[5][1] = 0.5        # (throttle: they drive)
-        self.p, self.v = p, v
-        self.pw, self.vw = tuple(_dev(w) for w in p), tuple(_dev(w) for w in v)
-        eng.sync()
-        torch.cuda.synchronize()
+    return Traffic(descs, COL_N, COL_T, COL_SEED, horizon=COL_HORIZON)
 
 
 def test_collector_equals_the_synchronised_loop_eagerly_and_from_a_graph(descs):
     import torch
-    from pgdrive_amd.rollout import RolloutCollector
     S = _Col(descs)
-    want = synchronised_rollouts(S, 3, COL_T, COL_SEED, KEYS)
+    want = synchronised_rollouts(S, 3)
     first_obs = S.first.cpu().numpy()
     S.eng.close()
 
@@ -425,7 +408,7 @@ def test_collector_equals_the_synchronised_loop_eagerly_and_from_a_graph(descs):
 
     # (a) the collector, eagerly, nothing synchronised inside collect()
     A = _Col(descs)
-    col = RolloutCollector(A.eng, A.pw, A.vw, COL_T, gamma=0.99, lam=0.95, seed=COL_SEED)
+    col = make_collector("single", A, gamma=0.99, lam=0.95)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s), torch.no_grad():
@@ -441,23 +424,6 @@ def test_collector_equals_the_synchronised_loop_eagerly_and_from_a_graph(descs):
 
     # (b) collect() captured in a HIP graph behind one eager rollout, replayed twice: the device counter advances the tick
     B = _Col(descs)
-    col = RolloutCollector(B.eng, B.pw, B.vw, COL_T, gamma=0.99, lam=0.95, seed=COL_SEED)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s), torch.no_grad():
-        got = _snapshot(col.collect(), KEYS)
-        for key in KEYS:
-            assert _bits_equal(got[key], want[0][key]), key
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(g, stream=s):
-        batch = col.collect()
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s), torch.no_grad():
-        for k in (1, 2):
-            g.replay()
-            got = _snapshot(batch, KEYS)
-            for key in KEYS:
-                assert _bits_equal(got[key], want[k][key]), "graph replay %d: %s differs from the synchronised loop" % (k, key)
-    del g
+    col = make_collector("single", B)
+    eager_then_graph(col.collect, lambda: _snapshot(col.batch, KEYS), want)
     B.eng.close()

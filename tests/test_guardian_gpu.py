@@ -18,7 +18,8 @@ from pgdrive_amd import _abi
 from tests import actor_critic_ref as ar
 from tests import guardian_ref as gr
 from tests import util
-from tests.train_util import SENT, bits_equal as _bits_equal, dev as _dev, snapshot as _snapshot
+from tests.train_util import KEYS, SENT, Traffic, bits_equal as _bits_equal, dev as _dev, eager_then_graph, make_collector, \
+    snapshot as _snapshot, synchronised_rollouts
 
 pytestmark = pytest.mark.gpu
 
@@ -305,7 +306,7 @@ def test_first_call_inside_a_graph_capture_and_the_device_tick(descs):
         with torch.cuda.stream(s):  # (the engine moves to the capture's stream outside the capture; no guardian launch yet)
             eng.lane_keep_actions(torch.zeros((rows, 1, 2), device="cuda"), 0)
         torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
+        g = torch.cuda.CUDAGraph()   # (its own capture: the first call on a fresh engine is made inside the capture, nothing runs eagerly in front)
         with torch.no_grad(), torch.cuda.graph(g, stream=s):
             eng.guardian(expert, 1.0, act, st, applied, info, SEED, 3, trace=trace, obs=obs)
             counter.add_(1)
@@ -434,72 +435,19 @@ def test_scalar_env_reports_the_three_info_keys():
 # collectors
 # ---------------------------------------------------------------------------------------------------------------------
 COL_N, COL_T, COL_SEED = 16, 8, 3
-KEYS = ("obs", "actions", "logp", "values", "rewards", "dones", "flags", "advantages", "returns")
 GKEYS = KEYS + ("applied_actions", "takeover", "guardian_trace")
 
 
-class _Col:
-    def __init__(self, descs):
-        import torch
-        from pgdrive_amd.engine import Engine
-        from pgdrive_amd.vec_env import load_saver_weights
-        mb, sb = util.make_banks(descs, n_maps=8)
-        self.eng = eng = Engine(_abi.make_config(COL_N, auto_reset=1, horizon=12, seed=5), mb, sb)
-        self.first = eng.reset(np.arange(COL_N) % 8).view(COL_N, -1).clone()
-        p, v = ar.make_networks(np.random.default_rng(0), eng.D, 4)
-        p[4][:, 0] *= 0.05
-        p[5][0] = 0.5   # (steering to one side: the guardian has something to do)
-        p[5][1] = 0.5
-        self.pw, self.vw = tuple(_dev(w) for w in p), tuple(_dev(w) for w in v)
-        self.expert = tuple(_dev(w) for w in load_saver_weights(dict(saver_weights=FIXTURE), eng.D))
-        self.guardian = dict(weights=self.expert, save_level=0.5)
-        eng.sync()
-        torch.cuda.synchronize()
-
-
-def _by_hand(S, n_rollouts):
-    """The collector's calls one at a time with a synchronisation behind each: evaluation j and the guardian of row j have tick j."""
-    import torch
-    from pgdrive_amd.rollout import GUARDIAN_SEED_XOR
-    eng, N, T = S.eng, COL_N, COL_T
-    obs = S.first.clone()
-    st = torch.zeros(N, dtype=torch.uint8, device="cuda")
-    prev = torch.zeros((N, 1), dtype=torch.int32, device="cuda")
-
-    def evaluate(o, tick):
-        a = torch.zeros((N, 1, 2), device="cuda"); lp = torch.zeros((N, 1), device="cuda"); v = torch.zeros((N, 1), device="cuda")
-        eng.mlp_actor_critic(S.pw, S.vw, a, lp, v, COL_SEED, tick, obs=o)
-        torch.cuda.synchronize()
-        return a, lp, v
-    a, lp, v = evaluate(obs, 0)
-    out = []
-    for k in range(n_rollouts):
-        rec = {key: [] for key in GKEYS}
-        for t in range(T):
-            rec["obs"].append(obs.view(N, -1)); rec["actions"].append(a.view(N, 2)); rec["logp"].append(lp.view(N)); rec["values"].append(v.view(N))
-            applied = torch.zeros((N, 1, 2), device="cuda"); info = torch.zeros(N, dtype=torch.uint8, device="cuda"); tr = torch.zeros((N, 4), device="cuda")
-            eng.guardian(S.expert, 0.5, a, st, applied, info, COL_SEED ^ GUARDIAN_SEED_XOR, k * T + t, prev_flags=prev, trace=tr, obs=obs)
-            torch.cuda.synchronize()
-            obs, rew, done, flags = eng.step(applied, out=eng.make_outputs())
-            torch.cuda.synchronize()
-            prev = flags.clone()
-            rec["applied_actions"].append(applied.view(N, 2)); rec["takeover"].append(info); rec["guardian_trace"].append(tr)
-            rec["rewards"].append(rew.view(N)); rec["dones"].append(done.view(N)); rec["flags"].append(flags.view(N))
-            a, lp, v = evaluate(obs, k * T + t + 1)
-        rec["values"].append(v.view(N))
-        r = {key: torch.stack(rec[key]) for key in GKEYS if rec[key]}
-        r["advantages"], r["returns"] = eng.gae(r["rewards"], r["values"], r["dones"], 0.99, 0.95)
-        torch.cuda.synchronize()
-        out.append(r)
-    return out
+def _Col(descs):
+    """16 envs with traffic, the policy steering to one side (the guardian has something to do), the expert of the fixture at save_level 0.5."""
+    return Traffic(descs, COL_N, COL_T, COL_SEED, steer_bias=0.5, expert=FIXTURE)
 
 
 def test_collector_with_guardian(descs):
     import torch
-    from pgdrive_amd.rollout import MultiAgentRolloutCollector, RolloutCollector
-    from tests.train_util import synchronised_rollouts
+    from pgdrive_amd.rollout import MultiAgentRolloutCollector
     S = _Col(descs)
-    want = _by_hand(S, 3)
+    want = synchronised_rollouts(S, 3, guardian=True)
     S.eng.close()
     take = sum(int((r["takeover"] & 1).sum()) for r in want)
     print("collector: takeover in %d of %d env-steps" % (take, 3 * COL_N * COL_T))
@@ -507,7 +455,7 @@ def test_collector_with_guardian(descs):
 
     # (a) eagerly; the takeover state survives from rollout to rollout and is part of state_dict()
     A = _Col(descs)
-    col = RolloutCollector(A.eng, A.pw, A.vw, COL_T, seed=COL_SEED, guardian=A.guardian)
+    col = make_collector("single", A, guardian=A.guardian)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s), torch.no_grad():
@@ -524,23 +472,8 @@ def test_collector_with_guardian(descs):
 
     # (b) one eager rollout, then collect() captured in a HIP graph and replayed twice: the device tick advances the expert's noise too
     B = _Col(descs)
-    col = RolloutCollector(B.eng, B.pw, B.vw, COL_T, seed=COL_SEED, guardian=B.guardian)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s), torch.no_grad():
-        col.collect()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(g, stream=s):
-        batch = col.collect()
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s), torch.no_grad():
-        for k in (1, 2):
-            g.replay()
-            got = _snapshot(batch, GKEYS)
-            for key in GKEYS:
-                assert _bits_equal(got[key], want[k][key]), "graph replay %d: %s differs from the calls made by hand" % (k, key)
-    del g
+    col = make_collector("single", B, guardian=B.guardian)
+    eager_then_graph(col.collect, lambda: _snapshot(col.batch, GKEYS), want)
     B.eng.close()
 
     # the safe collector takes the same argument: the cost critic beside actor and critic changes nothing of what is applied
@@ -556,10 +489,10 @@ def test_collector_with_guardian(descs):
     # (c) guardian=None: the bytes of today -- and the agent's own stream under the guardian equals them up to the first step whose
     # applied action differs
     Cc = _Col(descs)
-    plain = synchronised_rollouts(Cc, 1, COL_T, COL_SEED, KEYS)[0]
+    plain = synchronised_rollouts(Cc, 1)[0]
     Cc.eng.close()
     Dd = _Col(descs)
-    col = RolloutCollector(Dd.eng, Dd.pw, Dd.vw, COL_T, seed=COL_SEED, guardian=None)
+    col = make_collector("single", Dd, guardian=None)
     with torch.no_grad():
         got = _snapshot(col.collect(), KEYS)
     assert set(col.batch) == set(KEYS) and col.state_dict() == {}

@@ -19,8 +19,9 @@ import pytest
 
 from tests import actor_critic_ref as ar
 from tests import marl_rollout_ref as mr
-from tests.train_util import ERR_ARG, SENT, ac_nets as _nets, bits_equal as _bits_equal, dev as _dev, ego_engine as _ego_engine, snapshot as _snapshot, \
-    synchronised_rollouts
+from tests import train_util
+from tests.train_util import ERR_ARG, SENT, Roundabout, ac_nets as _nets, bits_equal as _bits_equal, dev as _dev, eager_then_graph, \
+    ego_engine as _ego_engine, make_collector, np_bits as _bits, snapshot as _snapshot, synchronised_rollouts
 
 pytestmark = pytest.mark.gpu
 
@@ -204,10 +205,6 @@ def _listed(eng, x, pw, vw, seed, tick, k, listed, det=False, group=-1, lo=0, hi
     return a[:rows], lp[:rows], v[:rows]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
-
-
 def _compare(got, want, listed, lo, hi, critic, where):
     on = np.zeros(len(want[0]), dtype=bool)
     on[listed] = True
@@ -372,37 +369,8 @@ def test_gae_masked(descs, T):
 # ---------------------------------------------------------------------------------------------------------------------
 # the collector
 # ---------------------------------------------------------------------------------------------------------------------
-COL_N, COL_A, COL_T, COL_HORIZON, COL_DELAY, COL_SEED, COL_ROLLOUTS = 6, 5, 32, 40, 3, 3, 3
-COL_CUT_ENVS, COL_CUT_AT = (4, 5), 12
-KEYS = ("obs", "actions", "logp", "values", "rewards", "dones", "flags", "advantages", "returns", "mask", "index", "count")
-
-
-class _Col:
-    """The roundabout with 5 seats, 6 envs, horizon 40, delay_done 3, freshly reset; random networks of the expert's shape with
-    log_std around 0 (the sampled actions are wide: agents leave the road and crash within a rollout).
-    Envs 4 and 5 start with their episode clock at 5 x horizon - 12, set through the checkpoint interface: from a fresh reset the env-wide
-    cut at 5 x horizon cannot be reached while an agent still drives -- no agent is spawned once the clock has passed the horizon, and
-    every agent ends within `horizon` steps of its own -- so a rollout that starts at a reset would never hold a PGD_F_RESET on an
-    agent that is not done."""
-    def __init__(self):
-        import torch
-        from pgdrive_amd import _abi
-        from pgdrive_amd.engine import Engine
-        from tests import util
-        _, mb, sb = util.make_marl_banks(num_agents=COL_A)
-        self.eng = eng = Engine(util.marl_config(COL_N, sb, horizon=COL_HORIZON, delay_done=COL_DELAY, seed=5), mb, sb)
-        self.first = eng.reset(np.arange(COL_N) % len(sb.scenarios)).clone()
-        f, i, ei = eng.get_state()
-        ei[_abi.EI["EP_STEPS"], list(COL_CUT_ENVS)] = 5 * COL_HORIZON - COL_CUT_AT
-        eng.set_state(f, i, ei)
-        self.active0 = (i[_abi.SI["STATUS"], :, :COL_A] == _abi.ST_ACTIVE)
-        rng = np.random.default_rng(0)
-        p, v = ar.make_networks(rng, eng.D, 4)
-        p[5][1] = 0.5        # (throttle: they drive)
-        p[5][2:4] += 1.0     # (log_std around 0)
-        self.pw, self.vw = tuple(_dev(w) for w in p), tuple(_dev(w) for w in v)
-        eng.sync()
-        torch.cuda.synchronize()
+COL_N, COL_A, COL_T, COL_SEED, COL_ROLLOUTS = Roundabout.N, Roundabout.A, 32, 3, 3
+KEYS = train_util.KEYS + ("mask", "index", "count")
 
 
 def _batch_equal(got, want, where):
@@ -416,7 +384,7 @@ def _batch_equal(got, want, where):
 
 
 def test_collector_on_the_roundabout():
-    """Three rollouts of T = 32 on 6 envs x 5 seats (horizon 40, delay_done 3; see _Col for the two envs that start near 5 x horizon).
+    """Three rollouts of T = 32 on 6 envs x 5 seats (horizon 40, delay_done 3; see train_util.Roundabout for the two envs that start near 5 x horizon).
     They hold -- asserted, so that nothing below passes vacuously -- agents ending by done, respawns (PGD_F_NEW without PGD_F_RESET), env
     resets, and resets that cut an agent that was not done.  Then:
     acted(t + 1) == live(t) for every t within and across the rollouts, and acted(0) is the state's ACTIVE seats; every tensor of the
@@ -424,10 +392,9 @@ def test_collector_on_the_roundabout():
     rows with mask 1 hold what mlp_actor_critic over ALL rows gives them; adv / ret within tolerance of the float64 checker on the
     collector's own arrays; index[:count] == flatnonzero(mask); actions, logp and values of seats that are not live are zero."""
     import torch
-    from pgdrive_amd.rollout import MultiAgentRolloutCollector
     T, N, A = COL_T, COL_N, COL_A
-    S = _Col()
-    want = synchronised_rollouts(S, COL_ROLLOUTS, COL_T, COL_SEED, KEYS, live0=np.flatnonzero(S.active0.reshape(-1)).astype(np.int32))
+    S = Roundabout(COL_T, COL_SEED)
+    want = synchronised_rollouts(S, COL_ROLLOUTS)
 
     # what the rollouts hold
     fl = np.concatenate([r["flags"].cpu().numpy() for r in want]).view(np.uint32)      # [3 T, N, A]
@@ -471,8 +438,8 @@ def test_collector_on_the_roundabout():
     S.eng.close()
 
     # (a) the collector, eagerly, nothing synchronised inside collect()
-    E = _Col()
-    col = MultiAgentRolloutCollector(E.eng, E.pw, E.vw, T, gamma=0.99, lam=0.95, seed=COL_SEED)
+    E = Roundabout(COL_T, COL_SEED)
+    col = make_collector("marl", E, gamma=0.99, lam=0.95)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s), torch.no_grad():
@@ -487,20 +454,7 @@ def test_collector_on_the_roundabout():
     E.eng.close()
 
     # (b) collect() captured in a HIP graph behind one eager rollout (which primes the collector), replayed twice
-    B = _Col()
-    col = MultiAgentRolloutCollector(B.eng, B.pw, B.vw, T, gamma=0.99, lam=0.95, seed=COL_SEED)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s), torch.no_grad():
-        _batch_equal(_snapshot(col.collect(), KEYS), want[0], "warm-up collect")
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(g, stream=s):
-        batch = col.collect()
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s), torch.no_grad():
-        for k in (1, 2):
-            g.replay()
-            _batch_equal(_snapshot(batch, KEYS), want[k], "graph replay %d" % k)
-    del g
+    B = Roundabout(COL_T, COL_SEED)
+    col = make_collector("marl", B)
+    eager_then_graph(col.collect, lambda: _snapshot(col.batch, KEYS), want, compare=_batch_equal)
     B.eng.close()

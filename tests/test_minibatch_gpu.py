@@ -18,8 +18,8 @@ import pytest
 from tests import actor_critic_ref as ar
 from tests import minibatch_ref as mr
 from tests import ppo_ref as rf
-from tests.test_ppo_update_gpu import _check, _grad, _Problem
-from tests.train_util import ERR_ARG, SENT, dev as _dev, ego_engine
+from tests.ppo_util import Problem as _Problem, check as _check, grad as _grad
+from tests.train_util import ERR_ARG, EVERY_LEARNER, Traffic, assert_same, dev as _dev, ego_engine, learner_state, make_collector, update_by_hand
 
 pytestmark = pytest.mark.gpu
 
@@ -146,8 +146,7 @@ def _adam_state(p0, n):
 def _same(a, b, what):
     import torch
     torch.cuda.synchronize()
-    for key in ("p", "m", "v", "step"):
-        assert torch.equal(a[key].view(torch.int32), b[key].view(torch.int32)), "%s: %s differs" % (what, key)
+    assert_same(a, b, what)
 
 
 @pytest.mark.parametrize("n_elem", [1, 1000])
@@ -245,54 +244,15 @@ SHUF_SEED = 9
 STOP_LR, STOP_KL = 3e-4, 19.0
 
 
-class _Single:
-    def __init__(self, descs):
-        import torch
-        from pgdrive_amd import _abi
-        from pgdrive_amd.engine import Engine
-        from pgdrive_amd.rollout import RolloutCollector
-        from tests import util
-        mb, sb = util.make_banks(descs, n_maps=8)
-        self.eng = eng = Engine(_abi.make_config(CL_N, auto_reset=1, horizon=12, seed=5), mb, sb)
-        eng.reset(np.arange(CL_N) % 8)
-        p, v = ar.make_networks(np.random.default_rng(0), eng.D, 4)
-        p[4][:, 0] *= 0.05
-        p[5][1] = 0.5
-        self.col = RolloutCollector(eng, tuple(_dev(w) for w in p), tuple(_dev(w) for w in v), CL_T, seed=CL_SEED)
-        eng.sync()
-        torch.cuda.synchronize()
+def _Single(descs):
+    S = Traffic(descs, CL_N, CL_T, CL_SEED)
+    S.col = make_collector("single", S)
+    return S
 
 
-def _learner_state(L):
-    import torch
-    torch.cuda.synchronize()
-    own = dict(params=L.params, m=L.m, v=L.v, step=L.step, stats=L.stats, grads=L.grads, shuffled=L.shuffled, live_count=L.live_count, gate=L.gate,
-               epoch=L._epoch)
-    return {k: x.clone() for k, x in own.items() if x is not None}
-
-
-def _equal_states(a, b, what, skip=()):
-    import torch
+def _equal_states(a, b, what):
     assert set(a) == set(b)
-    for key in a:
-        if key not in skip:
-            assert torch.equal(a[key].view(torch.int32), b[key].view(torch.int32)), "%s: %s differs" % (what, key)
-
-
-def _by_hand(eng, L, hb, n_steps=None, index=None, count=None):
-    """Today's update on L's buffers: adv_stats, then ppo_grad + adam per epoch and minibatch over the list as it lies; n_steps: stop after
-    that many."""
-    norm = eng.adv_stats(hb["advantages"], out=L.adv_stats)
-    k = 0
-    for _ in range(CL_KW["epochs"]):
-        for j in range(CL_KW["minibatches"]):
-            if n_steps is not None and k == n_steps:
-                return
-            eng.ppo_grad(L.policy_weights, L.value_weights, L.policy_grads, L.value_grads, hb["obs"], hb["actions"], hb["logp"], hb["advantages"],
-                         hb["returns"], L.stats[k], L.work, start=j, stride=4, rows=CL_ROWS // 4, adv_stats=norm, index=index, count=count,
-                         n_list=CL_ROWS)
-            eng.adam(L.params, L.grads, L.m, L.v, L.step, L.lr, eps=1e-5, max_grad_norm=0.5)
-            k += 1
+    assert_same(a, b, what, need=EVERY_LEARNER)
 
 
 def test_switches_off_and_a_shuffled_update_by_hand(descs):
@@ -319,24 +279,13 @@ def test_switches_off_and_a_shuffled_update_by_hand(descs):
                 batch = S.col.collect()
                 if it == 0:
                     off.update(batch)
-                    _by_hand(eng, off_hand, batch)
-                    _equal_states(_learner_state(off), _learner_state(off_hand), "switches off")
+                    update_by_hand(eng, off_hand, batch, **CL_KW)
+                    _equal_states(learner_state(off), learner_state(off_hand), "switches off")
                 stats = LS.update(batch)
-                got = _learner_state(LS)
-                live.fill_(CL_ROWS)
-                norm = eng.adv_stats(batch["advantages"], out=hand.adv_stats)
-                k = 0
-                for e in range(2):
-                    eng.shuffle_index(None, live, CL_ROWS, SHUF_SEED, e, epoch_dev=epoch, out=shuffled)
-                    for j in range(4):
-                        eng.ppo_grad(hand.policy_weights, hand.value_weights, hand.policy_grads, hand.value_grads, batch["obs"], batch["actions"],
-                                     batch["logp"], batch["advantages"], batch["returns"], hand.stats[k], hand.work, start=j, stride=4,
-                                     rows=CL_ROWS // 4, index=shuffled, count=live, n_list=CL_ROWS, adv_stats=norm)
-                        eng.adam(hand.params, hand.grads, hand.m, hand.v, hand.step, 3e-4, eps=1e-5, max_grad_norm=0.5)
-                        k += 1
-                epoch.add_(2)
-                want = _learner_state(hand)
-                want.update(shuffled=shuffled.clone(), live_count=live.clone(), epoch=epoch.clone())
+                got = learner_state(LS)
+                update_by_hand(eng, hand, batch, shuffle=dict(seed=SHUF_SEED, shuffled=shuffled, live=live, epoch=epoch), **CL_KW)
+                want = learner_state(hand)
+                want.update(shuffled=shuffled.clone(), live_count=live.clone(), _epoch=epoch.clone())
                 _equal_states(got, want, "iteration %d, shuffle=True" % it)
                 st = stats.cpu().numpy()
                 assert np.isfinite(st).all() and (st[:, 0] == CL_ROWS // 4).all() and int(LS.step[0]) == 8 * (it + 1)
@@ -354,7 +303,7 @@ def test_switches_off_and_a_shuffled_update_by_hand(descs):
             batch = S.col.collect()
             LS.update(batch)
             L2.update(batch)
-            _equal_states(_learner_state(LS), _learner_state(L2), "after load_state_dict")
+            _equal_states(learner_state(LS), learner_state(L2), "after load_state_dict")
             with pytest.raises(ValueError, match="_epoch"):
                 off.load_state_dict(sd)
             L3 = PPOLearner(S.col, lr_scale=True, **CL_KW)
@@ -381,13 +330,13 @@ def test_collect_and_update_from_one_graph_draws_new_permutations(descs):
             for it in range(3):
                 LA.lr_scale.fill_(scales[it])
                 LA.update(A.col.collect())
-                want.append(_learner_state(LA))
+                want.append(learner_state(LA))
                 assert LA.gate.tolist() == [0, 8, 0, 0] and int(LA.live_count[0]) == CL_ROWS
                 assert (LA.shuffled.cpu().numpy() == mr.permutation(CL_ROWS, SHUF_SEED, 2 * it + 1)).all()
             assert not torch.equal(want[1]["shuffled"], want[2]["shuffled"])
             LG.update(G.col.collect())
-            _equal_states(_learner_state(LG), want[0], "the eager iteration of the graph's engine")
-            graph = torch.cuda.CUDAGraph()
+            _equal_states(learner_state(LG), want[0], "the eager iteration of the graph's engine")
+            graph = torch.cuda.CUDAGraph()   # (its own capture: the host writes lr_scale between the replays)
         with torch.no_grad(), torch.cuda.graph(graph, stream=s):
             LG.update(G.col.collect())
         torch.cuda.synchronize()
@@ -395,7 +344,7 @@ def test_collect_and_update_from_one_graph_draws_new_permutations(descs):
             for it in (1, 2):
                 LG.lr_scale.fill_(scales[it])
                 graph.replay()
-                _equal_states(_learner_state(LG), want[it], "graph replay %d" % it)
+                _equal_states(learner_state(LG), want[it], "graph replay %d" % it)
         del graph
     finally:
         A.eng.close()
@@ -430,7 +379,7 @@ def test_an_update_that_stops_inside(descs):
             assert (st[applied + 1:, 0] == 0).all() and (st[applied + 1:] == 0).all(), "rows behind the stop are not empty"
             assert int(L.live_count[0]) == 0 and int(L.step[0]) == applied
             assert bool((L.grads == 0).all()) or applied + 1 == total, "a gradient call behind the stop found live rows"
-            _by_hand(eng, twin, batch, n_steps=applied)
+            update_by_hand(eng, twin, batch, n_steps=applied, **dict(CL_KW, lr=STOP_LR))
             torch.cuda.synchronize()
             for q in ("params", "m", "v", "step"):
                 assert torch.equal(getattr(L, q).view(torch.int32), getattr(twin, q).view(torch.int32)), "%s: not the %d steps made by hand" % (q, applied)
@@ -471,22 +420,8 @@ def test_ppo_lag_learner_with_both_switches():
         with torch.cuda.stream(s), torch.no_grad():
             batch = col.collect()
             stats = LA.update(batch)
-            eng.lagrange(batch["ep_cost_sum"], batch["ep_cost_count"], LB.lagrange_state, -1.0, 0.05, 100.0)
-            norm = eng.adv_stats(batch["advantages"], out=LB.adv_stats)
-            cnorm = eng.adv_stats(batch["cost_advantages"], out=LB.cadv_stats)
-            eng.adv_mix(batch["advantages"], batch["cost_advantages"], LB.lagrange_state, out=LB.mixed, adv_stats=norm, cadv_stats=cnorm)
-            live.fill_(n_list)
-            k = 0
-            for e in range(2):
-                eng.shuffle_index(None, live, n_list, SHUF_SEED, e, epoch_dev=epoch, out=shuffled)
-                for j in range(4):
-                    eng.ppo_grad_cost(LB.policy_weights, LB.value_weights, LB.cost_weights, LB.policy_grads, LB.value_grads, LB.cost_grads,
-                                      batch["obs"], batch["actions"], batch["logp"], LB.mixed, batch["returns"], batch["cost_returns"],
-                                      LB.stats[k], LB.work, start=j, stride=4, rows=n_list // 4, cvf_coef=0.5, index=shuffled, count=live,
-                                      n_list=n_list)
-                    eng.adam_gated(LB.params, LB.grads, LB.m, LB.v, LB.step, 3e-4, gate, eps=1e-5, max_grad_norm=0.5, kl=LB.stats[k, 4:],
-                                   kl_limit=1.5 * kl, count_gate=live)
-                    k += 1
+            update_by_hand(eng, LB, batch, 2, 4, lagrange=dict(cost_limit=-1.0, lambda_lr=0.05), gate=gate, kl_limit=1.5 * kl,
+                           shuffle=dict(seed=SHUF_SEED, shuffled=shuffled, live=live, epoch=epoch))
             torch.cuda.synchronize()
             for q in ("params", "m", "v", "step", "stats", "grads", "lagrange_state", "mixed"):
                 assert torch.equal(getattr(LA, q), getattr(LB, q)), "%s differs from the calls made by hand" % q

@@ -15,8 +15,7 @@ import pytest
 
 from tests import actor_critic_ref as ar
 from tests import obs_norm_ref as on
-from tests import test_return_norm_gpu as trn
-from tests.train_util import ERR_ARG, SENT, bits_equal, dev, ego_engine
+from tests.train_util import ERR_ARG, EVERY_LEARNER, KEYS, SENT, bits_equal, dev, eager_then_graph, ego_engine, learner_state, make, np_bits as _u64, restore, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +31,6 @@ def eng(descs):
     e = ego_engine(descs, 1)
     yield e
     e.close()
-
-
-def _u64(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
 def _fold(eng, obs, D, record=None, index=None, count=None, n_list=None):
@@ -187,7 +182,7 @@ def test_the_first_call_of_a_fresh_engine_is_capturable(descs):
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        graph = torch.cuda.CUDAGraph()
+        graph = torch.cuda.CUDAGraph()   # (its own capture: the first call on a fresh engine is made inside the capture, nothing runs eagerly in front)
         with torch.cuda.graph(graph, stream=s):
             fresh.obs_norm_update(x, rec_g, in_dim=D, work=work)
             fresh.obs_norm_publish(rec_g, tab_g, eps=EPS)
@@ -465,7 +460,7 @@ IDS = ["RolloutCollector", "RolloutCollector-bootstrap", "SafeRolloutCollector",
 
 def _make(kind, descs, bootstrap, **kw):
     extra = dict(bootstrap_truncations=True) if bootstrap else {}
-    return trn._make(kind, descs, **extra, **kw)
+    return make(kind, descs, **extra, **kw)
 
 
 def _hand_rows(kind, S, col, table, clip, t, tick, live):
@@ -486,16 +481,6 @@ def _hand_rows(kind, S, col, table, clip, t, tick, live):
         eng.mlp_actor_critic(col.policy_weights, col.value_weights, a, lp, v, col.seed, tick, obs=pre)
     torch.cuda.synchronize()
     return a, lp, v
-
-
-def _learner_state(L):
-    keys = ("params", "grads", "m", "v", "step", "stats", "adv_stats") + (("lagrange_state", "cadv_stats", "mixed") if hasattr(L, "lagrange_state") else ())
-    return {k: getattr(L, k).clone() for k in keys}
-
-
-def _restore(L, state):
-    for k, v in state.items():
-        getattr(L, k).copy_(v)
 
 
 @pytest.mark.parametrize("kind,bootstrap", KINDS, ids=IDS)
@@ -549,11 +534,11 @@ def test_collectors_and_learners(descs, kind, bootstrap):
                     assert bits_equal(x, y), (kind, it, "row 0 is not the carried row T")
             last_row = [x[T].clone() for x in (col._actions, col._logp, col.values)]
             # update(): the same calls by hand with the table bound
-            before = _learner_state(L)
+            before = learner_state(L)
             L.update(batch)
             torch.cuda.synchronize()
-            after = _learner_state(L)
-            _restore(L, before)
+            after = learner_state(L)
+            restore(L, before)
             index, count = batch.get("index"), batch.get("count")
             adv, norm = L._advantages(batch, index, count)
             eng.obs_norm_bind(batch["obs_norm"], D, C_CLIP)
@@ -566,18 +551,18 @@ def test_collectors_and_learners(descs, kind, bootstrap):
                     k += 1
             eng.obs_norm_bind(None)
             torch.cuda.synchronize()
-            hand = _learner_state(L)
+            hand = learner_state(L)
             for key in after:
                 assert bits_equal(after[key], hand[key]), (kind, it, key, "update() is not the calls by hand with the table bound")
             if it == 1:   # and without the table the gradients are others
-                _restore(L, before)
+                restore(L, before)
                 adv, norm = L._advantages(batch, index, count)
                 start, stride, rows = L.plan[0]
                 L._grad(batch, adv, L.stats[0], start=start, stride=stride, rows=rows, index=index, count=count, n_list=L.n_list, adv_stats=norm,
                         clip=L.clip, ent_coef=L.ent_coef, in_dim=L.in_dim)
                 torch.cuda.synchronize()
                 unbound = L.grads.clone()
-                _restore(L, after)
+                restore(L, after)
                 assert not bits_equal(unbound, after["grads"])
         # the frozen mode
         state = col.state_dict()
@@ -635,7 +620,7 @@ def test_prime_collect_update_in_one_graph(descs, kind, bootstrap):
     on the host and stays outside, as its docstring says) and replayed three times, against the same calls made eagerly, bit for bit."""
     import torch
     marl = kind == "marl"
-    keys = trn.KEYS + ON_KEYS + (("mask", "count") if marl else ()) + (("term_values", ) if bootstrap else ())
+    keys = KEYS + ON_KEYS + (("mask", "count") if marl else ()) + (("term_values", ) if bootstrap else ())
 
     def iteration(col, L):
         if not marl:
@@ -643,10 +628,7 @@ def test_prime_collect_update_in_one_graph(descs, kind, bootstrap):
         L.update(col.collect())
 
     def state(col, L):
-        torch.cuda.synchronize()
-        out = {k: col.batch[k].clone() for k in keys}
-        out.update(params=L.params.clone(), m=L.m.clone(), step=L.step.clone(), stats=L.stats.clone())
-        return out
+        return dict(snapshot(col.batch, keys), **learner_state(L))
 
     kw = dict(normalise_obs=True, clip_obs=C_CLIP, obs_eps=C_EPS)
     E, col, L = _make(kind, descs, bootstrap, **kw)
@@ -661,22 +643,5 @@ def test_prime_collect_update_in_one_graph(descs, kind, bootstrap):
     assert not bits_equal(want[1]["obs_norm"], want[2]["obs_norm"])
 
     G, col, L = _make(kind, descs, bootstrap, **kw)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s), torch.no_grad():
-        iteration(col, L)
-        got = state(col, L)
-        for key in got:
-            assert bits_equal(got[key], want[0][key]), key
-        graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(graph, stream=s):
-        iteration(col, L)
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s), torch.no_grad():
-        for it in (1, 2, 3):
-            graph.replay()
-            got = state(col, L)
-            for key in got:
-                assert bits_equal(got[key], want[it][key]), "graph replay %d: %s differs from the eager iteration" % (it, key)
-    del graph
+    eager_then_graph(lambda: iteration(col, L), lambda: state(col, L), want, replays=3, need=keys + EVERY_LEARNER)
     G.eng.close()

@@ -14,14 +14,13 @@ Errors are normalised per entry as tests/ppo_ref.py describes.  Tolerances, each
 summation order measures over the same cases (tests/test_ppo_update_cpu.py): gradients / statistics by the minibatch's live rows -- fewer
 than 16: 1.03e-6 / 1.64e-6; 16 to 1023: 2.57e-7 / 4.30e-7; 1024 and more: 8.26e-8 / 6.45e-8 --, TOL_ADV 2.30e-7, TOL_ADAM 6.92e-6.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from tests import actor_critic_ref as ar
 from tests import ppo_ref as rf
-from tests.train_util import ERR_ARG, SENT, ac_nets, dev as _dev, ego_engine, six
+from tests.ppo_util import Problem as _Problem, check as _check, grad as _grad, shapes as _shapes
+from tests.train_util import ERR_ARG, EVERY_LEARNER, SENT, Traffic, assert_same, dev as _dev, eager_then_graph, ego_engine, learner_state, make_collector, update_by_hand
 
 pytestmark = pytest.mark.gpu
 
@@ -32,83 +31,6 @@ def eng(descs):
     e = ego_engine(descs, 1)
     yield e
     e.close()
-
-
-def _shapes(in_dim, out_cols):
-    return [(in_dim, 256), (256, ), (256, 256), (256, ), (256, out_cols), (out_cols, )], [(in_dim, 256), (256, ), (256, 256), (256, ), (256, 1), (1, )]
-
-
-class _Problem:
-    """The rollout arrays of a case on the device -- n_rows rows, of which `where` hold the case's rows in minibatch order and every
-    other row holds NaN in every array -- and a list over them."""
-    def __init__(self, case, n_rows=None, where=None, index=None, count=None, n_list=None):
-        rows = case["x"].shape[0]
-        n_rows = rows if n_rows is None else n_rows
-        where = np.arange(rows) if where is None else np.asarray(where)
-        full = {}
-        for key, width in (("x", case["x"].shape[1]), ("action", 2), ("logp_old", 0), ("adv", 0), ("ret", 0)):
-            a = np.full((n_rows, width) if width else (n_rows, ), np.nan, dtype=np.float32)
-            a[where] = case[key]
-            full[key] = _dev(a)
-        self.t = full
-        self.case, self.n_rows = case, n_rows
-        self.index = _dev(np.asarray(index, dtype=np.int32)) if index is not None else None
-        self.count = _dev(np.array([count], dtype=np.int32)) if count is not None else None
-        self.n_list = int(n_list if n_list is not None else (len(index) if index is not None else n_rows))
-        self.stats_in = _dev(case["adv_stats"]) if case["adv_stats"] is not None else None
-        self.pw = tuple(_dev(w) for w in case["policy"])
-        self.vw = tuple(_dev(w) for w in case["value"])
-
-
-def _grad(eng, P, start=0, stride=1, rows=None, critic=True, ent_coef=rf.ENT_COEF, short_by=0, shift=0, expect=0):
-    """One pgd_ppo_grad through ctypes into sentinel-filled buffers -> dict(stats, policy, value) as numpy (value: the untouched buffers
-    without a critic), and the raw tensors for bit comparisons.  short_by: bytes taken off work_bytes; shift: floats added to the scratch
-    pointer; expect: the status such a call must return, with every output buffer left as it was."""
-    import torch
-    from pgdrive_amd import _abi
-    k, oc = P.case["in_dim"], P.case["policy"][4].shape[1]
-    rows = P.n_list if rows is None else rows
-    ps, vs = _shapes(k, oc)
-    pg = [torch.full(s, SENT, dtype=torch.float32, device="cuda") for s in ps]
-    vg = [torch.full(s, SENT, dtype=torch.float32, device="cuda") for s in vs]
-    stats = torch.full((8, ), SENT, dtype=torch.float32, device="cuda")
-    need = eng.L.pgd_ppo_work_bytes(k, rows, int(critic))
-    assert need > 0
-    work = torch.full(((need + 3) // 4 + shift, ), float("nan"), dtype=torch.float32, device="cuda")
-    nets, grads, b = ac_nets(P.pw, P.vw if critic else None, oc), six(_abi.PPOGrads(), pg), _abi.PPOBatch()
-    if critic:
-        six(grads, vg, "v")
-    b.obs, b.action, b.logp_old, b.adv, b.ret = [P.t[q].data_ptr() for q in ("x", "action", "logp_old", "adv", "ret")]
-    b.adv_stats = P.stats_in.data_ptr() if P.stats_in is not None else None
-    b.index = P.index.data_ptr() if P.index is not None else None
-    b.count = P.count.data_ptr() if P.count is not None else None
-    b.obs_stride, b.in_dim, b.n_rows, b.n_list, b.start, b.stride, b.rows = P.case["x"].shape[1], k, P.n_rows, P.n_list, start, stride, rows
-    hp = _abi.PPOHyper(rf.CLIP, rf.VF_COEF, ent_coef)
-    torch.cuda.synchronize()
-    eng._follow_stream()
-    rc = eng.L.pgd_ppo_grad(eng.h, C.byref(nets), C.byref(b), C.byref(hp), C.byref(grads), C.c_void_p(stats.data_ptr()),
-                            C.c_void_p(work.data_ptr() + 4 * shift), need - short_by)
-    assert rc == expect, rc
-    eng.sync()
-    torch.cuda.synchronize()
-    if expect:
-        for t in [stats] + pg + vg:
-            assert bool((t == SENT).all()), "a refused call wrote"
-        return None
-    out = dict(stats=stats.cpu().numpy(), policy=[g.cpu().numpy() for g in pg], value=[g.cpu().numpy() for g in vg], raw=[stats] + pg + vg)
-    for g in out["policy"] + (out["value"] if critic else []):
-        assert not (g == SENT).any(), "a gradient entry was not written"
-    return out
-
-
-def _check(got, ref, what):
-    eg, es = rf.grad_errors(got, ref)
-    tol_g, tol_s = rf.tolerances(int(ref["stats"][0]))
-    print("%s: gradients %.3f of %.2e, statistics %.3f of %.2e" % (what, eg / tol_g, tol_g, es / tol_s, tol_s))
-    assert eg < tol_g and es < tol_s, (what, eg, tol_g, es, tol_s)
-    oc = got["policy"][4].shape[1]
-    if oc > 4:
-        assert (got["policy"][4][:, 4:] == 0).all() and (got["policy"][5][4:] == 0).all(), (what, "unused head columns")
 
 
 def _weighted_sum_equals(parts, full, ref_full, what):
@@ -248,7 +170,7 @@ def test_the_first_call_of_a_fresh_engine_is_capturable(descs):
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        graph = torch.cuda.CUDAGraph()
+        graph = torch.cuda.CUDAGraph()   # (its own capture: the first call on a fresh engine is made inside the capture, nothing runs eagerly in front)
         with torch.cuda.graph(graph, stream=s):
             fresh.ppo_grad(P.pw, P.vw, pg, vg, P.t["x"], P.t["action"], P.t["logp_old"], P.t["adv"], P.t["ret"], stats, work, in_dim=k,
                            adv_stats=P.stats_in, clip=rf.CLIP, vf_coef=rf.VF_COEF, ent_coef=rf.ENT_COEF)
@@ -348,7 +270,7 @@ def test_adam_three_steps_and_three_replays_of_one_graph(eng):
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        graph = torch.cuda.CUDAGraph()
+        graph = torch.cuda.CUDAGraph()   # (its own capture: nothing runs eagerly in front, and the host writes the gradient between the replays)
         with torch.cuda.graph(graph, stream=s):
             eng.adam(cap["p"], gbuf, cap["m"], cap["v"], cap["step"], max_grad_norm=mx, **rf.ADAM_HYPER)
         torch.cuda.synchronize()
@@ -371,29 +293,10 @@ CL_N, CL_T, CL_SEED = 8, 8, 3
 CL_KW = dict(lr=3e-4, epochs=2, minibatches=2)
 
 
-class _Single:
-    def __init__(self, descs):
-        import torch
-        from pgdrive_amd import _abi
-        from pgdrive_amd.engine import Engine
-        from pgdrive_amd.rollout import RolloutCollector
-        from tests import util
-        mb, sb = util.make_banks(descs, n_maps=8)
-        self.eng = eng = Engine(_abi.make_config(CL_N, auto_reset=1, horizon=12, seed=5), mb, sb)
-        eng.reset(np.arange(CL_N) % 8)
-        p, v = ar.make_networks(np.random.default_rng(0), eng.D, 4)
-        p[4][:, 0] *= 0.05
-        p[5][1] = 0.5
-        self.p, self.v = p, v
-        self.col = RolloutCollector(eng, tuple(_dev(w) for w in p), tuple(_dev(w) for w in v), CL_T, seed=CL_SEED)
-        eng.sync()
-        torch.cuda.synchronize()
-
-
-def _learner_state(L):
-    import torch
-    torch.cuda.synchronize()
-    return dict(params=L.params.clone(), m=L.m.clone(), v=L.v.clone(), step=L.step.clone(), stats=L.stats.clone(), grads=L.grads.clone())
+def _Single(descs):
+    S = Traffic(descs, CL_N, CL_T, CL_SEED)
+    S.col = make_collector("single", S)
+    return S
 
 
 def test_single_agent_update_by_hand_from_a_graph_and_into_the_next_rollout(descs):
@@ -412,21 +315,9 @@ def test_single_agent_update_by_hand_from_a_graph_and_into_the_next_rollout(desc
             batch = A.col.collect()
             stats = LA.update(batch)
             assert stats.shape == (4, 8)
-            want.append(_learner_state(LA))
-            # by hand on B
-            hb = B.col.collect()
-            eng = B.eng
-            norm = eng.adv_stats(hb["advantages"], out=LB.adv_stats)
-            k = 0
-            for _ in range(2):
-                for j in range(2):
-                    eng.ppo_grad(LB.policy_weights, LB.value_weights, LB.policy_grads, LB.value_grads, hb["obs"], hb["actions"], hb["logp"],
-                                 hb["advantages"], hb["returns"], LB.stats[k], LB.work, start=j, stride=2, rows=CL_T * CL_N // 2, adv_stats=norm)
-                    eng.adam(LB.params, LB.grads, LB.m, LB.v, LB.step, 3e-4, eps=1e-5, max_grad_norm=0.5)
-                    k += 1
-            hand = _learner_state(LB)
-            for key in want[-1]:
-                assert torch.equal(want[-1][key], hand[key]), "iteration %d: %s differs from the calls made by hand" % (it, key)
+            want.append(learner_state(LA))
+            update_by_hand(B.eng, LB, B.col.collect(), **CL_KW)
+            assert_same(want[-1], learner_state(LB), "iteration %d, against the calls made by hand" % it, need=EVERY_LEARNER)
             st = stats.cpu().numpy()
             assert np.isfinite(st).all() and (st[:, 0] == CL_T * CL_N // 2).all() and int(LA.step[0]) == 4 * (it + 1)
             assert not torch.equal(old_p[0][0], LA.policy_weights[0]) and not torch.equal(old_p[1][0], LA.value_weights[0])
@@ -447,24 +338,7 @@ def test_single_agent_update_by_hand_from_a_graph_and_into_the_next_rollout(desc
     # (b) one collect() + update() captured in a graph behind one eager iteration, replayed twice
     G = _Single(descs)
     LG = PPOLearner(G.col, **CL_KW)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s), torch.no_grad():
-        LG.update(G.col.collect())
-        got = _learner_state(LG)
-        for key in got:
-            assert torch.equal(got[key], want[0][key]), key
-        graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(graph, stream=s):
-        LG.update(G.col.collect())
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s), torch.no_grad():
-        for it in (1, 2):
-            graph.replay()
-            got = _learner_state(LG)
-            for key in got:
-                assert torch.equal(got[key], want[it][key]), "graph replay %d: %s differs from the eager iteration" % (it, key)
-    del graph
+    eager_then_graph(lambda: LG.update(G.col.collect()), lambda: learner_state(LG), want, need=EVERY_LEARNER)
     G.eng.close()
 
 

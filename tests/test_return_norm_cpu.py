@@ -11,7 +11,7 @@ import pytest
 from tests import actor_critic_ref as ar
 from tests import marl_rollout_ref as mr
 from tests import return_norm_ref as rn
-from tests import safe_ppo_ref as sr
+from tests.recording_engine import CALLS, PRIME, T, TODAY, TODAY_MARL, TODAY_SAFE, collector as _collector
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -152,123 +152,6 @@ def test_the_scratch_size_and_the_null_arguments_without_a_gpu():
 # ---------------------------------------------------------------------------------------------------------------------
 # host logic: the collectors on a recording engine
 # ---------------------------------------------------------------------------------------------------------------------
-class RecordingEngine:
-    """What the collectors ask of an Engine, on CPU tensors: every call is recorded by name.  The step writes scripted rewards, dones and
-    flags; the networks write a constant value; the GAE forms and return_norm are the float64 checkers."""
-    def __init__(self, N, A, D, script):
-        import torch
-        self.torch, self.N, self.A, self.D, self.device = torch, N, A, D, "cpu"
-        self.obs = torch.zeros((N, A, D))
-        self.step_info = None
-        self.calls, self.script, self.t = [], script, 0
-
-    def _write(self, pairs):
-        for dst, src in pairs:
-            dst.copy_(self.torch.from_numpy(np.asarray(src)).to(dst.dtype).view(dst.shape))
-
-    def sync(self):
-        self.calls.append("sync")
-
-    def get_state(self):
-        from pgdrive_amd import _abi
-        si = np.zeros((_abi.NI, self.N, self.A), dtype=np.int32)
-        si[_abi.SI["STATUS"]] = _abi.ST_ACTIVE
-        return None, si, None
-
-    def actor_critic_tick(self, counter):
-        self.calls.append("actor_critic_tick")
-
-    def mlp_actor_critic(self, pw, vw, out, logp, value, seed, tick, obs=None, **kw):
-        self.calls.append("mlp_actor_critic")
-        value.fill_(0.5)
-
-    def mlp_actor_critic_cost(self, pw, vw, cw, out, logp, value, cost_value, seed, tick, obs=None, **kw):
-        self.calls.append("mlp_actor_critic_cost")
-        value.fill_(0.5)
-        cost_value.fill_(0.25)
-
-    def mlp_actor_critic_rows(self, pw, vw, rows, count, out, logp, value, seed, tick, obs=None, **kw):
-        self.calls.append("mlp_actor_critic_rows")
-        value.fill_(0.5)
-
-    def live_rows(self, flags, done, rows=None, count=None, group=-1):
-        self.calls.append("live_rows")
-
-    def rollout_index(self, flags, index=None, count=None):
-        self.calls.append("rollout_index")
-
-    def step(self, actions, out=None):
-        self.calls.append("step")
-        obs, rew, done, flags = out
-        r, d, f = [x[self.t % len(x)] for x in self.script]
-        self._write(((rew, r), (done, d), (flags, f)))
-        self.t += 1
-
-    def gae(self, reward, value, done, gamma, lam, adv=None, ret=None):
-        self.calls.append("gae")
-        self.gae_reward = reward
-        a, r = ar.gae_f64(reward.numpy(), value.numpy(), done.numpy(), gamma, lam)
-        self._write(((adv, a), (ret, r)))
-
-    def gae_masked(self, reward, value, done, flags, gamma, lam, adv=None, ret=None, mask=None):
-        self.calls.append("gae_masked")
-        self.gae_reward = reward
-        a, r, m = mr.gae_masked_f64(reward.numpy(), value.numpy(), done.numpy(), flags.numpy().view(np.uint32), gamma, lam)
-        self._write(((adv, a), (ret, r), (mask, m)))
-
-    def cost_gae(self, flags, done, cost_value, costs, gamma, lam, run, cost=None, adv=None, ret=None, ep_sum=None, ep_count=None):
-        self.calls.append("cost_gae")
-        ref = sr.cost_gae_f64(flags.numpy(), done.numpy(), cost_value.numpy(), costs, gamma, lam, run.numpy())
-        self._write(((cost, ref["cost"]), (adv, ref["cadv"]), (ret, ref["cret"]), (run, ref["run"]), (ep_sum, ref["ep_sum"]), (ep_count, ref["ep_count"])))
-
-    def return_norm_work_bytes(self, rows):
-        return 24 * ((rows + 63) // 64)
-
-    def return_norm_state(self, rows):
-        t = self.torch
-        return t.zeros((rows, ), dtype=t.float32), t.tensor(rn.RECORD_INIT, dtype=t.float64)
-
-    def return_norm(self, reward, done, gamma, carry, record, flags=None, eps=1e-8, clip=10.0, freeze=False, out=None, work=None):
-        self.calls.append("return_norm(freeze=%r)" % bool(freeze))
-        assert work.numel() * work.element_size() >= self.return_norm_work_bytes(carry.numel())
-        ref = rn.return_norm_f64(reward.numpy(), done.numpy(), gamma, carry.numpy().reshape(reward.shape[1:]), record.numpy(),
-                                 flags=None if flags is None else flags.numpy(), eps=eps, clip=clip, freeze=freeze)
-        self._write(((carry, ref["carry"]), (record, ref["record"]), (out, ref["scaled"])))
-        return out
-
-
-N, A, D, T = 5, 3, 6, 7
-W6 = tuple(range(6))   # the weights are handed through, never looked at
-TODAY = {"obs", "actions", "logp", "values", "rewards", "dones", "flags", "advantages", "returns"}
-TODAY_SAFE = TODAY | {"costs", "cost_values", "cost_advantages", "cost_returns", "ep_cost_sum", "ep_cost_count"}
-TODAY_MARL = TODAY | {"mask", "index", "count"}
-PRIME = ["actor_critic_tick", "%s", "actor_critic_tick"]
-
-
-def _script(shape, marl):
-    rng = np.random.default_rng(3)
-    reward = rng.integers(-8, 9, size=(3 * T, *shape)).astype(np.float32) * 25.0   # (returns in the hundreds)
-    if marl:
-        flags, done = rn.seat_history(rng, 3 * T, int(np.prod(shape)))
-        return reward, done.reshape(reward.shape), flags.reshape(reward.shape)
-    done = (rng.uniform(size=reward.shape) < 0.2).astype(np.uint8)
-    return reward, done, (done.astype(np.int32) * (32 | 1 << 16))
-
-
-def _collector(kind, **kw):
-    from pgdrive_amd.rollout import MultiAgentRolloutCollector, RolloutCollector, SafeRolloutCollector
-    marl = kind == "marl"
-    eng = RecordingEngine(N, A if marl else 1, D, _script((N, A) if marl else (N, ), marl))
-    if kind == "safe":
-        return eng, SafeRolloutCollector(eng, W6, W6, W6, T, gamma=0.5, lam=0.5, **kw)
-    return eng, (MultiAgentRolloutCollector if marl else RolloutCollector)(eng, W6, W6, T, gamma=0.5, lam=0.5, **kw)
-
-
-CALLS = dict(single=("mlp_actor_critic", ["step", "mlp_actor_critic"], ["gae"], []),
-             safe=("mlp_actor_critic_cost", ["step", "mlp_actor_critic_cost"], ["gae"], ["cost_gae"]),
-             marl=("mlp_actor_critic_rows", ["step", "live_rows", "mlp_actor_critic_rows"], ["gae_masked", "rollout_index"], []))
-
-
 @pytest.mark.parametrize("kind", ["single", "safe", "marl"])
 def test_switch_off_the_collectors_make_todays_calls_and_todays_batch(kind):
     import inspect

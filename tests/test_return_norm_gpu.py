@@ -15,11 +15,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests import actor_critic_ref as ar
 from tests import return_norm_ref as rn
-from tests import test_marl_rollout_gpu as tm
-from tests.train_util import ERR_ARG, SENT, bits_equal as _bits_equal, dev as _dev, ego_engine as _ego_engine, snapshot as _snapshot, \
-    synchronised_rollouts
+from tests.train_util import ERR_ARG, EVERY_LEARNER, KEYS, SENT, Ego, Roundabout, bits_equal as _bits_equal, dev as _dev, eager_then_graph, ego_engine as _ego_engine, \
+    hand_gae, learner_state, make, np_bits as _bits, snapshot as _snapshot, synchronised_rollouts
 
 pytestmark = pytest.mark.gpu
 
@@ -63,10 +61,6 @@ class _Buffers:
         assert bool((self._carry[self.rows:] == SENT).all()) and bool((self._scaled[:lo] == SENT).all()) and bool((self._scaled[hi:] == SENT).all()), \
             "written past the end"
         return dict(carry=self.carry.cpu().numpy(), record=self.record.cpu().numpy(), scaled=self.scaled.cpu().numpy())
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint64)
 
 
 def _check_record(got, want, where, same_merges=True):
@@ -283,7 +277,7 @@ def test_the_first_call_of_a_fresh_engine_is_capturable(descs):
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        graph = torch.cuda.CUDAGraph()
+        graph = torch.cuda.CUDAGraph()   # (its own capture: the first call on a fresh engine is made inside the capture, nothing runs eagerly in front)
         with torch.cuda.graph(graph, stream=s):
             fresh.return_norm(G.reward, G.done, GEN_GAMMA, G.carry, G.record, out=G.scaled, work=G.work)
         torch.cuda.synchronize()
@@ -307,62 +301,9 @@ def test_the_first_call_of_a_fresh_engine_is_capturable(descs):
 # ---------------------------------------------------------------------------------------------------------------------
 # the collectors
 # ---------------------------------------------------------------------------------------------------------------------
-COL_N, COL_T, COL_HORIZON, COL_SEED, COL_ITER = 6, 8, 5, 3, 3
-KEYS = ("obs", "actions", "logp", "values", "rewards", "dones", "flags", "advantages", "returns")
+COL_ITER = 3
 NORM_KEYS = ("scaled_rewards", "return_norm")
-LEARN_KW = dict(lr=3e-4, epochs=1, minibatches=2)
 CLIP, EPS = 2.0, 1e-6
-
-
-class _Ego:
-    """6 envs, ego only, no lidar, horizon 5 < T = 8 (every env ends at least once per rollout), freshly reset; random networks of the
-    expert's shape (a third one as cost critic)."""
-    def __init__(self, descs, safe):
-        import torch
-        self.safe = safe
-        self.eng = eng = _ego_engine(descs, COL_N, auto_reset=1, horizon=COL_HORIZON, seed=5, safe_rl_env=safe)
-        self.first = eng.reset(np.arange(COL_N) % 4).view(COL_N, -1).clone()
-        rng = np.random.default_rng(0)
-        p, v = ar.make_networks(rng, eng.D, 4)
-        _, c = ar.make_networks(rng, eng.D, 4)
-        p[4][:, 0] *= 0.05
-        p[5][1] = 0.5
-        self.pw, self.vw, self.cw = [tuple(_dev(w) for w in n) for n in (p, v, c)]
-        eng.sync()
-        torch.cuda.synchronize()
-
-
-def _make(kind, descs, **kw):
-    """-> (fixture, collector, learner or None) of a fresh engine."""
-    from pgdrive_amd.learner import PPOLagLearner, PPOLearner
-    from pgdrive_amd.rollout import MultiAgentRolloutCollector, RolloutCollector, SafeRolloutCollector
-    learn = kw.pop("learn", True)
-    if kind == "marl":
-        S = tm._Col()
-        col = MultiAgentRolloutCollector(S.eng, S.pw, S.vw, tm.COL_T, gamma=0.99, lam=0.95, seed=tm.COL_SEED, **kw)
-        return S, col, PPOLearner(col, **LEARN_KW) if learn else None
-    S = _Ego(descs, kind == "safe")
-    if kind == "safe":
-        col = SafeRolloutCollector(S.eng, S.pw, S.vw, S.cw, COL_T, seed=COL_SEED, **kw)
-        return S, col, PPOLagLearner(col, cost_limit=1.0, **LEARN_KW) if learn else None
-    col = RolloutCollector(S.eng, S.pw, S.vw, COL_T, seed=COL_SEED, **kw)
-    return S, col, PPOLearner(col, **LEARN_KW) if learn else None
-
-
-def _state(col, L, keys):
-    import torch
-    torch.cuda.synchronize()
-    out = {k: col.batch[k].clone() for k in keys}
-    out.update(carry=col._rn_carry.clone(), params=L.params.clone(), m=L.m.clone(), step=L.step.clone(), stats=L.stats.clone())
-    return out
-
-
-def _hand_gae(kind, eng, batch, bootstrap):
-    if kind == "marl":
-        return eng.gae_masked(batch["scaled_rewards"], batch["values"], batch["dones"], batch["flags"], 0.99, 0.95)[:2]
-    if bootstrap:
-        return eng.gae_bootstrap(batch["scaled_rewards"], batch["values"], batch["dones"], batch["term_values"], 0.99, 0.95)
-    return eng.gae(batch["scaled_rewards"], batch["values"], batch["dones"], 0.99, 0.95)
 
 
 @pytest.mark.parametrize("kind,bootstrap", [("single", False), ("single", True), ("safe", False), ("safe", True), ("marl", False)],
@@ -383,7 +324,10 @@ def test_collectors(descs, kind, bootstrap):
         (("costs", "cost_advantages", "cost_returns", "ep_cost_sum", "ep_cost_count") if kind == "safe" else ())
 
     # (a) eagerly
-    A, col, L = _make(kind, descs, **on_kw)
+    def snap(col, L):
+        return dict(_snapshot(col.batch, keys), carry=col._rn_carry.clone(), **learner_state(L))
+
+    A, col, L = make(kind, descs, **on_kw)
     shape = tuple(col.rewards.shape[1:])
     carry, record = np.zeros(shape, np.float32), np.array(rn.RECORD_INIT)
     want = []
@@ -394,7 +338,7 @@ def test_collectors(descs, kind, bootstrap):
             batch = col.collect()
             torch.cuda.synchronize()
             assert batch["scaled_rewards"].shape == batch["rewards"].shape and batch["return_norm"].dtype == torch.float64
-            adv, ret = _hand_gae(kind, A.eng, batch, bootstrap)
+            adv, ret = hand_gae(A.eng, batch, marl, bootstrap)
             torch.cuda.synchronize()
             assert _bits_equal(adv, batch["advantages"]) and _bits_equal(ret, batch["returns"]), (it, "not the GAE call on the scaled rewards")
             rew, dn, fl = [batch[k].cpu().numpy() for k in ("rewards", "dones", "flags")]
@@ -407,29 +351,12 @@ def test_collectors(descs, kind, bootstrap):
             print("%s, rollout %d: %d samples, scale %.4f, record against the checker %.1e" % (kind, it, ref["samples"].size, record[3], err))
             assert not _bits_equal(batch["scaled_rewards"], batch["rewards"])
             L.update(batch)
-            want.append(_state(col, L, keys))
+            want.append(snap(col, L))
     A.eng.close()
 
     # (b) one collect() + update() captured behind one eager iteration, replayed twice
-    G, col, L = _make(kind, descs, **on_kw)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s), torch.no_grad():
-        L.update(col.collect())
-        got = _state(col, L, keys)
-        for key in got:
-            assert _bits_equal(got[key], want[0][key]), key
-        graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(graph, stream=s):
-        L.update(col.collect())
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s), torch.no_grad():
-        for it in (1, 2):
-            graph.replay()
-            got = _state(col, L, keys)
-            for key in got:
-                assert _bits_equal(got[key], want[it][key]), "graph replay %d: %s differs from the eager iteration" % (it, key)
-    del graph
+    G, col, L = make(kind, descs, **on_kw)
+    eager_then_graph(lambda: L.update(col.collect()), lambda: snap(col, L), want, need=keys + ("carry", ) + EVERY_LEARNER)
     # a checkpoint of what the replays left, and the frozen mode
     state = col.state_dict()
     assert np.array_equal(_bits(state["return_norm"]), _bits(want[2]["return_norm"].cpu().numpy()))
@@ -447,7 +374,7 @@ def test_collectors(descs, kind, bootstrap):
 
     # (c) the switch off: today's batch, against the calls made one at a time (no update: the weights stay the first ones)
     off_keys = KEYS + (("mask", "index", "count") if marl else ())
-    O, col, _ = _make(kind, descs, learn=False, normalise_rewards=False, **extra)
+    O, col, _ = make(kind, descs, learn=False, normalise_rewards=False, **extra)
     off = []
     with torch.no_grad():
         for it in range(2):
@@ -462,9 +389,8 @@ def test_collectors(descs, kind, bootstrap):
         for key in ("costs", "cost_advantages", "cost_returns", "ep_cost_sum", "ep_cost_count"):
             assert _bits_equal(off[0][key], want[0][key]), (key, "the switch changed the cost side")
     if not bootstrap:
-        S = tm._Col() if marl else _Ego(descs, kind == "safe")
-        live0 = np.flatnonzero(S.active0.reshape(-1)).astype(np.int32) if marl else None
-        sync = synchronised_rollouts(S, 2, tm.COL_T if marl else COL_T, tm.COL_SEED if marl else COL_SEED, off_keys, live0=live0)
+        S = Roundabout() if marl else Ego(descs, kind == "safe")
+        sync = synchronised_rollouts(S, 2)
         S.eng.close()
         for it in range(2):
             if marl:

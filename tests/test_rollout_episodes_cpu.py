@@ -4,13 +4,13 @@ no device, and the host logic of the three collectors on a recording engine."""
 import ctypes as C
 import os
 import re
-import types
 
 import numpy as np
 import pytest
 
 from tests import rollout_episodes_ref as er
-from tests import test_return_norm_cpu as rc
+from tests import recording_engine as rc
+from tests.recording_engine import AllSwitchesEngine, collector as _collector
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -148,35 +148,6 @@ def test_the_library_exports_the_two_symbols_and_refuses_without_a_gpu():
 # ---------------------------------------------------------------------------------------------------------------------
 # host logic: the collectors on a recording engine
 # ---------------------------------------------------------------------------------------------------------------------
-class RecordingEngine(rc.RecordingEngine):
-    """test_return_norm_cpu's, with the episode statistics by the checker."""
-    def rollout_episodes_work_bytes(self, rows):
-        return 128 * ((rows + 63) // 64)
-
-    def rollout_episodes_state(self, rows):
-        t = self.torch
-        return t.zeros((rows, ), dtype=t.float32), t.zeros((rows, ), dtype=t.int32), t.tensor(er.INIT, dtype=t.float64)
-
-    def rollout_episodes(self, reward, done, flags, ret_carry, len_carry, record=None, call=None, seats=False, ep_return=None, ep_length=None,
-                         work=None):
-        self.calls.append("rollout_episodes(seats=%r)" % bool(seats))
-        self.episode_reward = reward
-        assert work.numel() * work.element_size() >= self.rollout_episodes_work_bytes(ret_carry.numel())
-        ref = er.by_definition(reward.numpy(), done.numpy(), flags.numpy(), ret_carry.numpy(), len_carry.numpy(), seats=seats)
-        self._write(((ret_carry, ref["ret_carry"]), (len_carry, ref["len_carry"]), (call, ref["call"]),
-                     (record, er.merge_record(record.numpy(), ref["call"])), (ep_return, ref["ep_return"]), (ep_length, ref["ep_length"])))
-        return record, call
-
-
-def _collector(kind, **kw):
-    from pgdrive_amd.rollout import MultiAgentRolloutCollector, RolloutCollector, SafeRolloutCollector
-    marl = kind == "marl"
-    eng = RecordingEngine(rc.N, rc.A if marl else 1, rc.D, rc._script((rc.N, rc.A) if marl else (rc.N, ), marl))
-    if kind == "safe":
-        return eng, SafeRolloutCollector(eng, rc.W6, rc.W6, rc.W6, rc.T, gamma=0.5, lam=0.5, **kw)
-    return eng, (MultiAgentRolloutCollector if marl else RolloutCollector)(eng, rc.W6, rc.W6, rc.T, gamma=0.5, lam=0.5, **kw)
-
-
 EP_KEYS = {"episode_stats", "episode_stats_rollout", "ep_returns", "ep_lengths"}
 
 
@@ -255,33 +226,6 @@ def test_switch_on_one_call_on_the_raw_rewards(kind, normalise):
 # ---------------------------------------------------------------------------------------------------------------------
 # the checkpoint of a collector with every switch on at once
 # ---------------------------------------------------------------------------------------------------------------------
-class AllSwitchesEngine(RecordingEngine):
-    """RecordingEngine with the two switches it lacks, as recorded calls that move their state: the observation normalisation (the fold
-    counts the rows it was given) and the guardian (the takeover state alternates with the tick)."""
-    cfg = types.SimpleNamespace(idm_agent=False, discrete_action=False, lidar_gaussian_noise=0.0, lidar_dropout_prob=0.0, num_lasers=40)
-
-    def obs_norm_work_bytes(self, D, rows):
-        return 8
-
-    def obs_norm_state(self, D):
-        t = self.torch
-        return t.zeros((1 + 2 * D, ), dtype=t.float64), t.zeros((2, (D + 3) & ~3), dtype=t.float32)
-
-    def obs_norm_publish(self, record, table, eps=1e-8):
-        self.calls.append("obs_norm_publish")
-
-    def obs_norm_bind(self, table, D, clip):
-        self.calls.append("obs_norm_bind")
-
-    def obs_norm_update(self, obs, record, index=None, count=None, n_list=None, work=None):
-        self.calls.append("obs_norm_update")
-        record.add_(float(n_list))
-
-    def guardian(self, weights, save_level, agent, state, applied, info, seed, tick, **kw):
-        self.calls.append("guardian")
-        state.copy_((self.torch.arange(state.numel()) + tick) % 2)
-
-
 SWITCH_KEYS = {"normalise_rewards": {"return_norm_carry", "return_norm"},
                "episode_stats": {"episode_return_carry", "episode_length_carry", "episode_stats"},
                "normalise_obs": {"obs_norm_record"},
@@ -291,12 +235,7 @@ SWITCH_OFF = {"normalise_rewards": "normalise_rewards=False", "episode_stats": "
 
 
 def _all_switches(kind, **kw):
-    from pgdrive_amd.rollout import MultiAgentRolloutCollector, RolloutCollector, SafeRolloutCollector
-    marl = kind == "marl"
-    eng = AllSwitchesEngine(rc.N, rc.A if marl else 1, rc.D, rc._script((rc.N, rc.A) if marl else (rc.N, ), marl))
-    if kind == "safe":
-        return eng, SafeRolloutCollector(eng, rc.W6, rc.W6, rc.W6, rc.T, gamma=0.5, lam=0.5, **kw)
-    return eng, (MultiAgentRolloutCollector if marl else RolloutCollector)(eng, rc.W6, rc.W6, rc.T, gamma=0.5, lam=0.5, **kw)
+    return _collector(kind, engine=AllSwitchesEngine, **kw)
 
 
 def _held(col):

@@ -15,9 +15,9 @@ import numpy as np
 import pytest
 
 from tests import rollout_episodes_ref as er
-from tests import test_return_norm_cpu as rc
-from tests import test_return_norm_gpu as tr
-from tests.train_util import ERR_ARG, SENT, bits_equal as _bits_equal, dev as _dev, ego_engine as _ego_engine
+from tests import recording_engine as rc
+from tests.train_util import ERR_ARG, SENT, Ego, bits_equal as _bits_equal, dev as _dev, eager_then_graph, ego_engine as _ego_engine, make, make_collector, \
+    snapshot as _snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -252,7 +252,7 @@ def test_the_first_call_of_a_fresh_engine_is_capturable(descs):
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        graph = torch.cuda.CUDAGraph()
+        graph = torch.cuda.CUDAGraph()   # (its own capture: the first call on a fresh engine is made inside the capture, nothing runs eagerly in front)
         with torch.cuda.graph(graph, stream=s):
             fresh.rollout_episodes(G.reward, G.done, G.flags, G.ret, G.len, record=G.record, call=G.call_record, seats=True, ep_return=G.ep_return,
                                    ep_length=G.ep_length, work=G.work)
@@ -288,7 +288,7 @@ def test_collectors_switch_off(descs, kind, monkeypatch):
         raise AssertionError("Engine.rollout_episodes called with the switch off")
 
     monkeypatch.setattr(Engine, "rollout_episodes", refuse)
-    S, col, _ = tr._make(kind, descs, learn=False, episode_stats=False)
+    S, col, _ = make(kind, descs, learn=False, episode_stats=False)
     try:
         with torch.no_grad():
             batch = col.collect()
@@ -301,11 +301,7 @@ def test_collectors_switch_off(descs, kind, monkeypatch):
 
 
 def _episode_state(col):
-    import torch
-    torch.cuda.synchronize()
-    out = {k: col.batch[k].clone() for k in EP_KEYS + TRAJECTORY}
-    out.update(ret_carry=col._ep_ret_carry.clone(), len_carry=col._ep_len_carry.clone())
-    return out
+    return dict(_snapshot(col.batch, EP_KEYS + TRAJECTORY), ret_carry=col._ep_ret_carry.clone(), len_carry=col._ep_len_carry.clone())
 
 
 @pytest.mark.parametrize("kind", [k for k, _ in KINDS], ids=[i for _, i in KINDS])
@@ -317,7 +313,7 @@ def test_collectors_switch_on(descs, kind):
     import torch
     marl = kind == "marl"
     # (a) eagerly
-    A, col, _ = tr._make(kind, descs, learn=False, episode_stats=True)
+    A, col, _ = make(kind, descs, learn=False, episode_stats=True)
     rows = col.rewards[0].numel()
     ret, length, record = np.zeros(rows, np.float32), np.zeros(rows, np.int32), er.INIT
     want = []
@@ -344,25 +340,8 @@ def test_collectors_switch_on(descs, kind):
     A.eng.close()
 
     # (b) one collect() captured behind one eager rollout, replayed twice
-    G, col, _ = tr._make(kind, descs, learn=False, episode_stats=True)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s), torch.no_grad():
-        col.collect()
-        got = _episode_state(col)
-        for key in got:
-            assert _bits_equal(got[key], want[0][key]), key
-        graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(graph, stream=s):
-        col.collect()
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s), torch.no_grad():
-        for it in (1, 2):
-            graph.replay()
-            got = _episode_state(col)
-            for key in got:
-                assert _bits_equal(got[key], want[it][key]), "graph replay %d: %s differs from the eager rollout" % (it, key)
-    del graph
+    G, col, _ = make(kind, descs, learn=False, episode_stats=True)
+    eager_then_graph(col.collect, lambda: _episode_state(col), want)
     # a checkpoint of what the replays left; clearing keeps the carries
     state = col.state_dict()
     assert set(state) == {"episode_return_carry", "episode_length_carry", "episode_stats"}
@@ -385,7 +364,7 @@ def test_collectors_switch_on(descs, kind):
     G.eng.close()
 
     # (c) with reward normalisation: GAE reads scaled rewards, the episode statistics read the raw ones
-    N, col, _ = tr._make(kind, descs, learn=False, episode_stats=True, normalise_rewards=True)
+    N, col, _ = make(kind, descs, learn=False, episode_stats=True, normalise_rewards=True)
     with torch.no_grad():
         for it in range(3):
             batch = col.collect()
@@ -401,11 +380,10 @@ def test_the_step_info_counts_the_same_episodes(descs):
     Engine.episode_stats(clear=False) equal the record's, exactly, over the same steps.  Only these integer quantities are compared: the
     step info sums the returns in another order (the float64 checker holds the returns, above)."""
     import torch
-    from pgdrive_amd.rollout import RolloutCollector
-    S = tr._Ego(descs, False)
+    S = Ego(descs, False)
     try:
         S.eng.enable_step_info()
-        col = RolloutCollector(S.eng, S.pw, S.vw, tr.COL_T, seed=tr.COL_SEED, episode_stats=True)
+        col = make_collector("single", S, episode_stats=True)
         with torch.no_grad():
             for it in range(3):
                 col.collect()
@@ -420,6 +398,6 @@ def test_the_step_info_counts_the_same_episodes(descs):
         for key, field in (("ep_count", "episodes"), ("ep_length_sum", "length_sum"), ("ep_arrive", "arrive"), ("ep_out_of_road", "out_of_road"),
                            ("ep_max_step", "max_step")):
             assert float(si[key].sum(dtype=torch.float64)) == rec[field], (key, field)
-        assert rec["steps"] == 3 * tr.COL_T * tr.COL_N and rec["cut"] == 0
+        assert rec["steps"] == 3 * S.T * S.N and rec["cut"] == 0
     finally:
         S.eng.close()

@@ -22,7 +22,8 @@ import pytest
 from tests import actor_critic_ref as ar
 from tests import ppo_ref as rf
 from tests import safe_ppo_ref as sr
-from tests.train_util import ERR_ARG, SENT, ac_nets, dev as _dev, ego_engine as _ego_engine, six
+from tests.train_util import ERR_ARG, LAGRANGIAN, SENT, ac_nets, assert_same, dev as _dev, eager_then_graph, ego_engine as _ego_engine, learner_state, six, \
+    update_by_hand
 
 pytestmark = pytest.mark.gpu
 
@@ -113,7 +114,7 @@ def test_forward_from_a_graph_with_a_device_tick_and_the_refusals(descs):
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        graph = torch.cuda.CUDAGraph()
+        graph = torch.cuda.CUDAGraph()   # (its own capture: nothing runs eagerly in front, and the host writes the tick between the replays)
         with torch.cuda.graph(graph, stream=s):
             e.mlp_actor_critic_cost(pw, vw, cwd, a, l, vv, cv, 11, 2, obs=xd, in_dim=in_dim)
         torch.cuda.synchronize()
@@ -265,7 +266,7 @@ def test_lagrange(eng, rows):
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
-    graph = torch.cuda.CUDAGraph()
+    graph = torch.cuda.CUDAGraph()   # (its own capture: three replays of one call against three eager calls, compared once at the end)
     with torch.cuda.graph(graph, stream=s):
         eng.lagrange(es, ec, cap, limit, lr, 100.0)
     torch.cuda.synchronize()
@@ -521,13 +522,6 @@ SAFE_T = 32
 SAFE_KW = dict(lr=3e-4, epochs=2, minibatches=2, lambda_lr=0.05)
 
 
-def _state(L):
-    import torch
-    torch.cuda.synchronize()
-    return dict(params=L.params.clone(), m=L.m.clone(), v=L.v.clone(), step=L.step.clone(), stats=L.stats.clone(), grads=L.grads.clone(),
-                lagrange=L.lagrange_state.clone(), mixed=L.mixed.clone())
-
-
 def test_closed_loop_on_the_safe_env():
     import torch
     from pgdrive_amd import PPOLagLearner, SafeRolloutCollector
@@ -570,54 +564,25 @@ def test_closed_loop_on_the_safe_env():
                     torch.cuda.synchronize()
                     assert float(LC.lagrange_state[0]) == 0.0 and float(LC.lagrange_state[2]) == float(ec.sum())
                     # the same Engine calls by hand, on LB's buffers
-                    eng.lagrange(batch["ep_cost_sum"], batch["ep_cost_count"], LB.lagrange_state, -1.0, 0.05, 100.0)
-                    norm = eng.adv_stats(batch["advantages"], out=LB.adv_stats)
-                    cnorm = eng.adv_stats(batch["cost_advantages"], out=LB.cadv_stats)
-                    eng.adv_mix(batch["advantages"], batch["cost_advantages"], LB.lagrange_state, out=LB.mixed, adv_stats=norm, cadv_stats=cnorm)
-                    k = 0
-                    for _ in range(2):
-                        for j in range(2):
-                            eng.ppo_grad_cost(LB.policy_weights, LB.value_weights, LB.cost_weights, LB.policy_grads, LB.value_grads, LB.cost_grads,
-                                              batch["obs"], batch["actions"], batch["logp"], LB.mixed, batch["returns"], batch["cost_returns"],
-                                              LB.stats[k], LB.work, start=j, stride=2, rows=SAFE_T * SAFE_N // 2, cvf_coef=0.5)
-                            eng.adam(LB.params, LB.grads, LB.m, LB.v, LB.step, 3e-4, eps=1e-5, max_grad_norm=0.5)
-                            k += 1
+                    update_by_hand(eng, LB, batch, SAFE_KW["epochs"], SAFE_KW["minibatches"], lr=SAFE_KW["lr"],
+                                   lagrange=dict(cost_limit=-1.0, lambda_lr=SAFE_KW["lambda_lr"]))
                 lam_before = float(LA.lagrange_state[0])
                 stats = LA.update(batch)
                 assert stats.shape == (4, 8)
-                want.append(_state(LA))
+                want.append(learner_state(LA))
                 st = stats.cpu().numpy()
                 assert np.isfinite(st).all() and (st[:, 0] == SAFE_T * SAFE_N // 2).all() and (st[:, 7] > 0).all()
                 lam, jc = float(LA.lagrange_state[0]), float(LA.lagrange_state[1])
                 assert lam > lam_before, "cost_limit -1: lambda does not grow"
                 if it == 0:
-                    hand = _state(LB)
-                    for key in hand:
-                        assert torch.equal(want[0][key], hand[key]), "%s differs from the calls made by hand" % key
+                    assert_same(learner_state(LB), want[0], "against the calls made by hand", need=LAGRANGIAN)
                     w = float(np.float32(0.05)) * (float(es.sum()) / int(ec.sum()) + 1.0)
                     assert abs(lam - w) <= sr.ulp32(w) and abs(jc - es.sum() / ec.sum()) <= sr.ulp32(jc), (lam, w, jc)
         # collect(); update() captured in one graph behind one eager iteration, replayed twice, from the same start on a second env
         pw, vw, cw = _safe_networks(env_g.engine.D)
         col_g = SafeRolloutCollector(env_g, pw, vw, cw, SAFE_T, seed=3)
         LG = PPOLagLearner(col_g, cost_limit=-1.0, **SAFE_KW)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s), torch.no_grad():
-            LG.update(col_g.collect())
-            got = _state(LG)
-            for key in got:
-                assert torch.equal(got[key], want[0][key]), "second env, eager iteration: %s" % key
-            graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(graph, stream=s):
-            LG.update(col_g.collect())
-        torch.cuda.synchronize()
-        with torch.cuda.stream(s), torch.no_grad():
-            for it in (1, 2):
-                graph.replay()
-                got = _state(LG)
-                for key in got:
-                    assert torch.equal(got[key], want[it][key]), "graph replay %d: %s differs from the eager iteration" % (it, key)
-        del graph
+        eager_then_graph(lambda: LG.update(col_g.collect()), lambda: learner_state(LG), want, need=LAGRANGIAN)
     finally:
         env.close()
         env_g.close()

@@ -12,6 +12,7 @@ import pytest
 from tests import actor_critic_ref as ar
 from tests import safe_ppo_ref as sr
 from tests import timelimit_ref as tl
+from tests.recording_engine import D, N, T, W6, RecordingEngine, truncation_script
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -157,81 +158,8 @@ def test_the_emulation_without_truncations_is_k_gaes():
 # ---------------------------------------------------------------------------------------------------------------------
 # host logic: the collectors on a recording engine
 # ---------------------------------------------------------------------------------------------------------------------
-class RecordingEngine:
-    """What the collectors ask of an Engine, on CPU tensors: every call is recorded by name; the step follows a script (constant reward,
-    PGD_F_MAX_STEP | PGD_F_RESET and a done where the script truncates), the networks return the constant `value`, and the GAE forms
-    are the float64 checkers."""
-    def __init__(self, N, D, reward, value, trunc, step_info=None):
-        import torch
-        self.torch, self.N, self.A, self.D, self.device = torch, N, 1, D, "cpu"
-        self.obs = torch.zeros((N, 1, D))
-        self.step_info = step_info
-        self.calls, self.reward, self.value, self.trunc, self.t = [], reward, value, trunc, 0
-
-    def enable_step_info(self, costs=(1.0, 1.0, 1.0), final_obs=True):
-        self.calls.append("enable_step_info(final_obs=%r)" % final_obs)
-        self.step_info = {"final_observation": self.torch.full((self.N, self.D), float("nan")) if final_obs else None}
-        return self.step_info
-
-    def actor_critic_tick(self, counter):
-        self.calls.append("actor_critic_tick")
-
-    def mlp_actor_critic(self, pw, vw, out, logp, value, seed, tick, obs=None, **kw):
-        self.calls.append("mlp_actor_critic")
-        value.fill_(self.value)
-
-    def mlp_actor_critic_cost(self, pw, vw, cw, out, logp, value, cost_value, seed, tick, obs=None, **kw):
-        self.calls.append("mlp_actor_critic_cost")
-        value.fill_(self.value)
-        cost_value.fill_(0.5 * self.value)
-
-    def step(self, actions, out=None):
-        self.calls.append("step")
-        obs, rew, done, flags = out
-        tr = self.torch.from_numpy(self.trunc[self.t % len(self.trunc)])
-        rew.fill_(self.reward)
-        done.copy_(tr.to(done.dtype))
-        flags.copy_(tr.to(flags.dtype) * (32 | 1 << 16))
-        self.t += 1
-
-    def mlp_terminal_value(self, vw, cw, term_obs, flags, done, term_value, term_cost_value=None, **kw):
-        from pgdrive_amd.rollout import truncated
-        self.calls.append("mlp_terminal_value")
-        assert term_obs is self.step_info["final_observation"] and (cw is None) == (term_cost_value is None)
-        tr = truncated(flags, done)
-        term_value.copy_(tr.to(term_value.dtype) * self.value)
-        if term_cost_value is not None:
-            term_cost_value.copy_(tr.to(term_value.dtype) * 0.5 * self.value)
-
-    def _write(self, pairs):
-        for dst, src in pairs:
-            dst.copy_(self.torch.from_numpy(np.asarray(src)).to(dst.dtype))
-
-    def gae(self, reward, value, done, gamma, lam, adv=None, ret=None):
-        self.calls.append("gae")
-        a, r = ar.gae_f64(reward.numpy(), value.numpy(), done.numpy(), gamma, lam)
-        self._write(((adv, a), (ret, r)))
-
-    def gae_bootstrap(self, reward, value, done, term_value, gamma, lam, adv=None, ret=None):
-        self.calls.append("gae_bootstrap")
-        a, r = tl.gae_bootstrap_f64(reward.numpy(), value.numpy(), done.numpy(), term_value.numpy(), gamma, lam)
-        self._write(((adv, a), (ret, r)))
-
-    def cost_gae(self, flags, done, cost_value, costs, gamma, lam, run, cost=None, adv=None, ret=None, ep_sum=None, ep_count=None):
-        self.calls.append("cost_gae")
-        ref = sr.cost_gae_f64(flags.numpy(), done.numpy(), cost_value.numpy(), costs, gamma, lam, run.numpy())
-        self._write(((cost, ref["cost"]), (adv, ref["cadv"]), (ret, ref["cret"]), (run, ref["run"]), (ep_sum, ref["ep_sum"]), (ep_count, ref["ep_count"])))
-
-    def cost_gae_bootstrap(self, flags, done, cost_value, term_cost_value, costs, gamma, lam, run, cost=None, adv=None, ret=None, ep_sum=None,
-                           ep_count=None):
-        self.calls.append("cost_gae_bootstrap")
-        ref = tl.cost_gae_bootstrap_f64(flags.numpy(), done.numpy(), cost_value.numpy(), term_cost_value.numpy(), costs, gamma, lam, run.numpy())
-        self._write(((cost, ref["cost"]), (adv, ref["cadv"]), (ret, ref["cret"]), (run, ref["run"]), (ep_sum, ref["ep_sum"]), (ep_count, ref["ep_count"])))
-
-
 # numbers that are exact in float32, which the collector's buffers are: r + gamma V - V == 0 with V = r / (1 - gamma) = 4
 R, GAMMA, LAM, V = 1.0, 0.75, 0.5, 4.0
-N, D, T = 5, 6, 7
 
 
 def _script():
@@ -240,18 +168,20 @@ def _script():
     return trunc
 
 
-W6 = tuple(range(6))   # the weights are handed through, never looked at
+def _engine(trunc, step_info=None):
+    """The recording engine on a script of the constant reward R and the truncations `trunc`; the networks say V, the cost critic V / 2."""
+    return RecordingEngine(N, 1, D, truncation_script(R, trunc), value=V, cost_value=0.5 * V, step_info=step_info)
 
 
 def test_switch_off_the_collectors_make_todays_calls():
     from pgdrive_amd.rollout import RolloutCollector, SafeRolloutCollector
-    eng = RecordingEngine(N, D, R, V, _script())
+    eng = _engine(_script())
     col = RolloutCollector(eng, W6, W6, T, gamma=GAMMA, lam=LAM)
     batch = col.collect()
     prime = ["actor_critic_tick", "mlp_actor_critic", "actor_critic_tick"]
     assert eng.calls == prime + ["actor_critic_tick"] + ["step", "mlp_actor_critic"] * T + ["actor_critic_tick", "gae"]
     assert eng.step_info is None and "term_values" not in batch and not col.bootstrap_truncations
-    eng = RecordingEngine(N, D, R, V, _script())
+    eng = _engine(_script())
     col = SafeRolloutCollector(eng, W6, W6, W6, T, gamma=GAMMA, lam=LAM)
     batch = col.collect()
     prime = ["actor_critic_tick", "mlp_actor_critic_cost", "actor_critic_tick"]
@@ -266,7 +196,7 @@ def test_switch_on_one_launch_per_step_and_the_property_through_the_collector():
     import torch
     from pgdrive_amd.rollout import RolloutCollector, SafeRolloutCollector
     script = _script()
-    on, off = RecordingEngine(N, D, R, V, script), RecordingEngine(N, D, R, V, script)
+    on, off = _engine(script), _engine(script)
     c_on = RolloutCollector(on, W6, W6, T, gamma=GAMMA, lam=LAM, bootstrap_truncations=True)
     c_off = RolloutCollector(off, W6, W6, T, gamma=GAMMA, lam=LAM)
     assert on.calls == ["enable_step_info(final_obs=True)"] and on.step_info["final_observation"].shape == (N, D)
@@ -281,11 +211,11 @@ def test_switch_on_one_launch_per_step_and_the_property_through_the_collector():
         assert torch.equal(b_on["advantages"], torch.zeros(T, N)) and torch.equal(b_on["returns"], torch.full((T, N), V))
         assert torch.equal(b_off["advantages"][tr], torch.full((int(tr.sum()), ), R - V))
     # an engine whose step info is on already is used as it is
-    eng = RecordingEngine(N, D, R, V, script, step_info={"final_observation": torch.zeros(N, D)})
+    eng = _engine(script, step_info={"final_observation": torch.zeros(N, D)})
     RolloutCollector(eng, W6, W6, T, bootstrap_truncations=True)
     assert eng.calls == []
     # the safe collector: the cost critic in the same launch, the cost side's bootstrap form
-    eng = RecordingEngine(N, D, R, V, script)
+    eng = _engine(script)
     col = SafeRolloutCollector(eng, W6, W6, W6, T, gamma=GAMMA, lam=LAM, cost_gamma=GAMMA, cost_lam=LAM, bootstrap_truncations=True)
     batch = col.collect()
     assert eng.calls == ["enable_step_info(final_obs=True)", "actor_critic_tick", "mlp_actor_critic_cost", "actor_critic_tick", "actor_critic_tick"] + \
@@ -302,11 +232,11 @@ def test_an_engine_without_final_observation_is_refused():
     info = {"final_observation": None, "cost": torch.zeros(N)}
     for make in (lambda e: RolloutCollector(e, W6, W6, T, bootstrap_truncations=True),
                  lambda e: SafeRolloutCollector(e, W6, W6, W6, T, bootstrap_truncations=True)):
-        eng = RecordingEngine(N, D, R, V, _script(), step_info=dict(info))
+        eng = _engine(_script(), step_info=dict(info))
         with pytest.raises(ValueError, match="final_observation"):
             make(eng)
         assert eng.calls == []
-    RolloutCollector(RecordingEngine(N, D, R, V, _script(), step_info=dict(info)), W6, W6, T)   # (the switch off: no objection)
+    RolloutCollector(_engine(_script(), step_info=dict(info)), W6, W6, T)   # (the switch off: no objection)
 
 
 def test_the_multi_agent_collector_has_no_such_switch():

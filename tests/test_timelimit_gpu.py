@@ -18,13 +18,11 @@ import pytest
 from tests import actor_critic_ref as ar
 from tests import policy_ref as pr
 from tests import timelimit_ref as tl
-from tests.train_util import ERR_ARG, SENT, bits_equal as _bits_equal, dev as _dev, ego_engine as _ego_engine, six as _six, snapshot as _snapshot
+from tests import train_util
+from tests.train_util import ERR_ARG, SENT, Traffic, bits_equal as _bits_equal, dev as _dev, eager_then_graph, ego_engine as _ego_engine, make_collector, \
+    np_bits, six as _six, snapshot as _snapshot, synchronised_rollouts
 
 pytestmark = pytest.mark.gpu
-
-
-def _i32(a):
-    return a.view(np.int32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -70,13 +68,13 @@ def _check_launch(eng, x, p, v, cw, in_dim, trunc, seed, safe=False, f64=False):
     xn[~trunc] = np.nan
     tv, none = _term(eng, xn, v, None, flags, done, in_dim)
     assert none is None
-    assert np.array_equal(_i32(tv[trunc]), _i32(want[trunc])), "truncated rows are not pgd_mlp_actor_critic's value bits"
-    assert np.array_equal(_i32(tv[~trunc]), np.zeros(int((~trunc).sum()), dtype=np.int32)), "a row that is not truncated is not exactly +0.0"
+    assert np.array_equal(np_bits(tv[trunc]), np_bits(want[trunc])), "truncated rows are not pgd_mlp_actor_critic's value bits"
+    assert np.array_equal(np_bits(tv[~trunc]), np.zeros(int((~trunc).sum()), dtype=np.int32)), "a row that is not truncated is not exactly +0.0"
     tv2, tcv = _term(eng, xn, v, cw, flags, done, in_dim)
-    assert np.array_equal(_i32(tv2), _i32(tv)), "the critic's output depends on the cost critic's presence"
+    assert np.array_equal(np_bits(tv2), np_bits(tv)), "the critic's output depends on the cost critic's presence"
     as_critic, _ = _term(eng, xn, cw, None, flags, done, in_dim)
-    assert np.array_equal(_i32(tcv), _i32(as_critic)), "y = 1 is not a call that is handed the cost network as critic"
-    assert np.array_equal(_i32(tcv[trunc]), _i32(want_c[trunc])) and np.array_equal(_i32(tcv[~trunc]), np.zeros(int((~trunc).sum()), dtype=np.int32))
+    assert np.array_equal(np_bits(tcv), np_bits(as_critic)), "y = 1 is not a call that is handed the cost network as critic"
+    assert np.array_equal(np_bits(tcv[trunc]), np_bits(want_c[trunc])) and np.array_equal(np_bits(tcv[~trunc]), np.zeros(int((~trunc).sum()), dtype=np.int32))
     if f64 and trunc.any():
         _, _, v64 = ar.heads_f64(x[trunc][:, :in_dim], p, v)
         err = float(np.abs(tv[trunc] - v64).max())
@@ -133,12 +131,12 @@ def test_no_truncation_reads_no_weight_and_no_observation(descs):
         flags, done = tl.flags_of(np.zeros(33, dtype=bool), np.random.default_rng(4))
         assert done.any() and (flags & tl.F_MAX_STEP).any()
         tv, tcv = _term(eng, np.full_like(x, np.nan), nan, nan, flags, done, 274)
-        assert np.array_equal(_i32(tv), np.zeros(33, dtype=np.int32)) and np.array_equal(_i32(tcv), np.zeros(33, dtype=np.int32))
+        assert np.array_equal(np_bits(tv), np.zeros(33, dtype=np.int32)) and np.array_equal(np_bits(tcv), np.zeros(33, dtype=np.int32))
         # one truncated row: its tile runs (and NaN weights show), the other two tiles still exit early
         trunc = tl.trunc_pattern(33, "last_row")
         flags, done = tl.flags_of(trunc, np.random.default_rng(5))
         tv, _ = _term(eng, x, nan, None, flags, done, 274)
-        assert np.isnan(tv[32]) and np.array_equal(_i32(tv[:32]), np.zeros(32, dtype=np.int32))
+        assert np.isnan(tv[32]) and np.array_equal(np_bits(tv[:32]), np.zeros(32, dtype=np.int32))
     finally:
         eng.close()
 
@@ -169,8 +167,8 @@ def test_env_groups(descs):
             eng.group_sync(g)
             for got, ref in ((tv.cpu().numpy(), want), (tcv.cpu().numpy(), want_c)):
                 assert (got[~mine] == SENT).all(), (g, "rows of the other group written")
-                assert np.array_equal(_i32(got[mine & trunc]), _i32(ref[mine & trunc])), g
-                assert np.array_equal(_i32(got[mine & ~trunc]), np.zeros(6, dtype=np.int32)), g
+                assert np.array_equal(np_bits(got[mine & trunc]), np_bits(ref[mine & trunc])), g
+                assert np.array_equal(np_bits(got[mine & ~trunc]), np.zeros(6, dtype=np.int32)), g
     finally:
         eng.close()
 
@@ -219,7 +217,7 @@ def test_refused_arguments(descs):
         # the same call with good arguments at the limit: the first launch of this engine, which needs the raised LDS limit
         assert call() == 0
         eng.sync()
-        assert np.array_equal(_i32(tv.cpu().numpy()), _i32(_values(eng, x, p, v, 416)))
+        assert np.array_equal(np_bits(tv.cpu().numpy()), np_bits(_values(eng, x, p, v, 416)))
         # T = 0, rows = 0 of the GAE forms
         z = torch.zeros(4, device="cuda")
         zb, zi = torch.zeros(4, dtype=torch.uint8, device="cuda"), torch.zeros(4, dtype=torch.int32, device="cuda")
@@ -373,88 +371,19 @@ def test_both_gae_forms(descs, T, rows):
 # the collectors
 # ---------------------------------------------------------------------------------------------------------------------
 COL_N, COL_T, COL_HORIZON, COL_SEED = 64, 16, 12, 3
-KEYS = ("obs", "actions", "logp", "values", "rewards", "dones", "flags", "term_values", "advantages", "returns")
+KEYS = train_util.KEYS + ("term_values", )
 SAFE_KEYS = KEYS + ("cost_values", "term_cost_values", "costs", "cost_advantages", "cost_returns", "ep_cost_sum", "ep_cost_count")
 COSTS = (1.0, 0.5, 0.25)
 
 
-class _Col:
+def _Col(descs, safe):
     """64 envs of the default configuration with traffic and horizon 12 < T = 16, freshly reset, the step info on; random networks of
     the expert's shape (a third one as cost critic)."""
-    def __init__(self, descs, safe, nets=None):
-        import torch
-        from pgdrive_amd import _abi
-        from pgdrive_amd.engine import Engine
-        from tests import util
-        mb, sb = util.make_banks(descs, n_maps=8)
-        self.safe = safe
-        self.eng = eng = Engine(_abi.make_config(COL_N, auto_reset=1, horizon=COL_HORIZON, seed=5, safe_rl_env=safe), mb, sb)
-        eng.enable_step_info(costs=COSTS)
-        eng.step_info["final_observation"].fill_(float("nan"))
-        self.first = eng.reset(np.arange(COL_N) % 8).view(COL_N, -1).clone()
-        if nets is None:
-            rng = np.random.default_rng(0)
-            p, v = ar.make_networks(rng, eng.D, 4)
-            _, c = ar.make_networks(rng, eng.D, 4)
-            p[4][:, 0] *= 0.05   # (steering: the cars stay on the road for a while, tests/test_policy_gpu.py)
-            p[5][1] = 0.5        # (throttle: they drive)
-            nets = (p, v, c)
-        self.p, self.v, self.c = nets
-        self.pw, self.vw, self.cw = [tuple(_dev(w) for w in n) for n in nets]
-        eng.sync()
-        torch.cuda.synchronize()
-
-    def collector(self, on=True):
-        from pgdrive_amd.rollout import RolloutCollector, SafeRolloutCollector
-        if self.safe:
-            return SafeRolloutCollector(self.eng, self.pw, self.vw, self.cw, COL_T, costs=COSTS, seed=COL_SEED, bootstrap_truncations=on)
-        return RolloutCollector(self.eng, self.pw, self.vw, COL_T, seed=COL_SEED, bootstrap_truncations=on)
+    return Traffic(descs, COL_N, COL_T, COL_SEED, horizon=COL_HORIZON, safe=safe, step_info_costs=COSTS)
 
 
-def _synchronised(S, n_rollouts):
-    """The collector's calls made one at a time into fresh buffers, a device synchronisation behind each; evaluation j has tick j.
-    -> per rollout the batch's tensors, plus "final_obs": a copy of step_info["final_observation"] behind every step."""
-    import torch
-    eng, N, D, T = S.eng, S.eng.N, S.eng.D, COL_T
-
-    def evaluate(obs, tick):
-        a = torch.full((N, 1, 2), SENT, dtype=torch.float32, device="cuda")
-        lp, v, cv = [torch.full((N, ), SENT, dtype=torch.float32, device="cuda") for _ in range(3)]
-        if S.safe:
-            eng.mlp_actor_critic_cost(S.pw, S.vw, S.cw, a, lp, v, cv, COL_SEED, tick, obs=obs)
-        else:
-            eng.mlp_actor_critic(S.pw, S.vw, a, lp, v, COL_SEED, tick, obs=obs)
-        torch.cuda.synchronize()
-        return a, lp, v, cv
-
-    obs = S.first.clone()
-    a, lp, v, cv = evaluate(obs, 0)
-    run = torch.zeros(N, device="cuda")
-    out = []
-    for k in range(n_rollouts):
-        rec = {key: [] for key in SAFE_KEYS + ("final_obs", )}
-        for t in range(T):
-            for key, x in (("obs", obs.view(N, D)), ("actions", a.view(N, 2)), ("logp", lp), ("values", v), ("cost_values", cv)):
-                rec[key].append(x)
-            obs, rew, done, flags = eng.step(a, out=eng.make_outputs())
-            torch.cuda.synchronize()
-            rec["rewards"].append(rew.view(N)); rec["dones"].append(done.view(N)); rec["flags"].append(flags.view(N))
-            rec["final_obs"].append(eng.step_info["final_observation"].clone())
-            tv, tcv = [torch.full((N, ), SENT, dtype=torch.float32, device="cuda") for _ in range(2)]
-            eng.mlp_terminal_value(S.vw, S.cw if S.safe else None, eng.step_info["final_observation"], flags.view(N), done.view(N), tv,
-                                   tcv if S.safe else None)
-            torch.cuda.synchronize()
-            rec["term_values"].append(tv); rec["term_cost_values"].append(tcv)
-            a, lp, v, cv = evaluate(obs, k * T + t + 1)
-        rec["values"].append(v); rec["cost_values"].append(cv)
-        r = {key: torch.stack(x) for key, x in rec.items() if x}
-        r["advantages"], r["returns"] = eng.gae_bootstrap(r["rewards"], r["values"], r["dones"], r["term_values"], 0.99, 0.95)
-        if S.safe:
-            r["costs"], r["cost_advantages"], r["cost_returns"], r["ep_cost_sum"], r["ep_cost_count"] = eng.cost_gae_bootstrap(
-                r["flags"], r["dones"], r["cost_values"], r["term_cost_values"], COSTS, 0.99, 0.95, run)
-        torch.cuda.synchronize()
-        out.append(r)
-    return out
+def _collector(S, on=True):
+    return make_collector("safe", S, costs=COSTS, bootstrap_truncations=on) if S.safe else make_collector("single", S, bootstrap_truncations=on)
 
 
 @pytest.mark.parametrize("safe", [False, True], ids=["RolloutCollector", "SafeRolloutCollector"])
@@ -463,7 +392,7 @@ def test_collectors_with_the_switch_on(descs, safe):
     from pgdrive_amd.rollout import truncated
     keys = SAFE_KEYS if safe else KEYS
     S = _Col(descs, safe)
-    want = _synchronised(S, 3)
+    want = synchronised_rollouts(S, 3, cost_critic=safe, bootstrap=True, costs=COSTS)
     S.eng.close()
 
     # what the rollouts hold
@@ -478,7 +407,7 @@ def test_collectors_with_the_switch_on(descs, safe):
         fo = r["final_obs"].cpu().numpy()
         for name, net in (("term_values", S.v), ("term_cost_values", S.c))[:2 if safe else 1]:
             tv = r[name].cpu().numpy()
-            assert np.array_equal(tv != 0, tr) and np.array_equal(_i32(tv[~tr]), np.zeros(int((~tr).sum()), dtype=np.int32))
+            assert np.array_equal(tv != 0, tr) and np.array_equal(np_bits(tv[~tr]), np.zeros(int((~tr).sum()), dtype=np.uint32))
             _, _, v64 = ar.heads_f64(fo[tr], S.p, net)
             err = float(np.abs(tv[tr] - v64).max())
             assert err < pr.TOL_EXACT, (k, name, err)
@@ -498,7 +427,7 @@ def test_collectors_with_the_switch_on(descs, safe):
 
     # (a) the collector, eagerly, nothing synchronised inside collect()
     A = _Col(descs, safe)
-    col = A.collector()
+    col = _collector(A)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     on = []
@@ -512,33 +441,16 @@ def test_collectors_with_the_switch_on(descs, safe):
                 assert _bits_equal(got[key], want[k][key]), "eager collect %d: %s differs from the synchronised loop" % (k, key)
     A.eng.close()
 
-    # (b) collect() captured in a HIP graph behind one eager rollout, replayed twice
+    # (b) collect() captured in a HIP graph behind one eager rollout, replayed twice, against the eager collects
     B = _Col(descs, safe)
-    col = B.collector()
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s), torch.no_grad():
-        got = _snapshot(col.collect(), keys)
-        for key in keys:
-            assert _bits_equal(got[key], on[0][key]), key
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(g, stream=s):
-        batch = col.collect()
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s), torch.no_grad():
-        for k in (1, 2):
-            g.replay()
-            got = _snapshot(batch, keys)
-            for key in keys:
-                assert _bits_equal(got[key], on[k][key]), "graph replay %d: %s differs from the eager collect" % (k, key)
-    del g
+    col = _collector(B)
+    eager_then_graph(col.collect, lambda: _snapshot(col.batch, keys), on)
     B.eng.close()
 
     # (c) the switch off, same engine configuration (step info on) and seeds: the same trajectory, today's pgd_gae bit for bit -- which
     # differs from the switched-on advantages at every truncated step
     Cc = _Col(descs, safe)
-    col = Cc.collector(on=False)
+    col = _collector(Cc, on=False)
     with torch.no_grad():
         for k in range(3):
             batch = col.collect()
@@ -573,7 +485,7 @@ def test_a_time_limit_is_invisible_to_a_correct_critic_on_the_device(descs):
             w[:] = 0.0
         S.v[5][0] = V
         S.vw = tuple(_dev(w) for w in S.v)
-        col = S.collector(on=on)
+        col = _collector(S, on=on)
         eng = S.eng
         try:
             with torch.no_grad():
