@@ -908,6 +908,14 @@ int pgd_forget_rows(pgd_handle h);
  * when the stamps agree.  (No reference counterpart: the reference ships no native binary on this path.) */
 const char* pgd_source_sha(void);
 
+/* The plan of a handle's table arena: the read-only tables of an engine (maps, lanes, grid cells, scenarios, spawn records, reset images,
+ * beam directions) live in one device allocation and are addressed by the kernels as its base + an UNSIGNED 32-bit byte offset.
+ * bytes[n]: the tables' sizes, in their order.  offsets[n] receives each table's byte offset (256-byte aligned, in that order, the first
+ * behind 4 KiB of padding), *total the arena's size.  PGD_ERR_ARG when the arena would exceed 4 GiB - 64 KiB: an offset plus an index inside a table must
+ * not wrap.  Pure arithmetic: nothing is allocated, no GPU is touched (the uploads call it; exported for the tests).
+ * (No reference counterpart: the reference keeps its maps in Python objects.) */
+int pgd_plan_arena(const uint64_t* bytes, int n, uint32_t* offsets, uint64_t* total);
+
 /* Top-down (bird's-eye) multi-channel observation: TopDownMultiChannel.observe (obs/top_down_obs_multi_channel.py:18-280) of
  * TopDownPGDriveEnv (envs/top_down_env.py:28-42) as a rasteriser kernel.  Image [N, R, R, 2 + frame_stack] float32 in [0, 1]:
  * channel 0 road network (lane lines, route lanes), 1 past ego positions, 2.. the other vehicles now and frame_skip, 2 *

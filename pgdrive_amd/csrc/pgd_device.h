@@ -23,6 +23,24 @@
 // (An opaque type: nothing indexes a record as an array element any more.)
 struct RecPiece { uint4 q; };
 
+// A read-only table of the handle's arena: the arena's base (wave-uniform, two scalar registers shared by every table) and the table's
+// byte offset in it.  Element i lies at base + zext(off + i * sizeof(T)), computed in UNSIGNED 32-BIT arithmetic -- indices must not widen
+// to 64 bits before the add: the arena is planned below 4 GiB, so nothing wraps, offsets above 2^31 included.
+template <class T> struct Tab {
+  const char* base;
+  uint32_t off;
+  DEV const T* at(uint32_t i) const { return reinterpret_cast<const T*>(base + (uint32_t)(off + i * (uint32_t)sizeof(T))); }
+  template <class I> DEV const T& operator[](I i) const { return *at((uint32_t)i); }
+  template <class I> DEV Tab operator+(I first) const { return from((uint32_t)first); }
+  DEV const T& operator*() const { return *at(0u); }
+  DEV const T* operator->() const { return at(0u); }
+  // element i of an array field (of F, `field_off` bytes into the record) of the view's first record, in the same 32-bit arithmetic
+  template <class F, class I> DEV F field(uint32_t field_off, I i) const {
+    return *reinterpret_cast<const F*>(base + (uint32_t)(off + field_off + (uint32_t)i * (uint32_t)sizeof(F)));
+  }
+  DEV Tab from(uint32_t first) const { return Tab{base, off + first * (uint32_t)sizeof(T)}; }  // the table from element `first` on
+};
+
 // ---------------------------------------------------------------------------------------------------------------------
 // device-side view of the engine
 // ---------------------------------------------------------------------------------------------------------------------
@@ -33,19 +51,38 @@ struct PgdDev {
   int sub;        // sub-lanes cooperating on one vehicle
   int pack_obs;   // several envs per wave (throughput mode): k_step appends the lidar observation of every env of the wave
   int sstride;    // pgd_spawn records per scenario: V slots + respawn_places * respawn_dests (multi-agent)
-  const pgd_map* maps;
-  const pgd_lane* lanes;
-  const pgd_road* roads;
-  const pgd_box* boxes;
-  const int32_t* cell_start;
-  const int32_t* cell_items;
-  const pgd_box* cell_boxes;  // cell-major copies of the boxes, lane boxes first inside each cell (pgd_upload_maps)
-  const struct LaneExt* cell_ext;  // same indexing: what localisation needs from the lane of a lane box
-  const struct LaneNav* lane_nav;  // per lane: what the navigation block of the observation needs
-  const pgd_scenario* scen;
-  const pgd_map* scen_map;    // [n_scen] copy of each scenario's map header
-  const pgd_spawn* spawns;
-  const float2* spawn_hv;     // [n_scen * sstride] (cos, sin) of each spawn heading (k_spawn_hv at upload)
+  // The read-only tables live in ONE device arena per handle (pgd_engine.hip: plan_arena): its base and an unsigned 32-bit byte offset
+  // per table.  A table address is tab + zext(offset + index * sizeof(T)), all of it 32-bit arithmetic (Tab above): the compiler
+  // selects the scalar-base form of the memory instructions (one VGPR of address instead of a pair), and the tables cost 2 + 16
+  // scalar registers instead of 32.
+  const char* tab;
+  uint32_t o_maps, o_lanes, o_roads, o_boxes, o_cell_start, o_cell_items;
+  uint32_t o_cell_boxes;  // cell-major copies of the boxes, lane boxes first inside each cell (pgd_upload_maps)
+  uint32_t o_cell_ext;    // same indexing: what localisation needs from the lane of a lane box
+  uint32_t o_lane_nav;    // per lane: what the navigation block of the observation needs
+  uint32_t o_scen;
+  uint32_t o_scen_map;    // [n_scen] copy of each scenario's map header
+  uint32_t o_spawns;
+  uint32_t o_spawn_hv;    // [n_scen * sstride] (cos, sin) of each spawn heading (k_spawn_hv at upload)
+  uint32_t o_reset_img;   // [n_scen] blocks of V records: every slot right after a reset of its scenario (k_reset_image)
+  uint32_t o_respawn_img; // [n_scen] blocks of sstride - V records (multi-agent): an agent right after it was spawned from respawn record V + k
+  uint32_t o_beam;        // [num_lasers] (cos, sin) of the beam angle i * 2 pi / num_lasers in the vehicle frame
+  DEV Tab<pgd_map> maps() const { return {tab, o_maps}; }
+  DEV Tab<pgd_lane> lanes() const { return {tab, o_lanes}; }
+  DEV Tab<pgd_road> roads() const { return {tab, o_roads}; }
+  DEV Tab<pgd_box> boxes() const { return {tab, o_boxes}; }
+  DEV Tab<int32_t> cell_start() const { return {tab, o_cell_start}; }
+  DEV Tab<int32_t> cell_items() const { return {tab, o_cell_items}; }
+  DEV Tab<pgd_box> cell_boxes() const { return {tab, o_cell_boxes}; }
+  DEV Tab<struct LaneExt> cell_ext() const { return {tab, o_cell_ext}; }
+  DEV Tab<struct LaneNav> lane_nav() const { return {tab, o_lane_nav}; }
+  DEV Tab<pgd_scenario> scen() const { return {tab, o_scen}; }
+  DEV Tab<pgd_map> scen_map() const { return {tab, o_scen_map}; }
+  DEV Tab<pgd_spawn> spawns() const { return {tab, o_spawns}; }
+  DEV Tab<float2> spawn_hv() const { return {tab, o_spawn_hv}; }
+  DEV Tab<RecPiece> reset_img() const { return {tab, o_reset_img}; }
+  DEV Tab<RecPiece> respawn_img() const { return {tab, o_respawn_img}; }
+  DEV Tab<float2> beam() const { return {tab, o_beam}; }
   int n_scen;
   RecPiece* rec;  // [N] blocks of V records of 128 bytes, piece planes (above; device layout, the ABI blobs are field-major)
   int32_t* ei;         // [N][PGD_NEI]
@@ -54,9 +91,6 @@ struct PgdDev {
   int use_imask;       // 0: every slot is read from the env's own record (one env per wave: one dependent load level less)
   int no_groups;       // no uploaded scenario has a traffic trigger group (pgd_upload_scenarios): the trigger test of a step is skipped
   unsigned long long* imask;  // [N] bit s: slot s of the env still equals its scenario's reset image (never stored since)
-  const RecPiece* reset_img;  // [n_scen] blocks of V records: every slot right after a reset of its scenario (k_reset_image)
-  const RecPiece* respawn_img;  // [n_scen] blocks of sstride - V records (multi-agent): an agent right after it was spawned from respawn record V + k
-  const float2* beam;  // [num_lasers] (cos, sin) of the beam angle i * 2 pi / num_lasers in the vehicle frame
   // output addressing of one launch: the observation row of (env e, agent a) starts at obs + e * ostride + a * D.
   // pgd_step: ostride = A * D (dense [N, A, D]).  pgd_step_packed: ostride = the caller's row stride and `prow` = the same
   // buffer: reward and done (as 0 / 1 floats) are written behind the A * D observation floats of the env's row, so the row
@@ -138,9 +172,9 @@ struct __attribute__((aligned(16))) LaneNav {
   float pad;
 };
 
-// The hot tables (lanes, grid cells and their boxes) are carried as pointers; the road table and the per-lane navigation extract
-// are touched once or twice per step and are addressed from the engine view where they are used (`roads()`, `lnav()`): every
-// pointer carried through the whole kernel costs two SGPRs, and k_step spills SGPRs.
+// The hot tables (lanes, grid cells and their boxes) are carried as arena offsets (Tab: one SGPR each on the shared base); the road
+// table and the per-lane navigation extract are touched once or twice per step and are addressed from the engine view where they are
+// used (`roads()`, `lnav()`): every value carried through the whole kernel costs scalar registers, and k_step spills SGPRs.
 // the scalars of the map header the step uses after its first store (grid geometry, lane width): read once with the header, at the
 // start of the kernel -- a read of the header later on is a vector-memory read (the compiler may not assume the table unchanged
 // once the kernel has stored anything), waited for on the spot
@@ -158,24 +192,25 @@ struct MapView {
   DEV float oy() const { return m->oy; }
   DEV float cell() const { return m->cell; }
   DEV float lane_width() const { return m->lane_width; }
-  const pgd_lane* lanes;
-  const int32_t* cstart;
-  const LaneExt* cext;
-  const pgd_box* cbox;
-  int road_off, lane_off;  // (two SGPRs instead of four: the bases come from the kernel arguments at the point of use)
-  DEV const pgd_road* roads() const { return dv->roads + road_off; }
-  DEV const LaneNav* lnav() const { return dv->lane_nav + lane_off; }
+  // the map's tables: the per-map first indices of the header are folded into the offsets (scalar 32-bit arithmetic)
+  Tab<pgd_lane> lanes;
+  Tab<int32_t> cstart;
+  Tab<LaneExt> cext;
+  Tab<pgd_box> cbox;
+  int road_off, lane_off;  // (the offsets come from the kernel arguments at the point of use)
+  DEV Tab<pgd_road> roads() const { return dv->roads().from((uint32_t)road_off); }
+  DEV Tab<LaneNav> lnav() const { return dv->lane_nav().from((uint32_t)lane_off); }
 };
 
 DEV MapView map_view_of(const PgdDev& d, const pgd_map* m) {
   MapView v;
   v.dv = &d;
   v.m = m;
-  v.lanes = d.lanes + m->lane_off;
+  v.lanes = d.lanes().from((uint32_t)m->lane_off);
   v.road_off = m->road_off; v.lane_off = m->lane_off;
-  v.cstart = d.cell_start + m->cell_off;
-  v.cext = d.cell_ext + m->item_off;
-  v.cbox = d.cell_boxes + m->item_off;
+  v.cstart = d.cell_start().from((uint32_t)m->cell_off);
+  v.cext = d.cell_ext().from((uint32_t)m->item_off);
+  v.cbox = d.cell_boxes().from((uint32_t)m->item_off);
   return v;
 }
 // the same view with the header's scalars read ahead, with the header itself (kernels specialised for a default configuration:
@@ -198,7 +233,7 @@ template <> DEV MapViewPre map_view_as<MapViewPre>(const PgdDev& d, const pgd_ma
   v.grid = MapGrid{m->gx, m->gy, m->ox, m->oy, m->cell, m->lane_width};
   return v;
 }
-DEV MapView map_view(const PgdDev& d, int map) { return map_view_of(d, d.maps + map); }
+DEV MapView map_view(const PgdDev& d, int map) { return map_view_of(d, d.maps().at((uint32_t)map)); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // scalar helpers: utils/math_utils.py:32-94, cutils.pyx:147-154

@@ -42,6 +42,9 @@ static Switches read_switches() {
 // (LDS_AC .. LDS_TERM_VALUE: the instantiations that normalise their observation rows, pgd_obs_norm_bind, have slots of their own behind them)
 enum LdsKernel { LDS_MLP, LDS_MLP_TANH, LDS_MLP_BF, LDS_MLP_BF_TANH, LDS_AC, LDS_AC_ROWS, LDS_AC_COST, LDS_PPO_ROWS, LDS_PPO_ROWS_COST, LDS_TERM_VALUE,
                  LDS_NORM_FIRST, LDS_GUARD = LDS_NORM_FIRST + (LDS_TERM_VALUE - LDS_AC + 1), LDS_GUARD_LEGACY, LDS_KERNELS };
+// the tables of the arena, in the order of their offsets (what follows the scenarios first, what follows the maps behind it)
+enum ArenaTable { TB_SCEN, TB_SCEN_MAP, TB_SPAWNS, TB_SPAWN_HV, TB_RESET_IMG, TB_RESPAWN_IMG, TB_MAPS, TB_LANES, TB_ROADS, TB_BOXES, TB_CELL_START,
+                  TB_CELL_ITEMS, TB_CELL_BOXES, TB_CELL_EXT, TB_LANE_NAV, TB_BEAM, TB_COUNT };
 struct pgd_engine {
   PgdDev d;
   Switches sw;
@@ -55,19 +58,15 @@ struct pgd_engine {
   hipEvent_t ev_ids;    // pgd_reset: the pinned id staging buffer has been consumed
   int32_t* h_ids;       // pinned staging [2N] of pgd_reset's host id lists (no stream synchronisation per reset)
   bool ids_pending;
-  pgd_map* maps; pgd_lane* lanes; pgd_road* roads; pgd_box* boxes; int32_t* cell_start; int32_t* cell_items;
-  pgd_box* cell_boxes;
-  LaneExt* cell_ext;
-  LaneNav* lane_nav;
-  float2* spawn_hv;
-  pgd_map* scen_map;  // per scenario: copy of its map header (saves one dependent load per block)
-  float2* beam;       // lidar beam directions in the vehicle frame
-  RecPiece* reset_img;  // [n_scen] blocks of V records, rebuilt after every map / scenario upload
-  RecPiece* respawn_img;  // [n_scen] blocks of sstride - V records (multi-agent), rebuilt with it
+  // the read-only tables (PgdDev::tab and its offsets): one device allocation, planned by pgd_plan_arena from the tables' sizes
+  // and rebuilt by arena_resize when an upload changes one of them
+  char* arena;
+  uint64_t arena_bytes;
+  uint64_t tab_bytes[TB_COUNT];
+  uint32_t tab_off[TB_COUNT];
   bool img_dirty;
   std::vector<pgd_map>* h_maps;
   std::vector<pgd_scenario>* h_scen;
-  pgd_scenario* scen; pgd_spawn* spawns;
   int32_t* d_ids;  // scratch [2N]
   bool have_maps, have_scen;
   // per-kernel HIP-event profile of pgd_step launches (bench.py roofline numbers)
@@ -381,12 +380,59 @@ static int step_info_launch(pgd_engine* h, const EnvGroup& g, const uint8_t* d_d
 static void render_mark_stale(pgd_engine* h);
 static int render_forget(pgd_engine* h, const int32_t* d_env, int n);
 
+template <typename T> static T* arena_ptr(const pgd_engine* h, int table) { return reinterpret_cast<T*>(h->arena + h->tab_off[table]); }
+
+// Gives the `n` tables `ids` the sizes `bytes`.  The other tables keep their contents, the resized ones hold nothing defined afterwards.
+// A plan that moves no table and fits the arena changes nothing; any other one is a new arena, built at the stream's quiet point (the
+// upload calls synchronise anyway): the kept tables are copied over, the old arena is freed, the device view follows.  Launches never
+// come here: they allocate nothing.
+static int arena_resize(pgd_engine* h, const int* ids, const uint64_t* bytes, int n) {
+  uint64_t want[TB_COUNT];
+  uint32_t off[TB_COUNT];
+  uint64_t total = 0;
+  bool resized[TB_COUNT] = {};
+  memcpy(want, h->tab_bytes, sizeof(want));
+  for (int k = 0; k < n; ++k) { want[ids[k]] = bytes[k]; resized[ids[k]] = true; }
+  { int rc = pgd_plan_arena(want, TB_COUNT, off, &total); if (rc) return rc; }
+  if (!h->arena || total > h->arena_bytes || memcmp(off, h->tab_off, sizeof(off)) != 0) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    char* fresh = nullptr;
+    HIPCHK(hipMalloc((void**)&fresh, (size_t)total));
+    for (int t = 0; t < TB_COUNT; ++t)
+      if (h->arena && !resized[t] && want[t])
+        HIPCHK(hipMemcpyAsync(fresh + off[t], h->arena + h->tab_off[t], (size_t)want[t], hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->arena) HIPCHK(hipFree(h->arena));
+    h->arena = fresh;
+    h->arena_bytes = total;
+    memcpy(h->tab_off, off, sizeof(off));
+  }
+  memcpy(h->tab_bytes, want, sizeof(want));
+  PgdDev& d = h->d;
+  const uint32_t* o = h->tab_off;
+  d.tab = h->arena;
+  d.o_maps = o[TB_MAPS]; d.o_lanes = o[TB_LANES]; d.o_roads = o[TB_ROADS]; d.o_boxes = o[TB_BOXES]; d.o_cell_start = o[TB_CELL_START];
+  d.o_cell_items = o[TB_CELL_ITEMS]; d.o_cell_boxes = o[TB_CELL_BOXES]; d.o_cell_ext = o[TB_CELL_EXT]; d.o_lane_nav = o[TB_LANE_NAV];
+  d.o_scen = o[TB_SCEN]; d.o_scen_map = o[TB_SCEN_MAP]; d.o_spawns = o[TB_SPAWNS]; d.o_spawn_hv = o[TB_SPAWN_HV];
+  d.o_reset_img = o[TB_RESET_IMG]; d.o_respawn_img = o[TB_RESPAWN_IMG]; d.o_beam = o[TB_BEAM];
+  return PGD_OK;
+}
+
+// host data into a table that arena_resize has sized (no synchronisation: the caller's, after its last table)
 template <typename T>
-static int upload(T** dst, const T* src, size_t n, hipStream_t st) {
-  if (*dst) { HIPCHK(hipFree(*dst)); *dst = nullptr; }
-  HIPCHK(hipMalloc(dst, sizeof(T) * (n ? n : 1)));
-  if (n) HIPCHK(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
+static int arena_fill(pgd_engine* h, int table, const T* src, size_t n) {
+  if (sizeof(T) * n > h->tab_bytes[table]) return PGD_ERR_STATE;
+  if (n) HIPCHK(hipMemcpyAsync(arena_ptr<T>(h, table), src, sizeof(T) * n, hipMemcpyHostToDevice, h->stream));
+  return PGD_OK;
+}
+// one table: size, fill, wait (the staging memory may go out of scope)
+template <typename T>
+static int upload(pgd_engine* h, int table, const T* src, size_t n) {
+  const int ids[1] = {table};
+  const uint64_t bytes[1] = {sizeof(T) * n};
+  int rc = arena_resize(h, ids, bytes, 1);
+  if (rc || (rc = arena_fill(h, table, src, n))) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
   return PGD_OK;
 }
 
@@ -398,10 +444,7 @@ static int build_scen_map(pgd_engine* h) {
     if (m < 0 || m >= (int)h->h_maps->size()) return PGD_ERR_ARG;
     sm[k] = (*h->h_maps)[m];
   }
-  int rc = upload(&h->scen_map, sm.data(), sm.size(), h->stream);
-  if (rc) return rc;
-  h->d.scen_map = h->scen_map;
-  return PGD_OK;
+  return upload(h, TB_SCEN_MAP, sm.data(), sm.size());
 }
 
 // rebuild the derived part of the records (needs maps + scenarios; deferred until both are there)
@@ -423,19 +466,18 @@ static int build_reset_image(pgd_engine* h) {
   h->derive_pending = true;
   { int rc = derive_records(h); if (rc) return rc; }
   if (!h->img_dirty) return PGD_OK;
-  if (h->reset_img) { HIPCHK(hipFree(h->reset_img)); h->reset_img = nullptr; }
-  HIPCHK(hipMalloc(&h->reset_img, sizeof(VehRec) * (size_t)h->d.n_scen * h->d.V));
-  h->d.reset_img = h->reset_img;
+  const size_t n_respawn = h->d.sstride > h->d.V ? (size_t)h->d.n_scen * (h->d.sstride - h->d.V) : 0;
+  {
+    const int ids[2] = {TB_RESET_IMG, TB_RESPAWN_IMG};
+    const uint64_t bytes[2] = {sizeof(VehRec) * (uint64_t)h->d.n_scen * h->d.V, sizeof(VehRec) * (uint64_t)n_respawn};
+    int rc = arena_resize(h, ids, bytes, 2);
+    if (rc) return rc;
+  }
   const int blocks = (h->d.n_scen + h->d.epw - 1) / h->d.epw;
-  hipLaunchKernelGGL(k_reset_image, dim3(blocks), dim3(WAVE), 0, h->stream, h->d, h->reset_img);
+  hipLaunchKernelGGL(k_reset_image, dim3(blocks), dim3(WAVE), 0, h->stream, h->d, arena_ptr<RecPiece>(h, TB_RESET_IMG));
   HIPCHK(hipGetLastError());
-  if (h->respawn_img) { HIPCHK(hipFree(h->respawn_img)); h->respawn_img = nullptr; }
-  h->d.respawn_img = nullptr;
-  if (h->d.sstride > h->d.V) {
-    const size_t n = (size_t)h->d.n_scen * (h->d.sstride - h->d.V);
-    HIPCHK(hipMalloc(&h->respawn_img, sizeof(VehRec) * n));
-    h->d.respawn_img = h->respawn_img;
-    hipLaunchKernelGGL(k_respawn_image, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d, h->respawn_img);
+  if (n_respawn) {
+    hipLaunchKernelGGL(k_respawn_image, dim3((unsigned)((n_respawn + 255) / 256)), dim3(256), 0, h->stream, h->d, arena_ptr<RecPiece>(h, TB_RESPAWN_IMG));
     HIPCHK(hipGetLastError());
   }
   h->img_dirty = false;
@@ -468,6 +510,20 @@ const char* pgd_version(void) { return "pgdrive_hip 0.1 (gfx950)"; }
 #define PGD_SOURCE_SHA "unstamped"  // (an experimental build outside pgdrive_amd/build.py: no committed counter pass is its own)
 #endif
 const char* pgd_source_sha(void) { return PGD_SOURCE_SHA; }
+
+int pgd_plan_arena(const uint64_t* bytes, int n, uint32_t* offsets, uint64_t* total) {
+  if (!bytes || !offsets || !total || n <= 0) return PGD_ERR_ARG;
+  const uint64_t limit = (1ull << 32) - (64ull << 10), align = 256;
+  uint64_t at = 4096;  // (a record in front of a table's first -- index -1, read and discarded here and there -- stays inside the arena)
+  for (int k = 0; k < n; ++k) {
+    if (at > limit || bytes[k] > limit - at) return PGD_ERR_ARG;  // (compared before the add: 64-bit sizes cannot wrap the sum)
+    offsets[k] = (uint32_t)at;
+    at = (at + bytes[k] + align - 1) / align * align;
+  }
+  if (at > limit) return PGD_ERR_ARG;
+  *total = at ? at : align;
+  return PGD_OK;
+}
 
 int pgd_obs_dim(const pgd_config* c) {
   const int toll = (c->marl_flags & PGD_MA_TOLLGATE) != 0;
@@ -546,9 +602,8 @@ int pgd_create(const pgd_config* cfg, int device, void* hip_stream, pgd_handle* 
       const double a = (double)i * (2.0 * 3.14159265358979323846 / (double)cfg->num_lasers);
       bt[(size_t)i] = make_float2((float)cos(a), (float)sin(a));
     }
-    int rc = upload(&h->beam, bt.data(), bt.size(), h->stream);
+    int rc = upload(h, TB_BEAM, bt.data(), bt.size());
     if (rc) return rc;
-    h->d.beam = h->beam;
   }
   *out = h;
   return PGD_OK;
@@ -562,11 +617,12 @@ int pgd_upload_maps(pgd_handle h, const pgd_map* maps, int n_maps, const pgd_lan
     if (maps[m].n_roads > 4095 || maps[m].n_lanes > 65535) return PGD_ERR_ARG;
   HIPCHK(hipSetDevice(h->device));
   int rc;
-  if ((rc = upload(&h->maps, maps, n_maps, h->stream))) return rc;
+  // (the device forms are built first, the arena is sized for all of them at once, then they are copied in)
+  std::vector<pgd_lane> dl(lanes, lanes + n_lanes);
+  std::vector<LaneNav> nav((size_t)(n_lanes > 0 ? n_lanes : 1));
   {
     // device copy of the lane table: `pad` carries the lane count of the lane's road (the lanes of a road are consecutive,
     // so neighbour lanes follow from the lane id alone: no road-record read in the IDM neighbour search)
-    std::vector<pgd_lane> dl(lanes, lanes + n_lanes);
     for (int m = 0; m < n_maps; ++m)
       for (int k = 0; k < maps[m].n_lanes; ++k) {
         pgd_lane& L = dl[(size_t)maps[m].lane_off + k];
@@ -636,8 +692,6 @@ int pgd_upload_maps(pgd_handle h, const pgd_map* maps, int n_maps, const pgd_lan
         L.pad = (L.road >= 0 && L.road < maps[m].n_roads) ? roads[(size_t)maps[m].road_off + L.road].from : (int16_t)-1;
       }
     }
-    if ((rc = upload(&h->lanes, dl.data(), n_lanes, h->stream))) return rc;
-    std::vector<LaneNav> nav((size_t)(n_lanes > 0 ? n_lanes : 1));
     for (int k = 0; k < n_lanes; ++k) {
       const pgd_lane& L = lanes[k];
       LaneNav& v = nav[(size_t)k];
@@ -650,12 +704,7 @@ int pgd_upload_maps(pgd_handle h, const pgd_map* maps, int n_maps, const pgd_lan
                     L.bx, L.dir, L.dir == 1.0f ? L.c - L.by : L.by - L.c, 0.0f};
       }
     }
-    if ((rc = upload(&h->lane_nav, nav.data(), (size_t)n_lanes, h->stream))) return rc;
-    h->d.lane_nav = h->lane_nav;
   }
-  if ((rc = upload(&h->roads, roads, n_roads, h->stream))) return rc;
-  if ((rc = upload(&h->boxes, boxes, n_boxes, h->stream))) return rc;
-  if ((rc = upload(&h->cell_items, ci, n_ci, h->stream))) return rc;
   // cell-major copies of the boxes: cell_boxes[item_off + k] = boxes[box_off + cell_items[item_off + k]] — one dependent
   // load less per box in the grid walks, and a cell's boxes are contiguous (coalesced across sub-lanes)
   {
@@ -690,12 +739,19 @@ int pgd_upload_maps(pgd_handle h, const pgd_map* maps, int n_maps, const pgd_lan
           }
       }
     }
-    if ((rc = upload(&h->cell_boxes, cb.data(), (size_t)n_ci, h->stream))) return rc;
-    if ((rc = upload(&h->cell_ext, cx.data(), (size_t)n_ci, h->stream))) return rc;
-    if ((rc = upload(&h->cell_start, cs2.data(), n_cs, h->stream))) return rc;
+    const int ids[9] = {TB_MAPS, TB_LANES, TB_LANE_NAV, TB_ROADS, TB_BOXES, TB_CELL_ITEMS, TB_CELL_BOXES, TB_CELL_EXT, TB_CELL_START};
+    const uint64_t bytes[9] = {sizeof(pgd_map) * (uint64_t)n_maps, sizeof(pgd_lane) * (uint64_t)n_lanes, sizeof(LaneNav) * (uint64_t)n_lanes,
+                               sizeof(pgd_road) * (uint64_t)n_roads, sizeof(pgd_box) * (uint64_t)n_boxes, sizeof(int32_t) * (uint64_t)n_ci,
+                               sizeof(pgd_box) * (uint64_t)n_ci, sizeof(LaneExt) * (uint64_t)n_ci, sizeof(int32_t) * (uint64_t)n_cs};
+    if ((rc = arena_resize(h, ids, bytes, 9))) return rc;
+    if ((rc = arena_fill(h, TB_MAPS, maps, (size_t)n_maps)) || (rc = arena_fill(h, TB_LANES, dl.data(), (size_t)n_lanes)) ||
+        (rc = arena_fill(h, TB_LANE_NAV, nav.data(), (size_t)n_lanes)) || (rc = arena_fill(h, TB_ROADS, roads, (size_t)n_roads)) ||
+        (rc = arena_fill(h, TB_BOXES, boxes, (size_t)n_boxes)) || (rc = arena_fill(h, TB_CELL_ITEMS, ci, (size_t)n_ci)) ||
+        (rc = arena_fill(h, TB_CELL_BOXES, cb.data(), (size_t)n_ci)) || (rc = arena_fill(h, TB_CELL_EXT, cx.data(), (size_t)n_ci)) ||
+        (rc = arena_fill(h, TB_CELL_START, cs2.data(), (size_t)n_cs)))
+      return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the staging vectors go out of scope)
   }
-  h->d.maps = h->maps; h->d.lanes = h->lanes; h->d.roads = h->roads; h->d.boxes = h->boxes;
-  h->d.cell_start = h->cell_start; h->d.cell_items = h->cell_items; h->d.cell_boxes = h->cell_boxes; h->d.cell_ext = h->cell_ext;
   if (!h->h_maps) h->h_maps = new std::vector<pgd_map>();
   h->h_maps->assign(maps, maps + n_maps);
   if ((rc = build_scen_map(h))) return rc;
@@ -711,7 +767,12 @@ int pgd_upload_scenarios(pgd_handle h, const pgd_scenario* scen, int n_scen, con
   if (!h || !scen || n_scen <= 0 || !spawns) return PGD_ERR_ARG;
   HIPCHK(hipSetDevice(h->device));
   int rc;
-  if ((rc = upload(&h->scen, scen, n_scen, h->stream))) return rc;
+  const size_t ns = (size_t)n_scen * h->d.sstride;
+  {
+    const int ids[3] = {TB_SCEN, TB_SPAWNS, TB_SPAWN_HV};
+    const uint64_t bytes[3] = {sizeof(pgd_scenario) * (uint64_t)n_scen, sizeof(pgd_spawn) * (uint64_t)ns, sizeof(float2) * (uint64_t)ns};
+    if ((rc = arena_resize(h, ids, bytes, 3)) || (rc = arena_fill(h, TB_SCEN, scen, (size_t)n_scen))) return rc;
+  }
   {
     // device-private form of the routes: PGD_CKPT_END from a route's last node on (update_checkpoints: a match on the last node
     // alone changes nothing, navigation.py:270-277 -- the search stops at the mark instead of reading the route length first)
@@ -720,18 +781,13 @@ int pgd_upload_scenarios(pgd_handle h, const pgd_scenario* scen, int n_scen, con
       const int n = q.n_ckpt < 0 ? 0 : (q.n_ckpt > PGD_MAX_CKPT ? PGD_MAX_CKPT : q.n_ckpt);
       for (int k = n > 0 ? n - 1 : 0; k < PGD_MAX_CKPT; ++k) q.ckpt[k] = (int16_t)PGD_CKPT_END;
     }
-    if ((rc = upload(&h->spawns, dsp.data(), dsp.size(), h->stream))) return rc;
+    if ((rc = arena_fill(h, TB_SPAWNS, dsp.data(), dsp.size()))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));  // (the staging vector goes out of scope)
   }
-  h->d.scen = h->scen; h->d.spawns = h->spawns; h->d.n_scen = n_scen;
-  {
-    const size_t ns = (size_t)n_scen * h->d.sstride;
-    if (h->spawn_hv) { HIPCHK(hipStreamSynchronize(h->stream)); HIPCHK(hipFree(h->spawn_hv)); h->spawn_hv = nullptr; }
-    HIPCHK(hipMalloc((void**)&h->spawn_hv, sizeof(float2) * ns));
-    hipLaunchKernelGGL(k_spawn_hv, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, h->stream, h->spawns, h->spawn_hv, ns);
-    HIPCHK(hipGetLastError());
-    h->d.spawn_hv = h->spawn_hv;
-  }
+  h->d.n_scen = n_scen;
+  hipLaunchKernelGGL(k_spawn_hv, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, h->stream, (const pgd_spawn*)arena_ptr<pgd_spawn>(h, TB_SPAWNS),
+                     arena_ptr<float2>(h, TB_SPAWN_HV), ns);
+  HIPCHK(hipGetLastError());
   for (size_t k = 0; k < (size_t)n_scen * h->d.sstride; ++k)
     if (spawns[k].lane >= 0 && (!(spawns[k].max_steer <= 1.0f) || spawns[k].n_ckpt > PGD_MAX_CKPT)) return PGD_ERR_ARG;  // tan_small
   h->d.no_groups = 1;
@@ -832,7 +888,7 @@ static int step_impl(pgd_handle h, const float* d_actions, float* d_obs, float* 
   dv.unit_off = p.g.first / h->d.epw;
   dv.state_rows = p.state_in_step ? d_obs : nullptr;
   if (h->sinfo) dv.cfg.auto_reset = 0;  // step info: the step leaves the terminal state and row, k_step_info restarts the env (pgd_step_info.h)
-  PgdCold cold_arg{dv.scen_map, dv.bev_fill, dv.spawn_hv, dv.respawn_img, dv.n_scen, dv.cfg.seed, dv.cfg.env_base,
+  PgdCold cold_arg{dv.bev_fill, dv.o_scen_map, dv.o_spawn_hv, dv.o_respawn_img, dv.n_scen, dv.cfg.seed, dv.cfg.env_base,
                    h->lk.obs, h->lk.k_lat, h->lk.k_head, h->lk.v_target, h->lk.noise, h->lk.tick};
   float* obs_arg = p.fuse ? d_obs : (float*)nullptr;
   const int blocks = (p.g.count + h->d.epw - 1) / h->d.epw;
@@ -1376,8 +1432,7 @@ int pgd_destroy(pgd_handle h) {
   if (!h) return PGD_ERR_ARG;
   (void)hipStreamSynchronize(h->stream);
   if (h->jit_mod) { (void)hipModuleUnload(h->jit_mod); h->jit_mod = nullptr; h->jit_fn = nullptr; }
-  void* bufs[] = {h->cmp_live, h->cmp_index, h->lk_act, h->rowz, h->d.rec, h->d.ei, h->d.imask, h->d.env_map, h->d_ids, h->maps, h->lanes, h->roads, h->boxes, h->cell_start,
-                  h->cell_items, h->cell_boxes, h->cell_ext, h->lane_nav, h->scen_map, h->scen, h->spawns, h->spawn_hv, h->beam, h->reset_img, h->respawn_img};
+  void* bufs[] = {h->cmp_live, h->cmp_index, h->lk_act, h->rowz, h->d.rec, h->d.ei, h->d.imask, h->d.env_map, h->d_ids, h->arena};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   (void)hipEventDestroy(h->ev0);

@@ -149,8 +149,8 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_guardian(const PgdDev d
   vl = min(vl, max(n_lanes, 1) - 1);
   vs = min(vs, d.sstride - 1);
   scen = min(max(scen, 0), d.n_scen - 1);
-  const pgd_lane ln = d.lanes[(size_t)lane_off + vl];
-  const float ms = d.spawns[(size_t)scen * d.sstride + vs].max_speed;
+  const pgd_lane ln = d.lanes()[(size_t)lane_off + vl];
+  const float ms = d.spawns()[(size_t)scen * d.sstride + vs].max_speed;
   if (LEGACY) gd_load_rows_legacy(obs, row0, r0, n_rows, obs_stride, in_dim, kp, xs, wave, lane, X);
   else ac_load_rows<false>(obs, row0, r0, n_rows, obs_stride, in_dim, kp, xs, wave, lane, X, ObsNorm{nullptr, 0.0f});
 #pragma unroll

@@ -18,13 +18,13 @@ __global__ void k_spawn_hv(const pgd_spawn* __restrict__ sp, float2* __restrict_
 DEV unsigned long long reset_slot(const PgdDev& d, const LaneMap& lm, int scen, Veh& r) {
   const int A = d.A, s = lm.s;
   const Grp g{lm.sub, d.sub, lm.lead};
-  const pgd_spawn* sp = d.spawns + (size_t)scen * d.sstride + s;
-  MapView mv = map_view(d, d.scen[scen].map);
-  reset_vehicle(*sp, d.spawn_hv[(size_t)scen * d.sstride + s], r, s, s < A && !d.cfg.idm_agent);
+  const Tab<pgd_spawn> sp = d.spawns() + (size_t)scen * d.sstride + s;
+  MapView mv = map_view(d, d.scen()[scen].map);
+  reset_vehicle(*sp, d.spawn_hv()[(size_t)scen * d.sstride + s], r, s, s < A && !d.cfg.idm_agent);
   RouteCtx ctx;
   if (r.status != ST_EMPTY) {
-    route_refresh(mv, *sp, r);
-    after_step_vehicle(d.cfg, mv, g, *sp, *sp, r, s < A, true, ctx);
+    route_refresh(mv, sp, r);
+    after_step_vehicle(d.cfg, mv, g, sp, *sp, r, s < A, true, ctx);
   }
   const unsigned long long am = __ballot(lm.sub == 0 && s < A && r.status == ST_ACTIVE);  // epw == 1 whenever A > 1
   if (s < A && r.status == ST_ACTIVE) r.agent_id = A == 1 ? 0.0f : (float)__popcll(am & ((1ull << lm.lead) - 1ull));
@@ -50,14 +50,14 @@ __global__ __launch_bounds__(256) void k_respawn_image(PgdDev d, RecPiece* __res
   if (k >= d.n_scen * n_extra) return;
   const int scen = k / n_extra, idx = d.V + k % n_extra;
   const Grp g{0, 1, (int)(threadIdx.x & (WAVE - 1))};
-  const pgd_spawn* sp = d.spawns + (size_t)scen * d.sstride + idx;
-  MapView mv = map_view(d, d.scen[scen].map);
+  const Tab<pgd_spawn> sp = d.spawns() + (size_t)scen * d.sstride + idx;
+  MapView mv = map_view(d, d.scen()[scen].map);
   Veh r;
-  reset_vehicle(*sp, d.spawn_hv[(size_t)scen * d.sstride + idx], r, idx, true);
+  reset_vehicle(*sp, d.spawn_hv()[(size_t)scen * d.sstride + idx], r, idx, true);
   RouteCtx ctx;
   if (r.status != ST_EMPTY) {
-    route_refresh(mv, *sp, r);
-    after_step_vehicle(d.cfg, mv, g, *sp, *sp, r, true, true, ctx);
+    route_refresh(mv, sp, r);
+    after_step_vehicle(d.cfg, mv, g, sp, *sp, r, true, true, ctx);
   }
   store_rec(rec_block(img, (size_t)scen, n_extra), n_extra, k % n_extra, r);
 }
@@ -76,11 +76,11 @@ __global__ __launch_bounds__(WAVE) void k_reset(PgdDev d, const int32_t* __restr
   if (lm.sub != 0) return;
   store_veh(d, e, s, r);
   if (s == 0) {
-    d.env_map[e] = d.scen_map[scen];
+    d.env_map[e] = d.scen_map()[scen];
     if (d.bev_fill) d.bev_fill[e] = 1;
     d.imask[e] = ((d.epw == 1 || d.pack_obs) && d.use_imask) ? (d.V >= 64 ? ~0ull : ((1ull << d.V) - 1ull)) : 0ull;  // every record equals the image now
     d.ei[(size_t)(e) * PGD_NEI + EI_NEXT_AGENT] = A == 1 ? 1 : __popcll(am);
-    d.ei[(size_t)(e) * PGD_NEI + EI_AUX] = d.scen[scen].aux;  // parking: free spaces of the new episode
+    d.ei[(size_t)(e) * PGD_NEI + EI_AUX] = d.scen()[scen].aux;  // parking: free spaces of the new episode
     d.ei[(size_t)(e) * PGD_NEI + EI_SCEN] = scen;
     d.ei[(size_t)(e) * PGD_NEI + EI_NEXT_GROUP] = 0;
     d.ei[(size_t)(e) * PGD_NEI + EI_EP_STEPS] = 0;
@@ -102,10 +102,10 @@ __global__ __launch_bounds__(256) void k_derive(PgdDev d) {
   r.road_cur = 0; r.road_next = 0; r.blk = 0; r.cur_first = 0; r.next_first = 0; r.cur_n = 0; r.next_n = 0;
   const int e = k / d.V;
   const int scen = d.ei[(size_t)e * PGD_NEI + EI_SCEN];
-  if (k == e * d.V && scen >= 0 && scen < d.n_scen) d.env_map[e] = d.scen_map[scen];  // the env's copy of its map header
+  if (k == e * d.V && scen >= 0 && scen < d.n_scen) d.env_map[e] = d.scen_map()[scen];  // the env's copy of its map header
   if (r.status != ST_EMPTY && scen >= 0 && scen < d.n_scen && (int)r.spawn < d.sstride) {
-    const MapView mv = map_view(d, d.scen[scen].map);
-    const pgd_spawn& sp = d.spawns[(size_t)scen * d.sstride + r.spawn];
+    const MapView mv = map_view(d, d.scen()[scen].map);
+    const Tab<pgd_spawn> sp = d.spawns() + ((size_t)scen * d.sstride + r.spawn);
     if ((int)r.lane < mv.m->n_lanes) {
       float lat;
       lane_local(mv.lanes[r.lane], r.x, r.y, r.lon, lat);
@@ -126,9 +126,9 @@ __global__ __launch_bounds__(WAVE) void k_refresh(PgdDev d) {
   load_veh(d, e, s, r);
   if (r.status != ST_ACTIVE && r.status != ST_PENDING && r.status != ST_DYING) return;
   int scen = d.ei[(size_t)(e) * PGD_NEI + EI_SCEN];
-  MapView mv = map_view(d, d.scen[scen].map);
+  MapView mv = map_view(d, d.scen()[scen].map);
   RouteCtx ctx;
-  after_step_vehicle(d.cfg, mv, g, d.spawns[(size_t)scen * d.sstride + r.spawn], d.spawns[(size_t)scen * d.sstride + r.spawn], r, s < A, true, ctx);
+  after_step_vehicle(d.cfg, mv, g, d.spawns() + ((size_t)scen * d.sstride + r.spawn), d.spawns()[(size_t)scen * d.sstride + r.spawn], r, s < A, true, ctx);
   if (lm.sub == 0) store_veh(d, e, s, r);
 }
 

@@ -101,8 +101,9 @@ DEV int get_current_lane(const MapView& mv, const Grp& g, int c, float px, float
 // and the next checkpoint pair, their first lanes and lane counts, block id of the current road.  Kept in the vehicle record
 // and rebuilt only here -- when a checkpoint is passed, at (re)spawn and by k_derive -- so that localisation, the IDM routing,
 // side distances, reward and observation read it from registers instead of walking spawn record -> road table every step.
-DEV void route_refresh(const MapView& mv, const pgd_spawn& sp, Veh& r) {
-  const int rc = sp.ckpt_road[r.ck0], rn = sp.ckpt_road[r.ck1];
+// (`sp`: the spawn record as a view of the arena: its route arrays are indexed in 32-bit arithmetic on the arena's base)
+DEV void route_refresh(const MapView& mv, const Tab<pgd_spawn>& sp, Veh& r) {
+  const int rc = sp.field<int16_t>(offsetof(pgd_spawn, ckpt_road), r.ck0), rn = sp.field<int16_t>(offsetof(pgd_spawn, ckpt_road), r.ck1);
   r.road_cur = (uint32_t)rc; r.road_next = (uint32_t)rn;  // -1 (no road) becomes 0xfff, which no map uses (<= 4095 roads)
   r.blk = 0; r.cur_first = 0; r.cur_n = 0; r.next_first = 0; r.next_n = 0;
   if (rc >= 0) {
@@ -122,7 +123,7 @@ DEV void route_refresh(const MapView& mv, const pgd_spawn& sp, Veh& r) {
 // lane -> road table chain in front of its reads: one memory round trip on every step of the first five metres of a lane where
 // rounds 1 - 5 made three dependent ones (lane record, road record, route; PGD_CKPT_CHAIN keeps that form for A/B).
 #define PGD_CKPT_END (-32768)
-DEV void update_checkpoints(const MapView& mv, const Grp& g, const pgd_spawn& sp, Veh& r, float lon, const int start_node) {
+DEV void update_checkpoints(const MapView& mv, const Grp& g, const Tab<pgd_spawn>& sp, Veh& r, float lon, const int start_node) {
   if (r.ck0 == r.ck1) return;
   if (!(lon < 5.0f)) return;
   // The first match decides, and a match on the last node alone changes nothing.  The sub-lanes of the vehicle split the tail,
@@ -130,12 +131,12 @@ DEV void update_checkpoints(const MapView& mv, const Grp& g, const pgd_spawn& sp
   unsigned hit = 0xffffffffu;
   const int step = g.SUB;
 #ifdef PGD_CKPT_CHAIN
-  const int n = sp.n_ckpt;
+  const int n = sp->n_ckpt;
   const int start_node_ = mv.roads()[mv.lanes[r.lane].road].from;
   for (int k = r.ck1 + g.sub; k < n - 1; k += 4 * step) {
     int v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = sp.ckpt[min(k + j * step, n - 2)];
+    for (int j = 0; j < 4; ++j) v[j] = sp.field<int16_t>(offsetof(pgd_spawn, ckpt), min(k + j * step, n - 2));
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (k + j * step < n - 1 && v[j] == start_node_) hit = min(hit, (unsigned)(k + j * step));
@@ -144,7 +145,7 @@ DEV void update_checkpoints(const MapView& mv, const Grp& g, const pgd_spawn& sp
   for (int k = r.ck1 + g.sub; k < PGD_MAX_CKPT; k += 4 * step) {
     int v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = sp.ckpt[min(k + j * step, PGD_MAX_CKPT - 1)];
+    for (int j = 0; j < 4; ++j) v[j] = sp.field<int16_t>(offsetof(pgd_spawn, ckpt), min(k + j * step, PGD_MAX_CKPT - 1));
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (k + j * step < PGD_MAX_CKPT && v[j] == start_node) hit = min(hit, (unsigned)(k + j * step));
@@ -154,7 +155,7 @@ DEV void update_checkpoints(const MapView& mv, const Grp& g, const pgd_spawn& sp
   hit = group_min(hit, g);
   if (hit == 0xffffffffu) return;
   const int idx = (int)hit;
-  const int n_nodes = sp.n_ckpt;  // (a checkpoint was passed: once per road)
+  const int n_nodes = sp->n_ckpt;  // (a checkpoint was passed: once per road)
   r.ck0 = idx;
   r.ck1 = (idx + 1 == n_nodes - 1) ? idx : idx + 1;
   route_refresh(mv, sp, r);
@@ -163,7 +164,7 @@ DEV void update_checkpoints(const MapView& mv, const Grp& g, const pgd_spawn& sp
 // Navigation.update_localization (navigation.py:155-183)
 // `PL` = the record of r.lane, read by the caller (ahead of time, together with its other lane reads)
 template <class MV>
-DEV void update_localization(const MV& mv, const Grp& g, const pgd_spawn& sp, Veh& r, float& lon_out, float& lat_out,
+DEV void update_localization(const MV& mv, const Grp& g, const Tab<pgd_spawn>& sp, Veh& r, float& lon_out, float& lat_out,
                              const pgd_lane& PL) {
   const float s = r.hy, c = r.hx;
   const int road_cur = (int)r.road_cur;  // the record's route context: no spawn-record read
@@ -298,7 +299,7 @@ struct RouteCtx {   // per-step by-products of an agent's after_step, consumed b
 // `sp`: the slot's spawn record in memory (route arrays); `sv`: where its scalar fields are read from (the same record, or the
 // caller's register copy of its head)
 template <bool AHEAD = false, class MV>
-DEV void after_step_vehicle(const pgd_config& cfg, const MV& mv, const Grp& g, const pgd_spawn& sp, const pgd_spawn& sv, Veh& r,
+DEV void after_step_vehicle(const pgd_config& cfg, const MV& mv, const Grp& g, const Tab<pgd_spawn>& sp, const pgd_spawn& sv, Veh& r,
                             bool is_agent, bool with_state_check, RouteCtx& ctx) {
   float lon_v, lat_v;
   // the two lane records every agent's after_step reads -- its lane of the previous step (almost always still its lane) and the

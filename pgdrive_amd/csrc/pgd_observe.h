@@ -201,8 +201,8 @@ DEV void obs_preload(const PgdDev& d, const MV& mv, const AgentView& ag, int tid
   if (tid >= 8 && tid < 18) p.nv = mv.lnav()[lid];
   p.bd0 = p.bd1 = p.bd2 = p.bd3 = make_float2(0.0f, 0.0f);
   if (NL > 0) {
-    p.bd0 = d.beam[min(tid, NL - 1)]; p.bd1 = d.beam[min(nt + tid, NL - 1)];
-    p.bd2 = d.beam[min(2 * nt + tid, NL - 1)]; p.bd3 = d.beam[min(3 * nt + tid, NL - 1)];
+    p.bd0 = d.beam()[min(tid, NL - 1)]; p.bd1 = d.beam()[min(nt + tid, NL - 1)];
+    p.bd2 = d.beam()[min(2 * nt + tid, NL - 1)]; p.bd3 = d.beam()[min(3 * nt + tid, NL - 1)];
   }
 }
 
@@ -333,7 +333,7 @@ DEV void state_block_one(const PgdDev& d, const MV& mv, const pgd_spawn& sp, con
 
 // the view of slot `o` of the env as an observed vehicle (the state vector a neighbour contributes to
 // LidarStateObservationMARound); its speed comes from the observer's snapshot
-DEV AgentView view_of_slot(const PgdDev& d, const MapView& mv, const RecPiece* recs, const pgd_spawn* spb, int o, float spd_kmh,
+DEV AgentView view_of_slot(const PgdDev& d, const MapView& mv, const RecPiece* recs, const Tab<pgd_spawn>& spb, int o, float spd_kmh,
                            int env, uint32_t tick) {
   Veh rc;
   load_rec(recs, d.V, o, rc);
@@ -377,7 +377,7 @@ DEV void row_sync() {
 // WAVE_ROW: see row_sync
 template <bool OBJ, bool STD = false, bool OTH = false, bool STATE = true, bool WAVE_ROW = false, class MV>
 DEV void observe_agent(const PgdDev& d, const MV& mv, const pgd_spawn& sp, const AgentView& ag, ObsLds& L,
-                       float* __restrict__ row, int tid, int nt, const RecPiece* recs = nullptr, const pgd_spawn* spb = nullptr,
+                       float* __restrict__ row, int tid, int nt, const RecPiece* recs = nullptr, const Tab<pgd_spawn> spb = Tab<pgd_spawn>{nullptr, 0u},
                        const ObsPre* pre = nullptr, unsigned* minb = nullptr) {
   const float px = ag.x, py = ag.y, hx = ag.hx, hy = ag.hy;
   const float R = d.cfg.lidar_dist;
@@ -394,8 +394,8 @@ DEV void observe_agent(const PgdDev& d, const MV& mv, const pgd_spawn& sp, const
   float2 bd0 = make_float2(0.0f, 0.0f), bd1 = bd0, bd2 = bd0, bd3 = bd0;
   if (pre) { bd0 = pre->bd0; bd1 = pre->bd1; bd2 = pre->bd2; bd3 = pre->bd3; }
   else if (NL > 0) {
-    bd0 = d.beam[min(tid, NL - 1)]; bd1 = d.beam[min(nt + tid, NL - 1)];
-    bd2 = d.beam[min(2 * nt + tid, NL - 1)]; bd3 = d.beam[min(3 * nt + tid, NL - 1)];
+    bd0 = d.beam()[min(tid, NL - 1)]; bd1 = d.beam()[min(nt + tid, NL - 1)];
+    bd2 = d.beam()[min(2 * nt + tid, NL - 1)]; bd3 = d.beam()[min(3 * nt + tid, NL - 1)];
   }
   if (STATE) state_block<STD>(d, mv, sp, ag, row, tid, nt, pre);
   if (toll && tid == 0) {  // TollGateObservation.observe (marl_tollgate.py:84-96)
@@ -561,7 +561,7 @@ DEV void observe_agent(const PgdDev& d, const MV& mv, const pgd_spawn& sp, const
   if (nt < NL) cast_round(nt, bd1);
   if (2 * nt < NL) cast_round(2 * nt, bd2);
   if (3 * nt < NL) cast_round(3 * nt, bd3);
-  for (int i0 = 4 * nt; i0 < NL; i0 += nt) cast_round(i0, d.beam[min(i0 + tid, NL - 1)]);
+  for (int i0 = 4 * nt; i0 < NL; i0 += nt) cast_round(i0, d.beam()[min(i0 + tid, NL - 1)]);
   PHASE_MARK(24);  // obs: lidar
 }
 
@@ -598,7 +598,7 @@ DEV void observe_row(const PgdDev& d, float* __restrict__ obs, const uint32_t* _
     return;
   }
   // batch 2: what the scenario and the spawn indices lead to -- map header, the observer's and the body's static parameters
-  const pgd_spawn* spb = d.spawns + (size_t)scen * d.sstride;
+  const Tab<pgd_spawn> spb = d.spawns() + (size_t)scen * d.sstride;
   const pgd_spawn& msp = spb[me.spawn];
   const pgd_spawn& so = spb[body.spawn];
   const float so_len = so.length, so_wid = so.width;
@@ -738,7 +738,7 @@ DEV void observe_env_body(const PgdDev& d, int e, float* __restrict__ obs, const
     tick = (uint32_t)d.ei[(size_t)(e) * PGD_NEI + EI_STEPS_TOTAL];
     if (STATE) mv = map_view_of(d, d.env_map + e);
   }
-  const pgd_spawn* spb = d.spawns + (size_t)scen * d.sstride;
+  const Tab<pgd_spawn> spb = d.spawns() + (size_t)scen * d.sstride;
   const pgd_spawn& msp = FUSED ? *in_wave->sp : spb[STATE ? me.spawn : 0];
   bool want = false;  // (STATE = false: the rows' state blocks are there already; `aWant` comes from the bodies' own lanes below)
   if (STATE) want = row_due(me.status, flags != nullptr, f_me) && s_on;
@@ -939,7 +939,7 @@ DEV void observe_env_body(const PgdDev& d, int e, float* __restrict__ obs, const
         int i = i0w + (t - start);
         i -= i >= NL ? NL : 0;
         const float ax = bX[ga], ay = bY[ga], ahx = bUX[ga], ahy = bUY[ga];
-        const float2 bd = d.beam[i];  // (cos, sin)(i * 2 pi / NL); rotated by the heading
+        const float2 bd = d.beam()[i];  // (cos, sin)(i * 2 pi / NL); rotated by the heading
         const float dx = R_lidar * (bd.x * ahx - bd.y * ahy), dy = R_lidar * (bd.y * ahx + bd.x * ahy);
         const float f = shape_ray<OBJ>(Obb{bX[qo], bY[qo], bUX[qo], bUY[qo], bHL[qo], bHW[qo]}, ax, ay, dx, dy);
         atomicMin(&s_minb[qa * NL + i], __float_as_uint(f));

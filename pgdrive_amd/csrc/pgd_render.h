@@ -132,7 +132,7 @@ __global__ __launch_bounds__(WAVE) void k_render_prep(PgdDev d, RenderDev r, con
   REnv st = r.env[e];
   const int episodes = d.ei[(size_t)e * PGD_NEI + EI_EPISODES];
   const int scen = d.ei[(size_t)e * PGD_NEI + EI_SCEN];
-  const int map = d.scen[scen].map;
+  const int map = d.scen()[scen].map;
   if (episodes != st.last_ep) { st.total = 0; st.dead_total = 0; }  // a new episode since the last render: no trail, no deads
   const double sc = r.geom[map * 3], ox = r.geom[map * 3 + 1], oy = r.geom[map * 3 + 2];
   const int S = r.S, W = r.W, H = r.H;
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(WAVE) void k_render_prep(PgdDev d, RenderDev r, con
   if (lane < V) {
     Veh rc;
     load_rec_head(rec_block(d.rec, (size_t)e, V), V, lane, rc);
-    const pgd_spawn& sp = d.spawns[(size_t)scen * d.sstride + rc.spawn];
+    const pgd_spawn& sp = d.spawns()[(size_t)scen * d.sstride + rc.spawn];
     const bool agent = lane < A;
     const bool present = agent ? (rc.status == ST_ACTIVE || rc.status == ST_DYING)
                                : (r.draw_traffic && (rc.status == ST_PENDING || rc.status == ST_ACTIVE) && sp.kind != PGD_OBJ_BUILDING);

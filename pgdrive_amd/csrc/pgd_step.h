@@ -109,10 +109,10 @@ template <bool SKIP_POSE> DEV void spawn_head_load(const pgd_spawn* sp, pgd_spaw
     o[0] = a; o[1] = b; o[2] = c; o[3] = e;
   }
 }
-template <bool REG> DEV const pgd_lane& dest_lane_ref(const pgd_lane& regs, const pgd_lane* lanes, int id) {
+template <bool REG> DEV const pgd_lane& dest_lane_ref(const pgd_lane& regs, const Tab<pgd_lane>& lanes, int id) {
   if constexpr (REG) return regs; else return lanes[id];
 }
-template <bool REG> DEV const pgd_spawn& spawn_ref(const pgd_spawn& regs, const pgd_spawn* mem) {
+template <bool REG> DEV const pgd_spawn& spawn_ref(const pgd_spawn& regs, const Tab<pgd_spawn>& mem) {
   if constexpr (REG) return regs; else return *mem;
 }
 #ifndef PGD_WAVES_PER_SIMD
@@ -261,10 +261,11 @@ static bool fix_config_matches(const PgdDev& d, bool one_env, int kind = FIXK_DE
 // written, so its fields are fetched from the argument segment where they are used -- in the specialised kernels `d` is a local
 // copy whose every used field is an entry load and stays live in a scalar register (or a spill lane) to the end.
 struct PgdCold {
-  const pgd_map* scen_map;
   uint8_t* bev_fill;
-  const float2* spawn_hv;
-  const RecPiece* respawn_img;
+  uint32_t o_scen_map, o_spawn_hv, o_respawn_img;  // arena offsets (PgdDev::tab): the tables only the rare paths read
+  DEV Tab<pgd_map> scen_map(const PgdDev& d) const { return {d.tab, o_scen_map}; }
+  DEV Tab<float2> spawn_hv(const PgdDev& d) const { return {d.tab, o_spawn_hv}; }
+  DEV Tab<RecPiece> respawn_img(const PgdDev& d) const { return {d.tab, o_respawn_img}; }
   int n_scen;
   uint32_t seed;
   int env_base;
@@ -278,11 +279,23 @@ struct PgdCold {
 };
 // LK: the scripted lane-keeping policy inside the step (pgd_step_lane_keep): an instantiation of its own -- as a run-time branch at
 // the head of every kernel it cost the metric's row 0.09 us (17.03 -> 17.12)
+// The engine view of a step kernel.  The specialised kernels work on their copy of the argument (write_fixed_config has written its
+// constants over it: every field they use is an entry load).  The GENERAL kernels read the argument IN PLACE, in the kernel-argument
+// segment (PgdDev is the kernel's first argument), a field where it is used: they have no scalar registers for entry loads.  Left to the
+// compiler that was an accident of how the copy got optimised away, and the table views (Tab) ended it: all fields loaded at the kernel's
+// head and parked in spill lanes, 47 -> 98 spilled SGPRs in the 72-beam / 12-slot kernel, its row 3 % slower (profiles/addr32_notes.md).
+template <bool IN_PLACE> DEV const PgdDev& step_view(const PgdDev& copy) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (IN_PLACE) return *(const PgdDev*)__builtin_amdgcn_kernarg_segment_ptr();
+#endif
+  return copy;
+}
 template <bool ONE_ENV, bool MARL, bool OBJ, bool STD = false, int FIX = 0, bool LK = false>
-__global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, const float* __restrict__ act, float* __restrict__ reward,
+__global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d_arg, const float* __restrict__ act, float* __restrict__ reward,
                                                 uint8_t* __restrict__ done, uint32_t* __restrict__ flags,
                                                 float* __restrict__ obs, const PgdCold cold) {
-  if (FIX) write_fixed_config<ONE_ENV, MARL, STD, FIX>(d);
+  if (FIX) write_fixed_config<ONE_ENV, MARL, STD, FIX>(d_arg);
+  const PgdDev& d = step_view<FIX == 0>(d_arg);
 
   __shared__ StepUnion U;
   Snap& S = U.step.S;
@@ -310,7 +323,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
   RouteCtx ctx{0.0f, 1.0f, 0, -1};  // of this lane's vehicle if it is an agent: refreshed by every after_step_vehicle
   using MV = typename std::conditional<FIX != 0 && !OBJ, MapViewPre, MapView>::type;
   MV mv;
-  const pgd_spawn* sp = nullptr;
+  Tab<pgd_spawn> sp{nullptr, 0u};
   // The scalar part of the slot's spawn record (dimensions, drive parameters, trigger group, destination: its first 64 bytes) is
   // read ONCE, four 16-byte loads in one round trip, when the record's address is known; the phases used to fetch its fields one
   // by one where they needed them, each time for a whole memory latency (profiles/r03_notes.md).  Kernels with one env per wave
@@ -324,7 +337,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
   pgd_spawn sl;
   pgd_lane FL;  // REGSP && FIX (registers to spare): the agent's destination lane record, read ahead
 #define SPV spawn_ref<REGSP>(sl, sp)
-  const pgd_scenario* sc = nullptr;
+  Tab<pgd_scenario> sc{nullptr, 0u};
   int ng = 0, ep_steps = 0;
   uint32_t steps_total = 0;
   // EI_NEAR, left by the observation of the previous step: 0 = no body of the env can reach an agent during this step, so no
@@ -375,7 +388,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
   if constexpr (STAGED) {
     rec_stage_issue<PGD_FIX_V>(rec_block(d.rec, (size_t)e, PGD_FIX_V), lane, stg);
     __builtin_amdgcn_sched_barrier(0);  // the records' reads stay the wave's first: left to itself the scheduler put the action and the spawn heads in front
-  } else if (valid && !own_first) load_rec(((ONE_ENV || packed) && ((im >> s) & 1ull)) ? rec_block(d.reset_img, (size_t)scen, V) : rec_block(d.rec, (size_t)e, V), V, s, r);
+  } else if (valid && !own_first) load_rec(((ONE_ENV || packed) && ((im >> s) & 1ull)) ? rec_block(d.reset_img(), (size_t)scen, V) : rec_block(d.rec, (size_t)e, V), V, s, r);
   // the agent's action: its address follows from the block index as well -- read here, used by the policy phase (read there it cost
   // every wave a memory latency of its own right after the snapshot: 1.5 k cycles of the metric's row).  BEHIND the record's reads:
   // issued ahead of the mask / scenario / record chain it delays that chain (17.76 -> 17.99 us), and so does a speculative read
@@ -393,7 +406,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
   // state set by hand may: checked below) -- the head's address follows from the scenario id like the record's, and its reads travel
   // with the record's instead of waiting for them (17.48 -> 17.40 us on the metric's row, now that the records' reads are short)
   constexpr bool EARLY_HEAD = !MARL && REGSP && FIX != 0 && !OBJ;  // (the general kernels have no registers for it: 19.5 -> 19.9 us there; nor has the object kernel)
-  if (EARLY_HEAD && valid) { sp = d.spawns + (size_t)scen * d.sstride + s; spawn_head_load<false>(sp, sl); }
+  if (EARLY_HEAD && valid) { sp = d.spawns() + (size_t)scen * d.sstride + s; spawn_head_load<false>(sp.at(0u), sl); }
   if constexpr (STAGED) rec_stage_take<PGD_FIX_V>(reinterpret_cast<uint4*>(&SUBP.p[0][0]), lane, stg, valid, s, r);
   const int key0 = valid ? (r.status ^ (r.vflags << 3)) : 0;  // what a vehicle that does not drive can change: status, flags
   // the env's counters.  The multi-agent kernels are out of scalar registers: read here, the compiler fetched the words one after the
@@ -411,7 +424,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
     }
   };
   if (one_env || valid) {
-    sc = d.scen + scen;
+    sc = d.scen() + scen;
     mv = map_view_as<MV>(d, d.env_map + e);  // per-env header copy: address known at kernel start
     if (!LATE_WORDS) env_words();
   }
@@ -419,8 +432,8 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
   XMARK(13);
   if (valid) {
     if (!EARLY_HEAD || (int)r.spawn != s) {
-      sp = d.spawns + (size_t)scen * d.sstride + r.spawn;
-      if (REGSP) spawn_head_load<MARL>(sp, sl);
+      sp = d.spawns() + (size_t)scen * d.sstride + r.spawn;
+      if (REGSP) spawn_head_load<MARL>(sp.at(0u), sl);
     }
     // (0) AgentManager.before_step (agent_manager.py:191-199): finished agents count down, then leave the world
     if (marl && r.status == ST_DYING && --r.timer == 0) r.status = ST_EMPTY;
@@ -666,7 +679,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
     // records are no longer live -- inside after_step it pushed the multi-agent kernel 66 registers over the 128 it may use
     // the destination lane of an agent (arrive test of reward_done) is known from its spawn record: read before the localisation
     if (REGSP && FIX && !OBJ && s < A) FL = mv.lanes[SPV.dest_lane];
-    after_step_vehicle<ONE_ENV>(d.cfg, mv, g, *sp, SPV, r, s < A, !one_env, ctx);
+    after_step_vehicle<ONE_ENV>(d.cfg, mv, g, sp, SPV, r, s < A, !one_env, ctx);
     if (s >= A && (r.vflags & PGD_F_OFF_LANE)) r.status = ST_REMOVED;
   }
   // the trigger test of the NEXT step (TrafficManager.before_step looks at the state this step leaves): the road of the agent's lane
@@ -801,14 +814,14 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
       // _respawn_vehicles takes ONE of the offered places per call (multi_agent_pgdrive.py:180-213): the second call of the frame finds
       // every free place already offered and stops -- at most one newcomer per step, on a random one of the free places
       // (rounds 2 - 4 filled every free place in the same step)
-      const pgd_spawn* rbase = d.spawns + (size_t)scen * d.sstride + V;
+      const Tab<pgd_spawn> rbase = d.spawns() + (size_t)scen * d.sstride + V;
       unsigned long long freem = 0ull;
       // the places' poses: lane p reads place p, one round trip for all of them (read inside the loop, place after place, the two
       // dependent reads per place were 5 k cycles of a step with 30 agents alive: profiles/r05_notes.md)
       float plx = 0.0f, ply = 0.0f, plc = 1.0f, pls = 0.0f;
       if (lane < gcf.respawn_places) {
         const pgd_spawn& place = rbase[lane * gcf.respawn_dests];
-        const float2 phv = cold.spawn_hv[(size_t)scen * d.sstride + V + lane * gcf.respawn_dests];
+        const float2 phv = cold.spawn_hv(d)[(size_t)scen * d.sstride + V + lane * gcf.respawn_dests];
         plx = place.x; ply = place.y; plc = phv.x; pls = phv.y;
       }
       const Obb mine = snap_obb(S, lane < V ? lane : 0);
@@ -846,8 +859,8 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
           fresh = true;
           my_fl |= PGD_F_NEW;
           if (leader) {
-            const pgd_spawn& nsp = d.spawns[(size_t)scen * d.sstride + fresh_idx];
-            const float2 nhv = cold.spawn_hv[(size_t)scen * d.sstride + fresh_idx];
+            const pgd_spawn& nsp = d.spawns()[(size_t)scen * d.sstride + fresh_idx];
+            const float2 nhv = cold.spawn_hv(d)[(size_t)scen * d.sstride + fresh_idx];
             S.x[slot] = nsp.x; S.y[slot] = nsp.y; S.ux[slot] = nhv.x; S.uy[slot] = nhv.y;
             S.hl[slot] = 0.5f * nsp.length; S.hw[slot] = 0.5f * nsp.width;
             S.present[slot] = 1;
@@ -858,9 +871,9 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
       }
     }
     if (fresh) {  // the new agent's record, first localisation included, from the respawn image (k_respawn_image)
-      sp = d.spawns + (size_t)scen * d.sstride + fresh_idx;
-      if (REGSP) spawn_head_load<MARL>(sp, sl);
-      load_rec(rec_block(cold.respawn_img, (size_t)scen, d.sstride - V), d.sstride - V, fresh_idx - V, r);
+      sp = d.spawns() + (size_t)scen * d.sstride + fresh_idx;
+      if (REGSP) spawn_head_load<MARL>(sp.at(0u), sl);
+      load_rec(rec_block(cold.respawn_img(d), (size_t)scen, d.sstride - V), d.sstride - V, fresh_idx - V, r);
       r.agent_id = (float)fresh_id;
     }
     PHASE_MARK(27);  // marl: respawn
@@ -897,22 +910,22 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
     episodes = d.ei[(size_t)(e) * PGD_NEI + EI_EPISODES] + 1;
     if (d.cfg.resample_scenario)
       scen = (int)(pgd_rng(cold.seed, (uint32_t)(cold.env_base + e), 0x5ce9a210u, (uint32_t)episodes) % (uint32_t)cold.n_scen);
-    sc = d.scen + scen;
-    mv = map_view_as<MV>(d, cold.scen_map + scen);  // the header of the new episode's map (the per-env copy is rewritten below)
+    sc = d.scen() + scen;
+    mv = map_view_as<MV>(d, cold.scen_map(d).at((uint32_t)scen));  // the header of the new episode's map (the per-env copy is rewritten below)
     ng = 0;
     ep_steps = 0;
   }
   if (valid && resetting) {
-    sp = d.spawns + (size_t)scen * d.sstride + s;
-    if (REGSP) spawn_head_load<MARL>(sp, sl);
+    sp = d.spawns() + (size_t)scen * d.sstride + s;
+    if (REGSP) spawn_head_load<MARL>(sp.at(0u), sl);
     // the slot right after a reset is a function of the scenario alone (spawn pose, first localisation, side distances,
     // agent id): read from the image k_reset_image built at upload instead of localising every vehicle again
-    load_rec(rec_block(d.reset_img, (size_t)scen, V), V, s, r);
+    load_rec(rec_block(d.reset_img(), (size_t)scen, V), V, s, r);
     const unsigned long long am = __ballot(leader && s < A && r.status == ST_ACTIVE);
     if (marl && s < A && r.status == ST_ACTIVE) my_fl |= PGD_F_NEW;
     if (s == 0 && d.cfg.resample_scenario)  // the env's header copy follows the scenario (any number of sub-lanes)
       for (int q = g.sub; q < (int)(sizeof(pgd_map) / 16); q += g.SUB)
-        reinterpret_cast<uint4*>(d.env_map + e)[q] = reinterpret_cast<const uint4*>(cold.scen_map + scen)[q];
+        reinterpret_cast<uint4*>(d.env_map + e)[q] = reinterpret_cast<const uint4*>(cold.scen_map(d).at((uint32_t)scen))[q];
     if (s == 0 && leader) {
       d.ei[(size_t)(e) * PGD_NEI + EI_SCEN] = scen;
       d.ei[(size_t)(e) * PGD_NEI + EI_EPISODES] = episodes;
@@ -1000,8 +1013,8 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
       step_sync();
       PHASE_MARK(21);  // obs: compaction
       XMARK(21);
-      observe_agent<OBJ, STD, false, true, true>(d, mvo, d.spawns[(size_t)scen_now * d.sstride + a], ag, OL,
-                                                 obs + (size_t)e * d.ostride + (size_t)a * d.D, lane, WAVE, nullptr, nullptr, &pre, lidar_minb(S));
+      observe_agent<OBJ, STD, false, true, true>(d, mvo, d.spawns()[(size_t)scen_now * d.sstride + a], ag, OL,
+                                                 obs + (size_t)e * d.ostride + (size_t)a * d.D, lane, WAVE, nullptr, Tab<pgd_spawn>{nullptr, 0u}, &pre, lidar_minb(S));
       step_sync();
     }
     // hint for the next step's contact tests (EI_NEAR); without a lidar the compaction looked at nothing: always test
@@ -1063,7 +1076,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
     if (valid) {  // the state blocks of all envs of the wave at once: the V lanes of an env share the 18 floats of its row
       AgentView ag = s_ag[el];
       ag.cur_n &= 0xff;
-      state_block<STD>(d, mv, d.spawns[(size_t)scen * d.sstride], ag, obs + (size_t)e * d.ostride, s, V);
+      state_block<STD>(d, mv, d.spawns()[(size_t)scen * d.sstride], ag, obs + (size_t)e * d.ostride, s, V);
     }
     for (int q = 0; q < d.epw; ++q) {
       const int eq = unit * d.epw + q;  // wave-uniform
@@ -1071,7 +1084,7 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
       AgentView ag = s_ag[q];
       const int scen_q = ag.cur_n >> 8;
       ag.cur_n &= 0xff;
-      const MV mvq = map_view_as<MV>(d, cold.scen_map + scen_q);
+      const MV mvq = map_view_as<MV>(d, cold.scen_map(d).at((uint32_t)scen_q));
       const int bq = q * V;
       const bool have = lane < V && d.cfg.num_lasers > 0;
       const int sl = bq + (lane < V ? lane : 0);
@@ -1085,8 +1098,8 @@ __global__ __launch_bounds__(WAVE, PGD_WAVES_PER_SIMD) void k_step(PgdDev d, con
         if (lane == 0) d.ei[(size_t)eq * PGD_NEI + EI_NEAR] = near_q ? 1 : 0;
       }
       step_sync();
-      observe_agent<OBJ, STD, false, false, true>(d, mvq, d.spawns[(size_t)scen_q * d.sstride], ag, OL, obs + (size_t)eq * d.ostride, lane, WAVE,
-                                                  nullptr, nullptr, nullptr, lidar_minb(S));
+      observe_agent<OBJ, STD, false, false, true>(d, mvq, d.spawns()[(size_t)scen_q * d.sstride], ag, OL, obs + (size_t)eq * d.ostride, lane, WAVE,
+                                                  nullptr, Tab<pgd_spawn>{nullptr, 0u}, nullptr, lidar_minb(S));
       step_sync();
     }
   }

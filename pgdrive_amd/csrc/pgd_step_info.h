@@ -72,16 +72,16 @@ __global__ __launch_bounds__(WAVE) void k_step_info(PgdDev d, const pgd_step_inf
   int scen = ew[EI_SCEN];
   if (d.cfg.resample_scenario)
     scen = (int)(pgd_rng(d.cfg.seed, (uint32_t)(d.cfg.env_base + e), 0x5ce9a210u, (uint32_t)episodes) % (uint32_t)d.n_scen);
-  const RecPiece* img = rec_block(d.reset_img, (size_t)scen, V);
+  const RecPiece* img = rec_block(d.reset_img(), (size_t)scen, V);
   for (int k = tid; k < 8 * V; k += WAVE) recs[k].q = img[k].q;
   if (d.cfg.resample_scenario)
     for (int q = tid; q < (int)(sizeof(pgd_map) / 16); q += WAVE)
-      reinterpret_cast<uint4*>(d.env_map + e)[q] = reinterpret_cast<const uint4*>(d.scen_map + scen)[q];
+      reinterpret_cast<uint4*>(d.env_map + e)[q] = reinterpret_cast<const uint4*>(d.scen_map().at((uint32_t)scen))[q];
   if (tid == 0) {
     ew[EI_SCEN] = scen;
     ew[EI_EPISODES] = episodes;
     ew[EI_NEXT_AGENT] = 1;
-    ew[EI_AUX] = d.scen[scen].aux;
+    ew[EI_AUX] = d.scen()[scen].aux;
     ew[EI_NEXT_GROUP] = 0;
     ew[EI_EP_STEPS] = 0;
     ew[EI_NEAR] = 1;  // test / unknown

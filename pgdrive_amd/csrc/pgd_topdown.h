@@ -102,10 +102,10 @@ __global__ __launch_bounds__(256) void k_topdown_raster(PgdDev d, int scen, floa
   __shared__ uint32_t s_route[128];
   for (int k = threadIdx.x; k < 128; k += 256) s_route[k] = 0u;
   __syncthreads();
-  const pgd_spawn& sp = d.spawns[(size_t)scen * d.sstride];
+  const pgd_spawn& sp = d.spawns()[(size_t)scen * d.sstride];
   if ((int)threadIdx.x < sp.n_ckpt - 1) { const int r = sp.ckpt_road[threadIdx.x]; if (r >= 0) atomicOr(&s_route[r >> 5], 1u << (r & 31)); }
   __syncthreads();
-  const MapView mv = map_view_of(d, d.scen_map + scen);
+  const MapView mv = map_view_of(d, d.scen_map().at((uint32_t)scen));
   const int tbw = (W + 7) >> 3, tbh = (H + 7) >> 3;
   const long long n = (long long)tbw * tbh * 64;  // tiled layout (td_tiled); texels past the edge of the last tiles are 0
   for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long long)gridDim.x * 256) {
@@ -187,8 +187,8 @@ __global__ __launch_bounds__(256, (U8 ? TD_OCC_U8 : TD_OCC)) void k_topdown(PgdD
   float2* s_vh = reinterpret_cast<float2*>(s_vc + 4 * V);   // [f * V + k]: half extents
   const RecPiece* recs = rec_block(d.rec, (size_t)e, V);
   const int scen = d.ei[(size_t)e * PGD_NEI + EI_SCEN];
-  const pgd_spawn* spb = d.spawns + (size_t)scen * d.sstride;
-  const MapView mv = map_view_of(d, d.scen_map + scen);
+  const Tab<pgd_spawn> spb = d.spawns() + (size_t)scen * d.sstride;
+  const MapView mv = map_view_of(d, d.scen_map().at((uint32_t)scen));
   const bool refill = fill[e] != 0;
   // ---- history: shift by one and insert the current state (or fill everything with it after a reset) ----
   float4* hp = t.pose + (size_t)e * t.n_frames * V;

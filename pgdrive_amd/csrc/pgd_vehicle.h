@@ -9,10 +9,16 @@
 // records in memory: blocks of n records as eight planes of n pieces (RecPiece, pgd_device.h)
 DEV const RecPiece* rec_block(const RecPiece* base, size_t block, int n) { return base + block * (size_t)(8 * n); }
 DEV RecPiece* rec_block(RecPiece* base, size_t block, int n) { return base + block * (size_t)(8 * n); }
+// ... of an arena table (the reset and respawn images): the block's offset is 32-bit arithmetic on the arena's base like every table's
+DEV const RecPiece* rec_block(const Tab<RecPiece>& t, size_t block, int n) { return t.at((uint32_t)block * (uint32_t)(8 * n)); }
+// Piece i of a block: the block's start is a 64-bit address (the per-env arrays scale with the env count), the part inside the block
+// -- (k * n + s) * 16 bytes, a few KB at the most -- an unsigned 32-bit offset on it: one VGPR of address on a scalar base
+DEV const RecPiece& rec_piece(const RecPiece* blk, int i) { return *reinterpret_cast<const RecPiece*>(reinterpret_cast<const char*>(blk) + (uint32_t)i * (uint32_t)sizeof(RecPiece)); }
+DEV RecPiece& rec_piece(RecPiece* blk, int i) { return *reinterpret_cast<RecPiece*>(reinterpret_cast<char*>(blk) + (uint32_t)i * (uint32_t)sizeof(RecPiece)); }
 DEV void load_rec(const RecPiece* blk, int n, int s, Veh& r) {
   uint4* dst = reinterpret_cast<uint4*>(&r);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) dst[k] = blk[k * n + s].q;
+  for (int k = 0; k < 8; ++k) dst[k] = rec_piece(blk, k * n + s).q;
 }
 // Block-wise, for a wave that owns the whole block of N records (N a literal): the block is contiguous, so ceil(8 N / 64) reads with all
 // 64 lanes on consecutive pieces fetch it -- 3 vector-memory instructions instead of load_rec's 8 for N = 17 -- into an LDS image of
@@ -26,7 +32,7 @@ DEV void load_rec(const RecPiece* blk, int n, int s, Veh& r) {
 template <int N, int J = 0> DEV void rec_stage_issue(const RecPiece* blk, int lane, uint4 (&t)[REC_STAGE_ROUNDS(N)]) {
   static_assert(WAVE == 64, "one piece per lane and round");
   if constexpr (J < REC_STAGE_ROUNDS(N)) {
-    const uint4 v = blk[(J + 1) * WAVE <= 8 * N ? J * WAVE + lane : min(J * WAVE + lane, 8 * N - 1)].q;
+    const uint4 v = rec_piece(blk, (J + 1) * WAVE <= 8 * N ? J * WAVE + lane : min(J * WAVE + lane, 8 * N - 1)).q;
     t[J] = v;
     rec_stage_issue<N, J + 1>(blk, lane, t);
   }
@@ -53,15 +59,15 @@ template <int N> DEV void rec_stage_take(uint4* img, int lane, const uint4 (&t)[
 DEV void load_rec_head(const RecPiece* blk, int n, int s, Veh& r) {
   uint4* dst = reinterpret_cast<uint4*>(&r);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) dst[k] = blk[k * n + s].q;
+  for (int k = 0; k < 4; ++k) dst[k] = rec_piece(blk, k * n + s).q;
 }
 DEV void store_rec(RecPiece* blk, int n, int s, const Veh& r) {
   const uint4* src = reinterpret_cast<const uint4*>(&r);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) blk[k * n + s].q = src[k];
+  for (int k = 0; k < 8; ++k) rec_piece(blk, k * n + s).q = src[k];
 }
 // 32-bit word w (0 .. 31) of record s: struct Veh's fields by their word index
-DEV uint32_t rec_word(const RecPiece* blk, int n, int s, int w) { return reinterpret_cast<const uint32_t*>(blk + (w >> 2) * n + s)[w & 3]; }
+DEV uint32_t rec_word(const RecPiece* blk, int n, int s, int w) { return reinterpret_cast<const uint32_t*>(&rec_piece(blk, (w >> 2) * n + s))[w & 3]; }
 DEV float rec_float(const RecPiece* blk, int n, int s, int w) { return __uint_as_float(rec_word(blk, n, s, w)); }
 enum { RW_X = 0, RW_Y = 1, RW_TH = 2, RW_LANE_SPAWN = 8 };
 DEV int rec_spawn(const RecPiece* blk, int n, int s) { return (int)(rec_word(blk, n, s, RW_LANE_SPAWN) >> 16); }  // Veh::spawn
