@@ -153,8 +153,8 @@ def _np_p(a):
 
 
 def _p(t):
-    """The device pointer of a tensor, as an argument of the C ABI."""
-    return C.c_void_p(t.data_ptr())
+    """The device pointer of a tensor, as an argument of the C ABI (None: a null pointer)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class PgdError(RuntimeError):
@@ -164,6 +164,47 @@ class PgdError(RuntimeError):
 def _chk(rc, what):
     if rc != 0:
         raise PgdError("%s failed with status %d" % (what, rc))
+
+
+class PgdArgError(AssertionError):
+    """An argument an Engine method refuses before it has called the library.  Raised, never asserted: the checks
+    are what stands between a wrong buffer and a kernel, and `python -O` must not remove them."""
+
+
+def _need(ok, where, wanted):
+    """A condition on a call's arguments that is not one tensor's."""
+    if not ok:
+        raise PgdArgError("%s: %s" % (where, wanted))
+
+
+def _dev(t, dtype, n=None, where="", name="", at_least=None, contiguous=True, align=0):
+    """`t` as a device buffer a kernel may read or write, checked -> `t`.  A cuda tensor of `dtype` (one, a tuple to choose from, or None:
+    any) with exactly `n` / at least `at_least` elements (None: not asked), contiguous unless told otherwise, its address a multiple of
+    `align` bytes.  `where` and `name`: the method and the argument, for the message."""
+    if (t.is_cuda and (t.dtype == dtype or dtype is None or (dtype.__class__ is tuple and t.dtype in dtype)) and
+            (n is None or t.numel() == n) and (at_least is None or t.numel() >= at_least) and (not contiguous or t.is_contiguous()) and
+            (not align or t.data_ptr() % align == 0)):
+        return t
+    raise PgdArgError(_refusal(t, dtype, n, where, name, at_least, contiguous, align))
+
+
+def _refusal(t, dtype, n, where, name, at_least, contiguous, align):
+    """The message for a tensor _dev refuses: the method, the argument, what was wanted and what was found."""
+    short = lambda d: str(d).replace("torch.", "")
+    wanted = "any" if dtype is None else " or ".join(short(d) for d in (dtype if dtype.__class__ is tuple else (dtype, )))
+    count = "" if n is None and at_least is None else " of %d elements" % n if at_least is None else " of at least %d elements" % at_least
+    found = "%s%s%s%s" % ("" if t.is_cuda else "cpu ", short(t.dtype), ", not contiguous," if contiguous and not t.is_contiguous() else "",
+                          " at an address that is not," if align and t.data_ptr() % align else "")
+    return "%s: %s: %s%s cuda tensor%s%s wanted, got %s of %d" % (where, name, "contiguous " if contiguous else "", wanted, count,
+                                                                  ", %d-byte aligned" % align if align else "", found, t.numel())
+
+
+def _opt(t, *spec):
+    """_dev for an argument that may be None."""
+    return None if t is None else _dev(t, *spec)
+
+
+_SIX = (".w1", ".b1", ".w2", ".b2", ".w3", ".b3")  # the six tensors of a network, as a message names them
 
 
 class Engine:
@@ -178,7 +219,7 @@ class Engine:
         self.N, self.A, self.T = cfg.num_envs, cfg.num_agents, cfg.num_traffic
         self.V = self.A + self.T
         self.D = _abi.obs_dim(cfg)
-        assert scen.V == self.V, "scenario bank built for V=%d, engine has V=%d" % (scen.V, self.V)
+        _need(scen.V == self.V, "Engine", "scenario bank built for V=%d, engine has V=%d" % (scen.V, self.V))
         self.device = torch.device("cuda", device)
         self.bank, self.scen = bank, scen
         h = C.c_void_p()
@@ -217,12 +258,29 @@ class Engine:
             _chk(self.L.pgd_set_stream(self.h, C.c_void_p(cur)), "pgd_set_stream")
             self._bound_stream = cur
 
-    def _check_actions(self, actions):
+    def _check_actions(self, actions, where="step", name="actions"):
         """An action tensor (or a buffer for one): float32 cuda, contiguous, [N, A, 2], 8-byte aligned (the step kernel reads an agent's
-        pair with one 8-byte load; pgd_step* refuse any other pointer with PGD_ERR_ARG)."""
-        assert actions.is_cuda and actions.dtype == self.torch.float32 and actions.is_contiguous()
-        assert actions.numel() == self.N * self.A * 2
-        assert actions.data_ptr() % 8 == 0, "actions must be 8-byte aligned (a view that starts at an odd float of its buffer is not)"
+        pair with one 8-byte load; pgd_step* refuse any other pointer with PGD_ERR_ARG: a view that starts at an odd float of its buffer)."""
+        if not (actions.is_cuda and actions.dtype == self.torch.float32 and actions.is_contiguous() and actions.numel() == self.N * self.A * 2 and
+                actions.data_ptr() % 8 == 0):  # (by hand on the per-step path, DESIGN section 32; _dev words the refusal)
+            _dev(actions, self.torch.float32, self.N * self.A * 2, where, name, None, True, 8)
+
+    def _obs_rows(self, o, rows, width, where, name="obs"):
+        """Observation rows as a kernel reads them: the 2-D view [rows, >= width] of `o` (rows None: as many as it has), float32 cuda with
+        unit column stride; the row stride is free -> the view, its row stride."""
+        o2 = o.view(-1, o.shape[-1])
+        if not (o2.is_cuda and o2.dtype == self.torch.float32 and o2.stride(1) == 1 and (rows is None or o2.shape[0] == rows) and
+                o2.shape[1] >= width):
+            raise PgdArgError("%s: %s: float32 cuda rows [%s, >= %d] with unit column stride wanted, got %s%s %s with strides %s" % (
+                where, name, "any" if rows is None else rows, width, "" if o2.is_cuda else "cpu ", o2.dtype, tuple(o2.shape), o2.stride()))
+        return o2, int(o2.stride(0))
+
+    def _scratch(self, work, need, device, where):
+        """A call's scratch: `work` as the caller gave it (any dtype; the library refuses one that is too small), or `need` new bytes -> the
+        tensor, its byte count."""
+        work = _dev(self.torch.empty(((need + 7) // 8, ), dtype=self.torch.float64, device=device) if work is None else work, None, None, where,
+                    "work")
+        return work, work.numel() * work.element_size()
 
     # -- reference surface ------------------------------------------------------------------------------------------
     def reset(self, scen_ids, env_ids=None, out=None):
@@ -233,13 +291,11 @@ class Engine:
         env_ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32).reshape(-1)
         if env_ids is not None and len(env_ids) != len(scen_ids):  # (the library reads len(scen_ids) entries of both)
             raise ValueError("reset: %d env ids for %d scenario ids" % (len(env_ids), len(scen_ids)))
-        obs = self.obs if out is None else out
-        assert obs.is_cuda and obs.dtype == self.torch.float32 and obs.is_contiguous() and obs.numel() == self.obs.numel()
+        obs = self.obs if out is None else _dev(out, self.torch.float32, self.obs.numel(), "reset", "out")
         self.torch.cuda.synchronize(self.device)
         if obs is not self.obs and self._unseen_rows(obs):
             _chk(self.L.pgd_forget_rows(self.h), "pgd_forget_rows")
-        _chk(self.L.pgd_reset(self.h, _np_p(env_ids), _np_p(scen_ids), len(scen_ids), C.c_void_p(obs.data_ptr())),
-             "pgd_reset")
+        _chk(self.L.pgd_reset(self.h, _np_p(env_ids), _np_p(scen_ids), len(scen_ids), _p(obs)), "pgd_reset")
         self.sync()
         return obs
 
@@ -268,76 +324,71 @@ class Engine:
         with PGD_NO_ROWZ=1 in the environment (the zero rows are then rewritten by every call).  `out` tensors need not be long-lived
         or zero-initialised: a tensor the engine has not seen alive makes it forget its marks (pgd_forget_rows) before the step."""
         self._check_actions(actions)
-        forget_first = False
         if out is None:  # the engine's own output buffers: their addresses never change
-            obs, reward, done, flags = self.obs, self.reward, self.done, self.flags
+            obs, rew, done, flags = self.obs, self.reward, self.done, self.flags
             p_obs, p_rew, p_done, p_flags = self._own_ptrs
         else:
-            obs, reward, done, flags = out
-            p_obs, p_rew, p_done, p_flags = (C.c_void_p(obs.data_ptr()), C.c_void_p(reward.data_ptr()),
-                                             C.c_void_p(done.data_ptr()), C.c_void_p(flags.data_ptr()))
-            # The zero-row marks of a multi-agent engine name a buffer by its address: a NEW tensor may sit where a freed one sat
-            # (torch's caching allocator; `out=torch.empty(...)` per step) and would inherit "known zero" marks for rows that hold
-            # anything.  Tensors seen before are kept alive here (their memory cannot be handed out again); any other tensor makes
-            # the engine forget its marks first (ADVICE r05).  The test is by IDENTITY of the tensor object, not by address, and the
-            # rollout collectors rely on that: they pass a fresh view (`obs[t + 1]`) per step, whose address recurs in every rollout
-            # while another row was written in between -- keyed by data_ptr, stale marks would get through.
-            forget_first = want_obs and self._unseen_rows(obs)
+            (obs, rew, done, flags), t, n = out, self.torch, self.N * self.A
+            if not (rew.is_cuda and done.is_cuda and flags.is_cuda and rew.dtype == t.float32 and done.dtype == t.uint8 and flags.dtype == t.int32 and
+                    rew.numel() == done.numel() == flags.numel() == n and rew.is_contiguous() and done.is_contiguous() and flags.is_contiguous() and
+                    (not want_obs or (obs.is_cuda and obs.dtype == t.float32 and obs.numel() == n * self.D and obs.is_contiguous()))):
+                [_dev(x, dt, size, "step", "out[%d]" % k) for k, (x, dt, size) in enumerate(  # (by hand above, as _check_actions; _dev words it)
+                    ((obs, t.float32, n * self.D), (rew, t.float32, n), (done, t.uint8, n), (flags, t.int32, n))) if k or want_obs]
+            p_obs, p_rew, p_done, p_flags = _p(obs), _p(rew), _p(done), _p(flags)
+        # The zero-row marks of a multi-agent engine name a buffer by its address: a NEW tensor may sit where a freed one sat
+        # (torch's caching allocator; `out=torch.empty(...)` per step) and would inherit "known zero" marks for rows that hold
+        # anything.  Tensors seen before are kept alive here (their memory cannot be handed out again); any other tensor makes
+        # the engine forget its marks first (ADVICE r05).  The test is by IDENTITY of the tensor object, not by address, and the
+        # rollout collectors rely on that: they pass a fresh view (`obs[t + 1]`) per step, whose address recurs in every rollout
+        # while another row was written in between -- keyed by data_ptr, stale marks would get through.
+        forget_first = out is not None and want_obs and self._unseen_rows(obs)
         self._follow_stream()
         if forget_first:
             _chk(self.L.pgd_forget_rows(self.h), "pgd_forget_rows")
-        _chk(
-            self.L.pgd_step(self.h, C.c_void_p(actions.data_ptr()), p_obs if want_obs else None, p_rew, p_done, p_flags),
-            "pgd_step"
-        )
-        return obs, reward, done, flags
+        _chk(self.L.pgd_step(self.h, _p(actions), p_obs if want_obs else None, p_rew, p_done, p_flags), "pgd_step")
+        return obs, rew, done, flags
 
     def step_packed(self, actions, rows):
         """Like step(), but the env's results go into `rows` [N, >= A*(D+2)] fp32 as [A*D obs | A reward | A done]: the
         row a per-step gather sends (pgdrive_amd/dist.py); `rows` may be a slice of the gather's receive buffer.  The zero-row marks
         of a multi-agent engine name `rows` by address and stride: as for step(out=...), a tensor the engine has not seen alive makes
         it forget its marks first (by identity of the tensor object: pass the same view while its rows are to be trusted)."""
-        self._check_actions(actions)
-        assert rows.is_cuda and rows.dtype == self.torch.float32 and rows.dim() == 2 and rows.shape[0] == self.N
-        assert rows.stride(1) == 1 and rows.stride(0) >= self.A * (self.D + 2)
+        self._check_actions(actions, "step_packed")
+        _dev(rows, self.torch.float32, None, "step_packed", "rows", None, False)
+        _need(rows.dim() == 2 and rows.shape[0] == self.N and rows.stride(1) == 1 and rows.stride(0) >= self.A * (self.D + 2), "step_packed",
+              "rows: [N, >= A * (D + 2)] with unit column stride wanted")
         forget_first = self._unseen_rows(rows)
         self._follow_stream()
         if forget_first:
             _chk(self.L.pgd_forget_rows(self.h), "pgd_forget_rows")
         p_obs, p_rew, p_done, p_flags = self._own_ptrs
-        _chk(self.L.pgd_step_packed(self.h, C.c_void_p(actions.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                    int(rows.stride(0)), p_rew, p_done, p_flags), "pgd_step_packed")
+        _chk(self.L.pgd_step_packed(self.h, _p(actions), _p(rows), int(rows.stride(0)), p_rew, p_done, p_flags), "pgd_step_packed")
         return rows, self.reward, self.done, self.flags
 
     def step_n(self, action_ring, first, n_steps, want_obs=True):
         """n_steps steps of `action_ring` [L, N, A, 2] (step k applies ring[(first + k) % L]) in one call (pgd_step_n): returns
         (obs after the last step or None, reward [n_steps, N, A], done, flags); the intermediate steps skip the observation."""
         t = self.torch
-        assert action_ring.is_cuda and action_ring.dtype == t.float32 and action_ring.is_contiguous() and action_ring.dim() == 4
-        assert tuple(action_ring.shape[1:]) == (self.N, self.A, 2) and action_ring.data_ptr() % 8 == 0  # (alignment: see _check_actions)
+        _dev(action_ring, t.float32, None, "step_n", "action_ring", None, True, 8)  # (alignment: see _check_actions)
+        _need(action_ring.dim() == 4 and tuple(action_ring.shape[1:]) == (self.N, self.A, 2), "step_n", "action_ring: [L, N, A, 2] wanted")
         self._follow_stream()
         rew = t.empty((n_steps, self.N, self.A), dtype=t.float32, device=self.obs.device)
         done = t.empty((n_steps, self.N, self.A), dtype=t.uint8, device=self.obs.device)
         flags = t.empty((n_steps, self.N, self.A), dtype=t.int32, device=self.obs.device)
         p_obs = self._own_ptrs[0] if want_obs else None
-        _chk(self.L.pgd_step_n(self.h, C.c_void_p(action_ring.data_ptr()), int(action_ring.shape[0]), int(first), int(n_steps), p_obs,
-                               C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()), C.c_void_p(flags.data_ptr())), "pgd_step_n")
+        _chk(self.L.pgd_step_n(self.h, _p(action_ring), int(action_ring.shape[0]), int(first), int(n_steps), p_obs, _p(rew), _p(done),
+                               _p(flags)), "pgd_step_n")
         return (self.obs if want_obs else None), rew, done, flags
 
     def mlp_prepare(self, weights):
         """The policy network's weights in the split-bf16 kernel's own layout (pgd_mlp_prepare): call once per policy update, hand the
         returned buffer to mlp_policy(prepared=...).  `weights` as for mlp_policy."""
         t = self.torch
-        w1, b1, w2, b2, w3, b3 = weights
-        for w in weights:
-            assert w.is_cuda and w.dtype == t.float32 and w.is_contiguous()
-        k = int(w1.shape[0])
-        assert w1.shape == (k, 256) and w2.shape == (256, 256) and w3.shape[0] == 256 and w3.shape[1] >= 2
+        k = int(weights[0].shape[0])
+        self._network(weights, k, 2, "mlp_prepare")
         buf = t.empty(int(self.L.pgd_mlp_prepared_bytes(k)), dtype=t.uint8, device=self.device)
         self._follow_stream()
-        _chk(self.L.pgd_mlp_prepare(self.h, k, 256, C.c_void_p(w1.data_ptr()), C.c_void_p(b1.data_ptr()), C.c_void_p(w2.data_ptr()),
-                                    C.c_void_p(b2.data_ptr()), C.c_void_p(w3.data_ptr()), C.c_void_p(b3.data_ptr()), int(w3.shape[1]),
-                                    C.c_void_p(buf.data_ptr())), "pgd_mlp_prepare")
+        _chk(self.L.pgd_mlp_prepare(self.h, k, 256, *map(_p, weights), int(weights[4].shape[1]), _p(buf)), "pgd_mlp_prepare")
         buf._pgd_in_dim = k
         return buf
 
@@ -357,11 +408,11 @@ class Engine:
     def lane_keep_actions(self, out, tick, obs=None, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):
         """Scripted lane-keeping actions for the ego from the last observation (pgd_lane_keep_actions): an action stream that
         keeps the ego driving (bench.py --actions expert).  `out` = float32 cuda tensor [N, 1, 2]."""
-        assert out.is_cuda and out.dtype == self.torch.float32 and out.is_contiguous() and out.numel() == self.N * 2
+        _dev(out, self.torch.float32, self.N * 2, "lane_keep_actions", "out")
+        o = self.obs if obs is None else _dev(obs, self.torch.float32, None, "lane_keep_actions", "obs", self.N * self.D)
         self._follow_stream()
-        o = self.obs if obs is None else obs
-        _chk(self.L.pgd_lane_keep_actions(self.h, C.c_void_p(o.data_ptr()), C.c_void_p(out.data_ptr()), k_lat, k_head,
-                                          v_target_kmh, noise, int(tick) & 0xffffffff), "pgd_lane_keep_actions")
+        _chk(self.L.pgd_lane_keep_actions(self.h, _p(o), _p(out), k_lat, k_head, v_target_kmh, noise, int(tick) & 0xffffffff),
+             "pgd_lane_keep_actions")
         return out
 
     def mlp_policy(self, weights, out, obs=None, group=-1, final_tanh=False, in_dim=None, prepared=None):
@@ -369,90 +420,89 @@ class Engine:
         `weights` = (w1 [in, 256], b1, w2 [256, 256], b2, w3 [256, >= 2], b3): contiguous float32 cuda tensors, row-major [in][out].
         `obs`: [rows, stride] float32 cuda (default: the engine's own observation buffer); `out`: float32 cuda [N, A, 2].
         group >= 0: only the rows of that env group, on the group's stream (then `obs` / `out` are still the FULL buffers)."""
-        t = self.torch
-        o = self.obs if obs is None else obs
-        o2 = o.view(-1, o.shape[-1])
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == self.N * self.A
-        self._check_actions(out)
+        prep = prepared is not None  # split-bf16 kernel on weights prepared by mlp_prepare (`weights` is then ignored)
+        k = int(in_dim if in_dim is not None else prepared._pgd_in_dim if prep else weights[0].shape[0])
+        o2, stride = self._obs_rows(self.obs if obs is None else obs, self.N * self.A, 0 if prep else k, "mlp_policy")
+        self._check_actions(out, "mlp_policy", "out")
+        if prep:
+            _dev(prepared, self.torch.uint8, None, "mlp_policy", "prepared", int(self.L.pgd_mlp_prepared_bytes(k)))
+        else:
+            self._network(weights, k, 2, "mlp_policy")
         if group < 0:
             self._follow_stream()
-        if prepared is not None:  # split-bf16 kernel on weights prepared by mlp_prepare (`weights` is then ignored)
-            k = int(in_dim if in_dim is not None else prepared._pgd_in_dim)
-            _chk(self.L.pgd_mlp_policy_prepared(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k,
-                                                C.c_void_p(prepared.data_ptr()), int(bool(final_tanh)), C.c_void_p(out.data_ptr())),
+        if prep:
+            _chk(self.L.pgd_mlp_policy_prepared(self.h, int(group), _p(o2), stride, k, _p(prepared), int(bool(final_tanh)), _p(out)),
                  "pgd_mlp_policy_prepared")
-            return out
-        w1, b1, w2, b2, w3, b3 = weights
-        for w in weights:
-            assert w.is_cuda and w.dtype == t.float32 and w.is_contiguous()
-        k = int(in_dim if in_dim is not None else w1.shape[0])
-        assert w1.shape == (k, 256) and w2.shape == (256, 256) and w3.shape[0] == 256 and w3.shape[1] >= 2 and k <= o2.shape[1]
-        _chk(self.L.pgd_mlp_policy(self.h, int(group), C.c_void_p(o2.data_ptr()), int(o2.stride(0)), k, 256,
-                                   C.c_void_p(w1.data_ptr()), C.c_void_p(b1.data_ptr()), C.c_void_p(w2.data_ptr()), C.c_void_p(b2.data_ptr()),
-                                   C.c_void_p(w3.data_ptr()), C.c_void_p(b3.data_ptr()), int(w3.shape[1]), int(bool(final_tanh)),
-                                   C.c_void_p(out.data_ptr())), "pgd_mlp_policy")
+        else:
+            _chk(self.L.pgd_mlp_policy(self.h, int(group), _p(o2), stride, k, 256, *map(_p, weights), int(weights[4].shape[1]),
+                                       int(bool(final_tanh)), _p(out)), "pgd_mlp_policy")
         return out
 
-    def _network(self, weights, k, heads):
-        """The six tensors of one network checked (float32 cuda, contiguous, [k, 256] / [256, 256] / [256, >= heads]) -> their pointers."""
-        t = self.torch
+    def _network(self, weights, k, heads, where, name="weights", cols=None):
+        """The six tensors of one network checked (float32 cuda, contiguous, [k, 256] / [256, 256] / [256, >= heads], or [256, cols], and
+        the biases of their lengths) -> their pointers."""
         w1, b1, w2, b2, w3, b3 = weights
-        for w in weights:
-            assert w.is_cuda and w.dtype == t.float32 and w.is_contiguous()
-        assert w1.shape == (k, 256) and w2.shape == (256, 256) and w3.dim() == 2 and w3.shape[0] == 256 and w3.shape[1] >= heads
-        assert b1.numel() == 256 and b2.numel() == 256 and b3.numel() == w3.shape[1]
-        return [w.data_ptr() for w in weights]
+        if not (w3.dim() == 2 and w3.shape[0] == 256 and (w3.shape[1] >= heads if cols is None else w3.shape[1] == cols) and
+                w1.shape == (k, 256) and w2.shape == (256, 256)):
+            raise PgdArgError("%s: %s: w1 [%d, 256], w2 [256, 256], w3 [256, %s] wanted" % (where, name, k, cols or ">= %d" % heads))
+        cols, f32 = int(w3.shape[1]), self.torch.float32
+        for w in weights:  # (by hand on the per-step path, as _check_actions; _dev words the refusal below)
+            if not (w.is_cuda and w.dtype == f32 and w.is_contiguous()):
+                break
+        else:
+            if b1.numel() == 256 and b2.numel() == 256 and b3.numel() == cols:
+                return [w.data_ptr() for w in weights]
+        for w, n, part in zip(weights, (k * 256, 256, 65536, 256, 256 * cols, cols), _SIX):
+            _dev(w, f32, n, where, name + part)
 
-    def _nets(self, st, policy, value, k):
+    def _nets(self, st, policy, value, k, where, name="policy_weights", vname="value_weights"):
         """`st` (ActorCritic of weights, PPOGrads of gradient buffers) with the checked pointers of the policy's six tensors and, unless
         `value` is None, of the critic's."""
-        st.w1, st.b1, st.w2, st.b2, st.w3, st.b3 = self._network(policy, k, 4)
+        st.w1, st.b1, st.w2, st.b2, st.w3, st.b3 = self._network(policy, k, 4, where, name)
         if value is not None:
-            st.vw1, st.vb1, st.vw2, st.vb2, st.vw3, st.vb3 = self._network(value, k, 1)
-            assert value[4].shape[1] == 1
+            st.vw1, st.vb1, st.vw2, st.vb2, st.vw3, st.vb3 = self._network(value, k, 1, where, vname, 1)
         return st
 
-    def _value_net(self, st, weights, k):
+    def _value_net(self, st, weights, k, where, name):
         """`st` (ValueNet, ValueGrads) with the checked pointers of a critic-shaped network's six tensors."""
-        st.w1, st.b1, st.w2, st.b2, st.w3, st.b3 = self._network(weights, k, 1)
-        assert weights[4].shape[1] == 1
+        st.w1, st.b1, st.w2, st.b2, st.w3, st.b3 = self._network(weights, k, 1, where, name, 1)
         return st
 
-    def _ac_args(self, policy_weights, value_weights, cost_weights, out, per_row, seed, tick, obs, group, deterministic, in_dim):
-        """What the mlp_actor_critic* calls share, checked: the observation rows, `out`, the `per_row` outputs, the networks (value_weights
-        and cost_weights None: none) -> the leading arguments of the C call, up to its flags.  Follows the caller's stream (group < 0)."""
-        t = self.torch
-        o = self.obs if obs is None else obs
-        o2 = o.view(-1, o.shape[-1])
+    def _ac_call(self, where, policy_weights, value_weights, cost_weights, out, per_row, seed, tick, obs, group, deterministic, in_dim, row_list=()):
+        """The mlp_actor_critic* call pgd_<where>: what the three share, checked -- the observation rows, `out`, the `per_row` outputs (logp,
+        value, cost_value), the networks (value_weights and cost_weights None: none) --, then the launch on the caller's stream (group < 0);
+        `row_list`: the two pointers of mlp_actor_critic_rows' list."""
         rows = self.N * self.A
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == rows
-        self._check_actions(out)
-        assert cost_weights is None or value_weights is not None, "the cost critic comes with a critic"
-        for v in per_row:
-            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == rows
         k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
-        assert k <= o2.shape[1]
-        nets = self._nets(_abi.ActorCritic(), policy_weights, value_weights, k)
+        o2, stride = self._obs_rows(self.obs if obs is None else obs, rows, k, where)
+        self._check_actions(out, where, "out")
+        f32, fn = self.torch.float32, "pgd_" + where
+        if cost_weights is not None and value_weights is None:
+            raise PgdArgError(where + ": the cost critic comes with a critic")
+        for i, v in enumerate(per_row[:3 if value_weights is not None else 1]):  # (no critic: logp alone; by hand, as _check_actions)
+            if not (v.is_cuda and v.dtype == f32 and v.is_contiguous() and v.numel() == rows):
+                _dev(v, f32, rows, where, ("logp", "value", "cost_value")[i])
+        nets = self._nets(_abi.ActorCritic(), policy_weights, value_weights, k, where)
         nets.out_cols = int(policy_weights[4].shape[1])
-        cnet = () if cost_weights is None else (C.byref(self._value_net(_abi.ValueNet(), cost_weights, k)), )
+        cnet = () if cost_weights is None else (C.byref(self._value_net(_abi.ValueNet(), cost_weights, k, where, "cost_weights")), )
         if group < 0:
             self._follow_stream()
-        return (self.h, int(group), _p(o2), int(o2.stride(0)), k, C.byref(nets), *cnet, int(seed) & 0xffffffff, int(tick) & 0xffffffff,
-                _abi.AC_DETERMINISTIC if deterministic else 0)
+        per_row = per_row if value_weights is not None else (per_row[0], None)  # (no critic: a null pointer for `value`)
+        _chk(getattr(self.L, fn)(self.h, int(group), _p(o2), stride, k, C.byref(nets), *cnet, int(seed) & 0xffffffff, int(tick) & 0xffffffff,
+                                 _abi.AC_DETERMINISTIC if deterministic else 0, *row_list, _p(out), *map(_p, per_row)), fn)
 
-    def _rollout_buffers(self, lead, table):
-        """The tensors of a rollout call checked: `lead` is [T, rows...]; `table` rows are (tensor, dtype, extra) with extra 0: T * rows
-        entries, 1: (T + 1) * rows, None: rows; a tensor that is None is allocated (of lead's shape, or [rows]).  Follows the caller's
-        stream.  -> T, rows, the tensors."""
-        t = self.torch
+    def _rollout_buffers(self, where, table):
+        """The tensors of a rollout call checked: `table` rows are (name, tensor, dtype, extra); the first is the lead, [T, rows...]; extra
+        0: T * rows entries, 1: (T + 1) * rows, None: rows; a tensor that is None is allocated (of lead's shape, or [rows]).  Follows the
+        caller's stream.  -> T, rows, the tensors."""
+        lead = table[0][1]
         T = int(lead.shape[0])
         rows = lead.numel() // max(T, 1)
         out = []
-        for v, dt, extra in table:
+        for name, v, dt, extra in table:
             if v is None:
-                v = t.empty(lead.shape if extra == 0 else (rows, ), dtype=dt, device=lead.device)
-            assert v.is_cuda and v.dtype == dt and v.is_contiguous() and v.numel() == (rows if extra is None else (T + extra) * rows)
-            out.append(v)
+                v = self.torch.empty(lead.shape if extra == 0 else (rows, ), dtype=dt, device=lead.device)
+            out.append(_dev(v, dt, rows if extra is None else (T + extra) * rows, where, name))
         self._follow_stream()
         return T, rows, out
 
@@ -464,9 +514,7 @@ class Engine:
         `out` [N, A, 2] (unclipped: step clips), `logp` and `value` [N, A]: float32 cuda.  The noise is a function of (seed, global row,
         tick); `tick` is added to the device counter of actor_critic_tick, if one is set.  deterministic: the action is the mean.
         `obs`, `group`, `in_dim` as for mlp_policy."""
-        a = self._ac_args(policy_weights, value_weights, None, out, (logp, ) if value_weights is None else (logp, value), seed, tick, obs, group,
-                          deterministic, in_dim)
-        _chk(self.L.pgd_mlp_actor_critic(*a, _p(out), _p(logp), _p(value) if value_weights is not None else None), "pgd_mlp_actor_critic")
+        self._ac_call("mlp_actor_critic", policy_weights, value_weights, None, out, (logp, value), seed, tick, obs, group, deterministic, in_dim)
         return out, logp, value
 
     def guardian(self, expert_weights, save_level, actions, state, applied, info, seed, tick, prev_flags=None, trace=None, obs=None, group=-1,
@@ -480,49 +528,49 @@ class Engine:
         samples with (seed, global row, tick + the device counter of actor_critic_tick) unless `deterministic`; `immediate` (not a
         reference behaviour) applies a correction in the step that raises it.  A bound observation normalisation is ignored."""
         t = self.torch
-        assert self.A == 1, "the guardian serves single-agent engines"
-        o = self.obs if obs is None else obs
-        o2 = o.view(-1, o.shape[-1])
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == self.N and o2.shape[1] >= self.D
-        self._check_actions(actions)
-        self._check_actions(applied)
-        for v in (state, info):
-            assert v.is_cuda and v.dtype == t.uint8 and v.is_contiguous() and v.numel() == self.N
-        if prev_flags is not None:
-            assert prev_flags.is_cuda and prev_flags.dtype == t.int32 and prev_flags.is_contiguous() and prev_flags.numel() == self.N
-        if trace is not None:
-            assert trace.is_cuda and trace.dtype == t.float32 and trace.is_contiguous() and trace.numel() == 4 * self.N
+        _need(self.A == 1, "guardian", "the guardian serves single-agent engines")
+        o2, stride = self._obs_rows(self.obs if obs is None else obs, self.N, self.D, "guardian")
+        self._check_actions(actions, "guardian")
+        self._check_actions(applied, "guardian", "applied")
+        _dev(state, t.uint8, self.N, "guardian", "state")
+        _dev(info, t.uint8, self.N, "guardian", "info")
+        _opt(prev_flags, t.int32, self.N, "guardian", "prev_flags")
+        _opt(trace, t.float32, 4 * self.N, "guardian", "trace")
         k = int(expert_weights[0].shape[0])
-        assert k in (self.D, self.D + 1), "the expert takes %d inputs (or %d with the lateral float), not %d" % (self.D, self.D + 1, k)
-        nets = self._nets(_abi.ActorCritic(), expert_weights, None, k)
+        if k not in (self.D, self.D + 1):
+            raise PgdArgError("guardian: the expert takes %d inputs (or %d with the lateral float), not %d" % (self.D, self.D + 1, k))
+        nets = self._nets(_abi.ActorCritic(), expert_weights, None, k, "guardian", "expert_weights")
         nets.out_cols = int(expert_weights[4].shape[1])
         mode = (_abi.GUARD_LEGACY_LATERAL if k == self.D + 1 else 0) | (_abi.GUARD_DETERMINISTIC if deterministic else 0) | \
             (_abi.GUARD_IMMEDIATE if immediate else 0)
         cfg = _abi.GuardianConfig(k, float(save_level), int(seed) & 0xffffffff, int(tick) & 0xffffffff, mode)
         if group < 0:
             self._follow_stream()
-        _chk(self.L.pgd_guardian(self.h, int(group), _p(o2), int(o2.stride(0)), C.byref(nets), C.byref(cfg), _p(actions),
-                                 _p(prev_flags) if prev_flags is not None else None, _p(state), _p(applied), _p(info),
-                                 _p(trace) if trace is not None else None), "pgd_guardian")
+        _chk(self.L.pgd_guardian(self.h, int(group), _p(o2), stride, C.byref(nets), C.byref(cfg), _p(actions), _p(prev_flags), _p(state),
+                                 _p(applied), _p(info), _p(trace)), "pgd_guardian")
         return applied, info
 
     def actor_critic_tick(self, counter):
         """Give the engine a tick counter in device memory (pgd_actor_critic_tick): a cuda int32 tensor of one element that every later
         mlp_actor_critic launch adds to its `tick` (modulo 2^32) when it RUNS -- what lets a captured rollout draw new noise at every
         replay.  None: back to the argument alone.  The engine keeps the tensor alive."""
-        if counter is not None:
-            assert counter.is_cuda and counter.dtype == self.torch.int32 and counter.numel() == 1
-        _chk(self.L.pgd_actor_critic_tick(self.h, C.c_void_p(counter.data_ptr()) if counter is not None else None), "pgd_actor_critic_tick")
+        _opt(counter, self.torch.int32, 1, "actor_critic_tick", "counter", None, False)
+        _chk(self.L.pgd_actor_critic_tick(self.h, _p(counter)), "pgd_actor_critic_tick")
         self._ac_tick = counter
 
     def gae(self, reward, value, done, gamma, lam, adv=None, ret=None):
         """Advantages and returns of a rollout (pgd_gae): reward, done (uint8) [T, rows...], value [T + 1, rows...] (the last row is the
         bootstrap), time-major contiguous cuda tensors; a done cuts the episode.  Returns (adv, ret), float32 of reward's shape (`adv`,
         `ret`: buffers to write).  Asynchronous on the caller's current stream."""
+        return self._gae("gae", reward, value, done, (), gamma, lam, adv, ret)
+
+    def _gae(self, fn, reward, value, done, term, gamma, lam, adv, ret):
+        """gae and gae_bootstrap (`term`: its table row for term_value, or none)."""
         t = self.torch
-        T, rows, (reward, value, done, adv, ret) = self._rollout_buffers(
-            reward, ((reward, t.float32, 0), (value, t.float32, 1), (done, t.uint8, 0), (adv, t.float32, 0), (ret, t.float32, 0)))
-        _chk(self.L.pgd_gae(self.h, _p(reward), _p(value), _p(done), T, rows, float(gamma), float(lam), _p(adv), _p(ret)), "pgd_gae")
+        T, rows, (*ins, adv, ret) = self._rollout_buffers(fn, (("reward", reward, t.float32, 0), ("value", value, t.float32, 1),
+                                                                ("done", done, t.uint8, 0), *term, ("adv", adv, t.float32, 0),
+                                                                ("ret", ret, t.float32, 0)))
+        _chk(getattr(self.L, "pgd_" + fn)(self.h, *map(_p, ins), T, rows, float(gamma), float(lam), _p(adv), _p(ret)), "pgd_" + fn)
         return adv, ret
 
     # -- rollouts of multi-agent engines (include/pgdrive_hip.h states the predicates acted / cont / live) -------------------------
@@ -535,18 +583,18 @@ class Engine:
         n = self.N * self.A
         rows = t.empty((n, ), dtype=t.int32, device=self.device) if rows is None else rows
         count = t.zeros((1, ), dtype=t.int32, device=self.device) if count is None else count
-        assert flags.is_cuda and flags.dtype == t.int32 and flags.is_contiguous() and flags.numel() == n
-        assert done.is_cuda and done.dtype == t.uint8 and done.is_contiguous() and done.numel() == n
-        assert rows.is_cuda and rows.dtype == t.int32 and rows.is_contiguous() and rows.numel() >= (n if group < 0 else n // self._n_groups())
-        assert count.is_cuda and count.dtype == t.int32 and count.numel() == 1
+        _dev(flags, t.int32, n, "live_rows", "flags")
+        _dev(done, t.uint8, n, "live_rows", "done")
+        lp, cp = self._list_args(rows, count, self._group_rows(group), "live_rows", "rows")
         if group < 0:
             self._follow_stream()
-        _chk(self.L.pgd_live_rows(self.h, int(group), C.c_void_p(flags.data_ptr()), C.c_void_p(done.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                  C.c_void_p(count.data_ptr())), "pgd_live_rows")
+        _chk(self.L.pgd_live_rows(self.h, int(group), _p(flags), _p(done), lp, cp), "pgd_live_rows")
         return rows, count
 
-    def _n_groups(self):
-        return max(1, int(self.n_groups or 1))
+    def _group_rows(self, group):
+        """How many seat rows a call on `group` (< 0: the whole engine) covers: what its row list has to hold."""
+        n = self.N * self.A
+        return n if group < 0 else n // max(1, int(self.n_groups or 1))
 
     def rollout_index(self, flags, index=None, count=None):
         """The entries t * rows + r of a time-major flag tensor [T, rows...] at which an agent acted (PGD_F_REPORT), ascending, into
@@ -557,12 +605,10 @@ class Engine:
         rows = flags.numel() // max(T, 1)
         index = t.empty((T * rows, ), dtype=t.int32, device=self.device) if index is None else index
         count = t.zeros((1, ), dtype=t.int32, device=self.device) if count is None else count
-        assert flags.is_cuda and flags.dtype == t.int32 and flags.is_contiguous()
-        assert index.is_cuda and index.dtype == t.int32 and index.is_contiguous() and index.numel() >= T * rows
-        assert count.is_cuda and count.dtype == t.int32 and count.numel() == 1
+        _dev(flags, t.int32, None, "rollout_index", "flags")
+        ip, cp = self._list_args(index, count, T * rows, "rollout_index")
         self._follow_stream()
-        _chk(self.L.pgd_rollout_index(self.h, C.c_void_p(flags.data_ptr()), T, rows, C.c_void_p(index.data_ptr()), C.c_void_p(count.data_ptr())),
-             "pgd_rollout_index")
+        _chk(self.L.pgd_rollout_index(self.h, _p(flags), T, rows, ip, cp), "pgd_rollout_index")
         return index, count
 
     def mlp_actor_critic_rows(self, policy_weights, value_weights, rows, count, out, logp, value, seed, tick, obs=None, group=-1,
@@ -570,14 +616,10 @@ class Engine:
         """mlp_actor_critic over the rows of a list (pgd_mlp_actor_critic_rows): `rows` / `count` as live_rows returns them.  A listed
         row gets bit for bit what mlp_actor_critic gives it; every other row of the range gets action 0, 0, logp 0, value 0 (written by
         this call) and its observation is never used (it may hold NaN).  The other arguments as for mlp_actor_critic."""
-        t = self.torch
-        n = self.N * self.A
-        assert rows.is_cuda and rows.dtype == t.int32 and rows.is_contiguous() and rows.numel() >= (n if group < 0 else n // self._n_groups())
-        assert count.is_cuda and count.dtype == t.int32 and count.numel() == 1
-        a = self._ac_args(policy_weights, value_weights, None, out, (logp, ) if value_weights is None else (logp, value), seed, tick, obs, group,
-                          deterministic, in_dim)
-        _chk(self.L.pgd_mlp_actor_critic_rows(*a, _p(rows), _p(count), _p(out), _p(logp), _p(value) if value_weights is not None else None),
-             "pgd_mlp_actor_critic_rows")
+        _need(rows is not None and count is not None, "mlp_actor_critic_rows", "rows and count wanted")
+        row_list = self._list_args(rows, count, self._group_rows(group), "mlp_actor_critic_rows", "rows")
+        self._ac_call("mlp_actor_critic_rows", policy_weights, value_weights, None, out, (logp, value), seed, tick, obs, group, deterministic,
+                      in_dim, row_list)
         return out, logp, value
 
     def gae_masked(self, reward, value, done, flags, gamma, lam, adv=None, ret=None, mask=None):
@@ -586,8 +628,8 @@ class Engine:
         Returns (adv, ret, mask): mask uint8 of reward's shape, 1 where an agent acted."""
         t = self.torch
         T, rows, (reward, value, done, flags, adv, ret, mask) = self._rollout_buffers(
-            reward, ((reward, t.float32, 0), (value, t.float32, 1), (done, t.uint8, 0), (flags, t.int32, 0), (adv, t.float32, 0), (ret, t.float32, 0),
-                     (mask, t.uint8, 0)))
+            "gae_masked", (("reward", reward, t.float32, 0), ("value", value, t.float32, 1), ("done", done, t.uint8, 0), ("flags", flags, t.int32, 0),
+                           ("adv", adv, t.float32, 0), ("ret", ret, t.float32, 0), ("mask", mask, t.uint8, 0)))
         _chk(self.L.pgd_gae_masked(self.h, _p(reward), _p(value), _p(done), _p(flags), T, rows, float(gamma), float(lam), _p(adv), _p(ret),
                                    _p(mask)), "pgd_gae_masked")
         return adv, ret, mask
@@ -597,28 +639,23 @@ class Engine:
         """The scratch pgd_ppo_grad needs for minibatches of up to `rows` positions (pgd_ppo_work_bytes); 0: the call would refuse them."""
         return int(self.L.pgd_ppo_work_bytes(int(in_dim), int(rows), int(bool(has_critic))))
 
-    def _list_args(self, index, count, n_list):
+    def _list_args(self, index, count, n_list, where, name="index"):
         """A row list checked: `index` int32 cuda [>= n_list] or None, `count` int32 cuda [1] or None -> their pointers."""
-        t = self.torch
-        if index is not None:
-            assert index.is_cuda and index.dtype == t.int32 and index.is_contiguous() and index.numel() >= n_list
-        if count is not None:
-            assert count.is_cuda and count.dtype == t.int32 and count.numel() == 1
-        return (C.c_void_p(index.data_ptr()) if index is not None else None, C.c_void_p(count.data_ptr()) if count is not None else None)
+        i32 = self.torch.int32
+        return _p(_opt(index, i32, None, where, name, n_list)), _p(_opt(count, i32, 1, where, "count", None, False))
 
     def adv_stats(self, adv, out=None, index=None, count=None, n_list=None):
         """Population mean and 1 / (std + 1e-8) of the advantages over a row list (pgd_adv_stats) -> `out`, float32 cuda [2].  The list:
         adv.view(-1)[index[q]] for q < count (`index` None: entry q itself; `count` None: n_list; n_list None: every entry of `adv`, or of
         `index`); `count` is read on the device.  No entries: (0, 1)."""
         t = self.torch
-        assert adv.is_cuda and adv.dtype == t.float32 and adv.is_contiguous()
         n_list = int((index if index is not None else adv).numel() if n_list is None else n_list)
-        assert 0 <= n_list and (index is not None or n_list <= adv.numel())
-        out = t.empty((2, ), dtype=t.float32, device=self.device) if out is None else out
-        assert out.is_cuda and out.dtype == t.float32 and out.is_contiguous() and out.numel() == 2
-        ip, cp = self._list_args(index, count, n_list)
+        _need(0 <= n_list, "adv_stats", "n_list >= 0 wanted")
+        _dev(adv, t.float32, None, "adv_stats", "adv", None if index is not None else n_list)
+        out = _dev(t.empty((2, ), dtype=t.float32, device=self.device) if out is None else out, t.float32, 2, "adv_stats", "out")
+        ip, cp = self._list_args(index, count, n_list, "adv_stats")
         self._follow_stream()
-        _chk(self.L.pgd_adv_stats(self.h, C.c_void_p(adv.data_ptr()), ip, cp, n_list, C.c_void_p(out.data_ptr())), "pgd_adv_stats")
+        _chk(self.L.pgd_adv_stats(self.h, _p(adv), ip, cp, n_list, _p(out)), "pgd_adv_stats")
         return out
 
     def ppo_grad(self, policy_weights, value_weights, policy_grads, value_grads, obs, actions, logp_old, adv, ret, stats, work, start=0, stride=1,
@@ -629,50 +666,49 @@ class Engine:
         of `index`); position q is row index[q] (`index` None: q).  `adv_stats`: the two floats of adv_stats(), or None.  Gradients are
         written into `policy_grads` / `value_grads`, tuples of the weights' shapes (value_weights None: no critic, value_grads ignored);
         `stats` float32 cuda [8] (_abi.PPO_STATS); `work` a cuda tensor of at least ppo_work_bytes(in_dim, rows) bytes.  Asynchronous."""
-        nets, _, b, grads, _ = self._ppo_batch((policy_weights, value_weights, None), (policy_grads, value_grads, None), obs, actions, logp_old, adv,
-                                               ret, None, stats, work, start, stride, rows, index, count, n_list, adv_stats, in_dim)
+        nets, _, b, grads, _ = self._ppo_batch("ppo_grad", (policy_weights, value_weights, None), (policy_grads, value_grads, None), obs, actions,
+                                               logp_old, adv, ret, None, stats, work, start, stride, rows, index, count, n_list, adv_stats, in_dim)
         hp = _abi.PPOHyper(float(clip), float(vf_coef), float(ent_coef))
         _chk(self.L.pgd_ppo_grad(self.h, C.byref(nets), C.byref(b), C.byref(hp), C.byref(grads), _p(stats), _p(work),
                                  work.numel() * work.element_size()), "pgd_ppo_grad")
         return stats
 
-    def _ppo_batch(self, weights, grad_bufs, obs, actions, logp_old, adv, ret, cost_ret, stats, work, start, stride, rows, index, count, n_list,
-                   adv_stats, in_dim):
+    def _ppo_batch(self, where, weights, grad_bufs, obs, actions, logp_old, adv, ret, cost_ret, stats, work, start, stride, rows, index, count,
+                   n_list, adv_stats, in_dim):
         """What ppo_grad and ppo_grad_cost share, checked: the rollout's tensors, the minibatch, `stats`, `work`, and the networks with their
         gradient buffers -- `weights` and `grad_bufs` are (policy, value or None, cost or None) -> ActorCritic, ValueNet (or None),
         PPOBatch, PPOGrads, ValueGrads (or None).  Follows the caller's stream."""
         t = self.torch
         (pw, vw, cw), (pg, vg, cg) = weights, grad_bufs
-        assert cw is None or vw is not None, "the cost critic comes with a critic"
-        o2 = obs.view(-1, obs.shape[-1])
-        n_rows = int(o2.shape[0])
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1
-        assert actions.is_cuda and actions.dtype == t.float32 and actions.is_contiguous() and actions.numel() == 2 * n_rows
-        for v in (logp_old, adv) + (() if vw is None else (ret, )) + (() if cw is None else (cost_ret, )):
-            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == n_rows
-        n_list = int((index.numel() if index is not None else n_rows) if n_list is None else n_list)
-        assert 0 <= n_list and (index is not None or n_list <= n_rows)
-        rows = int(max(1, -(-(n_list - int(start)) // int(stride))) if rows is None else rows)
-        assert int(start) >= 0 and int(stride) >= 1 and 1 <= rows <= _abi.PPO_ROWS_MAX
+        _need(cw is None or vw is not None, where, "the cost critic comes with a critic")
         k = int(in_dim if in_dim is not None else pw[0].shape[0])
-        assert k <= o2.shape[1]
-        assert stats.is_cuda and stats.dtype == t.float32 and stats.is_contiguous() and stats.numel() == 8
+        o2, obs_stride = self._obs_rows(obs, None, k, where)
+        n_rows = int(o2.shape[0])
+        _dev(actions, t.float32, 2 * n_rows, where, "actions")
+        by_row = (("logp_old", logp_old), ("adv", adv), ("ret", ret), ("cost_ret", cost_ret))
+        for name, v in by_row[:2 + (vw is not None) + (cw is not None)]:
+            _dev(v, t.float32, n_rows, where, name)
+        n_list = int((index.numel() if index is not None else n_rows) if n_list is None else n_list)
+        _need(0 <= n_list and (index is not None or n_list <= n_rows), where, "0 <= n_list <= the rows of obs wanted")
+        rows = int(max(1, -(-(n_list - int(start)) // int(stride))) if rows is None else rows)
+        _need(int(start) >= 0 and int(stride) >= 1 and 1 <= rows <= _abi.PPO_ROWS_MAX, where, "start >= 0, stride >= 1, rows <= PPO_ROWS_MAX wanted")
+        _dev(stats, t.float32, 8, where, "stats")
         need = self.ppo_work_bytes(k, rows, vw is not None) if cw is None else self.ppo_cost_work_bytes(k, rows)
-        assert need > 0 and work.is_cuda and work.is_contiguous() and work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
-        if adv_stats is not None:
-            assert adv_stats.is_cuda and adv_stats.dtype == t.float32 and adv_stats.is_contiguous() and adv_stats.numel() == 2
-        nets = self._nets(_abi.ActorCritic(), pw, vw, k)
+        _dev(work, None, None, where, "work", None, True, 16)
+        _need(0 < need <= work.numel() * work.element_size(), where, "work: at least %d bytes wanted (0: rows or in_dim out of range)" % need)
+        _opt(adv_stats, t.float32, 2, where, "adv_stats")
+        nets = self._nets(_abi.ActorCritic(), pw, vw, k, where)
         nets.out_cols = int(pw[4].shape[1])
-        grads = self._nets(_abi.PPOGrads(), pg, None if vw is None else vg, k)
-        assert all(g.shape == w.shape for g, w in zip(pg, pw))
-        cnet = None if cw is None else self._value_net(_abi.ValueNet(), cw, k)
-        cgrads = None if cw is None else self._value_net(_abi.ValueGrads(), cg, k)
+        grads = self._nets(_abi.PPOGrads(), pg, None if vw is None else vg, k, where, "policy_grads", "value_grads")
+        _need(all(g.shape == w.shape for g, w in zip(pg, pw)), where, "policy_grads of the weights' shapes wanted")
+        cnet = None if cw is None else self._value_net(_abi.ValueNet(), cw, k, where, "cost_weights")
+        cgrads = None if cw is None else self._value_net(_abi.ValueGrads(), cg, k, where, "cost_grads")
         b = _abi.PPOBatch()
         b.obs, b.action, b.logp_old, b.adv = o2.data_ptr(), actions.data_ptr(), logp_old.data_ptr(), adv.data_ptr()
         b.ret = ret.data_ptr() if vw is not None else None
         b.adv_stats = adv_stats.data_ptr() if adv_stats is not None else None
-        b.index, b.count = self._list_args(index, count, n_list)
-        b.obs_stride, b.in_dim, b.n_rows, b.n_list, b.start, b.stride, b.rows = int(o2.stride(0)), k, n_rows, n_list, int(start), int(stride), rows
+        b.index, b.count = self._list_args(index, count, n_list, where)
+        b.obs_stride, b.in_dim, b.n_rows, b.n_list, b.start, b.stride, b.rows = obs_stride, k, n_rows, n_list, int(start), int(stride), rows
         self._follow_stream()
         return nets, cnet, b, grads, cgrads
 
@@ -680,15 +716,21 @@ class Engine:
         """One Adam step on the flat float32 cuda buffer `param` (pgd_adam), `grad`, `m`, `v` of its length; max_grad_norm > 0 clips by the
         global gradient norm first.  `step`: int32 cuda [4], zero before the first step -- entry 0 counts the steps ON THE DEVICE (a
         replayed graph takes the next step), entries 1..3 are the call's record.  Asynchronous."""
+        a = self._adam_args("adam", param, grad, m, v, step, lr, betas, eps, max_grad_norm)
+        self._follow_stream()
+        _chk(self.L.pgd_adam(*a), "pgd_adam")
+        return param
+
+    def _adam_args(self, where, param, grad, m, v, step, lr, betas, eps, max_grad_norm):
+        """What adam and adam_gated share, checked -> the leading arguments of the C call."""
         t = self.torch
         n = int(param.numel())
-        for x in (param, grad, m, v):
-            assert x.is_cuda and x.dtype == t.float32 and x.is_contiguous() and x.numel() == n
-        assert n >= 1 and step.is_cuda and step.dtype == t.int32 and step.is_contiguous() and step.numel() == 4
-        self._follow_stream()
-        _chk(self.L.pgd_adam(self.h, C.c_void_p(param.data_ptr()), C.c_void_p(grad.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), n,
-                             C.c_void_p(step.data_ptr()), float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm)), "pgd_adam")
-        return param
+        _need(n >= 1, where, "param: at least one element wanted")
+        for name, x in (("param", param), ("grad", grad), ("m", m), ("v", v)):
+            _dev(x, t.float32, n, where, name)
+        _dev(step, t.int32, 4, where, "step")
+        return (self.h, _p(param), _p(grad), _p(m), _p(v), n, _p(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                float(max_grad_norm))
 
     def shuffle_index(self, index, count, n_list, seed, epoch, epoch_dev=None, out=None):
         """A keyed permutation of a row list (pgd_shuffle_index) -> `out`, int32 cuda [n_list]: out[q] = index[pi(q)] (`index` None: pi(q))
@@ -697,18 +739,17 @@ class Engine:
         what they held.  `out` must not share memory with `index`.  Asynchronous."""
         t = self.torch
         n_list = int(n_list)
-        assert 0 <= n_list <= _abi.PPO_ROWS_MAX and 0 <= int(seed) < 2 ** 32 and 0 <= int(epoch) < 2 ** 32
+        _need(0 <= n_list <= _abi.PPO_ROWS_MAX and 0 <= int(seed) < 2 ** 32 and 0 <= int(epoch) < 2 ** 32, "shuffle_index",
+              "0 <= n_list <= PPO_ROWS_MAX and seed, epoch in [0, 2^32) wanted")
         out = t.empty((n_list, ), dtype=t.int32, device=self.device) if out is None else out
-        assert out.is_cuda and out.dtype == t.int32 and out.is_contiguous() and out.numel() >= n_list
-        ip, cp = self._list_args(index, count, n_list)
+        _dev(out, t.int32, None, "shuffle_index", "out", n_list)
+        ip, cp = self._list_args(index, count, n_list, "shuffle_index")
         if index is not None:
             lo, hi = index.data_ptr(), index.data_ptr() + 4 * index.numel()
-            assert out.data_ptr() + 4 * out.numel() <= lo or hi <= out.data_ptr(), "shuffle_index: `out` overlaps `index`"
-        if epoch_dev is not None:
-            assert epoch_dev.is_cuda and epoch_dev.dtype == t.int32 and epoch_dev.numel() == 1
+            _need(out.data_ptr() + 4 * out.numel() <= lo or hi <= out.data_ptr(), "shuffle_index", "`out` overlaps `index`")
+        _opt(epoch_dev, t.int32, 1, "shuffle_index", "epoch_dev", None, False)
         self._follow_stream()
-        _chk(self.L.pgd_shuffle_index(self.h, ip, cp, n_list, int(seed), int(epoch), _p(epoch_dev) if epoch_dev is not None else None, _p(out)),
-             "pgd_shuffle_index")
+        _chk(self.L.pgd_shuffle_index(self.h, ip, cp, n_list, int(seed), int(epoch), _p(epoch_dev), _p(out)), "pgd_shuffle_index")
         return out
 
     def adam_gated(self, param, grad, m, v, step, lr, gate, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, lr_scale=None, kl=None,
@@ -718,18 +759,13 @@ class Engine:
         or None) is zeroed -- when gate[0] is set or `kl` (one float32 cuda, or None) is not <= kl_limit; else it applies adam's step with
         the learning rate lr * lr_scale[0] (`lr_scale`: one float32 cuda, or None) and counts it in gate[1].  Asynchronous."""
         t = self.torch
-        n = int(param.numel())
-        for x in (param, grad, m, v):
-            assert x.is_cuda and x.dtype == t.float32 and x.is_contiguous() and x.numel() == n
-        assert n >= 1 and step.is_cuda and step.dtype == t.int32 and step.is_contiguous() and step.numel() == 4
-        assert gate.is_cuda and gate.dtype == t.int32 and gate.is_contiguous() and gate.numel() == 4
-        for x in (lr_scale, kl):
-            assert x is None or (x.is_cuda and x.dtype == t.float32 and x.numel() >= 1 and x.data_ptr() % 4 == 0)
-        assert count_gate is None or (count_gate.is_cuda and count_gate.dtype == t.int32 and count_gate.numel() == 1)
+        a = self._adam_args("adam_gated", param, grad, m, v, step, lr, betas, eps, max_grad_norm)
+        _dev(gate, t.int32, 4, "adam_gated", "gate")
+        _opt(lr_scale, t.float32, None, "adam_gated", "lr_scale", 1, False, 4)
+        _opt(kl, t.float32, None, "adam_gated", "kl", 1, False, 4)
+        _opt(count_gate, t.int32, 1, "adam_gated", "count_gate", None, False)
         self._follow_stream()
-        opt = [_p(x) if x is not None else None for x in (lr_scale, kl, count_gate)]
-        _chk(self.L.pgd_adam_gated(self.h, _p(param), _p(grad), _p(m), _p(v), n, _p(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                   float(max_grad_norm), opt[0], opt[1], float(kl_limit), _p(gate), opt[2]), "pgd_adam_gated")
+        _chk(self.L.pgd_adam_gated(*a, _p(lr_scale), _p(kl), float(kl_limit), _p(gate), _p(count_gate)), "pgd_adam_gated")
         return param
 
     # -- safe RL behind a rollout: the cost side of the loop (include/pgdrive_hip.h states the formulas) ---------------------------
@@ -738,8 +774,8 @@ class Engine:
         """mlp_actor_critic with a cost critic beside actor and critic in the same launch (pgd_mlp_actor_critic_cost): `cost_weights` has
         the shapes of `value_weights` (both are required), `cost_value` [N, A] float32 cuda receives its output.  Every other argument,
         the noise and the tick rule as for mlp_actor_critic, whose bits `out`, `logp` and `value` are."""
-        a = self._ac_args(policy_weights, value_weights, cost_weights, out, (logp, value, cost_value), seed, tick, obs, group, deterministic, in_dim)
-        _chk(self.L.pgd_mlp_actor_critic_cost(*a, _p(out), _p(logp), _p(value), _p(cost_value)), "pgd_mlp_actor_critic_cost")
+        self._ac_call("mlp_actor_critic_cost", policy_weights, value_weights, cost_weights, out, (logp, value, cost_value), seed, tick, obs, group,
+                      deterministic, in_dim)
         return out, logp, value, cost_value
 
     def cost_gae(self, flags, done, cost_value, costs, gamma, lam, run, cost=None, adv=None, ret=None, ep_sum=None, ep_count=None):
@@ -748,13 +784,18 @@ class Engine:
         crash_vehicle, crash_object); `run` float32 [rows], read and written: the cost of every row's unfinished episode, carried from
         rollout to rollout.  Returns (cost, adv, ret, ep_sum, ep_count): the first three float32 of flags' shape, ep_sum float32 and
         ep_count int32 [rows] -- the episodes that finished in THIS rollout (each a buffer to write, allocated when None).  Asynchronous."""
+        return self._cost_gae("cost_gae", flags, done, cost_value, (), costs, gamma, lam, run, cost, adv, ret, ep_sum, ep_count)
+
+    def _cost_gae(self, fn, flags, done, cost_value, term, costs, gamma, lam, run, cost, adv, ret, ep_sum, ep_count):
+        """cost_gae and cost_gae_bootstrap (`term`: its table row for term_cost_value, or none)."""
         t = self.torch
-        T, rows, (flags, done, cost_value, cost, adv, ret, run, ep_sum, ep_count) = self._rollout_buffers(
-            flags, ((flags, t.int32, 0), (done, t.uint8, 0), (cost_value, t.float32, 1), (cost, t.float32, 0), (adv, t.float32, 0),
-                    (ret, t.float32, 0), (run, t.float32, None), (ep_sum, t.float32, None), (ep_count, t.int32, None)))
+        T, rows, (*ins, cost, adv, ret, run, ep_sum, ep_count) = self._rollout_buffers(
+            fn, (("flags", flags, t.int32, 0), ("done", done, t.uint8, 0), ("cost_value", cost_value, t.float32, 1), *term,
+                 ("cost", cost, t.float32, 0), ("adv", adv, t.float32, 0), ("ret", ret, t.float32, 0), ("run", run, t.float32, None),
+                 ("ep_sum", ep_sum, t.float32, None), ("ep_count", ep_count, t.int32, None)))
         c3 = (C.c_float * 3)(*[float(c) for c in costs])
-        _chk(self.L.pgd_cost_gae(self.h, _p(flags), _p(done), _p(cost_value), T, rows, c3, float(gamma), float(lam), _p(cost), _p(adv), _p(ret),
-                                 _p(run), _p(ep_sum), _p(ep_count)), "pgd_cost_gae")
+        _chk(getattr(self.L, "pgd_" + fn)(self.h, *map(_p, ins), T, rows, c3, float(gamma), float(lam), _p(cost), _p(adv), _p(ret), _p(run),
+                                          _p(ep_sum), _p(ep_count)), "pgd_" + fn)
         return cost, adv, ret, ep_sum, ep_count
 
     def lagrange(self, ep_sum, ep_count, state, cost_limit, lr, lambda_max=100.0):
@@ -764,12 +805,12 @@ class Engine:
         episode: unchanged.  Asynchronous."""
         t = self.torch
         rows = int(ep_sum.numel())
-        assert ep_sum.is_cuda and ep_sum.dtype == t.float32 and ep_sum.is_contiguous() and rows >= 1
-        assert ep_count.is_cuda and ep_count.dtype == t.int32 and ep_count.is_contiguous() and ep_count.numel() == rows
-        assert state.is_cuda and state.dtype == t.float32 and state.is_contiguous() and state.numel() == 4
+        _dev(ep_sum, t.float32, None, "lagrange", "ep_sum", 1)
+        _dev(ep_count, t.int32, rows, "lagrange", "ep_count")
+        _dev(state, t.float32, 4, "lagrange", "state")
         self._follow_stream()
-        _chk(self.L.pgd_lagrange(self.h, C.c_void_p(ep_sum.data_ptr()), C.c_void_p(ep_count.data_ptr()), rows, float(cost_limit), float(lr),
-                                 float(lambda_max), C.c_void_p(state.data_ptr())), "pgd_lagrange")
+        _chk(self.L.pgd_lagrange(self.h, _p(ep_sum), _p(ep_count), rows, float(cost_limit), float(lr), float(lambda_max), _p(state)),
+             "pgd_lagrange")
         return state
 
     def adv_mix(self, adv, cadv, state, out=None, adv_stats=None, cadv_stats=None):
@@ -779,16 +820,14 @@ class Engine:
         t = self.torch
         n = int(adv.numel())
         out = t.empty_like(adv) if out is None else out
-        for v in (adv, cadv, out):
-            assert v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == n
-        assert n >= 1 and state.is_cuda and state.dtype == t.float32 and state.is_contiguous() and state.numel() == 4
-        for v in (adv_stats, cadv_stats):
-            assert v is None or (v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == 2)
+        _need(n >= 1, "adv_mix", "adv: at least one element wanted")
+        for name, v in (("adv", adv), ("cadv", cadv), ("out", out)):
+            _dev(v, t.float32, n, "adv_mix", name)
+        _dev(state, t.float32, 4, "adv_mix", "state")
+        _opt(adv_stats, t.float32, 2, "adv_mix", "adv_stats")
+        _opt(cadv_stats, t.float32, 2, "adv_mix", "cadv_stats")
         self._follow_stream()
-        _chk(self.L.pgd_adv_mix(self.h, C.c_void_p(adv.data_ptr()), C.c_void_p(cadv.data_ptr()), n,
-                                C.c_void_p(adv_stats.data_ptr()) if adv_stats is not None else None,
-                                C.c_void_p(cadv_stats.data_ptr()) if cadv_stats is not None else None, C.c_void_p(state.data_ptr()),
-                                C.c_void_p(out.data_ptr())), "pgd_adv_mix")
+        _chk(self.L.pgd_adv_mix(self.h, _p(adv), _p(cadv), n, _p(adv_stats), _p(cadv_stats), _p(state), _p(out)), "pgd_adv_mix")
         return out
 
     def ppo_cost_work_bytes(self, in_dim, rows):
@@ -804,9 +843,9 @@ class Engine:
         `stats` float32 cuda [8] (_abi.PPO_COST_STATS: entry 7 is the cost critic's loss); `work` a cuda tensor of at least
         ppo_cost_work_bytes(in_dim, rows) bytes.  Every other argument as for ppo_grad, whose bits the actor's and the critic's
         gradients and stats[0..6] are.  Asynchronous."""
-        nets, cnet, b, grads, cgrads = self._ppo_batch((policy_weights, value_weights, cost_weights), (policy_grads, value_grads, cost_grads), obs,
-                                                       actions, logp_old, adv, ret, cost_ret, stats, work, start, stride, rows, index, count, n_list,
-                                                       adv_stats, in_dim)
+        nets, cnet, b, grads, cgrads = self._ppo_batch("ppo_grad_cost", (policy_weights, value_weights, cost_weights),
+                                                       (policy_grads, value_grads, cost_grads), obs, actions, logp_old, adv, ret, cost_ret, stats,
+                                                       work, start, stride, rows, index, count, n_list, adv_stats, in_dim)
         hp = _abi.PPOHyper(float(clip), float(vf_coef), float(ent_coef))
         pc = _abi.PPOCost(cost_ret.data_ptr(), float(cvf_coef))
         _chk(self.L.pgd_ppo_grad_cost(self.h, C.byref(nets), C.byref(cnet), C.byref(b), C.byref(pc), C.byref(hp), C.byref(grads), C.byref(cgrads),
@@ -823,48 +862,33 @@ class Engine:
         Asynchronous."""
         t = self.torch
         rows = self.N * self.A
-        o2 = term_obs.view(-1, term_obs.shape[-1])
-        assert o2.is_cuda and o2.dtype == t.float32 and o2.stride(1) == 1 and o2.shape[0] == rows
-        assert flags.is_cuda and flags.dtype == t.int32 and flags.is_contiguous() and flags.numel() == rows
-        assert done.is_cuda and done.dtype == t.uint8 and done.is_contiguous() and done.numel() == rows
-        assert (cost_weights is None) == (term_cost_value is None), "term_cost_value comes with the cost critic"
-        for v in (term_value, term_cost_value):
-            assert v is None or (v.is_cuda and v.dtype == t.float32 and v.is_contiguous() and v.numel() == rows)
         k = int(in_dim if in_dim is not None else value_weights[0].shape[0])
-        assert k <= o2.shape[1]
-        critic = self._value_net(_abi.ValueNet(), value_weights, k)
-        cost = None if cost_weights is None else C.byref(self._value_net(_abi.ValueNet(), cost_weights, k))
+        o2, stride = self._obs_rows(term_obs, rows, k, "mlp_terminal_value", "term_obs")
+        _dev(flags, t.int32, rows, "mlp_terminal_value", "flags")
+        _dev(done, t.uint8, rows, "mlp_terminal_value", "done")
+        _need((cost_weights is None) == (term_cost_value is None), "mlp_terminal_value", "term_cost_value comes with the cost critic")
+        _dev(term_value, t.float32, rows, "mlp_terminal_value", "term_value")
+        _opt(term_cost_value, t.float32, rows, "mlp_terminal_value", "term_cost_value")
+        critic = self._value_net(_abi.ValueNet(), value_weights, k, "mlp_terminal_value", "value_weights")
+        cost = None if cost_weights is None else C.byref(self._value_net(_abi.ValueNet(), cost_weights, k, "mlp_terminal_value", "cost_weights"))
         if group < 0:
             self._follow_stream()
-        _chk(self.L.pgd_mlp_terminal_value(self.h, int(group), _p(o2), int(o2.stride(0)), k, C.byref(critic), cost, _p(flags), _p(done),
-                                           _p(term_value), _p(term_cost_value) if term_cost_value is not None else None),
-             "pgd_mlp_terminal_value")
+        _chk(self.L.pgd_mlp_terminal_value(self.h, int(group), _p(o2), stride, k, C.byref(critic), cost, _p(flags), _p(done), _p(term_value),
+                                           _p(term_cost_value)), "pgd_mlp_terminal_value")
         return term_value, term_cost_value
 
     def gae_bootstrap(self, reward, value, done, term_value, gamma, lam, adv=None, ret=None):
         """gae with the one-step target of a done row taken from `term_value` [T, rows...] (pgd_gae_bootstrap): the critic's value of the
         terminal observation where the episode was truncated, 0 where it terminated, as mlp_terminal_value writes it.  Every other
         argument and the result as for gae."""
-        t = self.torch
-        T, rows, (reward, value, done, term_value, adv, ret) = self._rollout_buffers(
-            reward, ((reward, t.float32, 0), (value, t.float32, 1), (done, t.uint8, 0), (term_value, t.float32, 0), (adv, t.float32, 0),
-                     (ret, t.float32, 0)))
-        _chk(self.L.pgd_gae_bootstrap(self.h, _p(reward), _p(value), _p(done), _p(term_value), T, rows, float(gamma), float(lam), _p(adv), _p(ret)),
-             "pgd_gae_bootstrap")
-        return adv, ret
+        return self._gae("gae_bootstrap", reward, value, done, (("term_value", term_value, self.torch.float32, 0), ), gamma, lam, adv, ret)
 
     def cost_gae_bootstrap(self, flags, done, cost_value, term_cost_value, costs, gamma, lam, run, cost=None, adv=None, ret=None, ep_sum=None,
                            ep_count=None):
         """cost_gae with the one-step target of a done row taken from `term_cost_value` [T, rows...] (pgd_cost_gae_bootstrap); the costs
         and the books of episode costs are cost_gae's.  Every other argument and the result as for cost_gae."""
-        t = self.torch
-        T, rows, (flags, done, cost_value, term_cost_value, cost, adv, ret, run, ep_sum, ep_count) = self._rollout_buffers(
-            flags, ((flags, t.int32, 0), (done, t.uint8, 0), (cost_value, t.float32, 1), (term_cost_value, t.float32, 0), (cost, t.float32, 0),
-                    (adv, t.float32, 0), (ret, t.float32, 0), (run, t.float32, None), (ep_sum, t.float32, None), (ep_count, t.int32, None)))
-        c3 = (C.c_float * 3)(*[float(c) for c in costs])
-        _chk(self.L.pgd_cost_gae_bootstrap(self.h, _p(flags), _p(done), _p(cost_value), _p(term_cost_value), T, rows, c3, float(gamma), float(lam),
-                                           _p(cost), _p(adv), _p(ret), _p(run), _p(ep_sum), _p(ep_count)), "pgd_cost_gae_bootstrap")
-        return cost, adv, ret, ep_sum, ep_count
+        return self._cost_gae("cost_gae_bootstrap", flags, done, cost_value, (("term_cost_value", term_cost_value, self.torch.float32, 0), ), costs,
+                              gamma, lam, run, cost, adv, ret, ep_sum, ep_count)
 
     # -- reward scaling by the running return, in front of GAE (include/pgdrive_hip.h states the rule) -------------------------------------
     def return_norm_work_bytes(self, rows):
@@ -889,17 +913,13 @@ class Engine:
         reward's shape (`out`: the buffer to write).  `work`: a cuda tensor of at least return_norm_work_bytes(rows) bytes, allocated when
         None.  Three launches (freeze: one), asynchronous on the caller's current stream."""
         t = self.torch
-        T, rows, (reward, done, out, carry) = self._rollout_buffers(
-            reward, ((reward, t.float32, 0), (done, t.uint8, 0), (out, t.float32, 0), (carry, t.float32, None)))
-        assert flags is None or (flags.is_cuda and flags.dtype == t.int32 and flags.is_contiguous() and flags.numel() == T * rows)
-        assert record.is_cuda and record.dtype == t.float64 and record.is_contiguous() and record.numel() == 4
-        need = self.return_norm_work_bytes(rows)
-        if work is None:
-            work = t.empty(((need + 7) // 8, ), dtype=t.float64, device=reward.device)
-        assert work.is_cuda and work.is_contiguous()
-        _chk(self.L.pgd_return_norm(self.h, _p(reward), _p(done), _p(flags) if flags is not None else None, T, rows, float(gamma), float(eps),
-                                    float(clip), _abi.RN_FREEZE if freeze else 0, _p(carry), _p(record), _p(out), _p(work),
-                                    work.numel() * work.element_size()), "pgd_return_norm")
+        T, rows, (reward, done, out, carry) = self._rollout_buffers("return_norm", (
+            ("reward", reward, t.float32, 0), ("done", done, t.uint8, 0), ("out", out, t.float32, 0), ("carry", carry, t.float32, None)))
+        _opt(flags, t.int32, T * rows, "return_norm", "flags")
+        _dev(record, t.float64, 4, "return_norm", "record")
+        work, n_bytes = self._scratch(work, self.return_norm_work_bytes(rows), reward.device, "return_norm")
+        _chk(self.L.pgd_return_norm(self.h, _p(reward), _p(done), _p(flags), T, rows, float(gamma), float(eps), float(clip),
+                                    _abi.RN_FREEZE if freeze else 0, _p(carry), _p(record), _p(out), _p(work), n_bytes), "pgd_return_norm")
         return out
 
     # -- observation normalisation, fused into the training kernels' row loads (include/pgdrive_hip.h states the rule) -------------------
@@ -925,19 +945,17 @@ class Engine:
         of `index`).  `work`: a cuda tensor of at least obs_norm_work_bytes(in_dim, n_list) bytes, allocated when None.  Two launches,
         asynchronous on the caller's current stream.  Returns `record`."""
         t = self.torch
-        assert obs.is_cuda and obs.dtype == t.float32 and obs.is_contiguous()
+        _dev(obs, t.float32, None, "obs_norm_update", "obs")
         stride = int(obs.shape[-1])
         in_dim = stride if in_dim is None else int(in_dim)
         n_rows = obs.numel() // stride
         n_list = int((index.numel() if index is not None else n_rows) if n_list is None else n_list)
-        assert record.is_cuda and record.dtype == t.float64 and record.is_contiguous() and record.numel() == 1 + 2 * in_dim
-        ip, cp = self._list_args(index, count, n_list)
-        if work is None:
-            work = t.empty(((self.obs_norm_work_bytes(in_dim, n_list) + 7) // 8, ), dtype=t.float64, device=obs.device)
-        assert work.is_cuda and work.is_contiguous()
+        _dev(record, t.float64, 1 + 2 * in_dim, "obs_norm_update", "record")
+        ip, cp = self._list_args(index, count, n_list, "obs_norm_update")
+        work, n_bytes = self._scratch(work, self.obs_norm_work_bytes(in_dim, n_list), obs.device, "obs_norm_update")
         self._follow_stream()
-        _chk(self.L.pgd_obs_norm_update(self.h, _p(obs), stride, in_dim, n_rows, ip, cp, n_list, _p(record), _p(work),
-                                        work.numel() * work.element_size()), "pgd_obs_norm_update")
+        _chk(self.L.pgd_obs_norm_update(self.h, _p(obs), stride, in_dim, n_rows, ip, cp, n_list, _p(record), _p(work), n_bytes),
+             "pgd_obs_norm_update")
         return record
 
     def obs_norm_publish(self, record, table, eps=1e-8):
@@ -945,8 +963,8 @@ class Engine:
         empty; pgd_obs_norm_publish).  One small launch, asynchronous.  Returns `table`."""
         t = self.torch
         in_dim = (record.numel() - 1) // 2
-        assert record.is_cuda and record.dtype == t.float64 and record.is_contiguous() and record.numel() == 1 + 2 * in_dim
-        assert table.is_cuda and table.dtype == t.float32 and table.is_contiguous() and table.numel() == 2 * ((in_dim + 3) & ~3)
+        _dev(record, t.float64, 1 + 2 * in_dim, "obs_norm_publish", "record")
+        _dev(table, t.float32, 2 * ((in_dim + 3) & ~3), "obs_norm_publish", "table")
         self._follow_stream()
         _chk(self.L.pgd_obs_norm_publish(self.h, _p(record), in_dim, float(eps), _p(table)), "pgd_obs_norm_publish")
         return table
@@ -960,7 +978,7 @@ class Engine:
             _chk(self.L.pgd_obs_norm_bind(self.h, None, 0, 0.0), "pgd_obs_norm_bind")
         else:
             in_dim = self.D if in_dim is None else int(in_dim)
-            assert table.is_cuda and table.dtype == self.torch.float32 and table.is_contiguous() and table.numel() == 2 * ((in_dim + 3) & ~3)
+            _dev(table, self.torch.float32, 2 * ((in_dim + 3) & ~3), "obs_norm_bind", "table")
             _chk(self.L.pgd_obs_norm_bind(self.h, _p(table), in_dim, float(clip)), "pgd_obs_norm_bind")
         self._obs_norm_table = table
 
@@ -988,20 +1006,19 @@ class Engine:
         length at the entry where it ended, 0 everywhere else.  `work`: a cuda tensor of at least rollout_episodes_work_bytes(rows) bytes,
         allocated when None.  Two launches, asynchronous on the caller's current stream.  Returns (record, call)."""
         t = self.torch
-        assert not any(x is None for x in (reward, done, flags, ret_carry, len_carry))
+        where = "rollout_episodes"
+        _need(not any(x is None for x in (reward, done, flags, ret_carry, len_carry)), where, "reward, done, flags and both carries wanted")
         T, rows, (reward, done, flags, ret_carry, len_carry) = self._rollout_buffers(
-            reward, ((reward, t.float32, 0), (done, t.uint8, 0), (flags, t.int32, 0), (ret_carry, t.float32, None), (len_carry, t.int32, None)))
-        for rec in (record, call):
-            assert rec is None or (rec.is_cuda and rec.dtype == t.float64 and rec.is_contiguous() and rec.numel() == len(_abi.ROLLOUT_EPISODES))
-        for dense, dt in ((ep_return, t.float32), (ep_length, t.int32)):
-            assert dense is None or (dense.is_cuda and dense.dtype == dt and dense.is_contiguous() and dense.numel() == T * rows)
-        if work is None:
-            work = t.empty(((self.rollout_episodes_work_bytes(rows) + 7) // 8, ), dtype=t.float64, device=reward.device)
-        assert work.is_cuda and work.is_contiguous()
-        opt = lambda x: _p(x) if x is not None else None
+            where, (("reward", reward, t.float32, 0), ("done", done, t.uint8, 0), ("flags", flags, t.int32, 0),
+                    ("ret_carry", ret_carry, t.float32, None), ("len_carry", len_carry, t.int32, None)))
+        _opt(record, t.float64, len(_abi.ROLLOUT_EPISODES), where, "record")
+        _opt(call, t.float64, len(_abi.ROLLOUT_EPISODES), where, "call")
+        _opt(ep_return, t.float32, T * rows, where, "ep_return")
+        _opt(ep_length, t.int32, T * rows, where, "ep_length")
+        work, n_bytes = self._scratch(work, self.rollout_episodes_work_bytes(rows), reward.device, where)
         _chk(self.L.pgd_rollout_episodes(self.h, _p(reward), _p(done), _p(flags), T, rows, _abi.EP_SEATS if seats else 0, _p(ret_carry),
-                                         _p(len_carry), opt(record), opt(call), opt(ep_return), opt(ep_length), _p(work),
-                                         work.numel() * work.element_size()), "pgd_rollout_episodes")
+                                         _p(len_carry), _p(record), _p(call), _p(ep_return), _p(ep_length), _p(work), n_bytes),
+             "pgd_rollout_episodes")
         return record, call
 
     def step_lane_keep(self, tick, k_lat=1.0, k_head=2.0, v_target_kmh=30.0, noise=0.05):
@@ -1026,13 +1043,12 @@ class Engine:
     def observe_topdown(self, out=None):
         """Image [N, R, R, C] of the present state -- float32 in [0, 1], or bytes in [0, 255] when the buffer (`out`, else the engine's
         own) is a uint8 tensor; call once after every step / reset (it advances the frame history)."""
-        img = self.img if out is None else out
-        assert img.is_cuda and img.is_contiguous() and img.dtype in (self.torch.float32, self.torch.uint8) and img.numel() == self.img.numel()
+        img = self.img if out is None else _dev(out, (self.torch.float32, self.torch.uint8), self.img.numel(), "observe_topdown", "out")
         self._follow_stream()
         if img.dtype == self.torch.uint8:
-            _chk(self.L.pgd_observe_topdown_u8(self.h, C.c_void_p(img.data_ptr())), "pgd_observe_topdown_u8")
+            _chk(self.L.pgd_observe_topdown_u8(self.h, _p(img)), "pgd_observe_topdown_u8")
         else:
-            _chk(self.L.pgd_observe_topdown(self.h, C.c_void_p(img.data_ptr())), "pgd_observe_topdown")
+            _chk(self.L.pgd_observe_topdown(self.h, _p(img)), "pgd_observe_topdown")
         return img
 
     # -- step info on the device (pgd_step_info: terminal observation, the reference's info floats, episode statistics) ---------------
@@ -1087,7 +1103,7 @@ class Engine:
             cfg = render.make_config(render.parse_kwargs("top_down", cfg or {}))
         render.check_capacity(cfg.num_stack, self.V)
         geom = np.array([render.film_geometry(d, cfg.film_w, cfg.film_h) for d in self.bank.descs], dtype=np.float64)
-        assert len(geom) == len(self.bank.maps)
+        _need(len(geom) == len(self.bank.maps), "enable_render", "one film geometry per map wanted")
         self.render_cfg = cfg
         self.film_geom = geom
         _chk(self.L.pgd_render_enable(self.h, C.byref(cfg), _np_p(np.ascontiguousarray(geom))), "pgd_render_enable")
@@ -1099,11 +1115,10 @@ class Engine:
         ids = None if env_ids is None else np.ascontiguousarray(np.asarray(env_ids, dtype=np.int64).reshape(-1), dtype=np.int32)
         n = self.N if ids is None else len(ids)
         shape = (n, self.render_cfg.film_h, self.render_cfg.film_w, 3)
-        if out is None:
-            out = t.empty(shape, dtype=t.uint8, device=self.device)
-        assert out.is_cuda and out.dtype == t.uint8 and out.is_contiguous() and tuple(out.shape) == shape
+        out = _dev(t.empty(shape, dtype=t.uint8, device=self.device) if out is None else out, t.uint8, None, "render_topdown", "out")
+        _need(tuple(out.shape) == shape, "render_topdown", "out: shape %s wanted, got %s" % (shape, tuple(out.shape)))
         self._follow_stream()
-        _chk(self.L.pgd_render_topdown(self.h, _np_p(ids), n, C.c_void_p(out.data_ptr())), "pgd_render_topdown")
+        _chk(self.L.pgd_render_topdown(self.h, _np_p(ids), n, _p(out)), "pgd_render_topdown")
         return out
 
     def render_palette(self):
@@ -1131,9 +1146,9 @@ class Engine:
     def step_group(self, g, actions):
         """Step only the envs of group g, asynchronously on the group's stream; `actions` is the full [N, A, 2] tensor.
         Returns views of the group's rows of the engine's output buffers."""
-        self._check_actions(actions)
+        self._check_actions(actions, "step_group")
         p_obs, p_rew, p_done, p_flags = self._own_ptrs
-        _chk(self.L.pgd_step_group(self.h, int(g), C.c_void_p(actions.data_ptr()), p_obs, p_rew, p_done, p_flags), "pgd_step_group")
+        _chk(self.L.pgd_step_group(self.h, int(g), _p(actions), p_obs, p_rew, p_done, p_flags), "pgd_step_group")
         sl = self.group_slice(g)
         return self.obs[sl], self.reward[sl], self.done[sl], self.flags[sl]
 
@@ -1141,7 +1156,7 @@ class Engine:
         _chk(self.L.pgd_group_sync(self.h, int(g)), "pgd_group_sync")
 
     def observe(self):
-        _chk(self.L.pgd_observe(self.h, C.c_void_p(self.obs.data_ptr())), "pgd_observe")
+        _chk(self.L.pgd_observe(self.h, _p(self.obs)), "pgd_observe")
         self.sync()
         return self.obs
 
@@ -1176,7 +1191,7 @@ class Engine:
         f = np.ascontiguousarray(f, dtype=np.float32)
         i = np.ascontiguousarray(i, dtype=np.int32)
         ei = np.ascontiguousarray(ei, dtype=np.int32)
-        assert f.shape == (_abi.NF, self.N, self.V) and i.shape == (_abi.NI, self.N, self.V)
+        _need(f.shape == (_abi.NF, self.N, self.V) and i.shape == (_abi.NI, self.N, self.V), "set_state", "f [NF, N, V] and i [NI, N, V] wanted")
         _chk(self.L.pgd_set_state(self.h, _np_p(f), _np_p(i), _np_p(ei)), "pgd_set_state")
 
     def close(self):
