@@ -559,6 +559,58 @@ typedef struct pgd_ppo_grads {                        /* device buffers of the w
 size_t pgd_ppo_work_bytes(int in_dim, int rows, int has_critic);
 int pgd_ppo_grad(pgd_handle h, const pgd_actor_critic* nets, const pgd_ppo_batch* batch, const pgd_ppo_hyper* hyper,
                  const pgd_ppo_grads* grads, float* d_stats /*[8]*/, void* d_work, size_t work_bytes);
+/* ---- The categorical head: two independent categorical distributions over the same networks ------------------------------------------
+ * (No reference counterpart: the reference's env offers MultiDiscrete([discrete_steering_dim, discrete_throttle_dim]) with
+ * discrete_action=True and leaves the distribution to an RL library; this is SB3's MultiCategorical factorisation.)
+ * The networks are pgd_mlp_actor_critic's -- layout, alignment, hidden 256, tanh, the critic, in_dim 4 .. 416 -- with another actor head:
+ * steering with ks bins and throttle with kt bins, 2 <= ks, kt and K = ks + kt <= 16 (PGD_ERR_ARG otherwise).
+ * Layout: w3 [256][out_cols], b3 [out_cols], out_cols >= K (PGD_ERR_ARG below); columns 0 .. ks - 1 are the steering logits, columns
+ * ks .. K - 1 the throttle logits, columns at or beyond K are never read.
+ * Logits: fp32; the 256-term product on the f32 matrix cores as one 16-column tile, k split over the workgroup's four waves: wave w forms
+ * the k-ordered fma chain over k = 64 w .. 64 w + 63 from zero, logit = ((P0 + P1) + P2) + P3 + b3.  The head's weights are read from
+ * global memory, not staged: the workgroup's LDS is pgd_mlp_actor_critic's.
+ * Per head (fp32 logits l_j, j < K_head):  m = max_j l_j;  lse = m + log(sum_j exp(l_j - m));  logp_j = l_j - lse;  p_j = exp(logp_j)
+ * (max and sums in index order).  As compiled: the forward launch's exp and log are fp32 `expf` / `logf` under the library's build flags, i.e.
+ * the approximate forms (v_exp_f32 / v_log_f32 with the input or output scaled, about 1 ulp of the instruction plus the scaling's rounding);
+ * pgd_ppo_grad_cat works in double and forms p_j as exp(l_j - m) / sum_k exp(l_k - m), the same number as exp(logp_j) to a few 2^-53.
+ * Sampling: u_s = unit(r1), u_t = unit(r2) with r1, r2, unit() and g exactly pgd_mlp_actor_critic's two draws (same seed ^ 0xac7012c1,
+ * global row, stream, tick and tick ^ 0x80000000, the device counter of pgd_actor_critic_tick included).  c_j = p_0 + ... + p_j, summed
+ * in fp32 in index order; the index is the number of j in [0, K_head - 1) with c_j <= u -- it cannot leave the head whatever the last
+ * partial sum rounds to.  logp = logp_s[i_s] + logp_t[i_t].
+ * PGD_AC_DETERMINISTIC: the index is the argmax, the lowest index among equal logits; logp is that of the argmax.
+ * Outputs per row: d_action_index int32 [rows][2] (i_s, i_t); d_logp, d_value as pgd_mlp_actor_critic (d_value bit for bit its value on
+ * the same inputs); d_actions float [rows][2], the buffer pgd_step reads:
+ *   default            the grid value (float) i * (2.0f / (float) (K_head - 1)) - 1.0f -- one multiplication, then one subtraction, the
+ *                      quotient correctly rounded: pgd_step's own conversion of a discrete action -- for an engine with continuous actions
+ *   PGD_AC_EMIT_INDEX  the index as a float, for an engine with discrete_action set
+ * pgd_mlp_actor_critic_cat_rows is to pgd_mlp_actor_critic_cat what pgd_mlp_actor_critic_rows is to pgd_mlp_actor_critic: a listed row
+ * gets bit for bit what the full launch gives it; rows of the range that are not listed get action 0, 0, index 0, 0, logp 0 and (with a
+ * critic) value 0 from a clearing launch in front; the host never reads *d_count.  A bound observation table (pgd_obs_norm_bind) is
+ * applied by all three calls of this section as by their Gaussian namesakes.
+ *
+ * pgd_ppo_grad_cat: pgd_ppo_grad with this head.  Every argument, the minibatch rule, the critic, d_stats' slots, n = 0, what may hold
+ * NaN, the determinism and the capture rule are pgd_ppo_grad's; batch->action is not read (and may be null); d_action_index is the
+ * rollout's [n_rows][2].  A live row's index outside its head is a caller's error: it is held within [0, K_head) and never followed
+ * outside an array.  Per live row, with i the taken index of a head:
+ *   logp = logp_s[i_s] + logp_t[i_t];   r, the clipped surrogate, the cut rule, A, L_v, 1 / n: pgd_ppo_grad's
+ *   H = H_s + H_t,  H_head = -sum_j p_j logp_j              (d_stats[3] = mean H;  d_stats[4] = mean (logp_old - logp))
+ *   dlogp/dl_j = [j == i] - p_j;   dH_head/dl_j = -p_j (logp_j + H_head)
+ *   dL/dl_j = dL/dlogp ([j == i] - p_j) + ent_coef p_j (logp_j + H_head) / n
+ * formed in double from the fp32 logits (logp_j, p_j and H_head included; sums over a head in index order) and rounded to fp32 once.
+ * Head columns at or beyond K of dW3 / db3 are written as zero.  Scratch: the caller's, 16-byte aligned, work_bytes >=
+ * pgd_ppo_cat_work_bytes(in_dim, rows, has_critic) (0: the call refuses the shape; never below pgd_ppo_work_bytes: dOut is [rows][16]
+ * here).  Five launches (six with out_cols > K), asynchronous on the engine's stream, capturable from the first call. */
+#define PGD_AC_EMIT_INDEX 2u
+int pgd_mlp_actor_critic_cat(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets,
+                             int32_t ks, int32_t kt, uint32_t seed, uint32_t tick, uint32_t flags, float* d_actions /*[rows][2]*/,
+                             int32_t* d_action_index /*[rows][2]*/, float* d_logp /*[rows]*/, float* d_value /*[rows], may be null without critic*/);
+int pgd_mlp_actor_critic_cat_rows(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets,
+                                  int32_t ks, int32_t kt, uint32_t seed, uint32_t tick, uint32_t flags, const int32_t* d_rows,
+                                  const int32_t* d_count, float* d_actions, int32_t* d_action_index, float* d_logp, float* d_value);
+size_t pgd_ppo_cat_work_bytes(int in_dim, int rows, int has_critic);
+int pgd_ppo_grad_cat(pgd_handle h, const pgd_actor_critic* nets, const pgd_ppo_batch* batch, const pgd_ppo_hyper* hyper,
+                     const pgd_ppo_grads* grads, int32_t ks, int32_t kt, const int32_t* d_action_index /*[n_rows][2]*/,
+                     float* d_stats /*[8]*/, void* d_work, size_t work_bytes);
 /* Population mean and 1 / (std + 1e-8) of adv over the live entries of a list -- adv[index[q]] (index null: adv[q]) for q < count, the
  * count as for pgd_ppo_grad -- into two device floats.  One workgroup, a fixed summation order: deterministic.  n = 0: (0, 1).
  * Entries that are not listed may hold NaN.  The call is not told how long d_adv is: every index entry below the count must be a valid

@@ -49,6 +49,20 @@ class ActorCritic(C.Structure):
 
 
 AC_DETERMINISTIC = 1
+AC_EMIT_INDEX = 2  # PGD_AC_EMIT_INDEX: the categorical head writes the index, not the grid value, into the action buffer
+CAT_COLS = 16  # the categorical head's tile: ks + kt <= 16
+
+
+def cat_bins(bins, where):
+    """`bins` = (ks, kt) of the categorical head checked (ValueError) -> two ints: 2 <= ks, kt and ks + kt <= 16.  No device needed."""
+    try:
+        ks, kt = bins
+        ok = int(ks) == ks and int(kt) == kt and not isinstance(ks, bool) and not isinstance(kt, bool)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or ks < 2 or kt < 2 or ks + kt > CAT_COLS:
+        raise ValueError("%s: bins = %r: (steering, throttle) with 2 <= each and steering + throttle <= %d wanted" % (where, bins, CAT_COLS))
+    return int(ks), int(kt)
 
 
 class GuardianConfig(C.Structure):

@@ -175,28 +175,49 @@ __global__ __launch_bounds__(256) void k_ppo_stats_cost(const pgd_ppo_batch b, c
   ppo_stats_block(b, gr, 1, cost_b3, work, stats);
 }
 
-// ---- the one body of pgd_ppo_grad (cost_net, cost, cost_grads null) and pgd_ppo_grad_cost: one, two or three networks -------------------
-static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
-                           const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
-                           float* d_stats, void* d_work, size_t work_bytes) {
-  bool critic;
+// ---- what every pgd_ppo_grad* call shares on the host: the argument check, the scratch's plan and the observation binding ---------------
+// Checked before any HIP call: the pointers, the networks and their gradient buffers (nets_ok, grads_ok), the minibatch rule, the LDS of
+// the rows kernel (`lds`) and the scratch (`work_of`: ppo_work, or the categorical head's ppo_cat_work).  reads_action: the call reads
+// batch->action (the Gaussian head; the categorical head reads its index array instead).  The binding of the family (pgd_obs_norm_bind)
+// is resolved here for every entry point: `bound` chooses the NORM instantiations of the two launches that read observation rows.
+struct PpoPlan { bool critic, bound; int n_nets, out_cols; PpoWork wk; ObsNorm nm; };
+static int ppo_grad_plan(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch, bool reads_action,
+                         const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
+                         const float* d_stats, const void* d_work, size_t work_bytes, size_t lds, PpoWork (*work_of)(int, int, int), PpoPlan& p) {
   if (!h || !batch || !hyper || !d_stats || !d_work || (reinterpret_cast<uintptr_t>(d_work) & 15u) != 0u) return PGD_ERR_ARG;
   const pgd_ppo_batch& b = *batch;
-  if (!nets_ok(nets, cost_net, !cost_net, b.in_dim, b.obs_stride, &critic) || !grads_ok(grads, cost_grads, critic)) return PGD_ERR_ARG;
-  if (!b.obs || !b.action || !b.logp_old || !b.adv || (critic && !b.ret) || (cost && !cost->cost_ret)) return PGD_ERR_ARG;
-  const size_t lds = ppo_lds_bytes(b.in_dim);
+  if (!nets_ok(nets, cost_net, !cost_net, b.in_dim, b.obs_stride, &p.critic) || !grads_ok(grads, cost_grads, p.critic)) return PGD_ERR_ARG;
+  if (!b.obs || (reads_action && !b.action) || !b.logp_old || !b.adv || (p.critic && !b.ret) || (cost && !cost->cost_ret)) return PGD_ERR_ARG;
   if (lds > 65536) return PGD_ERR_ARG;
   if (b.rows < 1 || b.rows > PGD_PPO_ROWS_MAX || b.n_list < 0 || b.n_rows < 1 || b.start < 0 || b.stride < 1) return PGD_ERR_ARG;
   if ((long long)b.start + (long long)(b.rows - 1) * b.stride > 2147483647ll) return PGD_ERR_ARG;
   if (!b.index && b.n_list > b.n_rows) return PGD_ERR_ARG;  // (without an index a list position IS a row)
-  const int n_nets = cost_net ? 3 : (critic ? 2 : 1), out_cols = (int)nets->out_cols;
-  const PpoWork wk = ppo_work(b.in_dim, b.rows, n_nets);
-  if (work_bytes < sizeof(float) * wk.total) return PGD_ERR_ARG;
-  // the observation binding of the family (pgd_obs_norm_bind), resolved here for both entry points: the NORM instantiations of the two
-  // launches that read observation rows
-  const bool bound = h->obs_norm.table != nullptr;
-  if (bound && b.in_dim != h->obs_norm.in_dim) return PGD_ERR_ARG;
-  const ObsNorm nm = {h->obs_norm.table, h->obs_norm.clip};
+  p.n_nets = cost_net ? 3 : (p.critic ? 2 : 1);
+  p.out_cols = (int)nets->out_cols;
+  p.wk = work_of(b.in_dim, b.rows, p.n_nets);
+  if (work_bytes < sizeof(float) * p.wk.total) return PGD_ERR_ARG;
+  p.bound = h->obs_norm.table != nullptr;
+  if (p.bound && b.in_dim != h->obs_norm.in_dim) return PGD_ERR_ARG;
+  p.nm = ObsNorm{h->obs_norm.table, h->obs_norm.clip};
+  return PGD_OK;
+}
+// head columns [16, out_cols) of dW3 and [4, out_cols) of db3: zero (behind the reduction, in front of the statistics launch that writes db3)
+static void ppo_zero_head_launch(hipStream_t s, const pgd_ppo_grads* grads, int out_cols) {
+  hipLaunchKernelGGL(k_ppo_zero_head, dim3(std::max(1, std::min(out_cols - 16, 64))), dim3(MLP_H), 0, s, grads->w3, grads->b3, out_cols);
+}
+
+// ---- the one body of pgd_ppo_grad (cost_net, cost, cost_grads null) and pgd_ppo_grad_cost: one, two or three networks -------------------
+static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
+                           const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
+                           float* d_stats, void* d_work, size_t work_bytes) {
+  PpoPlan p;
+  const size_t lds = batch ? ppo_lds_bytes(batch->in_dim) : 0;
+  { int rc = ppo_grad_plan(h, nets, cost_net, batch, true, cost, hyper, grads, cost_grads, d_stats, d_work, work_bytes, lds, ppo_work, p); if (rc) return rc; }
+  const pgd_ppo_batch& b = *batch;
+  const bool bound = p.bound, critic = p.critic;
+  const int n_nets = p.n_nets, out_cols = p.out_cols;
+  const PpoWork wk = p.wk;
+  const ObsNorm nm = p.nm;
   const auto rows_cost = bound ? k_ppo_rows_cost<true> : k_ppo_rows_cost<false>;
   const auto rows_plain = bound ? k_ppo_rows<true> : k_ppo_rows<false>;
   const auto wgrad = bound ? k_ppo_wgrad<true> : k_ppo_wgrad<false>;
@@ -222,8 +243,7 @@ static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd
   } else {
     hipLaunchKernelGGL(k_ppo_reduce, reduce, dim3(MLP_H), 0, s, b, *grads, out_cols, work);
   }
-  if (out_cols > 4)
-    hipLaunchKernelGGL(k_ppo_zero_head, dim3(std::max(1, std::min(out_cols - 16, 64))), dim3(MLP_H), 0, s, grads->w3, grads->b3, out_cols);
+  if (out_cols > 4) ppo_zero_head_launch(s, grads, out_cols);
   if (cost_net) hipLaunchKernelGGL(k_ppo_stats_cost, dim3(1), dim3(256), 0, s, b, *grads, cost_grads->b3, work, d_stats);
   else hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, b, *grads, critic ? 1 : 0, work, d_stats);
   HIPCHK(hipGetLastError());

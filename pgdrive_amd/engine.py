@@ -42,6 +42,14 @@ _SIGS = {
     "pgd_rollout_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pgd_mlp_actor_critic_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ActorCritic), C.c_uint32, C.c_uint32,
                                             C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgd_mlp_actor_critic_cat": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ActorCritic), C.c_int32, C.c_int32,
+                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgd_mlp_actor_critic_cat_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ActorCritic), C.c_int32, C.c_int32,
+                                                C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
+    "pgd_ppo_cat_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "pgd_ppo_grad_cat": (C.c_int, [C.c_void_p, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.PPOBatch), C.POINTER(_abi.PPOHyper),
+                                   C.POINTER(_abi.PPOGrads), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "pgd_gae_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "pgd_ppo_work_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
@@ -468,10 +476,11 @@ class Engine:
         st.w1, st.b1, st.w2, st.b2, st.w3, st.b3 = self._network(weights, k, 1, where, name, 1)
         return st
 
-    def _ac_call(self, where, policy_weights, value_weights, cost_weights, out, per_row, seed, tick, obs, group, deterministic, in_dim, row_list=()):
-        """The mlp_actor_critic* call pgd_<where>: what the three share, checked -- the observation rows, `out`, the `per_row` outputs (logp,
+    def _ac_call(self, where, policy_weights, value_weights, cost_weights, out, per_row, seed, tick, obs, group, deterministic, in_dim, row_list=(),
+                 cat=None):
+        """The mlp_actor_critic* call pgd_<where>: what they share, checked -- the observation rows, `out`, the `per_row` outputs (logp,
         value, cost_value), the networks (value_weights and cost_weights None: none) --, then the launch on the caller's stream (group < 0);
-        `row_list`: the two pointers of mlp_actor_critic_rows' list."""
+        `row_list`: the two pointers of mlp_actor_critic_rows' list; `cat`: (bins, action_index, emit_index) of the categorical calls."""
         rows = self.N * self.A
         k = int(in_dim if in_dim is not None else policy_weights[0].shape[0])
         o2, stride = self._obs_rows(self.obs if obs is None else obs, rows, k, where)
@@ -485,11 +494,17 @@ class Engine:
         nets = self._nets(_abi.ActorCritic(), policy_weights, value_weights, k, where)
         nets.out_cols = int(policy_weights[4].shape[1])
         cnet = () if cost_weights is None else (C.byref(self._value_net(_abi.ValueNet(), cost_weights, k, where, "cost_weights")), )
+        bins, index, mode = (), (), _abi.AC_DETERMINISTIC if deterministic else 0
+        if cat is not None:
+            bins = _abi.cat_bins(cat[0], where)
+            _need(nets.out_cols >= sum(bins), where, "policy_weights: w3 [256, >= %d] wanted for bins %r" % (sum(bins), bins))
+            index = (_p(_dev(cat[1], self.torch.int32, 2 * rows, where, "action_index")), )
+            mode |= _abi.AC_EMIT_INDEX if cat[2] else 0
         if group < 0:
             self._follow_stream()
         per_row = per_row if value_weights is not None else (per_row[0], None)  # (no critic: a null pointer for `value`)
-        _chk(getattr(self.L, fn)(self.h, int(group), _p(o2), stride, k, C.byref(nets), *cnet, int(seed) & 0xffffffff, int(tick) & 0xffffffff,
-                                 _abi.AC_DETERMINISTIC if deterministic else 0, *row_list, _p(out), *map(_p, per_row)), fn)
+        _chk(getattr(self.L, fn)(self.h, int(group), _p(o2), stride, k, C.byref(nets), *cnet, *bins, int(seed) & 0xffffffff, int(tick) & 0xffffffff,
+                                 mode, *row_list, _p(out), *index, *map(_p, per_row)), fn)
 
     def _rollout_buffers(self, where, table):
         """The tensors of a rollout call checked: `table` rows are (name, tensor, dtype, extra); the first is the lead, [T, rows...]; extra
@@ -622,6 +637,50 @@ class Engine:
                       in_dim, row_list)
         return out, logp, value
 
+    # -- the categorical head (include/pgdrive_hip.h states the formulas) -------------------------------------------------------------
+    def mlp_actor_critic_cat(self, policy_weights, value_weights, bins, out, action_index, logp, value, seed, tick, obs=None, group=-1,
+                             deterministic=False, emit_index=False, in_dim=None):
+        """mlp_actor_critic with the categorical head (pgd_mlp_actor_critic_cat): `bins` = (ks, kt), 2 <= each, ks + kt <= 16; the policy's
+        w3 is [256, >= ks + kt] -- columns 0 .. ks - 1 the steering logits, ks .. ks + kt - 1 the throttle logits.  `action_index` int32
+        cuda [N, A, 2] receives the sampled indices, `logp` their log-probability, `value` the critic's output (mlp_actor_critic's bits);
+        `out` [N, A, 2] what the step reads: the grid value i * (2 / (K_head - 1)) - 1 for an engine with continuous actions, or, with
+        emit_index, the index as a float for an engine with discrete_action.  The draws are mlp_actor_critic's (seed, global row, tick +
+        the device counter).  deterministic: the argmax.  The other arguments as for mlp_actor_critic."""
+        self._ac_call("mlp_actor_critic_cat", policy_weights, value_weights, None, out, (logp, value), seed, tick, obs, group, deterministic, in_dim,
+                      cat=(bins, action_index, emit_index))
+        return out, action_index, logp, value
+
+    def mlp_actor_critic_cat_rows(self, policy_weights, value_weights, bins, rows, count, out, action_index, logp, value, seed, tick, obs=None,
+                                  group=-1, deterministic=False, emit_index=False, in_dim=None):
+        """mlp_actor_critic_cat over the rows of a list (pgd_mlp_actor_critic_cat_rows): `rows` / `count` as live_rows returns them.  A
+        listed row gets bit for bit what mlp_actor_critic_cat gives it; every other row of the range gets action 0, 0, index 0, 0, logp 0,
+        value 0 and its observation is never used."""
+        _need(rows is not None and count is not None, "mlp_actor_critic_cat_rows", "rows and count wanted")
+        row_list = self._list_args(rows, count, self._group_rows(group), "mlp_actor_critic_cat_rows", "rows")
+        self._ac_call("mlp_actor_critic_cat_rows", policy_weights, value_weights, None, out, (logp, value), seed, tick, obs, group, deterministic,
+                      in_dim, row_list, cat=(bins, action_index, emit_index))
+        return out, action_index, logp, value
+
+    def ppo_cat_work_bytes(self, in_dim, rows, has_critic=True):
+        """The scratch pgd_ppo_grad_cat needs for minibatches of up to `rows` positions (pgd_ppo_cat_work_bytes); 0: the call would refuse
+        them."""
+        return int(self.L.pgd_ppo_cat_work_bytes(int(in_dim), int(rows), int(bool(has_critic))))
+
+    def ppo_grad_cat(self, policy_weights, value_weights, policy_grads, value_grads, bins, obs, action_index, logp_old, adv, ret, stats, work,
+                     start=0, stride=1, rows=None, index=None, count=None, n_list=None, adv_stats=None, clip=0.2, vf_coef=0.5, ent_coef=0.0,
+                     in_dim=None):
+        """ppo_grad with the categorical head (pgd_ppo_grad_cat): `bins` as for mlp_actor_critic_cat, `action_index` int32 cuda [..., 2] the
+        rollout's sampled indices in place of `actions`; `work` of at least ppo_cat_work_bytes(in_dim, rows) bytes.  Every other argument,
+        `stats` and the minibatch rule as for ppo_grad."""
+        nets, _, b, grads, _ = self._ppo_batch("ppo_grad_cat", (policy_weights, value_weights, None), (policy_grads, value_grads, None), obs, None,
+                                               logp_old, adv, ret, None, stats, work, start, stride, rows, index, count, n_list, adv_stats, in_dim,
+                                               cat=(bins, action_index))
+        ks, kt = _abi.cat_bins(bins, "ppo_grad_cat")
+        hp = _abi.PPOHyper(float(clip), float(vf_coef), float(ent_coef))
+        _chk(self.L.pgd_ppo_grad_cat(self.h, C.byref(nets), C.byref(b), C.byref(hp), C.byref(grads), ks, kt, _p(action_index), _p(stats), _p(work),
+                                     work.numel() * work.element_size()), "pgd_ppo_grad_cat")
+        return stats
+
     def gae_masked(self, reward, value, done, flags, gamma, lam, adv=None, ret=None, mask=None):
         """Advantages and returns of a multi-agent rollout (pgd_gae_masked): as gae(), with the step flags [T, rows...] (int32) deciding
         where an agent acted and whether it continues; rows that did not act get adv = ret = 0 whatever their reward and value hold.
@@ -674,17 +733,23 @@ class Engine:
         return stats
 
     def _ppo_batch(self, where, weights, grad_bufs, obs, actions, logp_old, adv, ret, cost_ret, stats, work, start, stride, rows, index, count,
-                   n_list, adv_stats, in_dim):
-        """What ppo_grad and ppo_grad_cost share, checked: the rollout's tensors, the minibatch, `stats`, `work`, and the networks with their
-        gradient buffers -- `weights` and `grad_bufs` are (policy, value or None, cost or None) -> ActorCritic, ValueNet (or None),
-        PPOBatch, PPOGrads, ValueGrads (or None).  Follows the caller's stream."""
+                   n_list, adv_stats, in_dim, cat=None):
+        """What ppo_grad, ppo_grad_cost and ppo_grad_cat share, checked: the rollout's tensors, the minibatch, `stats`, `work`, and the networks
+        with their gradient buffers -- `weights` and `grad_bufs` are (policy, value or None, cost or None) -> ActorCritic, ValueNet (or None),
+        PPOBatch, PPOGrads, ValueGrads (or None).  `cat`: (bins, action_index) of ppo_grad_cat, which reads no `actions`.  Follows the
+        caller's stream."""
         t = self.torch
         (pw, vw, cw), (pg, vg, cg) = weights, grad_bufs
         _need(cw is None or vw is not None, where, "the cost critic comes with a critic")
         k = int(in_dim if in_dim is not None else pw[0].shape[0])
         o2, obs_stride = self._obs_rows(obs, None, k, where)
         n_rows = int(o2.shape[0])
-        _dev(actions, t.float32, 2 * n_rows, where, "actions")
+        if cat is None:
+            _dev(actions, t.float32, 2 * n_rows, where, "actions")
+        else:
+            _dev(cat[1], t.int32, 2 * n_rows, where, "action_index")
+            _need(int(pw[4].shape[1]) >= sum(_abi.cat_bins(cat[0], where)), where, "policy_weights: w3 [256, >= %d] wanted for bins %r" %
+                  (sum(cat[0]), cat[0]))
         by_row = (("logp_old", logp_old), ("adv", adv), ("ret", ret), ("cost_ret", cost_ret))
         for name, v in by_row[:2 + (vw is not None) + (cw is not None)]:
             _dev(v, t.float32, n_rows, where, name)
@@ -693,7 +758,8 @@ class Engine:
         rows = int(max(1, -(-(n_list - int(start)) // int(stride))) if rows is None else rows)
         _need(int(start) >= 0 and int(stride) >= 1 and 1 <= rows <= _abi.PPO_ROWS_MAX, where, "start >= 0, stride >= 1, rows <= PPO_ROWS_MAX wanted")
         _dev(stats, t.float32, 8, where, "stats")
-        need = self.ppo_work_bytes(k, rows, vw is not None) if cw is None else self.ppo_cost_work_bytes(k, rows)
+        need = self.ppo_cost_work_bytes(k, rows) if cw is not None else (self.ppo_work_bytes if cat is None else self.ppo_cat_work_bytes)(
+            k, rows, vw is not None)
         _dev(work, None, None, where, "work", None, True, 16)
         _need(0 < need <= work.numel() * work.element_size(), where, "work: at least %d bytes wanted (0: rows or in_dim out of range)" % need)
         _opt(adv_stats, t.float32, 2, where, "adv_stats")
@@ -704,7 +770,7 @@ class Engine:
         cnet = None if cw is None else self._value_net(_abi.ValueNet(), cw, k, where, "cost_weights")
         cgrads = None if cw is None else self._value_net(_abi.ValueGrads(), cg, k, where, "cost_grads")
         b = _abi.PPOBatch()
-        b.obs, b.action, b.logp_old, b.adv = o2.data_ptr(), actions.data_ptr(), logp_old.data_ptr(), adv.data_ptr()
+        b.obs, b.action, b.logp_old, b.adv = o2.data_ptr(), None if cat is not None else actions.data_ptr(), logp_old.data_ptr(), adv.data_ptr()
         b.ret = ret.data_ptr() if vw is not None else None
         b.adv_stats = adv_stats.data_ptr() if adv_stats is not None else None
         b.index, b.count = self._list_args(index, count, n_list, where)

@@ -13,7 +13,8 @@ Here: Engine.adv_stats once, then Engine.ppo_grad + Engine.adam for every epoch 
 or reads a device scalar, so one `collect(); update()` can be captured in a HIP graph and replayed: the Adam step number and the tick of
 the rollout's noise live in device memory and advance with every replay.  A collector built with normalise_obs=True: update() binds the
 collector's table (Engine.obs_norm_bind) before its first ppo_grad and unbinds behind the last adam, so the gradients see the inputs the
-rollout's evaluations saw.
+rollout's evaluations saw.  A collector built with action_head="categorical": the learner reads the head and the bins off it, sizes its
+scratch with Engine.ppo_cat_work_bytes and calls Engine.ppo_grad_cat with batch["action_index"]; everything else here is unchanged.
 
 Minibatch j of n takes the list positions j, j + n, j + 2 n, ...: the n minibatches partition the rollout's transitions whatever their
 number is.  For RolloutCollector the list is every (t, env) row; for MultiAgentRolloutCollector it is batch["index"] / batch["count"] as
@@ -86,6 +87,16 @@ def minibatch_options(name, shuffle, shuffle_seed, target_kl, lr_scale):
     return bool(shuffle), int(shuffle_seed), kl_limit, bool(lr_scale)
 
 
+def collector_head(name, collector, cost=False):
+    """(head, bins) a learner reads off its collector: ("gaussian", None) for a collector of before, ("categorical", (ks, kt)) for one built
+    with action_head="categorical" -- which the Lagrangian learner refuses (NotImplementedError: the three-network kernels know the Gaussian
+    head only).  No device needed."""
+    head, bins = getattr(collector, "action_head", "gaussian"), getattr(collector, "bins", None)
+    if head == "categorical" and cost:
+        raise NotImplementedError("%s: the categorical head is not served by pgd_ppo_grad_cost" % name)
+    return head, bins
+
+
 class PPOLearner:
     NETS = ("policy", "value")  # the collector's networks, in flat_layout's order
     GRAD = "pgd_ppo_grad"
@@ -95,6 +106,7 @@ class PPOLearner:
         name, cost = type(self).__name__, len(self.NETS) == 3
         self.shuffle, self.shuffle_seed, self.kl_limit, scaled = minibatch_options(name, shuffle, shuffle_seed, target_kl, lr_scale)
         self.target_kl = None if target_kl is None else float(target_kl)
+        self.action_head, self.bins = collector_head(name, collector, cost)
         eng = collector.engine
         t = eng.torch
         if int(epochs) < 1 or int(minibatches) < 1:
@@ -124,7 +136,8 @@ class PPOLearner:
         self.n_list = int(collector.rewards.numel())  # T * N (* A): every row of the rollout
         self.plan = minibatch_plan(self.n_list, self.minibatches)
         rows = max(rows for _, _, rows in self.plan)
-        need = eng.ppo_cost_work_bytes(self.in_dim, rows) if cost else eng.ppo_work_bytes(self.in_dim, rows, True)
+        work_bytes = eng.ppo_cat_work_bytes if self.action_head == "categorical" else eng.ppo_work_bytes
+        need = eng.ppo_cost_work_bytes(self.in_dim, rows) if cost else work_bytes(self.in_dim, rows, True)
         if need == 0:
             raise ValueError("%s: the networks' input width %d is outside what %s accepts" % (name, self.in_dim, self.GRAD))
         self.work = t.empty(((need + 3) // 4, ), **f32)
@@ -168,6 +181,11 @@ class PPOLearner:
         return adv, self.engine.adv_stats(adv, out=self.adv_stats, index=index, count=count, n_list=self.n_list)
 
     def _grad(self, batch, adv, stats, **minibatch):
+        if self.action_head == "categorical":
+            self.engine.ppo_grad_cat(self.policy_weights, self.value_weights, self.policy_grads, self.value_grads, self.bins, batch["obs"],
+                                     batch["action_index"], batch["logp"], adv, batch["returns"], stats, self.work, vf_coef=self.vf_coef,
+                                     **minibatch)
+            return
         self.engine.ppo_grad(self.policy_weights, self.value_weights, self.policy_grads, self.value_grads, batch["obs"], batch["actions"],
                              batch["logp"], adv, batch["returns"], stats, self.work, vf_coef=self.vf_coef, **minibatch)
 

@@ -79,6 +79,15 @@ takeover uint8 [T, N] (bit 0 takeover, 1 takeover_start, 2 takeover_end) and exp
 was applied; what a trainer makes of the difference is the trainer's business.  A bound observation normalisation does not reach the
 expert.  The takeover state [N] survives from rollout to rollout and is part of state_dict() (guardian_state).  None (the default): the
 launches and the batch of before.
+
+action_head="categorical", bins=(ks, kt) (RolloutCollector, MultiAgentRolloutCollector): the policy is two independent categorical
+distributions over ks steering and kt throttle bins in place of the Gaussian (Engine.mlp_actor_critic_cat / _cat_rows; DESIGN section
+33), 2 <= ks, kt and ks + kt <= 16, the policy's w3 [256, >= ks + kt].  The collector owns action_index [T + 1, rows, 2] int32, carried like
+`actions`; the batch gains action_index [T, ...]; `actions` stays what the step was fed -- the grid value i * 2 / (K - 1) - 1 of the
+sampled index on an engine with continuous actions (recommended), the index itself on a discrete_action engine, whose dims the bins must
+equal.  No other switch looks at the head, so they compose unchanged; the guardian and the safe collector refuse it.  "gaussian" (the
+default): the launches and the batch of before; on a discrete_action engine that still means Gaussian samples clipped and converted by
+the step, and one warning that says so.
 """
 import numpy as np
 
@@ -97,6 +106,38 @@ def truncated(flags, done, safe_rl_env=False):
     if safe_rl_env:
         natural = natural & ((flags & F_CRASH_COST) == 0)
     return (done != 0) & ((flags & F_MAX_STEP) != 0) & ~natural
+
+
+def action_head_options(name, action_head, bins, w3_cols, discrete_action=False, discrete_dims=None, guardian=None, safe=False):
+    """A collector's head switches checked -> (head, bins or None, emit_index).  No device needed.  "gaussian" (the default): bins must be
+    None; on a discrete_action engine the behaviour of before stays (the step clips and converts the Gaussian samples) and ONE warning
+    names action_head="categorical".  "categorical": bins = (ks, kt) required, 2 <= each, ks + kt <= 16 (ValueError); the policy's w3 needs
+    ks + kt columns (ValueError); on a discrete_action engine the bins must be its (discrete_steering_dim, discrete_throttle_dim)
+    (ValueError) and the launches emit the index; the guardian and the safe collector are refused (NotImplementedError)."""
+    from . import _abi
+    if action_head not in ("gaussian", "categorical"):
+        raise ValueError("%s: action_head = %r is neither \"gaussian\" nor \"categorical\"" % (name, action_head))
+    if action_head == "gaussian":
+        if bins is not None:
+            raise ValueError("%s: bins = %r come with action_head=\"categorical\"" % (name, bins))
+        if discrete_action:
+            import warnings
+            warnings.warn("%s: a discrete_action engine is fed Gaussian samples, which the step clips to [-1, 1] and converts as if they were "
+                          "indices; action_head=\"categorical\" with bins=%r samples the env's own MultiDiscrete space" %
+                          (name, tuple(discrete_dims) if discrete_dims is not None else None), stacklevel=3)
+        return "gaussian", None, False
+    if bins is None:
+        raise ValueError("%s: action_head=\"categorical\" needs bins=(steering, throttle)" % name)
+    bins = _abi.cat_bins(bins, name)
+    if safe:
+        raise NotImplementedError("%s: the categorical head is not served by the three-network kernels of the safe path" % name)
+    if guardian is not None:
+        raise NotImplementedError("%s: the expert guardian compares continuous actions; it does not serve the categorical head" % name)
+    if int(w3_cols) < sum(bins):
+        raise ValueError("%s: the policy's w3 has %d columns, bins %r need %d" % (name, int(w3_cols), bins, sum(bins)))
+    if discrete_action and tuple(int(d) for d in discrete_dims) != bins:
+        raise ValueError("%s: bins %r on a discrete_action engine whose MultiDiscrete space is %r" % (name, bins, tuple(discrete_dims)))
+    return "categorical", bins, bool(discrete_action)
 
 
 class _Collector:
@@ -129,6 +170,27 @@ class _Collector:
     def set_weights(self, policy_weights, value_weights):
         """The networks of the rollouts from now on (between two collect() calls): tuples as for Engine.mlp_actor_critic."""
         self.policy_weights, self.value_weights = tuple(policy_weights), tuple(value_weights)
+
+    @staticmethod
+    def _head_options(name, eng, policy_weights, action_head, bins, guardian=None, safe=False):
+        """action_head_options for this engine and policy (in front of _allocate: a refusal allocates nothing)."""
+        cfg = getattr(eng, "cfg", None)  # (an engine stand-in of the tests has none: continuous actions)
+        discrete = bool(getattr(cfg, "discrete_action", 0))
+        dims = (int(cfg.discrete_steering_dim), int(cfg.discrete_throttle_dim)) if discrete else None
+        w3 = tuple(policy_weights)[4]
+        return action_head_options(name, action_head, bins, int(w3.shape[1]) if hasattr(w3, "shape") else 0, discrete, dims, guardian, safe)
+
+    def _head(self, head):
+        """The policy head (behind _allocate; `head`: what _head_options returned).  Categorical: the collector owns action_index
+        [T + 1, rows, 2] int32, carried row T -> 0 like `actions`, and the batch gains action_index [T, ...]; `actions` stays what the step
+        was fed (the grid value, or the index on a discrete_action engine)."""
+        self.action_head, self.bins, self.emit_index = head
+        if self.action_head != "categorical":
+            return
+        t = self.engine.torch
+        self._action_index = t.zeros(self._actions.shape, dtype=t.int32, device=self.engine.device)
+        self._carry = self._carry + (self._action_index, )
+        self.batch.update(action_index=self._action_index[:self.T])
 
     def _checkpoint(self, on, what, off, **entries):
         """A switch's setup says what state_dict() holds for it -- key=the name of the attribute that holds the tensor -- and what
@@ -386,10 +448,17 @@ class RolloutCollector(_Collector):
     episode_stats_rollout (float64 [16]), ep_returns and ep_lengths [T, N].
     normalise_obs=True, clip_obs, obs_eps: the networks (the terminal-value launch included) read the observations normalised by their
     running mean and variance (the module's docstring); the batch gains obs_norm (float32 [2, Dp]) and obs_norm_record (float64
-    [1 + 2 D]); `obs` stays raw."""
+    [1 + 2 D]); `obs` stays raw.
+    action_head="categorical", bins=(ks, kt): the policy is two independent categorical distributions over ks steering and kt throttle bins
+    (Engine.mlp_actor_critic_cat) -- w3 [256, >= ks + kt].  The batch gains action_index int32 [T, N, 2]; `actions` is what
+    the step was fed: the grid value i * 2 / (K - 1) - 1 on an engine with continuous actions (recommended for training), the index itself on
+    a discrete_action engine, whose (discrete_steering_dim, discrete_throttle_dim) the bins must then equal.  Not with guardian=.  A
+    discrete_action engine with the default Gaussian head behaves as before and warns once."""
+    _SAFE = False  # (SafeRolloutCollector: the categorical head is refused)
+
     def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, bootstrap_truncations=False,
                  normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8, episode_stats=False, normalise_obs=False, clip_obs=10.0,
-                 obs_eps=1e-8, guardian=None):
+                 obs_eps=1e-8, guardian=None, action_head="gaussian", bins=None):
         eng = getattr(env_or_engine, "engine", env_or_engine)
         if eng.A != 1:
             raise NotImplementedError(
@@ -404,7 +473,9 @@ class RolloutCollector(_Collector):
             if eng.step_info.get("final_observation") is None:
                 raise ValueError("bootstrap_truncations needs the terminal observation of the step info, and this engine's step info has no "
                                  "final_observation (image observations: enable_step_info(final_obs=False))")
+        head = self._head_options(type(self).__name__, eng, policy_weights, action_head, bins, guardian, self._SAFE)
         self._allocate(eng, (eng.N, ), policy_weights, value_weights, T, gamma, lam, seed)
+        self._head(head)
         self._normalise(normalise_rewards, clip_reward, reward_eps)
         self._episodes(episode_stats)
         self._obs_norm(normalise_obs, clip_obs, obs_eps)
@@ -414,6 +485,10 @@ class RolloutCollector(_Collector):
             self.batch.update(term_values=self.term_values)
 
     def _evaluate(self, row):
+        if self.action_head == "categorical":
+            self.engine.mlp_actor_critic_cat(self.policy_weights, self.value_weights, self.bins, self._actions[row], self._action_index[row],
+                                             self._logp[row], self.values[row], self.seed, row, obs=self._obs[row], emit_index=self.emit_index)
+            return
         self.engine.mlp_actor_critic(self.policy_weights, self.value_weights, self._actions[row], self._logp[row], self.values[row], self.seed,
                                      row, obs=self._obs[row])
 
@@ -459,15 +534,19 @@ class SafeRolloutCollector(RolloutCollector):
 
     bootstrap_truncations=True: as for RolloutCollector, with the cost critic in the same terminal-value launch; the batch gains
     term_values and term_cost_values [T, N], and Engine.cost_gae_bootstrap takes the latter as the cost side's one-step target.  The
-    books of episode costs are unchanged: a truncated episode still finishes for them."""
+    books of episode costs are unchanged: a truncated episode still finishes for them.
+
+    action_head="categorical" is refused (NotImplementedError): the three-network kernels know the Gaussian head only."""
+    _SAFE = True
+
     def __init__(self, env_or_engine, policy_weights, value_weights, cost_weights, T, costs=None, gamma=0.99, lam=0.95, cost_gamma=0.99,
                  cost_lam=0.95, seed=0, bootstrap_truncations=False, normalise_rewards=False, clip_reward=10.0, reward_eps=1e-8,
-                 episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8, guardian=None):
+                 episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8, guardian=None, action_head="gaussian", bins=None):
         self.cost_weights = tuple(cost_weights)
         super().__init__(env_or_engine, policy_weights, value_weights, T, gamma=gamma, lam=lam, seed=seed,
                          bootstrap_truncations=bootstrap_truncations, normalise_rewards=normalise_rewards, clip_reward=clip_reward,
                          reward_eps=reward_eps, episode_stats=episode_stats, normalise_obs=normalise_obs, clip_obs=clip_obs, obs_eps=obs_eps,
-                         guardian=guardian)
+                         guardian=guardian, action_head=action_head, bins=bins)
         eng = self.engine
         t = eng.torch
         if costs is None:
@@ -543,9 +622,13 @@ class MultiAgentRolloutCollector(_Collector):
     share of the agents an env-wide restart took out.
 
     normalise_obs=True: as for RolloutCollector (the module's docstring); the fold takes the rows of `index` / `count` only, those at
-    which an agent acted -- the zero rows of seats that are not due are no samples."""
+    which an agent acted -- the zero rows of seats that are not due are no samples.
+
+    action_head="categorical", bins=(ks, kt): as for RolloutCollector, over the live rows (Engine.mlp_actor_critic_cat_rows); the batch gains
+    action_index int32 [T, N, A, 2], zeros in every seat that is not due."""
     def __init__(self, env_or_engine, policy_weights, value_weights, T, gamma=0.99, lam=0.95, seed=0, normalise_rewards=False, clip_reward=10.0,
-                 reward_eps=1e-8, episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8, guardian=None):
+                 reward_eps=1e-8, episode_stats=False, normalise_obs=False, clip_obs=10.0, obs_eps=1e-8, guardian=None, action_head="gaussian",
+                 bins=None):
         if guardian is not None:
             raise NotImplementedError("MultiAgentRolloutCollector: the expert guardian serves single-agent engines only (pgd_guardian)")
         eng = getattr(env_or_engine, "engine", env_or_engine)
@@ -554,7 +637,9 @@ class MultiAgentRolloutCollector(_Collector):
                                       "never reports PGD_F_REPORT -- use RolloutCollector")
         if int(T) < 1:
             raise ValueError("MultiAgentRolloutCollector: T = %r" % (T, ))
+        head = self._head_options("MultiAgentRolloutCollector", eng, policy_weights, action_head, bins)
         self._allocate(eng, (eng.N, eng.A), policy_weights, value_weights, T, gamma, lam, seed)
+        self._head(head)
         self._normalise(normalise_rewards, clip_reward, reward_eps)
         self._episodes(episode_stats, seats=True)
         self._obs_norm(normalise_obs, clip_obs, obs_eps)
@@ -569,6 +654,11 @@ class MultiAgentRolloutCollector(_Collector):
         self.batch.update(mask=self.mask, index=self.index, count=self.count)
 
     def _evaluate(self, row):
+        if self.action_head == "categorical":
+            self.engine.mlp_actor_critic_cat_rows(self.policy_weights, self.value_weights, self.bins, self._rows, self._n_rows, self._actions[row],
+                                                  self._action_index[row], self._logp[row], self.values[row], self.seed, row,
+                                                  obs=self._obs[row], emit_index=self.emit_index)
+            return
         self.engine.mlp_actor_critic_rows(self.policy_weights, self.value_weights, self._rows, self._n_rows, self._actions[row], self._logp[row],
                                           self.values[row], self.seed, row, obs=self._obs[row])
 
