@@ -221,25 +221,13 @@ __global__ __launch_bounds__(CMP_THREADS) void k_cat_clear_rows(const int row_lo
 }
 
 // ---- pgd_ppo_grad_cat -------------------------------------------------------------------------------------------------------------------
-// pgd_ppo_grad's five launches with this head: k_ppo_prep as it is; k_ppo_rows_cat, k_ppo_wgrad_cat, k_ppo_reduce_cat, k_ppo_stats_cat are
-// their namesakes of pgd_ppo.h with dOut [R16][16] and a tile-sum record of PPO_CAT_TS floats -- copies, so that the Gaussian kernels
-// stay the code they were (ppo_load_rows has its copy for the same reason).  k_ppo_zero_head follows k_ppo_reduce_cat when out_cols > K.
-// the scratch, in floats from its start: [net] W2^T | [net][H1, H2, dZ1, dZ2][R16][256] | [net] dOut [R16][16] | tile sums | partials
-DEV_HOST PpoWork ppo_cat_work(int in_dim, int rows, int nets) {
-  PpoWork w;
-  w.R16 = (rows + 15) & ~15;
-  w.P = (w.R16 + PPO_PART - 1) / PPO_PART;
-  w.mt1 = (in_dim + 15) / 16;
-  w.mt = w.mt1 + 19;  // dW1 tiles | db1 | 16 dW2 tiles | db2 | dW3^T
-  size_t o = 0;
-  w.w2t = o;  o += (size_t)nets * MLP_H * MLP_H;
-  w.act = o;  o += (size_t)nets * 4 * w.R16 * MLP_H;
-  w.dout = o; o += (size_t)nets * w.R16 * CAT_COLS;
-  w.tsum = o; o += (size_t)(w.R16 / 16) * PPO_CAT_TS;
-  w.part = o; o += (size_t)nets * w.P * w.mt * 16 * MLP_H;
-  w.total = o;
-  return w;
-}
+// pgd_ppo_grad's five launches with this head, dOut [R16][16] and a tile-sum record of PPO_CAT_TS floats: k_ppo_prep as it is;
+// k_ppo_wgrad_cat and k_ppo_reduce_cat call the bodies of their namesakes (ppo_wgrad_tile, ppo_reduce_entry of pgd_ppo.h) with this
+// head's two widths, and the scratch is ppo_work_of's plan with them.  k_ppo_rows_cat and k_ppo_stats_cat keep their OWN text beside
+// ppo_rows_tile and ppo_stats_block: every shared spelling that was tried changed the instructions of a kernel that exists today
+// (DESIGN section 34 lists them), and a folding is kept only where no kernel changes.  k_ppo_zero_head follows k_ppo_reduce_cat when
+// out_cols > K.
+DEV_HOST PpoWork ppo_cat_work(int in_dim, int rows, int nets) { return ppo_work_of<CAT_COLS, PPO_CAT_TS>(in_dim, rows, nets); }
 
 // 1 / n rounded to fp32 ONCE: the quotient is formed in double and passes through an empty asm statement -- left alone, the build
 // narrows a double quotient of two small integers to the fp32 division, which is its 2.5 ulp form
@@ -307,6 +295,8 @@ DEV void cat_row_loss(const float l, const int o, const int l16, const int ks, c
 // k_ppo_rows with the categorical head: network blockIdx.y of gridDim.y for the 16 minibatch positions blockIdx.x * 16 + [0, 16).
 // LDS: X | H1 | H2 | 4 KB: [0, 256) the critic's head weights (the actor: its partial logit tiles over all of it, dead behind cat_logits),
 // [256, 512) dOut [16][16], [512, 896) the rows' loss terms [16][PPO_CAT_TS] -- ac_lds_bytes, less than k_ppo_rows'.
+// The two hidden layers, the critic's dot product and loss, and the dZ1 epilogue are ppo_rows_tile's text: each was tried as a function
+// of its own that both call (one at a time), and each changed all six k_ppo_rows* symbols.
 template <bool NORM>
 __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows_cat(const pgd_actor_critic nets, const pgd_ppo_batch b, const pgd_ppo_hyper hp,
                                                                    const int ks, const int kt, const int32_t* __restrict__ aidx,
@@ -433,97 +423,26 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 4) void k_ppo_rows_cat(const pgd_
   }
 }
 
-// k_ppo_wgrad over ppo_cat_work's scratch: the A of dW3^T is dOut [R16][16], all sixteen columns (the critic's and the padding's are zero)
+// k_ppo_wgrad's body over ppo_cat_work's scratch: the A of dW3^T is dOut [R16][16], all sixteen columns (the critic's and the padding's are zero)
 template <bool NORM>
 __global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad_cat(const pgd_ppo_batch b, float* __restrict__ work, const ObsNorm nm) {
-  __shared__ float At[16 * (PPO_CHUNK + 2)];
-  const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
-  const int live16 = (n + 15) & ~15;
-  const int rbeg = (int)blockIdx.y * PPO_PART;
-  if (rbeg >= live16) return;
-  const int rend = min(rbeg + PPO_PART, live16);
-  const int in_dim = b.in_dim, net = (int)blockIdx.z;
-  const PpoWork wk = ppo_cat_work(in_dim, b.rows, (int)gridDim.z);
-  const size_t plane = (size_t)wk.R16 * MLP_H;
-  const float* __restrict__ H1g = work + wk.act + (size_t)net * 4 * plane;
-  const float* __restrict__ H2g = H1g + plane;
-  const float* __restrict__ dZ1g = H2g + plane;
-  const float* __restrict__ dZ2g = dZ1g + plane;
-  const float* __restrict__ dOg = work + wk.dout + (size_t)net * wk.R16 * CAT_COLS;
-  int m0;
-  const int kind = ppo_tile_kind((int)blockIdx.x, wk.mt1, m0);
-  const float* __restrict__ B = kind <= 1 ? dZ1g : (kind <= 3 ? dZ2g : H2g);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c0 = wave * 64;
-  const int m = tid & 15, jj = tid >> 4;
-  mlp_f32x4 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = mlp_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  for (int r0 = rbeg; r0 < rend; r0 += PPO_CHUNK) {
-    const int rc = min(PPO_CHUNK, rend - r0);  // (a multiple of 16)
-    for (int j = jj; j < rc; j += 16) {
-      float v;
-      if (kind == 0) {
-        const int row = ppo_row(b, r0 + j, n);
-        const bool in = row >= 0 && m0 + m < in_dim;
-        v = in ? b.obs[(size_t)row * b.obs_stride + m0 + m] : 0.0f;
-        if (NORM) v = in ? on_apply(v, nm.table[m0 + m], nm.table[((in_dim + 3) & ~3) + m0 + m], nm.clip) : 0.0f;
-      } else if (kind == 2) {
-        v = H1g[(size_t)(r0 + j) * MLP_H + m0 + m];
-      } else if (kind == 4) {
-        v = dOg[(size_t)(r0 + j) * CAT_COLS + m];
-      } else {
-        v = m == 0 ? 1.0f : 0.0f;
-      }
-      At[m * (PPO_CHUNK + 2) + j] = v;
-    }
-    __syncthreads();
-    mlp_layer(At, PPO_CHUNK + 2, B + (size_t)r0 * MLP_H, rc, rc, lane, c0, acc);
-    __syncthreads();
-  }
-  float* __restrict__ out = work + wk.part + ((((size_t)net * wk.P + blockIdx.y) * wk.mt + blockIdx.x) * 16) * MLP_H;
-  const int col = c0 + 4 * (lane & 15), r4 = (lane >> 4) * 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    *reinterpret_cast<float4*>(out + (size_t)(r4 + i) * MLP_H + col) = make_float4(acc[0][i], acc[1][i], acc[2][i], acc[3][i]);
+  ppo_wgrad_tile<NORM, CAT_COLS, PPO_CAT_TS>(b, work, nm);
 }
 
-// k_ppo_reduce over ppo_cat_work's scratch; head columns [K, min(out_cols, 16)) of dW3 are written as zero (those from 16 on: k_ppo_zero_head)
+// k_ppo_reduce's body over ppo_cat_work's scratch; head columns [K, min(out_cols, 16)) of dW3 are written as zero (those from 16 on: k_ppo_zero_head)
 __global__ __launch_bounds__(MLP_H) void k_ppo_reduce_cat(const pgd_ppo_batch b, const pgd_ppo_grads gr, const int out_cols, const int K,
                                                           const float* __restrict__ work) {
   const bool critic = blockIdx.y != 0;
-  float* __restrict__ dW1 = critic ? gr.vw1 : gr.w1;
-  float* __restrict__ db1 = critic ? gr.vb1 : gr.b1;
-  float* __restrict__ dW2 = critic ? gr.vw2 : gr.w2;
-  float* __restrict__ db2 = critic ? gr.vb2 : gr.b2;
-  float* __restrict__ dW3 = critic ? gr.vw3 : gr.w3;
-  const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
-  const int p_live = (((n + 15) & ~15) + PPO_PART - 1) / PPO_PART;
-  const int in_dim = b.in_dim, net = (int)blockIdx.y;
-  const PpoWork wk = ppo_cat_work(in_dim, b.rows, (int)gridDim.y);
-  const int tile = (int)blockIdx.x >> 4, m = (int)blockIdx.x & 15, c = threadIdx.x;
-  int m0;
-  const int kind = ppo_tile_kind(tile, wk.mt1, m0);
-  const float* __restrict__ part = work + wk.part + ((((size_t)net * wk.P) * wk.mt + tile) * 16 + m) * MLP_H + c;
-  float s = 0.0f;
-  for (int p = 0; p < p_live; ++p) s += part[(size_t)p * wk.mt * 16 * MLP_H];
-  if (kind == 0) {
-    if (m0 + m < in_dim) dW1[(size_t)(m0 + m) * MLP_H + c] = s;
-  } else if (kind == 1) {
-    if (m == 0) db1[c] = s;
-  } else if (kind == 2) {
-    dW2[(size_t)(m0 + m) * MLP_H + c] = s;
-  } else if (kind == 3) {
-    if (m == 0) db2[c] = s;
-  } else if (critic) {
-    if (m == 0) dW3[c] = s;
-  } else {
-    if (m < K) dW3[(size_t)c * out_cols + m] = s;
-    else if (m < out_cols) dW3[(size_t)c * out_cols + m] = 0.0f;
-  }
+  ppo_reduce_entry<CAT_COLS, PPO_CAT_TS>(b, critic, critic ? gr.vw1 : gr.w1, critic ? gr.vb1 : gr.b1, critic ? gr.vw2 : gr.w2,
+                                         critic ? gr.vb2 : gr.b2, critic ? gr.vw3 : gr.w3, out_cols, K, work);
 }
 
 // ONE workgroup: slot s of the tile sums over the live tiles -- thread (s, u) takes tiles u, u + 8, ... in order, then the eight u in
-// order -- -> d_stats, db3[0 .. K) and vb3
+// order -- -> d_stats, db3[0 .. K) and vb3.
+// Its own copy of ppo_stats_block.  As a caller of ppo_stats_block<DW, TS, SL> (red[256 / SL][SL], slots 5 + DW .., db3 written by a loop
+// over K, 1 / n as a template function) this kernel compiled to other code under every spelling tried -- batch and gradients by reference
+// or by value, with and without __restrict__ on the body's pointers, the network count derived or passed in, db3 unrolled under
+// `if constexpr (DW == 4)`: the sums keep their order, the v_add_f32 operands swap and the loop's address arithmetic changes.
 __global__ __launch_bounds__(256) void k_ppo_stats_cat(const pgd_ppo_batch b, const pgd_ppo_grads gr, const int has_critic, const int K,
                                                        const float* __restrict__ work, float* __restrict__ stats) {
   __shared__ float red[8][32];
@@ -569,45 +488,44 @@ __global__ __launch_bounds__(256) void k_ppo_stats_cat(const pgd_ppo_batch b, co
   }
 }
 
-extern "C" {
-
-int pgd_mlp_actor_critic_cat(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets, int32_t ks,
-                             int32_t kt, uint32_t seed, uint32_t tick, uint32_t flags, float* d_actions, int32_t* d_action_index, float* d_logp,
-                             float* d_value) {
+// pgd_mlp_actor_critic_cat (d_rows, d_count null, `list` false) and pgd_mlp_actor_critic_cat_rows (both required): one check, one launch
+static int cat_forward(pgd_handle h, int group, bool list, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets, int32_t ks,
+                       int32_t kt, uint32_t seed, uint32_t tick, uint32_t flags, const int32_t* d_rows, const int32_t* d_count, float* d_actions,
+                       int32_t* d_action_index, float* d_logp, float* d_value) {
   bool critic;
-  if (!h || !d_obs || !d_actions || !d_action_index || !d_logp || (flags & ~(PGD_AC_DETERMINISTIC | PGD_AC_EMIT_INDEX)) != 0u ||
-      !cat_bins_ok(ks, kt) || !nets_ok(nets, nullptr, true, in_dim, obs_stride, &critic) || nets->out_cols < ks + kt || (critic && !d_value) ||
-      ac_lds_bytes(in_dim) > 65536) return PGD_ERR_ARG;
-  return ac_forward(h, group, LDS_AC_CAT, k_mlp_actor_critic_cat<false, false>, k_mlp_actor_critic_cat<true, false>, in_dim,
-                    [&](const AcRows& r, auto kern) {
-    hipLaunchKernelGGL(kern, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream, d_obs,
-                       (const int32_t*)nullptr, (const int32_t*)nullptr, r.row0, r.rows, obs_stride, in_dim, *nets, (int)ks, (int)kt, cat_step(ks),
-                       cat_step(kt), seed, tick, h->ac_tick, r.row_base, flags, d_actions, d_action_index, d_logp, d_value, r.nm);
-  });
-}
-
-int pgd_mlp_actor_critic_cat_rows(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets, int32_t ks,
-                                  int32_t kt, uint32_t seed, uint32_t tick, uint32_t flags, const int32_t* d_rows, const int32_t* d_count,
-                                  float* d_actions, int32_t* d_action_index, float* d_logp, float* d_value) {
-  bool critic;
-  if (!h || !d_obs || !d_rows || !d_count || !d_actions || !d_action_index || !d_logp ||
+  if (!h || !d_obs || (list && (!d_rows || !d_count)) || !d_actions || !d_action_index || !d_logp ||
       (flags & ~(PGD_AC_DETERMINISTIC | PGD_AC_EMIT_INDEX)) != 0u || !cat_bins_ok(ks, kt) ||
       !nets_ok(nets, nullptr, true, in_dim, obs_stride, &critic) || nets->out_cols < ks + kt || (critic && !d_value) ||
       ac_lds_bytes(in_dim) > 65536) return PGD_ERR_ARG;
-  return ac_forward(h, group, LDS_AC_CAT_ROWS, k_mlp_actor_critic_cat<false, true>, k_mlp_actor_critic_cat<true, true>, in_dim,
-                    [&](const AcRows& r, auto kern) {
-    // the defined outputs of the rows that are not listed, then the listed rows (the host does not know how many: a grid for all)
-    hipLaunchKernelGGL(k_cat_clear_rows, dim3((r.rows + CMP_THREADS - 1) / CMP_THREADS), dim3(CMP_THREADS), 0, r.stream, r.row0, r.rows, d_actions,
-                       d_action_index, d_logp, critic ? d_value : nullptr);
+  return ac_forward(h, group, list ? LDS_AC_CAT_ROWS : LDS_AC_CAT, list ? k_mlp_actor_critic_cat<false, true> : k_mlp_actor_critic_cat<false, false>,
+                    list ? k_mlp_actor_critic_cat<true, true> : k_mlp_actor_critic_cat<true, false>, in_dim, [&](const AcRows& r, auto kern) {
+    // a list: the defined outputs of the rows that are not listed, then the listed rows (the host does not know how many: a grid for all)
+    if (list) hipLaunchKernelGGL(k_cat_clear_rows, dim3((r.rows + CMP_THREADS - 1) / CMP_THREADS), dim3(CMP_THREADS), 0, r.stream, r.row0, r.rows,
+                                 d_actions, d_action_index, d_logp, critic ? d_value : nullptr);
     hipLaunchKernelGGL(kern, dim3((r.rows + MLP_ROWS - 1) / MLP_ROWS, critic ? 2 : 1), dim3(WAVE * MLP_WAVES), r.lds, r.stream, d_obs, d_rows,
                        d_count, r.row0, r.rows, obs_stride, in_dim, *nets, (int)ks, (int)kt, cat_step(ks), cat_step(kt), seed, tick, h->ac_tick, r.row_base,
                        flags, d_actions, d_action_index, d_logp, d_value, r.nm);
   });
 }
 
+extern "C" {
+
+int pgd_mlp_actor_critic_cat(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets, int32_t ks,
+                             int32_t kt, uint32_t seed, uint32_t tick, uint32_t flags, float* d_actions, int32_t* d_action_index, float* d_logp,
+                             float* d_value) {
+  return cat_forward(h, group, false, d_obs, obs_stride, in_dim, nets, ks, kt, seed, tick, flags, nullptr, nullptr, d_actions, d_action_index, d_logp,
+                     d_value);
+}
+
+int pgd_mlp_actor_critic_cat_rows(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets, int32_t ks,
+                                  int32_t kt, uint32_t seed, uint32_t tick, uint32_t flags, const int32_t* d_rows, const int32_t* d_count,
+                                  float* d_actions, int32_t* d_action_index, float* d_logp, float* d_value) {
+  return cat_forward(h, group, true, d_obs, obs_stride, in_dim, nets, ks, kt, seed, tick, flags, d_rows, d_count, d_actions, d_action_index, d_logp,
+                     d_value);
+}
+
 size_t pgd_ppo_cat_work_bytes(int in_dim, int rows, int has_critic) {
-  if (in_dim < 4 || in_dim > 4096 || ac_lds_bytes(in_dim) > 65536 || rows < 1 || rows > PGD_PPO_ROWS_MAX) return 0;
-  return sizeof(float) * ppo_cat_work(in_dim, rows, has_critic ? 2 : 1).total;
+  return ppo_work_bytes_of<CAT_COLS, PPO_CAT_TS>(in_dim, rows, has_critic ? 2 : 1, ac_lds_bytes);
 }
 
 int pgd_ppo_grad_cat(pgd_handle h, const pgd_actor_critic* nets, const pgd_ppo_batch* batch, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads,

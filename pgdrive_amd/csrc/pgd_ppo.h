@@ -24,6 +24,10 @@
 //   k_ppo_stats   ONE workgroup: the tile sums over the live tiles in a fixed order -> d_stats and db3
 // k_ppo_rows, k_ppo_reduce and k_ppo_stats choose their network's pointers from blockIdx.y and hand them to a body (ppo_rows_tile,
 // ppo_reduce_entry, ppo_stats_block) that pgd_safe.h's three-network kernels call as well; k_ppo_wgrad takes its network count from its grid.
+// The categorical head (pgd_categorical.h) differs from this one in the width of dOut and the length of the tile-sum record: the scratch's
+// plan (ppo_work_of), the weight-gradient body (ppo_wgrad_tile) and the reduction body (ppo_reduce_entry) take the two as template
+// constants <DW, TS>, and k_ppo_wgrad_cat / k_ppo_reduce_cat call them with 16 and 24 where the kernels here say 4 and PPO_TS.
+// ppo_rows_tile and ppo_stats_block serve this head only (what was tried).
 // Deterministic: no atomics; a row's numbers never depend on its tile neighbours; every sum over rows has one owner and a fixed order
 // (rows within a partition, partitions in order; rows within a tile, tiles 16-strided, the sixteen strides in order).
 //
@@ -48,9 +52,12 @@
 #define PPO_LOG_2PI 1.8378770664093453f
 #define PPO_LOG_2PIE 2.8378770664093453f
 
-// the scratch, in floats from its start: [net] W2^T | [net][H1, H2, dZ1, dZ2][R16][256] | [net] dOut [R16][4] | tile sums | partials
+// the scratch, in floats from its start: [net] W2^T | [net][H1, H2, dZ1, dZ2][R16][256] | [net] dOut [R16][DW] | tile sums, TS floats per
+// tile | partials.  Two heads, two (DW, TS): the Gaussian's 4 and PPO_TS (ppo_work), the categorical's 16 and PPO_CAT_TS (ppo_cat_work,
+// pgd_categorical.h).  Template constants: as run-time arguments they moved six scalar instructions of k_ppo_wgrad's epilogue
 struct PpoWork { size_t w2t, act, dout, tsum, part, total; int R16, P, mt1, mt; };
-DEV_HOST PpoWork ppo_work(int in_dim, int rows, int nets) {
+template <int DW, int TS>
+DEV_HOST PpoWork ppo_work_of(int in_dim, int rows, int nets) {
   PpoWork w;
   w.R16 = (rows + 15) & ~15;
   w.P = (w.R16 + PPO_PART - 1) / PPO_PART;
@@ -59,12 +66,13 @@ DEV_HOST PpoWork ppo_work(int in_dim, int rows, int nets) {
   size_t o = 0;
   w.w2t = o;  o += (size_t)nets * MLP_H * MLP_H;
   w.act = o;  o += (size_t)nets * 4 * w.R16 * MLP_H;
-  w.dout = o; o += (size_t)nets * w.R16 * 4;
-  w.tsum = o; o += (size_t)(w.R16 / 16) * PPO_TS;
+  w.dout = o; o += (size_t)nets * w.R16 * DW;
+  w.tsum = o; o += (size_t)(w.R16 / 16) * TS;
   w.part = o; o += (size_t)nets * w.P * w.mt * 16 * MLP_H;
   w.total = o;
   return w;
 }
+DEV_HOST PpoWork ppo_work(int in_dim, int rows, int nets) { return ppo_work_of<4, PPO_TS>(in_dim, rows, nets); }
 DEV_HOST size_t ppo_lds_bytes(int in_dim) { return ac_lds_bytes(in_dim) + sizeof(float) * 16 * (4 + PPO_ST); }
 
 // the count of a list: *count within [0, n_list], n_list without a pointer
@@ -317,9 +325,11 @@ DEV int ppo_tile_kind(const int tile, const int mt1, int& m0) {
   return tile == mt1 + 17 ? 3 : 4;
 }
 
-// NORM: the X of dW1 is gathered as k_ppo_rows loaded it, normalised by the bound table (the table has not moved in between: one stream)
-template <bool NORM>
-__global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad(const pgd_ppo_batch b, float* __restrict__ work, const ObsNorm nm) {
+// One workgroup of k_ppo_wgrad over ppo_work_of<DW, TS>'s scratch: the A of dW3^T is dOut [R16][DW], columns at or beyond DW zero.
+// NORM: the X of dW1 is gathered as k_ppo_rows loaded it, normalised by the bound table (the table has not moved in between: one stream).
+// The batch BY VALUE: by const reference all four kernels scheduled their prologue otherwise
+template <bool NORM, int DW, int TS>
+DEV void ppo_wgrad_tile(const pgd_ppo_batch b, float* __restrict__ work, const ObsNorm nm) {
   __shared__ float At[16 * (PPO_CHUNK + 2)];
   const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
   const int live16 = (n + 15) & ~15;
@@ -327,13 +337,13 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad(const pgd_ppo
   if (rbeg >= live16) return;
   const int rend = min(rbeg + PPO_PART, live16);
   const int in_dim = b.in_dim, net = (int)blockIdx.z;
-  const PpoWork wk = ppo_work(in_dim, b.rows, (int)gridDim.z);
+  const PpoWork wk = ppo_work_of<DW, TS>(in_dim, b.rows, (int)gridDim.z);
   const size_t plane = (size_t)wk.R16 * MLP_H;
   const float* __restrict__ H1g = work + wk.act + (size_t)net * 4 * plane;
   const float* __restrict__ H2g = H1g + plane;
   const float* __restrict__ dZ1g = H2g + plane;
   const float* __restrict__ dZ2g = dZ1g + plane;
-  const float* __restrict__ dOg = work + wk.dout + (size_t)net * wk.R16 * 4;
+  const float* __restrict__ dOg = work + wk.dout + (size_t)net * wk.R16 * DW;
   int m0;
   const int kind = ppo_tile_kind((int)blockIdx.x, wk.mt1, m0);
   const float* __restrict__ B = kind <= 1 ? dZ1g : (kind <= 3 ? dZ2g : H2g);
@@ -354,7 +364,7 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad(const pgd_ppo
       } else if (kind == 2) {
         v = H1g[(size_t)(r0 + j) * MLP_H + m0 + m];
       } else if (kind == 4) {
-        v = m < 4 ? dOg[(size_t)(r0 + j) * 4 + m] : 0.0f;
+        v = m < DW ? dOg[(size_t)(r0 + j) * DW + m] : 0.0f;
       } else {
         v = m == 0 ? 1.0f : 0.0f;
       }
@@ -371,13 +381,20 @@ __global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad(const pgd_ppo
     *reinterpret_cast<float4*>(out + (size_t)(r4 + i) * MLP_H + col) = make_float4(acc[0][i], acc[1][i], acc[2][i], acc[3][i]);
 }
 
+template <bool NORM>
+__global__ __launch_bounds__(WAVE * MLP_WAVES, 2) void k_ppo_wgrad(const pgd_ppo_batch b, float* __restrict__ work, const ObsNorm nm) {
+  ppo_wgrad_tile<NORM, 4, PPO_TS>(b, work, nm);
+}
+
 // grid (16 mt, networks): block (16 tile + m, net), thread c: the partials of entry (m, c) of the tile over the live partitions, in order
+// (K: the head's live columns -- the Gaussian's literal 4, the categorical head's ks + kt; columns [K, min(out_cols, 16)) are written as zero)
+template <int DW, int TS>
 DEV void ppo_reduce_entry(const pgd_ppo_batch& b, const bool critic, float* dW1, float* db1, float* dW2,
-                          float* db2, float* dW3, const int out_cols, const float* work) {
+                          float* db2, float* dW3, const int out_cols, const int K, const float* work) {
   const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
   const int p_live = (((n + 15) & ~15) + PPO_PART - 1) / PPO_PART;
   const int in_dim = b.in_dim, net = (int)blockIdx.y;
-  const PpoWork wk = ppo_work(in_dim, b.rows, (int)gridDim.y);
+  const PpoWork wk = ppo_work_of<DW, TS>(in_dim, b.rows, (int)gridDim.y);
   const int tile = (int)blockIdx.x >> 4, m = (int)blockIdx.x & 15, c = threadIdx.x;
   int m0;
   const int kind = ppo_tile_kind(tile, wk.mt1, m0);
@@ -395,15 +412,15 @@ DEV void ppo_reduce_entry(const pgd_ppo_batch& b, const bool critic, float* dW1,
   } else if (critic) {
     if (m == 0) dW3[c] = s;
   } else {
-    if (m < 4) dW3[(size_t)c * out_cols + m] = s;
+    if (m < K) dW3[(size_t)c * out_cols + m] = s;
     else if (m < out_cols) dW3[(size_t)c * out_cols + m] = 0.0f;  // (head columns that are never read; those from 16 on: k_ppo_zero_head)
   }
 }
 
 __global__ __launch_bounds__(MLP_H) void k_ppo_reduce(const pgd_ppo_batch b, const pgd_ppo_grads gr, const int out_cols, const float* __restrict__ work) {
   const bool critic = blockIdx.y != 0;
-  ppo_reduce_entry(b, critic, critic ? gr.vw1 : gr.w1, critic ? gr.vb1 : gr.b1, critic ? gr.vw2 : gr.w2, critic ? gr.vb2 : gr.b2,
-                   critic ? gr.vw3 : gr.w3, out_cols, work);
+  ppo_reduce_entry<4, PPO_TS>(b, critic, critic ? gr.vw1 : gr.w1, critic ? gr.vb1 : gr.b1, critic ? gr.vw2 : gr.w2, critic ? gr.vb2 : gr.b2,
+                              critic ? gr.vw3 : gr.w3, out_cols, 4, work);
 }
 
 // head columns [16, out_cols) of dW3 and [4, out_cols) of db3: zero
@@ -559,11 +576,13 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ param, const f
   param[i] = (float)((double)param[i] - (double)lr * ((double)mi * (double)f[2]) / (sqrt((double)vi * (double)f[3]) + (double)eps));
 }
 
-// scratch of a gradient call over n_nets networks (0: in_dim or rows out of range)
-static size_t ppo_work_bytes(int in_dim, int rows, int n_nets) {
-  if (in_dim < 4 || in_dim > 4096 || ppo_lds_bytes(in_dim) > 65536 || rows < 1 || rows > PGD_PPO_ROWS_MAX) return 0;
-  return sizeof(float) * ppo_work(in_dim, rows, n_nets).total;
+// scratch of a gradient call over n_nets networks whose rows kernel takes lds_of(in_dim) bytes of LDS (0: in_dim or rows out of range)
+template <int DW, int TS>
+static size_t ppo_work_bytes_of(int in_dim, int rows, int n_nets, size_t (*lds_of)(int)) {
+  if (in_dim < 4 || in_dim > 4096 || lds_of(in_dim) > 65536 || rows < 1 || rows > PGD_PPO_ROWS_MAX) return 0;
+  return sizeof(float) * ppo_work_of<DW, TS>(in_dim, rows, n_nets).total;
 }
+static size_t ppo_work_bytes(int in_dim, int rows, int n_nets) { return ppo_work_bytes_of<4, PPO_TS>(in_dim, rows, n_nets, ppo_lds_bytes); }
 
 // pgd_ppo_grad and pgd_ppo_grad_cost are one body: pgd_safe.h, behind the three-network kernels
 static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,

@@ -165,9 +165,9 @@ __global__ __launch_bounds__(MLP_H) void k_ppo_reduce_cost(const pgd_ppo_batch b
   const int y = (int)blockIdx.y;
   const pgd_ppo_grads& g = gr.g;
   const pgd_value_grads& c = gr.c;
-  ppo_reduce_entry(b, y != 0, y == 0 ? g.w1 : (y == 1 ? g.vw1 : c.w1), y == 0 ? g.b1 : (y == 1 ? g.vb1 : c.b1),
-                   y == 0 ? g.w2 : (y == 1 ? g.vw2 : c.w2), y == 0 ? g.b2 : (y == 1 ? g.vb2 : c.b2), y == 0 ? g.w3 : (y == 1 ? g.vw3 : c.w3),
-                   out_cols, work);
+  ppo_reduce_entry<4, PPO_TS>(b, y != 0, y == 0 ? g.w1 : (y == 1 ? g.vw1 : c.w1), y == 0 ? g.b1 : (y == 1 ? g.vb1 : c.b1),
+                              y == 0 ? g.w2 : (y == 1 ? g.vw2 : c.w2), y == 0 ? g.b2 : (y == 1 ? g.vb2 : c.b2),
+                              y == 0 ? g.w3 : (y == 1 ? g.vw3 : c.w3), out_cols, 4, work);
 }
 
 __global__ __launch_bounds__(256) void k_ppo_stats_cost(const pgd_ppo_batch b, const pgd_ppo_grads gr, float* __restrict__ cost_b3,

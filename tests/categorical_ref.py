@@ -261,42 +261,14 @@ def emulate_forward(x, policy, bins, u=None):
     return index, _f32(logp[0] + logp[1])
 
 
-def _ordered_sum8(terms):
-    """terms [n, k] float32 -> [k]: tiles of 16 rows summed in row order, thread u takes tiles u, u + 8, ... in order, the eight u in order."""
-    n, k = terms.shape
-    tiles = (n + 15) // 16
-    pad = np.zeros((tiles * 16, k), dtype=np.float32)
-    pad[:n] = terms
-    ts = np.zeros((tiles, k), dtype=np.float32)
-    for q in range(16):
-        ts = _f32(ts + pad[q::16])
-    red = np.zeros((8, k), dtype=np.float32)
-    for t in range(tiles):
-        red[t % 8] = _f32(red[t % 8] + ts[t])
-    out = np.zeros(k, dtype=np.float32)
-    for u in range(8):
-        out = _f32(out + red[u])
-    return out
+def cat_head(K):
+    """The head of k_ppo_rows_cat for the emulation (ppo_ref.Head): K logits off the matrix cores, dOut W3^T as fma from zero over the K
+    columns, the tile sums 8-strided."""
+    return pp.Head(K, lambda h2, w3, b3: emulate_logits(h2, w3, b3, K), True, 8)
 
 
-def _emulate_net(x, net, d_out_fn, K, critic):
-    w1, b1, w2, b2, w3, b3 = [_f32(w) for w in net]
-    out_cols = w3.shape[1]
-    x = _f32(x)
-    h1, h2 = _hidden_dev(x, net)
-    o = _f32(ar._dots(h2, w3[:, :1], 16) + b3[:1]) if critic else emulate_logits(h2, w3, b3, K)
-    d_out, extra = d_out_fn(o)
-    acc = np.zeros((x.shape[0], H), dtype=np.float32)
-    for k in range(K):  # fma(dO_k, W3[:, k], acc), the columns in order from zero
-        acc = _f32(acc.astype(np.float64) + d_out[:, k, None].astype(np.float64) * w3[None, :, k].astype(np.float64))
-    dz2 = _f32(acc.astype(np.float64) * pp._one_minus_sq(h2).astype(np.float64))
-    dz1 = _f32(pr._fma_chain(dz2, np.ascontiguousarray(w2.T)).astype(np.float64) * pp._one_minus_sq(h1).astype(np.float64))
-    ones = np.ones((x.shape[0], 1), dtype=np.float32)
-    dw3 = np.zeros((H, out_cols), dtype=np.float32)
-    dw3[:, :K] = pp._wgrad(d_out, h2).T
-    db3 = np.zeros(out_cols, dtype=np.float32)
-    db3[:K] = _ordered_sum8(d_out)
-    return [pp._wgrad(x, dz1), pp._wgrad(ones, dz1)[0], pp._wgrad(h1, dz2), pp._wgrad(ones, dz2)[0], dw3, db3], extra
+# its critic: k_ppo_rows' dot product on sixteen lanes; one column from zero, 8-strided sums
+CRITIC_HEAD = pp.gaussian_head(1, 16)._replace(from_zero=True, strides=8)
 
 
 def emulate_grads(x, index, logp_old, adv, ret, policy, value, bins, clip=CLIP, vf_coef=VF_COEF, ent_coef=ENT_COEF, adv_stats=None):
@@ -305,7 +277,7 @@ def emulate_grads(x, index, logp_old, adv, ret, policy, value, bins, clip=CLIP, 
     in_dim = np.asarray(policy[0]).shape[0]
     x = _f32(np.asarray(x)[:, :in_dim])
     inv = float(np.float32(1.0 / n))
-    vf, ce = float(np.float32(vf_coef)), float(np.float32(ent_coef))
+    ce = float(np.float32(ent_coef))
 
     def actor(o):  # the row loss in double from the fp32 logits, rounded once
         A, logp, r, flows, rc, lpj, pj, hh, onehot, Htot = row_terms_f64(o.astype(np.float64), index, logp_old, adv,
@@ -315,20 +287,7 @@ def emulate_grads(x, index, logp_old, adv, ret, policy, value, bins, clip=CLIP, 
         t = _f32(np.stack([-np.minimum(r * A, rc * A), Htot, _f64(logp_old) - logp, (~flows).astype(np.float64), r], axis=1))
         return d, t
 
-    pg, t = _emulate_net(x, policy, actor, sum(bins), False)
-    sums = _ordered_sum8(t)
-    stats = np.zeros(8, dtype=np.float32)
-    stats[0] = n
-    stats[[1, 3, 4, 5, 6]] = _f32(sums * np.float32(inv))
-    vg = None
-    if value is not None:
-        def critic(o):
-            err = _f32(o[:, 0] - _f32(ret))
-            lv = _f32(_f32(np.float32(0.5) * err) * err)
-            return _f32(_f32(np.float32(vf) * err) * np.float32(inv))[:, None], lv[:, None]
-        vg, lv = _emulate_net(x, value, critic, 1, True)
-        stats[2] = _f32(_ordered_sum8(lv)[0] * np.float32(inv))
-    return dict(stats=stats, policy=pg, value=vg)
+    return pp.emulate_update(x, ret, policy, value, actor, cat_head(sum(bins)), CRITIC_HEAD, vf_coef)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -436,11 +395,7 @@ def grad_case(c):
     return _grad_case(_key(c))
 
 
-def subset_case(case, sel):
-    out = dict(case)
-    for key in ("x", "index", "logp_old", "adv", "ret", "branch"):
-        out[key] = case[key][sel]
-    return out
+subset_case = pp.subset_case
 
 
 @functools.lru_cache(maxsize=None)
@@ -479,10 +434,4 @@ def compared_grad_cases():
         yield "list: minibatch %d of %d" % (j, LIST_MB), subset_case(grad_case(LIST_CASE), sel), _reference(_key(LIST_CASE), True, tuple(sel)), True
 
 
-grad_errors = pp.grad_errors
-
-
-def stat_errors(got, ref):
-    """The normalised error of each statistics slot 1 .. 6 (what grad_errors takes the maximum of), for a test's printout."""
-    norm = np.where(ref["stat_norm"][1:7] > 0, ref["stat_norm"][1:7], 1.0)
-    return np.abs(_f64(got["stats"])[1:7] - ref["stats"][1:7]) / norm
+grad_errors, stat_errors = pp.grad_errors, pp.stat_errors

@@ -18,6 +18,7 @@ contributions are all zero must be exactly zero.
 Tolerances: each *_MEASURED constant is the largest normalised error of the emulation against float64 over exactly the cases named in
 its comment; the tolerance is twice that; the CPU test measures again and holds the emulation below half of the tolerance.
 """
+import collections
 import functools
 import zlib
 
@@ -208,8 +209,9 @@ def _one_minus_sq(h):
     return _f32(1.0 - h.astype(np.float64) ** 2)  # fma(-h, h, 1): one rounding
 
 
-def _ordered_sum(terms):
-    """terms [n, k] float32 -> [k]: tiles of 16 rows summed in row order, thread u takes tiles u, u + 16, ... in order, the sixteen u in order."""
+def _ordered_sum(terms, strides=16):
+    """terms [n, k] float32 -> [k]: tiles of 16 rows summed in row order, thread u takes tiles u, u + strides, ... in order, the `strides`
+    values of u in order (k_ppo_stats: 16; k_ppo_stats_cat: 8)."""
     n, k = terms.shape
     tiles = (n + 15) // 16
     pad = np.zeros((tiles * 16, k), dtype=np.float32)
@@ -217,11 +219,11 @@ def _ordered_sum(terms):
     ts = np.zeros((tiles, k), dtype=np.float32)
     for q in range(16):
         ts = _f32(ts + pad[q::16])
-    red = np.zeros((16, k), dtype=np.float32)
+    red = np.zeros((strides, k), dtype=np.float32)
     for t in range(tiles):
-        red[t % 16] = _f32(red[t % 16] + ts[t])
+        red[t % strides] = _f32(red[t % strides] + ts[t])
     out = np.zeros(k, dtype=np.float32)
-    for u in range(16):
+    for u in range(strides):
         out = _f32(out + red[u])
     return out
 
@@ -234,26 +236,56 @@ def _wgrad(a, dz):
     return out
 
 
-def _emulate_net(x, net, d_out_fn, heads, lanes):
+# What a head of a network is to the emulation: its live columns; out(h2, w3, b3) -> the head's outputs [n, cols] as its kernel forms them;
+# how dH2 = dOut W3^T starts -- from_zero False: dO_0 W3_0 as a PRODUCT, then fma with the columns behind it (ppo_rows_tile); True: fma over
+# all columns from zero (k_ppo_rows_cat) -- two recurrences on purpose, they round differently; and the strides of its tile sums.
+Head = collections.namedtuple("Head", "cols out from_zero strides")
+
+
+def gaussian_head(heads, lanes):
+    """The vector-ALU head of k_ppo_rows: `heads` dot products of 256 over `lanes` lanes each (the actor: 4 and 4; a critic: 1 and 16)."""
+    return Head(heads, lambda h2, w3, b3: _f32(ar._dots(h2, w3[:, :heads], lanes) + b3[:heads]), False, 16)
+
+
+def _emulate_net(x, net, d_out_fn, head):
     w1, b1, w2, b2, w3, b3 = [_f32(w) for w in net]
     out_cols = w3.shape[1]
     x = _f32(x)
     h1 = tanh_dev(_f32(pr._fma_chain(x, w1) + b1))
     h2 = tanh_dev(_f32(pr._fma_chain(h1, w2) + b2))
-    o = _f32(ar._dots(h2, w3[:, :heads], lanes) + b3[:heads])
-    d_out, extra = d_out_fn(o)
-    acc = None
-    for k in range(heads):  # dO0 W3[:, 0], then fma with columns 1, 2, 3
+    d_out, extra = d_out_fn(head.out(h2, w3, b3))
+    acc = np.zeros((x.shape[0], H), dtype=np.float32) if head.from_zero else None
+    for k in range(head.cols):
         prod = d_out[:, k, None].astype(np.float64) * w3[None, :, k].astype(np.float64)
         acc = _f32(prod) if acc is None else _f32(acc.astype(np.float64) + prod)
     dz2 = _f32(acc.astype(np.float64) * _one_minus_sq(h2).astype(np.float64))
     dz1 = _f32(pr._fma_chain(dz2, np.ascontiguousarray(w2.T)).astype(np.float64) * _one_minus_sq(h1).astype(np.float64))
     ones = np.ones((x.shape[0], 1), dtype=np.float32)
     dw3 = np.zeros((H, out_cols), dtype=np.float32)
-    dw3[:, :heads] = _wgrad(d_out, h2).T
+    dw3[:, :head.cols] = _wgrad(d_out, h2).T
     db3 = np.zeros(out_cols, dtype=np.float32)
-    db3[:heads] = _ordered_sum(d_out)
+    db3[:head.cols] = _ordered_sum(d_out, head.strides)
     return [_wgrad(x, dz1), _wgrad(ones, dz1)[0], _wgrad(h1, dz2), _wgrad(ones, dz2)[0], dw3, db3], extra
+
+
+def emulate_update(x, ret, policy, value, actor, head, critic_head, vf_coef):
+    """What emulate_grads of either head is around its row loss `actor(o) -> (dOut [n, cols], the five loss terms [n, 5])`: the actor's
+    network, the critic's (value None: none) with its loss, and the statistics.  x: float32 [n, in_dim], n >= 1."""
+    n = x.shape[0]
+    inv, vf = np.float32(1.0 / n), np.float32(vf_coef)
+    pg, t = _emulate_net(x, policy, actor, head)
+    stats = np.zeros(8, dtype=np.float32)
+    stats[0] = n
+    stats[[1, 3, 4, 5, 6]] = _f32(_ordered_sum(t, head.strides) * inv)
+    vg = None
+    if value is not None:
+        def critic(o):
+            err = _f32(o[:, 0] - _f32(ret))
+            lv = _f32(_f32(np.float32(0.5) * err) * err)
+            return _f32(_f32(vf * err) * inv)[:, None], lv[:, None]
+        vg, lv = _emulate_net(x, value, critic, critic_head)
+        stats[2] = _f32(_ordered_sum(lv, critic_head.strides)[0] * inv)
+    return dict(stats=stats, policy=pg, value=vg)
 
 
 def emulate_grads(x, action, logp_old, adv, ret, policy, value, clip=CLIP, vf_coef=VF_COEF, ent_coef=ENT_COEF, adv_stats=None):
@@ -262,7 +294,7 @@ def emulate_grads(x, action, logp_old, adv, ret, policy, value, clip=CLIP, vf_co
     in_dim = np.asarray(policy[0]).shape[0]
     x = _f32(np.asarray(x)[:, :in_dim])
     inv = float(np.float32(1.0 / n))
-    vf, ce = float(np.float32(vf_coef)), float(np.float32(ent_coef))
+    ce = float(np.float32(ent_coef))
 
     def actor(o):  # the row loss in double from the fp32 heads
         o64 = o.astype(np.float64)
@@ -274,20 +306,7 @@ def emulate_grads(x, action, logp_old, adv, ret, policy, value, clip=CLIP, vf_co
                            (~flows).astype(np.float64), r], axis=1))
         return d, t
 
-    pg, t = _emulate_net(x, policy, actor, 4, 4)
-    sums = _ordered_sum(t)
-    stats = np.zeros(8, dtype=np.float32)
-    stats[0] = n
-    stats[[1, 3, 4, 5, 6]] = _f32(sums * np.float32(inv))
-    vg = None
-    if value is not None:
-        def critic(o):
-            err = _f32(o[:, 0] - _f32(ret))
-            lv = _f32(_f32(np.float32(0.5) * err) * err)
-            return _f32(_f32(np.float32(vf) * err) * np.float32(inv))[:, None], lv[:, None]
-        vg, lv = _emulate_net(x, value, critic, 1, 16)
-        stats[2] = _f32(_ordered_sum(lv)[0] * np.float32(inv))
-    return dict(stats=stats, policy=pg, value=vg)
+    return emulate_update(x, ret, policy, value, actor, gaussian_head(4, 4), gaussian_head(1, 16), vf_coef)
 
 
 def _thread_strided(terms, fma_sq=False, threads=256):
@@ -408,9 +427,11 @@ def list_subsets():
 
 
 def subset_case(case, sel):
+    """The rows `sel` of a case of either head: every per-row array it has (`action` the Gaussian's, `index` the categorical's)."""
     out = dict(case)
-    for key in ("x", "action", "logp_old", "adv", "ret", "branch"):
-        out[key] = case[key][sel]
+    for key in ("x", "action", "index", "logp_old", "adv", "ret", "branch"):
+        if key in case:
+            out[key] = case[key][sel]
     return out
 
 
@@ -474,6 +495,12 @@ def grad_errors(got, ref):
     assert float(got["stats"][0]) == ref["stats"][0] and float(got["stats"][7]) == 0.0
     es = normalised_error(np.asarray(got["stats"])[1:7], ref["stats"][1:7], ref["stat_norm"][1:7])
     return eg, es
+
+
+def stat_errors(got, ref):
+    """The normalised error of each statistics slot 1 .. 6 (what grad_errors takes the maximum of), for a test's printout."""
+    norm = np.where(ref["stat_norm"][1:7] > 0, ref["stat_norm"][1:7], 1.0)
+    return np.abs(_f64(got["stats"])[1:7] - ref["stats"][1:7]) / norm
 
 
 def closed_loop_case():

@@ -8,6 +8,7 @@ import pytest
 
 from tests import categorical_ref as cf
 from tests import train_util as tu
+from tests.ppo_util import Problem, check, into_sentinels, shapes
 from tests.train_util import SENT, bits_equal, dev
 
 pytestmark = pytest.mark.gpu
@@ -164,64 +165,24 @@ def test_row_list_form():
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. pgd_ppo_grad_cat against float64
 # ---------------------------------------------------------------------------------------------------------------------
-class Problem:
-    """The rollout arrays of a checker case on the device: n_rows rows, of which `where` hold the case's rows in minibatch order; every
-    other row holds NaN (index: a wild number) in every array."""
-    def __init__(self, case, n_rows=None, where=None, index=None, count=None, n_list=None):
-        rows = case["x"].shape[0]
-        self.n_rows = n_rows = rows if n_rows is None else n_rows
-        where = np.arange(rows) if where is None else np.asarray(where)
-        self.t = {}
-        for key, width in (("x", case["x"].shape[1]), ("logp_old", 0), ("adv", 0), ("ret", 0)):
-            a = np.full((n_rows, width) if width else (n_rows, ), np.nan, dtype=np.float32)
-            a[where] = case[key]
-            self.t[key] = dev(a)
-        ai = np.full((n_rows, 2), 2 ** 30, dtype=np.int32)
-        ai[where] = case["index"]
-        self.t["index"] = dev(ai)
-        self.case = case
-        self.index = dev(np.asarray(index, dtype=np.int32)) if index is not None else None
-        self.count = dev(np.array([count], dtype=np.int32)) if count is not None else None
-        self.n_list = int(n_list if n_list is not None else (len(index) if index is not None else n_rows))
-        self.stats_in = dev(case["adv_stats"]) if case["adv_stats"] is not None else None
-        self.pw = tuple(dev(w) for w in case["policy"])
-        self.vw = tuple(dev(w) for w in case["value"])
-
-
 def _grad(eng, P, start=0, stride=1, rows=None, critic=True, ent_coef=cf.ENT_COEF):
-    """One ppo_grad_cat into sentinel-filled buffers and NaN-filled scratch -> dict(stats, policy, value, raw)."""
-    import torch
-    from tests.ppo_util import shapes
-    k, oc = P.case["in_dim"], P.case["policy"][4].shape[1]
+    """One ppo_grad_cat into sentinel-filled buffers and NaN-filled scratch (ppo_util.into_sentinels)."""
+    k = P.case["in_dim"]
     rows = P.n_list if rows is None else rows
-    ps, vs = shapes(k, oc)
-    pg = [torch.full(s, SENT, dtype=torch.float32, device="cuda") for s in ps]
-    vg = [torch.full(s, SENT, dtype=torch.float32, device="cuda") for s in vs]
-    stats = torch.full((8, ), SENT, dtype=torch.float32, device="cuda")
     need = eng.ppo_cat_work_bytes(k, rows, critic)
     assert need >= eng.ppo_work_bytes(k, rows, critic) > 0
-    work = torch.full(((need + 3) // 4, ), float("nan"), dtype=torch.float32, device="cuda")
-    eng.ppo_grad_cat(P.pw, P.vw if critic else None, pg, vg if critic else None, P.case["bins"], P.t["x"], P.t["index"], P.t["logp_old"],
-                     P.t["adv"], P.t["ret"], stats, work, start=start, stride=stride, rows=rows, index=P.index, count=P.count,
-                     n_list=P.n_list, adv_stats=P.stats_in, clip=cf.CLIP, vf_coef=cf.VF_COEF, ent_coef=ent_coef, in_dim=k)
-    eng.sync()
-    torch.cuda.synchronize()
-    out = dict(stats=stats.cpu().numpy(), policy=[g.cpu().numpy() for g in pg], value=[g.cpu().numpy() for g in vg] if critic else None,
-               raw=[stats] + pg + (vg if critic else []))
-    for g in out["policy"] + (out["value"] or []):
-        assert not (g == SENT).any(), "a gradient entry was not written"
-    if not critic:
-        assert all(bool((g == SENT).all()) for g in vg)
-    return out
+
+    def call(pg, vg, stats, work):
+        eng.ppo_grad_cat(P.pw, P.vw if critic else None, pg, vg if critic else None, P.case["bins"], P.t["x"], P.t["index"], P.t["logp_old"],
+                         P.t["adv"], P.t["ret"], stats, work, start=start, stride=stride, rows=rows, index=P.index, count=P.count,
+                         n_list=P.n_list, adv_stats=P.stats_in, clip=cf.CLIP, vf_coef=cf.VF_COEF, ent_coef=ent_coef, in_dim=k)
+        eng.sync()
+
+    return into_sentinels(P, critic, (need + 3) // 4, call)
 
 
 def _check(got, ref, what, K):
-    eg, es = cf.grad_errors(got, ref)
-    tol_g, tol_s = cf.tolerances(int(ref["stats"][0]))
-    print("%s: gradients %.3f of %.2e, statistics %.3f of %.2e; per slot 1 .. 6: %s" % (
-        what, eg / tol_g, tol_g, es / tol_s, tol_s, " ".join("%.2e" % e for e in cf.stat_errors(got, ref))))
-    assert eg < tol_g and es < tol_s, (what, eg, tol_g, es, tol_s)
-    assert (got["policy"][4][:, K:] == 0).all() and (got["policy"][5][K:] == 0).all(), (what, "the surplus head columns")
+    check(got, ref, what, live=K, tolerances=cf.tolerances)
 
 
 @pytest.mark.parametrize("c", cf.GRAD_CASES + cf.SWEEP_CASES + cf.MORE_CASES, ids=lambda c: "rows%d-in%d-bins%dx%d-cols%d" % (c["rows"], c["in_dim"], *c["bins"], c["out_cols"]))
@@ -284,7 +245,6 @@ def test_refusals_of_the_row_list_and_gradient_calls():
     torch.cuda.synchronize()
     assert all(bool((t == SENT).all()) for t in (act, logp, value))
     # the gradient call
-    from tests.ppo_util import shapes
     g = cf.GRAD_CASES[1]
     gcase = cf.grad_case(g)
     P = Problem(gcase)
