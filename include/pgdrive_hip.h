@@ -724,6 +724,51 @@ size_t pgd_ppo_cost_work_bytes(int in_dim, int rows);
 int pgd_ppo_grad_cost(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
                       const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
                       float* d_stats /*[8]*/, void* d_work, size_t work_bytes);
+/* ---- Expert-guided PPO: the gradient that knows which rows the guardian overrode -------------------------------------------------------
+ * (No reference counterpart: the reference puts takeover and raw_action into the step info, agent_manager.py:187, and leaves their use
+ * to an RL library.)  Under a takeover the applied action is not the sampled one: the advantage of such a row credits an action the
+ * agent did not take, and the clipped surrogate would push the probability of the one it sampled.
+ * pgd_ppo_grad_guided: pgd_ppo_grad (cost_net, cost, cost_grads null) or pgd_ppo_grad_cost (all three given) -- one, two or three
+ * networks, the Gaussian head -- with a guide.  Notation, the minibatch rule, the critics, 1 / n and the arithmetic are pgd_ppo_grad's.
+ * Per live row p:
+ *   u     = guide->mask ? (mask[p] & mask_bits) != 0 : 1          the row is GUIDED
+ *   s     = !u || (mode & PGD_GUIDE_KEEP_SURROGATE)               the row carries the surrogate
+ *   e_k   = exp(-ls_k);   zt_k = (target[p][k] - mean_k) e_k;   c = u ? bc_coef / n : 0
+ *   g     = pgd_ppo_grad's dL/dlogp where s holds, 0 otherwise
+ *   dL/dmean_k = g z_k e_k - c zt_k e_k
+ *   dL/dls_k   = g (z_k^2 - 1) + c (1 - zt_k^2) - ent_coef / n
+ * that is L = (1/n) [ sum over s of the clipped surrogate's terms + bc_coef sum over u of -logp(target) ] + vf_coef L_v - ent_coef mean H.
+ * 1 / n is over ALL live rows of the minibatch: a masked row contributes zero and does not renormalise, so strided minibatches still
+ * sum to the whole.  The critics regress on ret (cost_ret) on every live row -- the returns are those of the guarded system -- and the
+ * entropy term applies to every live row.
+ * mask [n_rows] and target [n_rows][target_stride] are indexed by rollout ROW (not by list position), read at live rows only through
+ * the clamp of the index, the target only where u holds and only its columns 0 and 1: a NaN in the target of a free or dead row, or in
+ * columns 2 and 3 of a stride-4 target, reaches no output.  u and s SELECT: a row without the surrogate takes nothing from its action,
+ * advantage or logp_old.  The free part of dL/d(mean, ls) is formed from pgd_ppo_grad's operands in its order, in double, rounded once,
+ * and the imitation part is added only where u holds: with NO guided row the gradients and d_stats[0..7] are bit for bit pgd_ppo_grad's
+ * (with a cost net pgd_ppo_grad_cost's).
+ * d_stats, 12 floats: 0 n; 2 L_v, 3 mean H, 7 L_c (0 without a cost net): means over n; 1 L_pi, 4 mean (logp_old - logp), 5 the share
+ * of cut rows, 6 mean r: means over n_s, the rows with s, each 0 when n_s = 0 (slot 4 keeps pgd_adam_gated's meaning: it averages the
+ * rows that carry a ratio); 8 n_g, the guided live rows; 9 bc_loss = the mean of -logp(target) over n_g, 0 when n_g = 0; 10, 11 zero.
+ * Scratch: pgd_ppo_work_bytes / pgd_ppo_cost_work_bytes, unchanged (n_g and the sum of -logp(target) take two free slots of the
+ * tile-sum record).  Launches: pgd_ppo_grad's, with the rows kernel and the statistics kernel in their guided forms; same LDS and the
+ * same refusal of in_dim > 416; no atomics, deterministic; nothing is allocated; asynchronous, capturable from the first call.
+ * Refusals (PGD_ERR_ARG): pgd_ppo_grad's / pgd_ppo_grad_cost's, a cost net without cost or cost_grads (or the reverse), and the
+ * guide's: null guide or target, target_stride < 2, a mode bit other than PGD_GUIDE_KEEP_SURROGATE, bc_coef negative or not finite,
+ * mask_bits == 0 with a mask. */
+typedef struct pgd_ppo_guide {
+  const float*   target;        /* [n_rows][target_stride], by rollout ROW (not list position) */
+  const uint8_t* mask;          /* [n_rows] by row, or null: every live row is guided */
+  int32_t  target_stride;       /* >= 2; 2 for applied actions, 4 for pgd_guardian's d_trace */
+  uint32_t mask_bits;           /* row is guided iff (mask[row] & mask_bits) != 0 */
+  float    bc_coef;             /* >= 0, finite */
+  uint32_t mode;                /* PGD_GUIDE_KEEP_SURROGATE; other bits PGD_ERR_ARG */
+} pgd_ppo_guide;
+#define PGD_GUIDE_KEEP_SURROGATE 1u
+int pgd_ppo_grad_guided(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net /* or null */,
+                        const pgd_ppo_batch* batch, const pgd_ppo_cost* cost /* with cost_net */, const pgd_ppo_guide* guide,
+                        const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads /* with cost_net */,
+                        float* d_stats /*[12]*/, void* d_work, size_t work_bytes);
 /* ---- GAE that bootstraps through a time limit: terminal values on the device (single-agent engines) -------------------------------------
  * (No reference counterpart: the reference returns the terminal observation from env.step, base_env.py:303-344, and `max_step` in its
  * info, base_env.py:190-192; an RL library evaluates its critic on it on the host and patches the reward.)

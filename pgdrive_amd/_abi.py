@@ -121,9 +121,19 @@ class ValueGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
 
 
+class PPOGuide(C.Structure):
+    """pgd_ppo_guide: the target actions and the guided-row mask BY ROLLOUT ROW (mask None: every live row is guided), the target's row
+    stride in floats, the mask bits that make a row guided, the imitation weight and the GUIDE_* mode bits."""
+    _fields_ = [("target", C.c_void_p), ("mask", C.c_void_p), ("target_stride", C.c_int32), ("mask_bits", C.c_uint32), ("bc_coef", C.c_float),
+                ("mode", C.c_uint32)]
+
+
+GUIDE_KEEP_SURROGATE = 1  # PGD_GUIDE_KEEP_SURROGATE, a mode bit of pgd_ppo_grad_guided: a guided row keeps its clipped surrogate
 PPO_ROWS_MAX = 16777216
 PPO_STATS = ("n", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "ratio", "reserved")  # d_stats of pgd_ppo_grad
 PPO_COST_STATS = PPO_STATS[:7] + ("cost_value_loss", )  # d_stats of pgd_ppo_grad_cost
+# d_stats of pgd_ppo_grad_guided: slots 1, 4, 5, 6 average the rows that carry the surrogate, bc_loss the guided rows
+PPO_GUIDED_STATS = PPO_COST_STATS + ("guided_rows", "bc_loss", "reserved_10", "reserved_11")
 ADAM_GATE = ("stopped", "applied", "skipped", "skipped_now")  # d_gate of pgd_adam_gated, four int32
 LAGRANGE_STATE = ("lambda", "episode_cost", "episodes", "reserved")  # d_state of pgd_lagrange
 RN_FREEZE = 1  # PGD_RN_FREEZE, a mode bit of pgd_return_norm

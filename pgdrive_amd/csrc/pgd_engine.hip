@@ -39,9 +39,10 @@ static Switches read_switches() {
           rowz && rowz[0] != '0', on("PGD_NO_UNI"), pack ? (atoi(pack) != 0 ? 1 : 0) : -1, on("PGD_NO_IMASK") ? 0 : (on("PGD_IMASK") ? 1 : -1)};
 }
 // The kernels that take more than 48 KB of dynamic LDS at wide inputs: their limit is raised once per engine (raise_lds_limit)
-// (LDS_AC .. LDS_PPO_ROWS_CAT: the instantiations that normalise their observation rows, pgd_obs_norm_bind, have slots of their own behind them)
+// (LDS_AC .. LDS_PPO_ROWS_COST_GUIDED: the instantiations that normalise their observation rows, pgd_obs_norm_bind, have slots of their own behind them)
 enum LdsKernel { LDS_MLP, LDS_MLP_TANH, LDS_MLP_BF, LDS_MLP_BF_TANH, LDS_AC, LDS_AC_ROWS, LDS_AC_COST, LDS_PPO_ROWS, LDS_PPO_ROWS_COST, LDS_TERM_VALUE,
-                 LDS_AC_CAT, LDS_AC_CAT_ROWS, LDS_PPO_ROWS_CAT, LDS_NORM_FIRST, LDS_GUARD = LDS_NORM_FIRST + (LDS_PPO_ROWS_CAT - LDS_AC + 1), LDS_GUARD_LEGACY, LDS_KERNELS };
+                 LDS_AC_CAT, LDS_AC_CAT_ROWS, LDS_PPO_ROWS_CAT, LDS_PPO_ROWS_GUIDED, LDS_PPO_ROWS_COST_GUIDED, LDS_NORM_FIRST,
+                 LDS_GUARD = LDS_NORM_FIRST + (LDS_PPO_ROWS_COST_GUIDED - LDS_AC + 1), LDS_GUARD_LEGACY, LDS_KERNELS };
 // the tables of the arena, in the order of their offsets (what follows the scenarios first, what follows the maps behind it)
 enum ArenaTable { TB_SCEN, TB_SCEN_MAP, TB_SPAWNS, TB_SPAWN_HV, TB_RESET_IMG, TB_RESPAWN_IMG, TB_MAPS, TB_LANES, TB_ROADS, TB_BOXES, TB_CELL_START,
                   TB_CELL_ITEMS, TB_CELL_BOXES, TB_CELL_EXT, TB_LANE_NAV, TB_BEAM, TB_COUNT };
@@ -1471,6 +1472,7 @@ int pgd_destroy(pgd_handle h) {
 #include "pgd_step_info.h"
 #include "pgd_ppo.h"
 #include "pgd_safe.h"
+#include "pgd_guided.h"
 #include "pgd_categorical.h"
 #include "pgd_timelimit.h"
 #include "pgd_guardian.h"

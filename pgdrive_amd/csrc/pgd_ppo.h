@@ -27,7 +27,8 @@
 // The categorical head (pgd_categorical.h) differs from this one in the width of dOut and the length of the tile-sum record: the scratch's
 // plan (ppo_work_of), the weight-gradient body (ppo_wgrad_tile) and the reduction body (ppo_reduce_entry) take the two as template
 // constants <DW, TS>, and k_ppo_wgrad_cat / k_ppo_reduce_cat call them with 16 and 24 where the kernels here say 4 and PPO_TS.
-// ppo_rows_tile and ppo_stats_block serve this head only (what was tried).
+// ppo_rows_tile and ppo_stats_block serve this head only (what was tried); with their switch GUIDED they are the
+// bodies of pgd_guided.h's kernels as well, and without it the code they were.
 // Deterministic: no atomics; a row's numbers never depend on its tile neighbours; every sum over rows has one owner and a fixed order
 // (rows within a partition, partitions in order; rows within a tile, tiles 16-strided, the sixteen strides in order).
 //
@@ -46,7 +47,7 @@
 
 #define PPO_PART 1024   // rows per partial sum of a weight gradient
 #define PPO_CHUNK 256   // rows of A^T staged in LDS at a time
-#define PPO_TS 16       // floats per tile-sum record: 0 L_pi, 1 H, 2 logp_old - logp, 3 cut, 4 r, 5..8 dOut (actor); 9 L_v, 10 dv (critic); 11 L_c, 12 dv_c (cost critic, pgd_safe.h)
+#define PPO_TS 16       // floats per tile-sum record: 0 L_pi, 1 H, 2 logp_old - logp, 3 cut, 4 r, 5..8 dOut (actor); 9 L_v, 10 dv (critic); 11 L_c, 12 dv_c (cost critic, pgd_safe.h); 13 guided rows, 14 -logp(target) (pgd_guided.h)
 #define PPO_ST 12       // loss terms per row in LDS (the record's first eleven slots)
 #define PPO_BATCH 8     // reads a thread of a one-workgroup reduction keeps in flight: the loop waits for memory once per batch, the sum keeps its order
 #define PPO_LOG_2PI 1.8378770664093453f
@@ -146,11 +147,15 @@ __global__ __launch_bounds__(MLP_H) void k_ppo_prep(const pgd_actor_critic nets,
 // One workgroup of k_ppo_rows: network blockIdx.y of gridDim.y -- the actor (critic false) or a critic on (W1 .. b3) with the target `ret` and
 // the coefficient `vf_coef`, whose two tile sums go to slots 9 + ts_shift and 10 + ts_shift of the tile's record -- for the 16 minibatch
 // positions blockIdx.x * 16 + [0, 16).  k_ppo_rows and k_ppo_rows_cost (pgd_safe.h) choose the network and call it.
-template <bool NORM>
+// GUIDED (k_ppo_rows_guided, k_ppo_rows_cost_guided: pgd_guided.h, which states the slots): the actor's row lane knows which rows the
+// expert overrode (`gd`), drops their surrogate and imitates their target; slots 9 and 10 of the row record, the critic's in ITS
+// workgroup, hold the guided bit and -logp(target) in the actor's and go to slots 13 and 14 of the tile's record.  Not GUIDED: `gd` is
+// never looked at and every line below compiles to what it compiled to without the switch.
+template <bool NORM, bool GUIDED = false>
 DEV void ppo_rows_tile(const bool critic, const float* W1, const float* b1, const float* W2,
                        const float* b2, const float* W3, const float* b3, const int out_cols,
                        const float* ret, const float vf_coef, const int ts_shift, const pgd_ppo_batch& b, const pgd_ppo_hyper& hp,
-                       float* work, const ObsNorm nm) {
+                       float* work, const ObsNorm nm, const pgd_ppo_guide* gd = nullptr) {
   extern __shared__ float mlp_lds[];
   const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
   const int i0 = (int)blockIdx.x * MLP_ROWS;  // (the tile's first minibatch position)
@@ -238,6 +243,7 @@ DEV void ppo_rows_tile(const bool critic, const float* W1, const float* b1, cons
     const float m0 = __shfl(v, l16), m1 = __shfl(v, l16 + 4), ls0 = __shfl(v, l16 + 8), ls1 = __shfl(v, l16 + 12);
     if ((lane & 15) == 0) {
       float d[4] = {0.0f, 0.0f, 0.0f, 0.0f}, t[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+      [[maybe_unused]] float gt[2] = {0.0f, 0.0f};  // GUIDED: the guided bit u and -logp(target)
       if (row >= 0) {
         // in double, from the fp32 heads: four lanes of a wave are here, once per tile, and the ratio and the cut are where a rounding
         // of logp shows (the library's build makes expf the 1 ulp exp2 form: pgdrive_amd/build.py)
@@ -253,6 +259,36 @@ DEV void ppo_rows_tile(const bool critic, const float* W1, const float* b1, cons
         const bool flows = s1 <= s2;
         const double g = flows ? -A * ratio * inv : 0.0;  // dL / dlogp
         const double ge = (double)hp.ent_coef * inv;
+        if constexpr (GUIDED) {
+          // u and sur SELECT: a row without the surrogate takes nothing from its action, advantage or old log-probability, and a
+          // target is read only where u holds.  The free part is the expressions of the other branch SPELLED AS THERE and selected
+          // afterwards -- the build contracts g (z^2 - 1) - ge into one fma, and a select in front of the subtraction moved the
+          // contraction to the other product: another rounding of the double --, rounded once with what u adds.
+          const bool u = gd->mask ? (gd->mask[row] & gd->mask_bits) != 0u : true;
+          const bool sur = !u || (gd->mode & PGD_GUIDE_KEEP_SURROGATE) != 0u;
+          const double f0 = g * z0 * e0, f1 = g * z1 * e1, f2 = g * (z0 * z0 - 1.0) - ge, f3 = g * (z1 * z1 - 1.0) - ge;
+          double d0 = sur ? f0 : 0.0, d1 = sur ? f1 : 0.0, d2 = sur ? f2 : -ge, d3 = sur ? f3 : -ge;
+          if (u) {
+            const float* tg = gd->target + (size_t)row * gd->target_stride;
+            const double c = (double)gd->bc_coef * inv;
+            const double zt0 = ((double)tg[0] - (double)m0) * e0, zt1 = ((double)tg[1] - (double)m1) * e1;
+            d0 -= c * zt0 * e0;
+            d1 -= c * zt1 * e1;
+            d2 += c * (1.0 - zt0 * zt0);
+            d3 += c * (1.0 - zt1 * zt1);
+            gt[0] = 1.0f;
+            gt[1] = (float)(0.5 * (zt0 * zt0 + zt1 * zt1) + (double)ls0 + (double)ls1 + 1.8378770664093453);
+          }
+          d[0] = (float)d0;
+          d[1] = (float)d1;
+          d[2] = (float)d2;
+          d[3] = (float)d3;
+          t[0] = sur ? (float)(-(s1 < s2 ? s1 : s2)) : 0.0f;
+          t[1] = ls0 + ls1 + PPO_LOG_2PIE;
+          t[2] = sur ? (float)(lpo - logp) : 0.0f;
+          t[3] = sur && !flows ? 1.0f : 0.0f;
+          t[4] = sur ? (float)ratio : 0.0f;
+        } else {
         d[0] = (float)(g * z0 * e0);
         d[1] = (float)(g * z1 * e1);
         d[2] = (float)(g * (z0 * z0 - 1.0) - ge);
@@ -262,6 +298,7 @@ DEV void ppo_rows_tile(const bool critic, const float* W1, const float* b1, cons
         t[2] = (float)(lpo - logp);
         t[3] = flows ? 0.0f : 1.0f;
         t[4] = (float)ratio;
+        }
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) dO[r * 4 + k] = d[k];
@@ -269,14 +306,18 @@ DEV void ppo_rows_tile(const bool critic, const float* W1, const float* b1, cons
       for (int k = 0; k < 5; ++k) st[r * PPO_ST + k] = t[k];
 #pragma unroll
       for (int k = 0; k < 4; ++k) st[r * PPO_ST + 5 + k] = d[k];
+      if constexpr (GUIDED) {
+        st[r * PPO_ST + 9] = gt[0];
+        st[r * PPO_ST + 10] = gt[1];
+      }
     }
   }
   __syncthreads();
-  // the tile's sums, rows in order: one owner per slot
-  if (tid < 11 && (critic ? tid >= 9 : tid < 9)) {
+  // the tile's sums, rows in order: one owner per slot (GUIDED: the actor's slots 9 and 10 are the record's 13 and 14)
+  if (tid < 11 && (critic ? tid >= 9 : (GUIDED || tid < 9))) {
     float s = 0.0f;
     for (int q = 0; q < MLP_ROWS; ++q) s += st[q * PPO_ST + tid];
-    tsum[critic ? tid + ts_shift : tid] = s;
+    tsum[critic ? tid + ts_shift : (GUIDED && tid >= 9 ? tid + 4 : tid)] = s;
   }
   if (tid < MLP_ROWS * 4) dOg[(size_t)i0 * 4 + tid] = dO[tid];
   // H1, H2 out; dZ2 = (dOut W3^T)(1 - H2^2) in H2's place and out
@@ -434,8 +475,11 @@ __global__ __launch_bounds__(MLP_H) void k_ppo_zero_head(float* __restrict__ dW3
 // ONE workgroup: slot s of the tile sums over the live tiles -- thread (s, u) takes tiles u, u + 16, ... in order, then the sixteen u in
 // order -- -> d_stats and db3
 // (cost_b3 set: three networks, the cost critic's sums in slots 11 and 12 -> stats[7] and cost_b3[0]; k_ppo_stats_cost, pgd_safe.h)
+// (GUIDED, k_ppo_stats_guided of pgd_guided.h: slots 13 and 14 as well, twelve statistics; n_g = slot 13, a sum of ones, exact up to
+// PGD_PPO_ROWS_MAX; the surrogate's means are over n_s = n with `keep`, n - n_g without: with n_g = 0 the expressions of the other branch)
+template <bool GUIDED = false>
 DEV void ppo_stats_block(const pgd_ppo_batch& b, const pgd_ppo_grads& gr, const int has_critic, float* cost_b3,
-                         const float* work, float* stats) {
+                         const float* work, float* stats, const int keep = 0) {
   __shared__ float red[16][PPO_TS];
   __shared__ float tot[PPO_TS];
   const int n = ppo_live(ppo_count(b.count, b.n_list), b.start, b.stride, b.rows);
@@ -443,7 +487,7 @@ DEV void ppo_stats_block(const pgd_ppo_batch& b, const pgd_ppo_grads& gr, const 
   const PpoWork wk = ppo_work(b.in_dim, b.rows, cost_b3 ? 3 : (has_critic ? 2 : 1));
   const float* __restrict__ tsum = work + wk.tsum;
   const int s = threadIdx.x & 15, u = threadIdx.x >> 4;
-  const bool used = s < 9 || (has_critic && s < 11) || (cost_b3 && s < 13);
+  const bool used = s < 9 || (has_critic && s < 11) || (cost_b3 && s < 13) || (GUIDED && (s == 13 || s == 14));
   float a = 0.0f;
   if (used)
     for (int t0 = u; t0 < tiles; t0 += 16 * PPO_BATCH) {  // (PPO_BATCH reads in flight, then their sum in the same order)
@@ -466,13 +510,22 @@ DEV void ppo_stats_block(const pgd_ppo_batch& b, const pgd_ppo_grads& gr, const 
   __syncthreads();
   if (threadIdx.x == 0) {
     const float inv = n > 0 ? (float)(1.0 / (double)n) : 0.0f;
+    float inv_s = inv;  // (1 / n_s: the rows that carry the surrogate)
+    if constexpr (GUIDED) {
+      const int n_g = (int)tot[13], n_s = keep ? n : n - n_g;
+      inv_s = n_s > 0 ? (float)(1.0 / (double)n_s) : 0.0f;
+      stats[8] = (float)n_g;
+      stats[9] = n_g > 0 ? tot[14] * (float)(1.0 / (double)n_g) : 0.0f;
+      stats[10] = 0.0f;
+      stats[11] = 0.0f;
+    }
     stats[0] = (float)n;
-    stats[1] = tot[0] * inv;
+    stats[1] = tot[0] * inv_s;
     stats[2] = has_critic ? tot[9] * inv : 0.0f;
     stats[3] = tot[1] * inv;
-    stats[4] = tot[2] * inv;
-    stats[5] = tot[3] * inv;
-    stats[6] = tot[4] * inv;
+    stats[4] = tot[2] * inv_s;
+    stats[5] = tot[3] * inv_s;
+    stats[6] = tot[4] * inv_s;
     stats[7] = cost_b3 ? tot[11] * inv : 0.0f;
     gr.b3[0] = tot[5];
     gr.b3[1] = tot[6];
@@ -584,10 +637,10 @@ static size_t ppo_work_bytes_of(int in_dim, int rows, int n_nets, size_t (*lds_o
 }
 static size_t ppo_work_bytes(int in_dim, int rows, int n_nets) { return ppo_work_bytes_of<4, PPO_TS>(in_dim, rows, n_nets, ppo_lds_bytes); }
 
-// pgd_ppo_grad and pgd_ppo_grad_cost are one body: pgd_safe.h, behind the three-network kernels
+// pgd_ppo_grad, pgd_ppo_grad_cost and pgd_ppo_grad_guided are one body: pgd_guided.h, behind the three-network and the guided kernels
 static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
-                           const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
-                           float* d_stats, void* d_work, size_t work_bytes);
+                           const pgd_ppo_cost* cost, const pgd_ppo_guide* guide, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads,
+                           const pgd_value_grads* cost_grads, float* d_stats, void* d_work, size_t work_bytes);
 
 extern "C" {
 
@@ -595,7 +648,7 @@ size_t pgd_ppo_work_bytes(int in_dim, int rows, int has_critic) { return ppo_wor
 
 int pgd_ppo_grad(pgd_handle h, const pgd_actor_critic* nets, const pgd_ppo_batch* batch, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads,
                  float* d_stats, void* d_work, size_t work_bytes) {
-  return ppo_grad_launch(h, nets, nullptr, batch, nullptr, hyper, grads, nullptr, d_stats, d_work, work_bytes);
+  return ppo_grad_launch(h, nets, nullptr, batch, nullptr, nullptr, hyper, grads, nullptr, d_stats, d_work, work_bytes);
 }
 
 int pgd_adv_stats(pgd_handle h, const float* d_adv, const int32_t* d_index, const int32_t* d_count, int n_list, float* d_out) {

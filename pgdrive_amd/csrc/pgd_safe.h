@@ -206,50 +206,7 @@ static void ppo_zero_head_launch(hipStream_t s, const pgd_ppo_grads* grads, int 
   hipLaunchKernelGGL(k_ppo_zero_head, dim3(std::max(1, std::min(out_cols - 16, 64))), dim3(MLP_H), 0, s, grads->w3, grads->b3, out_cols);
 }
 
-// ---- the one body of pgd_ppo_grad (cost_net, cost, cost_grads null) and pgd_ppo_grad_cost: one, two or three networks -------------------
-static int ppo_grad_launch(pgd_handle h, const pgd_actor_critic* nets, const pgd_value_net* cost_net, const pgd_ppo_batch* batch,
-                           const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
-                           float* d_stats, void* d_work, size_t work_bytes) {
-  PpoPlan p;
-  const size_t lds = batch ? ppo_lds_bytes(batch->in_dim) : 0;
-  { int rc = ppo_grad_plan(h, nets, cost_net, batch, true, cost, hyper, grads, cost_grads, d_stats, d_work, work_bytes, lds, ppo_work, p); if (rc) return rc; }
-  const pgd_ppo_batch& b = *batch;
-  const bool bound = p.bound, critic = p.critic;
-  const int n_nets = p.n_nets, out_cols = p.out_cols;
-  const PpoWork wk = p.wk;
-  const ObsNorm nm = p.nm;
-  const auto rows_cost = bound ? k_ppo_rows_cost<true> : k_ppo_rows_cost<false>;
-  const auto rows_plain = bound ? k_ppo_rows<true> : k_ppo_rows<false>;
-  const auto wgrad = bound ? k_ppo_wgrad<true> : k_ppo_wgrad<false>;
-  HIPCHK(hipSetDevice(h->device));
-  { int rc = cost_net ? raise_lds_limit(h, lds_slot(LDS_PPO_ROWS_COST, bound), reinterpret_cast<const void*>(rows_cost), lds)
-                      : raise_lds_limit(h, lds_slot(LDS_PPO_ROWS, bound), reinterpret_cast<const void*>(rows_plain), lds);
-    if (rc) return rc; }
-  float* work = static_cast<float*>(d_work);
-  hipStream_t s = h->stream;
-  const dim3 prep(MLP_H, n_nets), rows(wk.R16 / 16, n_nets), reduce(16 * wk.mt, n_nets), tile(WAVE * MLP_WAVES);
-  if (cost_net) {
-    const SafeNets sn = {*nets, *cost_net};
-    hipLaunchKernelGGL(k_ppo_prep_cost, prep, dim3(MLP_H), 0, s, sn, work);
-    hipLaunchKernelGGL(rows_cost, rows, tile, lds, s, sn, b, *hyper, *cost, work, nm);
-  } else {
-    hipLaunchKernelGGL(k_ppo_prep, prep, dim3(MLP_H), 0, s, *nets, work);
-    hipLaunchKernelGGL(rows_plain, rows, tile, lds, s, *nets, b, *hyper, work, nm);
-  }
-  hipLaunchKernelGGL(wgrad, dim3(wk.mt, wk.P, n_nets), tile, 0, s, b, work, nm);
-  if (cost_net) {
-    const SafeGrads sg = {*grads, *cost_grads};
-    hipLaunchKernelGGL(k_ppo_reduce_cost, reduce, dim3(MLP_H), 0, s, b, sg, out_cols, work);
-  } else {
-    hipLaunchKernelGGL(k_ppo_reduce, reduce, dim3(MLP_H), 0, s, b, *grads, out_cols, work);
-  }
-  if (out_cols > 4) ppo_zero_head_launch(s, grads, out_cols);
-  if (cost_net) hipLaunchKernelGGL(k_ppo_stats_cost, dim3(1), dim3(256), 0, s, b, *grads, cost_grads->b3, work, d_stats);
-  else hipLaunchKernelGGL(k_ppo_stats, dim3(1), dim3(256), 0, s, b, *grads, critic ? 1 : 0, work, d_stats);
-  HIPCHK(hipGetLastError());
-  return PGD_OK;
-}
-
+// (the one body of pgd_ppo_grad, pgd_ppo_grad_cost and pgd_ppo_grad_guided, ppo_grad_launch: pgd_guided.h, behind the guided kernels)
 extern "C" {
 
 int pgd_mlp_actor_critic_cost(pgd_handle h, int group, const float* d_obs, int obs_stride, int in_dim, const pgd_actor_critic* nets,
@@ -300,7 +257,7 @@ int pgd_ppo_grad_cost(pgd_handle h, const pgd_actor_critic* nets, const pgd_valu
                       const pgd_ppo_cost* cost, const pgd_ppo_hyper* hyper, const pgd_ppo_grads* grads, const pgd_value_grads* cost_grads,
                       float* d_stats, void* d_work, size_t work_bytes) {
   if (!cost_net || !cost || !cost_grads) return PGD_ERR_ARG;
-  return ppo_grad_launch(h, nets, cost_net, batch, cost, hyper, grads, cost_grads, d_stats, d_work, work_bytes);
+  return ppo_grad_launch(h, nets, cost_net, batch, cost, nullptr, hyper, grads, cost_grads, d_stats, d_work, work_bytes);
 }
 
 }  // extern "C"

@@ -71,6 +71,9 @@ _SIGS = {
     "pgd_ppo_grad_cost": (C.c_int, [C.c_void_p, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.ValueNet), C.POINTER(_abi.PPOBatch),
                                     C.POINTER(_abi.PPOCost), C.POINTER(_abi.PPOHyper), C.POINTER(_abi.PPOGrads), C.POINTER(_abi.ValueGrads),
                                     C.c_void_p, C.c_void_p, C.c_size_t]),
+    "pgd_ppo_grad_guided": (C.c_int, [C.c_void_p, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.ValueNet), C.POINTER(_abi.PPOBatch),
+                                      C.POINTER(_abi.PPOCost), C.POINTER(_abi.PPOGuide), C.POINTER(_abi.PPOHyper), C.POINTER(_abi.PPOGrads),
+                                      C.POINTER(_abi.ValueGrads), C.c_void_p, C.c_void_p, C.c_size_t]),
     "pgd_mlp_terminal_value": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.ValueNet), C.POINTER(_abi.ValueNet),
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pgd_guardian": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(_abi.ActorCritic), C.POINTER(_abi.GuardianConfig)] +
@@ -733,8 +736,8 @@ class Engine:
         return stats
 
     def _ppo_batch(self, where, weights, grad_bufs, obs, actions, logp_old, adv, ret, cost_ret, stats, work, start, stride, rows, index, count,
-                   n_list, adv_stats, in_dim, cat=None):
-        """What ppo_grad, ppo_grad_cost and ppo_grad_cat share, checked: the rollout's tensors, the minibatch, `stats`, `work`, and the networks
+                   n_list, adv_stats, in_dim, cat=None, n_stats=8):
+        """What ppo_grad, ppo_grad_cost, ppo_grad_cat and ppo_grad_guided (`n_stats` 12) share, checked: the rollout's tensors, the minibatch, `stats`, `work`, and the networks
         with their gradient buffers -- `weights` and `grad_bufs` are (policy, value or None, cost or None) -> ActorCritic, ValueNet (or None),
         PPOBatch, PPOGrads, ValueGrads (or None).  `cat`: (bins, action_index) of ppo_grad_cat, which reads no `actions`.  Follows the
         caller's stream."""
@@ -757,7 +760,7 @@ class Engine:
         _need(0 <= n_list and (index is not None or n_list <= n_rows), where, "0 <= n_list <= the rows of obs wanted")
         rows = int(max(1, -(-(n_list - int(start)) // int(stride))) if rows is None else rows)
         _need(int(start) >= 0 and int(stride) >= 1 and 1 <= rows <= _abi.PPO_ROWS_MAX, where, "start >= 0, stride >= 1, rows <= PPO_ROWS_MAX wanted")
-        _dev(stats, t.float32, 8, where, "stats")
+        _dev(stats, t.float32, n_stats, where, "stats")
         need = self.ppo_cost_work_bytes(k, rows) if cw is not None else (self.ppo_work_bytes if cat is None else self.ppo_cat_work_bytes)(
             k, rows, vw is not None)
         _dev(work, None, None, where, "work", None, True, 16)
@@ -916,6 +919,39 @@ class Engine:
         pc = _abi.PPOCost(cost_ret.data_ptr(), float(cvf_coef))
         _chk(self.L.pgd_ppo_grad_cost(self.h, C.byref(nets), C.byref(cnet), C.byref(b), C.byref(pc), C.byref(hp), C.byref(grads), C.byref(cgrads),
                                       _p(stats), _p(work), work.numel() * work.element_size()), "pgd_ppo_grad_cost")
+        return stats
+
+    def ppo_grad_guided(self, policy_weights, value_weights, policy_grads, value_grads, obs, actions, logp_old, adv, ret, stats, work, target,
+                        mask=None, mask_bits=1, bc_coef=1.0, keep_surrogate=False, cost_weights=None, cost_grads=None, cost_ret=None, cvf_coef=0.5,
+                        start=0, stride=1, rows=None, index=None, count=None, n_list=None, adv_stats=None, clip=0.2, vf_coef=0.5, ent_coef=0.0,
+                        in_dim=None):
+        """ppo_grad -- with `cost_weights`, `cost_grads`, `cost_ret`: ppo_grad_cost -- that knows which rows an expert overrode
+        (pgd_ppo_grad_guided).  `target` float32 cuda [..., 2] or [..., 4] BY ROLLOUT ROW (the stride is its last dimension: 2 for a
+        collector's applied_actions, 4 for its guardian_trace, of which columns 0 and 1 are read); `mask` uint8 cuda by row, a row is
+        guided where (mask & mask_bits) != 0, None: every live row is.  A guided row drops its clipped surrogate (keep_surrogate: keeps
+        it) and adds bc_coef * -logp(target) / n to the loss; critics and the entropy term see every live row.  `stats` float32 cuda
+        [12] (_abi.PPO_GUIDED_STATS); `work` as for ppo_grad / ppo_grad_cost.  With no guided row the gradients and stats[0:8] are
+        those calls' bits.  Every other argument as for ppo_grad.  Asynchronous."""
+        where, t = "ppo_grad_guided", self.torch
+        _need(cost_weights is None or (cost_grads is not None and cost_ret is not None), where, "cost_weights come with cost_grads and cost_ret")
+        nets, cnet, b, grads, cgrads = self._ppo_batch(where, (policy_weights, value_weights, cost_weights), (policy_grads, value_grads, cost_grads),
+                                                       obs, actions, logp_old, adv, ret, cost_ret if cost_weights is not None else None, stats,
+                                                       work, start, stride, rows, index, count, n_list, adv_stats, in_dim, n_stats=12)
+        ts = int(target.shape[-1]) if target.dim() else 0
+        _need(ts in (2, 4), where, "target: a last dimension of 2 or 4 wanted, got shape %r" % (tuple(target.shape), ))
+        _dev(target, t.float32, None, where, "target", b.n_rows * ts)
+        _opt(mask, t.uint8, None, where, "mask", b.n_rows)
+        bc = float(bc_coef)
+        _need(0.0 <= bc < float("inf"), where, "bc_coef: a finite number >= 0 wanted, got %r" % (bc_coef, ))
+        _need(mask is None or 0 < int(mask_bits) < 256, where, "mask_bits: 1 .. 255 wanted with a mask, got %r" % (mask_bits, ))
+        gd = _abi.PPOGuide(target.data_ptr(), None if mask is None else mask.data_ptr(), ts, int(mask_bits) if mask is not None else 0, bc,
+                           _abi.GUIDE_KEEP_SURROGATE if keep_surrogate else 0)
+        hp = _abi.PPOHyper(float(clip), float(vf_coef), float(ent_coef))
+        pc = None if cnet is None else _abi.PPOCost(cost_ret.data_ptr(), float(cvf_coef))
+        _chk(self.L.pgd_ppo_grad_guided(self.h, C.byref(nets), None if cnet is None else C.byref(cnet), C.byref(b),
+                                        None if pc is None else C.byref(pc), C.byref(gd), C.byref(hp), C.byref(grads),
+                                        None if cgrads is None else C.byref(cgrads), _p(stats), _p(work), work.numel() * work.element_size()),
+             "pgd_ppo_grad_guided")
         return stats
 
     # -- GAE that bootstraps through a time limit (include/pgdrive_hip.h states `truncated` and the formulas) ---------------------------

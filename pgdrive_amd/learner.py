@@ -4,7 +4,7 @@
     learner = PPOLearner(col, lr=3e-4)
     while training:
         batch = col.collect()
-        stats = learner.update(batch)       # [epochs * minibatches, 8] on the device: _abi.PPO_STATS
+        stats = learner.update(batch)       # [epochs * minibatches, 8] on the device: _abi.PPO_STATS ([.., 12] with guide=)
 
 What a trainer otherwise writes as framework code: an autograd pass over two 3-layer networks, an optimiser step, a gather of minibatch
 rows out of the time-major rollout and -- for the multi-agent collector -- a host read of batch["count"] before a minibatch can be sized.  (Constrained RL on the safe env: PPOLagLearner,
@@ -15,6 +15,11 @@ the rollout's noise live in device memory and advance with every replay.  A coll
 collector's table (Engine.obs_norm_bind) before its first ppo_grad and unbinds behind the last adam, so the gradients see the inputs the
 rollout's evaluations saw.  A collector built with action_head="categorical": the learner reads the head and the bins off it, sizes its
 scratch with Engine.ppo_cat_work_bytes and calls Engine.ppo_grad_cat with batch["action_index"]; everything else here is unchanged.
+A collector built with guardian=: under a takeover the applied action is not the sampled one and the plain update trains on a wrong
+gradient there.  guide="takeover" makes every gradient call Engine.ppo_grad_guided: the overridden rows drop their clipped surrogate
+(keep_surrogate=True: keep it) and imitate batch["applied_actions"] with the weight bc_coef; guide="all": every row imitates the expert
+(batch["guardian_trace"]) -- behaviour cloning on the visited states, the critics still learn.  guide_options() states the two; the
+statistics tensor is then [epochs * minibatches, 12] (_abi.PPO_GUIDED_STATS: guided_rows and bc_loss in slots 8 and 9).  DESIGN section 35.
 
 Minibatch j of n takes the list positions j, j + n, j + 2 n, ...: the n minibatches partition the rollout's transitions whatever their
 number is.  For RolloutCollector the list is every (t, env) row; for MultiAgentRolloutCollector it is batch["index"] / batch["count"] as
@@ -97,14 +102,50 @@ def collector_head(name, collector, cost=False):
     return head, bins
 
 
+GUIDES = ("takeover", "all")
+
+
+def guide_options(name, guide, bc_coef, keep_surrogate, guardian):
+    """The learner's guide switches checked (ValueError) -> None (guide=None: today's calls), or what Engine.ppo_grad_guided is handed:
+    dict(target, mask: keys of the batch (mask None: every row is guided), mask_bits, bc_coef, keep_surrogate).  `guardian`: the
+    collector's guardian settings (collector.guardian; None: built without guardian=).  No device needed.
+    "takeover": the rows whose applied action is not the sampled one imitate batch["applied_actions"] -- what the return credits, agent
+    and expert components mixed.  Those rows are (takeover & 1) != 0, and with the guardian's immediate=True, which also applies the
+    correction of a takeover's first step, (takeover & 3) != 0 (bit 1: takeover_start).
+    "all": every row imitates the expert's steering and throttle, columns 0 and 1 of batch["guardian_trace"]; with keep_surrogate=False
+    that is behaviour cloning of the expert on the states the guarded agent visits (DAgger)."""
+    if not isinstance(keep_surrogate, (bool, int)) or keep_surrogate not in (0, 1):
+        raise ValueError("%s: keep_surrogate = %r is not a bool" % (name, keep_surrogate))
+    if guide is None:
+        if keep_surrogate:
+            raise ValueError("%s: keep_surrogate=True without guide= (one of %s)" % (name, ", ".join(map(repr, GUIDES))))
+        return None
+    if guide not in GUIDES:
+        raise ValueError("%s: guide = %r is not one of None, %s" % (name, guide, ", ".join(map(repr, GUIDES))))
+    if guardian is None:
+        raise ValueError("%s: guide=%r reads what the expert guardian records: build the collector with guardian=dict(weights=...)" % (name, guide))
+    try:
+        bc = float(bc_coef)
+    except (TypeError, ValueError):
+        bc = float("nan")
+    if isinstance(bc_coef, bool) or not (0.0 <= bc < float("inf")):
+        raise ValueError("%s: bc_coef = %r is not a finite number >= 0" % (name, bc_coef))
+    if guide == "takeover":
+        return dict(target="applied_actions", mask="takeover", mask_bits=3 if guardian.get("immediate") else 1, bc_coef=bc,
+                    keep_surrogate=bool(keep_surrogate))
+    return dict(target="guardian_trace", mask=None, mask_bits=1, bc_coef=bc, keep_surrogate=bool(keep_surrogate))
+
+
 class PPOLearner:
     NETS = ("policy", "value")  # the collector's networks, in flat_layout's order
     GRAD = "pgd_ppo_grad"
 
     def __init__(self, collector, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.0, epochs=4, minibatches=4, max_grad_norm=0.5, betas=(0.9, 0.999),
-                 eps=1e-5, normalise_advantages=True, shuffle=False, shuffle_seed=0, target_kl=None, lr_scale=False):
+                 eps=1e-5, normalise_advantages=True, shuffle=False, shuffle_seed=0, target_kl=None, lr_scale=False, guide=None, bc_coef=1.0,
+                 keep_surrogate=False):
         name, cost = type(self).__name__, len(self.NETS) == 3
         self.shuffle, self.shuffle_seed, self.kl_limit, scaled = minibatch_options(name, shuffle, shuffle_seed, target_kl, lr_scale)
+        self.guide = guide_options(name, guide, bc_coef, keep_surrogate, getattr(collector, "guardian", None))
         self.target_kl = None if target_kl is None else float(target_kl)
         self.action_head, self.bins = collector_head(name, collector, cost)
         eng = collector.engine
@@ -142,7 +183,7 @@ class PPOLearner:
             raise ValueError("%s: the networks' input width %d is outside what %s accepts" % (name, self.in_dim, self.GRAD))
         self.work = t.empty(((need + 3) // 4, ), **f32)
         self.adv_stats = t.zeros((2, ), **f32)
-        self.stats = t.zeros((self.epochs * self.minibatches, 8), **f32)
+        self.stats = t.zeros((self.epochs * self.minibatches, 8 if self.guide is None else 12), **f32)  # (guided: _abi.PPO_GUIDED_STATS)
         # the minibatch switches' device state; None where a switch is off (then update() makes today's calls and no others)
         i32 = dict(dtype=t.int32, device=eng.device)
         self.shuffled = t.zeros((self.n_list, ), **i32) if self.shuffle else None
@@ -180,7 +221,18 @@ class PPOLearner:
             return adv, None
         return adv, self.engine.adv_stats(adv, out=self.adv_stats, index=index, count=count, n_list=self.n_list)
 
+    def _guided_cost(self, batch):
+        """The cost critic's arguments of Engine.ppo_grad_guided: none here."""
+        return {}
+
     def _grad(self, batch, adv, stats, **minibatch):
+        if self.guide is not None:  # (a collector with a guardian has the Gaussian head)
+            g = self.guide
+            self.engine.ppo_grad_guided(self.policy_weights, self.value_weights, self.policy_grads, self.value_grads, batch["obs"],
+                                        batch["actions"], batch["logp"], adv, batch["returns"], stats, self.work, batch[g["target"]],
+                                        mask=None if g["mask"] is None else batch[g["mask"]], mask_bits=g["mask_bits"], bc_coef=g["bc_coef"],
+                                        keep_surrogate=g["keep_surrogate"], vf_coef=self.vf_coef, **self._guided_cost(batch), **minibatch)
+            return
         if self.action_head == "categorical":
             self.engine.ppo_grad_cat(self.policy_weights, self.value_weights, self.policy_grads, self.value_grads, self.bins, batch["obs"],
                                      batch["action_index"], batch["logp"], adv, batch["returns"], stats, self.work, vf_coef=self.vf_coef,
@@ -191,7 +243,8 @@ class PPOLearner:
 
     def update(self, batch):
         """epochs x minibatches gradient steps on the rollout `batch` (what collector.collect() returned).  Returns the statistics
-        tensor [epochs * minibatches, 8] (the same object every time).  Asynchronous: nothing here waits for the device."""
+        tensor [epochs * minibatches, 8] -- with guide= [epochs * minibatches, 12], _abi.PPO_GUIDED_STATS -- (the same object every time).
+        Asynchronous: nothing here waits for the device."""
         eng = self.engine
         index, count = batch.get("index"), batch.get("count")  # (the multi-agent collector's list; None: every row)
         adv, norm = self._advantages(batch, index, count)
@@ -244,7 +297,8 @@ class PPOLagLearner(PPOLearner):
     episodes that finished in the rollout; none: unchanged), Engine.adv_stats for the reward and for the cost advantages, Engine.adv_mix
     (((adv - m) s - lambda (cadv - m_c)) / (1 + lambda): the cost advantage centred, not rescaled), then Engine.ppo_grad_cost +
     Engine.adam for every epoch and minibatch.  No host read: `collect(); update()` is capturable in one HIP graph, and a replay takes
-    the next multiplier step from the lambda it finds.  ONE flat buffer holds the eighteen weight tensors (flat_layout(...,
+    the next multiplier step from the lambda it finds.  guide=, bc_coef=, keep_surrogate= as for PPOLearner (Engine.ppo_grad_guided with the
+    cost critic's arguments; statistics [.., 12]).  ONE flat buffer holds the eighteen weight tensors (flat_layout(...,
     has_cost_critic=True)); the collector is handed the views.  `ppo_kwargs`: PPOLearner's arguments (normalise_advantages False: no
     scaling of the reward advantage and no centring of either; shuffle, shuffle_seed, target_kl, lr_scale as there: the permutation is
     drawn over every row, the stop reads the same statistics slot, the multiplier step is taken before the gate is looked at)."""
@@ -253,11 +307,12 @@ class PPOLagLearner(PPOLearner):
 
     def __init__(self, collector, cost_limit, lambda_lr=0.05, lambda_init=0.0, lambda_max=100.0, cvf_coef=0.5, lr=3e-4, clip=0.2, vf_coef=0.5,
                  ent_coef=0.0, epochs=4, minibatches=4, max_grad_norm=0.5, betas=(0.9, 0.999), eps=1e-5, normalise_advantages=True, shuffle=False,
-                 shuffle_seed=0, target_kl=None, lr_scale=False):
+                 shuffle_seed=0, target_kl=None, lr_scale=False, guide=None, bc_coef=1.0, keep_surrogate=False):
         if not (0.0 <= float(lambda_init) <= float(lambda_max)):
             raise ValueError("PPOLagLearner: lambda_init = %r outside [0, lambda_max = %r]" % (lambda_init, lambda_max))
         super().__init__(collector, lr, clip, vf_coef, ent_coef, epochs, minibatches, max_grad_norm, betas, eps, normalise_advantages,
-                         shuffle=shuffle, shuffle_seed=shuffle_seed, target_kl=target_kl, lr_scale=lr_scale)
+                         shuffle=shuffle, shuffle_seed=shuffle_seed, target_kl=target_kl, lr_scale=lr_scale, guide=guide, bc_coef=bc_coef,
+                         keep_surrogate=keep_surrogate)
         self.cost_limit, self.lambda_lr, self.lambda_max, self.cvf_coef = float(cost_limit), float(lambda_lr), float(lambda_max), float(cvf_coef)
         t = self.engine.torch
         f32 = dict(dtype=t.float32, device=self.engine.device)
@@ -278,7 +333,12 @@ class PPOLagLearner(PPOLearner):
         eng.adv_mix(adv, cadv, self.lagrange_state, out=self.mixed, adv_stats=norm, cadv_stats=cnorm)
         return self.mixed, None
 
+    def _guided_cost(self, batch):
+        return dict(cost_weights=self.cost_weights, cost_grads=self.cost_grads, cost_ret=batch["cost_returns"], cvf_coef=self.cvf_coef)
+
     def _grad(self, batch, adv, stats, **minibatch):
+        if self.guide is not None:
+            return super()._grad(batch, adv, stats, **minibatch)
         self.engine.ppo_grad_cost(self.policy_weights, self.value_weights, self.cost_weights, self.policy_grads, self.value_grads, self.cost_grads,
                                   batch["obs"], batch["actions"], batch["logp"], adv, batch["returns"], batch["cost_returns"], stats, self.work,
                                   vf_coef=self.vf_coef, cvf_coef=self.cvf_coef, **minibatch)
