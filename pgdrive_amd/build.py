@@ -5,7 +5,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "pgd_engine.hip")
-DEPS = [SRC] + [os.path.join(HERE, "csrc", h) for h in ("pgd_device.h", "pgd_step.h", "pgd_kernels.h", "pgd_vehicle.h", "pgd_localize.h", "pgd_idm.h",
+DEPS = [SRC] + [os.path.join(HERE, "csrc", h) for h in ("pgd_device.h", "pgd_records.h", "pgd_host_prep.h", "pgd_step.h", "pgd_kernels.h", "pgd_vehicle.h", "pgd_localize.h", "pgd_idm.h",
                                                          "pgd_dynamics.h", "pgd_observe.h", "pgd_gather.h", "pgd_topdown.h", "pgd_render.h", "pgd_policy.h", "pgd_actor_critic.h", "pgd_marl_rollout.h", "pgd_step_info.h", "pgd_ppo.h", "pgd_safe.h", "pgd_timelimit.h", "pgd_guardian.h", "pgd_return_norm.h", "pgd_obs_norm.h", "pgd_rollout_episodes.h", "pgd_minibatch.h", "pgd_categorical.h", "pgd_guided.h")] + \
     [os.path.join(HERE, "..", "include", "pgdrive_hip.h"), os.path.join(HERE, "..", "include", "pgd_state_layout.h"),
      os.path.abspath(__file__)]  # the flags below are part of the build: a change of this file rebuilds

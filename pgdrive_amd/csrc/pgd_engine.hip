@@ -1,5 +1,6 @@
 // pgd_engine.hip — the single translation unit of the MI355X-native batched PGDrive step engine and its host side: the engine handle, the
-// launch plan of a step and the C ABI (include/pgdrive_hip.h).  The device code is in the headers included here, in this order: pgd_device.h,
+// launch plan of a step and the C ABI (include/pgdrive_hip.h).  What the entry points prepare on the CPU -- geometry, the device forms of the
+// tables, the state conversion -- is pgd_host_prep.h (no HIP in it).  The device code is in the headers included here, in this order: pgd_device.h,
 // pgd_step.h (k_step; it includes pgd_vehicle.h ... pgd_policy.h, pgd_actor_critic.h), pgd_kernels.h (reset / derive / refresh / observe),
 // pgd_marl_rollout.h (live rows, the networks over a row list, masked GAE) and, at the end,
 // pgd_topdown.h, pgd_render.h, pgd_gather.h, pgd_step_info.h, pgd_ppo.h (the PPO update) and pgd_safe.h (its cost side) with their own
@@ -28,6 +29,7 @@
 #ifndef PGD_JIT  // (a run-time build, pgdrive_amd/jit.py, is the device code above and nothing else)
 #include "pgd_kernels.h"
 #include "pgd_marl_rollout.h"
+#include "pgd_host_prep.h"  // the GPU-free preparation of the entry points below: geometry, table forms, state conversion
 
 // The library's environment switches (include/pgdrive_hip.h lists them), read once, by pgd_create.  pack / imask: -1 = not forced.
 struct Switches { bool no_fuse, no_fix, jit_force, row_observe, no_state_in_step, no_rowz, no_uni; int pack, imask; };
@@ -504,6 +506,92 @@ static int compact_launch(const uint32_t* d_flags, const uint8_t* d_done, int fi
   return PGD_OK;
 }
 
+// The shared tail of the two table uploads: no mask, hint or reset image is trusted across a change of the tables
+static int tables_changed(pgd_engine* h) {
+  h->img_dirty = true;  // running envs fall back to their own records until their next reset
+  HIPCHK(hipMemsetAsync(h->d.imask, 0, sizeof(unsigned long long) * (size_t)h->d.N, h->stream));
+  hipLaunchKernelGGL(k_clear_hints, dim3((h->d.N + 255) / 256), dim3(256), 0, h->stream, h->d.ei, h->d.N);
+  HIPCHK(hipGetLastError());
+  return build_reset_image(h);  // eagerly (needs maps + scenarios): pgd_step never allocates, so it can be graph-captured
+}
+
+// Everything a handle owns, and the handle: pgd_destroy, and pgd_create when it fails half way (every member is null until it is set)
+static void engine_free(pgd_engine* h) {
+  (void)hipStreamSynchronize(h->stream);
+  if (h->jit_mod) { (void)hipModuleUnload(h->jit_mod); h->jit_mod = nullptr; h->jit_fn = nullptr; }
+  void* bufs[] = {h->cmp_live, h->cmp_index, h->lk_act, h->rowz, h->d.rec, h->d.ei, h->d.imask, h->d.env_map, h->d_ids, h->arena};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  for (hipEvent_t ev : {h->ev0, h->ev1, h->ev_move, h->ev_ids})
+    if (ev) (void)hipEventDestroy(ev);
+  if (h->h_ids) (void)hipHostFree(h->h_ids);
+  if (h->prof_ev) {
+    for (hipEvent_t ev : *h->prof_ev) (void)hipEventDestroy(ev);
+    delete h->prof_ev;
+  }
+  if (h->gstreams) {
+    for (int g = 0; g < h->n_groups; ++g) { (void)hipStreamSynchronize(h->gstreams[g]); (void)hipStreamDestroy(h->gstreams[g]); }
+    free(h->gstreams);
+  }
+  if (h->cmp_retired) {
+    for (uint32_t* b : *h->cmp_retired) (void)hipFree(b);
+    delete h->cmp_retired;
+  }
+  topdown_free(h);
+  render_free(h);
+  step_info_free(h);
+  delete h->h_maps;
+  delete h->h_scen;
+  if (h->own_stream) (void)hipStreamDestroy(h->stream);
+  if (h->retired) (void)hipStreamDestroy(h->retired);
+  free(h);
+}
+
+// pgd_create behind its refusals: the device state of a zeroed handle for N x V slots.  A failure leaves the handle to the caller's engine_free.
+static int engine_init(pgd_engine* h, const pgd_config* cfg, const Geometry& g, int device, void* hip_stream) {
+  h->device = device;
+  h->d.cfg = *cfg;
+  h->d.N = cfg->num_envs; h->d.A = cfg->num_agents; h->d.T = cfg->num_traffic; h->d.V = g.V;
+  h->d.D = g.D;
+  h->d.NV = g.NV;
+  h->d.ostride = h->d.A * h->d.D;  // (prow, unit_off: null / 0 from calloc; a step sets them in its launch copy)
+  h->d.dbg_exit = 255;  // no exit mark, no ablation bits (exit-profile builds only)
+  h->n_groups = 1;
+  h->d.sstride = g.sstride; h->d.sub = g.sub; h->d.epw = g.epw; h->d.pack_obs = g.pack_obs; h->d.use_imask = g.use_imask;
+  const bool marl = (cfg->marl_flags & PGD_MA_ENABLED) != 0;
+  if (hip_stream) { h->stream = (hipStream_t)hip_stream; h->own_stream = false; }
+  else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
+  HIPCHK(hipEventCreate(&h->ev0));
+  HIPCHK(hipEventCreate(&h->ev1));
+  HIPCHK(hipEventCreateWithFlags(&h->ev_move, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&h->ev_ids, hipEventDisableTiming));
+  HIPCHK(hipHostMalloc((void**)&h->h_ids, sizeof(int32_t) * (size_t)cfg->num_envs * 2, hipHostMallocDefault));
+  size_t nv = (size_t)h->d.NV;
+  HIPCHK(hipMalloc(&h->d.rec, sizeof(VehRec) * nv));
+  HIPCHK(hipMalloc(&h->d.ei, sizeof(int32_t) * (size_t)h->d.N * PGD_NEI));
+  HIPCHK(hipMalloc(&h->d_ids, sizeof(int32_t) * (size_t)h->d.N * 2));
+  HIPCHK(hipMemsetAsync(h->d.rec, 0, sizeof(VehRec) * nv, h->stream));
+  HIPCHK(hipMemsetAsync(h->d.ei, 0, sizeof(int32_t) * (size_t)h->d.N * PGD_NEI, h->stream));
+  if (marl && !h->sw.no_rowz) {  // (PGD_NO_ROWZ=1: no marks -- every row that is not due is zero-filled by every call)
+    HIPCHK(hipMalloc(&h->rowz, sizeof(ulonglong2) * (size_t)h->d.N));
+    HIPCHK(hipMemsetAsync(h->rowz, 0, sizeof(ulonglong2) * (size_t)h->d.N, h->stream));
+    h->d.rowz = h->rowz;
+  }
+  HIPCHK(hipMalloc(&h->cmp_live, sizeof(uint32_t) * live_scratch_entries(h->d.N, h->d.A)));
+  HIPCHK(hipMalloc(&h->d.env_map, sizeof(pgd_map) * (size_t)h->d.N));
+  HIPCHK(hipMemsetAsync(h->d.env_map, 0, sizeof(pgd_map) * (size_t)h->d.N, h->stream));
+  HIPCHK(hipMalloc(&h->d.imask, sizeof(unsigned long long) * (size_t)h->d.N));  // (read while use_imask is set: imask_rule, pgd_host_prep.h)
+  HIPCHK(hipMemsetAsync(h->d.imask, 0, sizeof(unsigned long long) * (size_t)h->d.N, h->stream));
+  // beam i points at theta + i * 2 pi / n (distance_detector.py:65-94): its direction is the heading rotated by a
+  // constant angle, tabulated once in double precision instead of one sincosf per beam and step
+  std::vector<float2> bt((size_t)(cfg->num_lasers > 0 ? cfg->num_lasers : 1));
+  for (int i = 0; i < cfg->num_lasers; ++i) {
+    const double a = (double)i * (2.0 * 3.14159265358979323846 / (double)cfg->num_lasers);
+    bt[(size_t)i] = make_float2((float)cos(a), (float)sin(a));
+  }
+  return upload(h, TB_BEAM, bt.data(), bt.size());
+}
+
 extern "C" {
 
 const char* pgd_version(void) { return "pgdrive_hip 0.1 (gfx950)"; }
@@ -526,297 +614,80 @@ int pgd_plan_arena(const uint64_t* bytes, int n, uint32_t* offsets, uint64_t* to
   return PGD_OK;
 }
 
-int pgd_obs_dim(const pgd_config* c) {
-  const int toll = (c->marl_flags & PGD_MA_TOLLGATE) != 0;
-  const int state = (c->side_lasers > 0 ? c->side_lasers : 2) + 6 + c->lane_line_lasers + (c->random_agent_model ? 2 : 0) +
-                    (toll ? 0 : PGD_NAVI_DIM);
-  const int per_other = (c->marl_flags & PGD_MA_OTHERS_STATE) ? state : 4;
-  return state + per_other * c->num_others + c->num_lasers + (toll ? 2 : 0);
-}
+int pgd_obs_dim(const pgd_config* c) { return obs_dim(*c); }
 
 int pgd_create(const pgd_config* cfg, int device, void* hip_stream, pgd_handle* out) {
   if (!cfg || !out) return PGD_ERR_ARG;
-  int V = cfg->num_agents + cfg->num_traffic;
-  if (cfg->num_envs <= 0 || cfg->num_agents <= 0 || V > MAXV || cfg->num_others > 16 || cfg->num_lasers < 0) return PGD_ERR_ARG;
+  const Switches sw = read_switches();
+  Geometry g;
+  { int rc = plan_geometry(*cfg, sw.pack, sw.imask, g); if (rc) return rc; }  // (every refusal: before the first HIP call, nothing allocated)
   HIPCHK(hipSetDevice(device));
   pgd_engine* h = (pgd_engine*)calloc(1, sizeof(pgd_engine));
-  h->device = device;
-  h->sw = read_switches();
-  h->d.cfg = *cfg;
-  h->d.N = cfg->num_envs; h->d.A = cfg->num_agents; h->d.T = cfg->num_traffic; h->d.V = V;
-  h->d.D = pgd_obs_dim(cfg);
-  h->d.NV = h->d.N * V;
-  h->d.ostride = h->d.A * h->d.D;  // (prow, unit_off: null / 0 from calloc; a step sets them in its launch copy)
-  h->d.dbg_exit = 255;  // no exit mark, no ablation bits (exit-profile builds only)
-  h->n_groups = 1;
-  const bool marl = (cfg->marl_flags & PGD_MA_ENABLED) != 0;
-  // multi-agent engines have no IDM traffic; num_traffic slots may hold static bodies (toll booths, group PGD_GROUP_NEVER)
-  if (marl && (cfg->respawn_places < 0 || cfg->respawn_places > 64 || cfg->respawn_dests < 0)) return PGD_ERR_ARG;  // (free places: one 64-bit mask)
-  if (cfg->idm_agent && (marl || cfg->num_agents != 1)) return PGD_ERR_ARG;  // the agent's PID / routing fields double as multi-agent bookkeeping
-  if (marl && cfg->horizon > 0x7fff) return PGD_ERR_ARG;  // the per-agent episode length is a 16-bit field of the record
-  h->d.sstride = V + (marl ? cfg->respawn_places * cfg->respawn_dests : 0);
-  h->d.sub = WAVE / V < 16 ? WAVE / V : 16;  // sub-lanes per vehicle
-  h->d.epw = marl ? 1 : WAVE / (V * h->d.sub);  // whole environments per wave (the multi-agent tail needs the env alone in its wave)
-  // Throughput mode: at large N the step is bound by instruction issue, not by the latency of one wave (profiles/r02_sweep.md:
-  // 4.2 ns per env-step from 32768 envs on), and the SUB lanes of a vehicle run its scalar phases redundantly.  Engines with
-  // >= 32768 single-ego envs (PGD_PACK=1 / 0 overrides; measured against the one-env kernel, profiles/r03_sweep.md: -7 % at 16384 envs, +6 % at 32768, +18 % at 262144) carry one vehicle per lane and as many whole envs per wave as fit --
-  // three at V = 17 -- with the lidar observation of each env appended to the same launch.
-  const int epw1 = std::min(WAVE / V, FUSE_MAX_AGENTS);
-  const bool can_pack = !marl && cfg->num_agents == 1 && cfg->num_traffic >= 1 && epw1 >= 2 && epw1 * V <= PGD_SUBV && cfg->num_lasers > 0;
-  const bool want_pack = h->sw.pack >= 0 ? h->sw.pack != 0 : cfg->num_envs >= 32768;
-  if (can_pack && want_pack) { h->d.sub = 1; h->d.epw = epw1; h->d.pack_obs = 1; }
-  if (hip_stream) { h->stream = (hipStream_t)hip_stream; h->own_stream = false; }
-  else { HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
-  HIPCHK(hipEventCreate(&h->ev0));
-  HIPCHK(hipEventCreate(&h->ev1));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_move, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&h->ev_ids, hipEventDisableTiming));
-  HIPCHK(hipHostMalloc((void**)&h->h_ids, sizeof(int32_t) * (size_t)cfg->num_envs * 2, hipHostMallocDefault));
-  size_t nv = (size_t)h->d.NV;
-  HIPCHK(hipMalloc(&h->d.rec, sizeof(VehRec) * nv));
-  HIPCHK(hipMalloc(&h->d.ei, sizeof(int32_t) * (size_t)h->d.N * PGD_NEI));
-  HIPCHK(hipMalloc(&h->d_ids, sizeof(int32_t) * (size_t)h->d.N * 2));
-  HIPCHK(hipMemsetAsync(h->d.rec, 0, sizeof(VehRec) * nv, h->stream));
-  HIPCHK(hipMemsetAsync(h->d.ei, 0, sizeof(int32_t) * (size_t)h->d.N * PGD_NEI, h->stream));
-  if (marl && !h->sw.no_rowz) {  // (PGD_NO_ROWZ=1: no marks -- every row that is not due is zero-filled by every call)
-    HIPCHK(hipMalloc(&h->rowz, sizeof(ulonglong2) * (size_t)h->d.N));
-    HIPCHK(hipMemsetAsync(h->rowz, 0, sizeof(ulonglong2) * (size_t)h->d.N, h->stream));
-    h->d.rowz = h->rowz;
-  }
-  HIPCHK(hipMalloc(&h->cmp_live, sizeof(uint32_t) * live_scratch_entries(h->d.N, h->d.A)));
-  HIPCHK(hipMalloc(&h->d.env_map, sizeof(pgd_map) * (size_t)h->d.N));
-  HIPCHK(hipMemsetAsync(h->d.env_map, 0, sizeof(pgd_map) * (size_t)h->d.N, h->stream));
-  // never-written slots are read from the scenario's reset image (cache resident, shared by every env of the scenario) instead
-  // of the env's own record: halves the HBM bytes of a step and is worth +13 % at 262144 envs.  THROUGHPUT MODE ONLY (several envs
-  // per wave, from 32768 envs on): with one env per wave the step is bound by its chain of memory round trips, and the mask is one
-  // of them -- mask + scenario id -> records -> ...; without it the records' reads go out at once (round 5: 4096 envs 17.38 -> 17.12 us,
-  // 16384 envs 47.3 -> 46.8, 8 agents 22.4 -> 22.1, 40 seats' step 27.7 -> 27.0; 32768 envs in throughput mode 77.2 -> 77.7 without
-  // the image).  PGD_NO_IMASK=1 / PGD_IMASK=1 force it off / on (A/B; the specialised kernels are compiled for the default).
-  h->d.use_imask = h->sw.imask >= 0 ? h->sw.imask : (h->d.pack_obs ? 1 : 0);
-  HIPCHK(hipMalloc(&h->d.imask, sizeof(unsigned long long) * (size_t)h->d.N));
-  HIPCHK(hipMemsetAsync(h->d.imask, 0, sizeof(unsigned long long) * (size_t)h->d.N, h->stream));
-  {
-    // beam i points at theta + i * 2 pi / n (distance_detector.py:65-94): its direction is the heading rotated by a
-    // constant angle, tabulated once in double precision instead of one sincosf per beam and step
-    std::vector<float2> bt((size_t)(cfg->num_lasers > 0 ? cfg->num_lasers : 1));
-    for (int i = 0; i < cfg->num_lasers; ++i) {
-      const double a = (double)i * (2.0 * 3.14159265358979323846 / (double)cfg->num_lasers);
-      bt[(size_t)i] = make_float2((float)cos(a), (float)sin(a));
-    }
-    int rc = upload(h, TB_BEAM, bt.data(), bt.size());
-    if (rc) return rc;
-  }
+  if (!h) return PGD_ERR_STATE;
+  h->sw = sw;
+  const int rc = engine_init(h, cfg, g, device, hip_stream);
+  if (rc) { engine_free(h); return rc; }
   *out = h;
   return PGD_OK;
 }
 
+// (the device forms are built first -- build_map_tables, which refuses a malformed bank before anything here has changed --, the arena
+// is sized for all of them at once, then they are copied in)
 int pgd_upload_maps(pgd_handle h, const pgd_map* maps, int n_maps, const pgd_lane* lanes, int n_lanes,
                     const pgd_road* roads, int n_roads, const pgd_box* boxes, int n_boxes, const int32_t* cs, int n_cs,
                     const int32_t* ci, int n_ci) {
-  if (!h || !maps || n_maps <= 0) return PGD_ERR_ARG;
-  for (int m = 0; m < n_maps; ++m)  // packed ids of the device record: 12-bit road ids, 16-bit lane ids
-    if (maps[m].n_roads > 4095 || maps[m].n_lanes > 65535) return PGD_ERR_ARG;
+  if (!h) return PGD_ERR_ARG;
+  MapTables t;
+  int rc = build_map_tables(maps, n_maps, lanes, n_lanes, roads, n_roads, boxes, n_boxes, cs, n_cs, ci, n_ci, t);
+  if (rc) return rc;
+  if (h->h_scen && !scenario_maps_ok(h->h_scen->data(), h->h_scen->size(), (size_t)n_maps)) return PGD_ERR_ARG;
   HIPCHK(hipSetDevice(h->device));
-  int rc;
-  // (the device forms are built first, the arena is sized for all of them at once, then they are copied in)
-  std::vector<pgd_lane> dl(lanes, lanes + n_lanes);
-  std::vector<LaneNav> nav((size_t)(n_lanes > 0 ? n_lanes : 1));
-  {
-    // device copy of the lane table: `pad` carries the lane count of the lane's road (the lanes of a road are consecutive,
-    // so neighbour lanes follow from the lane id alone: no road-record read in the IDM neighbour search)
-    for (int m = 0; m < n_maps; ++m)
-      for (int k = 0; k < maps[m].n_lanes; ++k) {
-        pgd_lane& L = dl[(size_t)maps[m].lane_off + k];
-        if (L.road < 0 || L.road >= maps[m].n_roads) return PGD_ERR_ARG;
-        const pgd_road& R = roads[maps[m].road_off + L.road];
-        if (R.first_lane + L.index != k) return PGD_ERR_ARG;
-        L.pad = R.n_lanes;
-        // device-private use of `ex` (the end point is not read on the device): half-width of the strip around a straight
-        // lane's axis that no line / sidewalk box of the map reaches.  The lateral coordinate is linear over a box, so its
-        // extremes sit at the corners; a box with corners on both sides crosses.  A car whose box stays inside that strip AND
-        // between the lane's ends touches nothing: k_step then skips the line / sidewalk test.  Boxes that lie wholly before the
-        // lane's start or behind its end (5 cm of slack for the fp32 coordinate on the device) cannot reach such a car -- the lane's
-        // direction separates them -- and do not count: rounds 2 - 4 counted everything within 6 m of the ends, and the first
-        // piece of a curved line behind a junction then voided the strip of a QUARTER of the straight lane length of the
-        // PGDrive-v0 maps and of every entry road of the multi-agent roundabout (where most agents of a random policy live).
-        double clear = 0.0;
-#ifdef PGD_NO_STRIP
-        if (false) {
-#else
-        if (L.dir == 0.0f) {
-#endif
-          clear = 1e9;
-          const pgd_map& M = maps[m];
-          for (int b = 0; b < M.n_boxes && clear > 0.0; ++b) {
-            const pgd_box& B = boxes[M.box_off + b];
-            if (B.kind == PGD_BOX_LANE) continue;
-            double lo_lon = 1e30, hi_lon = -1e30, lo_lat = 1e30, hi_lat = -1e30;
-            for (int q = 0; q < 4; ++q) {
-              const double sl = (q & 1) ? 1.0 : -1.0, sw = (q & 2) ? 1.0 : -1.0;
-              const double px = B.cx + sl * B.hl * B.ux - sw * B.hw * B.uy, py = B.cy + sl * B.hl * B.uy + sw * B.hw * B.ux;
-              const double dx = px - L.ax, dy = py - L.ay;
-              const double lon = dx * L.bx + dy * L.by, lat = dy * L.bx - dx * L.by;
-              lo_lon = std::min(lo_lon, lon); hi_lon = std::max(hi_lon, lon);
-              lo_lat = std::min(lo_lat, lat); hi_lat = std::max(hi_lat, lat);
-            }
-            if (hi_lon < -0.05 || lo_lon > (double)L.length + 0.05) continue;  // (the car lies within [0, length]: see below)
-            if (lo_lat <= 0.0 && hi_lat >= 0.0) clear = 0.0;
-            else clear = std::min(clear, std::min(std::fabs(lo_lat), std::fabs(hi_lat)));
-          }
-          clear = clear > 1e8 ? 0.0 : std::max(0.0, clear - 0.03);  // 3 cm of slack for the fp32 forms on the device
-        }
-        L.ex = (float)clear;
-        L.ey = 0.0f;  // (the bits of the related-lanes mask, below)
-      }
-    // device-private use of `ey`: the 32-bit set { id & 31 } over the lane itself, its successors and its predecessors (the lanes
-    // whose successor list holds it) -- every lane an object must be on to count in the IDM front / back search of this lane
-    // (FrontBackObjects: same lane, successor lane, predecessor lane; idm_policy.py:107-131).  find_front_back drops the other
-    // bodies of the broad phase with one shift per body before its search loop; a superset (ids collide mod 32) keeps it exact.
-    for (int m = 0; m < n_maps; ++m) {
-      std::vector<uint32_t> rel((size_t)maps[m].n_lanes, 0u);
-      for (int k = 0; k < maps[m].n_lanes; ++k) {
-        const pgd_lane& L = dl[(size_t)maps[m].lane_off + k];
-        rel[(size_t)k] |= 1u << (k & 31);
-        for (int q = 0; q < PGD_MAX_SUCC; ++q) {
-          const int sid = L.succ[q];
-          if (sid < 0 || sid >= maps[m].n_lanes) continue;
-          rel[(size_t)k] |= 1u << (sid & 31);
-          rel[(size_t)sid] |= 1u << (k & 31);
-        }
-      }
-      for (int k = 0; k < maps[m].n_lanes; ++k) memcpy(&dl[(size_t)maps[m].lane_off + k].ey, &rel[(size_t)k], 4);
-      // device-private use of `pad`: the from-node of the lane's road -- what Navigation._update_target_checkpoints looks up in the
-      // route (navigation.py:262-282); with it in the lane record the checkpoint test needs no lane -> road table chain (two
-      // dependent reads per vehicle on every step of the first five metres of a lane: round 6)
-      for (int k = 0; k < maps[m].n_lanes; ++k) {
-        pgd_lane& L = dl[(size_t)maps[m].lane_off + k];
-        L.pad = (L.road >= 0 && L.road < maps[m].n_roads) ? roads[(size_t)maps[m].road_off + L.road].from : (int16_t)-1;
-      }
-    }
-    for (int k = 0; k < n_lanes; ++k) {
-      const pgd_lane& L = lanes[k];
-      LaneNav& v = nav[(size_t)k];
-      if (L.dir == 0.0f) {  // straight_lane.py:53-67: start + lon * direction + lat * direction_lateral
-        v = LaneNav{(float)((double)L.ax + (double)L.length * L.bx), (float)((double)L.ay + (double)L.length * L.by),
-                    -L.by, L.bx, 0.0f, 0.0f, 0.0f, 0.0f};
-      } else {  // circular_lane.py:41-49: centre + (radius - lat * direction) * (cos phi, sin phi)
-        const double phi = (double)L.dir * L.length / L.bx + L.by, c = cos(phi), s = sin(phi);
-        v = LaneNav{(float)(L.ax + (double)L.bx * c), (float)(L.ay + (double)L.bx * s), (float)(-L.dir * c), (float)(-L.dir * s),
-                    L.bx, L.dir, L.dir == 1.0f ? L.c - L.by : L.by - L.c, 0.0f};
-      }
-    }
-  }
-  // cell-major copies of the boxes: cell_boxes[item_off + k] = boxes[box_off + cell_items[item_off + k]] — one dependent
-  // load less per box in the grid walks, and a cell's boxes are contiguous (coalesced across sub-lanes)
-  {
-    // Inside each cell the lane-surface boxes are moved to the front (stable), and the device copy of cell_start packs
-    // the number of lane boxes into the top byte (see cell_first / cell_mid).
-    std::vector<pgd_box> cb((size_t)(n_ci > 0 ? n_ci : 1));
-    std::vector<LaneExt> cx((size_t)(n_ci > 0 ? n_ci : 1), LaneExt{0.f, 0.f, 0.f, -1});
-    std::vector<int32_t> cs2(cs, cs + n_cs);
-    for (int m = 0; m < n_maps; ++m) {
-      const pgd_map& M = maps[m];
-      const int n_cells = M.gx * M.gy;
-      if (cs[M.cell_off + n_cells] >= (1 << 24)) return PGD_ERR_ARG;
-      for (int c = 0; c < n_cells; ++c) {
-        const int a = cs[M.cell_off + c], b = cs[M.cell_off + c + 1];
-        int w = a;
-        for (int pass = 0; pass < 2; ++pass)
-          for (int k = a; k < b; ++k) {
-            const pgd_box& bx = boxes[M.box_off + ci[M.item_off + k]];
-            if ((bx.kind == PGD_BOX_LANE) == (pass == 0)) {
-              if (pass == 0) {
-                if (bx.lane < 0 || bx.lane >= M.n_lanes) return PGD_ERR_ARG;
-                const pgd_lane& L = lanes[M.lane_off + bx.lane];
-                cx[(size_t)M.item_off + w] = L.dir == 0.0f ? LaneExt{L.bx, L.by, 0.0f, L.road} : LaneExt{L.ax, L.ay, L.dir, L.road};
-              }
-              cb[(size_t)M.item_off + w++] = bx;
-            }
-            if (pass == 0 && k == b - 1) {
-              const int n_lane_boxes = w - a;
-              if (n_lane_boxes > 255) return PGD_ERR_ARG;
-              cs2[M.cell_off + c] = a | (n_lane_boxes << 24);
-            }
-          }
-      }
-    }
-    const int ids[9] = {TB_MAPS, TB_LANES, TB_LANE_NAV, TB_ROADS, TB_BOXES, TB_CELL_ITEMS, TB_CELL_BOXES, TB_CELL_EXT, TB_CELL_START};
-    const uint64_t bytes[9] = {sizeof(pgd_map) * (uint64_t)n_maps, sizeof(pgd_lane) * (uint64_t)n_lanes, sizeof(LaneNav) * (uint64_t)n_lanes,
-                               sizeof(pgd_road) * (uint64_t)n_roads, sizeof(pgd_box) * (uint64_t)n_boxes, sizeof(int32_t) * (uint64_t)n_ci,
-                               sizeof(pgd_box) * (uint64_t)n_ci, sizeof(LaneExt) * (uint64_t)n_ci, sizeof(int32_t) * (uint64_t)n_cs};
-    if ((rc = arena_resize(h, ids, bytes, 9))) return rc;
-    if ((rc = arena_fill(h, TB_MAPS, maps, (size_t)n_maps)) || (rc = arena_fill(h, TB_LANES, dl.data(), (size_t)n_lanes)) ||
-        (rc = arena_fill(h, TB_LANE_NAV, nav.data(), (size_t)n_lanes)) || (rc = arena_fill(h, TB_ROADS, roads, (size_t)n_roads)) ||
-        (rc = arena_fill(h, TB_BOXES, boxes, (size_t)n_boxes)) || (rc = arena_fill(h, TB_CELL_ITEMS, ci, (size_t)n_ci)) ||
-        (rc = arena_fill(h, TB_CELL_BOXES, cb.data(), (size_t)n_ci)) || (rc = arena_fill(h, TB_CELL_EXT, cx.data(), (size_t)n_ci)) ||
-        (rc = arena_fill(h, TB_CELL_START, cs2.data(), (size_t)n_cs)))
-      return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));  // (the staging vectors go out of scope)
-  }
+  const int ids[9] = {TB_MAPS, TB_LANES, TB_LANE_NAV, TB_ROADS, TB_BOXES, TB_CELL_ITEMS, TB_CELL_BOXES, TB_CELL_EXT, TB_CELL_START};
+  const uint64_t bytes[9] = {sizeof(pgd_map) * (uint64_t)n_maps, sizeof(pgd_lane) * (uint64_t)n_lanes, sizeof(LaneNav) * (uint64_t)n_lanes,
+                             sizeof(pgd_road) * (uint64_t)n_roads, sizeof(pgd_box) * (uint64_t)n_boxes, sizeof(int32_t) * (uint64_t)n_ci,
+                             sizeof(pgd_box) * (uint64_t)n_ci, sizeof(LaneExt) * (uint64_t)n_ci, sizeof(int32_t) * (uint64_t)n_cs};
+  if ((rc = arena_resize(h, ids, bytes, 9))) return rc;
+  if ((rc = arena_fill(h, TB_MAPS, maps, (size_t)n_maps)) || (rc = arena_fill(h, TB_LANES, t.lanes.data(), (size_t)n_lanes)) ||
+      (rc = arena_fill(h, TB_LANE_NAV, t.nav.data(), (size_t)n_lanes)) || (rc = arena_fill(h, TB_ROADS, roads, (size_t)n_roads)) ||
+      (rc = arena_fill(h, TB_BOXES, boxes, (size_t)n_boxes)) || (rc = arena_fill(h, TB_CELL_ITEMS, ci, (size_t)n_ci)) ||
+      (rc = arena_fill(h, TB_CELL_BOXES, t.cell_boxes.data(), (size_t)n_ci)) || (rc = arena_fill(h, TB_CELL_EXT, t.cell_ext.data(), (size_t)n_ci)) ||
+      (rc = arena_fill(h, TB_CELL_START, t.cell_start.data(), (size_t)n_cs)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));  // (the staging vectors go out of scope)
   if (!h->h_maps) h->h_maps = new std::vector<pgd_map>();
   h->h_maps->assign(maps, maps + n_maps);
   if ((rc = build_scen_map(h))) return rc;
   h->have_maps = true;
-  h->img_dirty = true;  // running envs fall back to their own records until their next reset
-  HIPCHK(hipMemsetAsync(h->d.imask, 0, sizeof(unsigned long long) * (size_t)h->d.N, h->stream));
-  hipLaunchKernelGGL(k_clear_hints, dim3((h->d.N + 255) / 256), dim3(256), 0, h->stream, h->d.ei, h->d.N);
-  HIPCHK(hipGetLastError());
-  return build_reset_image(h);  // eagerly (needs maps + scenarios): pgd_step never allocates, so it can be graph-captured
+  return tables_changed(h);
 }
 
 int pgd_upload_scenarios(pgd_handle h, const pgd_scenario* scen, int n_scen, const pgd_spawn* spawns) {
-  if (!h || !scen || n_scen <= 0 || !spawns) return PGD_ERR_ARG;
+  if (!h) return PGD_ERR_ARG;
+  ScenarioTables t;
+  int rc = build_scenario_tables(scen, spawns, n_scen, h->d.sstride, h->sw.no_uni, t);
+  if (rc) return rc;
+  if (h->h_maps && !scenario_maps_ok(scen, (size_t)n_scen, h->h_maps->size())) return PGD_ERR_ARG;
   HIPCHK(hipSetDevice(h->device));
-  int rc;
-  const size_t ns = (size_t)n_scen * h->d.sstride;
-  {
-    const int ids[3] = {TB_SCEN, TB_SPAWNS, TB_SPAWN_HV};
-    const uint64_t bytes[3] = {sizeof(pgd_scenario) * (uint64_t)n_scen, sizeof(pgd_spawn) * (uint64_t)ns, sizeof(float2) * (uint64_t)ns};
-    if ((rc = arena_resize(h, ids, bytes, 3)) || (rc = arena_fill(h, TB_SCEN, scen, (size_t)n_scen))) return rc;
-  }
-  {
-    // device-private form of the routes: PGD_CKPT_END from a route's last node on (update_checkpoints: a match on the last node
-    // alone changes nothing, navigation.py:270-277 -- the search stops at the mark instead of reading the route length first)
-    std::vector<pgd_spawn> dsp(spawns, spawns + (size_t)n_scen * h->d.sstride);
-    for (pgd_spawn& q : dsp) {
-      const int n = q.n_ckpt < 0 ? 0 : (q.n_ckpt > PGD_MAX_CKPT ? PGD_MAX_CKPT : q.n_ckpt);
-      for (int k = n > 0 ? n - 1 : 0; k < PGD_MAX_CKPT; ++k) q.ckpt[k] = (int16_t)PGD_CKPT_END;
-    }
-    if ((rc = arena_fill(h, TB_SPAWNS, dsp.data(), dsp.size()))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));  // (the staging vector goes out of scope)
-  }
+  const size_t ns = t.spawns.size();
+  const int ids[3] = {TB_SCEN, TB_SPAWNS, TB_SPAWN_HV};
+  const uint64_t bytes[3] = {sizeof(pgd_scenario) * (uint64_t)n_scen, sizeof(pgd_spawn) * (uint64_t)ns, sizeof(float2) * (uint64_t)ns};
+  if ((rc = arena_resize(h, ids, bytes, 3)) || (rc = arena_fill(h, TB_SCEN, scen, (size_t)n_scen)) ||
+      (rc = arena_fill(h, TB_SPAWNS, t.spawns.data(), ns)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));  // (the staging vector goes out of scope)
   h->d.n_scen = n_scen;
   hipLaunchKernelGGL(k_spawn_hv, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, h->stream, (const pgd_spawn*)arena_ptr<pgd_spawn>(h, TB_SPAWNS),
                      arena_ptr<float2>(h, TB_SPAWN_HV), ns);
   HIPCHK(hipGetLastError());
-  for (size_t k = 0; k < (size_t)n_scen * h->d.sstride; ++k)
-    if (spawns[k].lane >= 0 && (!(spawns[k].max_steer <= 1.0f) || spawns[k].n_ckpt > PGD_MAX_CKPT)) return PGD_ERR_ARG;  // tan_small
-  h->d.no_groups = 1;
-  for (int k = 0; k < n_scen; ++k)
-    if (scen[k].n_groups > 0) { h->d.no_groups = 0; break; }
-  h->has_objects = false;
-  for (size_t k = 0; k < (size_t)n_scen * h->d.sstride; ++k)
-    if (spawns[k].lane >= 0 && spawns[k].kind != PGD_OBJ_VEHICLE) { h->has_objects = true; break; }
-  {  // one body size for the whole upload?  (unused slots -- lane < 0 -- never enter a world)
-    float ul = 0.0f, uw = 0.0f;
-    bool uni = !h->has_objects && !h->sw.no_uni;
-    for (size_t k = 0; uni && k < (size_t)n_scen * h->d.sstride; ++k) {
-      if (spawns[k].lane < 0) continue;
-      if (ul == 0.0f) { ul = spawns[k].length; uw = spawns[k].width; }
-      uni = spawns[k].length == ul && spawns[k].width == uw && ul > 0.0f && uw > 0.0f;
-    }
-    h->d.uni_len = uni ? ul : 0.0f;
-    h->d.uni_wid = uni ? uw : 0.0f;
-  }
+  h->d.no_groups = t.no_groups;
+  h->has_objects = t.has_objects;
+  h->d.uni_len = t.uni_len;
+  h->d.uni_wid = t.uni_wid;
   if (!h->h_scen) h->h_scen = new std::vector<pgd_scenario>();
   h->h_scen->assign(scen, scen + n_scen);
   if ((rc = build_scen_map(h))) return rc;
   h->have_scen = true;
-  h->img_dirty = true;
-  HIPCHK(hipMemsetAsync(h->d.imask, 0, sizeof(unsigned long long) * (size_t)h->d.N, h->stream));
-  hipLaunchKernelGGL(k_clear_hints, dim3((h->d.N + 255) / 256), dim3(256), 0, h->stream, h->d.ei, h->d.N);
-  HIPCHK(hipGetLastError());
-  return build_reset_image(h);
+  return tables_changed(h);
 }
 
 int pgd_reset(pgd_handle h, const int32_t* env_ids, const int32_t* scen_ids, int n, float* d_obs) {
@@ -944,29 +815,20 @@ int pgd_step_packed(pgd_handle h, const float* d_actions, float* d_rows, int row
 
 /* ---- env groups: asynchronous vector-env groups inside one handle ---------------------------------------------------- */
 int pgd_set_groups(pgd_handle h, int n_groups) {
-  if (!h || n_groups < 1 || n_groups > 64) return PGD_ERR_ARG;
-  if (h->d.N % n_groups != 0) return PGD_ERR_ARG;  // equal groups
-  int pack = h->d.pack_obs, sub = h->d.sub, epw = h->d.epw;
-  if ((h->d.N / n_groups) % epw != 0) {
-    // groups are launched as whole waves.  Throughput mode (pgd_create picks it from 32768 envs on: three envs of 17 slots per
-    // wave) does not divide a power-of-two group size: such an engine goes back to one env per wave -- the record, image and
-    // mask layouts do not depend on the lane mapping, so the switch is a change of launch geometry only.  The new geometry is
-    // worked out in locals and committed only when every check has passed (a refused call leaves the engine as it was), and the
-    // switch is reported: pgd_describe_step says so from then on (by the r03 sweep it costs 6 - 18 % at 32768 envs)
-    if (!pack) return PGD_ERR_ARG;
-    pack = 0;
-    sub = WAVE / h->d.V < 16 ? WAVE / h->d.V : 16;
-    epw = WAVE / (h->d.V * sub);
-    if ((h->d.N / n_groups) % epw != 0) return PGD_ERR_ARG;
-  }
-  if (pack != h->d.pack_obs) h->left_pack_mode = true;
-  h->d.pack_obs = pack; h->d.sub = sub; h->d.epw = epw;
-  const int use_imask = h->sw.imask >= 0 ? h->sw.imask : (pack ? 1 : 0);
+  if (!h) return PGD_ERR_ARG;
+  // the new geometry is worked out first and committed only when every check has passed (a refused call leaves the engine as it
+  // was); leaving throughput mode is reported: pgd_describe_step says so from then on
+  const Geometry now{h->d.V, h->d.D, h->d.NV, h->d.sstride, h->d.sub, h->d.epw, h->d.pack_obs, h->d.use_imask};
+  Geometry geo;
+  bool left_pack;
+  { int rc = regroup_geometry(now, h->d.N, n_groups, h->sw.imask, geo, &left_pack); if (rc) return rc; }
+  if (left_pack) h->left_pack_mode = true;
+  h->d.pack_obs = geo.pack_obs; h->d.sub = geo.sub; h->d.epw = geo.epw;
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  if (use_imask != h->d.use_imask) {  // (the masks are only kept up while they are read: none is trusted across the switch)
+  if (geo.use_imask != h->d.use_imask) {  // (the masks are only kept up while they are read: none is trusted across the switch)
     HIPCHK(hipMemsetAsync(h->d.imask, 0, sizeof(unsigned long long) * (size_t)h->d.N, h->stream));
-    h->d.use_imask = use_imask;
+    h->d.use_imask = geo.use_imask;
   }
   if (h->gstreams) {
     for (int g = 0; g < h->n_groups; ++g) { (void)hipStreamSynchronize(h->gstreams[g]); (void)hipStreamDestroy(h->gstreams[g]); }
@@ -1236,88 +1098,38 @@ int pgd_state_dims(pgd_handle h, int* nf, int* ni, int* nei) {
   if (nei) *nei = PGD_NEI;
   return PGD_OK;
 }
-}  // extern "C" (state conversion helpers are C++ templates)
 
 // ABI order is field-major ([field][env*V + slot], [field][env]); the device keeps one 128 B record per vehicle and one
-// PGD_NEI-int row per env — converted on the host
-// host copies of the record array: record k = (env k / V, slot k % V) out of / into the piece planes of its env's block (RecPiece)
-static void record_from_planes(const RecPiece* raw, int V, size_t k, VehRec& t) {
-  const RecPiece* blk = raw + (k / (size_t)V) * (size_t)(8 * V);
-  for (int p = 0; p < 8; ++p) memcpy(reinterpret_cast<char*>(&t) + 16 * p, blk + (size_t)p * V + k % (size_t)V, 16);
-}
-static void record_to_planes(RecPiece* raw, int V, size_t k, const VehRec& t) {
-  RecPiece* blk = raw + (k / (size_t)V) * (size_t)(8 * V);
-  for (int p = 0; p < 8; ++p) memcpy(blk + (size_t)p * V + k % (size_t)V, reinterpret_cast<const char*>(&t) + 16 * p, 16);
-}
-extern "C" int pgd_get_state(pgd_handle h, float* f, int32_t* i, int32_t* ei) {
+// PGD_NEI-int row per env -- converted on the host (state_to_fields / state_from_fields, pgd_host_prep.h)
+static_assert(sizeof(RecUnit) == sizeof(RecPiece), "the host copy of the records is the device's piece planes");
+int pgd_get_state(pgd_handle h, float* f, int32_t* i, int32_t* ei) {
   if (!h || !f || !i || !ei) return PGD_ERR_ARG;
   const size_t nv = (size_t)h->d.NV;
-  const int N = h->d.N;
   HIPCHK(hipSetDevice(h->device));
-  std::vector<RecPiece> tr(nv * 8);
-  std::vector<int32_t> te((size_t)N * PGD_NEI);
+  std::vector<RecUnit> tr(nv * 8);
+  std::vector<int32_t> te((size_t)h->d.N * PGD_NEI);
   HIPCHK(hipMemcpyAsync(tr.data(), h->d.rec, sizeof(VehRec) * nv, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(te.data(), h->d.ei, sizeof(int32_t) * te.size(), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  for (size_t k = 0; k < nv; ++k) {  // device record -> ABI fields (struct Veh in pgd_device.h)
-    VehRec t;
-    record_from_planes(tr.data(), h->d.V, k, t);
-    const float fv[PGD_NF] = {t.x, t.y, t.th, t.v, t.steer, t.a1t /* SF_THROTTLE */, t.lastx, t.lasty, t.lasthx, t.lasthy, t.a0s, t.a0t,
-                              t.a1s, t.a1t, t.php, t.phi, t.plp, t.pli, t.target, t.energy, t.dl, t.dr, t.eprew, t.agent_id, t.hx, t.hy};
-    const int32_t iv[PGD_NI] = {(int32_t)t.status, (int32_t)t.lane, (int32_t)t.ck0, (int32_t)t.ck1, (int32_t)t.rlane, (int32_t)t.timer,
-                                (int32_t)t.vflags, (int32_t)t.spawn};
-    for (int q = 0; q < PGD_NF; ++q) f[(size_t)q * nv + k] = fv[q];
-    for (int q = 0; q < PGD_NI; ++q) i[(size_t)q * nv + k] = iv[q];
-  }
-  for (int e = 0; e < N; ++e)
-    for (int q = 0; q < PGD_NEI; ++q) ei[(size_t)q * N + e] = q == EI_NEAR ? 0 : te[(size_t)e * PGD_NEI + q];
+  state_to_fields(tr.data(), te.data(), h->d.N, h->d.V, f, i, ei);
   return PGD_OK;
 }
-extern "C" int pgd_set_state(pgd_handle h, const float* f, const int32_t* i, const int32_t* ei) {
+int pgd_set_state(pgd_handle h, const float* f, const int32_t* i, const int32_t* ei) {
   if (!h || !f || !i || !ei) return PGD_ERR_ARG;
   const size_t nv = (size_t)h->d.NV;
-  const int N = h->d.N;
-  std::vector<RecPiece> tr(nv * 8);
-  std::vector<int32_t> te((size_t)N * PGD_NEI);
-  for (size_t k = 0; k < nv; ++k) {  // ABI fields -> device record; the derived part is rebuilt on the device (k_derive)
-    VehRec t;
-    memset(&t, 0, sizeof(t));
-    auto F = [&](int q) { return f[(size_t)q * nv + k]; };
-    auto I = [&](int q) { return i[(size_t)q * nv + k]; };
-    t.x = F(SF_X); t.y = F(SF_Y); t.th = F(SF_THETA); t.v = F(SF_SPEED); t.steer = F(SF_STEER);
-    t.lastx = F(SF_LASTX); t.lasty = F(SF_LASTY); t.lasthx = F(SF_LASTHX); t.lasthy = F(SF_LASTHY);
-    t.a0s = F(SF_ACT0S); t.a0t = F(SF_ACT0T); t.a1s = F(SF_ACT1S); t.a1t = F(SF_ACT1T);
-    t.php = F(SF_PID_HP); t.phi = F(SF_PID_HI); t.plp = F(SF_PID_LP); t.pli = F(SF_PID_LI);
-    t.target = F(SF_TARGET_SPEED); t.energy = F(SF_ENERGY); t.dl = F(SF_DIST_LEFT); t.dr = F(SF_DIST_RIGHT);
-    t.eprew = F(SF_EP_REWARD); t.agent_id = F(SF_AGENT_ID);
-    {  // the carried heading vector is taken from the checkpoint only while it agrees with THETA (a caller that edits THETA,
-       // or builds a state by hand, gets cos / sin of it)
-      const double c = cos((double)t.th), sn = sin((double)t.th);
-      t.hx = F(SF_HX); t.hy = F(SF_HY);
-      if (!(fabs((double)t.hx - c) <= 1e-4 && fabs((double)t.hy - sn) <= 1e-4)) { t.hx = (float)c; t.hy = (float)sn; }
-    }
-    const int32_t lane = I(SI_LANE), spawn = I(SI_SPAWN), rlane = I(SI_RLANE), timer = I(SI_TIMER), vflags = I(SI_VFLAGS),
-                  status = I(SI_STATUS), ck0 = I(SI_CK0), ck1 = I(SI_CK1);
-    if (lane < 0 || lane > 0xffff || spawn < 0 || spawn > 0xffff || rlane < -1 || rlane > 0x7fff || timer < 0 || status < 0 ||
-        status > 15 || ck0 < 0 || ck0 >= PGD_MAX_CKPT || ck1 < 0 || ck1 >= PGD_MAX_CKPT || (vflags & ~0xffff))
-      return PGD_ERR_ARG;
-    t.lane = (uint32_t)lane; t.spawn = (uint32_t)spawn; t.rlane = rlane; t.timer = (uint32_t)std::min(timer, 0xffff);
-    t.vflags = (uint32_t)vflags; t.status = (uint32_t)status; t.ck0 = (uint32_t)ck0; t.ck1 = (uint32_t)ck1;
-    record_to_planes(tr.data(), h->d.V, k, t);
-  }
-  for (int e = 0; e < N; ++e)
-    for (int q = 0; q < PGD_NEI; ++q) te[(size_t)e * PGD_NEI + q] = q == EI_NEAR ? 1 : ei[(size_t)q * N + e];
+  std::vector<RecUnit> tr(nv * 8);
+  std::vector<int32_t> te((size_t)h->d.N * PGD_NEI);
+  { int rc = state_from_fields(f, i, ei, h->d.N, h->d.V, tr.data(), te.data()); if (rc) return rc; }
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipMemcpyAsync(h->d.rec, tr.data(), sizeof(VehRec) * nv, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->d.ei, te.data(), sizeof(int32_t) * te.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(h->d.imask, 0, sizeof(unsigned long long) * (size_t)N, h->stream));  // arbitrary records: none is the image
+  HIPCHK(hipMemsetAsync(h->d.imask, 0, sizeof(unsigned long long) * (size_t)h->d.N, h->stream));  // arbitrary records: none is the image
   h->derive_pending = true;
   { int rc = derive_records(h); if (rc) return rc; }
   HIPCHK(hipStreamSynchronize(h->stream));
   return PGD_OK;
 }
 
-extern "C" {
 int pgd_enable_step_timing(pgd_handle h, int on) {
   if (!h) return PGD_ERR_ARG;
   h->step_timing = on != 0;
@@ -1431,36 +1243,7 @@ int pgd_sync(pgd_handle h) {
 
 int pgd_destroy(pgd_handle h) {
   if (!h) return PGD_ERR_ARG;
-  (void)hipStreamSynchronize(h->stream);
-  if (h->jit_mod) { (void)hipModuleUnload(h->jit_mod); h->jit_mod = nullptr; h->jit_fn = nullptr; }
-  void* bufs[] = {h->cmp_live, h->cmp_index, h->lk_act, h->rowz, h->d.rec, h->d.ei, h->d.imask, h->d.env_map, h->d_ids, h->arena};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  (void)hipEventDestroy(h->ev0);
-  (void)hipEventDestroy(h->ev1);
-  (void)hipEventDestroy(h->ev_move);
-  (void)hipEventDestroy(h->ev_ids);
-  if (h->h_ids) (void)hipHostFree(h->h_ids);
-  if (h->prof_ev) {
-    for (hipEvent_t ev : *h->prof_ev) (void)hipEventDestroy(ev);
-    delete h->prof_ev;
-  }
-  if (h->gstreams) {
-    for (int g = 0; g < h->n_groups; ++g) { (void)hipStreamSynchronize(h->gstreams[g]); (void)hipStreamDestroy(h->gstreams[g]); }
-    free(h->gstreams);
-  }
-  if (h->cmp_retired) {
-    for (uint32_t* b : *h->cmp_retired) (void)hipFree(b);
-    delete h->cmp_retired;
-  }
-  topdown_free(h);
-  render_free(h);
-  step_info_free(h);
-  delete h->h_maps;
-  delete h->h_scen;
-  if (h->own_stream) (void)hipStreamDestroy(h->stream);
-  if (h->retired) (void)hipStreamDestroy(h->retired);
-  free(h);
+  engine_free(h);
   return PGD_OK;
 }
 

@@ -122,7 +122,7 @@ DEV void route_refresh(const MapView& mv, const Tab<pgd_spawn>& sp, Veh& r) {
 // checkpoints[ck1:].index(start_node) with index < len - 1 (navigation.py:270-277) -- then needs neither the route length nor the
 // lane -> road table chain in front of its reads: one memory round trip on every step of the first five metres of a lane where
 // rounds 1 - 5 made three dependent ones (lane record, road record, route; PGD_CKPT_CHAIN keeps that form for A/B).
-#define PGD_CKPT_END (-32768)
+// (PGD_CKPT_END: pgd_records.h)
 DEV void update_checkpoints(const MapView& mv, const Grp& g, const Tab<pgd_spawn>& sp, Veh& r, float lon, const int start_node) {
   if (r.ck0 == r.ck1) return;
   if (!(lon < 5.0f)) return;

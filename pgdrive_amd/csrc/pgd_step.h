@@ -13,8 +13,7 @@
 //              localisation, line / sidewalk test, reward, done, auto-reset AND the observation row (state + navigation +
 //              neighbours + lidar fan) run in this one launch; the stand-alone k_observe serves pgd_reset / pgd_observe,
 //              engines with several envs per wave and the multi-agent step.
-#define WAVE 64
-#define MAXV 64
+// (WAVE, MAXV, FUSE_MAX_AGENTS: pgd_records.h)
 
 // Optional per-phase cycle counters of k_step (build with -DPGD_PROF; never enabled in the shipped library)
 #ifndef PGD_MA_PRIO3
@@ -87,8 +86,6 @@ DEV LaneMap lane_map(const PgdDev& d, int unit, int n_units) {
   return m;
 }
 
-
-#define FUSE_MAX_AGENTS 8
 // first 64 bytes of a spawn record (everything but the route arrays) into a local copy; the copy is only ever read by field, so it
 // lives in registers and the fields nobody reads cost nothing
 template <bool SKIP_POSE> DEV void spawn_head_load(const pgd_spawn* sp, pgd_spawn& out) {

@@ -4,7 +4,7 @@
 #define PGD_VEHICLE_H
 
 // ---------------------------------------------------------------------------------------------------------------------
-// per-lane vehicle registers: struct Veh (pgd_device.h) is the record itself
+// per-lane vehicle registers: struct Veh (pgd_records.h) is the record itself
 // ---------------------------------------------------------------------------------------------------------------------
 // records in memory: blocks of n records as eight planes of n pieces (RecPiece, pgd_device.h)
 DEV const RecPiece* rec_block(const RecPiece* base, size_t block, int n) { return base + block * (size_t)(8 * n); }
@@ -99,10 +99,7 @@ DEV Obb snap_obb(const Snap& S, int k) { return Obb{S.x[k], S.y[k], S.ux[k], S.u
 // raised inside each doPhysics call (engine_core.py:276-278, collision_callback.py:7-36).  Lives in the same LDS bytes as
 // ObsLds (union ObsScratch, pgd_observe.h): the contact test is over before the observation scratch is first written.
 #define PGD_MAX_SUB 5
-#ifndef PGD_SUBV
-#define PGD_SUBV 52  // slots of a wave with sub-step poses (the largest shipped env: 40 agents + 8 toll booths; three packed
-                     // envs of 17 slots); waves with more slots test contacts at the end pose only
-#endif
+// (PGD_SUBV, the slots of a wave with sub-step poses: pgd_records.h)
 struct SubPose {
   float4 p[PGD_MAX_SUB - 1][PGD_SUBV];  // (x, y, unit vector of the MOTION direction) of the slot after sub-step k + 1
   float2 beta[PGD_SUBV];                // (cos, sin) of the slip angle: heading = motion direction rotated back by it
